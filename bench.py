@@ -2,7 +2,14 @@
 """Headline benchmark: Gibbs sweeps/sec (all chains) for BOOM's spike-and-slab
 sampler at BASELINE.json config 2 -- n=1e4, p=512, 1024 chains per MI355X, fp64.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.
+--full adds everything else the line can carry, each measured by runs of its own
+after the timed steps: the same steps kept apart, ESS/s, sweeps/s against chains
+per GPU, the callers' one-draw loop, the other BASELINE configurations, the
+roofline and the CPU baseline.  --dump-outputs DIR writes what the timed steps
+computed as .npy files (dump_outputs).
 
 With --gpus N > 1 and no torch.distributed environment the script starts its own
 N ranks (python -m torch.distributed.run ... bench.py) before anything touches a
@@ -39,6 +46,8 @@ ESS_SWEEPS = 1000
 DATA_SEED = 8675309
 SAMPLER_SEED = 8675309
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_BYTES = 63_000_000  # --dump-outputs: payload of all files together (64 MB with the .npy headers)
+DUMP_SEED = 20240917     # ... and the fixed sample of chains taken where all of them would not fit
 
 
 def geyer_ess(x):
@@ -197,6 +206,29 @@ def _rebase(old, tag, prefix, rate, unit, waves_per_chain):
     if "note" in old:
         new["note"] = old["note"] + "; frac = executed instructions at the guide's 4-cycle issue cost over the wavefronts' measured lifetime"
     return new
+
+
+def dump_outputs(path, eng, blocks, p):
+    """--dump-outputs: what the timed steps computed, as a caller of the path receives it --
+    every chain's state after the last timed step (gamma as 0 / 1, beta, sigma^2; rank 0's
+    chains) and the job's posterior summaries over the timed steps (boom_amd.dist.aggregate
+    of the gathered blocks) -- one float32 / float64 .npy file each.  Where the states of all
+    chains would not fit in DUMP_BYTES, a fixed sample of chains (DUMP_SEED) is written;
+    chain.npy holds the indices of the chains written."""
+    from boom_amd import dist as bd
+    gam, beta, sig = eng.get_states()
+    agg = bd.aggregate(blocks, p)
+    arrays = {k: np.asarray(agg[k], np.float64) for k in ("inclusion_prob", "beta_mean", "beta_second_moment")}
+    per_chain = p * (4 + 8) + 8 + 8
+    room = (DUMP_BYTES - sum(a.nbytes for a in arrays.values())) // per_chain
+    chain = np.arange(len(sig))
+    if len(chain) > room:
+        chain = np.sort(np.random.default_rng(DUMP_SEED).choice(len(chain), room, replace=False))
+    arrays.update(chain=chain.astype(np.float64), gamma=gam[chain].astype(np.float32),
+                  beta=beta[chain], sigsq=sig[chain])
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _per_launch(times):
@@ -848,6 +880,8 @@ def run_config3(args, boom_amd, torch, dist, rank, local_rank, world):
                      suf_block=(block.cpu().numpy() if block is not None else np.zeros(0)))
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, allb, p)
     sc = allb[:, 3 * p:]
     total = float(sc[:, 0].sum())
     kbar = float(sc[:, 3].sum() / total)
@@ -913,6 +947,8 @@ def run_config4(args, boom_amd, torch, dist, rank, local_rank, world):
         np.savez(args.dump_blocks, blocks=allb)
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, allb, p)
     total = float(world * C * R * args.steps)
     counted = float(allb[:, 3 * p].sum())
     incl = allb[:, :p].sum(axis=0) / max(counted, 1.0)
@@ -970,12 +1006,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="(configs[1]) after the headline, also measure every extra key of the line: the same "
+                         "steps kept apart, ESS/s, the diagnostics, the other configurations, the roofline and "
+                         "the CPU baseline (minutes)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed steps computed to DIR/<name>.npy (chain states after the last "
+                         "step, posterior summaries over the timed steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) no CPU baseline")
     ap.add_argument("--keep-apart", action="store_true",
                     help="(profiling) join the engine's two streams after every launch of the timed region: "
                          "hardware counters of overlapping dispatches cannot be told apart")
     ap.add_argument("--no-curve", action="store_true",
-                    help="skip the sweeps/s-vs-chains diagnostic (extra key, untimed)")
+                    help="(with --full) skip the diagnostics and the other configurations (extra keys, untimed)")
     ap.add_argument("--config", type=int, default=1, choices=(1, 3, 4),
                     help="1 (default): BASELINE configs[1], the headline; 3: configs[3], n=1e5 p=4096, "
                          "1024 chains per GPU, the design matrix row-sharded over the ranks and ONE "
@@ -1081,7 +1124,8 @@ def main():
     # launches apart): roofline.kernel_ms is the average of those per-launch durations -- what
     # rocprofv3 --kernel-trace reports per dispatch; overlapping durations add up to more than
     # the wall time, which is the point.  The same steps kept apart (round 3's headline mode)
-    # are measured right after as `separate_launches`.
+    # are measured right after as `separate_launches`.  (The event pairs are recorded in a
+    # plain run too, so that its timed steps are the same as --full's.)
     for _ in range(args.warmup):
         eng.sweep(SWEEPS_PER_STEP, sync=False)
         if args.keep_apart:
@@ -1134,6 +1178,51 @@ def main():
     kbar = float(sc[:, 3].sum() / total_sweeps)
     incl = allb[:, :P].sum(axis=0) / total_sweeps
     value = total_sweeps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, allb, P)
+
+    # decision safety of the timed sweeps themselves: smallest |log u - delta|
+    # any chain saw (a flip decision could differ from the reference's only below
+    # the ~1e-12 rounding difference), and the chains' status words (ba_sync
+    # returned OK for every rank or we would not be here)
+    decisions = {"min_margin": float(sc[:, 6].min()),
+                 "accepted_flips": float(sc[:, 4].sum()),
+                 "proposed_flips": float(sc[:, 5].sum()),
+                 "chains_in_error": 0, "worst_chain_status": "CHAIN_OK"}
+    out = {
+        "metric": "Gibbs sweeps/sec (all chains), n=1e4 p=512 spike-slab",
+        "value": round(value, 1),
+        "unit": "sweeps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": "BregVsSampler spike-and-slab n=1e4 p=512, "
+                               "1024 chains per GPU, fp64 (BASELINE configs[1])",
+                   "chains_per_gpu": CHAINS_PER_GPU,
+                   "sweeps_per_step": SWEEPS_PER_STEP,
+                   "true_signals": N_SIGNAL, "mean_model_size": round(kbar, 2),
+                   "burn_in": BURN_IN, "parallelism": "chains sharded, %d GPU(s)" % world,
+                   "launches": "consecutive ba_sweep calls overlap (chain hand-over between launches): the "
+                               "engine's default",
+                   "suf_build": ("rows sharded, local MFMA syrk, one all-reduce" if world > 1
+                                 else "single device MFMA syrk")},
+        "decisions": decisions,
+        "suf_build_ms": round(suf_build_s * 1e3, 2),
+        "collectives": coll,
+        "signal_inclusion_min": round(float(incl[:N_SIGNAL].min()), 4),
+        "null_inclusion_max": round(float(incl[N_SIGNAL:].max()), 4),
+    }
+    if not args.full:
+        print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- the same steps kept apart (extra key; round 3's headline mode): ba_stream() between
     # the calls joins the engine's two streams, so every launch starts when the previous one
@@ -1152,15 +1241,6 @@ def main():
     torch.cuda.synchronize()
     sep_elapsed = time.perf_counter() - t0
     sep_kernel_ms = ev0.elapsed_time(ev1) / max(1, args.steps)
-
-    # decision safety of the timed sweeps themselves: smallest |log u - delta|
-    # any chain saw (a flip decision could differ from the reference's only below
-    # the ~1e-12 rounding difference), and the chains' status words (ba_sync
-    # returned OK for every rank or we would not be here)
-    decisions = {"min_margin": float(sc[:, 6].min()),
-                 "accepted_flips": float(sc[:, 4].sum()),
-                 "proposed_flips": float(sc[:, 5].sum()),
-                 "chains_in_error": 0, "worst_chain_status": "CHAIN_OK"}
 
     # ESS/s: an extra, untimed run of ESS_SWEEPS recorded sweeps on rank 0:
     # sigma^2, |gamma|, log posterior and the five largest-|beta| coefficients
@@ -1358,33 +1438,10 @@ def main():
                                     "file -- git-ignored, not gpurun-ignored -- and is loaded there by the "
                                     "tests only: reference-side binding, goldens; it is not timed there)"}
 
-    out = {
-        "metric": "Gibbs sweeps/sec (all chains), n=1e4 p=512 spike-slab",
-        "value": round(value, 1),
-        "unit": "sweeps/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": "BregVsSampler spike-and-slab n=1e4 p=512, "
-                               "1024 chains per GPU, fp64 (BASELINE configs[1])",
-                   "chains_per_gpu": CHAINS_PER_GPU,
-                   "sweeps_per_step": SWEEPS_PER_STEP,
-                   "true_signals": N_SIGNAL, "mean_model_size": round(kbar, 2),
-                   "burn_in": BURN_IN, "parallelism": "chains sharded, %d GPU(s)" % world,
-                   "launches": "consecutive ba_sweep calls overlap (chain hand-over between launches): the "
-                               "engine's default",
-                   "suf_build": ("rows sharded, local MFMA syrk, one all-reduce" if world > 1
-                                 else "single device MFMA syrk")},
+    out.update({
         "ess_per_sec": round(ess_per_sec, 1),
         "ess_fraction": round(ess_frac, 4),
         "ess_traces": {k: round(v / (CHAINS_PER_GPU * trace_len), 4) for k, v in ess.items()},
-        "decisions": decisions,
         "sweeps_per_sec_vs_chains_per_gpu": curve,
         "drop_in_loop_sweeps_per_sec": loop,
         "overlapped_launches_sweeps_per_sec": overlapped,
@@ -1394,13 +1451,9 @@ def main():
                               "what": "the same K steps with ba_stream() between the calls: one launch at a "
                                       "time, each as long as its slowest chain (round 3's headline mode)"},
         "other_configs": other,
-        "suf_build_ms": round(suf_build_s * 1e3, 2),
-        "collectives": coll,
-        "signal_inclusion_min": round(float(incl[:N_SIGNAL].min()), 4),
-        "null_inclusion_max": round(float(incl[N_SIGNAL:].max()), 4),
         "roofline": roofline,
         "cpu_baseline": cpu,
-    }
+    })
     print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

@@ -8,7 +8,7 @@ set -u
 TAG=${1:-r02}
 shift || true
 SCRIPT=${PROFILE_SCRIPT:-bench.py}
-ARGS=${@:---no-cpu-baseline --no-curve}
+ARGS=${@:---full --no-cpu-baseline --no-curve}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT

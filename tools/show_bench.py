@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One line per configuration of a bench.py JSON line: rate, roofline fraction, CPU baseline."""
+"""One line per configuration of a `bench.py --full` JSON line: rate, roofline fraction, CPU baseline."""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print("headline: %s = %.4g %s, %.3f ms per step, roofline frac %.3f, cpu %s" % (
