@@ -127,6 +127,15 @@ SIGNATURES = {
     "ba_poisson_set_mixtures": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64),
                                           C.POINTER(C.c_int32), _dp, _dp, _dp, C.c_int64]),
     "ba_poisson_sweep": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ba_student_set_data": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp]),
+    "ba_student_set_nu_prior": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double]),
+    "ba_student_set_nu": (C.c_int, [C.c_void_p, C.c_int64, C.c_double]),
+    "ba_student_get_nu": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
+    "ba_student_sweep": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ba_student_get_weights": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
+    "ba_student_get_nu_draws": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp]),
+    "ba_student_get_margin": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
+    "ba_student_allow_model_selection": (C.c_int, [C.c_void_p, C.c_int32]),
     "ba_ss_set_structural": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [_dp] * 6),
     "ba_ss_get_structural": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp]),
     "ba_ss_add_ar": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double,
@@ -506,6 +515,52 @@ class Engine:
         self._check(self.lib.ba_poisson_sweep(self._h, nsweeps))
         if sync:
             self.sync()
+
+    # ---- TRegressionSpikeSlabSampler ---------------------------------------------
+    def student_set_data(self, X, y):
+        X = np.asfortranarray(X, dtype=np.float64)
+        self.p = X.shape[1]
+        self.n = X.shape[0]
+        self._check(self.lib.ba_student_set_data(self._h, X.shape[0], X.shape[1], _p(X), _p(_f64(y))))
+
+    def set_sigma_prior(self, prior_df, sigma_guess, sigma_upper_limit=float("inf")):
+        self._check(self.lib.ba_set_sigma_prior(self._h, float(prior_df), float(sigma_guess),
+                                                float(sigma_upper_limit)))
+
+    def student_set_nu_prior(self, kind, a, b):
+        """kind 0: Uniform(a, b); kind 1: Gamma(a, b) (shape, rate)"""
+        self._check(self.lib.ba_student_set_nu_prior(self._h, int(kind), float(a), float(b)))
+
+    def student_set_nu(self, nu, chain=-1):
+        self._check(self.lib.ba_student_set_nu(self._h, int(chain), float(nu)))
+
+    def student_get_nu(self, chain=-1):
+        out = np.zeros(self.chains if chain < 0 else 1)
+        self._check(self.lib.ba_student_get_nu(self._h, int(chain), _p(out)))
+        return out if chain < 0 else float(out[0])
+
+    def student_get_margin(self, chain=-1):
+        out = np.zeros(self.chains if chain < 0 else 1)
+        self._check(self.lib.ba_student_get_margin(self._h, int(chain), _p(out)))
+        return out if chain < 0 else float(out[0])
+
+    def student_allow_model_selection(self, allow=True):
+        self._check(self.lib.ba_student_allow_model_selection(self._h, int(bool(allow))))
+
+    def student_sweep(self, nsweeps=1, sync=True):
+        self._check(self.lib.ba_student_sweep(self._h, nsweeps))
+        if sync:
+            self.sync()
+
+    def student_get_weights(self, chain):
+        out = np.zeros(self.n)
+        self._check(self.lib.ba_student_get_weights(self._h, int(chain), _p(out)))
+        return out
+
+    def student_get_nu_draws(self, chain, nsweeps):
+        out = np.zeros(int(nsweeps))
+        self._check(self.lib.ba_student_get_nu_draws(self._h, int(chain), int(nsweeps), _p(out)))
+        return out
 
     def logit_set_imputer(self, kind):
         """0: the reference's auxiliary mixture (default); 1: Polya-Gamma"""

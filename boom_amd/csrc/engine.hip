@@ -19,6 +19,7 @@
 #include "ktimer.h"
 #include "probit_params.h"
 #include "ssvs_params.h"
+#include "student_params.h"
 
 namespace boom_amd {
 // ssvs_kernel.hip
@@ -44,6 +45,9 @@ hipError_t launch_ssm_simsmooth(hipStream_t stream, const SsParams &P, int draw_
 hipError_t launch_ssm_forecast(hipStream_t stream, const SsParams &P, int horizon, const double *newX,
                                uint64_t *pos_forecast, double *out);
 hipError_t launch_probit_impute(hipStream_t stream, const ProbitParams &P, double *planes);
+hipError_t launch_student_impute(hipStream_t stream, const StudentParams &P, const double *Xsq,
+                                 const double *slab_precision, double *xtz, double *v_diag, double *planes);
+hipError_t launch_student_sigma_nu(hipStream_t stream, const StudentParams &P);
 hipError_t launch_logit_impute(hipStream_t stream, const ProbitParams &P, const double *Xsq,
                                const double *slab_precision, double *v_diag, double *planes,
                                int polya_gamma);
@@ -134,6 +138,10 @@ const char *status_message(int st) {
       return "A chain's model size exceeded the engine's working capacity "
              "(a pinned max_model_size_hint, or more than 1024 variables in "
              "the model).";
+    case STUDENT_SLICE_ERROR:
+      return "The slice sampler of nu failed in ScalarSliceSampler (an infinite "
+             "log density at the current value, an infinite upper limit, more than "
+             "100 doublings or more than 100 contractions).";
     default:
       return "unknown chain status";
   }
@@ -147,6 +155,7 @@ int status_code(int st) {
     case CHAIN_RNG_BRANCH: return BA_E_RNG_BRANCH;
     case CHAIN_FORECAST_VARIANCE: return BA_E_FORECAST_VARIANCE;
     case CHAIN_MODEL_TOO_LARGE: return BA_E_MODEL_TOO_LARGE;
+    case STUDENT_SLICE_ERROR: return BA_E_RNG_BRANCH;
     default: return BA_E_INVALID;
   }
 }
@@ -370,6 +379,15 @@ struct ba_engine {
   DevBuf<int32_t> dpois_off, dpois_obs;
   DevBuf<double> dpois_mu, dpois_sigma, dpois_logw;
   int poisson_mix_one = -1;
+  // TRegressionSpikeSlabSampler (student_kernel.hip): the logit path's machinery (logit_mode
+  // is set with it) with its own imputation, sigma^2 per chain and the nu draw; per chain nu,
+  // the slice sampler's suggested_dx, the smallest slice margin, the recorded nu path; the
+  // u_i = (r_i / sigma)^2 of the last draw (chains x n)
+  bool student_mode = false;
+  bool student_allow_selection = true;   // (ba_student_allow_model_selection)
+  int student_nu_kind = STUDENT_NU_UNIFORM;
+  double student_nu_a = 0.1, student_nu_b = 100.0;
+  DevBuf<double> dstu_nu, dstu_dx, dstu_margin, dstu_u, dstu_nu_rec;
   int slot_limit = 0;              // (ba_set_slot_limit)
   DevBuf<double> dlogit_w, dlogit_V;
   // ... V built a vector at a time (xtwx_cols_kernel.hip): the squared design matrix
@@ -723,10 +741,12 @@ void fill_params(ba_engine *e, SsvsParams &P) {
     P.cm_start = nullptr;
     P.max_flips = (e->sss_max_flips > 0) ? std::min(e->sss_max_flips, e->p) : e->p;
   }
+  if (e->cur_mode == 1 && e->student_mode && !e->student_allow_selection)
+    P.max_flips = 0;   // SpikeSlabSampler::allow_model_selection(false): no indicator draws
   if (e->cur_mode == 1 && e->logit_mode && e->dlogit_V.count) {
     // BinomialLogitSpikeSlabSampler: the sampler's own shuffle, every chain's own V
     // (which moves with the latent data: factors and tables are rebuilt)
-    P.mode = e->poisson_mode ? 1 : 2;   // (the Poisson sampler drives the plain SpikeSlabSampler)
+    P.mode = (e->poisson_mode || e->student_mode) ? 1 : 2;   // (the Poisson and Student samplers drive the plain SpikeSlabSampler)
     P.V = e->dlogit_V.ptr;
     P.v_chain_stride = (int64_t)e->p * e->p;
     P.model_keep = 0;
@@ -1952,7 +1972,7 @@ const char *ba_kernel_class_name(int32_t cls) {
       "ssm_simsmooth_kernel", "atb_mfma_kernel", "probit_impute_kernel", "logit_impute_kernel",
       "xtwx_cols_kernel<false>+plain_reduce_kernel", "xtwx_cols_kernel<true>+xtwx_cols_reduce_kernel",
       "xtx_mfma_kernel+plane_sum_kernel+col_reduce_kernel", "poisson_impute_kernel",
-      "kalman_prepare_kernel", "ss_round_kernel"};
+      "kalman_prepare_kernel", "ss_round_kernel", "student_impute_kernel", "student_sigma_nu_kernel"};
   return (cls >= 0 && cls < KT_CLASSES) ? names[cls] : "";
 }
 
@@ -2007,7 +2027,7 @@ int ba_upload_regression_suf(ba_engine *e, int32_t p, const double *xtx,
   e->sumy = ybar * n;
   e->have_suf = true;
   e->device_dirty = true;
-  e->probit_mode = e->logit_mode = e->ss_mode = e->poisson_mode = false;   // (plain regression data now; the binomial, Poisson and state-space setters say otherwise after this)
+  e->probit_mode = e->logit_mode = e->ss_mode = e->poisson_mode = e->student_mode = false;   // (plain regression data now; the binomial, Poisson and state-space setters say otherwise after this)
   return BA_OK;
 }
 
@@ -2044,7 +2064,7 @@ int ba_build_suf_from_xy_device(ba_engine *e, int64_t n, int32_t p,
   e->n = (double)n;
   e->have_suf = true;
   e->device_dirty = true;
-  e->probit_mode = e->logit_mode = e->ss_mode = e->poisson_mode = false;   // (plain regression data now; the binomial, Poisson and state-space setters say otherwise after this)
+  e->probit_mode = e->logit_mode = e->ss_mode = e->poisson_mode = e->student_mode = false;   // (plain regression data now; the binomial, Poisson and state-space setters say otherwise after this)
   return BA_OK;
 }
 
@@ -2090,7 +2110,7 @@ int ba_set_suf_from_block_device(ba_engine *e, int64_t n_total, int32_t p,
   e->n = (double)n_total;
   e->have_suf = true;
   e->device_dirty = true;
-  e->probit_mode = e->logit_mode = e->ss_mode = e->poisson_mode = false;   // (plain regression data now; the binomial, Poisson and state-space setters say otherwise after this)
+  e->probit_mode = e->logit_mode = e->ss_mode = e->poisson_mode = e->student_mode = false;   // (plain regression data now; the binomial, Poisson and state-space setters say otherwise after this)
   return BA_OK;
 }
 
@@ -2287,7 +2307,7 @@ int ba_set_state(ba_engine *e, int64_t chain, const uint8_t *gamma,
   if (!gamma) return fail(BA_E_INVALID, "null argument");
   const int64_t C = e->cfg.chains;
   if (chain < -1 || chain >= C) return fail(BA_E_INVALID, "chain index out of range");
-  if ((e->probit_mode || e->logit_mode) && sigsq != 1.0)
+  if ((e->probit_mode || e->logit_mode) && !e->student_mode && sigsq != 1.0)
     return fail(BA_E_INVALID, "the binomial samplers' latent data have unit variance: sigsq must be 1");
   if (chain < 0) la_discard(e);  // every chain is overwritten: nothing to rewind to
   MUTATE(e);
@@ -2517,6 +2537,7 @@ namespace {
 int sweep_impl(ba_engine *e, int32_t nsweeps, bool record, int la_half) {
   if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
   if (e->ss_mode) return fail(BA_E_STATE, "state-space data are set: use ba_ss_sweep");
+  if (e->student_mode) return fail(BA_E_STATE, "Student-t regression data are set: use ba_student_sweep");
   if (e->logit_mode || e->probit_mode)
     return fail(BA_E_STATE, "binomial data are set: use ba_logit_sweep / ba_probit_sweep (the regression sampler has no meaning on latent data)");
   int rc = switch_mode(e, 0, 1.0);
@@ -3064,7 +3085,7 @@ int ba_set_sigsq(ba_engine *e, int64_t chain, double sigsq) {
   ENGINE_PROLOGUE(e);
   MUTATE(e);
   if (!(sigsq > 0)) return fail(BA_E_INVALID, "sigsq must be positive");
-  if ((e->probit_mode || e->logit_mode) && sigsq != 1.0)
+  if ((e->probit_mode || e->logit_mode) && !e->student_mode && sigsq != 1.0)
     return fail(BA_E_INVALID, "the binomial samplers' latent data have unit variance: sigsq must be 1");
   int rc = alloc_chain_state(e);
   if (rc) return rc;
@@ -3101,6 +3122,7 @@ int ba_sss_sweep(ba_engine *e, int32_t nsweeps) {
   MUTATE(e);
   if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
   if (e->ss_mode) return fail(BA_E_STATE, "state-space data are set: use ba_ss_sweep");
+  if (e->student_mode) return fail(BA_E_STATE, "Student-t regression data are set: use ba_student_sweep");
   if (e->logit_mode || e->probit_mode)
     return fail(BA_E_STATE, "binomial data are set: use ba_logit_sweep / ba_probit_sweep (a sweep without the imputation is not a draw of those samplers)");
   if (!e->have_slab) return fail(BA_E_STATE, "call ba_sss_set_slab first");
@@ -3171,6 +3193,7 @@ int ba_probit_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, cons
   HIP_TRY(hipMemcpy(e->dprob_nt.ptr, ntrials, (size_t)n * 8, hipMemcpyHostToDevice));
   e->probit_mode = true;
   e->logit_mode = false;
+  e->student_mode = false;
   e->dprob_z.release();
   e->probit_n = n;
   e->probit_clt = clt_threshold;
@@ -3183,6 +3206,7 @@ int ba_probit_sweep(ba_engine *e, int32_t nsweeps) {
   ENGINE_PROLOGUE(e);
   MUTATE(e);
   if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
+  if (e->student_mode) return fail(BA_E_STATE, "Student-t regression data are set: use ba_student_sweep");
   if (!e->probit_mode) return fail(BA_E_STATE, "call ba_probit_set_data first");
   if (!e->have_slab) return fail(BA_E_STATE, "call ba_sss_set_slab first");
   if (e->sss_slab_scales) return fail(BA_E_INVALID, "the probit sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
@@ -3275,6 +3299,7 @@ int ba_logit_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, const
   HIP_TRY(launch_square(e->stream, e->dprob_X.ptr, (size_t)n * p, e->dlogit_Xsq.ptr));
   e->logit_mode = true;
   e->poisson_mode = false;
+  e->student_mode = false;
   e->probit_mode = false;
   e->probit_n = n;
   e->probit_clt = clt_threshold;
@@ -3310,6 +3335,7 @@ int ba_poisson_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, con
   for (int64_t i = 0; i < n; ++i) e->poisson_y[(size_t)i] = (int64_t)std::llround(y[i]);
   e->logit_mode = true;      // (the logit path's buffers and column service)
   e->poisson_mode = true;
+  e->student_mode = false;
   e->poisson_mix_set = false;
   e->probit_mode = false;
   e->probit_n = n;
@@ -3372,7 +3398,171 @@ int ba_poisson_set_mixtures(ba_engine *e, int32_t ncounts, const int64_t *counts
 
 }  // extern "C"
 static int logit_family_sweep(ba_engine *e, int32_t nsweeps);
+
+// the Student sampler's per-chain state: nu = 30 (TRegression.cpp:35-45), suggested_dx = 1
+// (TRegressionSampler.cpp:88-107), no slice comparison seen yet
+static int student_prepare(ba_engine *e) {
+  int rc = alloc_chain_state(e);
+  if (rc) return rc;
+  const size_t C = (size_t)e->cfg.chains;
+  if (e->dstu_nu.count == C) return BA_OK;
+  HIP_TRY(e->dstu_nu.resize(C));
+  HIP_TRY(e->dstu_dx.resize(C));
+  HIP_TRY(e->dstu_margin.resize(C));
+  std::vector<double> nu(C, 30.0), dx(C, 1.0), m(C, std::numeric_limits<double>::infinity());
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(e->dstu_nu.ptr, nu.data(), C * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->dstu_dx.ptr, dx.data(), C * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->dstu_margin.ptr, m.data(), C * 8, hipMemcpyHostToDevice));
+  return BA_OK;
+}
+
 extern "C" {
+
+// ------------------------ TRegressionSpikeSlabSampler
+int ba_student_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!X || !y) return fail(BA_E_INVALID, "null argument");
+  if (n <= 0 || p <= 0) return fail(BA_E_INVALID, "n and p must be positive");
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(y[i])) return fail(BA_E_INVALID, "responses must be finite");
+  std::vector<double> zero((size_t)n, 0.0);
+  int rc = ba_build_suf_from_xy(e, n, p, X, zero.data());   // (dimensions and the shared buffers)
+  if (rc) return rc;
+  HIP_TRY(e->dprob_X.resize((size_t)n * p));
+  HIP_TRY(e->dprob_y.resize((size_t)n));
+  HIP_TRY(hipMemcpy(e->dprob_X.ptr, X, (size_t)n * p * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->dprob_y.ptr, y, (size_t)n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(e->dlogit_Xsq.resize((size_t)n * p));
+  HIP_TRY(launch_square(e->stream, e->dprob_X.ptr, (size_t)n * p, e->dlogit_Xsq.ptr));
+  e->logit_mode = true;      // (the logit path's buffers and column service)
+  e->student_mode = true;
+  e->poisson_mode = false;
+  e->probit_mode = false;
+  e->probit_n = n;
+  e->probit_clt = 0;
+  e->probit_sweep = 0;
+  e->ss_mode = false;
+  e->dprob_z.release();
+  e->dstu_u.release();
+  // a new TRegressionModel: nu = 30, suggested_dx = 1, no slice margin yet (student_prepare)
+  e->dstu_nu.release();
+  e->dstu_dx.release();
+  e->dstu_margin.release();
+  return BA_OK;
+}
+
+int ba_student_allow_model_selection(ba_engine *e, int32_t allow) {
+  if (!e) return fail(BA_E_INVALID, "null engine");
+  MUTATE(e);
+  e->student_allow_selection = allow != 0;
+  return BA_OK;
+}
+
+int ba_student_set_nu_prior(ba_engine *e, int32_t kind, double a, double b) {
+  if (!e) return fail(BA_E_INVALID, "null engine");
+  if (kind == STUDENT_NU_UNIFORM) {
+    if (!(std::isfinite(a) && std::isfinite(b) && a >= 0 && b > a))
+      return fail(BA_E_INVALID, "a Uniform(a, b) prior on nu needs 0 <= a < b, both finite");
+  } else if (kind == STUDENT_NU_GAMMA) {
+    if (!(std::isfinite(a) && std::isfinite(b) && a > 0 && b > 0))
+      return fail(BA_E_INVALID, "a Gamma(a, b) prior on nu needs a positive shape and rate");
+  } else {
+    return fail(BA_E_INVALID, "kind must be 0 (Uniform) or 1 (Gamma)");
+  }
+  MUTATE(e);
+  e->student_nu_kind = kind;
+  e->student_nu_a = a;
+  e->student_nu_b = b;
+  return BA_OK;
+}
+
+int ba_student_set_nu(ba_engine *e, int64_t chain, double nu) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!(nu > 0) || !std::isfinite(nu)) return fail(BA_E_INVALID, "nu must be positive and finite");
+  const int64_t C = e->cfg.chains;
+  if (chain < -1 || chain >= C) return fail(BA_E_INVALID, "chain index out of range");
+  int rc = student_prepare(e);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (chain < 0) {
+    std::vector<double> v((size_t)C, nu);
+    HIP_TRY(hipMemcpy(e->dstu_nu.ptr, v.data(), (size_t)C * 8, hipMemcpyHostToDevice));
+  } else {
+    HIP_TRY(hipMemcpy(e->dstu_nu.ptr + chain, &nu, 8, hipMemcpyHostToDevice));
+  }
+  return BA_OK;
+}
+
+int ba_student_get_nu(ba_engine *e, int64_t chain, double *nu) {
+  ENGINE_PROLOGUE(e);
+  if (!nu) return fail(BA_E_INVALID, "null argument");
+  const int64_t C = e->cfg.chains;
+  if (chain < -1 || chain >= C) return fail(BA_E_INVALID, "chain index out of range");
+  int rc = student_prepare(e);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (chain < 0) HIP_TRY(hipMemcpy(nu, e->dstu_nu.ptr, (size_t)C * 8, hipMemcpyDeviceToHost));
+  else HIP_TRY(hipMemcpy(nu, e->dstu_nu.ptr + chain, 8, hipMemcpyDeviceToHost));
+  return BA_OK;
+}
+
+int ba_student_get_margin(ba_engine *e, int64_t chain, double *margin) {
+  ENGINE_PROLOGUE(e);
+  if (!margin) return fail(BA_E_INVALID, "null argument");
+  const int64_t C = e->cfg.chains;
+  if (chain < -1 || chain >= C) return fail(BA_E_INVALID, "chain index out of range");
+  int rc = student_prepare(e);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (chain < 0) HIP_TRY(hipMemcpy(margin, e->dstu_margin.ptr, (size_t)C * 8, hipMemcpyDeviceToHost));
+  else HIP_TRY(hipMemcpy(margin, e->dstu_margin.ptr + chain, 8, hipMemcpyDeviceToHost));
+  return BA_OK;
+}
+
+int ba_student_get_weights(ba_engine *e, int64_t chain, double *w) {
+  ENGINE_PROLOGUE(e);
+  if (!w) return fail(BA_E_INVALID, "null argument");
+  if (!e->student_mode) return fail(BA_E_STATE, "call ba_student_set_data first");
+  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  const size_t n = (size_t)e->probit_n;
+  if (e->dlogit_w.count != (size_t)e->cfg.chains * n || e->probit_sweep == 0)
+    return fail(BA_E_STATE, "no imputation has run yet: call ba_student_sweep first");
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(w, e->dlogit_w.ptr + (size_t)chain * n, n * 8, hipMemcpyDeviceToHost));
+  return BA_OK;
+}
+
+int ba_student_get_nu_draws(ba_engine *e, int64_t chain, int32_t nsweeps, double *out) {
+  ENGINE_PROLOGUE(e);
+  if (!out) return fail(BA_E_INVALID, "null argument");
+  if (e->trace_stride <= 0 || e->dstu_nu_rec.count == 0)
+    return fail(BA_E_STATE, "draws are not recorded: call ba_enable_draws before ba_student_sweep");
+  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  if (nsweeps <= 0 || nsweeps > e->trace_stride) return fail(BA_E_INVALID, "nsweeps out of range");
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(out, e->dstu_nu_rec.ptr + (size_t)chain * e->trace_stride, (size_t)nsweeps * 8,
+                    hipMemcpyDeviceToHost));
+  return BA_OK;
+}
+
+int ba_student_sweep(ba_engine *e, int32_t nsweeps) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
+  if (e->ss_mode) return fail(BA_E_STATE, "state-space data are set: use ba_ss_sweep");
+  if (e->poisson_mode) return fail(BA_E_STATE, "Poisson data are set: use ba_poisson_sweep");
+  if (e->probit_mode) return fail(BA_E_STATE, "binomial data are set: use ba_probit_sweep");
+  if (!e->student_mode && e->logit_mode) return fail(BA_E_STATE, "binomial data are set: use ba_logit_sweep");
+  if (!e->student_mode) return fail(BA_E_STATE, "call ba_student_set_data first");
+  if (e->trace_stride > 0 && e->dstu_nu_rec.count != (size_t)e->cfg.chains * e->trace_stride) {
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(e->dstu_nu_rec.resize((size_t)e->cfg.chains * e->trace_stride));
+  }
+  return logit_family_sweep(e, nsweeps);
+}
 
 int ba_logit_set_imputer(ba_engine *e, int32_t kind) {
   if (!e) return fail(BA_E_INVALID, "null engine");
@@ -3386,6 +3576,7 @@ int ba_logit_sweep(ba_engine *e, int32_t nsweeps) {
   ENGINE_PROLOGUE(e);
   MUTATE(e);
   if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
+  if (e->student_mode) return fail(BA_E_STATE, "Student-t regression data are set: use ba_student_sweep");
   if (e->poisson_mode) return fail(BA_E_STATE, "Poisson data are set: use ba_poisson_sweep");
   if (!e->logit_mode) return fail(BA_E_STATE, "call ba_logit_set_data first");
   return logit_family_sweep(e, nsweeps);
@@ -3395,6 +3586,7 @@ int ba_poisson_sweep(ba_engine *e, int32_t nsweeps) {
   ENGINE_PROLOGUE(e);
   MUTATE(e);
   if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
+  if (e->student_mode) return fail(BA_E_STATE, "Student-t regression data are set: use ba_student_sweep");
   if (!e->poisson_mode) return fail(BA_E_STATE, "call ba_poisson_set_data first");
   if (!e->poisson_mix_set) return fail(BA_E_STATE, "call ba_poisson_set_mixtures first");
   return logit_family_sweep(e, nsweeps);
@@ -3407,11 +3599,21 @@ int ba_poisson_sweep(ba_engine *e, int32_t nsweeps) {
 // coefficient draws with park-and-replay for vectors requested mid-sweep
 static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
   {
+  const bool student = e->student_mode;
   if (!e->have_slab) return fail(BA_E_STATE, "call ba_sss_set_slab first");
-  if (e->sss_slab_scales) return fail(BA_E_INVALID, "the logit sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
+  if (student && !e->sss_slab_scales)
+    return fail(BA_E_INVALID, "the Student-t sampler takes a slab whose precision scales with sigma^2 (scales_with_sigsq = 1)");
+  if (!student && e->sss_slab_scales) return fail(BA_E_INVALID, "the logit sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
   int rc = alloc_chain_state(e);
   if (rc) return rc;
   const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, n = (size_t)e->probit_n;
+  if (student) {
+    rc = student_prepare(e);
+    if (rc) return rc;
+    if (e->trace_stride > 0 && nsweeps > e->trace_stride)
+      return fail(BA_E_INVALID, "nsweeps exceeds the enabled trace length");
+    if (e->dstu_u.count != C * n) HIP_TRY(e->dstu_u.resize(C * n));
+  }
   if (e->dprob_z.count != C * n || e->dlogit_V.count != C * p * p) {
     HIP_TRY(e->dprob_z.resize(C * n));
     HIP_TRY(e->dlogit_w.resize(C * n));
@@ -3429,7 +3631,7 @@ static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
     e->logit_req_batch = std::min<int64_t>(e->logit_req_batch, (int64_t)(C * p));
     HIP_TRY(e->dlogit_planes.resize((size_t)e->logit_req_batch * per_req / 8));
   }
-  {
+  if (!student) {
     std::vector<double> one(C, 1.0);   // (sigma^2 = 1: see ba_probit_sweep)
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(e->dsigsq.ptr, one.data(), C * 8, hipMemcpyHostToDevice));
@@ -3467,13 +3669,53 @@ static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
   Q.obs_mix = e->dpois_obs.ptr;
   Q.mix_one = e->poisson_mix_one;
   const int imputer = e->poisson_mode ? 2 : e->logit_imputer;
+  StudentParams T;
+  std::memset(&T, 0, sizeof(T));
+  if (student) {
+    T.n = (int32_t)n;
+    T.p = (int32_t)p;
+    T.chains = (int32_t)C;
+    T.slot_limit = e->slot_limit;
+    T.chain_offset = e->cfg.chain_offset;
+    T.X = e->dprob_X.ptr;
+    T.y = e->dprob_y.ptr;
+    T.gamma = e->dgamma.ptr;
+    T.beta = e->dbeta.ptr;
+    T.sigsq = e->dsigsq.ptr;
+    T.nu = e->dstu_nu.ptr;
+    T.dx = e->dstu_dx.ptr;
+    T.margin = e->dstu_margin.ptr;
+    T.z = e->dprob_z.ptr;
+    T.w = e->dlogit_w.ptr;
+    T.u = e->dstu_u.ptr;
+    T.seed_lo = (uint32_t)e->seed;
+    T.seed_hi = (uint32_t)(e->seed >> 32);
+    T.status = e->dstatus.ptr;
+    T.prior_df = e->prior_df;
+    T.prior_ss = e->prior_ss;
+    T.sigma_max = e->sigma_max;
+    T.nu_kind = e->student_nu_kind;
+    T.nu_a = e->student_nu_a;
+    T.nu_b = e->student_nu_b;
+    T.trace_idx = e->dtrace_idx.ptr;
+    T.trace_sigsq = e->dtr_sig.ptr;
+    T.trace_nu = e->dstu_nu_rec.ptr;
+    T.trace_stride = e->dstu_nu_rec.count ? e->trace_stride : 0;
+    T.acc = e->dacc.ptr;
+    // (the draws recorded are those of the last ba_student_sweep call)
+    if (e->trace_stride > 0) HIP_TRY(hipMemsetAsync(e->dtrace_idx.ptr, 0, C * 4, e->stream));
+  }
   // BinomialLogitSpikeSlabSampler::draw (BinomialLogitSpikeSlabSampler.cpp:50-54) /
   // PoissonRegressionSpikeSlabSampler::draw (PoissonRegressionSpikeSlabSampler.cpp:55-59)
   for (int i = 0; i < nsweeps; ++i) {
-    Q.sweep = e->probit_sweep++;
+    Q.sweep = T.sweep = e->probit_sweep++;
     // impute_latent_data: z, w, X'Wz and the diagonal of V = slab precision + X'WX ...
-    HIP_TRY(launch_logit_impute(e->stream, Q, e->dlogit_Xsq.ptr, e->dA.ptr, e->dlogit_vdiag.ptr,
-                                e->dlogit_planes.ptr, imputer));
+    if (student)
+      HIP_TRY(launch_student_impute(e->stream, T, e->dlogit_Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->dlogit_vdiag.ptr,
+                                    e->dlogit_planes.ptr));
+    else
+      HIP_TRY(launch_logit_impute(e->stream, Q, e->dlogit_Xsq.ptr, e->dA.ptr, e->dlogit_vdiag.ptr,
+                                  e->dlogit_planes.ptr, imputer));
     // ... and the vectors of V the sweep starts from: those of the included variables
     HIP_TRY(launch_xtwx_cols_start(e->stream, e->dgamma.ptr, (int)C, (int)p, e->dlogit_req.ptr,
                                    e->dlogit_cnt.ptr, e->dlogit_valid.ptr, e->logit_words));
@@ -3490,6 +3732,12 @@ static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
     HIP_TRY(hipStreamSynchronize(e->stream));
     rc = check_chain_status(e);
     if (rc) return rc;
+    if (student) {
+      // draw_sigsq_full_conditional, draw_nu_given_observed_data
+      HIP_TRY(launch_student_sigma_nu(e->stream, T));
+      rc = check_chain_status(e);
+      if (rc) return rc;
+    }
     fill_params(e, P);
   }
   e->table_ok = false;
@@ -3536,6 +3784,7 @@ int ba_adaptive_sweep(ba_engine *e, int32_t nsweeps) {
   MUTATE(e);
   if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
   if (e->ss_mode) return fail(BA_E_STATE, "state-space data are set: use ba_ss_sweep");
+  if (e->student_mode) return fail(BA_E_STATE, "Student-t regression data are set: use ba_student_sweep");
   if (e->logit_mode || e->probit_mode)
     return fail(BA_E_STATE, "binomial data are set: use ba_logit_sweep / ba_probit_sweep (the regression sampler has no meaning on latent data)");
   int rc = alloc_chain_state(e);
@@ -3702,6 +3951,7 @@ int ba_ss_set_data(ba_engine *e, int32_t T, int32_t p, const double *y,
     e->dss_obs_mask.release();
   }
   e->ss_mode = true;
+  e->student_mode = false;
   e->ss_initialized = false;
   e->dss_scratch.release();
   e->device_dirty = true;

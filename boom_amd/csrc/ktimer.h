@@ -26,6 +26,8 @@ enum KernelClass {
   KT_POISSON_IMPUTE,// poisson_impute_kernel
   KT_KALMAN_PREPARE,// kalman_prepare_kernel (level variance + normals, second stream)
   KT_SS_ROUND,      // ss_round_kernel (the local-level bsts rounds of a call, one persistent launch)
+  KT_STUDENT_IMPUTE,   // student_impute_kernel
+  KT_STUDENT_SIGMA_NU, // student_sigma_nu_kernel
   KT_CLASSES
 };
 

@@ -1,0 +1,284 @@
+// TRegressionSpikeSlabSampler for many chains: the two kernels of a draw() that the logit
+// path does not already have.
+//   TRegressionSpikeSlabSampler::draw          (Models/Glm/PosteriorSamplers/
+//                                               TRegressionSpikeSlabSampler.cpp:41-47)
+//   impute_latent_data / TDataImputer::impute  (TRegressionSampler.cpp:124-140,
+//                                               TDataImputer.cpp:26-30)
+//   draw_sigsq_full_conditional                (TRegressionSampler.cpp:160-166,
+//                                               GenericGaussianVarianceSampler.cpp:44-63)
+//   draw_nu_given_observed_data                (TRegressionSampler.cpp:173-176,
+//                                               Samplers/ScalarSliceSampler.cpp:75-253)
+//
+// student_impute_kernel: one thread per (chain, observation), the grid of
+// logit_impute_kernel.  w_i ~ Gamma((nu + 1) / 2, rate (nu + delta_i^2) / 2) with
+// delta_i = (y_i - x_i'beta) / sigma, by the device's reference-exact gamma sampler, from the
+// chain's stream STUDENT_IMPUTE_STREAM at slot (s n + i).  It writes w_i and z_i = w_i y_i;
+// X'Wy and the diagonal of Omega^{-1} + X'WX are the logit path's rows-times-columns GEMMs.
+//
+// student_sigma_nu_kernel: one workgroup per chain, after the inclusion / coefficient draws.
+//   1. r_i = y_i - x_i'beta at the NEW beta; wsse = sum_i w_i r_i^2 (one pass, see DESIGN:
+//      the reference forms beta'X'WX beta - 2 beta'X'Wy + y'Wy from the suf);
+//   2. sigma^2 by the device variance sampler (rtrun_gamma when sigma has an upper limit);
+//   3. u_i = (r_i / sigma)^2 once, kept in a chains x n buffer (L2 / MALL);
+//   4. nu by the slice sampler with lower limit 0, unimodal = false, the chain's own
+//      suggested_dx.  log f(nu) = log prior(nu) + n [lgamma((nu+1)/2) - lgamma(nu/2)
+//      - log(nu pi) / 2] - n log sigma - (nu+1)/2 sum_i log1p(u_i / nu): dt in closed form,
+//      one workgroup reduction per evaluation.  Every lane takes the same control path
+//      (every value that steers it is a broadcast reduction or a draw every lane makes from
+//      the same stream position).
+// sigma^2 and nu read the chain's stream STUDENT_SN_STREAM at slot s.
+#include <hip/hip_runtime.h>
+
+#include "ktimer.h"
+
+#include "device_rng.h"
+#include "ssvs_params.h"
+#include "student_params.h"
+
+namespace boom_amd {
+
+namespace {
+
+__device__ __forceinline__ uint32_t stu_serve(const StudentParams &P, uint32_t stride) {
+  return (P.slot_limit > 0 && (uint32_t)P.slot_limit < stride) ? (uint32_t)P.slot_limit : stride;
+}
+
+// the chain's included variables and their coefficients, in index order, into LDS (256 threads)
+__device__ __forceinline__ int stu_included(const StudentParams &P, int chain, int *s_idx, double *s_beta) {
+  __shared__ int s_wave_count[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint8_t *g = P.gamma + (size_t)chain * P.p;
+  const double *b = P.beta + (size_t)chain * P.p;
+  int base = 0;
+  for (int j0 = 0; j0 < P.p; j0 += 256) {
+    const int j = j0 + tid;
+    const bool inc = j < P.p && g[j] != 0;
+    const unsigned long long m = __ballot(inc);
+    if (lane == 0) s_wave_count[wave] = __popcll(m);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int c = s_wave_count[w];
+      before += (w < wave) ? c : 0;
+      total += c;
+    }
+    if (inc) {
+      const int pos = base + before + __popcll(m & ((1ull << lane) - 1ull));
+      if (pos < STUDENT_KMAX) { s_idx[pos] = j; s_beta[pos] = b[j]; }
+    }
+    base += total;
+    __syncthreads();
+  }
+  return base;
+}
+
+// sum over the workgroup's 256 threads, in a fixed order; every thread gets the result
+__device__ __forceinline__ double stu_block_sum(double v, double *s_red) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();   // (s_red may still be read from the previous call)
+  if (lane == 0) s_red[wave] = v;
+  __syncthreads();
+  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void student_impute_kernel(StudentParams P) {
+  const int chain = (int)blockIdx.y, i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  __shared__ int s_status;
+  if (threadIdx.x == 0) s_status = __atomic_load_n(P.status + chain, __ATOMIC_RELAXED);
+  __syncthreads();
+  if (s_status != CHAIN_OK) return;
+  __shared__ int s_idx[STUDENT_KMAX];
+  __shared__ double s_beta[STUDENT_KMAX];
+  const int k = stu_included(P, chain, s_idx, s_beta);
+  if (k > STUDENT_KMAX) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) P.status[chain] = CHAIN_MODEL_TOO_LARGE;
+    return;
+  }
+  if (i >= P.n) return;
+  double eta = 0.0;
+  for (int m = 0; m < k; ++m) eta += P.X[(size_t)s_idx[m] * P.n + i] * s_beta[m];
+  const double yi = P.y[i];
+  const double nu = P.nu[chain];
+  const double delta = (yi - eta) / sqrt(P.sigsq[chain]);
+  SeqRng rng = SeqRng::slot(PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), STUDENT_IMPUTE_STREAM},
+                            P.sweep * (uint64_t)P.n + (uint64_t)i, STUDENT_IMPUTE_STRIDE,
+                            stu_serve(P, STUDENT_IMPUTE_STRIDE));
+  // rgamma_mt(rng, (nu + 1) / 2, (nu + delta^2) / 2): shape, rate.  The shape is above 1/2,
+  // so the small-shape branch (wave-uniform only) is never taken.
+  int bad = 0;
+  const double w = d_rgamma_scale(rng, 0.5 * (nu + 1), 1.0 / (0.5 * (nu + delta * delta)), &bad);
+  if (bad || rng.overran()) P.status[chain] = CHAIN_RNG_BRANCH;
+  P.w[(size_t)chain * P.n + i] = w;
+  P.z[(size_t)chain * P.n + i] = w * yi;
+}
+
+namespace {
+
+struct StuSlice {
+  const StudentParams *P;
+  const double *u;   // this chain's u_i
+  double n_log_sigma;
+  double *s_red;
+  double margin;
+  // log f(nu): the prior's logp, then (unless that is -inf) the observed-data likelihood
+  __device__ double logf(double nu) {
+    double lp;
+    if (P->nu_kind == STUDENT_NU_UNIFORM) {
+      lp = (nu > P->nu_b || nu < P->nu_a) ? -__builtin_inf() : log(1.0 / (P->nu_b - P->nu_a));
+    } else {
+      const double a = P->nu_a, b = P->nu_b;
+      lp = !(nu > 0) ? -__builtin_inf() : a * log(b) - lgamma(a) + (a - 1) * log(nu) - b * nu;
+    }
+    if (lp <= -__builtin_inf()) return lp;
+    double part = 0.0;
+    const double inv = 1.0 / nu;
+    for (int i = threadIdx.x; i < P->n; i += STUDENT_SN_BLOCK) part += log1p(u[i] * inv);
+    const double s = stu_block_sum(part, s_red);
+    const double nn = (double)P->n;
+    const double c = lgamma(0.5 * (nu + 1)) - lgamma(0.5 * nu) - 0.5 * log(nu * 3.141592653589793);
+    return lp + (nn * c - n_log_sigma) - 0.5 * (nu + 1) * s;
+  }
+  __device__ void note(double a, double b) {
+    if (!isfinite(a) || !isfinite(b)) return;
+    const double den = fmax(fmax(fabs(a), fabs(b)), 1e-300);
+    margin = fmin(margin, fabs(a - b) / den);
+  }
+};
+
+}  // namespace
+
+__global__ __launch_bounds__(STUDENT_SN_BLOCK) void student_sigma_nu_kernel(StudentParams P) {
+  const int chain = (int)blockIdx.x, tid = (int)threadIdx.x;
+  __shared__ int s_status;
+  __shared__ double s_red[4];
+  if (tid == 0) s_status = __atomic_load_n(P.status + chain, __ATOMIC_RELAXED);
+  __syncthreads();
+  if (s_status != CHAIN_OK) return;
+  __shared__ int s_idx[STUDENT_KMAX];
+  __shared__ double s_beta[STUDENT_KMAX];
+  const int k = stu_included(P, chain, s_idx, s_beta);
+  if (k > STUDENT_KMAX) {
+    if (tid == 0) P.status[chain] = CHAIN_MODEL_TOO_LARGE;
+    return;
+  }
+  const int n = P.n;
+  const double *w = P.w + (size_t)chain * n;
+  double *u = P.u + (size_t)chain * n;
+  // 1. residuals at the new beta, the weighted sum of squared errors
+  double part = 0.0;
+  for (int i = tid; i < n; i += STUDENT_SN_BLOCK) {
+    double eta = 0.0;
+    for (int m = 0; m < k; ++m) eta += P.X[(size_t)s_idx[m] * n + i] * s_beta[m];
+    const double r = P.y[i] - eta;
+    u[i] = r;
+    part += w[i] * (r * r);
+  }
+  const double wsse = stu_block_sum(part, s_red);
+  // 2. sigma^2 (GenericGaussianVarianceSampler::draw: n observations, not sum w)
+  SeqRng rng = SeqRng::slot(PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), STUDENT_SN_STREAM},
+                            P.sweep, STUDENT_SN_STRIDE, stu_serve(P, STUDENT_SN_STRIDE));
+  int bad = 0;
+  const double sigsq = d_draw_variance(rng, (double)n + P.prior_df, wsse + P.prior_ss, P.sigma_max, &bad);
+  if (bad) {
+    if (tid == 0) P.status[chain] = CHAIN_RNG_BRANCH;
+    return;
+  }
+  const double sigma = sqrt(sigsq);
+  // 3. u_i = (r_i / sigma)^2 (dstudent's (x - mu) / sigma, squared as dt squares it)
+  for (int i = tid; i < n; i += STUDENT_SN_BLOCK) {
+    const double t = u[i] / sigma;
+    u[i] = t * t;
+  }
+  __syncthreads();   // (every thread reads every u_i from here on)
+  // 4. nu: ScalarSliceSampler::draw with lower limit 0 (find_limits -> find_upper_limit)
+  StuSlice S{&P, u, (double)n * log(sigma), s_red, __builtin_inf()};
+  const double x = P.nu[chain];
+  const double sigsq_in = P.sigsq[chain];   // (the sweep's: its summaries hold this one)
+  double dx = P.dx[chain];
+  int err = 0;
+  double nu = x;
+  const double logp_slice = S.logf(x) - d_rexp(rng, 1.0);
+  if (!isfinite(logp_slice)) err = 1;                        // check_finite
+  double lo = 0.0, hi = 0.0;
+  if (!err) {
+    hi = x + dx;
+    double logphi = S.logf(hi);
+    S.note(logphi, logp_slice);
+    int doublings = 0;
+    while (logphi >= logp_slice || d_runif(rng, 0.0, 1.0) > .5) {
+      hi = x + 2 * (hi - x);                                   // double_hi
+      if (!isfinite(hi)) { err = 1; break; }
+      logphi = S.logf(hi);
+      S.note(logphi, logp_slice);
+      if (++doublings > 100) { err = 1; break; }
+    }
+    if (!err && (!isfinite(hi) || isnan(logphi))) err = 1;   // check_upper_limit
+  }
+  if (!err) {
+    int tries = 0;
+    for (;;) {
+      const double cand = d_runif(rng, lo, hi);
+      const double lp = S.logf(cand);
+      S.note(lp, logp_slice);
+      if (!(lp < logp_slice)) { nu = cand; break; }
+      if (cand > x) hi = cand; else lo = cand;                 // contract
+      dx = hi - lo;
+      if (++tries > 100) { err = 1; break; }
+    }
+  }
+  if (rng.overran()) err = 2;
+  if (tid == 0) {
+    P.sigsq[chain] = sigsq;
+    if (P.acc) {
+      // the summaries' sigma^2 moments are those of the draws, not of the sweeps' inputs
+      double *a = P.acc + (size_t)chain * ACC_COUNT;
+      a[ACC_SIGSQ] = (a[ACC_SIGSQ] - sigsq_in) + sigsq;
+      a[ACC_SIGSQ2] = (a[ACC_SIGSQ2] - sigsq_in * sigsq_in) + sigsq * sigsq;
+    }
+    if (err) {
+      P.status[chain] = err == 2 ? CHAIN_RNG_BRANCH : STUDENT_SLICE_ERROR;
+    } else {
+      P.nu[chain] = nu;
+      P.dx[chain] = dx;
+    }
+    P.margin[chain] = fmin(P.margin[chain], S.margin);
+    if (P.trace_stride > 0) {
+      const int row = P.trace_idx[chain] - 1;
+      if (row >= 0 && row < P.trace_stride) {
+        P.trace_sigsq[(size_t)chain * P.trace_stride + row] = sigsq;
+        P.trace_nu[(size_t)chain * P.trace_stride + row] = nu;
+      }
+    }
+  }
+}
+
+hipError_t launch_rows_times_columns(hipStream_t stream, const double *U, int R, const double *B, int64_t n,
+                                     int p, const double *diag_base, double *out, double *planes);
+
+// impute, X'Wz and the diagonal of V = slab precision + X'WX for every chain
+hipError_t launch_student_impute(hipStream_t stream, const StudentParams &P, const double *Xsq,
+                                 const double *slab_precision, double *xtz, double *v_diag, double *planes) {
+  hipError_t err;
+  {
+    KtScope kt(stream, KT_STUDENT_IMPUTE);
+    hipLaunchKernelGGL(student_impute_kernel, dim3((P.n + 255) / 256, P.chains), dim3(256), 0, stream, P);
+    err = hipGetLastError();
+  }
+  if (err != hipSuccess) return err;
+  err = launch_rows_times_columns(stream, P.z, P.chains, P.X, (int64_t)P.n, P.p, nullptr, xtz, planes);
+  if (err != hipSuccess) return err;
+  return launch_rows_times_columns(stream, P.w, P.chains, Xsq, (int64_t)P.n, P.p, slab_precision, v_diag, planes);
+}
+
+hipError_t launch_student_sigma_nu(hipStream_t stream, const StudentParams &P) {
+  KtScope kt(stream, KT_STUDENT_SIGMA_NU);
+  hipLaunchKernelGGL(student_sigma_nu_kernel, dim3(P.chains), dim3(STUDENT_SN_BLOCK), 0, stream, P);
+  return hipGetLastError();
+}
+
+}  // namespace boom_amd

@@ -509,4 +509,52 @@ PYBIND11_MODULE(_boom, boom) {
            py::arg("model"), py::arg("slab"), py::arg("spike"), py::arg("number_of_threads") = 1,
            py::arg("seeding_rng") = py::none(), py::keep_alive<1, 2>())
       .def("limit_model_selection", &PoissonRegressionSpikeSlabSampler::limit_model_selection);
+
+  // ---- Student-t regression spike and slab (GlmModel_def.cpp:468-495) ----------------------
+  py::class_<DoubleModel, Ptr<DoubleModel>>(boom, "DoubleModel");
+  py::class_<UniformModel, DoubleModel, Ptr<UniformModel>>(boom, "UniformModel")
+      .def(py::init<double, double>(), py::arg("lo") = 0.0, py::arg("hi") = 1.0)
+      .def_property_readonly("lo", &UniformModel::lo)
+      .def_property_readonly("hi", &UniformModel::hi);
+  py::class_<GammaModel, DoubleModel, Ptr<GammaModel>>(boom, "GammaModel")
+      .def(py::init<double, double>(), py::arg("a") = 1.0, py::arg("b") = 1.0, "shape a, rate b")
+      .def_property_readonly("alpha", &GammaModel::alpha)
+      .def_property_readonly("beta", &GammaModel::beta);
+  py::class_<TRegressionModel, Ptr<TRegressionModel>>(boom, "TRegressionModel")
+      .def(py::init([](const NpArray &X, const NpArray &y, int chains, uint64_t seed, int device) {
+             return new TRegressionModel(matrix_from(X), vector_from(y), chains, seed, device);
+           }),
+           py::arg("predictors"), py::arg("response"), py::arg("chains") = 1,
+           py::arg("seed") = 8675309ull, py::arg("device") = 0)
+      .def("drop_all", &TRegressionModel::drop_all)
+      .def("add", &TRegressionModel::add)
+      .def("drop", &TRegressionModel::drop)
+      .def_property_readonly("inc", [](const TRegressionModel &m) {
+        std::vector<bool> g(m.xdim());
+        for (int j = 0; j < m.xdim(); ++j) g[j] = m.inc()[j];
+        return g;
+      })
+      .def_property_readonly("Beta", [](const TRegressionModel &m) { return to_numpy(m.Beta()); })
+      .def("set_Beta", [](TRegressionModel &m, const NpArray &b) { m.set_Beta(vector_from(b)); })
+      .def_property_readonly("sigsq", &TRegressionModel::sigsq)
+      .def_property_readonly("sigma", [](const TRegressionModel &m) { return std::sqrt(m.sigsq()); })
+      .def_property_readonly("nu", &TRegressionModel::nu)
+      .def("set_sigsq", &TRegressionModel::set_sigsq)
+      .def("set_nu", &TRegressionModel::set_nu)
+      .def("set_method", [](TRegressionModel &m, const Ptr<PosteriorSampler> &s) { m.set_method(s); })
+      .def("sample_posterior", &TRegressionModel::sample_posterior);
+  py::class_<TRegressionSpikeSlabSampler, PosteriorSampler, Ptr<TRegressionSpikeSlabSampler>>(
+      boom, "TRegressionSpikeSlabSampler")
+      .def(py::init([](TRegressionModel *model, const Ptr<MvnGivenScalarSigma> &slab,
+                       const Ptr<VariableSelectionPrior> &spike, const Ptr<ChisqModel> &siginv_prior,
+                       const Ptr<DoubleModel> &nu_prior, py::object) {
+             return new TRegressionSpikeSlabSampler(model, slab, spike, siginv_prior, nu_prior);
+           }),
+           py::arg("model"), py::arg("coefficient_slab"), py::arg("coefficient_spike"),
+           py::arg("siginv_prior"), py::arg("nu_prior"), py::arg("seeding_rng") = py::none(),
+           py::keep_alive<1, 2>())
+      .def("draw", &TRegressionSpikeSlabSampler::draw)
+      .def("set_sigma_upper_limit", &TRegressionSpikeSlabSampler::set_sigma_upper_limit)
+      .def("limit_model_selection", &TRegressionSpikeSlabSampler::limit_model_selection)
+      .def("allow_model_selection", &TRegressionSpikeSlabSampler::allow_model_selection);
 }

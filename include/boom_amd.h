@@ -336,6 +336,43 @@ int ba_poisson_set_mixtures(ba_engine *e, int32_t ncounts, const int64_t *counts
                             const double *weight, int64_t largest_index);
 int ba_poisson_sweep(ba_engine *e, int32_t nsweeps);
 
+/* ---- TRegressionSpikeSlabSampler (lm.spike's error.distribution = "student") ---------------
+ * Models/Glm/PosteriorSamplers/TRegressionSpikeSlabSampler.cpp:41-47: per sweep the weights
+ * w_i ~ Gamma((nu + 1) / 2, rate (nu + (r_i / sigma)^2) / 2) (TDataImputer.cpp:26-30), then
+ * SpikeSlabSampler's inclusion / coefficient draws given sigma^2 on the weighted suf (the
+ * logit path's machinery: X'Wy by one GEMM, every chain's own Omega^{-1} + X'WX a vector at a
+ * time), sigma^2 | beta, w (GenericGaussianVarianceSampler, n observations), and nu by the
+ * slice sampler on the observed-data likelihood (ScalarSliceSampler, lower limit 0).
+ *   ba_student_set_data      X n x p column-major, y n; Student mode
+ *   priors                   ba_sss_set_slab(mu, precision, 1, max_flips), ba_set_spike,
+ *                            ba_set_sigma_prior(df, sigma_guess, sigma_upper_limit)
+ *   ba_student_set_nu_prior  kind 0: Uniform(a, b); kind 1: Gamma(a, b) (shape, rate);
+ *                            default Uniform(0.1, 100) (R's lm.spike)
+ *   ba_student_set_nu / _get_nu   chain -1: every chain; the default nu is 30
+ *   ba_student_sweep         nsweeps x draw() on every chain; ba_set_state / ba_get_state(s)
+ *                            carry gamma, beta and sigma^2; with ba_enable_draws the draws
+ *                            of the call are recorded (ba_get_draws, ba_predict) and
+ *                            ba_student_get_nu_draws returns the recorded nu path
+ *   ba_student_get_weights   the last imputation's n weights of one chain (diagnostics)
+ *   ba_student_get_margin    per chain (chain -1: all), the smallest relative gap between the
+ *                            two sides of a slice-sampler comparison since the data were set
+ *   ba_student_allow_model_selection  SpikeSlabSampler::allow_model_selection: 0 skips the
+ *                            inclusion draws (no numbers read for them), 1 (default) draws them
+ * ba_student_set_data starts a new model: nu = 30, the slice width 1, no margin yet.
+ * ba_get_summaries' sigma^2 moments are those of the sigma^2 draws.
+ * RNG: stream 3 for the inclusion / coefficient draws; stream 31 from position
+ * (s n + i) * 256 for the weight of observation i in sweep s; stream 15 from position
+ * s * 4096 for sigma^2 and then nu in sweep s. */
+int ba_student_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y);
+int ba_student_set_nu_prior(ba_engine *e, int32_t kind, double a, double b);
+int ba_student_set_nu(ba_engine *e, int64_t chain, double nu);
+int ba_student_get_nu(ba_engine *e, int64_t chain, double *nu);
+int ba_student_sweep(ba_engine *e, int32_t nsweeps);
+int ba_student_get_weights(ba_engine *e, int64_t chain, double *w);
+int ba_student_get_nu_draws(ba_engine *e, int64_t chain, int32_t nsweeps, double *out);
+int ba_student_get_margin(ba_engine *e, int64_t chain, double *margin);
+int ba_student_allow_model_selection(ba_engine *e, int32_t allow);
+
 /* ---- posterior summaries --------------------------------------------------- */
 /* Running sums over every sweep since the last ba_reset_summaries(), reduced
  * over this engine's chains on the device:

@@ -920,4 +920,107 @@ class PoissonRegressionSpikeSlabSampler : public PosteriorSampler {
   Ptr<MvnModel> slab_;
 };
 
+// ---- Student-t regression spike and slab ----------------------------------------------
+// TRegressionModel + TRegressionSpikeSlabSampler (Models/Glm/TRegression.hpp,
+// PosteriorSamplers/TRegressionSpikeSlabSampler.cpp:41-47): the weights, the inclusion /
+// coefficient draws given sigma^2, sigma^2 and the slice-sampler draw of nu, on the device
+// (ba_student_*).  The prior on nu is a UniformModel(lo, hi) or a GammaModel(a, b).
+struct DoubleModel {
+  DoubleModel(int kind, double a, double b) : kind_(kind), a_(a), b_(b) {}
+  virtual ~DoubleModel() {}
+  int kind_;
+  double a_, b_;
+};
+struct UniformModel : DoubleModel {
+  UniformModel(double lo = 0.0, double hi = 1.0) : DoubleModel(0, lo, hi) {}
+  double lo() const { return a_; }
+  double hi() const { return b_; }
+};
+struct GammaModel : DoubleModel {   // shape a, rate b
+  GammaModel(double a = 1.0, double b = 1.0) : DoubleModel(1, a, b) {}
+  double alpha() const { return a_; }
+  double beta() const { return b_; }
+};
+
+// TRegressionModel(X, y): sigma^2 = 1 and nu = 30 (TRegression.cpp:35-45); chain 0 backs
+// the model's accessors
+class TRegressionModel : public Model {
+ public:
+  TRegressionModel(const Matrix &X, const Vector &y, int chains = 1, uint64_t seed = 8675309, int device = 0)
+      : eng_(new Engine(chains, seed, device)), p_(X.ncol()), inc_(X.ncol(), true), beta_(X.ncol(), 0.0) {
+    if (X.nrow() != (int)y.size()) report_error("X and y are incompatible in TRegressionModel constructor.");
+    eng_->check(ba_student_set_data(eng_->get(), X.nrow(), X.ncol(), X.data(), y.data()));
+  }
+  int xdim() const { return p_; }
+  const Selector &inc() const { return inc_; }
+  void drop_all() { inc_.drop_all(); dirty_ = true; }
+  void add(int i) { inc_.add(i); dirty_ = true; }
+  void drop(int i) { inc_.drop(i); dirty_ = true; }
+  const Vector &Beta() const { return beta_; }
+  void set_Beta(const Vector &b) { beta_ = b; dirty_ = true; }
+  double sigsq() const { return sigsq_; }
+  void set_sigsq(double s2) { sigsq_ = s2; dirty_ = true; }
+  double nu() const { return nu_; }
+  void set_nu(double nu) {
+    eng_->check(ba_student_set_nu(eng_->get(), -1, nu));
+    nu_ = nu;
+  }
+  bool dirty() const { return dirty_; }
+  const Ptr<Engine> &engine() const { return eng_; }
+  void push_state() {
+    eng_->check(ba_set_state(eng_->get(), -1, inc_.bytes().data(), beta_.data(), sigsq_));
+    dirty_ = false;
+  }
+  void pull_chain0() {
+    eng_->check(ba_get_state(eng_->get(), 0, inc_.bytes().data(), beta_.data(), &sigsq_));
+    eng_->check(ba_student_get_nu(eng_->get(), 0, &nu_));
+    dirty_ = false;
+  }
+ private:
+  Ptr<Engine> eng_;
+  int p_;
+  Selector inc_;
+  Vector beta_;
+  double sigsq_ = 1.0, nu_ = 30.0;
+  bool dirty_ = true;
+};
+// TRegressionSpikeSlabSampler(model, slab, spike, siginv_prior, nu_prior)
+class TRegressionSpikeSlabSampler : public PosteriorSampler {
+ public:
+  TRegressionSpikeSlabSampler(TRegressionModel *model, const Ptr<MvnGivenScalarSigma> &slab,
+                              const Ptr<VariableSelectionPrior> &spike, const Ptr<ChisqModel> &siginv_prior,
+                              const Ptr<DoubleModel> &nu_prior)
+      : model_(model), slab_(slab), siginv_(siginv_prior) {
+    if (slab->dim() != model->xdim()) report_error("Slab does not match model dimension.");
+    if ((int)spike->potential_nvars() != model->xdim()) report_error("Spike does not match model dimension.");
+    check(ba_sss_set_slab(h(), slab->mu().data(), slab->unscaled_precision().data(), 1, -1));
+    check(ba_set_spike(h(), spike->prior_inclusion_probabilities().data(), spike->max_model_size()));
+    check(ba_set_sigma_prior(h(), siginv_prior->df(), siginv_prior->sigma(), sigma_max_));
+    check(ba_student_set_nu_prior(h(), nu_prior->kind_, nu_prior->a_, nu_prior->b_));
+  }
+  void draw() override {
+    if (model_->dirty()) model_->push_state();
+    check(ba_student_sweep(h(), 1));
+    check(ba_sync(h()));
+    model_->pull_chain0();
+  }
+  double logpri() const override { report_error("logpri() is not implemented for the Student-t sampler"); return 0; }
+  void set_seed(unsigned long s) override { check(ba_seed(h(), s)); }
+  void set_sigma_upper_limit(double max_sigma) {
+    sigma_max_ = max_sigma;
+    check(ba_set_sigma_prior(h(), siginv_->df(), siginv_->sigma(), sigma_max_));
+  }
+  void limit_model_selection(int max_flips) {
+    check(ba_sss_set_slab(h(), slab_->mu().data(), slab_->unscaled_precision().data(), 1, max_flips));
+  }
+  void allow_model_selection(bool allow) { check(ba_student_allow_model_selection(h(), allow ? 1 : 0)); }
+ private:
+  ba_engine *h() const { return model_->engine()->get(); }
+  void check(int rc) const { model_->engine()->check(rc); }
+  TRegressionModel *model_;
+  Ptr<MvnGivenScalarSigma> slab_;
+  Ptr<ChisqModel> siginv_;
+  double sigma_max_ = std::numeric_limits<double>::infinity();
+};
+
 }  // namespace boom_amd_api
