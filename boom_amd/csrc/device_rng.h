@@ -230,6 +230,14 @@ __device__ __forceinline__ void stream_seek(WinRng &r, uint64_t p) {
   r.set_pos(((uint64_t)hi << 32) | lo);
 }
 
+// The plain sequential view an out-of-line routine reads through, and the caller's view
+// moved on to where that routine stopped.  A slot's view keeps its limit and spill position:
+// numbers past the slot's share come from its spill stream, inside the routine as outside.
+__device__ __forceinline__ SeqRng seq_view(const SeqRng &r) { return r; }
+__device__ __forceinline__ SeqRng seq_view(const WinRng &r) { return SeqRng{stream_key(r), stream_pos(r)}; }
+__device__ __forceinline__ void seq_resume(SeqRng &r, const SeqRng &v) { r = v; }
+__device__ __forceinline__ void seq_resume(WinRng &r, const SeqRng &v) { stream_seek(r, v.pos); }
+
 template <class R>
 __device__ __forceinline__ double d_runif(R &r, double a, double b) {
   if (a == b) return a;
@@ -366,10 +374,10 @@ __device__ __forceinline__ double d_rgamma_scale(R &rng, double a, double scale,
   if (a < .3) {
     // (the out-of-line routine reads the stream through the plain sequential
     // view, whatever view the caller uses: same numbers, same positions)
-    SeqRng sr{stream_key(rng), stream_pos(rng)};
+    SeqRng sr = seq_view(rng);
     int b2 = 0;
     const double lg = d_rloggamma_small_alpha(sr, a, &b2);
-    stream_seek(rng, sr.pos);
+    seq_resume(rng, sr);
     *bad |= __builtin_amdgcn_readfirstlane(b2);
     const double x = exp(lg + log(scale));
     const unsigned long long xb = __builtin_bit_cast(unsigned long long, x);
@@ -621,10 +629,10 @@ __device__ __forceinline__ double d_draw_variance(R &rng, double DF, double SS,
   if (!(cut < mode)) {
     // (the out-of-line routines read the stream through the plain sequential
     // view, whatever view the caller uses: same numbers, same positions)
-    SeqRng sr{stream_key(rng), stream_pos(rng)};
+    SeqRng sr = seq_view(rng);
     int b2 = 0;
     const double x = (a > 1) ? d_ars_gamma_tail(sr, a, b, cut, &b2) : d_slice_gamma_tail(sr, a, b, cut);
-    stream_seek(rng, sr.pos);
+    seq_resume(rng, sr);
     // (every lane computed the same thing; tell the compiler, whose callers
     // steer wave-uniform control flow by these values)
     *bad |= __builtin_amdgcn_readfirstlane(b2);

@@ -18,6 +18,10 @@
 #include <vector>
 
 #include "Models/Glm/PoissonRegressionModel.hpp"
+#include "Models/Glm/TRegression.hpp"
+#include "Models/Glm/PosteriorSamplers/TRegressionSpikeSlabSampler.hpp"
+#include "Models/GammaModel.hpp"
+#include "Models/UniformModel.hpp"
 #include "Models/Glm/PosteriorSamplers/PoissonRegressionSpikeSlabSampler.hpp"
 #include "Models/Glm/PosteriorSamplers/NormalMixtureApproximation.hpp"
 #include "Models/Glm/PosteriorSamplers/poisson_mixture_approximation_table.hpp"
@@ -1308,6 +1312,73 @@ int ref_poisson_run(int n, int p, const double *X, const double *y, const double
       out_gamma[(size_t)i * p + j] = inc[j] ? 1 : 0;
       out_beta[(size_t)i * p + j] = beta[j];
     }
+  }
+  REF_CATCH
+}
+
+// ---- TRegressionSpikeSlabSampler (Student-t errors) ------------------------------------
+// TRegressionModel(p) with slab MvnGivenScalarSigma(mu, prec, sigsq), spike
+// VariableSelectionPrior(pi), sigma^-2 prior ChisqModel(sigma_df, sigma_guess) and nu prior
+// UniformModel(a, b) (nu_kind 0) or GammaModel(a, b) (nu_kind 1); stepped with
+// sample_posterior() from (init_gamma, init_beta, init_sigsq, init_nu).  Per sweep: gamma,
+// beta, sigma^2, nu, and from complete_data_sufficient_statistics() (the suf the sweep's
+// weights built) sum of weights, y'Wy and X'Wy.  sigma_max = inf: no upper limit.
+int ref_student_run(int n, int p, const double *X, const double *y, const double *mu,
+                    const double *prec, const double *pi, int64_t max_model_size,
+                    int max_flips, int allow_selection, double sigma_df, double sigma_guess,
+                    double sigma_max, int nu_kind, double nu_a, double nu_b, uint64_t seed,
+                    const uint8_t *init_gamma, const double *init_beta, double init_sigsq,
+                    double init_nu, int nsweeps, uint8_t *out_gamma, double *out_beta,
+                    double *out_sigsq, double *out_nu, double *out_sumw, double *out_yty,
+                    double *out_xty) {
+  REF_TRY
+  GlobalRng::rng.seed(seed);
+  NEW(TRegressionModel, model)(p);
+  for (int i = 0; i < n; ++i) {
+    Vector x(p);
+    for (int j = 0; j < p; ++j) x[j] = X[(size_t)j * n + i];
+    NEW(RegressionData, dp)(y[i], x);
+    model->add_data(dp);
+  }
+  NEW(MvnGivenScalarSigma, slab)(make_vector(p, mu), make_spd(p, prec), model->Sigsq_prm());
+  NEW(VariableSelectionPrior, spike)(make_vector(p, pi));
+  if (max_model_size >= 0) spike->set_max_model_size(max_model_size);
+  NEW(ChisqModel, siginv_prior)(sigma_df, sigma_guess);
+  Ptr<DoubleModel> nu_prior;
+  if (nu_kind == 0)
+    nu_prior = new UniformModel(nu_a, nu_b);
+  else
+    nu_prior = new GammaModel(nu_a, nu_b);
+  NEW(TRegressionSpikeSlabSampler, sam)(model.get(), slab, spike, siginv_prior, nu_prior);
+  if (std::isfinite(sigma_max)) sam->set_sigma_upper_limit(sigma_max);
+  if (max_flips >= 0) sam->limit_model_selection(max_flips);
+  if (!allow_selection) sam->allow_model_selection(false);
+  model->set_method(sam);
+  model->coef().drop_all();
+  Vector b0(p, 0.0);
+  for (int j = 0; j < p; ++j)
+    if (init_gamma[j]) {
+      model->coef().add(j);
+      b0[j] = init_beta[j];
+    }
+  model->coef().set_Beta(b0);
+  model->set_sigsq(init_sigsq);
+  model->set_nu(init_nu);
+  for (int i = 0; i < nsweeps; ++i) {
+    model->sample_posterior();
+    const Selector &inc(model->coef().inc());
+    const Vector &beta(model->Beta());
+    for (int j = 0; j < p; ++j) {
+      out_gamma[(size_t)i * p + j] = inc[j] ? 1 : 0;
+      out_beta[(size_t)i * p + j] = beta[j];
+    }
+    out_sigsq[i] = model->sigsq();
+    out_nu[i] = model->nu();
+    const WeightedRegSuf &suf(sam->complete_data_sufficient_statistics());
+    out_sumw[i] = suf.sumw();
+    out_yty[i] = suf.yty();
+    Vector xty = suf.xty();
+    for (int j = 0; j < p; ++j) out_xty[(size_t)i * p + j] = xty[j];
   }
   REF_CATCH
 }

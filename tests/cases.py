@@ -368,3 +368,19 @@ def poisson_data(n, p, nsig, seed, max_exposure=1.0, intercept=0.5):
     exposure = np.ones(n) if max_exposure == 1.0 else rng.uniform(0.5, max_exposure, n)
     y = rng.poisson(exposure * np.exp(X @ beta)).astype(float)
     return X, y, exposure, beta
+
+
+def student_data(n, p, nsig, seed, df=3.0, outliers=0.0, scale=0.8, offset=0.0):
+    """regression data with an intercept column and t_df errors (df = inf: Gaussian; df = 1:
+    Cauchy); `outliers` of the rows shifted by +-25; `offset` added to every y"""
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((n, p))
+    X[:, 0] = 1.0
+    beta = np.zeros(p)
+    beta[:nsig] = rng.choice([-2.0, -1.0, 1.0, 1.5], nsig)
+    e = rng.standard_t(df, n) if np.isfinite(df) else rng.standard_normal(n)
+    y = X @ beta + scale * e
+    if outliers:
+        k = int(outliers * n)
+        y[rng.choice(n, k, replace=False)] += rng.choice([-1, 1], k) * 25.0
+    return X, y + offset, beta

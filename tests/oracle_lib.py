@@ -1368,6 +1368,28 @@ class Ref:
             _u8(gam), _dp(beta)))
         return dict(gamma=gam, beta=beta)
 
+    def student_run(self, X, y, mu, prec, pi, seed, init_gamma, nsweeps, init_beta=None,
+                    init_sigsq=1.0, init_nu=30.0, nu_prior=(0, 0.1, 100.0), sigma_prior=(1.0, 1.0),
+                    sigma_max=float("inf"), max_model_size=-1, max_flips=-1, allow_selection=True):
+        """TRegressionSpikeSlabSampler: nu_prior = (0, a, b) UniformModel, (1, a, b) GammaModel;
+        sigma_prior = ChisqModel(df, sigma_guess).  Per sweep gamma, beta, sigma^2, nu and the
+        complete-data suf's sum of weights, y'Wy and X'Wy."""
+        n, p = X.shape
+        gam = np.zeros((nsweeps, p), dtype=np.uint8)
+        beta = np.zeros((nsweeps, p))
+        sigsq, nu, sumw, yty = (np.zeros(nsweeps) for _ in range(4))
+        xty = np.zeros((nsweeps, p))
+        g0 = np.ascontiguousarray(init_gamma, dtype=np.uint8)
+        b0 = np.zeros(p) if init_beta is None else f64(init_beta)
+        D = C.c_double
+        self._check(self.lib.ref_student_run(
+            n, p, _dp(fcol(X)), _dp(f64(y)), _dp(f64(mu)), _dp(fcol(prec)), _dp(f64(pi)),
+            C.c_int64(max_model_size), int(max_flips), int(bool(allow_selection)),
+            D(sigma_prior[0]), D(sigma_prior[1]), D(sigma_max), int(nu_prior[0]), D(nu_prior[1]),
+            D(nu_prior[2]), C.c_uint64(seed), _u8(g0), _dp(b0), D(init_sigsq), D(init_nu),
+            int(nsweeps), _u8(gam), _dp(beta), _dp(sigsq), _dp(nu), _dp(sumw), _dp(yty), _dp(xty)))
+        return dict(gamma=gam, beta=beta, sigsq=sigsq, nu=nu, sumw=sumw, yty=yty, xty=xty)
+
     def poisson_mixtures(self, y, max_comp=16):
         """the reference table's normal-mixture approximation of NegLogGamma(n) for 1 and
         every positive count in y, asked for in the order a sampler's pass over the data

@@ -20,8 +20,20 @@ One draw() (Models/Glm/PosteriorSamplers/TRegressionSpikeSlabSampler.cpp:41-47):
      log prior(nu) + sum_i dstudent(y_i, x_i'beta, sigma, nu, log) at the new beta and
      sigma^2 (TRegression.cpp:74-86, student_fix.cpp:28-42).  The same stream as sigma^2,
      after it.
+
+rng_setup=("mt", seed) swaps only the random-number provider for the reference's layout
+(oracle/ref_driver.cpp ref_student_run, the golden fixtures tests/golden/student_*.npz): one
+MT19937-64 stream, the sampler's, seeded from GlobalRng(seed) (PosteriorSampler's
+seed_rng), read in draw() order -- the n weights, the SpikeSlabSampler draws, sigma^2, then
+the slice sampler's exponential and uniforms.  The arithmetic is the same code path in
+both modes, so the golden pins the substream mode the device is compared with.
+
+wsse="exact" forms sigma^2's sum of squares as fsum_i w_i r_i^2 over residuals
+r_i = fsum(y_i, -x_ij beta_j) instead of the reference's suf form (the yardstick of the
+device's direct sum at a large offset in y); "suf" (the default) is the reference's.
 """
 import ctypes as C
+import math
 
 import numpy as np
 from scipy.special import gammaln
@@ -102,11 +114,13 @@ def slice_draw_nu(unif, rexp1, logf, x, dx):
 
 
 class StudentOracle:
-    """One chain of TRegressionSpikeSlabSampler on the device's substreams."""
+    """One chain of TRegressionSpikeSlabSampler on the device's substreams (rng_setup=("mt", seed):
+    on the reference's one stream; seed and chain are then not read)."""
 
     def __init__(self, o, X, y, mu, prec, pi, seed, chain, gamma0, beta0=None, sigsq0=1.0,
                  nu0=30.0, nu_prior=(0, 0.1, 100.0), sigma_prior=(1.0, 1.0),
-                 sigma_max=np.inf, max_flips=-1, max_model_size=-1, allow_selection=True):
+                 sigma_max=np.inf, max_flips=-1, max_model_size=-1, allow_selection=True,
+                 rng_setup=None, wsse="suf"):
         self.o, self.L = o, o.lib
         o._declare_sss()
         L = self.L
@@ -127,17 +141,34 @@ class StudentOracle:
         self.sigma_max = float(sigma_max)
         self.max_flips, self.max_model_size = int(max_flips), int(max_model_size)
         self.allow_selection = bool(allow_selection)   # SpikeSlabSampler::allow_model_selection
+        assert wsse in ("suf", "exact")
+        self.wsse_form = wsse
+        self.mt = rng_setup is not None and rng_setup[0] == "mt"
         self.sss_rng = BoRng()
-        L.bo_rng_seed_philox(C.byref(self.sss_rng), self.seed, self.chain, 3, 0)
+        if self.mt:
+            glob = o.rng_mt(int(rng_setup[1]))
+            L.bo_rng_seed_mt(C.byref(self.sss_rng), L.bo_seed_rng(C.byref(glob)))
+        else:
+            L.bo_rng_seed_philox(C.byref(self.sss_rng), self.seed, self.chain, 3, 0)
         self.sweep = 0
         self.margin = np.inf
         self.weights = None
+        self.suf = None
 
     def _slot(self, stream, index, stride):
+        if self.mt:
+            return self.sss_rng     # the sampler's one stream, in draw() order
         r = BoRng()
         self.L.bo_rng_seed_philox(C.byref(r), self.seed, self.chain, stream, 0)
         self.L.bo_rng_slot(C.byref(r), int(index), int(stride))
         return r
+
+    def exact_wsse(self, w, gamma, beta):
+        """fsum_i w_i r_i^2, r_i = fsum(y_i, -x_ij beta_j) over the included j"""
+        inc = np.flatnonzero(gamma)
+        r = [math.fsum([float(self.y[i])] + [-float(v) for v in self.X[i, inc] * beta[inc]])
+             for i in range(self.n)]
+        return math.fsum(float(wi) * ri * ri for wi, ri in zip(w, r))
 
     def impute(self):
         o, n, s = self.o, self.n, self.sweep
@@ -160,6 +191,7 @@ class StudentOracle:
         xtx = self.X.T @ Xw
         xty = Xw.T @ self.y
         yty = float(np.dot(self.y * w, self.y))
+        self.suf = dict(sumw=float(np.sum(w)), yty=yty, xty=xty.copy())
         # SpikeSlabSampler given sigma^2
         h = L.bo_sss_create(p, _dp(fcol(xtx)), _dp(f64(xty)), 1, _dp(self.mu), _dp(fcol(self.prec)),
                             _dp(self.pi))
@@ -181,6 +213,9 @@ class StudentOracle:
         self.gamma, self.beta = g, b
         # sigma^2 | beta, w
         wsse = float(b @ xtx @ b - 2 * (b @ xty) + yty)
+        self.suf["wsse_suf"] = wsse
+        if self.wsse_form == "exact":
+            wsse = self.suf["wsse_exact"] = self.exact_wsse(w, g, b)
         DF, SS = n + self.prior_df, wsse + self.prior_ss
         rng = self._slot(SN_STREAM, self.sweep, SN_STRIDE)
         if np.isinf(self.sigma_max):

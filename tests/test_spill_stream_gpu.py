@@ -3,7 +3,8 @@ SPILL stream (device_rng.h; the oracle's bo_rng_slot): the probit / logit / Poly
 Poisson imputers (4096 / 256 / 4096 / 256 positions an observation; until round 5 the state
 draw's Kinderman-Ramage normals too, 256 a normal -- they are Box-Muller pairs now and read two
 uniforms for two draws, so the state-draw tests below only check that the switch leaves them
-alone).  At those strides that is an event of probability < 1e-40, so the
+alone), the Student-t weights (256 an observation) and its sigma^2 / nu slot (4096 a sweep,
+the slice sampler's uniforms included).  At those strides that is an event of probability < 1e-40, so the
 path is FORCED here: ba_set_slot_limit / bo_set_slot_limit let a slot serve only a few
 numbers, every slow normal and nearly every imputation then reads its spill stream, and
 the parity tests of each family run once more under that switch -- the device against the
@@ -18,6 +19,7 @@ import test_probit_gpu as tpr
 import test_state_space_gpu as tss
 import test_structural_general_gpu as tsg
 import test_structural_gpu as tst
+import test_student_gpu as tsu
 
 pytestmark = pytest.mark.gpu
 
@@ -94,3 +96,9 @@ def test_logit_imputers(oracle, small_slots):
 def test_poisson_imputer(oracle, small_slots):
     tpo.test_poisson_sweeps_match_oracle(oracle, "poisson_small_counts")
     tpo.test_poisson_sweeps_match_oracle(oracle, "poisson_exposure")
+
+
+def test_student_imputer_and_slice_sampler(oracle, small_slots):
+    tsu.test_student_sweeps_match_restatement(oracle, 0)
+    tsu.test_student_sweeps_match_restatement(oracle, 4)    # sigma^2 by adaptive rejection (out of line)
+    tsu.test_student_prior_edges(oracle, "heavy_tails")     # weights' GS branch

@@ -21,17 +21,8 @@ def relerr(a, b, floor=1e-3):
 
 
 def make_data(n, p, nsig, seed, df=3.0, outliers=0.0):
-    rng = np.random.default_rng(seed)
-    X = rng.standard_normal((n, p))
-    X[:, 0] = 1.0
-    beta = np.zeros(p)
-    beta[:nsig] = rng.choice([-2.0, -1.0, 1.0, 1.5], nsig)
-    e = rng.standard_t(df, n) if np.isfinite(df) else rng.standard_normal(n)
-    y = X @ beta + 0.8 * e
-    if outliers:
-        k = int(outliers * n)
-        y[rng.choice(n, k, replace=False)] += rng.choice([-1, 1], k) * 25.0
-    return X, y, beta
+    from cases import student_data
+    return student_data(n, p, nsig, seed, df=df, outliers=outliers)
 
 
 def make_engine(chains, seed, X, y, mu, prec, pi, g0, nu_prior=(0, 0.1, 100.0), sigma_prior=(1.0, 1.0),
@@ -143,7 +134,10 @@ def test_student_large_model_escalates(oracle):
             assert relerr(beta[c], b) < RTOL and relerr(sig[c], s2) < RTOL and relerr(nu[c], v) < RTOL, (c, s)
 
 
-def test_student_weights_match_the_imputation(oracle):
+@pytest.mark.parametrize("nu", [0.15, 0.6, 0.999, 1.0, 1.001, 4.5, 99.9])
+def test_student_weights_match_the_imputation(oracle, nu):
+    """the weights' shape (nu + 1) / 2 on both sides of 1: below it the gamma draw takes
+    its GS branch (nu < 1), at 1 and above the normal-based one"""
     n, p = 700, 12
     X, y, _ = make_data(n, p, 3, 3)
     mu, prec, pi = np.zeros(p), 0.1 * np.eye(p), np.full(p, 0.3)
@@ -153,12 +147,164 @@ def test_student_weights_match_the_imputation(oracle):
     chains, seed = 3, 77
     eng = make_engine(chains, seed, X, y, mu, prec, pi, g0)
     eng.set_state(g0, beta0, sigsq=1.7)
-    eng.student_set_nu(4.5)
+    eng.student_set_nu(nu)
     eng.student_sweep(1)
     for c in range(chains):
-        o = StudentOracle(oracle, X, y, mu, prec, pi, seed, c, g0, beta0=beta0, sigsq0=1.7, nu0=4.5)
+        o = StudentOracle(oracle, X, y, mu, prec, pi, seed, c, g0, beta0=beta0, sigsq0=1.7, nu0=nu)
         w = o.impute()
         assert relerr(eng.student_get_weights(c), w, floor=1e-300) < 1e-12
+
+
+def check_parity(eng, ora, nsweeps, each=None):
+    """nsweeps single sweeps of the engine against the restatements ora (chain -> StudentOracle)
+    at the file's bars; each(s, gamma, beta, sigsq, nu) sees the engine's state after sweep s.
+    Returns the checked chains' nu draws."""
+    nus = {c: [] for c in ora}
+    for s in range(nsweeps):
+        eng.student_sweep(1)
+        gam, beta, sig = eng.get_states()
+        nu = eng.student_get_nu()
+        if each is not None:
+            each(s, gam, beta, sig, nu)
+        for c, o in ora.items():
+            g, b, s2, v = o.draw()
+            assert np.array_equal(gam[c], g), (c, s)
+            assert relerr(beta[c], b) < RTOL, (c, s)
+            assert relerr(sig[c], s2) < RTOL, (c, s)
+            assert relerr(nu[c], v) < RTOL, (c, s)
+            nus[c].append(nu[c])
+    margin = eng.student_get_margin()
+    for c, o in ora.items():
+        assert margin[c] > 1e-9, (c, margin[c])
+        assert abs(margin[c] - o.margin) <= 1e-6 * max(o.margin, 1e-12) + 1e-12
+    return nus
+
+
+def test_student_more_than_256_variables(oracle):
+    """p = 520: the included-variable compaction runs in three chunks of 256 (a ballot and a
+    prefix sum carried by base), with included variables on both sides of 256 and 512"""
+    n, p = 600, 520
+    rng = np.random.default_rng(520)
+    X = rng.standard_normal((n, p))
+    X[:, 0] = 1.0
+    sig_idx = [0, 3, 255, 256, 300, 511, 512, 519]
+    beta = np.zeros(p)
+    beta[sig_idx] = [1.0, -1.5, 1.5, -1.0, 2.0, -2.0, 1.0, 1.5]
+    y = X @ beta + 0.8 * rng.standard_t(3.0, n)
+    mu, prec = np.zeros(p), 0.1 * np.eye(p)
+    pi = np.full(p, 0.01)
+    pi[sig_idx] = 0.9
+    g0 = np.zeros(p, np.uint8)
+    g0[sig_idx] = 1
+    chains, seed = 2, 52
+    eng = make_engine(chains, seed, X, y, mu, prec, pi, g0)
+    ora = {c: StudentOracle(oracle, X, y, mu, prec, pi, seed, c, g0) for c in range(chains)}
+
+    def straddles(s, gam, beta, sig, nu):
+        for c in range(chains):
+            inc = np.flatnonzero(gam[c])
+            assert inc.min() < 256 and np.any((inc >= 256) & (inc < 512)) and inc.max() >= 512, (c, s)
+    check_parity(eng, ora, 5, straddles)
+
+
+@pytest.mark.parametrize("n", [37, 256, 257])
+def test_student_small_n_and_block_edges(oracle, n):
+    """n below one impute block (idle lanes in every per-chain reduction), exactly one block,
+    and one past it"""
+    p = 6
+    X, y, _ = make_data(n, p, 2, 400 + n)
+    mu, prec, pi = np.zeros(p), 0.1 * np.eye(p), np.full(p, 0.5)
+    g0 = np.zeros(p, np.uint8)
+    g0[:2] = 1
+    chains, seed = 6, 60 + n
+    eng = make_engine(chains, seed, X, y, mu, prec, pi, g0)
+    ora = {c: StudentOracle(oracle, X, y, mu, prec, pi, seed, c, g0) for c in (0, chains - 1)}
+    check_parity(eng, ora, 15)
+
+
+# the prior-edge cases of tests/golden/make_golden_student.py, on the device's substreams:
+# data (n, p, nsig, seed, error df), starting nu
+PRIOR_EDGES = {
+    "heavy_tails": ((300, 8, 3, 106, 0.7), 2.0),     # nu below 1
+    "gaussian": ((400, 8, 3, 107, np.inf), 60.0),    # nu against Uniform(0.1, 100)'s bound
+}
+
+
+@pytest.mark.parametrize("name", sorted(PRIOR_EDGES))
+def test_student_prior_edges(oracle, name):
+    from cases import student_data
+    (n, p, nsig, dseed, df), nu0 = PRIOR_EDGES[name]
+    X, y, _ = student_data(n, p, nsig, dseed, df=df)
+    mu, prec, pi = np.zeros(p), 0.1 * np.eye(p), np.full(p, 5.0 / p)
+    g0 = np.zeros(p, np.uint8)
+    g0[:2] = 1
+    chains, seed = 4, 41
+    eng = make_engine(chains, seed, X, y, mu, prec, pi, g0)
+    eng.student_set_nu(nu0)
+    ora = {c: StudentOracle(oracle, X, y, mu, prec, pi, seed, c, g0, nu0=nu0) for c in (0, chains - 1)}
+    nus = check_parity(eng, ora, 60)
+    for c, v in nus.items():
+        if name == "heavy_tails":
+            assert min(v) < 1.0, (c, min(v))
+        else:
+            assert max(v) > 90.0, (c, max(v))
+
+
+def test_student_many_chains(oracle):
+    """1024 chains, draw for draw at the first, a middle and the last (high blockIdx.y in the
+    impute grid, late workgroups of the sigma^2 / nu kernel)"""
+    n, p = 300, 10
+    X, y, _ = make_data(n, p, 3, 1024)
+    mu, prec, pi = np.zeros(p), 0.1 * np.eye(p), np.full(p, 0.5)
+    g0 = np.zeros(p, np.uint8)
+    g0[:2] = 1
+    chains, seed = 1024, 88
+    eng = make_engine(chains, seed, X, y, mu, prec, pi, g0)
+    ora = {c: StudentOracle(oracle, X, y, mu, prec, pi, seed, c, g0) for c in (0, 511, 1023)}
+    check_parity(eng, ora, 10)
+
+
+def test_student_wsse_at_a_large_offset(oracle, capsys):
+    """y = 1e4 + t_3 noise with an intercept: y'Wy is ~1e8 times the weighted sum of squared
+    errors.  The device sums w_i r_i^2 directly; the reference's suf form
+    beta'X'WX beta - 2 beta'X'Wy + y'Wy loses about log10(y'Wy / wsse) digits there.  Without a
+    sigma limit sigma^2 is proportional to SS, so holding the device's sigma^2 to 1e-10 of the
+    restatement's exactly summed form (wsse="exact") measures the sum alone."""
+    from cases import student_data
+    n, p = 400, 6
+    X, y, _ = student_data(n, p, 3, 9, offset=1e4)
+    mu, prec, pi = np.zeros(p), 0.1 * np.eye(p), np.full(p, 0.5)
+    mu[0], pi[0] = 1e4, 1.0
+    g0 = np.zeros(p, np.uint8)
+    g0[:2] = 1
+    beta0 = np.zeros(p)
+    beta0[0] = 1e4
+    chains, seed, nsw, bar = 4, 43, 12, 1e-10
+    eng = make_engine(chains, seed, X, y, mu, prec, pi, g0)
+    eng.set_state(g0, beta0)
+    ora = {c: StudentOracle(oracle, X, y, mu, prec, pi, seed, c, g0, beta0=beta0, wsse="exact")
+           for c in (0, chains - 1)}
+    eps = np.finfo(float).eps
+    suf_err, dev_err = [], []
+    for s in range(nsw):
+        eng.student_sweep(1)
+        gam, beta, sig = eng.get_states()
+        nu = eng.student_get_nu()
+        for c, o in ora.items():
+            g, b, s2, v = o.draw()
+            assert np.array_equal(gam[c], g), (c, s)
+            assert relerr(beta[c], b) < RTOL and relerr(nu[c], v) < RTOL, (c, s)
+            dev_err.append(abs(sig[c] - s2) / s2)
+            assert dev_err[-1] <= bar, (c, s, dev_err[-1])
+            ss = o.suf["wsse_exact"] + o.prior_ss
+            # the case still discriminates: the suf form's expected error is 100 x the bar
+            assert eps * o.suf["yty"] / ss >= 100 * bar, (c, s)
+            suf_err.append(abs(o.suf["wsse_suf"] + o.prior_ss - ss) / ss)
+    # ... and its measured error is too
+    assert max(suf_err) >= 100 * bar, max(suf_err)
+    with capsys.disabled():
+        print("\nlarge offset: sigma^2 relative error, device %.2e (max); suf form %.2e max, %.2e median"
+              % (max(dev_err), max(suf_err), float(np.median(suf_err))))
 
 
 def _gibbs_numpy(X, y, prec, prior_df, guess, nu_prior, iters, seed):
