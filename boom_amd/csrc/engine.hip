@@ -2,121 +2,21 @@
 // engine, assembles priors the way BregVsSampler's constructors do, launches
 // the kernels and turns per-chain status words back into the reference's
 // error messages.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <limits>
-#include <string>
-#include <unordered_map>
-#include <vector>
-
-#include "../../include/boom_amd.h"
-#include "kalman_params.h"
-#include "ktimer.h"
-#include "probit_params.h"
-#include "ssvs_params.h"
-#include "student_params.h"
+#include "engine_internal.h"
 
 namespace boom_amd {
-// ssvs_kernel.hip
-hipError_t launch_ssvs_sweep(hipStream_t stream, const SsvsParams &P, int nsweeps);
-// ssvs_big_kernel.hip
-hipError_t launch_ssvs_big(hipStream_t stream, const SsvsParams &P, int nsweeps);
-// ssvs_adaptive_kernel.hip
-hipError_t launch_ssvs_adaptive(hipStream_t stream, const SsvsParams &P, int nsweeps);
-hipError_t launch_ssvs_logp(hipStream_t stream, const SsvsParams &P,
-                            const uint8_t *gammas, int ngamma, double *out,
-                            int *status_out);
-hipError_t launch_lds_exchange_order(hipStream_t stream, int *bad_device);
-hipError_t launch_ssvs_reduce_summaries(hipStream_t stream, const SsvsParams &P,
-                                        double *out);
-// suf_kernel.hip
-int suf_row_slices(int64_t n, int p);
-int launch_suf_from_xy(hipStream_t stream, int64_t n, int p, const double *X,
-                       const double *y, double *xtx, double *xty,
-                       double *scalars /* yty, sumy */, double *xsum,
-                       double *planes /* suf_row_slices(n, p) * p * p doubles, or null */);
-// kalman_kernel.hip
-hipError_t launch_ssm_simsmooth(hipStream_t stream, const SsParams &P, int draw_variances);
-hipError_t launch_ssm_forecast(hipStream_t stream, const SsParams &P, int horizon, const double *newX,
-                               uint64_t *pos_forecast, double *out);
-hipError_t launch_probit_impute(hipStream_t stream, const ProbitParams &P, double *planes);
-hipError_t launch_student_impute(hipStream_t stream, const StudentParams &P, const double *Xsq,
-                                 const double *slab_precision, double *xtz, double *v_diag, double *planes);
-hipError_t launch_student_sigma_nu(hipStream_t stream, const StudentParams &P);
-hipError_t launch_logit_impute(hipStream_t stream, const ProbitParams &P, const double *Xsq,
-                               const double *slab_precision, double *v_diag, double *planes,
-                               int polya_gamma);
-// xtwx_cols_kernel.hip
-hipError_t launch_ssvs_big_logp(hipStream_t stream, const SsvsParams &P, int kcap, const uint8_t *gammas,
-                                const int *which, int nwhich, double *model_ws, double *xs_ws, double *out,
-                                int *status_out);
-hipError_t launch_predict(hipStream_t stream, const double *trace_k, const uint16_t *rec_idx,
-                          const double *rec_beta, int stride, int cap, int first_draw, int ndraws,
-                          int chains, int p, const double *newX, int nnew, double *out);
-int xtwx_cols_planes(int64_t n);
-int xte_planes(int64_t n);
-hipError_t launch_xtwx_cols(hipStream_t stream, const double *X, int64_t n, int p, const double *w,
-                            const int32_t *req, int R, const double *base, double *V,
-                            uint32_t *valid, int words, double *planes);
-hipError_t launch_xtwx_cols_start(hipStream_t stream, const uint8_t *gamma, int chains, int p,
-                                  int32_t *req, int32_t *count, uint32_t *valid, int words);
-hipError_t launch_square(hipStream_t stream, const double *x, size_t count, double *out);
-hipError_t launch_kalman_simsmooth(hipStream_t stream, const SsParams &P,
-                                   int draw_level);
-hipError_t launch_kalman_main(hipStream_t stream, const SsParams &P, int draw_level);
-hipError_t launch_kalman_xte(hipStream_t stream, const SsParams &P, bool planes_only);
-hipError_t launch_kalman_prepare(hipStream_t stream, const SsParams &P, int draw_level);
-hipError_t launch_ss_round(hipStream_t stream, const SsvsParams &P, const SsParams &S, const SsRoundParams &F,
-                           int *max_resident);
-size_t ss_round_lds(int p, int kcap);
-hipError_t launch_ss_forecast(hipStream_t stream, const SsParams &P, int horizon, const double *newX,
-                              uint64_t *pos_forecast, double *out);
-}  // namespace boom_amd
 
-using namespace boom_amd;
-
-namespace {
-
-thread_local std::string g_error = "";
+static thread_local std::string g_error = "";
 
 int fail(int code, const std::string &msg) {
   g_error = msg;
   return code;
 }
 
-#define HIP_TRY(expr)                                                       \
-  do {                                                                      \
-    hipError_t err__ = (expr);                                              \
-    if (err__ != hipSuccess) {                                              \
-      return fail(BA_E_HIP, std::string(#expr) + ": " +                     \
-                                hipGetErrorString(err__));                  \
-    }                                                                       \
-  } while (0)
+}  // namespace boom_amd
 
-template <class T>
-struct DevBuf {
-  T *ptr = nullptr;
-  size_t count = 0;
-  ~DevBuf() { release(); }
-  void release() {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    count = 0;
-  }
-  hipError_t resize(size_t n) {
-    if (n == count && ptr) return hipSuccess;
-    release();
-    if (n == 0) return hipSuccess;
-    hipError_t e = hipMalloc((void **)&ptr, n * sizeof(T));
-    if (e == hipSuccess) count = n;
-    return e;
-  }
-};
+namespace {
+
 
 const char *status_message(int st) {
   switch (st) {
@@ -162,40 +62,8 @@ int status_code(int st) {
 
 }  // namespace
 
-// ba_set_kernel_timing: the event pairs of the launches since the last read
-struct KtSpan { int cls; hipEvent_t a, b; };
-struct KTimer {
-  std::vector<KtSpan> spans;
-  std::vector<hipEvent_t> open;   // begin events by class (launches do not nest within a class)
-  std::vector<hipEvent_t> pool;
-  double ms[KT_CLASSES] = {};
-  int64_t launches[KT_CLASSES] = {};
-  hipEvent_t get() {
-    if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
-    hipEvent_t e = nullptr;
-    (void)hipEventCreate(&e);
-    return e;
-  }
-  // fold the finished spans into the totals (the caller has synchronised the stream)
-  void collect() {
-    for (const KtSpan &sp : spans) {
-      float t = 0.f;
-      if (hipEventElapsedTime(&t, sp.a, sp.b) == hipSuccess) { ms[sp.cls] += t; ++launches[sp.cls]; }
-      pool.push_back(sp.a);
-      pool.push_back(sp.b);
-    }
-    spans.clear();
-  }
-  ~KTimer() {
-    for (const KtSpan &sp : spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
-    for (hipEvent_t e : open) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : pool) (void)hipEventDestroy(e);
-  }
-};
-namespace {
-thread_local KTimer *g_kt = nullptr;   // the timer of the engine whose entry point this thread is in
-}
 namespace boom_amd {
+thread_local KTimer *g_kt = nullptr;   // the timer of the engine whose entry point this thread is in
 bool kt_active() { return g_kt != nullptr; }
 void kt_mark(hipStream_t stream, int cls, bool begin) {
   KTimer *k = g_kt;
@@ -215,258 +83,12 @@ void kt_mark(hipStream_t stream, int cls, bool begin) {
 }
 }  // namespace boom_amd
 
-struct ba_engine {
-  ba_config cfg{};
-  bool kt_enabled = false;
-  bool kt_overlap = false;   // (timing on, consecutive sweep launches still overlap: ba_set_kernel_timing(e, 2))
-  KTimer kt;
-  hipStream_t stream = nullptr;
-  int p = 0;
-  int cu_count = 256;
-  size_t lds_per_cu = 160 * 1024;
-
-  // ---- host copies (RegSuf + priors)
-  bool have_suf = false, have_slab = false, have_spike = false,
-       have_sigma = false;
-  std::vector<double> xtx, xty, xsum;
-  double yty = 0, n = 0, sumy = 0;
-  std::vector<double> b, ominv, pi;
-  int64_t max_model_size = -1;
-  double prior_df = 0, prior_ss = 0, sigma_guess = 0;
-  double sigma_max = std::numeric_limits<double>::infinity();
-  int max_flips = -1;  // < 0: p
-  double swap_threshold = 0.8;
-  int draw_beta = 1, draw_sigma = 1;
-  bool device_dirty = true;   // V/A/b/logpi/cm need (re)upload
-  bool state_ready = false;
-
-  // ---- device: shared
-  DevBuf<double> dV, dA, db, dl1, dl0, dpi, dxty, dscal /* yty, n */;
-  DevBuf<int32_t> dcm_start, dcm_idx;
-  DevBuf<double> dcm_cor;
-  bool cm_enabled = false;
-  // ---- device: per chain
-  DevBuf<uint8_t> dgamma;
-  DevBuf<double> dbeta, dsigsq;
-  DevBuf<uint16_t> dperm;
-  DevBuf<uint64_t> dpos;
-  DevBuf<int32_t> dstatus, dfail, dtodo, dmaxk, dtrace_idx;
-  DevBuf<uint32_t> dinc;
-  DevBuf<double> dbsum, dbsumsq, dacc, dsummary;
-  DevBuf<double> dtr_sig, dtr_logp, dtr_k;
-  DevBuf<uint16_t> drec_idx;  // recorded draws (ba_enable_draws)
-  DevBuf<double> drec_beta;
-  DevBuf<double> dmodel;  // per-chain model scratch (scalar-cache reads)
-  DevBuf<double> dtab_lp;   // per-chain proposal table
-  DevBuf<uint8_t> dtab_kind;
-  DevBuf<int32_t> dtab_tag, dmodel_tag;
-  DevBuf<int32_t> dran;  // catch-up launches of the state-space path: sweeps done per chain
-  bool table_ok = false;  // nothing but ba_sweep launches since the tables were built
-  bool model_ok = false;  // nothing that changes a model's factors since the last sweep launch
-  int trace_stride = 0;
-  // scratch for suf build
-  DevBuf<double> dX, dy, dxtx, dxsum, dsufscal;
-
-  int kcap = 0;
-  int waves = 1;  // wavefronts per chain
-  // ba_draw_next: the look-ahead batch.  la_avail draws are recorded on the
-  // device, la_served of them have been handed out; the snapshot is the chains'
-  // state (and the running summaries) at the start of the batch, which is what
-  // a rewind restores before replaying the la_served draws already seen.
-  int la_len = 1, la_avail = 0, la_served = 0;
-  // host copies of the batch's record for the chains the caller reads (the
-  // per-iteration loop reads chain 0 after every draw: one set of copies per
-  // batch instead of per call); la_synced: the batch's launch has been waited for
-  // and its chain statuses checked
-  struct LaRows { std::vector<double> k, sig, beta; std::vector<uint16_t> idx; };
-  std::unordered_map<int64_t, LaRows> la_cache;
-  bool la_synced = false;
-  // Overlapping look-ahead batches: the record holds two batches (halves la_slot and
-  // la_slot ^ 1 of 2 la_len rows), the batch after the one being served is launched as soon
-  // as serving starts (la_ahead) and the launches hand chains over (pipelined sweeps); each
-  // batch's workgroups save their chain's state on entry (snapshot set = half) for rewinds.
-  bool la_pipe = true;        // allowed (off for good after a batch had to be redone the old way)
-  bool la_cur_piped = false;  // the batch being served was launched that way
-  bool la_ahead = false;
-  int la_slot = 0;
-  hipEvent_t la_done[2] = {nullptr, nullptr};
-  DevBuf<uint8_t> snap_gamma;
-  DevBuf<double> snap_beta, snap_sigsq, snap_bsum, snap_bsumsq, snap_acc;
-  DevBuf<uint16_t> snap_perm;
-  DevBuf<uint64_t> snap_pos;
-  DevBuf<int32_t> snap_fail;
-  DevBuf<uint32_t> snap_inc;
-  int rec_cap = 64;  // variables per recorded draw (ba_enable_draws)
-  // HBM-resident path for models of more than 64 variables (ssvs_big_kernel.hip):
-  // active once a chain has outgrown the LDS kernel, capacity grows on demand
-  bool big_active = false;
-  int big_kcap = 0;
-  DevBuf<double> dbig_model, dbig_xs;
-  // ba_set_tuning overrides (0 / -1: the engine chooses)
-  int tune_waves = 0, tune_walk_policy = -1, tune_kcap_start = 0;
-  // SpikeSlabSampler (sigma^2 given) mode
-  int cur_mode = 0;          // mode of the launches in flight (0 BregVs, 1 SSS)
-  int sss_slab_scales = 1;   // slab precision = Omega^{-1} / sigma^2
-  int sss_max_flips = -1;    // limits only when > 0 (SpikeSlabSampler.cpp:77)
-  double v_scale = 1.0;      // V = Omega^{-1} + v_scale * XtX currently on the device
-  double v_scale_want = 1.0;
-  DevBuf<uint64_t> dpos_sss;
-  uint64_t seed = 0;
-  // AdaptiveSpikeSlabRegressionSampler (mode 2): rates, iteration counts, options
-  DevBuf<double> dada_birth, dada_death, dada_ws;
-  DevBuf<uint64_t> dada_iter, dpos_ada;
-  int ada_max_flips = 100;
-  double ada_step = .001, ada_target = .345;
-
-  // ---- state space (bsts local level + regression)
-  bool ss_mode = false, ss_level_set = false, ss_initialized = false;
-  int T = 0;
-  DevBuf<double> dss_y, dss_X, dss_scratch;
-  // The callers' loop is "one round, then read chain 0": what the accessors copy goes
-  // through ONE pinned staging buffer per call (a batch of asynchronous copies, one
-  // synchronisation) instead of one blocking copy per field, and a ba_sync() that follows
-  // a clean ba_sync() with no call in between that could have enqueued or changed anything
-  // is free (api_seq counts such calls, clean_seq remembers the last clean check).
-  void *pinned = nullptr;
-  size_t pinned_bytes = 0;
-  uint64_t api_seq = 1, clean_seq = 0;
-  int api_depth = 0;   // calls other than accessors in progress (they may enqueue after an inner ba_sync)
-  // lane-major copies for kalman_lm_kernel (kalman_params.h): local level, T <= LM_TP
-  DevBuf<double> dss_yt, dss_Xt;
-  DevBuf<uint32_t> dss_obs_mask;
-  DevBuf<uint8_t> dss_obs;
-  DevBuf<double> dxty_c, dyty_c, dnobs_c;       // per-chain regression suf
-  DevBuf<double> dlev_sigsq, dlev_n, dlev_sumsq;
-  DevBuf<uint64_t> dpos_level, dpos_state, dpos_forecast;
-  // kalman_prepare_kernel (level variance + normals of the next state draw) runs on a
-  // second stream beside the X'e GEMM and the SSVS launch
-  hipStream_t stream2 = nullptr;
-  hipEvent_t ev_state = nullptr, ev_prep[2] = {nullptr, nullptr};
-  int ss_zbuf = 0;   // the normals buffer the next state draw reads
-  // pipelined sweeps: consecutive ba_sweep launches alternate between `stream` and
-  // pipe_stream and hand chains over through a ring of four queues (ssvs_kernel.hip)
-  hipStream_t pipe_stream = nullptr;
-  hipEvent_t pipe_ev[4] = {}, pipe_join_ev = nullptr;
-  DevBuf<int32_t> dpipe_q, dpipe_err;
-  bool pipe_on = false;      // the last thing enqueued was a pipelined sweep launch
-  bool pipe_unchecked = false;   // a pipelined launch has gone out since the error word was last read
-  int pipe_k = 0;            // launches in the current pipeline
-  bool pipe_groups = false;  // ... which are the chain GROUPS of an engine of more chains than the machine holds
-  DevBuf<int32_t> dprep_n;
-  DevBuf<uint64_t> dprep_pos_state, dprep_pos_level;
-  DevBuf<double> dprep_level;
-  DevBuf<double> dxte_planes;   // split-K planes of the X'e GEMM
-  double level_prior_df = 0, level_prior_ss = 0;
-  double level_sigma_max = std::numeric_limits<double>::infinity();
-  double ss_a0 = 0, ss_P0 = 1, ss_initial_level_sigsq = 1;
-  // BinomialProbitSpikeSlabSampler (probit_kernel.hip): data on the device, the
-  // latent sums z (chains x n), imputations done so far
-  bool probit_mode = false;
-  int64_t probit_n = 0;
-  int probit_clt = 5;
-  uint64_t probit_sweep = 0;
-  DevBuf<double> dprob_X, dprob_y, dprob_nt, dprob_z;
-  // BinomialLogitSpikeSlabSampler: the same buffers plus the observations' total
-  // precisions (chains x n) and every chain's own V = slab precision + X'WX
-  bool logit_mode = false;
-  int logit_imputer = 0;           // 0: the reference's auxiliary mixture, 1: Polya-Gamma
-  // PoissonRegressionSpikeSlabSampler: the logit path's machinery (every chain's own V a
-  // vector at a time) with its own imputation kernel and SpikeSlabSampler's shuffle;
-  // dprob_nt holds the exposures; the reference table's mixtures by count
-  bool poisson_mode = false;
-  bool poisson_mix_set = false;
-  std::vector<int64_t> poisson_y;             // host copy of the counts (to map them to mixtures)
-  DevBuf<int32_t> dpois_off, dpois_obs;
-  DevBuf<double> dpois_mu, dpois_sigma, dpois_logw;
-  int poisson_mix_one = -1;
-  // TRegressionSpikeSlabSampler (student_kernel.hip): the logit path's machinery (logit_mode
-  // is set with it) with its own imputation, sigma^2 per chain and the nu draw; per chain nu,
-  // the slice sampler's suggested_dx, the smallest slice margin, the recorded nu path; the
-  // u_i = (r_i / sigma)^2 of the last draw (chains x n)
-  bool student_mode = false;
-  bool student_allow_selection = true;   // (ba_student_allow_model_selection)
-  int student_nu_kind = STUDENT_NU_UNIFORM;
-  double student_nu_a = 0.1, student_nu_b = 100.0;
-  DevBuf<double> dstu_nu, dstu_dx, dstu_margin, dstu_u, dstu_nu_rec;
-  int slot_limit = 0;              // (ba_set_slot_limit)
-  DevBuf<double> dlogit_w, dlogit_V;
-  // ... V built a vector at a time (xtwx_cols_kernel.hip): the squared design matrix
-  // (for the diagonal), the diagonals (chains x p), which vectors hold this sweep's
-  // values (bits, logit_words words per chain), the request list (chain, variable) and
-  // its length, the variable a parked chain waits for, the GEMM's split-K planes
-  DevBuf<double> dlogit_Xsq, dlogit_vdiag, dlogit_planes;
-  DevBuf<uint32_t> dlogit_valid;
-  DevBuf<int32_t> dlogit_req, dlogit_cnt, dcol_request;
-  int logit_words = 0;
-  int64_t logit_req_batch = 0;     // requests per GEMM launch (bounds the planes)
-  int64_t logit_cols_built = 0, logit_cols_requested = 0, logit_replays = 0;   // (diagnostics)
-  // structural state (a list of state models, ssm_kernel.hip) instead of the local level
-  bool ssm_set = false;
-  SsgSpec ssg{};                   // the host's copy of the specification
-  DevBuf<uint8_t> dssg_spec;       // ... and the device's
-  double ssg_initial_sigsq[SSG_MAX_VAR] = {};
-  double ssg_initial_phi[SSG_MAX_AR][AR_MAX] = {};
-  // the template of ba_ss_set_structural (level / slope / seasonal -> variance index, -1: none)
-  int ssg_template_var[3] = {-1, -1, -1};
-  int ssg_template_ar = -1;        // ... and the block ba_ss_add_ar appended
-  int ssg_kernel_choice = 1;       // (ba_ss_set_tuning: 0 general, 1 the default choice, 3 shape-specialised)
-  // the local-level rounds of a call as one persistent launch (ss_round_kernel.hip); the
-  // tile words of its X'e step, zeroed before every launch; how many chains' workgroups the
-  // device holds at once, by launch capacity (0: not asked yet, < 0: the kernel does not fit)
-  bool ss_round_enabled = true;    // (ba_ss_set_tuning 4 / 5: the separate launches of rounds 1-4 / this)
-  DevBuf<int32_t> dround_ctl, dround_members, dround_reg;
-  int ss_round_resident[4] = {0, 0, 0, 0};
-  bool round_debug = false;        // (ba_ss_set_tuning 6 / 7: the round kernel's notes of a debugging session on / off)
-  DevBuf<int32_t> dround_debug;    // ... on this engine's device
-  DevBuf<double> dssm_sigsq, dssm_n, dssm_ss, dssm_work;   // chains x SSG_MAX_VAR (sigsq, n, ss)
-  DevBuf<double> dar_phi, dar_suf;                         // chains x SSG_MAX_AR x (AR_MAX | AR_SUF_STRIDE)
-  DevBuf<uint64_t> dpos_var;                               // chains x SSG_MAX_VAR
-  // ---- look-ahead on the bsts path (ba_ss_set_lookahead / ba_ss_draw_next): a batch of
-  // `len` sweep rounds per enqueue, every round's draw recorded on the device -- gamma,
-  // beta, sigma^2, the state models' variances and coefficients for EVERY chain, the
-  // state path for the registered chains -- and handed out one per call.  Two halves:
-  // the batch after the one being served is enqueued as soon as serving starts.  Any
-  // entry point that is not served from the record first puts the chains where the
-  // caller has seen them (ss_la_settle: the snapshot of the batch's start, replayed up
-  // to the draw being served), so the look-ahead is unobservable.
-  struct SsLa {
-    int len = 0;                // rounds per batch at most (<= 1: off)
-    // rounds per batch NOW.  A caller whose loop reads something the record does not hold
-    // (another chain's state path, sufficient statistics, a forecast) or changes something
-    // (priors under the sampler) after every draw pays a rewind + replay of the batch each
-    // time: so a settle halves the batch, a batch served to its end doubles it again (up to
-    // len); at one round per call the look-ahead is off and is tried again after
-    // `probe_wait` calm draws (16, doubling while the tries keep failing).
-    int cur = 0, calm = 0, probe_wait = 16;
-    bool clean = true;          // nothing has settled the batch being served
-    int ahead_len = 0;          // rounds of the batch that is running ahead
-    int avail = 0, served = 0, slot = 0;
-    bool ahead = false;         // the next batch is enqueued (half slot ^ 1)
-    bool synced = false;        // the batch being served is complete and its chains sound
-    bool busy = false;          // (a settle in progress: entry points it calls do not settle again)
-    hipEvent_t done[2] = {nullptr, nullptr};
-    std::vector<int32_t> reg{0};            // chains whose state path is recorded (always the size of dreg / rstate's rows)
-    std::vector<int32_t> want;              // ... and the ones asked for since: ss_la_alloc takes them into reg, as far as the record has room
-    DevBuf<int32_t> dreg;
-    DevBuf<double> lev_used;                // the level variance every chain's last state draw used
-    size_t nvar = 0, nphi = 0, state_doubles = 0;   // per chain and round
-    DevBuf<uint8_t> rgamma;                 // [slot][chain][round][p]
-    DevBuf<double> rbeta, rsig, rvar, rphi; // [slot][chain][round][...]
-    DevBuf<double> rstate;                  // [slot][registered chain][round][state_doubles]
-    DevBuf<double> snap;                    // the state-space half of the chain state, two sets
-    DevBuf<uint64_t> snap_pos;
-    size_t snap_doubles = 0, snap_words = 0;
-    struct Rows { std::vector<uint8_t> gamma; std::vector<double> beta, sig, var, phi, state; bool has_state = false; };
-    std::unordered_map<int64_t, Rows> cache;
-  } ssla;
-};
-
-namespace {
+namespace boom_amd {
 
 // CorrelationMap::fill, Models/Glm/PosteriorSamplers/CorrelationMap.cpp:41-59
-void build_correlation_map(const ba_engine &e, std::vector<int32_t> &start,
-                           std::vector<int32_t> &idx,
-                           std::vector<double> &cor) {
+static void build_correlation_map(const ba_engine &e, std::vector<int32_t> &start,
+                                  std::vector<int32_t> &idx,
+                                  std::vector<double> &cor) {
   const int p = e.p;
   const double n = e.n;
   std::vector<double> xbar(p), sd(p);
@@ -501,7 +123,7 @@ void build_correlation_map(const ba_engine &e, std::vector<int32_t> &start,
 // stops at a sweep boundary and is resumed by ba_sync() with the next size
 // (escalate()), and the capacity follows the largest model seen.  A
 // max_model_size prior caps it; ba_config.max_model_size_hint pins it.
-int lds_cap(const ba_engine &e) {   // largest capacity whose LDS set fits a CU
+static int lds_cap(const ba_engine &e) {   // largest capacity whose LDS set fits a CU
   int k = 64;
   while (k > 16 && ssvs_lds_layout(e.p, k).total > e.lds_per_cu) k -= 16;
   return k;
@@ -512,7 +134,7 @@ int cap_limit(const ba_engine &e) {
   const int k = (int)std::min<int64_t>(64, ((need + 15) / 16) * 16);
   return std::min(k, lds_cap(e));
 }
-int choose_kcap(const ba_engine &e) {
+static int choose_kcap(const ba_engine &e) {
   const int limit = cap_limit(e);
   if (e.cfg.max_model_size_hint > 0) {
     const int k = (int)std::min<int64_t>(64, (((int64_t)e.cfg.max_model_size_hint + 15) / 16) * 16);
@@ -543,7 +165,7 @@ int choose_waves(const ba_engine &e, int kcap) {
   // 512 chains 144 / 144, 1024 167 / 172, 2048 279 / 304, 4096 545 / 590).
   // (the local-level round only: with the structural kernel behind it the same choice makes
   // THAT kernel slower -- 5.72 vs 5.06 ms per round at m = 13 -- for reasons not understood)
-  if (e.ss_mode && !e.ssm_set) return 1;
+  if (e.data_kind == DATA_STATE_SPACE && !e.ssm_set) return 1;
   return 2;
 }
 
@@ -670,13 +292,13 @@ void fill_params(ba_engine *e, SsvsParams &P) {
   P.l1 = e->dl1.ptr;
   P.l0 = e->dl0.ptr;
   P.pi = e->dpi.ptr;
-  if (e->ss_mode) {
+  if (e->data_kind == DATA_STATE_SPACE) {
     P.xty = e->dxty_c.ptr;
     P.xty_stride = e->p;
     P.yty = e->dyty_c.ptr;
     P.nobs = e->dnobs_c.ptr;
     P.suf_stride = 1;
-  } else if ((e->probit_mode || e->logit_mode) && e->dxty_c.count) {
+  } else if (latent_data(e->data_kind) && e->dxty_c.count) {
     P.xty = e->dxty_c.ptr;      // X'z of every chain's own imputation
     P.xty_stride = e->p;
     P.yty = e->dscal.ptr;
@@ -718,7 +340,7 @@ void fill_params(ba_engine *e, SsvsParams &P) {
   P.table_keep = e->table_ok ? 1 : 0;
   P.model_tag = e->dmodel_tag.ptr;
   P.model_keep = e->model_ok ? 1 : 0;
-  P.suf_changed = (e->ss_mode || e->probit_mode || e->logit_mode) ? 1 : 0;
+  P.suf_changed = (e->data_kind == DATA_STATE_SPACE || latent_data(e->data_kind)) ? 1 : 0;
   P.run_limit = 0;
   P.ran = nullptr;
   P.model_scratch_stride = (int64_t)ssvs_scalar_layout(64).total;
@@ -741,12 +363,12 @@ void fill_params(ba_engine *e, SsvsParams &P) {
     P.cm_start = nullptr;
     P.max_flips = (e->sss_max_flips > 0) ? std::min(e->sss_max_flips, e->p) : e->p;
   }
-  if (e->cur_mode == 1 && e->student_mode && !e->student_allow_selection)
+  if (e->cur_mode == 1 && e->data_kind == DATA_STUDENT && !e->student_allow_selection)
     P.max_flips = 0;   // SpikeSlabSampler::allow_model_selection(false): no indicator draws
-  if (e->cur_mode == 1 && e->logit_mode && e->dlogit_V.count) {
+  if (e->cur_mode == 1 && column_service(e->data_kind) && e->dlogit_V.count) {
     // BinomialLogitSpikeSlabSampler: the sampler's own shuffle, every chain's own V
     // (which moves with the latent data: factors and tables are rebuilt)
-    P.mode = (e->poisson_mode || e->student_mode) ? 1 : 2;   // (the Poisson and Student samplers drive the plain SpikeSlabSampler)
+    P.mode = e->data_kind == DATA_LOGIT ? 2 : 1;   // (the Poisson and Student samplers drive the plain SpikeSlabSampler)
     P.V = e->dlogit_V.ptr;
     P.v_chain_stride = (int64_t)e->p * e->p;
     P.model_keep = 0;
@@ -791,13 +413,13 @@ void fill_params(ba_engine *e, SsvsParams &P) {
 // ---- models of more than 64 variables: the HBM-resident kernel -------------------
 enum { BIG_KCAP_MAX = 1024 };
 // largest capacity that can ever be needed (0: the LDS kernel covers everything)
-int big_limit(const ba_engine &e) {
+static int big_limit(const ba_engine &e) {
   int64_t need = e.p;
   if (e.max_model_size >= 0) need = std::min<int64_t>(need, e.max_model_size);
   if (need <= 64) return 0;
   return (int)std::min<int64_t>(BIG_KCAP_MAX, ((need + 63) / 64) * 64);
 }
-int ensure_big_buffers(ba_engine *e) {
+static int ensure_big_buffers(ba_engine *e) {
   const size_t C = (size_t)e->cfg.chains, kc = (size_t)e->big_kcap;
   const size_t want_model = 2 * C * ssvs_scalar_layout(e->big_kcap).total;
   const size_t want_xs = C * 2 * kc * 64;
@@ -853,58 +475,9 @@ int grow_big(ba_engine *e, int *stuck) {
   return ensure_big_buffers(e);
 }
 
-// the vectors of V named by dlogit_req[0, R), in batches the planes can hold
-int build_columns(ba_engine *e, int64_t R) {
-  const int64_t n = e->probit_n;
-  for (int64_t r0 = 0; r0 < R; r0 += e->logit_req_batch) {
-    const int64_t nr = std::min<int64_t>(e->logit_req_batch, R - r0);
-    HIP_TRY(launch_xtwx_cols(e->stream, e->dprob_X.ptr, n, e->p, e->dlogit_w.ptr,
-                             e->dlogit_req.ptr + 2 * r0, (int)nr, e->dA.ptr, e->dlogit_V.ptr,
-                             e->dlogit_valid.ptr, e->logit_words, e->dlogit_planes.ptr));
-  }
-  return BA_OK;
-}
-
-// Chains of the logit sampler parked at "add variable j" for want of vector j of
-// their V (CHAIN_NEED_COLUMN): the vectors are computed -- one GEMM for all of
-// them -- and the chains replay the sweep they were in, from its start and with the
-// same draws, now finding the vector.  *served: something was replayed (st is fresh).
-int serve_columns(ba_engine *e, std::vector<int32_t> &st, bool *served) {
-  *served = false;
-  if (!e->logit_mode || !e->dcol_request.count) return BA_OK;
-  const size_t C = (size_t)e->cfg.chains;
-  bool any = false;
-  for (size_t c = 0; c < C; ++c) any = any || st[c] == CHAIN_NEED_COLUMN || st[c] == CHAIN_NEED_COLUMN_BIG;
-  if (!any) return BA_OK;
-  std::vector<int32_t> want(C), req;
-  HIP_TRY(hipMemcpy(want.data(), e->dcol_request.ptr, C * 4, hipMemcpyDeviceToHost));
-  for (size_t c = 0; c < C; ++c) {
-    if (st[c] != CHAIN_NEED_COLUMN && st[c] != CHAIN_NEED_COLUMN_BIG) continue;
-    if (want[c] < 0 || want[c] >= e->p) return fail(BA_E_STATE, "a parked chain names no variable");
-    req.push_back((int32_t)c);
-    req.push_back(want[c]);
-    // (the large-model kernel takes its chains back in the parked state)
-    st[c] = (st[c] == CHAIN_NEED_COLUMN) ? CHAIN_OK : CHAIN_MODEL_TOO_LARGE;
-  }
-  const int64_t R = (int64_t)req.size() / 2;
-  HIP_TRY(hipMemcpyAsync(e->dlogit_req.ptr, req.data(), req.size() * 4, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->dstatus.ptr, st.data(), C * 4, hipMemcpyHostToDevice, e->stream));
-  int rc = build_columns(e, R);
-  if (rc) return rc;
-  e->logit_cols_requested += R;
-  ++e->logit_replays;
-  SsvsParams P;
-  fill_params(e, P);
-  HIP_TRY(launch_sweeps(e, P, 0));   // the sweep still owed
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  HIP_TRY(hipMemcpy(st.data(), e->dstatus.ptr, C * 4, hipMemcpyDeviceToHost));
-  *served = true;
-  return BA_OK;
-}
-
 // Resume chains that outgrew the capacity of the launch they were in, with the
 // next larger capacity; then follow the largest model size seen.
-int escalate(ba_engine *e, std::vector<int32_t> &st) {
+static int escalate(ba_engine *e, std::vector<int32_t> &st) {
   const size_t C = (size_t)e->cfg.chains;
   for (;;) {
     {
@@ -943,172 +516,6 @@ int escalate(ba_engine *e, std::vector<int32_t> &st) {
   }
 }
 
-// per chain: K (m T) | state (m T) | smoothed disturbances (nvar T) | normals (<= (nvar + 1) T + m + 1)
-int64_t ssm_work_stride(const ba_engine &e) {
-  // (the template kernel keeps four disturbance series and up to five normals a step)
-  // (general kernel: a smoothed-disturbance series per state-error row, and as many normals a step + 1)
-  const int64_t per_step = std::max(2 * e.ssg.m + 2 * std::max(e.ssg.nvar, e.ssg.nerr) + 1, 2 * e.ssg.m + 9);
-  return per_step * e.T + SSG_MAX_STATE + 72;
-}
-
-// does the block list have the shape the template kernel is compiled for?
-// [local level | local linear trend] [seasonal, duration 1] [autoregression], m <= 16
-void ssg_template_shape(const SsgSpec &q, int32_t *trend, int32_t *nseasons, int32_t *ar_lags) {
-  *trend = *nseasons = *ar_lags = 0;
-  if (q.nblocks < 1 || q.nblocks > 3 || q.m > 16) return;
-  for (int i = 0; i < q.nblocks; ++i)
-    if (q.blk[i].nvar == 0) return;   // (a static intercept: the general kernel)
-  int b = 0, tr = 0, ns = 0, lags = 0;
-  if (q.blk[0].kind == SSG_LOCAL_LEVEL) tr = 1;
-  else if (q.blk[0].kind == SSG_LOCAL_LINEAR_TREND) tr = 2;
-  else return;
-  b = 1;
-  if (b < q.nblocks && q.blk[b].kind == SSG_SEASONAL) {
-    if (q.blk[b].duration != 1) return;
-    ns = q.blk[b].nseasons;
-    ++b;
-  }
-  if (b < q.nblocks && q.blk[b].kind == SSG_AR) {
-    lags = q.blk[b].lags;
-    ++b;
-  }
-  if (b != q.nblocks) return;
-  *trend = tr;
-  *nseasons = ns;
-  *ar_lags = lags;
-}
-
-// the local-level path of a series of at most LM_TP steps runs lane-major
-// (kalman_lm_kernel): its scratch arrays have pitch LM_TP
-static bool ss_lane_major(const ba_engine &e) { return !e.ssm_set && e.T <= LM_TP; }
-static size_t ss_pitch(const ba_engine &e) { return ss_lane_major(e) ? (size_t)LM_TP : (size_t)e.T; }
-
-void fill_ss_params(ba_engine *e, SsParams &S) {
-  std::memset(&S, 0, sizeof(S));  // (only_ran = nullptr: every chain)
-  S.T = e->T;
-  S.slot_limit = e->slot_limit;
-  S.p = e->p;
-  S.chains = e->cfg.chains;
-  S.chain_first = 0;
-  S.chain_count = e->cfg.chains;
-  S.chain_offset = e->cfg.chain_offset;
-  S.y = e->dss_y.ptr;
-  S.X = e->dss_X.ptr;
-  S.observed = e->dss_obs.ptr;
-  S.Xt = e->dss_Xt.ptr;
-  S.yt = e->dss_yt.ptr;
-  S.obs_mask = e->dss_obs_mask.ptr;
-  S.lane_major = ss_lane_major(*e) ? 1 : 0;
-  S.TP = (int32_t)ss_pitch(*e);
-  S.gamma = e->dgamma.ptr;
-  S.beta = e->dbeta.ptr;
-  S.sigsq = e->dsigsq.ptr;
-  S.level_sigsq = e->dlev_sigsq.ptr;
-  S.level_n = e->dlev_n.ptr;
-  S.level_sumsq = e->dlev_sumsq.ptr;
-  S.level_prior_df = e->level_prior_df;
-  S.level_prior_ss = e->level_prior_ss;
-  S.level_sigma_max = e->level_sigma_max;
-  S.a0 = e->ss_a0;
-  S.P0 = e->ss_P0;
-  S.seed_lo = (uint32_t)e->seed;
-  S.seed_hi = (uint32_t)(e->seed >> 32);
-  S.pos_level = e->dpos_level.ptr;
-  S.pos_state = e->dpos_state.ptr;
-  S.status = e->dstatus.ptr;
-  S.scratch = e->dss_scratch.ptr;
-  S.scratch_stride = (int64_t)SS_SCRATCH_ARRAYS * (int64_t)ss_pitch(*e);
-  S.xty = e->dxty_c.ptr;
-  S.yty = e->dyty_c.ptr;
-  S.nobs = e->dnobs_c.ptr;
-  S.xte_planes = e->dxte_planes.ptr;
-  S.prepared = 0;
-  S.prep_n = e->dprep_n.ptr;
-  S.prep_pos_state = e->dprep_pos_state.ptr;
-  S.prep_pos_level = e->dprep_pos_level.ptr;
-  S.prep_level_sigsq = e->dprep_level.ptr;
-  S.zbuf = e->ss_zbuf;
-  S.level_used = e->ssla.lev_used.ptr;
-  if (e->ssm_set) {
-    S.ssm.spec = reinterpret_cast<const SsgSpec *>(e->dssg_spec.ptr);
-    S.ssm.m = e->ssg.m;
-    S.ssm.nblocks = e->ssg.nblocks;
-    S.ssm.nvar = e->ssg.nvar;
-    S.ssm.nar = e->ssg.nar;
-    S.ssm.ld = e->ssg.ld;
-    S.ssm.bl = e->ssg.bl;
-    S.ssm.nerr = e->ssg.nerr;
-    if (e->ssg_kernel_choice == 1 || e->ssg_kernel_choice == 3)
-      ssg_template_shape(e->ssg, &S.ssm.tpl_trend, &S.ssm.tpl_nseasons, &S.ssm.tpl_ar_lags);
-    S.ssm.glob = 0;
-    for (int b = 0; b < e->ssg.nblocks; ++b)
-      if (e->ssg.blk[b].kind == SSG_TRIG || e->ssg.blk[b].kind == SSG_SEMILOCAL) S.ssm.glob = 1;
-    S.ssm.var_sigsq = e->dssm_sigsq.ptr;
-    S.ssm.var_n = e->dssm_n.ptr;
-    S.ssm.var_ss = e->dssm_ss.ptr;
-    S.ssm.pos_var = e->dpos_var.ptr;
-    S.ssm.ar_phi = e->dar_phi.ptr;
-    S.ssm.ar_suf = e->dar_suf.ptr;
-    S.ssm.work = e->dssm_work.ptr;
-    S.ssm.work_stride = ssm_work_stride(*e);
-  }
-}
-
-// the state half of a state-space sweep: the structural kernel when a trend /
-// seasonal specification is set, the local-level kernel otherwise
-hipError_t launch_state_kernel(ba_engine *e, const SsParams &S, int draw) {
-  return e->ssm_set ? launch_ssm_simsmooth(e->stream, S, draw)
-                    : launch_kalman_simsmooth(e->stream, S, draw);
-}
-
-// The same for the state-space path, where a chain's sweeps alternate with the
-// Kalman kernel: a chain that outgrew the capacity sat out the rest of the call
-// (its SSVS launches booked the sweeps, its Kalman launches were skipped), so
-// it is caught up one (SSVS, Kalman) pair at a time; chains that owe nothing
-// leave both kernels at once.
-int ss_escalate(ba_engine *e, std::vector<int32_t> &st) {
-  const size_t C = (size_t)e->cfg.chains;
-  for (;;) {
-    bool any = false;
-    for (size_t c = 0; c < C; ++c) any = any || (st[c] == CHAIN_MODEL_TOO_LARGE);
-    if (!any) return BA_OK;
-    if (e->cfg.max_model_size_hint > 0) return BA_OK;  // stays an error
-    const bool to_big = e->kcap >= cap_limit(*e);
-    if (to_big) {
-      int stuck = 0;
-      int rc = grow_big(e, &stuck);
-      if (rc) return rc;
-      if (stuck) return BA_OK;
-    } else {
-      e->kcap += 16;
-      e->waves = choose_waves(*e, e->kcap);
-    }
-    std::vector<int32_t> todo(C);
-    HIP_TRY(hipMemcpy(todo.data(), e->dtodo.ptr, C * 4, hipMemcpyDeviceToHost));
-    int rounds = 0;
-    for (size_t c = 0; c < C; ++c) {
-      if (st[c] == CHAIN_MODEL_TOO_LARGE) {
-        if (!to_big) st[c] = CHAIN_OK;   // (the large-model kernel takes parked chains as they are)
-        rounds = std::max(rounds, (int)todo[c]);
-      }
-    }
-    HIP_TRY(hipMemcpyAsync(e->dstatus.ptr, st.data(), C * 4, hipMemcpyHostToDevice, e->stream));
-    SsvsParams P;
-    fill_params(e, P);
-    P.run_limit = 1;
-    P.ran = e->dran.ptr;
-    SsParams S;
-    fill_ss_params(e, S);
-    S.only_ran = e->dran.ptr;
-    for (int r = 0; r < rounds; ++r) {
-      HIP_TRY(launch_sweeps(e, P, 0));
-      HIP_TRY(launch_state_kernel(e, S, 1));
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(st.data(), e->dstatus.ptr, C * 4, hipMemcpyDeviceToHost));
-  }
-}
-
 // the pinned staging buffer of the accessors' batched copies (engine struct)
 hipError_t pinned_reserve(ba_engine *e, size_t bytes) {
   if (bytes <= e->pinned_bytes) return hipSuccess;
@@ -1123,8 +530,7 @@ hipError_t pinned_reserve(ba_engine *e, size_t bytes) {
 
 // (debugging sessions, ba_ss_set_tuning(e, 6): what THIS engine's round kernel noted, printed
 // when one of its chains stops; the buffer lives on the engine's device)
-int set_device(const ba_engine *e);
-void dump_round_debug(ba_engine *e) {
+static void dump_round_debug(ba_engine *e) {
   if (!e->round_debug || e->dround_debug.count == 0 || set_device(e)) return;
   DevBuf<int32_t> &g_round_debug = e->dround_debug;
   int32_t h[16 * 17];
@@ -1161,7 +567,7 @@ int check_chain_status(ba_engine *e) {
   for (size_t c = 0; c < C; ++c) all_ok = all_ok && st[c] == CHAIN_OK;
   {
     int rc = BA_OK;
-    if (!all_ok) rc = e->ss_mode ? ss_escalate(e, st) : escalate(e, st);
+    if (!all_ok) rc = e->data_kind == DATA_STATE_SPACE ? ss_escalate(e, st) : escalate(e, st);
     if (rc) return rc;
     // capacity follows the models: room for growth, no more
     if (follow) {
@@ -1214,13 +620,13 @@ int set_device(const ba_engine *e) {
 // process created before).  So a candidate is TESTED: a kernel on the main stream waits
 // (bounded: 20 ms) for a flag that a kernel on the candidate sets; the first candidate whose
 // kernel gets through while the other is waiting is kept.
-__global__ void stream_probe_wait_kernel(volatile int *flag, int *saw, long long ticks) {
+static __global__ void stream_probe_wait_kernel(volatile int *flag, int *saw, long long ticks) {
   const long long t0 = wall_clock64();
   int v = 0;
   while ((v = *flag) == 0 && wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
   *saw = v;
 }
-__global__ void stream_probe_set_kernel(volatile int *flag) { *flag = 1; }
+static __global__ void stream_probe_set_kernel(volatile int *flag) { *flag = 1; }
 
 int concurrent_stream(ba_engine *e, hipStream_t *out) {
   DevBuf<int32_t> buf;
@@ -1268,7 +674,7 @@ int pipe_join(ba_engine *e) {
 }
 // (force: read the word whatever the flag says -- the look-ahead's batches, whose launches
 // and checks interleave)
-int pipe_check(ba_engine *e, bool force = false) {
+static int pipe_check(ba_engine *e, bool force = false) {
   if (e->dpipe_err.count == 0 || (!force && !e->pipe_unchecked)) return BA_OK;
   e->pipe_unchecked = false;
   int32_t err = 0;
@@ -1281,24 +687,22 @@ int pipe_check(ba_engine *e, bool force = false) {
 }
 
 // ---- look-ahead serving (ba_draw_next) ------------------------------------------
-int sweep_impl(ba_engine *e, int32_t nsweeps, bool record = true, int la_half = -1);
-int read_record(ba_engine *e, int64_t c, int row0, int nrows, uint8_t *gamma,
-                double *beta, double *sigsq);
-int read_record_row_all(ba_engine *e, int row, uint8_t *gamma, double *beta, double *sigsq);
+static int sweep_impl(ba_engine *e, int32_t nsweeps, bool record = true, int la_half = -1);
+static int read_record(ba_engine *e, int64_t c, int row0, int nrows, uint8_t *gamma,
+                       double *beta, double *sigsq);
+static int read_record_row_all(ba_engine *e, int row, uint8_t *gamma, double *beta, double *sigsq);
 
-void la_discard(ba_engine *e) {
+static void la_discard(ba_engine *e) {
   e->la_avail = e->la_served = 0;
   e->la_cache.clear();
   e->la_synced = false;
 }
 
-int la_copy(ba_engine *e, bool save, int set = 0);
-int la_redo_batch(ba_engine *e);
-int ss_la_settle(ba_engine *e);
+static int la_redo_batch(ba_engine *e);
 
 // the batch being served is complete and sound; a pipelined batch in which a chain stopped
 // (capacity, an error) is run again the old way -- same draws -- where those are dealt with
-int la_wait(ba_engine *e) {
+static int la_wait(ba_engine *e) {
   if (e->la_synced) return BA_OK;
   if (e->la_cur_piped) {
     HIP_TRY(hipEventSynchronize(e->la_done[e->la_slot]));
@@ -1324,7 +728,7 @@ int la_wait(ba_engine *e) {
 
 // the draw ba_draw_next is serving, for one chain: from the host copy of the
 // chain's rows of the batch (fetched at the chain's first read in the batch)
-int la_read(ba_engine *e, int64_t c, uint8_t *gamma, double *beta, double *sigsq) {
+static int la_read(ba_engine *e, int64_t c, uint8_t *gamma, double *beta, double *sigsq) {
   {
     int rc = la_wait(e);
     if (rc) return rc;
@@ -1358,7 +762,7 @@ int la_read(ba_engine *e, int64_t c, uint8_t *gamma, double *beta, double *sigsq
 }
 
 // snapshot set `set` (0 / 1) <-> the live chain state
-int la_snap_alloc(ba_engine *e) {
+static int la_snap_alloc(ba_engine *e) {
   const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p;
   HIP_TRY(e->snap_gamma.resize(2 * C * p));
   HIP_TRY(e->snap_beta.resize(2 * C * p));
@@ -1400,7 +804,7 @@ int la_copy(ba_engine *e, bool save, int set) {
 
 // every launch of the look-ahead has finished (the main stream has caught up with the other
 // one) and nothing is ahead any more; *ahead_was: a batch beyond the one being served ran
-int la_quiesce(ba_engine *e, bool *ahead_was) {
+static int la_quiesce(ba_engine *e, bool *ahead_was) {
   *ahead_was = e->la_ahead;
   e->la_ahead = false;
   int rc = pipe_join(e);
@@ -1413,7 +817,7 @@ int la_quiesce(ba_engine *e, bool *ahead_was) {
 // capacity, an error): everything in flight is dropped, the chains go back to the batch's
 // start and the batch runs again the way batches ran before they overlapped -- the same
 // draws, with the escalation / error report of that path.  Overlap stays off afterwards.
-int la_redo_batch(ba_engine *e) {
+static int la_redo_batch(ba_engine *e) {
   bool ahead = false;
   int rc = la_quiesce(e, &ahead);
   if (rc) return rc;
@@ -1485,388 +889,7 @@ int la_rewind(ba_engine *e) {
   return rc;
 }
 
-// ---- look-ahead on the bsts path --------------------------------------------------------
-int ss_sweep_impl(ba_engine *e, int32_t nsweeps, int rec_slot);
-
-// what a round leaves for the callers' loop, copied into the record: one workgroup per
-// chain (gamma, beta, sigma^2, the state models' variances and coefficients), then one per
-// registered chain (its state path)
-struct SsRecParams {
-  int32_t C, p, nvar, nphi, nreg, L, row;   // row: slot * L + round
-  int64_t var_stride, phi_stride, state_stride, state_doubles;
-  const uint8_t *gamma;
-  const double *beta, *sigsq, *var, *phi, *state;
-  const int32_t *reg;
-  uint8_t *rgamma;
-  double *rbeta, *rsig, *rvar, *rphi, *rstate;
-};
-__global__ __launch_bounds__(256) void ss_record_kernel(SsRecParams R) {
-  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
-  const int slot = R.row / R.L, i = R.row % R.L;
-  if (b < R.C) {
-    const size_t at = ((size_t)slot * R.C + b) * R.L + i;
-    const size_t p = (size_t)R.p;
-    for (size_t j = tid; j < p; j += 256) {
-      R.rgamma[at * p + j] = R.gamma[(size_t)b * p + j];
-      R.rbeta[at * p + j] = R.beta[(size_t)b * p + j];
-    }
-    if (tid == 0) R.rsig[at] = R.sigsq[b];
-    if (tid < R.nvar) R.rvar[at * R.nvar + tid] = R.var[(size_t)b * R.var_stride + tid];
-    if (tid < R.nphi) R.rphi[at * R.nphi + tid] = R.phi[(size_t)b * R.phi_stride + tid];
-  } else {
-    const int r = b - R.C;
-    const size_t c = (size_t)R.reg[r];
-    const size_t at = ((size_t)slot * R.nreg + r) * R.L + i;
-    const double *src = R.state + c * (size_t)R.state_stride;
-    double *dst = R.rstate + at * (size_t)R.state_doubles;
-    for (int64_t j = tid; j < R.state_doubles; j += 256) dst[j] = src[j];
-  }
-}
-
-bool ss_la_on(const ba_engine *e) { return e->ssla.len > 1; }
-bool ss_la_serving(const ba_engine *e) { return e->ssla.len > 1 && e->ssla.avail > 0 && !e->ssla.busy; }
-
-hipError_t ss_la_record(ba_engine *e, int slot, int round) {
-  ba_engine::SsLa &A = e->ssla;
-  SsRecParams R{};
-  R.C = e->cfg.chains;
-  R.p = e->p;
-  R.nvar = (int32_t)A.nvar;
-  R.nphi = (int32_t)A.nphi;
-  R.nreg = (int32_t)A.reg.size();
-  R.L = A.len;
-  R.row = slot * A.len + round;
-  R.gamma = e->dgamma.ptr;
-  R.beta = e->dbeta.ptr;
-  R.sigsq = e->dsigsq.ptr;
-  if (e->ssm_set) {
-    R.var = e->dssm_sigsq.ptr;
-    R.var_stride = SSG_MAX_VAR;
-    R.phi = e->dar_phi.ptr;
-    R.phi_stride = SSG_MAX_AR * AR_MAX;
-    R.state = e->dssm_work.ptr + (size_t)e->ssg.m * e->T;
-    R.state_stride = ssm_work_stride(*e);
-  } else {
-    R.var = e->ssla.lev_used.ptr;   // (the live value may be the NEXT round's: drawn ahead)
-    R.var_stride = 1;
-    R.phi = nullptr;
-    R.phi_stride = 0;
-    R.state = e->dss_scratch.ptr + (size_t)SS_STATE_ARRAY * ss_pitch(*e);
-    R.state_stride = (int64_t)SS_SCRATCH_ARRAYS * (int64_t)ss_pitch(*e);
-  }
-  R.state_doubles = (int64_t)A.state_doubles;
-  R.reg = A.dreg.ptr;
-  R.rgamma = A.rgamma.ptr;
-  R.rbeta = A.rbeta.ptr;
-  R.rsig = A.rsig.ptr;
-  R.rvar = A.rvar.ptr;
-  R.rphi = A.rphi.ptr;
-  R.rstate = A.rstate.ptr;
-  hipLaunchKernelGGL(ss_record_kernel, dim3((unsigned)(R.C + R.nreg)), dim3(256), 0, e->stream, R);
-  return hipGetLastError();
-}
-
-// the record's and the snapshots' buffers for the current specification
-int ss_la_alloc(ba_engine *e) {
-  ba_engine::SsLa &A = e->ssla;
-  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, L = (size_t)A.len;
-  A.nvar = e->ssm_set ? (size_t)e->ssg.nvar : 1;
-  A.nphi = e->ssm_set ? (size_t)e->ssg.nar * AR_MAX : 0;
-  A.state_doubles = e->ssm_set ? (size_t)e->ssg.m * e->T : ss_pitch(*e);
-  {
-    // chains whose state path was read since the last allocation join the record while their
-    // rows fit in 2 GiB (m = 64, T = 2048, 256 rounds: half a gigabyte per chain); the others
-    // keep being read by going back to the draw being served
-    const double per_chain = 2.0 * (double)L * (double)A.state_doubles * 8.0;
-    for (int32_t w : A.want)
-      if (((double)A.reg.size() + 1.0) * per_chain <= 2147483648.0) A.reg.push_back(w);
-    A.want.clear();
-  }
-  const size_t nreg = A.reg.size();
-  HIP_TRY(A.rgamma.resize(2 * C * L * p));
-  HIP_TRY(A.rbeta.resize(2 * C * L * p));
-  HIP_TRY(A.rsig.resize(2 * C * L));
-  HIP_TRY(A.rvar.resize(2 * C * L * A.nvar));
-  HIP_TRY(A.rphi.resize(2 * C * L * std::max<size_t>(A.nphi, 1)));
-  HIP_TRY(A.rstate.resize(2 * nreg * L * A.state_doubles));
-  HIP_TRY(A.dreg.resize(nreg));
-  HIP_TRY(A.lev_used.resize(C));
-  HIP_TRY(hipMemcpy(A.dreg.ptr, A.reg.data(), nreg * 4, hipMemcpyHostToDevice));
-  {  // (the round kernel's view of the same list: chain -> its index among the registered)
-    std::vector<int32_t> of(C, -1);
-    for (size_t r = 0; r < nreg; ++r) of[(size_t)A.reg[r]] = (int32_t)r;
-    HIP_TRY(e->dround_reg.resize(C));
-    HIP_TRY(hipMemcpy(e->dround_reg.ptr, of.data(), C * 4, hipMemcpyHostToDevice));
-  }
-  // snapshot: level (sigsq, n, sumsq) | xty | yty | nobs [| state models: sigsq, n, ss | phi | ar suf]
-  A.snap_doubles = C * (3 + p + 2);
-  A.snap_words = 2 * C;
-  if (e->ssm_set) {
-    A.snap_doubles += C * (3 * SSG_MAX_VAR + SSG_MAX_AR * AR_MAX + SSG_MAX_AR * AR_SUF_STRIDE);
-    A.snap_words += C * SSG_MAX_VAR;
-  }
-  HIP_TRY(A.snap.resize(2 * A.snap_doubles));
-  HIP_TRY(A.snap_pos.resize(2 * A.snap_words));
-  for (int i = 0; i < 2; ++i)
-    if (!A.done[i]) HIP_TRY(hipEventCreateWithFlags(&A.done[i], hipEventDisableTiming));
-  return BA_OK;
-}
-
-// snapshot set `set` <-> the live chain state (both halves: the regression's by la_copy)
-int ss_la_copy(ba_engine *e, bool save, int set) {
-  ba_engine::SsLa &A = e->ssla;
-  int rc = la_copy(e, save, set);
-  if (rc) return rc;
-  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p;
-  hipStream_t s = e->stream;
-  double *d = A.snap.ptr + (size_t)set * A.snap_doubles;
-  uint64_t *w = A.snap_pos.ptr + (size_t)set * A.snap_words;
-#define SS_CP(live, n, T_)                                                                     \
-  do {                                                                                          \
-    const size_t bytes__ = (size_t)(n) * sizeof(T_);                                            \
-    if ((live) && bytes__)                                                                      \
-      HIP_TRY(hipMemcpyAsync(save ? (void *)cur__ : (void *)(live), save ? (const void *)(live) : (const void *)cur__, \
-                             bytes__, hipMemcpyDeviceToDevice, s));                             \
-    cur__ += (n);                                                                               \
-  } while (0)
-  {
-    double *cur__ = d;
-    SS_CP(e->dlev_sigsq.ptr, C, double);
-    SS_CP(e->dlev_n.ptr, C, double);
-    SS_CP(e->dlev_sumsq.ptr, C, double);
-    SS_CP(e->dxty_c.ptr, C * p, double);
-    SS_CP(e->dyty_c.ptr, C, double);
-    SS_CP(e->dnobs_c.ptr, C, double);
-    if (e->ssm_set) {
-      SS_CP(e->dssm_sigsq.ptr, C * SSG_MAX_VAR, double);
-      SS_CP(e->dssm_n.ptr, C * SSG_MAX_VAR, double);
-      SS_CP(e->dssm_ss.ptr, C * SSG_MAX_VAR, double);
-      SS_CP(e->dar_phi.ptr, e->ssg.nar > 0 ? C * SSG_MAX_AR * AR_MAX : 0, double);
-      SS_CP(e->dar_suf.ptr, e->ssg.nar > 0 ? C * SSG_MAX_AR * AR_SUF_STRIDE : 0, double);
-    }
-  }
-  {
-    uint64_t *cur__ = w;
-    SS_CP(e->dpos_level.ptr, C, uint64_t);
-    SS_CP(e->dpos_state.ptr, C, uint64_t);
-    if (e->ssm_set) SS_CP(e->dpos_var.ptr, C * SSG_MAX_VAR, uint64_t);
-  }
-#undef SS_CP
-  return BA_OK;
-}
-
-// enqueue one batch into half `slot`: the snapshot of where it starts, then `len` rounds,
-// each followed by its record
-int ss_la_launch(ba_engine *e, int slot) {
-  ba_engine::SsLa &A = e->ssla;
-  A.busy = true;
-  int rc = ss_la_copy(e, true, slot);
-  if (!rc) rc = ss_sweep_impl(e, A.cur, slot);
-  A.busy = false;
-  if (rc) return rc;
-  HIP_TRY(hipEventRecord(A.done[slot], e->stream));
-  return BA_OK;
-}
-
-void ss_la_reset(ba_engine *e) {
-  ba_engine::SsLa &A = e->ssla;
-  A.avail = A.served = 0;
-  A.slot = 0;
-  A.ahead = false;
-  A.synced = false;
-  A.cache.clear();
-}
-
-// The chains as the caller has seen them: nothing of the look-ahead left in flight.  The
-// batch being served is restored to its start and replayed up to the draw handed out
-// last (same stream positions, so the same draws).
-int ss_la_settle(ba_engine *e) {
-  ba_engine::SsLa &A = e->ssla;
-  if (A.len <= 1 || A.busy || A.avail == 0) return BA_OK;
-  A.busy = true;
-  struct Unbusy { ba_engine::SsLa &a; ~Unbusy() { a.busy = false; } } unbusy{A};
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (e->stream2) HIP_TRY(hipStreamSynchronize(e->stream2));
-  const int served = A.served, slot = A.slot;
-  const bool at_end = served >= A.avail && !A.ahead;   // the chains ARE at the draw served last
-  // (With the whole batch handed out and the next one running, the next batch's own snapshot
-  // IS the chains at the draw served last -- but not the state PATH of that draw, which a
-  // forecast or another chain's state read asks for and only the replay brings back: the
-  // batch is replayed then too.)
-  ss_la_reset(e);
-  if (at_end) return check_chain_status(e);   // (nothing dropped, nothing replayed: free)
-  // a rewind and a replay follow (see SsLa::cur: whoever made this necessary may do so after
-  // every draw, so the batches get shorter)
-  A.clean = false;
-  if (A.cur <= 2 && A.cur > 1) A.probe_wait = std::min(1024, A.probe_wait * 2);
-  A.cur = std::max(1, A.cur / 2);
-  A.calm = 0;
-  int rc = ss_la_copy(e, false, slot);
-  if (rc) return rc;
-  {  // (a chain that stopped in the dropped rounds stopped after the point we return to)
-    const size_t C = (size_t)e->cfg.chains;
-    HIP_TRY(hipMemsetAsync(e->dstatus.ptr, 0, C * 4, e->stream));
-    HIP_TRY(hipMemsetAsync(e->dtodo.ptr, 0, C * 4, e->stream));
-  }
-  e->table_ok = false;
-  e->model_ok = false;
-  if (served > 0) {
-    rc = ss_sweep_impl(e, served, -1);
-    if (rc) return rc;
-  }
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return check_chain_status(e);
-}
-
-// the batch being served is complete and every chain went through it; a batch in which
-// a chain stopped (capacity, an error) is run again round by round, with the stops dealt
-// with where they happen -- the same draws
-int ss_la_wait(ba_engine *e) {
-  ba_engine::SsLa &A = e->ssla;
-  if (A.synced) return BA_OK;
-  HIP_TRY(hipEventSynchronize(A.done[A.slot]));
-  const size_t C = (size_t)e->cfg.chains;
-  std::vector<int32_t> st(C);
-  HIP_TRY(hipMemcpy(st.data(), e->dstatus.ptr, C * 4, hipMemcpyDeviceToHost));
-  bool ok = true;
-  for (size_t c = 0; c < C; ++c) ok = ok && st[c] == CHAIN_OK;
-  if (!ok) {
-    A.busy = true;
-    struct Unbusy { ba_engine::SsLa &a; ~Unbusy() { a.busy = false; } } unbusy{A};
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (e->stream2) HIP_TRY(hipStreamSynchronize(e->stream2));
-    const int slot = A.slot;
-    A.ahead = false;
-    int rc = ss_la_copy(e, false, slot);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(e->dstatus.ptr, 0, C * 4, e->stream));
-    HIP_TRY(hipMemsetAsync(e->dtodo.ptr, 0, C * 4, e->stream));
-    e->table_ok = false;
-    e->model_ok = false;
-    rc = ss_la_copy(e, true, slot);   // (the same starting point, for a later settle)
-    for (int i = 0; i < A.avail && !rc; ++i) {
-      rc = ss_sweep_impl(e, 1, -1);
-      if (!rc) HIP_TRY(hipStreamSynchronize(e->stream));
-      if (!rc) rc = check_chain_status(e);   // (escalates, catches the chain up, reports errors)
-      if (!rc) HIP_TRY(ss_la_record(e, slot, i));
-    }
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    A.cache.clear();
-  }
-  A.synced = true;
-  return BA_OK;
-}
-
-// one chain's rows of the batch being served, on the host (one set of copies per batch)
-int ss_la_rows(ba_engine *e, int64_t c, bool want_state, const ba_engine::SsLa::Rows **out) {
-  ba_engine::SsLa &A = e->ssla;
-  int rc = ss_la_wait(e);
-  if (rc) return rc;
-  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, L = (size_t)A.len;
-  auto it = A.cache.find(c);
-  if (it == A.cache.end()) {
-    ba_engine::SsLa::Rows r;
-    r.gamma.resize(L * p); r.beta.resize(L * p); r.sig.resize(L); r.var.resize(L * A.nvar); r.phi.resize(L * A.nphi);
-    const size_t at = ((size_t)A.slot * C + (size_t)c) * L;
-    HIP_TRY(hipMemcpy(r.gamma.data(), A.rgamma.ptr + at * p, L * p, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(r.beta.data(), A.rbeta.ptr + at * p, L * p * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(r.sig.data(), A.rsig.ptr + at, L * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(r.var.data(), A.rvar.ptr + at * A.nvar, L * A.nvar * 8, hipMemcpyDeviceToHost));
-    if (A.nphi) HIP_TRY(hipMemcpy(r.phi.data(), A.rphi.ptr + at * A.nphi, L * A.nphi * 8, hipMemcpyDeviceToHost));
-    it = A.cache.emplace(c, std::move(r)).first;
-  }
-  if (want_state && !it->second.has_state) {
-    size_t ri = 0;
-    while (ri < A.reg.size() && A.reg[ri] != c) ++ri;
-    if (ri == A.reg.size()) return fail(BA_E_STATE, "the chain's state path is not in the look-ahead's record");
-    it->second.state.resize(L * A.state_doubles);
-    const size_t at = ((size_t)A.slot * A.reg.size() + ri) * L;
-    HIP_TRY(hipMemcpy(it->second.state.data(), A.rstate.ptr + at * A.state_doubles, L * A.state_doubles * 8,
-                      hipMemcpyDeviceToHost));
-    it->second.has_state = true;
-  }
-  *out = &it->second;
-  return BA_OK;
-}
-bool ss_la_registered(const ba_engine *e, int64_t c) {
-  for (int32_t r : e->ssla.reg)
-    if (r == c) return true;
-  return false;
-}
-// A chain whose state path was asked for and is not in the record: this read goes back to the
-// draw being served (ss_la_settle), the batches from here on record the chain too -- a caller
-// that reads chain c after every draw pays for it once, not every time.
-// (the list the device buffers are sized by, `reg`, changes in ss_la_alloc only; the state
-// record is bounded there)
-void ss_la_want_state(ba_engine *e, int64_t c) {
-  ba_engine::SsLa &A = e->ssla;
-  if (ss_la_registered(e, c)) return;
-  for (int32_t w : A.want)
-    if (w == c) return;
-  if (A.reg.size() + A.want.size() < 32) A.want.push_back((int32_t)c);
-}
-
-struct ApiScope {
-  ba_engine *e;
-  explicit ApiScope(ba_engine *en) : e(en) { e->api_seq++; e->api_depth++; }
-  ~ApiScope() { e->api_depth--; }
-  ApiScope(const ApiScope &) = delete;
-};
-
-// (a mutator changes what the next launch reads -- priors, data, options -- through copies
-// on the main stream: a pipelined sweep launch still running on the other stream must be
-// behind the main stream first, or it would see half of the new values)
-#define MUTATE(e)                        \
-  do {                                   \
-    (e)->api_seq++;                      \
-    int rc_m__ = set_device(e);          \
-    if (!rc_m__) rc_m__ = pipe_join(e);  \
-    if (!rc_m__) rc_m__ = ss_la_settle(e); \
-    if (!rc_m__) rc_m__ = la_rewind(e);  \
-    if (rc_m__) return rc_m__;           \
-    (e)->table_ok = false;               \
-    (e)->model_ok = false;               \
-  } while (0)
-
-// (accessors that enqueue nothing and change nothing: they do not count as a call
-// between two ba_sync()s)
-#define ENGINE_ACCESSOR_NOJOIN(e)                              \
-  if (!(e)) return fail(BA_E_INVALID, "null engine");          \
-  g_kt = (e)->kt_enabled ? &(e)->kt : nullptr;                 \
-  {                                                            \
-    int rc__ = set_device(e);                                  \
-    if (rc__) return rc__;                                     \
-  }
-#define ENGINE_PROLOGUE_NOJOIN(e)                              \
-  ENGINE_ACCESSOR_NOJOIN(e)                                    \
-  ApiScope api_scope__(e);
-// (everything but ba_sweep itself first lets the main stream catch up with a pipeline
-// of sweep launches)
-#define ENGINE_PROLOGUE(e)                                     \
-  ENGINE_PROLOGUE_NOJOIN(e)                                    \
-  {                                                            \
-    int rc__ = pipe_join(e);                                   \
-    if (!rc__) rc__ = ss_la_settle(e);                         \
-    if (rc__) return rc__;                                     \
-  }
-#define ENGINE_ACCESSOR(e)                                     \
-  ENGINE_ACCESSOR_NOJOIN(e)                                    \
-  {                                                            \
-    int rc__ = pipe_join(e);                                   \
-    if (!rc__) rc__ = ss_la_settle(e);                         \
-    if (rc__) return rc__;                                     \
-  }
-// (the entry points that serve the draw of ba_ss_draw_next from the device's record)
-#define ENGINE_ACCESSOR_SERVED(e)                              \
-  ENGINE_ACCESSOR_NOJOIN(e)                                    \
-  {                                                            \
-    int rc__ = pipe_join(e);                                   \
-    if (rc__) return rc__;                                     \
-  }
-
-}  // namespace
+}  // namespace boom_amd
 
 extern "C" {
 
@@ -2027,7 +1050,7 @@ int ba_upload_regression_suf(ba_engine *e, int32_t p, const double *xtx,
   e->sumy = ybar * n;
   e->have_suf = true;
   e->device_dirty = true;
-  e->probit_mode = e->logit_mode = e->ss_mode = e->poisson_mode = e->student_mode = false;   // (plain regression data now; the binomial, Poisson and state-space setters say otherwise after this)
+  e->data_kind = DATA_REGRESSION;   // (the binomial, Poisson, Student-t and state-space setters say otherwise after this)
   return BA_OK;
 }
 
@@ -2064,7 +1087,7 @@ int ba_build_suf_from_xy_device(ba_engine *e, int64_t n, int32_t p,
   e->n = (double)n;
   e->have_suf = true;
   e->device_dirty = true;
-  e->probit_mode = e->logit_mode = e->ss_mode = e->poisson_mode = e->student_mode = false;   // (plain regression data now; the binomial, Poisson and state-space setters say otherwise after this)
+  e->data_kind = DATA_REGRESSION;   // (the binomial, Poisson, Student-t and state-space setters say otherwise after this)
   return BA_OK;
 }
 
@@ -2110,7 +1133,7 @@ int ba_set_suf_from_block_device(ba_engine *e, int64_t n_total, int32_t p,
   e->n = (double)n_total;
   e->have_suf = true;
   e->device_dirty = true;
-  e->probit_mode = e->logit_mode = e->ss_mode = e->poisson_mode = e->student_mode = false;   // (plain regression data now; the binomial, Poisson and state-space setters say otherwise after this)
+  e->data_kind = DATA_REGRESSION;   // (the binomial, Poisson, Student-t and state-space setters say otherwise after this)
   return BA_OK;
 }
 
@@ -2299,6 +1322,16 @@ int ba_set_tuning(ba_engine *e, int32_t waves_per_chain, int32_t walk_policy,
   return BA_OK;
 }
 
+// for the tests of the spill streams (device_rng.h): a slot of a substream hands out `uniforms`
+// numbers, not its whole stride (0: the default again).  Changes the draws.
+int ba_set_slot_limit(ba_engine *e, int32_t uniforms) {
+  if (!e) return fail(BA_E_INVALID, "null engine");
+  if (uniforms < 0 || (uniforms & 1)) return fail(BA_E_INVALID, "uniforms must be even and non-negative");
+  MUTATE(e);
+  e->slot_limit = uniforms;
+  return BA_OK;
+}
+
 // --------------------------------------------------------------- state
 int ba_set_state(ba_engine *e, int64_t chain, const uint8_t *gamma,
                  const double *beta, double sigsq) {
@@ -2307,7 +1340,7 @@ int ba_set_state(ba_engine *e, int64_t chain, const uint8_t *gamma,
   if (!gamma) return fail(BA_E_INVALID, "null argument");
   const int64_t C = e->cfg.chains;
   if (chain < -1 || chain >= C) return fail(BA_E_INVALID, "chain index out of range");
-  if ((e->probit_mode || e->logit_mode) && !e->student_mode && sigsq != 1.0)
+  if (latent_data(e->data_kind) && e->data_kind != DATA_STUDENT && sigsq != 1.0)
     return fail(BA_E_INVALID, "the binomial samplers' latent data have unit variance: sigsq must be 1");
   if (chain < 0) la_discard(e);  // every chain is overwritten: nothing to rewind to
   MUTATE(e);
@@ -2509,9 +1542,13 @@ int ba_seed(ba_engine *e, uint64_t seed) {
   return BA_OK;
 }
 
+}  // extern "C"
+
+namespace boom_amd {
+
 // A change of sampler (BregVs <-> SpikeSlab) or of the XtX scale inside V has
 // to wait for the launches in flight (they may still be escalated).
-static int switch_mode(ba_engine *e, int mode, double v_scale) {
+int switch_mode(ba_engine *e, int mode, double v_scale) {
   if (e->cur_mode == mode && e->v_scale_want == v_scale) return BA_OK;
   if (e->state_ready) {
     int rc = ba_sync(e);
@@ -2527,20 +1564,71 @@ static int switch_mode(ba_engine *e, int mode, double v_scale) {
   return BA_OK;
 }
 
-// ------------------------------------------------------------ hot path
-}  // extern "C"
+// ---- which sweep serves which data ------------------------------------------------------
+// indexed by DataKind: what a family's entry point says while the engine holds other data ...
+static const char *const kSetDataFirst[] = {nullptr,
+                                            "call ba_ss_set_data first",
+                                            "call ba_probit_set_data first",
+                                            "call ba_logit_set_data first",
+                                            "call ba_poisson_set_data first",
+                                            "call ba_student_set_data first"};
+// ... and where the data in hand send a caller of another family's entry point
+static const char *const kUseSweep[] = {nullptr,
+                                        "state-space data are set: use ba_ss_sweep",
+                                        "binomial data are set: use ba_probit_sweep",
+                                        "binomial data are set: use ba_logit_sweep",
+                                        "Poisson data are set: use ba_poisson_sweep",
+                                        "Student-t regression data are set: use ba_student_sweep"};
 
-namespace {
+const char *set_data_first(DataKind wants) { return kSetDataFirst[wants]; }
+
+// Every cell is BA_E_STATE; tests/test_data_kind_gpu.py holds the whole matrix.
+int sweep_refusal(const ba_engine *e, DataKind wants, bool sss) {
+  const DataKind have = e->data_kind;
+  if (have == wants) return BA_OK;
+  if (wants == DATA_STATE_SPACE) return fail(BA_E_STATE, kSetDataFirst[wants]);
+  if (have == DATA_STUDENT) return fail(BA_E_STATE, kUseSweep[have]);
+  if (wants == DATA_REGRESSION) {   // ba_sweep, ba_draw_next, ba_adaptive_sweep; ba_sss_sweep
+    if (have == DATA_STATE_SPACE) return fail(BA_E_STATE, kUseSweep[have]);
+    return fail(BA_E_STATE,
+                sss ? "binomial data are set: use ba_logit_sweep / ba_probit_sweep (a sweep without the imputation is not a draw of those samplers)"
+                    : "binomial data are set: use ba_logit_sweep / ba_probit_sweep (the regression sampler has no meaning on latent data)");
+  }
+  // ba_student_sweep names the sweep of whatever data are set, ba_logit_sweep that of Poisson
+  // data (which run on the logit sampler's machinery); the others ask for their own data
+  if (have != DATA_REGRESSION && (wants == DATA_STUDENT || (wants == DATA_LOGIT && have == DATA_POISSON)))
+    return fail(BA_E_STATE, kUseSweep[have]);
+  return fail(BA_E_STATE, kSetDataFirst[wants]);
+}
+
+// ---- one double per chain (chain == -1: every chain) --------------------------------------
+int write_per_chain(ba_engine *e, double *dev, int64_t chain, double value) {
+  const size_t C = (size_t)e->cfg.chains;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (chain < 0) {
+    std::vector<double> v(C, value);
+    HIP_TRY(hipMemcpy(dev, v.data(), C * 8, hipMemcpyHostToDevice));
+  } else {
+    HIP_TRY(hipMemcpy(dev + chain, &value, 8, hipMemcpyHostToDevice));
+  }
+  return BA_OK;
+}
+int read_per_chain(ba_engine *e, const double *dev, int64_t chain, double *out) {
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (chain < 0) HIP_TRY(hipMemcpy(out, dev, (size_t)e->cfg.chains * 8, hipMemcpyDeviceToHost));
+  else HIP_TRY(hipMemcpy(out, dev + chain, 8, hipMemcpyDeviceToHost));
+  return BA_OK;
+}
+
+// ------------------------------------------------------------ hot path
 // la_half >= 0: a look-ahead batch that overlaps its neighbours -- recorded into that half of
 // the draw record, the chains' state on entry saved into that snapshot set (the caller has
 // checked la_can_overlap)
-int sweep_impl(ba_engine *e, int32_t nsweeps, bool record, int la_half) {
+static int sweep_impl(ba_engine *e, int32_t nsweeps, bool record, int la_half) {
   if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
-  if (e->ss_mode) return fail(BA_E_STATE, "state-space data are set: use ba_ss_sweep");
-  if (e->student_mode) return fail(BA_E_STATE, "Student-t regression data are set: use ba_student_sweep");
-  if (e->logit_mode || e->probit_mode)
-    return fail(BA_E_STATE, "binomial data are set: use ba_logit_sweep / ba_probit_sweep (the regression sampler has no meaning on latent data)");
-  int rc = switch_mode(e, 0, 1.0);
+  int rc = sweep_refusal(e, DATA_REGRESSION);
+  if (rc) return rc;
+  rc = switch_mode(e, 0, 1.0);
   if (rc) return rc;
   rc = upload_shared(e);
   if (rc) return rc;
@@ -2675,13 +1763,13 @@ int sweep_impl(ba_engine *e, int32_t nsweeps, bool record, int la_half) {
   e->model_ok = true;
   return BA_OK;
 }
-}  // namespace
+}  // namespace boom_amd
 
 extern "C" {
 
 int ba_sweep(ba_engine *e, int32_t nsweeps) {
   ENGINE_PROLOGUE_NOJOIN(e);
-  if (e->la_served < e->la_avail || e->ss_mode || e->logit_mode || e->probit_mode || e->cur_mode != 0) {
+  if (e->la_served < e->la_avail || e->data_kind != DATA_REGRESSION || e->cur_mode != 0) {
     int rcj = pipe_join(e);   // (anything but a plain continuation)
     if (rcj) return rcj;
   }
@@ -2786,7 +1874,7 @@ int ba_log_model_prob(ba_engine *e, int32_t ngamma, const uint8_t *gammas,
   if (!gammas || !out || ngamma <= 0) return fail(BA_E_INVALID, "bad argument");
   // the regression model's own sufficient statistics: in state-space mode they
   // are per chain and move every sweep, so there is no one answer
-  if (e->ss_mode)
+  if (e->data_kind == DATA_STATE_SPACE)
     return fail(BA_E_STATE, "ba_log_model_prob is not defined once state-space data are set (per-chain sufficient statistics)");
   // BregVsSampler's V = Omega^{-1} + XtX (a SpikeSlabSampler launch with a fixed
   // slab precision leaves XtX / sigma^2 in it)
@@ -2926,10 +2014,10 @@ int ba_enable_draws(ba_engine *e, int32_t max_sweeps) {
 
 }  // extern "C"
 
-namespace {
+namespace boom_amd {
 // rows [row0, row0 + nrows) of one chain's record, expanded to dense gamma / beta
-int read_record(ba_engine *e, int64_t c, int row0, int nrows, uint8_t *gamma,
-                double *beta, double *sigsq) {
+static int read_record(ba_engine *e, int64_t c, int row0, int nrows, uint8_t *gamma,
+                       double *beta, double *sigsq) {
   const size_t p = (size_t)e->p, cap = (size_t)e->rec_cap;
   const size_t base = (size_t)c * e->trace_stride + row0;
   std::vector<double> ks(nrows), sig(nrows), b((size_t)nrows * cap);
@@ -2955,7 +2043,7 @@ int read_record(ba_engine *e, int64_t c, int row0, int nrows, uint8_t *gamma,
 }
 
 // one row of EVERY chain's record (the draw ba_draw_next is serving)
-int read_record_row_all(ba_engine *e, int row, uint8_t *gamma, double *beta, double *sigsq) {
+static int read_record_row_all(ba_engine *e, int row, uint8_t *gamma, double *beta, double *sigsq) {
   const size_t p = (size_t)e->p, cap = (size_t)e->rec_cap, C = (size_t)e->cfg.chains;
   const size_t stride = (size_t)e->trace_stride;
   std::vector<double> ks(C), sig(C), b(C * cap);
@@ -2981,7 +2069,7 @@ int read_record_row_all(ba_engine *e, int row, uint8_t *gamma, double *beta, dou
   }
   return BA_OK;
 }
-}  // namespace
+}  // namespace boom_amd
 
 extern "C" {
 
@@ -3085,20 +2173,12 @@ int ba_set_sigsq(ba_engine *e, int64_t chain, double sigsq) {
   ENGINE_PROLOGUE(e);
   MUTATE(e);
   if (!(sigsq > 0)) return fail(BA_E_INVALID, "sigsq must be positive");
-  if ((e->probit_mode || e->logit_mode) && !e->student_mode && sigsq != 1.0)
+  if (latent_data(e->data_kind) && e->data_kind != DATA_STUDENT && sigsq != 1.0)
     return fail(BA_E_INVALID, "the binomial samplers' latent data have unit variance: sigsq must be 1");
   int rc = alloc_chain_state(e);
   if (rc) return rc;
-  const int64_t C = e->cfg.chains;
-  if (chain < -1 || chain >= C) return fail(BA_E_INVALID, "chain index out of range");
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (chain < 0) {
-    std::vector<double> v((size_t)C, sigsq);
-    HIP_TRY(hipMemcpy(e->dsigsq.ptr, v.data(), (size_t)C * 8, hipMemcpyHostToDevice));
-  } else {
-    HIP_TRY(hipMemcpy(e->dsigsq.ptr + chain, &sigsq, 8, hipMemcpyHostToDevice));
-  }
-  return BA_OK;
+  if (chain < -1 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  return write_per_chain(e, e->dsigsq.ptr, chain, sigsq);
 }
 
 int ba_sss_set_slab(ba_engine *e, const double *mu, const double *precision,
@@ -3121,12 +2201,10 @@ int ba_sss_sweep(ba_engine *e, int32_t nsweeps) {
   ENGINE_PROLOGUE(e);
   MUTATE(e);
   if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
-  if (e->ss_mode) return fail(BA_E_STATE, "state-space data are set: use ba_ss_sweep");
-  if (e->student_mode) return fail(BA_E_STATE, "Student-t regression data are set: use ba_student_sweep");
-  if (e->logit_mode || e->probit_mode)
-    return fail(BA_E_STATE, "binomial data are set: use ba_logit_sweep / ba_probit_sweep (a sweep without the imputation is not a draw of those samplers)");
+  int rc = sweep_refusal(e, DATA_REGRESSION, /*sss=*/true);
+  if (rc) return rc;
   if (!e->have_slab) return fail(BA_E_STATE, "call ba_sss_set_slab first");
-  int rc = alloc_chain_state(e);
+  rc = alloc_chain_state(e);
   if (rc) return rc;
   double v_scale = 1.0;
   if (!e->sss_slab_scales) {
@@ -3155,598 +2233,6 @@ int ba_sss_sweep(ba_engine *e, int32_t nsweeps) {
   HIP_TRY(launch_sweeps(e, P, (int)nsweeps));
   return BA_OK;
 }
-
-// ------------------------ BinomialProbitSpikeSlabSampler (data augmentation + SpikeSlabSampler)
-int ba_probit_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y,
-                       const double *ntrials, int32_t clt_threshold) {
-  ENGINE_PROLOGUE(e);
-  MUTATE(e);
-  if (!X || !y || !ntrials) return fail(BA_E_INVALID, "null argument");
-  if (n <= 0 || p <= 0) return fail(BA_E_INVALID, "n and p must be positive");
-  // up to 2 * clt_threshold truncated-normal draws per observation read the
-  // observation's substream of PROBIT_STRIDE uniforms (a draw takes 2 - 20 of them)
-  if (clt_threshold < 0 || clt_threshold > 64)
-    return fail(BA_E_INVALID, "clt_threshold must be between 0 and 64");
-  for (int64_t i = 0; i < n; ++i) {
-    if (y[i] < 0 || ntrials[i] < 0)
-      return fail(BA_E_INVALID, "Negative values not allowed in BinomialProbitDataImputer::impute().");
-    if (y[i] > ntrials[i])
-      return fail(BA_E_INVALID, "Success count exceeds trial count in BinomialProbitDataImputer::impute.");
-  }
-  // refresh_xtx (BinomialProbitSpikeSlabSampler.cpp:71-77): X'NX, built on the
-  // matrix cores from the rows scaled by sqrt(n_i).  Exact for Bernoulli data; for
-  // trial counts that are not perfect squares sqrt(n_i)^2 differs from n_i by one
-  // rounding, i.e. an element differs from the reference's sum_i n_i x x' by no more
-  // than the two summation orders already differ (~1e-16 relative per term).  The
-  // binomial cases of tests/test_probit_gpu.py (1 - 8 and 1 - 12 trials) hold the
-  // inclusion indicators bit-exact against the oracle on this matrix.
-  std::vector<double> Xs((size_t)n * p), zero((size_t)n, 0.0);
-  for (int32_t j = 0; j < p; ++j)
-    for (int64_t i = 0; i < n; ++i) Xs[(size_t)j * n + i] = X[(size_t)j * n + i] * std::sqrt(ntrials[i]);
-  int rc = ba_build_suf_from_xy(e, n, p, Xs.data(), zero.data());
-  if (rc) return rc;
-  HIP_TRY(e->dprob_X.resize((size_t)n * p));
-  HIP_TRY(e->dprob_y.resize((size_t)n));
-  HIP_TRY(e->dprob_nt.resize((size_t)n));
-  HIP_TRY(hipMemcpy(e->dprob_X.ptr, X, (size_t)n * p * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->dprob_y.ptr, y, (size_t)n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->dprob_nt.ptr, ntrials, (size_t)n * 8, hipMemcpyHostToDevice));
-  e->probit_mode = true;
-  e->logit_mode = false;
-  e->student_mode = false;
-  e->dprob_z.release();
-  e->probit_n = n;
-  e->probit_clt = clt_threshold;
-  e->probit_sweep = 0;
-  e->ss_mode = false;
-  return BA_OK;
-}
-
-int ba_probit_sweep(ba_engine *e, int32_t nsweeps) {
-  ENGINE_PROLOGUE(e);
-  MUTATE(e);
-  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
-  if (e->student_mode) return fail(BA_E_STATE, "Student-t regression data are set: use ba_student_sweep");
-  if (!e->probit_mode) return fail(BA_E_STATE, "call ba_probit_set_data first");
-  if (!e->have_slab) return fail(BA_E_STATE, "call ba_sss_set_slab first");
-  if (e->sss_slab_scales) return fail(BA_E_INVALID, "the probit sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
-  int rc = alloc_chain_state(e);
-  if (rc) return rc;
-  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, n = (size_t)e->probit_n;
-  if (e->dprob_z.count != C * n) {
-    HIP_TRY(e->dprob_z.resize(C * n));
-    HIP_TRY(e->dxty_c.resize(C * p));
-    HIP_TRY(e->dlogit_planes.resize((size_t)xtwx_cols_planes((int64_t)n) * C * p));   // (split-K planes of X'z)
-  }
-  {
-    // the latent data have unit variance: sigma^2 = 1 in every chain, whatever a
-    // caller left there before the binomial data were set
-    std::vector<double> one(C, 1.0);
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(e->dsigsq.ptr, one.data(), C * 8, hipMemcpyHostToDevice));
-  }
-  rc = switch_mode(e, 1, 1.0);
-  if (rc) return rc;
-  rc = upload_shared(e);
-  if (rc) return rc;
-  HIP_TRY(e->dmodel.resize(2 * C * ssvs_scalar_layout(64).total));
-  SsvsParams P;
-  fill_params(e, P);
-  ProbitParams Q;
-  std::memset(&Q, 0, sizeof(Q));
-  Q.n = (int32_t)n;
-  Q.p = (int32_t)p;
-  Q.chains = (int32_t)C;
-  Q.clt_threshold = e->probit_clt;
-  Q.slot_limit = e->slot_limit;
-  Q.chain_offset = e->cfg.chain_offset;
-  Q.X = e->dprob_X.ptr;
-  Q.y = e->dprob_y.ptr;
-  Q.ntrials = e->dprob_nt.ptr;
-  Q.gamma = e->dgamma.ptr;
-  Q.beta = e->dbeta.ptr;
-  Q.z = e->dprob_z.ptr;
-  Q.xtz = e->dxty_c.ptr;
-  Q.seed_lo = (uint32_t)e->seed;
-  Q.seed_hi = (uint32_t)(e->seed >> 32);
-  Q.status = e->dstatus.ptr;
-  // BinomialProbitSpikeSlabSampler::draw (BinomialProbitSpikeSlabSampler.cpp:40-46)
-  for (int i = 0; i < nsweeps; ++i) {
-    Q.sweep = e->probit_sweep++;
-    HIP_TRY(launch_probit_impute(e->stream, Q, e->dlogit_planes.ptr));   // impute_latent_data, X'z
-    HIP_TRY(launch_sweeps(e, P, 1));               // draw_model_indicators, draw_beta
-    // (a chain that outgrew the launch's capacity replays THIS sweep's draws on
-    // this sweep's latent data before the next imputation)
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    rc = check_chain_status(e);
-    if (rc) return rc;
-    fill_params(e, P);
-    P.model_keep = 1;
-    e->model_ok = true;
-  }
-  return BA_OK;
-}
-
-// ------------------------ BinomialLogitSpikeSlabSampler (auxiliary-mixture augmentation)
-int ba_logit_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y,
-                      const double *ntrials, int32_t clt_threshold) {
-  ENGINE_PROLOGUE(e);
-  MUTATE(e);
-  if (!X || !y || !ntrials) return fail(BA_E_INVALID, "null argument");
-  if (n <= 0 || p <= 0) return fail(BA_E_INVALID, "n and p must be positive");
-  // (per-trial imputation reads two uniforms per trial of the observation's substream
-  // of LOGIT_STRIDE; the large-sample branch beyond the threshold a few dozen)
-  if (clt_threshold < 1 || 4 * clt_threshold > LOGIT_STRIDE)
-    return fail(BA_E_INVALID, "clt_threshold must be between 1 and 64");
-  for (int64_t i = 0; i < n; ++i) {
-    if (y[i] < 0 || ntrials[i] < 0)
-      return fail(BA_E_INVALID, "The number of successes and the number of trials must both be non-negative in BinomialLogitPartialAugmentationDataImputer::impute().");
-    if (y[i] > ntrials[i])
-      return fail(BA_E_INVALID, "The number of successes must not exceed the number of trials in BinomialLogitPartialAugmentationDataImputer::impute().");
-  }
-  // (dimensions, the shared buffers and a placeholder X'X; the sweeps use every
-  // chain's own X'WX)
-  std::vector<double> zero((size_t)n, 0.0);
-  int rc = ba_build_suf_from_xy(e, n, p, X, zero.data());
-  if (rc) return rc;
-  HIP_TRY(e->dprob_X.resize((size_t)n * p));
-  HIP_TRY(e->dprob_y.resize((size_t)n));
-  HIP_TRY(e->dprob_nt.resize((size_t)n));
-  HIP_TRY(hipMemcpy(e->dprob_X.ptr, X, (size_t)n * p * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->dprob_y.ptr, y, (size_t)n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->dprob_nt.ptr, ntrials, (size_t)n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(e->dlogit_Xsq.resize((size_t)n * p));
-  HIP_TRY(launch_square(e->stream, e->dprob_X.ptr, (size_t)n * p, e->dlogit_Xsq.ptr));
-  e->logit_mode = true;
-  e->poisson_mode = false;
-  e->student_mode = false;
-  e->probit_mode = false;
-  e->probit_n = n;
-  e->probit_clt = clt_threshold;
-  e->probit_sweep = 0;
-  e->ss_mode = false;
-  e->dprob_z.release();
-  return BA_OK;
-}
-
-// ------------------------ PoissonRegressionSpikeSlabSampler
-int ba_poisson_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y,
-                        const double *exposure) {
-  ENGINE_PROLOGUE(e);
-  MUTATE(e);
-  if (!X || !y || !exposure) return fail(BA_E_INVALID, "null argument");
-  if (n <= 0 || p <= 0) return fail(BA_E_INVALID, "n and p must be positive");
-  for (int64_t i = 0; i < n; ++i) {
-    if (y[i] < 0 || y[i] != std::floor(y[i])) return fail(BA_E_INVALID, "counts must be non-negative integers");
-    if (!(exposure[i] > 0)) return fail(BA_E_INVALID, "exposures must be positive");
-  }
-  std::vector<double> zero((size_t)n, 0.0);
-  int rc = ba_build_suf_from_xy(e, n, p, X, zero.data());   // (dimensions and the shared buffers)
-  if (rc) return rc;
-  HIP_TRY(e->dprob_X.resize((size_t)n * p));
-  HIP_TRY(e->dprob_y.resize((size_t)n));
-  HIP_TRY(e->dprob_nt.resize((size_t)n));
-  HIP_TRY(hipMemcpy(e->dprob_X.ptr, X, (size_t)n * p * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->dprob_y.ptr, y, (size_t)n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->dprob_nt.ptr, exposure, (size_t)n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(e->dlogit_Xsq.resize((size_t)n * p));
-  HIP_TRY(launch_square(e->stream, e->dprob_X.ptr, (size_t)n * p, e->dlogit_Xsq.ptr));
-  e->poisson_y.resize((size_t)n);
-  for (int64_t i = 0; i < n; ++i) e->poisson_y[(size_t)i] = (int64_t)std::llround(y[i]);
-  e->logit_mode = true;      // (the logit path's buffers and column service)
-  e->poisson_mode = true;
-  e->student_mode = false;
-  e->poisson_mix_set = false;
-  e->probit_mode = false;
-  e->probit_n = n;
-  e->probit_clt = 0;
-  e->probit_sweep = 0;
-  e->ss_mode = false;
-  e->dprob_z.release();
-  return BA_OK;
-}
-
-int ba_poisson_set_mixtures(ba_engine *e, int32_t ncounts, const int64_t *counts, const int32_t *ncomp,
-                            const double *mu, const double *sigma, const double *weight,
-                            int64_t largest_index) {
-  ENGINE_PROLOGUE(e);
-  MUTATE(e);
-  if (!e->poisson_mode) return fail(BA_E_STATE, "call ba_poisson_set_data first");
-  if (ncounts <= 0 || !counts || !ncomp || !mu || !sigma || !weight) return fail(BA_E_INVALID, "null argument");
-  std::vector<int32_t> off((size_t)ncounts + 1, 0);
-  for (int i = 0; i < ncounts; ++i) {
-    if (i > 0 && counts[i] <= counts[i - 1]) return fail(BA_E_INVALID, "counts must be ascending and distinct");
-    if (ncomp[i] <= 0 || ncomp[i] > POISSON_MAX_COMP) return fail(BA_E_INVALID, "a mixture has 1 .. 32 components");
-    off[(size_t)i + 1] = off[(size_t)i] + ncomp[i];
-  }
-  const size_t tot = (size_t)off[(size_t)ncounts];
-  std::vector<double> logw(tot);
-  for (size_t c = 0; c < tot; ++c) {
-    if (!(weight[c] > 0) || !(sigma[c] > 0)) return fail(BA_E_INVALID, "mixture weights and standard deviations must be positive");
-    logw[c] = std::log(weight[c]);
-  }
-  auto find = [&](int64_t v) -> int {
-    const int64_t *it = std::lower_bound(counts, counts + ncounts, v);
-    return (it != counts + ncounts && *it == v) ? (int)(it - counts) : -2;
-  };
-  const size_t n = e->poisson_y.size();
-  std::vector<int32_t> obs(n, -1);
-  for (size_t i = 0; i < n; ++i) {
-    const int64_t v = e->poisson_y[i];
-    if (v <= 0) continue;
-    if (v >= largest_index) { obs[i] = -1; continue; }   // the Gaussian limit (poisson_mixture_approximation_table.cpp:49-55)
-    const int m = find(v);
-    if (m < 0) return fail(BA_E_INVALID, "no mixture was given for a count that occurs in the data");
-    obs[i] = m;
-  }
-  const int one = find(1);
-  if (one < 0) return fail(BA_E_INVALID, "the mixture of count 1 (the event past the interval) is needed");
-  HIP_TRY(e->dpois_off.resize(off.size()));
-  HIP_TRY(e->dpois_mu.resize(tot));
-  HIP_TRY(e->dpois_sigma.resize(tot));
-  HIP_TRY(e->dpois_logw.resize(tot));
-  HIP_TRY(e->dpois_obs.resize(n));
-  HIP_TRY(hipMemcpy(e->dpois_off.ptr, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->dpois_mu.ptr, mu, tot * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->dpois_sigma.ptr, sigma, tot * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->dpois_logw.ptr, logw.data(), tot * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->dpois_obs.ptr, obs.data(), n * 4, hipMemcpyHostToDevice));
-  e->poisson_mix_one = one;
-  e->poisson_mix_set = true;
-  return BA_OK;
-}
-
-}  // extern "C"
-static int logit_family_sweep(ba_engine *e, int32_t nsweeps);
-
-// the Student sampler's per-chain state: nu = 30 (TRegression.cpp:35-45), suggested_dx = 1
-// (TRegressionSampler.cpp:88-107), no slice comparison seen yet
-static int student_prepare(ba_engine *e) {
-  int rc = alloc_chain_state(e);
-  if (rc) return rc;
-  const size_t C = (size_t)e->cfg.chains;
-  if (e->dstu_nu.count == C) return BA_OK;
-  HIP_TRY(e->dstu_nu.resize(C));
-  HIP_TRY(e->dstu_dx.resize(C));
-  HIP_TRY(e->dstu_margin.resize(C));
-  std::vector<double> nu(C, 30.0), dx(C, 1.0), m(C, std::numeric_limits<double>::infinity());
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  HIP_TRY(hipMemcpy(e->dstu_nu.ptr, nu.data(), C * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->dstu_dx.ptr, dx.data(), C * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->dstu_margin.ptr, m.data(), C * 8, hipMemcpyHostToDevice));
-  return BA_OK;
-}
-
-extern "C" {
-
-// ------------------------ TRegressionSpikeSlabSampler
-int ba_student_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y) {
-  ENGINE_PROLOGUE(e);
-  MUTATE(e);
-  if (!X || !y) return fail(BA_E_INVALID, "null argument");
-  if (n <= 0 || p <= 0) return fail(BA_E_INVALID, "n and p must be positive");
-  for (int64_t i = 0; i < n; ++i)
-    if (!std::isfinite(y[i])) return fail(BA_E_INVALID, "responses must be finite");
-  std::vector<double> zero((size_t)n, 0.0);
-  int rc = ba_build_suf_from_xy(e, n, p, X, zero.data());   // (dimensions and the shared buffers)
-  if (rc) return rc;
-  HIP_TRY(e->dprob_X.resize((size_t)n * p));
-  HIP_TRY(e->dprob_y.resize((size_t)n));
-  HIP_TRY(hipMemcpy(e->dprob_X.ptr, X, (size_t)n * p * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->dprob_y.ptr, y, (size_t)n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(e->dlogit_Xsq.resize((size_t)n * p));
-  HIP_TRY(launch_square(e->stream, e->dprob_X.ptr, (size_t)n * p, e->dlogit_Xsq.ptr));
-  e->logit_mode = true;      // (the logit path's buffers and column service)
-  e->student_mode = true;
-  e->poisson_mode = false;
-  e->probit_mode = false;
-  e->probit_n = n;
-  e->probit_clt = 0;
-  e->probit_sweep = 0;
-  e->ss_mode = false;
-  e->dprob_z.release();
-  e->dstu_u.release();
-  // a new TRegressionModel: nu = 30, suggested_dx = 1, no slice margin yet (student_prepare)
-  e->dstu_nu.release();
-  e->dstu_dx.release();
-  e->dstu_margin.release();
-  return BA_OK;
-}
-
-int ba_student_allow_model_selection(ba_engine *e, int32_t allow) {
-  if (!e) return fail(BA_E_INVALID, "null engine");
-  MUTATE(e);
-  e->student_allow_selection = allow != 0;
-  return BA_OK;
-}
-
-int ba_student_set_nu_prior(ba_engine *e, int32_t kind, double a, double b) {
-  if (!e) return fail(BA_E_INVALID, "null engine");
-  if (kind == STUDENT_NU_UNIFORM) {
-    if (!(std::isfinite(a) && std::isfinite(b) && a >= 0 && b > a))
-      return fail(BA_E_INVALID, "a Uniform(a, b) prior on nu needs 0 <= a < b, both finite");
-  } else if (kind == STUDENT_NU_GAMMA) {
-    if (!(std::isfinite(a) && std::isfinite(b) && a > 0 && b > 0))
-      return fail(BA_E_INVALID, "a Gamma(a, b) prior on nu needs a positive shape and rate");
-  } else {
-    return fail(BA_E_INVALID, "kind must be 0 (Uniform) or 1 (Gamma)");
-  }
-  MUTATE(e);
-  e->student_nu_kind = kind;
-  e->student_nu_a = a;
-  e->student_nu_b = b;
-  return BA_OK;
-}
-
-int ba_student_set_nu(ba_engine *e, int64_t chain, double nu) {
-  ENGINE_PROLOGUE(e);
-  MUTATE(e);
-  if (!(nu > 0) || !std::isfinite(nu)) return fail(BA_E_INVALID, "nu must be positive and finite");
-  const int64_t C = e->cfg.chains;
-  if (chain < -1 || chain >= C) return fail(BA_E_INVALID, "chain index out of range");
-  int rc = student_prepare(e);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (chain < 0) {
-    std::vector<double> v((size_t)C, nu);
-    HIP_TRY(hipMemcpy(e->dstu_nu.ptr, v.data(), (size_t)C * 8, hipMemcpyHostToDevice));
-  } else {
-    HIP_TRY(hipMemcpy(e->dstu_nu.ptr + chain, &nu, 8, hipMemcpyHostToDevice));
-  }
-  return BA_OK;
-}
-
-int ba_student_get_nu(ba_engine *e, int64_t chain, double *nu) {
-  ENGINE_PROLOGUE(e);
-  if (!nu) return fail(BA_E_INVALID, "null argument");
-  const int64_t C = e->cfg.chains;
-  if (chain < -1 || chain >= C) return fail(BA_E_INVALID, "chain index out of range");
-  int rc = student_prepare(e);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (chain < 0) HIP_TRY(hipMemcpy(nu, e->dstu_nu.ptr, (size_t)C * 8, hipMemcpyDeviceToHost));
-  else HIP_TRY(hipMemcpy(nu, e->dstu_nu.ptr + chain, 8, hipMemcpyDeviceToHost));
-  return BA_OK;
-}
-
-int ba_student_get_margin(ba_engine *e, int64_t chain, double *margin) {
-  ENGINE_PROLOGUE(e);
-  if (!margin) return fail(BA_E_INVALID, "null argument");
-  const int64_t C = e->cfg.chains;
-  if (chain < -1 || chain >= C) return fail(BA_E_INVALID, "chain index out of range");
-  int rc = student_prepare(e);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (chain < 0) HIP_TRY(hipMemcpy(margin, e->dstu_margin.ptr, (size_t)C * 8, hipMemcpyDeviceToHost));
-  else HIP_TRY(hipMemcpy(margin, e->dstu_margin.ptr + chain, 8, hipMemcpyDeviceToHost));
-  return BA_OK;
-}
-
-int ba_student_get_weights(ba_engine *e, int64_t chain, double *w) {
-  ENGINE_PROLOGUE(e);
-  if (!w) return fail(BA_E_INVALID, "null argument");
-  if (!e->student_mode) return fail(BA_E_STATE, "call ba_student_set_data first");
-  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
-  const size_t n = (size_t)e->probit_n;
-  if (e->dlogit_w.count != (size_t)e->cfg.chains * n || e->probit_sweep == 0)
-    return fail(BA_E_STATE, "no imputation has run yet: call ba_student_sweep first");
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  HIP_TRY(hipMemcpy(w, e->dlogit_w.ptr + (size_t)chain * n, n * 8, hipMemcpyDeviceToHost));
-  return BA_OK;
-}
-
-int ba_student_get_nu_draws(ba_engine *e, int64_t chain, int32_t nsweeps, double *out) {
-  ENGINE_PROLOGUE(e);
-  if (!out) return fail(BA_E_INVALID, "null argument");
-  if (e->trace_stride <= 0 || e->dstu_nu_rec.count == 0)
-    return fail(BA_E_STATE, "draws are not recorded: call ba_enable_draws before ba_student_sweep");
-  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
-  if (nsweeps <= 0 || nsweeps > e->trace_stride) return fail(BA_E_INVALID, "nsweeps out of range");
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  HIP_TRY(hipMemcpy(out, e->dstu_nu_rec.ptr + (size_t)chain * e->trace_stride, (size_t)nsweeps * 8,
-                    hipMemcpyDeviceToHost));
-  return BA_OK;
-}
-
-int ba_student_sweep(ba_engine *e, int32_t nsweeps) {
-  ENGINE_PROLOGUE(e);
-  MUTATE(e);
-  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
-  if (e->ss_mode) return fail(BA_E_STATE, "state-space data are set: use ba_ss_sweep");
-  if (e->poisson_mode) return fail(BA_E_STATE, "Poisson data are set: use ba_poisson_sweep");
-  if (e->probit_mode) return fail(BA_E_STATE, "binomial data are set: use ba_probit_sweep");
-  if (!e->student_mode && e->logit_mode) return fail(BA_E_STATE, "binomial data are set: use ba_logit_sweep");
-  if (!e->student_mode) return fail(BA_E_STATE, "call ba_student_set_data first");
-  if (e->trace_stride > 0 && e->dstu_nu_rec.count != (size_t)e->cfg.chains * e->trace_stride) {
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(e->dstu_nu_rec.resize((size_t)e->cfg.chains * e->trace_stride));
-  }
-  return logit_family_sweep(e, nsweeps);
-}
-
-int ba_logit_set_imputer(ba_engine *e, int32_t kind) {
-  if (!e) return fail(BA_E_INVALID, "null engine");
-  if (kind != 0 && kind != 1) return fail(BA_E_INVALID, "imputer must be 0 (auxiliary mixture) or 1 (Polya-Gamma)");
-  MUTATE(e);
-  e->logit_imputer = kind;
-  return BA_OK;
-}
-
-int ba_logit_sweep(ba_engine *e, int32_t nsweeps) {
-  ENGINE_PROLOGUE(e);
-  MUTATE(e);
-  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
-  if (e->student_mode) return fail(BA_E_STATE, "Student-t regression data are set: use ba_student_sweep");
-  if (e->poisson_mode) return fail(BA_E_STATE, "Poisson data are set: use ba_poisson_sweep");
-  if (!e->logit_mode) return fail(BA_E_STATE, "call ba_logit_set_data first");
-  return logit_family_sweep(e, nsweeps);
-}
-
-int ba_poisson_sweep(ba_engine *e, int32_t nsweeps) {
-  ENGINE_PROLOGUE(e);
-  MUTATE(e);
-  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
-  if (e->student_mode) return fail(BA_E_STATE, "Student-t regression data are set: use ba_student_sweep");
-  if (!e->poisson_mode) return fail(BA_E_STATE, "call ba_poisson_set_data first");
-  if (!e->poisson_mix_set) return fail(BA_E_STATE, "call ba_poisson_set_mixtures first");
-  return logit_family_sweep(e, nsweeps);
-}
-
-}  // extern "C"
-
-// the sweep loop shared by the logit and the Poisson samplers: imputation (per family),
-// X'Wz and the diagonal, the vectors of V the sweep starts from, the inclusion /
-// coefficient draws with park-and-replay for vectors requested mid-sweep
-static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
-  {
-  const bool student = e->student_mode;
-  if (!e->have_slab) return fail(BA_E_STATE, "call ba_sss_set_slab first");
-  if (student && !e->sss_slab_scales)
-    return fail(BA_E_INVALID, "the Student-t sampler takes a slab whose precision scales with sigma^2 (scales_with_sigsq = 1)");
-  if (!student && e->sss_slab_scales) return fail(BA_E_INVALID, "the logit sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
-  int rc = alloc_chain_state(e);
-  if (rc) return rc;
-  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, n = (size_t)e->probit_n;
-  if (student) {
-    rc = student_prepare(e);
-    if (rc) return rc;
-    if (e->trace_stride > 0 && nsweeps > e->trace_stride)
-      return fail(BA_E_INVALID, "nsweeps exceeds the enabled trace length");
-    if (e->dstu_u.count != C * n) HIP_TRY(e->dstu_u.resize(C * n));
-  }
-  if (e->dprob_z.count != C * n || e->dlogit_V.count != C * p * p) {
-    HIP_TRY(e->dprob_z.resize(C * n));
-    HIP_TRY(e->dlogit_w.resize(C * n));
-    HIP_TRY(e->dlogit_V.resize(C * p * p));
-    HIP_TRY(e->dxty_c.resize(C * p));
-    e->logit_words = (int)((p + 31) / 32);
-    HIP_TRY(e->dlogit_vdiag.resize(C * p));
-    HIP_TRY(e->dlogit_valid.resize(C * (size_t)e->logit_words));
-    HIP_TRY(e->dlogit_req.resize(2 * C * p));
-    HIP_TRY(e->dlogit_cnt.resize(1));
-    HIP_TRY(e->dcol_request.resize(C));
-    // the planes of one GEMM launch: at most 1 GiB, at least one request tile
-    const size_t per_req = (size_t)xtwx_cols_planes((int64_t)n) * p * 8;
-    e->logit_req_batch = (int64_t)std::min<size_t>(std::max<size_t>(((size_t)1 << 30) / per_req, 64), 32768);
-    e->logit_req_batch = std::min<int64_t>(e->logit_req_batch, (int64_t)(C * p));
-    HIP_TRY(e->dlogit_planes.resize((size_t)e->logit_req_batch * per_req / 8));
-  }
-  if (!student) {
-    std::vector<double> one(C, 1.0);   // (sigma^2 = 1: see ba_probit_sweep)
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(e->dsigsq.ptr, one.data(), C * 8, hipMemcpyHostToDevice));
-  }
-  rc = switch_mode(e, 1, 1.0);
-  if (rc) return rc;
-  rc = upload_shared(e);
-  if (rc) return rc;
-  HIP_TRY(e->dmodel.resize(2 * C * ssvs_scalar_layout(64).total));
-  SsvsParams P;
-  fill_params(e, P);
-  ProbitParams Q;
-  std::memset(&Q, 0, sizeof(Q));
-  Q.n = (int32_t)n;
-  Q.p = (int32_t)p;
-  Q.chains = (int32_t)C;
-  Q.clt_threshold = e->probit_clt;
-  Q.slot_limit = e->slot_limit;
-  Q.chain_offset = e->cfg.chain_offset;
-  Q.X = e->dprob_X.ptr;
-  Q.y = e->dprob_y.ptr;
-  Q.ntrials = e->dprob_nt.ptr;
-  Q.gamma = e->dgamma.ptr;
-  Q.beta = e->dbeta.ptr;
-  Q.z = e->dprob_z.ptr;
-  Q.w = e->dlogit_w.ptr;
-  Q.xtz = e->dxty_c.ptr;
-  Q.seed_lo = (uint32_t)e->seed;
-  Q.seed_hi = (uint32_t)(e->seed >> 32);
-  Q.status = e->dstatus.ptr;
-  Q.mix_off = e->dpois_off.ptr;
-  Q.mix_mu = e->dpois_mu.ptr;
-  Q.mix_sigma = e->dpois_sigma.ptr;
-  Q.mix_logw = e->dpois_logw.ptr;
-  Q.obs_mix = e->dpois_obs.ptr;
-  Q.mix_one = e->poisson_mix_one;
-  const int imputer = e->poisson_mode ? 2 : e->logit_imputer;
-  StudentParams T;
-  std::memset(&T, 0, sizeof(T));
-  if (student) {
-    T.n = (int32_t)n;
-    T.p = (int32_t)p;
-    T.chains = (int32_t)C;
-    T.slot_limit = e->slot_limit;
-    T.chain_offset = e->cfg.chain_offset;
-    T.X = e->dprob_X.ptr;
-    T.y = e->dprob_y.ptr;
-    T.gamma = e->dgamma.ptr;
-    T.beta = e->dbeta.ptr;
-    T.sigsq = e->dsigsq.ptr;
-    T.nu = e->dstu_nu.ptr;
-    T.dx = e->dstu_dx.ptr;
-    T.margin = e->dstu_margin.ptr;
-    T.z = e->dprob_z.ptr;
-    T.w = e->dlogit_w.ptr;
-    T.u = e->dstu_u.ptr;
-    T.seed_lo = (uint32_t)e->seed;
-    T.seed_hi = (uint32_t)(e->seed >> 32);
-    T.status = e->dstatus.ptr;
-    T.prior_df = e->prior_df;
-    T.prior_ss = e->prior_ss;
-    T.sigma_max = e->sigma_max;
-    T.nu_kind = e->student_nu_kind;
-    T.nu_a = e->student_nu_a;
-    T.nu_b = e->student_nu_b;
-    T.trace_idx = e->dtrace_idx.ptr;
-    T.trace_sigsq = e->dtr_sig.ptr;
-    T.trace_nu = e->dstu_nu_rec.ptr;
-    T.trace_stride = e->dstu_nu_rec.count ? e->trace_stride : 0;
-    T.acc = e->dacc.ptr;
-    // (the draws recorded are those of the last ba_student_sweep call)
-    if (e->trace_stride > 0) HIP_TRY(hipMemsetAsync(e->dtrace_idx.ptr, 0, C * 4, e->stream));
-  }
-  // BinomialLogitSpikeSlabSampler::draw (BinomialLogitSpikeSlabSampler.cpp:50-54) /
-  // PoissonRegressionSpikeSlabSampler::draw (PoissonRegressionSpikeSlabSampler.cpp:55-59)
-  for (int i = 0; i < nsweeps; ++i) {
-    Q.sweep = T.sweep = e->probit_sweep++;
-    // impute_latent_data: z, w, X'Wz and the diagonal of V = slab precision + X'WX ...
-    if (student)
-      HIP_TRY(launch_student_impute(e->stream, T, e->dlogit_Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->dlogit_vdiag.ptr,
-                                    e->dlogit_planes.ptr));
-    else
-      HIP_TRY(launch_logit_impute(e->stream, Q, e->dlogit_Xsq.ptr, e->dA.ptr, e->dlogit_vdiag.ptr,
-                                  e->dlogit_planes.ptr, imputer));
-    // ... and the vectors of V the sweep starts from: those of the included variables
-    HIP_TRY(launch_xtwx_cols_start(e->stream, e->dgamma.ptr, (int)C, (int)p, e->dlogit_req.ptr,
-                                   e->dlogit_cnt.ptr, e->dlogit_valid.ptr, e->logit_words));
-    int32_t R = 0;
-    HIP_TRY(hipMemcpyAsync(&R, e->dlogit_cnt.ptr, 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    rc = build_columns(e, R);
-    if (rc) return rc;
-    e->logit_cols_built += R;
-    HIP_TRY(launch_sweeps(e, P, 1));                                         // draw_model_indicators, draw_beta
-    // (a chain that stopped for a missing vector of V, or outgrew the launch's
-    // capacity, replays THIS sweep's draws on this sweep's latent data before the
-    // next imputation: check_chain_status serves both)
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    rc = check_chain_status(e);
-    if (rc) return rc;
-    if (student) {
-      // draw_sigsq_full_conditional, draw_nu_given_observed_data
-      HIP_TRY(launch_student_sigma_nu(e->stream, T));
-      rc = check_chain_status(e);
-      if (rc) return rc;
-    }
-    fill_params(e, P);
-  }
-  e->table_ok = false;
-  e->model_ok = false;
-  return BA_OK;
-  }
-}
-
-extern "C" {
 
 // ------------------------ AdaptiveSpikeSlabRegressionSampler (birth / death)
 static int ada_prepare(ba_engine *e) {
@@ -3783,11 +2269,9 @@ int ba_adaptive_sweep(ba_engine *e, int32_t nsweeps) {
   ENGINE_PROLOGUE(e);
   MUTATE(e);
   if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
-  if (e->ss_mode) return fail(BA_E_STATE, "state-space data are set: use ba_ss_sweep");
-  if (e->student_mode) return fail(BA_E_STATE, "Student-t regression data are set: use ba_student_sweep");
-  if (e->logit_mode || e->probit_mode)
-    return fail(BA_E_STATE, "binomial data are set: use ba_logit_sweep / ba_probit_sweep (the regression sampler has no meaning on latent data)");
-  int rc = alloc_chain_state(e);
+  int rc = sweep_refusal(e, DATA_REGRESSION);
+  if (rc) return rc;
+  rc = alloc_chain_state(e);
   if (rc) return rc;
   rc = switch_mode(e, 2, 1.0);
   if (rc) return rc;
@@ -3822,1053 +2306,4 @@ int ba_adaptive_get_rates(ba_engine *e, int64_t chain, double *birth_rates,
   return BA_OK;
 }
 
-// --------------------------------------------------- state space (kalman)
-static int ss_prepare(ba_engine *e) {
-  if (!e->ss_mode) return fail(BA_E_STATE, "call ba_ss_set_data first");
-  if (!e->ss_level_set && !e->ssm_set)
-    return fail(BA_E_STATE, "call ba_ss_set_local_level or ba_ss_set_structural first");
-  int rc = upload_shared(e);
-  if (rc) return rc;
-  rc = alloc_chain_state(e);
-  if (rc) return rc;
-  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, T = ss_pitch(*e);
-  if (e->dss_scratch.count != C * SS_SCRATCH_ARRAYS * T) {
-    HIP_TRY(e->dss_scratch.resize(C * SS_SCRATCH_ARRAYS * T));
-    HIP_TRY(e->dxty_c.resize(C * p));
-    HIP_TRY(e->dyty_c.resize(C));
-    HIP_TRY(e->dnobs_c.resize(C));
-    HIP_TRY(e->dlev_sigsq.resize(C));
-    HIP_TRY(e->dlev_n.resize(C));
-    HIP_TRY(e->dlev_sumsq.resize(C));
-    HIP_TRY(e->dpos_level.resize(C));
-    HIP_TRY(e->dpos_state.resize(C));
-    HIP_TRY(e->dpos_forecast.resize(C));
-    HIP_TRY(hipMemsetAsync(e->dpos_forecast.ptr, 0, C * 8, e->stream));
-    HIP_TRY(e->dprep_n.resize(2 * C));
-    HIP_TRY(e->dprep_pos_state.resize(2 * C));
-    HIP_TRY(e->dprep_pos_level.resize(2 * C));
-    HIP_TRY(e->dprep_level.resize(2 * C));
-    HIP_TRY(hipMemsetAsync(e->dprep_n.ptr, 0, 2 * C * 4, e->stream));
-    e->ss_zbuf = 0;
-    HIP_TRY(e->dxte_planes.resize((size_t)xte_planes((int64_t)T) * C * p));
-    // regression suf starts as the data's own (before the first impute_state)
-    std::vector<double> xty(C * p), yty(C, e->yty), nobs(C, e->n),
-        lev(C, e->ss_initial_level_sigsq);
-    for (size_t c = 0; c < C; ++c) std::memcpy(&xty[c * p], e->xty.data(), p * 8);
-    hipStream_t s = e->stream;
-    HIP_TRY(hipMemcpyAsync(e->dxty_c.ptr, xty.data(), xty.size() * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(e->dyty_c.ptr, yty.data(), C * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(e->dnobs_c.ptr, nobs.data(), C * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(e->dlev_sigsq.ptr, lev.data(), C * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(e->dlev_n.ptr, 0, C * 8, s));
-    HIP_TRY(hipMemsetAsync(e->dlev_sumsq.ptr, 0, C * 8, s));
-    HIP_TRY(hipMemsetAsync(e->dpos_level.ptr, 0, C * 8, s));
-    HIP_TRY(hipMemsetAsync(e->dpos_state.ptr, 0, C * 8, s));
-    HIP_TRY(hipMemsetAsync(e->dss_scratch.ptr, 0, C * SS_SCRATCH_ARRAYS * T * 8, s));
-    if (e->ssm_set) {
-      const size_t NV = SSG_MAX_VAR;
-      HIP_TRY(e->dssm_sigsq.resize(C * NV));
-      HIP_TRY(e->dssm_n.resize(C * NV));
-      HIP_TRY(e->dssm_ss.resize(C * NV));
-      HIP_TRY(e->dpos_var.resize(C * NV));
-      HIP_TRY(e->dssm_work.resize(C * (size_t)ssm_work_stride(*e)));
-      HIP_TRY(e->dssg_spec.resize(sizeof(SsgSpec)));
-      HIP_TRY(hipMemcpy(e->dssg_spec.ptr, &e->ssg, sizeof(SsgSpec), hipMemcpyHostToDevice));
-      std::vector<double> v0(C * NV);
-      for (size_t c = 0; c < C; ++c)
-        for (size_t i = 0; i < NV; ++i) v0[c * NV + i] = e->ssg_initial_sigsq[i];
-      HIP_TRY(hipMemcpy(e->dssm_sigsq.ptr, v0.data(), C * NV * 8, hipMemcpyHostToDevice));
-      HIP_TRY(hipMemsetAsync(e->dssm_n.ptr, 0, C * NV * 8, s));
-      HIP_TRY(hipMemsetAsync(e->dssm_ss.ptr, 0, C * NV * 8, s));
-      HIP_TRY(hipMemsetAsync(e->dpos_var.ptr, 0, C * NV * 8, s));
-      HIP_TRY(hipMemsetAsync(e->dssm_work.ptr, 0, C * (size_t)ssm_work_stride(*e) * 8, s));
-      if (e->ssg.nar > 0) {
-        HIP_TRY(e->dar_phi.resize(C * SSG_MAX_AR * AR_MAX));
-        HIP_TRY(e->dar_suf.resize(C * SSG_MAX_AR * AR_SUF_STRIDE));
-        std::vector<double> ph(C * SSG_MAX_AR * AR_MAX, 0.0);
-        for (size_t c = 0; c < C; ++c)
-          for (int a = 0; a < SSG_MAX_AR; ++a)
-            for (int i = 0; i < AR_MAX; ++i) ph[(c * SSG_MAX_AR + a) * AR_MAX + i] = e->ssg_initial_phi[a][i];
-        HIP_TRY(hipMemcpy(e->dar_phi.ptr, ph.data(), ph.size() * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemsetAsync(e->dar_suf.ptr, 0, C * SSG_MAX_AR * AR_SUF_STRIDE * 8, s));
-      }
-    }
-    HIP_TRY(hipStreamSynchronize(s));  // (the host vectors above go out of scope)
-    e->ss_initialized = false;
-  }
-  HIP_TRY(e->dmodel.resize(2 * (size_t)e->cfg.chains * ssvs_scalar_layout(64).total));
-  return BA_OK;
-}
-
-int ba_ss_set_data(ba_engine *e, int32_t T, int32_t p, const double *y,
-                   const double *X, const uint8_t *observed) {
-  ENGINE_PROLOGUE(e);
-  MUTATE(e);
-  if (!y || !X) return fail(BA_E_INVALID, "null argument");
-  if (T <= 0 || p <= 0) return fail(BA_E_INVALID, "T and p must be positive");
-  // The regression model's fixed XtX (and the initial Xty, ...) are over the
-  // OBSERVED rows only: missing points never update the sufficient statistics
-  // (StateSpaceRegressionModel.cpp:100-125, SufstatDataPolicy.hpp:166-167).
-  std::vector<double> Xo((size_t)T * p), yo(T);
-  std::vector<uint8_t> obs(T, 1);
-  double nobs = 0;
-  for (int t = 0; t < T; ++t) {
-    if (observed) obs[t] = observed[t] ? 1 : 0;
-    nobs += obs[t];
-    yo[t] = obs[t] ? y[t] : 0.0;
-  }
-  for (int j = 0; j < p; ++j)
-    for (int t = 0; t < T; ++t)
-      Xo[(size_t)j * T + t] = obs[t] ? X[(size_t)j * T + t] : 0.0;
-  int rc = ba_build_suf_from_xy(e, T, p, Xo.data(), yo.data());
-  if (rc) return rc;
-  e->n = nobs;
-  e->T = T;
-  HIP_TRY(e->dss_y.resize(T));
-  HIP_TRY(e->dss_X.resize((size_t)T * p));
-  HIP_TRY(e->dss_obs.resize(T));
-  HIP_TRY(hipMemcpy(e->dss_y.ptr, y, (size_t)T * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->dss_X.ptr, X, (size_t)T * p * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->dss_obs.ptr, obs.data(), T, hipMemcpyHostToDevice));
-  if (T <= LM_TP) {
-    std::vector<double> Xt((size_t)LM_TP * p, 0.0), yt(LM_TP, 0.0);
-    std::vector<uint32_t> mask(LM_THREADS, 0u);
-    for (int t = 0; t < T; ++t) {
-      yt[lm_at(t)] = y[t];
-      if (obs[t]) mask[t / LM_BS] |= 1u << (t % LM_BS);
-    }
-    for (int j = 0; j < p; ++j)
-      for (int t = 0; t < T; ++t) Xt[(size_t)j * LM_TP + lm_at(t)] = X[(size_t)j * T + t];
-    HIP_TRY(e->dss_yt.resize(LM_TP));
-    HIP_TRY(e->dss_Xt.resize((size_t)LM_TP * p));
-    HIP_TRY(e->dss_obs_mask.resize(LM_THREADS));
-    HIP_TRY(hipMemcpy(e->dss_yt.ptr, yt.data(), (size_t)LM_TP * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->dss_Xt.ptr, Xt.data(), (size_t)LM_TP * p * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->dss_obs_mask.ptr, mask.data(), LM_THREADS * 4, hipMemcpyHostToDevice));
-  } else {
-    e->dss_yt.release();
-    e->dss_Xt.release();
-    e->dss_obs_mask.release();
-  }
-  e->ss_mode = true;
-  e->student_mode = false;
-  e->ss_initialized = false;
-  e->dss_scratch.release();
-  e->device_dirty = true;
-  return BA_OK;
-}
-
-int ba_ss_set_local_level(ba_engine *e, double level_df, double level_sigma_guess,
-                          double level_sigma_upper_limit,
-                          double initial_state_mean,
-                          double initial_state_variance,
-                          double initial_level_sigma) {
-  if (!e) return fail(BA_E_INVALID, "null engine");
-  MUTATE(e);
-  if (level_sigma_upper_limit < 0 || initial_state_variance < 0)
-    return fail(BA_E_INVALID, "sigma_max must be non-negative.");
-  // ChisqModel(df, sigma_guess): 2 alpha = df, 2 beta = df sigma^2
-  e->level_prior_df = 2 * (level_df / 2.0);
-  e->level_prior_ss = 2 * (level_df * level_sigma_guess * level_sigma_guess / 2.0);
-  e->level_sigma_max = level_sigma_upper_limit;
-  e->ss_a0 = initial_state_mean;
-  e->ss_P0 = initial_state_variance;
-  e->ss_initial_level_sigsq = initial_level_sigma * initial_level_sigma;
-  e->ss_level_set = true;
-  e->ssm_set = false;
-  e->dss_scratch.release();
-  return BA_OK;
-}
-
 }  // extern "C"
-
-namespace {
-// the scalars of the specification that follow from the block list
-void ssg_finish(SsgSpec &q) {
-  // P's leading dimension: odd (a lane per column and a lane per row both conflict-free), and
-  // one of the four values ssg_simsmooth_kernel is compiled for
-  q.ld = q.m <= 16 ? 17 : (q.m <= 32 ? 33 : (q.m <= 60 ? 61 : 65));
-  // state-error rows: one per variance slot, except that a trig block's every component has one
-  q.nerr = 0;
-  for (int i = 0; i < q.nblocks; ++i) {
-    q.blk[i].err0 = q.nerr;
-    q.nerr += q.blk[i].kind == SSG_TRIG ? q.blk[i].dim
-              : ((q.blk[i].kind == SSG_LOCAL_LINEAR_TREND || q.blk[i].kind == SSG_SEMILOCAL) ? 2 : 1);
-  }
-  // steps per block of the passes: the most that leaves FOUR workgroups to a CU's 160 KB of
-  // LDS (all 1024 chains of a launch resident; at m = 59 sixteen steps left room for three,
-  // and the launch ran as two rounds), never below 8; see ssg_pass_lds_doubles
-  q.bl = 64;
-  while (q.bl > 8 && (2 * q.bl * q.m + q.m * q.ld + q.bl * (q.nerr + 1) + SSG_MAX_STATE + 8 +
-                      q.nar * AR_MAX * (AR_MAX + 1)) * 8 > 39 * 1024)
-    q.bl /= 2;
-}
-// ArModel's constructor: "Attempt to initialize ArModel with an illegal value of the
-// autoregression coefficients." (the quick bound, then the step-down recursion)
-bool ar_stationary_host(const double *phi, int lags) {
-  double a[AR_MAX], b[AR_MAX], sum = 0;
-  for (int i = 0; i < lags; ++i) { a[i] = phi[i]; sum += std::fabs(a[i]); }
-  if (sum < 1) return true;
-  for (int k = lags; k >= 1; --k) {
-    const double r = a[k - 1];
-    if (!(std::fabs(r) < 1)) return false;
-    for (int j = 0; j + 1 < k; ++j) b[j] = (a[j] + r * a[k - 2 - j]) / (1 - r * r);
-    for (int j = 0; j + 1 < k; ++j) a[j] = b[j];
-  }
-  return true;
-}
-// the Philox sampler id of variance parameter v of the block about to be appended: level 1,
-// slope 6, seasonal 7, autoregression 12 for the first block of its family (local level
-// and local linear trend are one family), + 16 for every earlier block of the family
-int ssg_stream_id(const SsgSpec &q, int kind, int v) {
-  // (a semilocal trend's level variance is of the level family; its NonzeroMeanAr1Sampler a
-  // family of its own, id 14)
-  if (kind == SSG_SEMILOCAL && v == 1) {
-    int occ = 0;
-    for (int i = 0; i < q.nblocks; ++i) occ += q.blk[i].kind == SSG_SEMILOCAL;
-    return 14 + 16 * occ;
-  }
-  auto family = [](int k) { return (k == SSG_LOCAL_LINEAR_TREND || k == SSG_SEMILOCAL) ? (int)SSG_LOCAL_LEVEL : k; };
-  const int fam = family(kind);
-  int occ = 0;
-  for (int i = 0; i < q.nblocks; ++i) {
-    const int k = q.blk[i].kind;
-    if (q.blk[i].nvar == 0) continue;   // (a static intercept has no sampler: it is in no family)
-    if (family(k) == fam) ++occ;
-  }
-  const int base = kind == SSG_SEASONAL ? 7 : (kind == SSG_AR ? 12 : (kind == SSG_TRIG ? 13 : (v == 0 ? 1 : 6)));
-  return base + 16 * occ;
-}
-// model->add_state(...) on the engine's copy of the specification
-int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const double *var_df,
-            const double *var_sigma_guess, const double *var_sigma_upper_limit,
-            const double *var_initial_sigma, const double *initial_phi,
-            const double *initial_state_mean, const double *initial_state_variance) {
-  SsgSpec &q = e->ssg;
-  const bool is_static = kind == SSG_STATIC_INTERCEPT;   // (no parameter: the var_* arrays are not read)
-  if ((!is_static && (!var_df || !var_sigma_guess || !var_sigma_upper_limit || !var_initial_sigma)) ||
-      !initial_state_mean || !initial_state_variance)
-    return fail(BA_E_INVALID, "null argument");
-  if (q.nblocks >= SSG_MAX_BLOCKS) return fail(BA_E_INVALID, "more than 8 state models");
-  SsgBlock k{};
-  k.kind = kind;
-  k.nvar = 1;
-  k.duration = 1;
-  k.ar_index = -1;
-  switch (kind) {
-    case SSG_LOCAL_LEVEL: k.dim = 1; break;
-    case SSG_LOCAL_LINEAR_TREND: k.dim = 2; k.nvar = 2; break;
-    case SSG_SEASONAL: {
-      if (!iparams) return fail(BA_E_INVALID, "null argument");
-      // SeasonalStateModelBase: "'nseasons' must be positive"; one season has no state
-      if (iparams[0] < 2) return fail(BA_E_INVALID, "nseasons must be at least 2");
-      if (iparams[1] < 1) return fail(BA_E_INVALID, "season_duration must be positive");
-      // (the kernels keep a block's duration and its running phase in 16-bit fields)
-      if (iparams[1] > 65535) return fail(BA_E_INVALID, "season_duration exceeds 65535");
-      k.nseasons = iparams[0];
-      k.duration = iparams[1];
-      // new_season(t): (t - time_of_first_observation) is a multiple of the duration
-      k.phase = ((iparams[2] % k.duration) + k.duration) % k.duration;
-      k.dim = k.nseasons - 1;
-      break;
-    }
-    case SSG_STATIC_INTERCEPT:
-      // StaticInterceptStateModel: T = 1, RQR = 0, nothing to learn and no sampler -- a local
-      // level whose variance (a slot of its own, never drawn) is 0
-      k.kind = SSG_LOCAL_LEVEL;
-      k.dim = 1;
-      k.nvar = 0;
-      break;
-    case SSG_TRIG:
-      // TrigStateModel: "At least one frequency needed ..."; the rotations as the transition
-      // matrix holds them: (cos, sin) per frequency in initial_phi
-      if (!iparams || !initial_phi) return fail(BA_E_INVALID, "null argument");
-      if (iparams[0] < 1) return fail(BA_E_INVALID, "At least one frequency needed to initialize TrigStateModel.");
-      if (2 * iparams[0] > SSG_MAX_STATE) return fail(BA_E_INVALID, "state dimension exceeds 64");
-      k.nfreq = iparams[0];
-      k.dim = 2 * k.nfreq;
-      break;
-    case SSG_SEMILOCAL:
-      // SemilocalLinearTrendStateModel(level, slope): iparams = {force_stationary,
-      // force_ar1_positive}; initial_phi = {slope mean prior mu, sigma, AR(1) coefficient prior mu,
-      // sigma, initial mu, initial phi}
-      if (!iparams || !initial_phi) return fail(BA_E_INVALID, "null argument");
-      if (iparams[1] && !iparams[0])
-        return fail(BA_E_INVALID, "force_ar1_positive without force_stationary (a one-sided truncation of the slope's "
-                                  "AR(1) coefficient) is not built");
-      if (!(initial_phi[1] > 0) || !(initial_phi[3] > 0)) return fail(BA_E_INVALID, "the slope's prior standard deviations must be positive");
-      if (q.nar >= SSG_MAX_AR) return fail(BA_E_INVALID, "more than 4 autoregression / semilocal state models");
-      k.dim = 3;
-      k.nvar = 2;
-      k.ar_index = q.nar;
-      k.sl_truncate = iparams[0] != 0;
-      k.sl_positive = iparams[1] != 0;
-      break;
-    case SSG_AR:
-      if (!iparams) return fail(BA_E_INVALID, "null argument");
-      if (iparams[0] < 1) return fail(BA_E_INVALID, "lags must be positive");
-      if (iparams[0] > AR_MAX) return fail(BA_E_INVALID, "more than 16 lags");
-      if (q.nar >= SSG_MAX_AR) return fail(BA_E_INVALID, "more than 4 autoregression state models");
-      k.lags = iparams[0];
-      k.dim = k.lags;
-      k.ar_index = q.nar;
-      break;
-    default:
-      return fail(BA_E_INVALID, "state model kind must be 1 (local level), 2 (local linear trend), 3 (seasonal), 4 (autoregression), 5 (static intercept), 6 (trig) or 7 (semilocal linear trend)");
-  }
-  const int nslot = is_static ? 1 : k.nvar;   // variance slots the block takes
-  if (q.m + k.dim > SSG_MAX_STATE) return fail(BA_E_INVALID, "state dimension exceeds 64");
-  if (q.nvar + nslot > SSG_MAX_VAR) return fail(BA_E_INVALID, "more than 16 variance parameters");
-  for (int v = 0; v < k.nvar; ++v) {
-    if (var_sigma_upper_limit[v] < 0) return fail(BA_E_INVALID, "sigma_max must be non-negative.");
-    if ((kind == SSG_AR || kind == SSG_SEMILOCAL) && !(var_initial_sigma[v] > 0))
-      return fail(BA_E_INVALID, "initial sigma must be positive");
-  }
-  for (int i = 0; i < k.dim; ++i) {
-    // (a multivariate initial state goes through a Cholesky factor in the reference: it
-    // needs a positive variance; the local level model alone does not)
-    const bool ok = initial_state_variance[i] > 0.0 ||
-                    ((kind == SSG_LOCAL_LEVEL || is_static) && initial_state_variance[i] == 0.0) ||
-                    (kind == SSG_SEMILOCAL && i == 2);   // (the slope's long-run mean: a parameter, variance 0 whatever is passed)
-    if (!ok) return fail(BA_E_INVALID, "initial state variances must be positive");
-  }
-  if (kind == SSG_AR && initial_phi && !ar_stationary_host(initial_phi, k.lags))
-    return fail(BA_E_INVALID, "the initial autoregression coefficients are not stationary");
-  k.first = q.m;
-  k.var0 = q.nvar;
-  for (int v = 0; v < k.nvar; ++v) {
-    const int vi = k.var0 + v;
-    // ChisqModel(df, sigma_guess): 2 alpha = df, 2 beta = df sigma^2
-    q.prior_df[vi] = 2 * (var_df[v] / 2.0);
-    q.prior_ss[vi] = 2 * (var_df[v] * var_sigma_guess[v] * var_sigma_guess[v] / 2.0);
-    q.sigma_max[vi] = var_sigma_upper_limit[v];
-    e->ssg_initial_sigsq[vi] = var_initial_sigma[v] * var_initial_sigma[v];
-    k.sid[v] = ssg_stream_id(q, kind, v);
-  }
-  if (is_static) {
-    // (the slot: variance 0, a sampler that is never run)
-    q.prior_df[k.var0] = 0.0;
-    q.prior_ss[k.var0] = 0.0;
-    q.sigma_max[k.var0] = std::numeric_limits<double>::infinity();
-    e->ssg_initial_sigsq[k.var0] = 0.0;
-  }
-  for (int i = 0; i < k.dim; ++i) {
-    q.a0[k.first + i] = initial_state_mean[i];
-    q.P0[k.first + i] = initial_state_variance[i];
-    q.trig_c[k.first + i] = kind == SSG_TRIG ? initial_phi[2 * (i / 2)] : 0.0;
-    q.trig_s[k.first + i] = kind == SSG_TRIG ? initial_phi[2 * (i / 2) + 1] : 0.0;
-  }
-  if (kind == SSG_AR) {
-    for (int i = 0; i < AR_MAX; ++i)
-      e->ssg_initial_phi[k.ar_index][i] = (initial_phi && i < k.lags) ? initial_phi[i] : 0.0;
-    q.nar += 1;
-  }
-  if (kind == SSG_SEMILOCAL) {
-    for (int i = 0; i < AR_MAX; ++i) e->ssg_initial_phi[k.ar_index][i] = 0.0;
-    e->ssg_initial_phi[k.ar_index][0] = initial_phi[5];   // phi
-    e->ssg_initial_phi[k.ar_index][1] = initial_phi[4];   // mu
-    for (int i = 0; i < 4; ++i) q.sl_prior[k.ar_index][i] = initial_phi[i];
-    // initial_state_mean()[2] = slope->mu() (per chain, per draw: the kernel's), variance 0
-    q.a0[k.first + 2] = initial_phi[4];
-    q.P0[k.first + 2] = 0.0;
-    q.nar += 1;
-  }
-  q.blk[q.nblocks] = k;
-  q.nblocks += 1;
-  q.m += k.dim;
-  q.nvar += nslot;
-  ssg_finish(q);
-  e->ssm_set = true;
-  e->ss_level_set = false;
-  e->dss_scratch.release();
-  return BA_OK;
-}
-void ssg_clear(ba_engine *e) {
-  e->ssg = SsgSpec{};
-  for (int i = 0; i < 3; ++i) e->ssg_template_var[i] = -1;
-  e->ssg_template_ar = -1;
-  e->ssm_set = false;
-  e->dss_scratch.release();
-}
-}  // namespace
-
-extern "C" {
-
-// for the tests of the spill streams (device_rng.h): a slot of a substream hands out `uniforms`
-// numbers, not its whole stride (0: the default again).  Changes the draws.
-int ba_set_slot_limit(ba_engine *e, int32_t uniforms) {
-  if (!e) return fail(BA_E_INVALID, "null engine");
-  if (uniforms < 0 || (uniforms & 1)) return fail(BA_E_INVALID, "uniforms must be even and non-negative");
-  MUTATE(e);
-  e->slot_limit = uniforms;
-  return BA_OK;
-}
-
-// diagnostic, changes no draw: 0 = the general kernel also where the shape-specialised one
-// applies (the two are compared by the tests), 1 = the default
-int ba_ss_set_tuning(ba_engine *e, int32_t kernel) {
-  if (!e) return fail(BA_E_INVALID, "null engine");
-  if (kernel < 0 || kernel > 7 || kernel == 2)
-    return fail(BA_E_INVALID, "kernel must be 0, 1, 3, 4, 5, 6 or 7 (2, four chains per wavefront, was removed: it never won)");
-  MUTATE(e);
-  // 4 / 5: the local-level rounds as the separate launches of rounds 1-4 / as the round
-  // kernel (the default where it applies); the structural kernels' choice stays
-  // 6 / 7: the round kernel's diagnostic notes (printed when a chain stops) on / off
-  if (kernel >= 6) e->round_debug = kernel == 6;
-  else if (kernel >= 4) e->ss_round_enabled = kernel == 5;
-  else e->ssg_kernel_choice = kernel;
-  return BA_OK;
-}
-
-int ba_ss_clear_state_models(ba_engine *e) {
-  if (!e) return fail(BA_E_INVALID, "null engine");
-  MUTATE(e);
-  ssg_clear(e);
-  return BA_OK;
-}
-
-int ba_ss_add_state_model(ba_engine *e, int32_t kind, const int32_t *iparams, const double *var_df,
-                          const double *var_sigma_guess, const double *var_sigma_upper_limit,
-                          const double *var_initial_sigma, const double *initial_phi,
-                          const double *initial_state_mean, const double *initial_state_variance) {
-  if (!e) return fail(BA_E_INVALID, "null engine");
-  MUTATE(e);
-  if (e->ss_level_set) ssg_clear(e);   // (a local-level specification is replaced, not extended)
-  e->ss_level_set = false;
-  return ssg_add(e, kind, iparams, var_df, var_sigma_guess, var_sigma_upper_limit, var_initial_sigma,
-                 initial_phi, initial_state_mean, initial_state_variance);
-}
-
-int ba_ss_state_dimension(ba_engine *e, int32_t *state_dimension, int32_t *nblocks) {
-  if (!e) return fail(BA_E_INVALID, "null engine");
-  if (state_dimension) *state_dimension = e->ssm_set ? e->ssg.m : (e->ss_level_set ? 1 : 0);
-  if (nblocks) *nblocks = e->ssm_set ? e->ssg.nblocks : (e->ss_level_set ? 1 : 0);
-  return BA_OK;
-}
-
-int ba_ss_set_structural(ba_engine *e, int32_t trend, int32_t nseasons, const double *var_df,
-                         const double *var_sigma_guess, const double *var_sigma_upper_limit,
-                         const double *var_initial_sigma, const double *initial_state_mean,
-                         const double *initial_state_variance) {
-  if (!e) return fail(BA_E_INVALID, "null engine");
-  MUTATE(e);
-  if (!var_df || !var_sigma_guess || !var_sigma_upper_limit || !var_initial_sigma ||
-      !initial_state_mean || !initial_state_variance)
-    return fail(BA_E_INVALID, "null argument");
-  if (trend != 1 && trend != 2) return fail(BA_E_INVALID, "trend must be 1 (local level) or 2 (local linear trend)");
-  if (nseasons != 0 && nseasons < 2) return fail(BA_E_INVALID, "nseasons must be 0 or at least 2");
-  const int m = trend + (nseasons > 0 ? nseasons - 1 : 0);
-  if (m > SSG_MAX_STATE) return fail(BA_E_INVALID, "state dimension exceeds 64");
-  for (int i = 0; i < 3; ++i) {
-    const bool used = i == 0 || (i == 1 && trend == 2) || (i == 2 && nseasons > 0);
-    if (used && var_sigma_upper_limit[i] < 0) return fail(BA_E_INVALID, "sigma_max must be non-negative.");
-  }
-  ssg_clear(e);
-  int rc = ssg_add(e, trend == 2 ? SSG_LOCAL_LINEAR_TREND : SSG_LOCAL_LEVEL, nullptr, var_df, var_sigma_guess,
-                   var_sigma_upper_limit, var_initial_sigma, nullptr, initial_state_mean, initial_state_variance);
-  if (!rc && nseasons > 0) {
-    const int32_t ip[3] = {nseasons, 1, 0};
-    rc = ssg_add(e, SSG_SEASONAL, ip, var_df + 2, var_sigma_guess + 2, var_sigma_upper_limit + 2,
-                 var_initial_sigma + 2, nullptr, initial_state_mean + trend, initial_state_variance + trend);
-  }
-  if (rc) {
-    ssg_clear(e);
-    return rc;
-  }
-  e->ssg_template_var[0] = 0;
-  e->ssg_template_var[1] = trend == 2 ? 1 : -1;
-  e->ssg_template_var[2] = nseasons > 0 ? trend : -1;
-  return BA_OK;
-}
-
-int ba_ss_add_ar(ba_engine *e, int32_t lags, double prior_df, double sigma_guess,
-                 double sigma_upper_limit, double initial_sigma, const double *initial_phi,
-                 const double *initial_state_mean, const double *initial_state_variance) {
-  if (!e) return fail(BA_E_INVALID, "null engine");
-  MUTATE(e);
-  if (!e->ssm_set) return fail(BA_E_STATE, "call ba_ss_set_structural first");
-  if (e->ssg_template_ar >= 0) return fail(BA_E_STATE, "the state already has an autoregression block");
-  if (!initial_state_mean || !initial_state_variance) return fail(BA_E_INVALID, "null argument");
-  if (lags < 1) return fail(BA_E_INVALID, "lags must be positive");
-  const int32_t ip[3] = {lags, 0, 0};
-  const int rc = ssg_add(e, SSG_AR, ip, &prior_df, &sigma_guess, &sigma_upper_limit, &initial_sigma, initial_phi,
-                         initial_state_mean, initial_state_variance);
-  if (rc) return rc;
-  e->ssg_template_ar = e->ssg.nblocks - 1;
-  return BA_OK;
-}
-
-// block `block` of one chain: its variance parameters, the state model's sufficient
-// statistics of the last sweep, and for an autoregression block its coefficients and ArModel
-// sufficient statistics
-int ba_ss_get_state_model(ba_engine *e, int64_t chain, int32_t block, double *variances, double *suf_n,
-                          double *suf_ss, double *phi, double *ar_xtx, double *ar_xty, double *ar_yty,
-                          double *ar_n) {
-  ENGINE_ACCESSOR_SERVED(e);
-  if (!e->ss_mode || !e->ssm_set || e->dssm_work.count == 0)
-    return fail(BA_E_STATE, "no structural state-space run yet");
-  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
-  if (block < 0 || block >= e->ssg.nblocks) return fail(BA_E_INVALID, "state model index out of range");
-  const SsgBlock &k = e->ssg.blk[block];
-  const bool is_sl = k.kind == SSG_SEMILOCAL;
-  const bool is_ar = k.kind == SSG_AR || is_sl;   // (both keep coefficients and statistics in an autoregression slot)
-  if (!is_ar && (phi || ar_xtx || ar_xty || ar_yty || ar_n))
-    return fail(BA_E_INVALID, "not an autoregression state model");
-  if (is_sl && (ar_xty || ar_yty))
-    return fail(BA_E_INVALID, "a semilocal linear trend's Ar1Suf comes back through ar_xtx (six doubles) and ar_n");
-  if (ss_la_serving(e)) {
-    if (!suf_n && !suf_ss && !ar_xtx && !ar_xty && !ar_yty && !ar_n) {
-      // the draw ba_ss_draw_next is serving, from the record
-      const ba_engine::SsLa::Rows *r = nullptr;
-      int rcr = ss_la_rows(e, chain, false, &r);
-      if (rcr) return rcr;
-      const size_t row = (size_t)e->ssla.served - 1;
-      if (variances)
-        for (int v = 0; v < k.nvar; ++v) variances[v] = r->var[row * e->ssla.nvar + k.var0 + v];
-      if (phi)
-        for (int i = 0; i < (is_sl ? 2 : k.lags); ++i) phi[i] = r->phi[row * e->ssla.nphi + (size_t)k.ar_index * AR_MAX + i];
-      return BA_OK;
-    }
-    int rcs = ss_la_settle(e);   // (sufficient statistics are not in the record)
-    if (rcs) return rcs;
-  }
-  int rc = ba_sync(e);
-  if (rc) return rc;
-  HIP_TRY(pinned_reserve(e, (6 + AR_MAX + AR_SUF_STRIDE) * 8));
-  double *hv = (double *)e->pinned, *hphi = hv + 6, *hsuf = hphi + AR_MAX;
-  const size_t at = (size_t)chain * SSG_MAX_VAR + k.var0;
-  HIP_TRY(hipMemcpyAsync(hv, e->dssm_sigsq.ptr + at, (size_t)k.nvar * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(hv + 2, e->dssm_n.ptr + at, (size_t)k.nvar * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(hv + 4, e->dssm_ss.ptr + at, (size_t)k.nvar * 8, hipMemcpyDeviceToHost, e->stream));
-  if (is_ar) {
-    const size_t slot = (size_t)chain * SSG_MAX_AR + k.ar_index;
-    HIP_TRY(hipMemcpyAsync(hphi, e->dar_phi.ptr + slot * AR_MAX, AR_MAX * 8, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(hsuf, e->dar_suf.ptr + slot * AR_SUF_STRIDE, AR_SUF_STRIDE * 8, hipMemcpyDeviceToHost,
-                           e->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  for (int v = 0; v < k.nvar; ++v) {
-    if (variances) variances[v] = hv[v];
-    if (suf_n) suf_n[v] = hv[2 + v];
-    if (suf_ss) suf_ss[v] = hv[4 + v];
-  }
-  if (k.kind == SSG_SEMILOCAL) {
-    // (phi, mu) of the slope's NonzeroMeanAr1Model; its Ar1Suf -- sumsq, sum, cross, n, first,
-    // last value -- through ar_xtx (six doubles)
-    if (phi) { phi[0] = hphi[0]; phi[1] = hphi[1]; }
-    if (ar_xtx) std::memcpy(ar_xtx, hsuf, 6 * 8);
-    if (ar_n) *ar_n = hsuf[3];
-  } else if (is_ar) {
-    const int L = k.lags;
-    if (phi) std::memcpy(phi, hphi, (size_t)L * 8);
-    if (ar_xtx)
-      for (int i = 0; i < L; ++i)
-        for (int j = 0; j < L; ++j) ar_xtx[(size_t)j * L + i] = hsuf[(size_t)i * AR_MAX + j];
-    if (ar_xty) std::memcpy(ar_xty, hsuf + AR_SUF_XTY, (size_t)L * 8);
-    if (ar_yty) *ar_yty = hsuf[AR_SUF_YTY];
-    if (ar_n) *ar_n = hsuf[AR_SUF_N];
-  }
-  return BA_OK;
-}
-
-int ba_ss_get_ar(ba_engine *e, int64_t chain, double *phi, double *sigsq, double *suf_xtx,
-                 double *suf_xty, double *suf_yty, double *suf_n) {
-  if (!e) return fail(BA_E_INVALID, "null engine");
-  if (!e->ss_mode || !e->ssm_set || e->ssg_template_ar < 0 || e->dar_phi.count == 0)
-    return fail(BA_E_STATE, "no structural run with an autoregression block yet");
-  return ba_ss_get_state_model(e, chain, e->ssg_template_ar, sigsq, nullptr, nullptr, phi, suf_xtx, suf_xty,
-                               suf_yty, suf_n);
-}
-
-// one chain's state draw, T x m (step t at [t * m, (t + 1) * m))
-int ba_ss_get_state_draw(ba_engine *e, int64_t chain, double *state) {
-  ENGINE_ACCESSOR_SERVED(e);
-  if (!e->ss_mode || !e->ssm_set || e->dssm_work.count == 0)
-    return fail(BA_E_STATE, "no structural state-space run yet");
-  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
-  if (!state) return fail(BA_E_INVALID, "null argument");
-  if (ss_la_serving(e)) {
-    if (ss_la_registered(e, chain)) {
-      const ba_engine::SsLa::Rows *r = nullptr;
-      int rcr = ss_la_rows(e, chain, true, &r);
-      if (rcr) return rcr;
-      const size_t SD = e->ssla.state_doubles;
-      std::memcpy(state, &r->state[((size_t)e->ssla.served - 1) * SD], SD * 8);
-      return BA_OK;
-    }
-    ss_la_want_state(e, chain);
-    int rcs = ss_la_settle(e);
-    if (rcs) return rcs;
-  }
-  int rc = ba_sync(e);
-  if (rc) return rc;
-  const size_t T = (size_t)e->T, m = (size_t)e->ssg.m;
-  HIP_TRY(pinned_reserve(e, m * T * 8));
-  HIP_TRY(hipMemcpyAsync(e->pinned, e->dssm_work.ptr + (size_t)chain * ssm_work_stride(*e) + m * T, m * T * 8,
-                         hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  std::memcpy(state, e->pinned, m * T * 8);
-  return BA_OK;
-}
-
-int ba_ss_get_structural(ba_engine *e, int64_t chain, double *state, double *variances,
-                         double *suf_n, double *suf_ss) {
-  ENGINE_ACCESSOR_SERVED(e);
-  if (!e->ss_mode || !e->ssm_set || e->dssm_work.count == 0)
-    return fail(BA_E_STATE, "no structural state-space run yet");
-  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
-  if ((variances || suf_n || suf_ss) && e->ssg_template_var[0] < 0)
-    return fail(BA_E_STATE, "the state was not set with ba_ss_set_structural: use ba_ss_get_state_model");
-  if (ss_la_serving(e)) {
-    if (!suf_n && !suf_ss && (!state || ss_la_registered(e, chain))) {
-      const ba_engine::SsLa::Rows *r = nullptr;
-      int rcr = ss_la_rows(e, chain, state != nullptr, &r);
-      if (rcr) return rcr;
-      const size_t row = (size_t)e->ssla.served - 1, SD = e->ssla.state_doubles;
-      if (state) std::memcpy(state, &r->state[row * SD], SD * 8);
-      if (variances)
-        for (int i = 0; i < 3; ++i) {
-          const int vi = e->ssg_template_var[i];
-          variances[i] = vi >= 0 ? r->var[row * e->ssla.nvar + vi] : 0.0;
-        }
-      return BA_OK;
-    }
-    if (state) ss_la_want_state(e, chain);
-    int rcs = ss_la_settle(e);
-    if (rcs) return rcs;
-  }
-  if (state) {
-    const int rc = ba_ss_get_state_draw(e, chain, state);
-    if (rc) return rc;
-  }
-  int rc = ba_sync(e);
-  if (rc) return rc;
-  // (one batch through the pinned staging buffer: variances | n | sums of squares)
-  const size_t NV = SSG_MAX_VAR;
-  HIP_TRY(pinned_reserve(e, 3 * NV * 8));
-  double *hv = (double *)e->pinned;
-  HIP_TRY(hipMemcpyAsync(hv, e->dssm_sigsq.ptr + chain * NV, NV * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(hv + NV, e->dssm_n.ptr + chain * NV, NV * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(hv + 2 * NV, e->dssm_ss.ptr + chain * NV, NV * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  for (int i = 0; i < 3; ++i) {
-    const int vi = e->ssg_template_var[i];
-    // (an unused slot reports what it was given: the initial value, no statistics)
-    if (variances) variances[i] = vi >= 0 ? hv[vi] : 0.0;
-    if (suf_n) suf_n[i] = vi >= 0 ? hv[NV + vi] : 0.0;
-    if (suf_ss) suf_ss[i] = vi >= 0 ? hv[2 * NV + vi] : 0.0;
-  }
-  return BA_OK;
-}
-
-int ba_ss_impute_state(ba_engine *e) {
-  ENGINE_PROLOGUE(e);
-  e->table_ok = false;
-  int rc = ss_prepare(e);
-  if (rc) return rc;
-  SsParams S;
-  fill_ss_params(e, S);
-  HIP_TRY(launch_state_kernel(e, S, 0));
-  e->ss_initialized = true;
-  return BA_OK;
-}
-
-}  // extern "C"
-namespace {
-#ifdef BA_RSTAMPS
-double *g_round_stamps = nullptr;
-size_t g_round_stamps_n = 0;
-#endif
-// The round kernel (ss_round_kernel.hip) serves the local-level model on a series of at most
-// LM_TP steps while every chain is in the LDS sweep kernel's range; how many chains one launch
-// can take (0: the separate launches instead).
-int ss_round_chains(ba_engine *e) {
-  if (!e->ss_round_enabled || e->ssm_set || !ss_lane_major(*e) || e->big_active || e->cur_mode != 0) return 0;
-  if (e->kcap != 16 && e->kcap != 32 && e->kcap != 48) return 0;
-  int &res = e->ss_round_resident[e->kcap / 16];
-  if (res == 0) {
-    res = -1;
-    if (ss_round_lds(e->p, e->kcap) <= (size_t)e->lds_per_cu / 2) {   // (two chains to a CU at least)
-      SsvsParams P{};
-      SsParams S{};
-      SsRoundParams F{};
-      P.kcap = e->kcap;
-      P.p = e->p;
-      int n = 0;
-      if (launch_ss_round(e->stream, P, S, F, &n) == hipSuccess && n > 0) res = n;
-      if (e->round_debug) std::fprintf(stderr, "round kernel: kcap %d lds %zu resident %d\n", e->kcap, ss_round_lds(e->p, e->kcap), n);
-    }
-  }
-  return res > 0 ? std::min<int>(res, e->cfg.chains) : 0;
-}
-
-// `rounds` rounds of every chain: one launch per group of co-resident chains and per
-// SS_ROUND_MAX_ROUNDS rounds; round i of the call goes to row rec_first + i of the record
-int ss_round_launches(ba_engine *e, SsvsParams &P, SsParams &S, int rounds, int rec_slot) {
-  const int per = ss_round_chains(e), C = e->cfg.chains;
-  const size_t ctl = (size_t)SS_ROUND_MAX_ROUNDS * (1 + 2 * (size_t)per);   // (ticket | sizes | diagnostic variants: a done count per tile)
-  const size_t mem = (size_t)SS_ROUND_MAX_ROUNDS * ((size_t)per * SS_ROUND_TILE + 2 * SS_ROUND_TILE);
-  if (e->dround_ctl.count != ctl) HIP_TRY(e->dround_ctl.resize(ctl));
-  if (e->dround_members.count != mem) HIP_TRY(e->dround_members.resize(mem));
-  SsRoundParams F{};
-  F.close_ticks = 100000;   // 1 ms: a tile is short of members only when another launch shares the machine (ss_round_kernel.hip)
-  F.ticket = e->dround_ctl.ptr;
-  F.sizes = F.ticket + SS_ROUND_MAX_ROUNDS;
-  F.members = e->dround_members.ptr;
-  F.planes = e->dxte_planes.ptr;
-  if (e->round_debug) {
-    if (e->dround_debug.count == 0) {
-      HIP_TRY(e->dround_debug.resize(16 * 17 + 64));
-      HIP_TRY(hipMemset(e->dround_debug.ptr, 0, (16 * 17 + 64) * 4));
-    }
-    F.debug = e->dround_debug.ptr;
-  }
-#ifdef BA_RSTAMPS
-  {  // (diagnostic build: printed per call by tools/ss_round_phases.py through BA_RSTAMPS_DUMP)
-    static DevBuf<double> stamps;
-    if (stamps.count != (size_t)C * 16) {
-      HIP_TRY(stamps.resize((size_t)C * 16));
-      HIP_TRY(hipMemsetAsync(stamps.ptr, 0, (size_t)C * 16 * 8, e->stream));
-    }
-    F.stamps = stamps.ptr;
-    g_round_stamps = stamps.ptr;
-    g_round_stamps_n = (size_t)C * 16;
-  }
-#endif
-  if (rec_slot >= 0) {
-    ba_engine::SsLa &A = e->ssla;
-    F.rgamma = A.rgamma.ptr;
-    F.rbeta = A.rbeta.ptr;
-    F.rsig = A.rsig.ptr;
-    F.rvar = A.rvar.ptr;
-    F.rstate = A.rstate.ptr;
-    F.reg_of_chain = e->dround_reg.ptr;
-    F.rec_slot = rec_slot;
-    F.rec_len = A.len;
-    F.nreg = (int32_t)A.reg.size();
-  }
-  for (int g0 = 0; g0 < C; g0 += per) {
-    const int gc = std::min(per, C - g0);
-    SsvsParams Pg = P;
-    SsParams Sg = S;
-    Pg.chain_first = Sg.chain_first = g0;
-    Pg.chain_count = Sg.chain_count = gc;
-    for (int r0 = 0; r0 < rounds; r0 += SS_ROUND_MAX_ROUNDS) {
-      F.rounds = std::min<int>(SS_ROUND_MAX_ROUNDS, rounds - r0);
-      F.rec_first = r0;
-#ifdef BA_RSTAMPS
-      { static int seq = 0; F.debug_seq = ++seq; }
-#endif
-      HIP_TRY(hipMemsetAsync(e->dround_ctl.ptr, 0, ctl * 4, e->stream));
-      HIP_TRY(hipMemsetAsync(e->dround_members.ptr, 0xff, mem * 4, e->stream));
-      HIP_TRY(launch_ss_round(e->stream, Pg, Sg, F, nullptr));
-      Pg.model_keep = 1;   // (from here on the chains' model blocks are their own last launch's)
-    }
-  }
-  P.model_keep = 1;
-  e->model_ok = true;
-  return BA_OK;
-}
-
-// nsweeps x StateSpacePosteriorSampler::draw on every chain; rec_slot >= 0: every round's
-// draw goes to that half of the look-ahead's record
-int ss_sweep_impl(ba_engine *e, int32_t nsweeps, int rec_slot) {
-  e->table_ok = false;
-  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
-  int rc = ss_prepare(e);
-  if (rc) return rc;
-  SsvsParams P;
-  fill_params(e, P);
-  SsParams S;
-  fill_ss_params(e, S);
-  // StateSpacePosteriorSampler::draw (StateSpacePosteriorSampler.cpp:42-64)
-  if (!e->ss_initialized) {
-    HIP_TRY(launch_state_kernel(e, S, 0));
-    e->ss_initialized = true;
-  }
-  // The local-level state draw in two pieces: what does not depend on the round's
-  // regression sweep (level variance, the normals) is done ahead on a second stream into
-  // the chains' other normals buffer -- the step for round i + 1 goes out behind round
-  // i's state draw, beside its X'e GEMM, its plane sum and the start of round i + 1's
-  // SSVS launch (kalman_prepare_kernel).
-  if (nsweeps > 0 && ss_round_chains(e) > 0) return ss_round_launches(e, P, S, nsweeps, rec_slot);
-  const bool ahead = !e->ssm_set && nsweeps > 0;
-  if (ahead && !e->stream2) {
-    {
-      int rcs = concurrent_stream(e, &e->stream2);
-      if (rcs) return rcs;
-    }
-    HIP_TRY(hipEventCreateWithFlags(&e->ev_state, hipEventDisableTiming));
-    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&e->ev_prep[i], hipEventDisableTiming));
-  }
-  auto prepare_ahead = [&](int zbuf) -> hipError_t {
-    // (after everything enqueued on the main stream so far: the chains' status words of the
-    // sweep just launched, the buffer's last reader)
-    hipError_t err = hipEventRecord(e->ev_state, e->stream);
-    if (err != hipSuccess) return err;
-    err = hipStreamWaitEvent(e->stream2, e->ev_state, 0);
-    if (err != hipSuccess) return err;
-    SsParams A = S;
-    A.zbuf = zbuf;
-    err = launch_kalman_prepare(e->stream2, A, 1);
-    if (err != hipSuccess) return err;
-    return hipEventRecord(e->ev_prep[zbuf], e->stream2);
-  };
-  if (ahead) {
-    HIP_TRY(prepare_ahead(e->ss_zbuf));   // the call's first round: nothing to run beside
-    S.prepared = 1;
-  }
-  for (int i = 0; i < nsweeps; ++i) {
-    HIP_TRY(launch_sweeps(e, P, 1));                  // observation model
-    if (ahead) {
-      const int cur = e->ss_zbuf;
-      HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_prep[cur], 0));
-      S.zbuf = cur;
-      HIP_TRY(launch_kalman_main(e->stream, S, 1));   // state models, state
-      // (the state draw's wavefronts fill the register files -- 2 x 256 registers to a
-      // SIMD -- so a prepare step launched beside it only delays it: it goes out behind)
-      if (i + 1 < nsweeps) HIP_TRY(prepare_ahead(cur ^ 1));
-      // ... and the regression's X'e: inside a call the plane sum is left to the next
-      // round's sweep launch (one wave per chain on this path)
-      const bool fold = i + 1 < nsweeps && !e->big_active && e->waves == 1 && e->cur_mode != 2;
-      HIP_TRY(launch_kalman_xte(e->stream, S, fold));
-      P.xty_planes = fold ? e->dxte_planes.ptr : nullptr;
-      P.xty_nplanes = xte_planes((int64_t)S.TP);
-      P.xty_plane_stride = (int64_t)e->cfg.chains * e->p;
-      e->ss_zbuf = cur ^ 1;
-    } else {
-      HIP_TRY(launch_state_kernel(e, S, 1));          // state models, state
-    }
-    if (rec_slot >= 0) HIP_TRY(ss_la_record(e, rec_slot, i));
-    P.model_keep = 1;  // from here on the chains' model blocks are their own last launch's
-    e->model_ok = true;
-  }
-  return BA_OK;
-}
-
-}  // namespace
-extern "C" {
-
-int ba_ss_sweep(ba_engine *e, int32_t nsweeps) {
-  ENGINE_PROLOGUE(e);   // (unserved look-ahead draws: the rounds asked for here come after the last one served)
-  return ss_sweep_impl(e, nsweeps, -1);
-}
-
-// The callers' loop on the bsts path -- for (i in niter) { model.sample_posterior(); record }
-// (Interfaces/R/bsts/src/bsts.cc:82-119) -- at the device's rate: rounds are enqueued
-// `lookahead` at a time, every round's draw recorded on the device, and ba_ss_draw_next
-// hands them out one per call; the accessors below see the draw being served.
-int ba_ss_set_lookahead(ba_engine *e, int32_t lookahead) {
-  ENGINE_PROLOGUE(e);
-  if (lookahead < 1) return fail(BA_E_INVALID, "lookahead must be at least 1");
-  MUTATE(e);
-  {
-    // the record: two halves x chains x rounds x (gamma + beta [+ variances, coefficients]);
-    // a look-ahead it has no room for (p = 4096 with 1024 chains: 75 MB a round) is cut
-    // down to what 2 GiB hold rather than failing in hipMalloc
-    const double per_round = 2.0 * (double)e->cfg.chains * ((double)std::max(e->p, 1) * 9.0 + 8.0 * (SSG_MAX_VAR + SSG_MAX_AR * AR_MAX + 1));
-    const double budget = 2147483648.0;
-    if ((double)lookahead * per_round > budget) lookahead = std::max<int32_t>(1, (int32_t)(budget / per_round));
-  }
-  e->ssla.len = lookahead;
-  e->ssla.cur = 0;
-  e->ssla.calm = 0;
-  e->ssla.probe_wait = 16;
-  ss_la_reset(e);
-  return BA_OK;
-}
-
-// the chains whose STATE PATH the look-ahead records (default: chain 0); the other chains'
-// state is read by going back to the draw being served (correct, and slow)
-int ba_ss_lookahead_chains(ba_engine *e, int32_t nchains, const int64_t *chains) {
-  ENGINE_PROLOGUE(e);
-  if (nchains < 0 || (nchains > 0 && !chains)) return fail(BA_E_INVALID, "bad argument");
-  for (int i = 0; i < nchains; ++i)
-    if (chains[i] < 0 || chains[i] >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
-  MUTATE(e);
-  e->ssla.reg.clear();
-  e->ssla.want.clear();
-  for (int i = 0; i < nchains; ++i) e->ssla.reg.push_back((int32_t)chains[i]);
-  ss_la_reset(e);
-  return BA_OK;
-}
-
-int ba_ss_draw_next(ba_engine *e) {
-  ENGINE_PROLOGUE_NOJOIN(e);
-  {
-    int rcj = pipe_join(e);
-    if (rcj) return rcj;
-  }
-  ba_engine::SsLa &A = e->ssla;
-  if (A.len <= 1) return ss_sweep_impl(e, 1, -1);
-  if (A.cur <= 1) {
-    // (every draw of late was followed by something the record could not serve: one round
-    // per call, and another try with a batch of two after a while)
-    if (A.cur < 1) A.cur = A.len;   // (first call after ba_ss_set_lookahead)
-    else {
-      if (++A.calm >= A.probe_wait) { A.cur = 2; A.calm = 0; }
-      return ss_sweep_impl(e, 1, -1);
-    }
-  }
-  if (A.served == A.avail) {
-    if (A.avail > 0 && A.clean) {   // a batch served to its end in peace
-      A.cur = std::min(A.len, A.cur * 2);
-      A.probe_wait = 16;
-    }
-    A.clean = true;
-    if (A.ahead) {
-      // the record is used up: on to the batch that is already running (or done)
-      A.slot ^= 1;
-      A.ahead = false;
-      A.avail = A.ahead_len;
-    } else {
-      // ... or from the chains' current state
-      int rc = ss_la_settle(e);
-      if (!rc) rc = la_rewind(e);
-      if (!rc) rc = ss_prepare(e);
-      if (!rc) rc = ss_la_alloc(e);
-      // (the first impute_state of a run, if it is still to come, is not part of a batch:
-      // a batch's snapshot is a point between two rounds)
-      if (!rc) rc = ss_sweep_impl(e, 0, -1);
-      if (rc) return rc;
-      A.slot = 0;
-      rc = ss_la_launch(e, 0);
-      if (rc) return rc;
-      A.avail = A.cur;
-    }
-    A.served = 0;
-    A.synced = false;
-    A.cache.clear();
-    // the batch after this one goes out now, into the other half
-    A.ahead_len = A.cur;
-    int rc = ss_la_launch(e, A.slot ^ 1);
-    if (rc) return rc;
-    A.ahead = true;
-  }
-  ++A.served;
-  return BA_OK;
-}
-
-int ba_ss_forecast(ba_engine *e, int32_t horizon, const double *newX, double *out) {
-  ENGINE_PROLOGUE(e);
-  if (!newX || !out || horizon <= 0) return fail(BA_E_INVALID, "bad argument");
-  if (!e->ss_mode || e->dss_scratch.count == 0 || !e->ss_initialized)
-    return fail(BA_E_STATE, "no state draw yet: run ba_ss_sweep or ba_ss_impute_state first");
-  int rc = ba_sync(e);
-  if (rc) return rc;
-  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, h = (size_t)horizon;
-  DevBuf<double> dnx, dout;
-  HIP_TRY(dnx.resize(h * p));
-  HIP_TRY(dout.resize(C * h));
-  HIP_TRY(hipMemcpyAsync(dnx.ptr, newX, h * p * 8, hipMemcpyHostToDevice, e->stream));
-  SsParams S;
-  fill_ss_params(e, S);
-  if (e->ssm_set)
-    HIP_TRY(launch_ssm_forecast(e->stream, S, horizon, dnx.ptr, e->dpos_forecast.ptr, dout.ptr));
-  else
-    HIP_TRY(launch_ss_forecast(e->stream, S, horizon, dnx.ptr, e->dpos_forecast.ptr, dout.ptr));
-  HIP_TRY(hipMemcpyAsync(out, dout.ptr, C * h * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return BA_OK;
-}
-
-int ba_ss_get_state(ba_engine *e, int64_t chain, double *state,
-                    double *level_sigsq, double *level_n, double *level_sumsq) {
-  ENGINE_ACCESSOR_SERVED(e);
-  if (!e->ss_mode || e->dss_scratch.count == 0) return fail(BA_E_STATE, "no state-space run yet");
-  if (e->ssm_set) return fail(BA_E_STATE, "a structural state is set: use ba_ss_get_structural");
-  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
-  if (ss_la_serving(e)) {
-    if (!level_n && !level_sumsq && (!state || ss_la_registered(e, chain))) {
-      // the draw ba_ss_draw_next is serving, from the record
-      const ba_engine::SsLa::Rows *r = nullptr;
-      int rcr = ss_la_rows(e, chain, state != nullptr, &r);
-      if (rcr) return rcr;
-      const size_t row = (size_t)e->ssla.served - 1, T = (size_t)e->T, SD = e->ssla.state_doubles;
-      if (level_sigsq) *level_sigsq = r->var[row];
-      if (state) {
-        const double *src = &r->state[row * SD];
-        if (ss_lane_major(*e)) {
-          for (size_t t = 0; t < T; ++t) state[t] = src[(size_t)lm_at((int)t)];
-        } else {
-          std::memcpy(state, src, T * 8);
-        }
-      }
-      return BA_OK;
-    }
-    if (state) ss_la_want_state(e, chain);
-    int rcs = ss_la_settle(e);   // (not in the record: the chains go back to the draw being served)
-    if (rcs) return rcs;
-  }
-  int rc = ba_sync(e);
-  if (rc) return rc;
-  // (one batch through the pinned staging buffer: state | level variance | n | sum of squares)
-  const size_t T = (size_t)e->T, TP = ss_pitch(*e);
-  HIP_TRY(pinned_reserve(e, (TP + 3) * 8));
-  double *hstate = (double *)e->pinned, *hl = hstate + TP;
-  if (state)
-    HIP_TRY(hipMemcpyAsync(hstate, e->dss_scratch.ptr + ((size_t)chain * SS_SCRATCH_ARRAYS + SS_STATE_ARRAY) * TP,
-                           (ss_lane_major(*e) ? TP : T) * 8, hipMemcpyDeviceToHost, e->stream));
-  if (level_sigsq) HIP_TRY(hipMemcpyAsync(hl, e->dlev_sigsq.ptr + chain, 8, hipMemcpyDeviceToHost, e->stream));
-  if (level_n) HIP_TRY(hipMemcpyAsync(hl + 1, e->dlev_n.ptr + chain, 8, hipMemcpyDeviceToHost, e->stream));
-  if (level_sumsq) HIP_TRY(hipMemcpyAsync(hl + 2, e->dlev_sumsq.ptr + chain, 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (state) {
-    if (ss_lane_major(*e)) {
-      for (size_t t = 0; t < T; ++t) state[t] = hstate[(size_t)lm_at((int)t)];
-    } else {
-      std::memcpy(state, hstate, T * 8);
-    }
-  }
-  if (level_sigsq) *level_sigsq = hl[0];
-  if (level_n) *level_n = hl[1];
-  if (level_sumsq) *level_sumsq = hl[2];
-  return BA_OK;
-}
-
-int ba_ss_set_level_sigsq(ba_engine *e, int64_t chain, double sigsq) {
-  ENGINE_PROLOGUE(e);
-  MUTATE(e);
-  int rc = ss_prepare(e);
-  if (rc) return rc;
-  const int64_t C = e->cfg.chains;
-  if (chain < -1 || chain >= C) return fail(BA_E_INVALID, "chain index out of range");
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (chain < 0) {
-    std::vector<double> v((size_t)C, sigsq);
-    HIP_TRY(hipMemcpy(e->dlev_sigsq.ptr, v.data(), (size_t)C * 8, hipMemcpyHostToDevice));
-  } else {
-    HIP_TRY(hipMemcpy(e->dlev_sigsq.ptr + chain, &sigsq, 8, hipMemcpyHostToDevice));
-  }
-  return BA_OK;
-}
-
-int ba_ss_get_chain_suf(ba_engine *e, int64_t chain, double *xty, double *yty,
-                        double *n) {
-  ENGINE_PROLOGUE(e);
-  if (!e->ss_mode || e->dxty_c.count == 0) return fail(BA_E_STATE, "no state-space run yet");
-  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
-  int rc = ba_sync(e);
-  if (rc) return rc;
-  const size_t p = (size_t)e->p;
-  if (xty) HIP_TRY(hipMemcpy(xty, e->dxty_c.ptr + (size_t)chain * p, p * 8, hipMemcpyDeviceToHost));
-  if (yty) HIP_TRY(hipMemcpy(yty, e->dyty_c.ptr + chain, 8, hipMemcpyDeviceToHost));
-  if (n) HIP_TRY(hipMemcpy(n, e->dnobs_c.ptr + chain, 8, hipMemcpyDeviceToHost));
-  return BA_OK;
-}
-
-}  // extern "C"
-
-#ifdef BA_RSTAMPS
-// diagnostic build only (tools/build/libboomamd_rstamps.so): the round kernel's phase ticks
-// since the last call, chains x 2 x 8, and reset
-extern "C" int ba_debug_round_stamps(double *out, int64_t n) {
-  using namespace boom_amd;
-  if (!g_round_stamps) return -1;
-  const size_t m = std::min<size_t>((size_t)n, g_round_stamps_n);
-  if (hipDeviceSynchronize() != hipSuccess) return -2;
-  if (hipMemcpy(out, g_round_stamps, m * 8, hipMemcpyDeviceToHost) != hipSuccess) return -2;
-  if (hipMemset(g_round_stamps, 0, g_round_stamps_n * 8) != hipSuccess) return -2;
-  return (int)m;
-}
-#endif

@@ -1,0 +1,584 @@
+// Host side of the latent-data families: BinomialProbit-, BinomialLogit-, PoissonRegression-
+// and TRegressionSpikeSlabSampler.  Each imputes its latent data (probit_kernel.hip,
+// student_kernel.hip) and lets the SpikeSlabSampler sweep draw indicators and coefficients on
+// the imputed regression; the logit, Poisson and Student-t samplers keep every chain's own
+// V = slab precision + X'WX, built a vector at a time (the column service, xtwx_cols_kernel.hip).
+#include "engine_internal.h"
+
+namespace boom_amd {
+
+// the vectors of V named by dlogit_req[0, R), in batches the planes can hold
+static int build_columns(ba_engine *e, int64_t R) {
+  const int64_t n = e->probit_n;
+  for (int64_t r0 = 0; r0 < R; r0 += e->logit_req_batch) {
+    const int64_t nr = std::min<int64_t>(e->logit_req_batch, R - r0);
+    HIP_TRY(launch_xtwx_cols(e->stream, e->dprob_X.ptr, n, e->p, e->dlogit_w.ptr,
+                             e->dlogit_req.ptr + 2 * r0, (int)nr, e->dA.ptr, e->dlogit_V.ptr,
+                             e->dlogit_valid.ptr, e->logit_words, e->dlogit_planes.ptr));
+  }
+  return BA_OK;
+}
+
+// Chains of the logit sampler parked at "add variable j" for want of vector j of
+// their V (CHAIN_NEED_COLUMN): the vectors are computed -- one GEMM for all of
+// them -- and the chains replay the sweep they were in, from its start and with the
+// same draws, now finding the vector.  *served: something was replayed (st is fresh).
+int serve_columns(ba_engine *e, std::vector<int32_t> &st, bool *served) {
+  *served = false;
+  if (!column_service(e->data_kind) || !e->dcol_request.count) return BA_OK;
+  const size_t C = (size_t)e->cfg.chains;
+  bool any = false;
+  for (size_t c = 0; c < C; ++c) any = any || st[c] == CHAIN_NEED_COLUMN || st[c] == CHAIN_NEED_COLUMN_BIG;
+  if (!any) return BA_OK;
+  std::vector<int32_t> want(C), req;
+  HIP_TRY(hipMemcpy(want.data(), e->dcol_request.ptr, C * 4, hipMemcpyDeviceToHost));
+  for (size_t c = 0; c < C; ++c) {
+    if (st[c] != CHAIN_NEED_COLUMN && st[c] != CHAIN_NEED_COLUMN_BIG) continue;
+    if (want[c] < 0 || want[c] >= e->p) return fail(BA_E_STATE, "a parked chain names no variable");
+    req.push_back((int32_t)c);
+    req.push_back(want[c]);
+    // (the large-model kernel takes its chains back in the parked state)
+    st[c] = (st[c] == CHAIN_NEED_COLUMN) ? CHAIN_OK : CHAIN_MODEL_TOO_LARGE;
+  }
+  const int64_t R = (int64_t)req.size() / 2;
+  HIP_TRY(hipMemcpyAsync(e->dlogit_req.ptr, req.data(), req.size() * 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->dstatus.ptr, st.data(), C * 4, hipMemcpyHostToDevice, e->stream));
+  int rc = build_columns(e, R);
+  if (rc) return rc;
+  e->logit_cols_requested += R;
+  ++e->logit_replays;
+  SsvsParams P;
+  fill_params(e, P);
+  HIP_TRY(launch_sweeps(e, P, 0));   // the sweep still owed
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(st.data(), e->dstatus.ptr, C * 4, hipMemcpyDeviceToHost));
+  *served = true;
+  return BA_OK;
+}
+
+// A family's data on the device: X, the responses, the family's third vector (trial counts /
+// exposures; none for Student-t), X squared for the families of the column service (the
+// diagonal of X'WX).  The imputation starts over: no latent data, sweep 0.
+static int upload_latent_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y,
+                              const double *third, bool squared, int clt_threshold) {
+  HIP_TRY(e->dprob_X.resize((size_t)n * p));
+  HIP_TRY(e->dprob_y.resize((size_t)n));
+  if (third) HIP_TRY(e->dprob_nt.resize((size_t)n));
+  HIP_TRY(hipMemcpy(e->dprob_X.ptr, X, (size_t)n * p * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->dprob_y.ptr, y, (size_t)n * 8, hipMemcpyHostToDevice));
+  if (third) HIP_TRY(hipMemcpy(e->dprob_nt.ptr, third, (size_t)n * 8, hipMemcpyHostToDevice));
+  if (squared) {
+    HIP_TRY(e->dlogit_Xsq.resize((size_t)n * p));
+    HIP_TRY(launch_square(e->stream, e->dprob_X.ptr, (size_t)n * p, e->dlogit_Xsq.ptr));
+  }
+  e->dprob_z.release();
+  e->probit_n = n;
+  e->probit_clt = clt_threshold;
+  e->probit_sweep = 0;
+  return BA_OK;
+}
+
+// the latent data of the binomial and Poisson samplers have unit variance: sigma^2 = 1 in
+// every chain, whatever a caller left there before the data were set
+static int set_unit_sigsq(ba_engine *e) { return write_per_chain(e, e->dsigsq.ptr, -1, 1.0); }
+
+// the imputation kernels' view of the data (the probit kernel reads neither w nor the mixtures)
+static void fill_probit_params(ba_engine *e, ProbitParams &Q) {
+  std::memset(&Q, 0, sizeof(Q));
+  Q.n = (int32_t)e->probit_n;
+  Q.p = (int32_t)e->p;
+  Q.chains = (int32_t)e->cfg.chains;
+  Q.clt_threshold = e->probit_clt;
+  Q.slot_limit = e->slot_limit;
+  Q.chain_offset = e->cfg.chain_offset;
+  Q.X = e->dprob_X.ptr;
+  Q.y = e->dprob_y.ptr;
+  Q.ntrials = e->dprob_nt.ptr;
+  Q.gamma = e->dgamma.ptr;
+  Q.beta = e->dbeta.ptr;
+  Q.z = e->dprob_z.ptr;
+  Q.w = e->dlogit_w.ptr;
+  Q.xtz = e->dxty_c.ptr;
+  Q.seed_lo = (uint32_t)e->seed;
+  Q.seed_hi = (uint32_t)(e->seed >> 32);
+  Q.status = e->dstatus.ptr;
+  Q.mix_off = e->dpois_off.ptr;
+  Q.mix_mu = e->dpois_mu.ptr;
+  Q.mix_sigma = e->dpois_sigma.ptr;
+  Q.mix_logw = e->dpois_logw.ptr;
+  Q.obs_mix = e->dpois_obs.ptr;
+  Q.mix_one = e->poisson_mix_one;
+}
+
+static void fill_student_params(ba_engine *e, StudentParams &T) {
+  std::memset(&T, 0, sizeof(T));
+  T.n = (int32_t)e->probit_n;
+  T.p = (int32_t)e->p;
+  T.chains = (int32_t)e->cfg.chains;
+  T.slot_limit = e->slot_limit;
+  T.chain_offset = e->cfg.chain_offset;
+  T.X = e->dprob_X.ptr;
+  T.y = e->dprob_y.ptr;
+  T.gamma = e->dgamma.ptr;
+  T.beta = e->dbeta.ptr;
+  T.sigsq = e->dsigsq.ptr;
+  T.nu = e->dstu_nu.ptr;
+  T.dx = e->dstu_dx.ptr;
+  T.margin = e->dstu_margin.ptr;
+  T.z = e->dprob_z.ptr;
+  T.w = e->dlogit_w.ptr;
+  T.u = e->dstu_u.ptr;
+  T.seed_lo = (uint32_t)e->seed;
+  T.seed_hi = (uint32_t)(e->seed >> 32);
+  T.status = e->dstatus.ptr;
+  T.prior_df = e->prior_df;
+  T.prior_ss = e->prior_ss;
+  T.sigma_max = e->sigma_max;
+  T.nu_kind = e->student_nu_kind;
+  T.nu_a = e->student_nu_a;
+  T.nu_b = e->student_nu_b;
+  T.trace_idx = e->dtrace_idx.ptr;
+  T.trace_sigsq = e->dtr_sig.ptr;
+  T.trace_nu = e->dstu_nu_rec.ptr;
+  T.trace_stride = e->dstu_nu_rec.count ? e->trace_stride : 0;
+  T.acc = e->dacc.ptr;
+}
+
+// the Student sampler's per-chain state: nu = 30 (TRegression.cpp:35-45), suggested_dx = 1
+// (TRegressionSampler.cpp:88-107), no slice comparison seen yet
+static int student_prepare(ba_engine *e) {
+  int rc = alloc_chain_state(e);
+  if (rc) return rc;
+  const size_t C = (size_t)e->cfg.chains;
+  if (e->dstu_nu.count == C) return BA_OK;
+  HIP_TRY(e->dstu_nu.resize(C));
+  HIP_TRY(e->dstu_dx.resize(C));
+  HIP_TRY(e->dstu_margin.resize(C));
+  std::vector<double> nu(C, 30.0), dx(C, 1.0), m(C, std::numeric_limits<double>::infinity());
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(e->dstu_nu.ptr, nu.data(), C * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->dstu_dx.ptr, dx.data(), C * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->dstu_margin.ptr, m.data(), C * 8, hipMemcpyHostToDevice));
+  return BA_OK;
+}
+
+// the sweep loop shared by the logit, the Poisson and the Student-t samplers: imputation (per
+// family), X'Wz and the diagonal, the vectors of V the sweep starts from, the inclusion /
+// coefficient draws with park-and-replay for vectors requested mid-sweep
+static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
+  const bool student = e->data_kind == DATA_STUDENT;
+  if (!e->have_slab) return fail(BA_E_STATE, "call ba_sss_set_slab first");
+  if (student && !e->sss_slab_scales)
+    return fail(BA_E_INVALID, "the Student-t sampler takes a slab whose precision scales with sigma^2 (scales_with_sigsq = 1)");
+  if (!student && e->sss_slab_scales) return fail(BA_E_INVALID, "the logit sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
+  int rc = alloc_chain_state(e);
+  if (rc) return rc;
+  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, n = (size_t)e->probit_n;
+  if (student) {
+    rc = student_prepare(e);
+    if (rc) return rc;
+    if (e->trace_stride > 0 && nsweeps > e->trace_stride)
+      return fail(BA_E_INVALID, "nsweeps exceeds the enabled trace length");
+    if (e->dstu_u.count != C * n) HIP_TRY(e->dstu_u.resize(C * n));
+  }
+  if (e->dprob_z.count != C * n || e->dlogit_V.count != C * p * p) {
+    HIP_TRY(e->dprob_z.resize(C * n));
+    HIP_TRY(e->dlogit_w.resize(C * n));
+    HIP_TRY(e->dlogit_V.resize(C * p * p));
+    HIP_TRY(e->dxty_c.resize(C * p));
+    e->logit_words = (int)((p + 31) / 32);
+    HIP_TRY(e->dlogit_vdiag.resize(C * p));
+    HIP_TRY(e->dlogit_valid.resize(C * (size_t)e->logit_words));
+    HIP_TRY(e->dlogit_req.resize(2 * C * p));
+    HIP_TRY(e->dlogit_cnt.resize(1));
+    HIP_TRY(e->dcol_request.resize(C));
+    // the planes of one GEMM launch: at most 1 GiB, at least one request tile
+    const size_t per_req = (size_t)xtwx_cols_planes((int64_t)n) * p * 8;
+    e->logit_req_batch = (int64_t)std::min<size_t>(std::max<size_t>(((size_t)1 << 30) / per_req, 64), 32768);
+    e->logit_req_batch = std::min<int64_t>(e->logit_req_batch, (int64_t)(C * p));
+    HIP_TRY(e->dlogit_planes.resize((size_t)e->logit_req_batch * per_req / 8));
+  }
+  if (!student) {
+    rc = set_unit_sigsq(e);
+    if (rc) return rc;
+  }
+  rc = switch_mode(e, 1, 1.0);
+  if (rc) return rc;
+  rc = upload_shared(e);
+  if (rc) return rc;
+  HIP_TRY(e->dmodel.resize(2 * C * ssvs_scalar_layout(64).total));
+  SsvsParams P;
+  fill_params(e, P);
+  ProbitParams Q;
+  fill_probit_params(e, Q);
+  const int imputer = e->data_kind == DATA_POISSON ? 2 : e->logit_imputer;
+  StudentParams T;
+  fill_student_params(e, T);   // (read by the Student-t launches only)
+  // (the draws recorded are those of the last ba_student_sweep call)
+  if (student && e->trace_stride > 0) HIP_TRY(hipMemsetAsync(e->dtrace_idx.ptr, 0, C * 4, e->stream));
+  // BinomialLogitSpikeSlabSampler::draw (BinomialLogitSpikeSlabSampler.cpp:50-54) /
+  // PoissonRegressionSpikeSlabSampler::draw (PoissonRegressionSpikeSlabSampler.cpp:55-59)
+  for (int i = 0; i < nsweeps; ++i) {
+    Q.sweep = T.sweep = e->probit_sweep++;
+    // impute_latent_data: z, w, X'Wz and the diagonal of V = slab precision + X'WX ...
+    if (student)
+      HIP_TRY(launch_student_impute(e->stream, T, e->dlogit_Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->dlogit_vdiag.ptr,
+                                    e->dlogit_planes.ptr));
+    else
+      HIP_TRY(launch_logit_impute(e->stream, Q, e->dlogit_Xsq.ptr, e->dA.ptr, e->dlogit_vdiag.ptr,
+                                  e->dlogit_planes.ptr, imputer));
+    // ... and the vectors of V the sweep starts from: those of the included variables
+    HIP_TRY(launch_xtwx_cols_start(e->stream, e->dgamma.ptr, (int)C, (int)p, e->dlogit_req.ptr,
+                                   e->dlogit_cnt.ptr, e->dlogit_valid.ptr, e->logit_words));
+    int32_t R = 0;
+    HIP_TRY(hipMemcpyAsync(&R, e->dlogit_cnt.ptr, 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    rc = build_columns(e, R);
+    if (rc) return rc;
+    e->logit_cols_built += R;
+    HIP_TRY(launch_sweeps(e, P, 1));                                         // draw_model_indicators, draw_beta
+    // (a chain that stopped for a missing vector of V, or outgrew the launch's
+    // capacity, replays THIS sweep's draws on this sweep's latent data before the
+    // next imputation: check_chain_status serves both)
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    rc = check_chain_status(e);
+    if (rc) return rc;
+    if (student) {
+      // draw_sigsq_full_conditional, draw_nu_given_observed_data
+      HIP_TRY(launch_student_sigma_nu(e->stream, T));
+      rc = check_chain_status(e);
+      if (rc) return rc;
+    }
+    fill_params(e, P);
+  }
+  e->table_ok = false;
+  e->model_ok = false;
+  return BA_OK;
+}
+
+}  // namespace boom_amd
+
+extern "C" {
+
+// ------------------------ BinomialProbitSpikeSlabSampler (data augmentation + SpikeSlabSampler)
+int ba_probit_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y,
+                       const double *ntrials, int32_t clt_threshold) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!X || !y || !ntrials) return fail(BA_E_INVALID, "null argument");
+  if (n <= 0 || p <= 0) return fail(BA_E_INVALID, "n and p must be positive");
+  // up to 2 * clt_threshold truncated-normal draws per observation read the
+  // observation's substream of PROBIT_STRIDE uniforms (a draw takes 2 - 20 of them)
+  if (clt_threshold < 0 || clt_threshold > 64)
+    return fail(BA_E_INVALID, "clt_threshold must be between 0 and 64");
+  for (int64_t i = 0; i < n; ++i) {
+    if (y[i] < 0 || ntrials[i] < 0)
+      return fail(BA_E_INVALID, "Negative values not allowed in BinomialProbitDataImputer::impute().");
+    if (y[i] > ntrials[i])
+      return fail(BA_E_INVALID, "Success count exceeds trial count in BinomialProbitDataImputer::impute.");
+  }
+  // refresh_xtx (BinomialProbitSpikeSlabSampler.cpp:71-77): X'NX, built on the
+  // matrix cores from the rows scaled by sqrt(n_i).  Exact for Bernoulli data; for
+  // trial counts that are not perfect squares sqrt(n_i)^2 differs from n_i by one
+  // rounding, i.e. an element differs from the reference's sum_i n_i x x' by no more
+  // than the two summation orders already differ (~1e-16 relative per term).  The
+  // binomial cases of tests/test_probit_gpu.py (1 - 8 and 1 - 12 trials) hold the
+  // inclusion indicators bit-exact against the oracle on this matrix.
+  std::vector<double> Xs((size_t)n * p), zero((size_t)n, 0.0);
+  for (int32_t j = 0; j < p; ++j)
+    for (int64_t i = 0; i < n; ++i) Xs[(size_t)j * n + i] = X[(size_t)j * n + i] * std::sqrt(ntrials[i]);
+  int rc = ba_build_suf_from_xy(e, n, p, Xs.data(), zero.data());
+  if (rc) return rc;
+  rc = upload_latent_data(e, n, p, X, y, ntrials, /*squared=*/false, clt_threshold);
+  if (rc) return rc;
+  e->data_kind = DATA_PROBIT;
+  return BA_OK;
+}
+
+int ba_probit_sweep(ba_engine *e, int32_t nsweeps) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
+  int rc = sweep_refusal(e, DATA_PROBIT);
+  if (rc) return rc;
+  if (!e->have_slab) return fail(BA_E_STATE, "call ba_sss_set_slab first");
+  if (e->sss_slab_scales) return fail(BA_E_INVALID, "the probit sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
+  rc = alloc_chain_state(e);
+  if (rc) return rc;
+  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, n = (size_t)e->probit_n;
+  if (e->dprob_z.count != C * n) {
+    HIP_TRY(e->dprob_z.resize(C * n));
+    HIP_TRY(e->dxty_c.resize(C * p));
+    HIP_TRY(e->dlogit_planes.resize((size_t)xtwx_cols_planes((int64_t)n) * C * p));   // (split-K planes of X'z)
+  }
+  rc = set_unit_sigsq(e);
+  if (rc) return rc;
+  rc = switch_mode(e, 1, 1.0);
+  if (rc) return rc;
+  rc = upload_shared(e);
+  if (rc) return rc;
+  HIP_TRY(e->dmodel.resize(2 * C * ssvs_scalar_layout(64).total));
+  SsvsParams P;
+  fill_params(e, P);
+  ProbitParams Q;
+  fill_probit_params(e, Q);
+  // BinomialProbitSpikeSlabSampler::draw (BinomialProbitSpikeSlabSampler.cpp:40-46)
+  for (int i = 0; i < nsweeps; ++i) {
+    Q.sweep = e->probit_sweep++;
+    HIP_TRY(launch_probit_impute(e->stream, Q, e->dlogit_planes.ptr));   // impute_latent_data, X'z
+    HIP_TRY(launch_sweeps(e, P, 1));               // draw_model_indicators, draw_beta
+    // (a chain that outgrew the launch's capacity replays THIS sweep's draws on
+    // this sweep's latent data before the next imputation)
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    rc = check_chain_status(e);
+    if (rc) return rc;
+    fill_params(e, P);
+    P.model_keep = 1;
+    e->model_ok = true;
+  }
+  return BA_OK;
+}
+
+// ------------------------ BinomialLogitSpikeSlabSampler (auxiliary-mixture augmentation)
+int ba_logit_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y,
+                      const double *ntrials, int32_t clt_threshold) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!X || !y || !ntrials) return fail(BA_E_INVALID, "null argument");
+  if (n <= 0 || p <= 0) return fail(BA_E_INVALID, "n and p must be positive");
+  // (per-trial imputation reads two uniforms per trial of the observation's substream
+  // of LOGIT_STRIDE; the large-sample branch beyond the threshold a few dozen)
+  if (clt_threshold < 1 || 4 * clt_threshold > LOGIT_STRIDE)
+    return fail(BA_E_INVALID, "clt_threshold must be between 1 and 64");
+  for (int64_t i = 0; i < n; ++i) {
+    if (y[i] < 0 || ntrials[i] < 0)
+      return fail(BA_E_INVALID, "The number of successes and the number of trials must both be non-negative in BinomialLogitPartialAugmentationDataImputer::impute().");
+    if (y[i] > ntrials[i])
+      return fail(BA_E_INVALID, "The number of successes must not exceed the number of trials in BinomialLogitPartialAugmentationDataImputer::impute().");
+  }
+  // (dimensions, the shared buffers and a placeholder X'X; the sweeps use every
+  // chain's own X'WX)
+  std::vector<double> zero((size_t)n, 0.0);
+  int rc = ba_build_suf_from_xy(e, n, p, X, zero.data());
+  if (rc) return rc;
+  rc = upload_latent_data(e, n, p, X, y, ntrials, /*squared=*/true, clt_threshold);
+  if (rc) return rc;
+  e->data_kind = DATA_LOGIT;
+  return BA_OK;
+}
+
+int ba_logit_set_imputer(ba_engine *e, int32_t kind) {
+  if (!e) return fail(BA_E_INVALID, "null engine");
+  if (kind != 0 && kind != 1) return fail(BA_E_INVALID, "imputer must be 0 (auxiliary mixture) or 1 (Polya-Gamma)");
+  MUTATE(e);
+  e->logit_imputer = kind;
+  return BA_OK;
+}
+
+int ba_logit_sweep(ba_engine *e, int32_t nsweeps) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
+  int rc = sweep_refusal(e, DATA_LOGIT);
+  if (rc) return rc;
+  return logit_family_sweep(e, nsweeps);
+}
+
+// ------------------------ PoissonRegressionSpikeSlabSampler
+int ba_poisson_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y,
+                        const double *exposure) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!X || !y || !exposure) return fail(BA_E_INVALID, "null argument");
+  if (n <= 0 || p <= 0) return fail(BA_E_INVALID, "n and p must be positive");
+  for (int64_t i = 0; i < n; ++i) {
+    if (y[i] < 0 || y[i] != std::floor(y[i])) return fail(BA_E_INVALID, "counts must be non-negative integers");
+    if (!(exposure[i] > 0)) return fail(BA_E_INVALID, "exposures must be positive");
+  }
+  std::vector<double> zero((size_t)n, 0.0);
+  int rc = ba_build_suf_from_xy(e, n, p, X, zero.data());   // (dimensions and the shared buffers)
+  if (rc) return rc;
+  rc = upload_latent_data(e, n, p, X, y, exposure, /*squared=*/true, 0);
+  if (rc) return rc;
+  e->poisson_y.resize((size_t)n);
+  for (int64_t i = 0; i < n; ++i) e->poisson_y[(size_t)i] = (int64_t)std::llround(y[i]);
+  e->poisson_mix_set = false;
+  e->data_kind = DATA_POISSON;
+  return BA_OK;
+}
+
+int ba_poisson_set_mixtures(ba_engine *e, int32_t ncounts, const int64_t *counts, const int32_t *ncomp,
+                            const double *mu, const double *sigma, const double *weight,
+                            int64_t largest_index) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (e->data_kind != DATA_POISSON) return fail(BA_E_STATE, set_data_first(DATA_POISSON));
+  if (ncounts <= 0 || !counts || !ncomp || !mu || !sigma || !weight) return fail(BA_E_INVALID, "null argument");
+  std::vector<int32_t> off((size_t)ncounts + 1, 0);
+  for (int i = 0; i < ncounts; ++i) {
+    if (i > 0 && counts[i] <= counts[i - 1]) return fail(BA_E_INVALID, "counts must be ascending and distinct");
+    if (ncomp[i] <= 0 || ncomp[i] > POISSON_MAX_COMP) return fail(BA_E_INVALID, "a mixture has 1 .. 32 components");
+    off[(size_t)i + 1] = off[(size_t)i] + ncomp[i];
+  }
+  const size_t tot = (size_t)off[(size_t)ncounts];
+  std::vector<double> logw(tot);
+  for (size_t c = 0; c < tot; ++c) {
+    if (!(weight[c] > 0) || !(sigma[c] > 0)) return fail(BA_E_INVALID, "mixture weights and standard deviations must be positive");
+    logw[c] = std::log(weight[c]);
+  }
+  auto find = [&](int64_t v) -> int {
+    const int64_t *it = std::lower_bound(counts, counts + ncounts, v);
+    return (it != counts + ncounts && *it == v) ? (int)(it - counts) : -2;
+  };
+  const size_t n = e->poisson_y.size();
+  std::vector<int32_t> obs(n, -1);
+  for (size_t i = 0; i < n; ++i) {
+    const int64_t v = e->poisson_y[i];
+    if (v <= 0) continue;
+    if (v >= largest_index) { obs[i] = -1; continue; }   // the Gaussian limit (poisson_mixture_approximation_table.cpp:49-55)
+    const int m = find(v);
+    if (m < 0) return fail(BA_E_INVALID, "no mixture was given for a count that occurs in the data");
+    obs[i] = m;
+  }
+  const int one = find(1);
+  if (one < 0) return fail(BA_E_INVALID, "the mixture of count 1 (the event past the interval) is needed");
+  HIP_TRY(e->dpois_off.resize(off.size()));
+  HIP_TRY(e->dpois_mu.resize(tot));
+  HIP_TRY(e->dpois_sigma.resize(tot));
+  HIP_TRY(e->dpois_logw.resize(tot));
+  HIP_TRY(e->dpois_obs.resize(n));
+  HIP_TRY(hipMemcpy(e->dpois_off.ptr, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->dpois_mu.ptr, mu, tot * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->dpois_sigma.ptr, sigma, tot * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->dpois_logw.ptr, logw.data(), tot * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->dpois_obs.ptr, obs.data(), n * 4, hipMemcpyHostToDevice));
+  e->poisson_mix_one = one;
+  e->poisson_mix_set = true;
+  return BA_OK;
+}
+
+int ba_poisson_sweep(ba_engine *e, int32_t nsweeps) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
+  int rc = sweep_refusal(e, DATA_POISSON);
+  if (rc) return rc;
+  if (!e->poisson_mix_set) return fail(BA_E_STATE, "call ba_poisson_set_mixtures first");
+  return logit_family_sweep(e, nsweeps);
+}
+
+// ------------------------ TRegressionSpikeSlabSampler
+int ba_student_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!X || !y) return fail(BA_E_INVALID, "null argument");
+  if (n <= 0 || p <= 0) return fail(BA_E_INVALID, "n and p must be positive");
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(y[i])) return fail(BA_E_INVALID, "responses must be finite");
+  std::vector<double> zero((size_t)n, 0.0);
+  int rc = ba_build_suf_from_xy(e, n, p, X, zero.data());   // (dimensions and the shared buffers)
+  if (rc) return rc;
+  rc = upload_latent_data(e, n, p, X, y, nullptr, /*squared=*/true, 0);
+  if (rc) return rc;
+  e->dstu_u.release();
+  // a new TRegressionModel: nu = 30, suggested_dx = 1, no slice margin yet (student_prepare)
+  e->dstu_nu.release();
+  e->dstu_dx.release();
+  e->dstu_margin.release();
+  e->data_kind = DATA_STUDENT;
+  return BA_OK;
+}
+
+int ba_student_allow_model_selection(ba_engine *e, int32_t allow) {
+  if (!e) return fail(BA_E_INVALID, "null engine");
+  MUTATE(e);
+  e->student_allow_selection = allow != 0;
+  return BA_OK;
+}
+
+int ba_student_set_nu_prior(ba_engine *e, int32_t kind, double a, double b) {
+  if (!e) return fail(BA_E_INVALID, "null engine");
+  if (kind == STUDENT_NU_UNIFORM) {
+    if (!(std::isfinite(a) && std::isfinite(b) && a >= 0 && b > a))
+      return fail(BA_E_INVALID, "a Uniform(a, b) prior on nu needs 0 <= a < b, both finite");
+  } else if (kind == STUDENT_NU_GAMMA) {
+    if (!(std::isfinite(a) && std::isfinite(b) && a > 0 && b > 0))
+      return fail(BA_E_INVALID, "a Gamma(a, b) prior on nu needs a positive shape and rate");
+  } else {
+    return fail(BA_E_INVALID, "kind must be 0 (Uniform) or 1 (Gamma)");
+  }
+  MUTATE(e);
+  e->student_nu_kind = kind;
+  e->student_nu_a = a;
+  e->student_nu_b = b;
+  return BA_OK;
+}
+
+int ba_student_set_nu(ba_engine *e, int64_t chain, double nu) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!(nu > 0) || !std::isfinite(nu)) return fail(BA_E_INVALID, "nu must be positive and finite");
+  if (chain < -1 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  int rc = student_prepare(e);
+  if (rc) return rc;
+  return write_per_chain(e, e->dstu_nu.ptr, chain, nu);
+}
+
+int ba_student_get_nu(ba_engine *e, int64_t chain, double *nu) {
+  ENGINE_PROLOGUE(e);
+  if (!nu) return fail(BA_E_INVALID, "null argument");
+  if (chain < -1 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  int rc = student_prepare(e);
+  if (rc) return rc;
+  return read_per_chain(e, e->dstu_nu.ptr, chain, nu);
+}
+
+int ba_student_get_margin(ba_engine *e, int64_t chain, double *margin) {
+  ENGINE_PROLOGUE(e);
+  if (!margin) return fail(BA_E_INVALID, "null argument");
+  if (chain < -1 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  int rc = student_prepare(e);
+  if (rc) return rc;
+  return read_per_chain(e, e->dstu_margin.ptr, chain, margin);
+}
+
+int ba_student_get_weights(ba_engine *e, int64_t chain, double *w) {
+  ENGINE_PROLOGUE(e);
+  if (!w) return fail(BA_E_INVALID, "null argument");
+  if (e->data_kind != DATA_STUDENT) return fail(BA_E_STATE, set_data_first(DATA_STUDENT));
+  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  const size_t n = (size_t)e->probit_n;
+  if (e->dlogit_w.count != (size_t)e->cfg.chains * n || e->probit_sweep == 0)
+    return fail(BA_E_STATE, "no imputation has run yet: call ba_student_sweep first");
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(w, e->dlogit_w.ptr + (size_t)chain * n, n * 8, hipMemcpyDeviceToHost));
+  return BA_OK;
+}
+
+int ba_student_get_nu_draws(ba_engine *e, int64_t chain, int32_t nsweeps, double *out) {
+  ENGINE_PROLOGUE(e);
+  if (!out) return fail(BA_E_INVALID, "null argument");
+  if (e->trace_stride <= 0 || e->dstu_nu_rec.count == 0)
+    return fail(BA_E_STATE, "draws are not recorded: call ba_enable_draws before ba_student_sweep");
+  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  if (nsweeps <= 0 || nsweeps > e->trace_stride) return fail(BA_E_INVALID, "nsweeps out of range");
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(out, e->dstu_nu_rec.ptr + (size_t)chain * e->trace_stride, (size_t)nsweeps * 8,
+                    hipMemcpyDeviceToHost));
+  return BA_OK;
+}
+
+int ba_student_sweep(ba_engine *e, int32_t nsweeps) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
+  int rc = sweep_refusal(e, DATA_STUDENT);
+  if (rc) return rc;
+  if (e->trace_stride > 0 && e->dstu_nu_rec.count != (size_t)e->cfg.chains * e->trace_stride) {
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(e->dstu_nu_rec.resize((size_t)e->cfg.chains * e->trace_stride));
+  }
+  return logit_family_sweep(e, nsweeps);
+}
+
+}  // extern "C"

@@ -1,0 +1,501 @@
+// What the host side's translation units share: the engine itself, the launchers of the
+// kernel files, the entry points' prologues and the host helpers that cross files.
+//   engine.hip      creation, timing, regression data, priors, state, the BregVs / SpikeSlab /
+//                   adaptive sweeps, pipelined launches, ba_draw_next's look-ahead, summaries,
+//                   traces, prediction, check_chain_status
+//   engine_glm.hip  probit, logit, Poisson, Student-t (the latent-data families)
+//   engine_ss.hip   state space: ba_ss_*, its look-ahead, the round kernel's launches
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/boom_amd.h"
+#include "kalman_params.h"
+#include "ktimer.h"
+#include "probit_params.h"
+#include "ssvs_params.h"
+#include "student_params.h"
+
+namespace boom_amd {
+// ssvs_kernel.hip
+hipError_t launch_ssvs_sweep(hipStream_t stream, const SsvsParams &P, int nsweeps);
+// ssvs_big_kernel.hip
+hipError_t launch_ssvs_big(hipStream_t stream, const SsvsParams &P, int nsweeps);
+// ssvs_adaptive_kernel.hip
+hipError_t launch_ssvs_adaptive(hipStream_t stream, const SsvsParams &P, int nsweeps);
+hipError_t launch_ssvs_logp(hipStream_t stream, const SsvsParams &P,
+                            const uint8_t *gammas, int ngamma, double *out,
+                            int *status_out);
+hipError_t launch_lds_exchange_order(hipStream_t stream, int *bad_device);
+hipError_t launch_ssvs_reduce_summaries(hipStream_t stream, const SsvsParams &P,
+                                        double *out);
+// suf_kernel.hip
+int suf_row_slices(int64_t n, int p);
+int launch_suf_from_xy(hipStream_t stream, int64_t n, int p, const double *X,
+                       const double *y, double *xtx, double *xty,
+                       double *scalars /* yty, sumy */, double *xsum,
+                       double *planes /* suf_row_slices(n, p) * p * p doubles, or null */);
+// kalman_kernel.hip
+hipError_t launch_ssm_simsmooth(hipStream_t stream, const SsParams &P, int draw_variances);
+hipError_t launch_ssm_forecast(hipStream_t stream, const SsParams &P, int horizon, const double *newX,
+                               uint64_t *pos_forecast, double *out);
+hipError_t launch_probit_impute(hipStream_t stream, const ProbitParams &P, double *planes);
+hipError_t launch_student_impute(hipStream_t stream, const StudentParams &P, const double *Xsq,
+                                 const double *slab_precision, double *xtz, double *v_diag, double *planes);
+hipError_t launch_student_sigma_nu(hipStream_t stream, const StudentParams &P);
+hipError_t launch_logit_impute(hipStream_t stream, const ProbitParams &P, const double *Xsq,
+                               const double *slab_precision, double *v_diag, double *planes,
+                               int polya_gamma);
+// xtwx_cols_kernel.hip
+hipError_t launch_ssvs_big_logp(hipStream_t stream, const SsvsParams &P, int kcap, const uint8_t *gammas,
+                                const int *which, int nwhich, double *model_ws, double *xs_ws, double *out,
+                                int *status_out);
+hipError_t launch_predict(hipStream_t stream, const double *trace_k, const uint16_t *rec_idx,
+                          const double *rec_beta, int stride, int cap, int first_draw, int ndraws,
+                          int chains, int p, const double *newX, int nnew, double *out);
+int xtwx_cols_planes(int64_t n);
+int xte_planes(int64_t n);
+hipError_t launch_xtwx_cols(hipStream_t stream, const double *X, int64_t n, int p, const double *w,
+                            const int32_t *req, int R, const double *base, double *V,
+                            uint32_t *valid, int words, double *planes);
+hipError_t launch_xtwx_cols_start(hipStream_t stream, const uint8_t *gamma, int chains, int p,
+                                  int32_t *req, int32_t *count, uint32_t *valid, int words);
+hipError_t launch_square(hipStream_t stream, const double *x, size_t count, double *out);
+hipError_t launch_kalman_simsmooth(hipStream_t stream, const SsParams &P,
+                                   int draw_level);
+hipError_t launch_kalman_main(hipStream_t stream, const SsParams &P, int draw_level);
+hipError_t launch_kalman_xte(hipStream_t stream, const SsParams &P, bool planes_only);
+hipError_t launch_kalman_prepare(hipStream_t stream, const SsParams &P, int draw_level);
+hipError_t launch_ss_round(hipStream_t stream, const SsvsParams &P, const SsParams &S, const SsRoundParams &F,
+                           int *max_resident);
+size_t ss_round_lds(int p, int kcap);
+hipError_t launch_ss_forecast(hipStream_t stream, const SsParams &P, int horizon, const double *newX,
+                              uint64_t *pos_forecast, double *out);
+
+// sets the text ba_last_error() returns (one thread_local string for the whole library,
+// engine.hip) and returns `code`
+int fail(int code, const std::string &msg);
+
+#define HIP_TRY(expr)                                                       \
+  do {                                                                      \
+    hipError_t err__ = (expr);                                              \
+    if (err__ != hipSuccess) {                                              \
+      return fail(BA_E_HIP, std::string(#expr) + ": " +                     \
+                                hipGetErrorString(err__));                  \
+    }                                                                       \
+  } while (0)
+
+template <class T>
+struct DevBuf {
+  T *ptr = nullptr;
+  size_t count = 0;
+  ~DevBuf() { release(); }
+  void release() {
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    count = 0;
+  }
+  hipError_t resize(size_t n) {
+    if (n == count && ptr) return hipSuccess;
+    release();
+    if (n == 0) return hipSuccess;
+    hipError_t e = hipMalloc((void **)&ptr, n * sizeof(T));
+    if (e == hipSuccess) count = n;
+    return e;
+  }
+};
+
+// Which data the engine holds: one kind at a time.  A data setter installs its kind as its
+// last step; DATA_REGRESSION is also the state of a fresh engine (have_suf says whether
+// anything was uploaded).  Every sweep entry point serves one kind and refuses the others
+// (sweep_refusal, engine.hip).
+enum DataKind { DATA_REGRESSION, DATA_STATE_SPACE, DATA_PROBIT, DATA_LOGIT, DATA_POISSON, DATA_STUDENT };
+// the latent-data families: the regression runs on every chain's own imputed responses
+inline bool latent_data(DataKind k) { return k == DATA_PROBIT || k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT; }
+// ... and those of them whose V = slab precision + X'WX is every chain's own, built a vector
+// at a time (serve_columns, engine_glm.hip)
+inline bool column_service(DataKind k) { return k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT; }
+
+}  // namespace boom_amd
+
+using namespace boom_amd;   // (this header is the three host files' own)
+
+// ba_set_kernel_timing: the event pairs of the launches since the last read
+struct KtSpan { int cls; hipEvent_t a, b; };
+struct KTimer {
+  std::vector<KtSpan> spans;
+  std::vector<hipEvent_t> open;   // begin events by class (launches do not nest within a class)
+  std::vector<hipEvent_t> pool;
+  double ms[KT_CLASSES] = {};
+  int64_t launches[KT_CLASSES] = {};
+  hipEvent_t get() {
+    if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
+    hipEvent_t e = nullptr;
+    (void)hipEventCreate(&e);
+    return e;
+  }
+  // fold the finished spans into the totals (the caller has synchronised the stream)
+  void collect() {
+    for (const KtSpan &sp : spans) {
+      float t = 0.f;
+      if (hipEventElapsedTime(&t, sp.a, sp.b) == hipSuccess) { ms[sp.cls] += t; ++launches[sp.cls]; }
+      pool.push_back(sp.a);
+      pool.push_back(sp.b);
+    }
+    spans.clear();
+  }
+  ~KTimer() {
+    for (const KtSpan &sp : spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
+    for (hipEvent_t e : open) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : pool) (void)hipEventDestroy(e);
+  }
+};
+
+struct ba_engine {
+  ba_config cfg{};
+  bool kt_enabled = false;
+  bool kt_overlap = false;   // (timing on, consecutive sweep launches still overlap: ba_set_kernel_timing(e, 2))
+  KTimer kt;
+  hipStream_t stream = nullptr;
+  int p = 0;
+  int cu_count = 256;
+  size_t lds_per_cu = 160 * 1024;
+
+  DataKind data_kind = DATA_REGRESSION;   // which data are installed (one kind at a time)
+  // ---- host copies (RegSuf + priors)
+  bool have_suf = false, have_slab = false, have_spike = false,
+       have_sigma = false;
+  std::vector<double> xtx, xty, xsum;
+  double yty = 0, n = 0, sumy = 0;
+  std::vector<double> b, ominv, pi;
+  int64_t max_model_size = -1;
+  double prior_df = 0, prior_ss = 0, sigma_guess = 0;
+  double sigma_max = std::numeric_limits<double>::infinity();
+  int max_flips = -1;  // < 0: p
+  double swap_threshold = 0.8;
+  int draw_beta = 1, draw_sigma = 1;
+  bool device_dirty = true;   // V/A/b/logpi/cm need (re)upload
+  bool state_ready = false;
+
+  // ---- device: shared
+  DevBuf<double> dV, dA, db, dl1, dl0, dpi, dxty, dscal /* yty, n */;
+  DevBuf<int32_t> dcm_start, dcm_idx;
+  DevBuf<double> dcm_cor;
+  bool cm_enabled = false;
+  // ---- device: per chain
+  DevBuf<uint8_t> dgamma;
+  DevBuf<double> dbeta, dsigsq;
+  DevBuf<uint16_t> dperm;
+  DevBuf<uint64_t> dpos;
+  DevBuf<int32_t> dstatus, dfail, dtodo, dmaxk, dtrace_idx;
+  DevBuf<uint32_t> dinc;
+  DevBuf<double> dbsum, dbsumsq, dacc, dsummary;
+  DevBuf<double> dtr_sig, dtr_logp, dtr_k;
+  DevBuf<uint16_t> drec_idx;  // recorded draws (ba_enable_draws)
+  DevBuf<double> drec_beta;
+  DevBuf<double> dmodel;  // per-chain model scratch (scalar-cache reads)
+  DevBuf<double> dtab_lp;   // per-chain proposal table
+  DevBuf<uint8_t> dtab_kind;
+  DevBuf<int32_t> dtab_tag, dmodel_tag;
+  DevBuf<int32_t> dran;  // catch-up launches of the state-space path: sweeps done per chain
+  bool table_ok = false;  // nothing but ba_sweep launches since the tables were built
+  bool model_ok = false;  // nothing that changes a model's factors since the last sweep launch
+  int trace_stride = 0;
+  // scratch for suf build
+  DevBuf<double> dX, dy, dxtx, dxsum, dsufscal;
+
+  int kcap = 0;
+  int waves = 1;  // wavefronts per chain
+  // ba_draw_next: the look-ahead batch.  la_avail draws are recorded on the
+  // device, la_served of them have been handed out; the snapshot is the chains'
+  // state (and the running summaries) at the start of the batch, which is what
+  // a rewind restores before replaying the la_served draws already seen.
+  int la_len = 1, la_avail = 0, la_served = 0;
+  // host copies of the batch's record for the chains the caller reads (the
+  // per-iteration loop reads chain 0 after every draw: one set of copies per
+  // batch instead of per call); la_synced: the batch's launch has been waited for
+  // and its chain statuses checked
+  struct LaRows { std::vector<double> k, sig, beta; std::vector<uint16_t> idx; };
+  std::unordered_map<int64_t, LaRows> la_cache;
+  bool la_synced = false;
+  // Overlapping look-ahead batches: the record holds two batches (halves la_slot and
+  // la_slot ^ 1 of 2 la_len rows), the batch after the one being served is launched as soon
+  // as serving starts (la_ahead) and the launches hand chains over (pipelined sweeps); each
+  // batch's workgroups save their chain's state on entry (snapshot set = half) for rewinds.
+  bool la_pipe = true;        // allowed (off for good after a batch had to be redone the old way)
+  bool la_cur_piped = false;  // the batch being served was launched that way
+  bool la_ahead = false;
+  int la_slot = 0;
+  hipEvent_t la_done[2] = {nullptr, nullptr};
+  DevBuf<uint8_t> snap_gamma;
+  DevBuf<double> snap_beta, snap_sigsq, snap_bsum, snap_bsumsq, snap_acc;
+  DevBuf<uint16_t> snap_perm;
+  DevBuf<uint64_t> snap_pos;
+  DevBuf<int32_t> snap_fail;
+  DevBuf<uint32_t> snap_inc;
+  int rec_cap = 64;  // variables per recorded draw (ba_enable_draws)
+  // HBM-resident path for models of more than 64 variables (ssvs_big_kernel.hip):
+  // active once a chain has outgrown the LDS kernel, capacity grows on demand
+  bool big_active = false;
+  int big_kcap = 0;
+  DevBuf<double> dbig_model, dbig_xs;
+  // ba_set_tuning overrides (0 / -1: the engine chooses)
+  int tune_waves = 0, tune_walk_policy = -1, tune_kcap_start = 0;
+  // SpikeSlabSampler (sigma^2 given) mode
+  int cur_mode = 0;          // mode of the launches in flight (0 BregVs, 1 SSS)
+  int sss_slab_scales = 1;   // slab precision = Omega^{-1} / sigma^2
+  int sss_max_flips = -1;    // limits only when > 0 (SpikeSlabSampler.cpp:77)
+  double v_scale = 1.0;      // V = Omega^{-1} + v_scale * XtX currently on the device
+  double v_scale_want = 1.0;
+  DevBuf<uint64_t> dpos_sss;
+  uint64_t seed = 0;
+  // AdaptiveSpikeSlabRegressionSampler (mode 2): rates, iteration counts, options
+  DevBuf<double> dada_birth, dada_death, dada_ws;
+  DevBuf<uint64_t> dada_iter, dpos_ada;
+  int ada_max_flips = 100;
+  double ada_step = .001, ada_target = .345;
+
+  // ---- state space (bsts local level + regression)
+  bool ss_level_set = false, ss_initialized = false;
+  int T = 0;
+  DevBuf<double> dss_y, dss_X, dss_scratch;
+  // The callers' loop is "one round, then read chain 0": what the accessors copy goes
+  // through ONE pinned staging buffer per call (a batch of asynchronous copies, one
+  // synchronisation) instead of one blocking copy per field, and a ba_sync() that follows
+  // a clean ba_sync() with no call in between that could have enqueued or changed anything
+  // is free (api_seq counts such calls, clean_seq remembers the last clean check).
+  void *pinned = nullptr;
+  size_t pinned_bytes = 0;
+  uint64_t api_seq = 1, clean_seq = 0;
+  int api_depth = 0;   // calls other than accessors in progress (they may enqueue after an inner ba_sync)
+  // lane-major copies for kalman_lm_kernel (kalman_params.h): local level, T <= LM_TP
+  DevBuf<double> dss_yt, dss_Xt;
+  DevBuf<uint32_t> dss_obs_mask;
+  DevBuf<uint8_t> dss_obs;
+  DevBuf<double> dxty_c, dyty_c, dnobs_c;       // per-chain regression suf
+  DevBuf<double> dlev_sigsq, dlev_n, dlev_sumsq;
+  DevBuf<uint64_t> dpos_level, dpos_state, dpos_forecast;
+  // kalman_prepare_kernel (level variance + normals of the next state draw) runs on a
+  // second stream beside the X'e GEMM and the SSVS launch
+  hipStream_t stream2 = nullptr;
+  hipEvent_t ev_state = nullptr, ev_prep[2] = {nullptr, nullptr};
+  int ss_zbuf = 0;   // the normals buffer the next state draw reads
+  // pipelined sweeps: consecutive ba_sweep launches alternate between `stream` and
+  // pipe_stream and hand chains over through a ring of four queues (ssvs_kernel.hip)
+  hipStream_t pipe_stream = nullptr;
+  hipEvent_t pipe_ev[4] = {}, pipe_join_ev = nullptr;
+  DevBuf<int32_t> dpipe_q, dpipe_err;
+  bool pipe_on = false;      // the last thing enqueued was a pipelined sweep launch
+  bool pipe_unchecked = false;   // a pipelined launch has gone out since the error word was last read
+  int pipe_k = 0;            // launches in the current pipeline
+  bool pipe_groups = false;  // ... which are the chain GROUPS of an engine of more chains than the machine holds
+  DevBuf<int32_t> dprep_n;
+  DevBuf<uint64_t> dprep_pos_state, dprep_pos_level;
+  DevBuf<double> dprep_level;
+  DevBuf<double> dxte_planes;   // split-K planes of the X'e GEMM
+  double level_prior_df = 0, level_prior_ss = 0;
+  double level_sigma_max = std::numeric_limits<double>::infinity();
+  double ss_a0 = 0, ss_P0 = 1, ss_initial_level_sigsq = 1;
+  // BinomialProbitSpikeSlabSampler (probit_kernel.hip): data on the device, the
+  // latent sums z (chains x n), imputations done so far
+  int64_t probit_n = 0;
+  int probit_clt = 5;
+  uint64_t probit_sweep = 0;
+  DevBuf<double> dprob_X, dprob_y, dprob_nt, dprob_z;
+  // BinomialLogitSpikeSlabSampler: the same buffers plus the observations' total
+  // precisions (chains x n) and every chain's own V = slab precision + X'WX
+  int logit_imputer = 0;           // 0: the reference's auxiliary mixture, 1: Polya-Gamma
+  // PoissonRegressionSpikeSlabSampler: the logit path's machinery (every chain's own V a
+  // vector at a time) with its own imputation kernel and SpikeSlabSampler's shuffle;
+  // dprob_nt holds the exposures; the reference table's mixtures by count
+  bool poisson_mix_set = false;
+  std::vector<int64_t> poisson_y;             // host copy of the counts (to map them to mixtures)
+  DevBuf<int32_t> dpois_off, dpois_obs;
+  DevBuf<double> dpois_mu, dpois_sigma, dpois_logw;
+  int poisson_mix_one = -1;
+  // TRegressionSpikeSlabSampler (student_kernel.hip): the logit path's machinery (its
+  // column service too) with its own imputation, sigma^2 per chain and the nu draw; per chain nu,
+  // the slice sampler's suggested_dx, the smallest slice margin, the recorded nu path; the
+  // u_i = (r_i / sigma)^2 of the last draw (chains x n)
+  bool student_allow_selection = true;   // (ba_student_allow_model_selection)
+  int student_nu_kind = STUDENT_NU_UNIFORM;
+  double student_nu_a = 0.1, student_nu_b = 100.0;
+  DevBuf<double> dstu_nu, dstu_dx, dstu_margin, dstu_u, dstu_nu_rec;
+  int slot_limit = 0;              // (ba_set_slot_limit)
+  DevBuf<double> dlogit_w, dlogit_V;
+  // ... V built a vector at a time (xtwx_cols_kernel.hip): the squared design matrix
+  // (for the diagonal), the diagonals (chains x p), which vectors hold this sweep's
+  // values (bits, logit_words words per chain), the request list (chain, variable) and
+  // its length, the variable a parked chain waits for, the GEMM's split-K planes
+  DevBuf<double> dlogit_Xsq, dlogit_vdiag, dlogit_planes;
+  DevBuf<uint32_t> dlogit_valid;
+  DevBuf<int32_t> dlogit_req, dlogit_cnt, dcol_request;
+  int logit_words = 0;
+  int64_t logit_req_batch = 0;     // requests per GEMM launch (bounds the planes)
+  int64_t logit_cols_built = 0, logit_cols_requested = 0, logit_replays = 0;   // (diagnostics)
+  // structural state (a list of state models, ssm_kernel.hip) instead of the local level
+  bool ssm_set = false;
+  SsgSpec ssg{};                   // the host's copy of the specification
+  DevBuf<uint8_t> dssg_spec;       // ... and the device's
+  double ssg_initial_sigsq[SSG_MAX_VAR] = {};
+  double ssg_initial_phi[SSG_MAX_AR][AR_MAX] = {};
+  // the template of ba_ss_set_structural (level / slope / seasonal -> variance index, -1: none)
+  int ssg_template_var[3] = {-1, -1, -1};
+  int ssg_template_ar = -1;        // ... and the block ba_ss_add_ar appended
+  int ssg_kernel_choice = 1;       // (ba_ss_set_tuning: 0 general, 1 the default choice, 3 shape-specialised)
+  // the local-level rounds of a call as one persistent launch (ss_round_kernel.hip); the
+  // tile words of its X'e step, zeroed before every launch; how many chains' workgroups the
+  // device holds at once, by launch capacity (0: not asked yet, < 0: the kernel does not fit)
+  bool ss_round_enabled = true;    // (ba_ss_set_tuning 4 / 5: the separate launches of rounds 1-4 / this)
+  DevBuf<int32_t> dround_ctl, dround_members, dround_reg;
+  int ss_round_resident[4] = {0, 0, 0, 0};
+  bool round_debug = false;        // (ba_ss_set_tuning 6 / 7: the round kernel's notes of a debugging session on / off)
+  DevBuf<int32_t> dround_debug;    // ... on this engine's device
+  DevBuf<double> dssm_sigsq, dssm_n, dssm_ss, dssm_work;   // chains x SSG_MAX_VAR (sigsq, n, ss)
+  DevBuf<double> dar_phi, dar_suf;                         // chains x SSG_MAX_AR x (AR_MAX | AR_SUF_STRIDE)
+  DevBuf<uint64_t> dpos_var;                               // chains x SSG_MAX_VAR
+  // ---- look-ahead on the bsts path (ba_ss_set_lookahead / ba_ss_draw_next): a batch of
+  // `len` sweep rounds per enqueue, every round's draw recorded on the device -- gamma,
+  // beta, sigma^2, the state models' variances and coefficients for EVERY chain, the
+  // state path for the registered chains -- and handed out one per call.  Two halves:
+  // the batch after the one being served is enqueued as soon as serving starts.  Any
+  // entry point that is not served from the record first puts the chains where the
+  // caller has seen them (ss_la_settle: the snapshot of the batch's start, replayed up
+  // to the draw being served), so the look-ahead is unobservable.
+  struct SsLa {
+    int len = 0;                // rounds per batch at most (<= 1: off)
+    // rounds per batch NOW.  A caller whose loop reads something the record does not hold
+    // (another chain's state path, sufficient statistics, a forecast) or changes something
+    // (priors under the sampler) after every draw pays a rewind + replay of the batch each
+    // time: so a settle halves the batch, a batch served to its end doubles it again (up to
+    // len); at one round per call the look-ahead is off and is tried again after
+    // `probe_wait` calm draws (16, doubling while the tries keep failing).
+    int cur = 0, calm = 0, probe_wait = 16;
+    bool clean = true;          // nothing has settled the batch being served
+    int ahead_len = 0;          // rounds of the batch that is running ahead
+    int avail = 0, served = 0, slot = 0;
+    bool ahead = false;         // the next batch is enqueued (half slot ^ 1)
+    bool synced = false;        // the batch being served is complete and its chains sound
+    bool busy = false;          // (a settle in progress: entry points it calls do not settle again)
+    hipEvent_t done[2] = {nullptr, nullptr};
+    std::vector<int32_t> reg{0};            // chains whose state path is recorded (always the size of dreg / rstate's rows)
+    std::vector<int32_t> want;              // ... and the ones asked for since: ss_la_alloc takes them into reg, as far as the record has room
+    DevBuf<int32_t> dreg;
+    DevBuf<double> lev_used;                // the level variance every chain's last state draw used
+    size_t nvar = 0, nphi = 0, state_doubles = 0;   // per chain and round
+    DevBuf<uint8_t> rgamma;                 // [slot][chain][round][p]
+    DevBuf<double> rbeta, rsig, rvar, rphi; // [slot][chain][round][...]
+    DevBuf<double> rstate;                  // [slot][registered chain][round][state_doubles]
+    DevBuf<double> snap;                    // the state-space half of the chain state, two sets
+    DevBuf<uint64_t> snap_pos;
+    size_t snap_doubles = 0, snap_words = 0;
+    struct Rows { std::vector<uint8_t> gamma; std::vector<double> beta, sig, var, phi, state; bool has_state = false; };
+    std::unordered_map<int64_t, Rows> cache;
+  } ssla;
+};
+
+// ---- host helpers that cross files ---------------------------------------------------
+namespace boom_amd {
+// the timer of the engine whose entry point this thread is in (engine.hip)
+extern thread_local KTimer *g_kt;
+
+// engine.hip
+int set_device(const ba_engine *e);
+int upload_shared(ba_engine *e);
+int alloc_chain_state(ba_engine *e);
+void fill_params(ba_engine *e, SsvsParams &P);
+hipError_t launch_sweeps(ba_engine *e, const SsvsParams &P, int nsweeps);
+int cap_limit(const ba_engine &e);
+int choose_waves(const ba_engine &e, int kcap);
+int grow_big(ba_engine *e, int *stuck);
+int check_chain_status(ba_engine *e);
+int switch_mode(ba_engine *e, int mode, double v_scale);
+hipError_t pinned_reserve(ba_engine *e, size_t bytes);
+int concurrent_stream(ba_engine *e, hipStream_t *out);
+int pipe_join(ba_engine *e);
+int la_rewind(ba_engine *e);
+int la_copy(ba_engine *e, bool save, int set = 0);
+// BA_OK when the engine holds the data the entry point samples (`wants`; sss: ba_sss_sweep,
+// the other sweep of plain regression data), else the entry point's refusal for the kind held
+int sweep_refusal(const ba_engine *e, DataKind wants, bool sss = false);
+const char *set_data_first(DataKind wants);   // "call ba_<family>_set_data first"
+// one double per chain, chain == -1: all of them (the caller has validated `chain`); both
+// wait for the stream first
+int write_per_chain(ba_engine *e, double *dev, int64_t chain, double value);
+int read_per_chain(ba_engine *e, const double *dev, int64_t chain, double *out);
+// engine_glm.hip
+int serve_columns(ba_engine *e, std::vector<int32_t> &st, bool *served);
+// engine_ss.hip
+int ss_escalate(ba_engine *e, std::vector<int32_t> &st);
+int ss_la_settle(ba_engine *e);
+bool ss_la_serving(const ba_engine *e);
+int ss_la_wait(ba_engine *e);
+int ss_la_rows(ba_engine *e, int64_t c, bool want_state, const ba_engine::SsLa::Rows **out);
+}  // namespace boom_amd
+
+struct ApiScope {
+  ba_engine *e;
+  explicit ApiScope(ba_engine *en) : e(en) { e->api_seq++; e->api_depth++; }
+  ~ApiScope() { e->api_depth--; }
+  ApiScope(const ApiScope &) = delete;
+};
+
+// (a mutator changes what the next launch reads -- priors, data, options -- through copies
+// on the main stream: a pipelined sweep launch still running on the other stream must be
+// behind the main stream first, or it would see half of the new values)
+#define MUTATE(e)                        \
+  do {                                   \
+    (e)->api_seq++;                      \
+    int rc_m__ = set_device(e);          \
+    if (!rc_m__) rc_m__ = pipe_join(e);  \
+    if (!rc_m__) rc_m__ = ss_la_settle(e); \
+    if (!rc_m__) rc_m__ = la_rewind(e);  \
+    if (rc_m__) return rc_m__;           \
+    (e)->table_ok = false;               \
+    (e)->model_ok = false;               \
+  } while (0)
+
+// (accessors that enqueue nothing and change nothing: they do not count as a call
+// between two ba_sync()s)
+#define ENGINE_ACCESSOR_NOJOIN(e)                              \
+  if (!(e)) return fail(BA_E_INVALID, "null engine");          \
+  g_kt = (e)->kt_enabled ? &(e)->kt : nullptr;                 \
+  {                                                            \
+    int rc__ = set_device(e);                                  \
+    if (rc__) return rc__;                                     \
+  }
+#define ENGINE_PROLOGUE_NOJOIN(e)                              \
+  ENGINE_ACCESSOR_NOJOIN(e)                                    \
+  ApiScope api_scope__(e);
+// (everything but ba_sweep itself first lets the main stream catch up with a pipeline
+// of sweep launches)
+#define ENGINE_PROLOGUE(e)                                     \
+  ENGINE_PROLOGUE_NOJOIN(e)                                    \
+  {                                                            \
+    int rc__ = pipe_join(e);                                   \
+    if (!rc__) rc__ = ss_la_settle(e);                         \
+    if (rc__) return rc__;                                     \
+  }
+#define ENGINE_ACCESSOR(e)                                     \
+  ENGINE_ACCESSOR_NOJOIN(e)                                    \
+  {                                                            \
+    int rc__ = pipe_join(e);                                   \
+    if (!rc__) rc__ = ss_la_settle(e);                         \
+    if (rc__) return rc__;                                     \
+  }
+// (the entry points that serve the draw of ba_ss_draw_next from the device's record)
+#define ENGINE_ACCESSOR_SERVED(e)                              \
+  ENGINE_ACCESSOR_NOJOIN(e)                                    \
+  {                                                            \
+    int rc__ = pipe_join(e);                                   \
+    if (rc__) return rc__;                                     \
+  }

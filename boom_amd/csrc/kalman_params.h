@@ -1,5 +1,5 @@
 // Launch parameters of the Kalman filter / simulation smoother kernel
-// (kalman_kernel.hip), shared with the host side (engine.hip).
+// (kalman_kernel.hip), shared with the host side (engine_ss.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -148,7 +148,7 @@ struct SsRoundParams {
   int32_t *sizes;           // [rounds][chain_count]
   int32_t *members;         // [rounds][chain_count * SS_ROUND_TILE + 2 * SS_ROUND_TILE]
   double *planes;           // SS_ROUND_TILE x chains x p: a chain's partial products, by row of the series
-  // the look-ahead's record of every round's draw (engine.hip; rgamma == nullptr: none):
+  // the look-ahead's record of every round's draw (engine_ss.hip; rgamma == nullptr: none):
   // chain c's row of round r is (rec_slot * chains + c) * rec_len + rec_first + r
   uint8_t *rgamma;
   double *rbeta, *rsig, *rvar, *rstate;

@@ -1,5 +1,5 @@
 // Launch parameters of the probit data-augmentation kernel (probit_kernel.hip),
-// shared with the host side (engine.hip).
+// shared with the host side (engine_glm.hip).
 #pragma once
 #include <stdint.h>
 

@@ -381,7 +381,7 @@ __global__ __launch_bounds__(LM_THREADS, 2) void ss_round_kernel(SsvsParams P, S
       }
     }
     RSTAMP(5);   // waiting for the other members' shares, plane sum
-    // ---- 4. what the callers' loop reads of this round's draw (engine.hip, look-ahead)
+    // ---- 4. what the callers' loop reads of this round's draw (engine_ss.hip, look-ahead)
     if (F.rgamma) {
       const size_t at = ((size_t)F.rec_slot * S.chains + chain) * F.rec_len + F.rec_first + r;
       for (int j = lane; j < p; j += WAVE) {

@@ -1,4 +1,4 @@
-// Launch parameters and memory layout shared by the host side (engine.hip) and
+// Launch parameters and memory layout shared by the host side (engine*.hip) and
 // the SSVS sweep kernel (ssvs_kernel.hip).
 #pragma once
 #include <stdint.h>

@@ -1,5 +1,5 @@
 // Launch parameters of the Student-t regression kernels (student_kernel.hip), shared with
-// the host side (engine.hip).
+// the host side (engine_glm.hip).
 #pragma once
 #include <stdint.h>
 
