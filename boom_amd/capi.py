@@ -136,6 +136,9 @@ SIGNATURES = {
     "ba_student_get_nu_draws": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp]),
     "ba_student_get_margin": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
     "ba_student_allow_model_selection": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ba_quantile_set_data": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp, C.c_double]),
+    "ba_quantile_sweep": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ba_quantile_get_weights": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
     "ba_ss_set_structural": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [_dp] * 6),
     "ba_ss_get_structural": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp]),
     "ba_ss_add_ar": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double,
@@ -560,6 +563,25 @@ class Engine:
     def student_get_nu_draws(self, chain, nsweeps):
         out = np.zeros(int(nsweeps))
         self._check(self.lib.ba_student_get_nu_draws(self._h, int(chain), int(nsweeps), _p(out)))
+        return out
+
+    # ---- QuantileRegressionSpikeSlabSampler --------------------------------------
+    def quantile_set_data(self, X, y, quantile):
+        X = np.asfortranarray(X, dtype=np.float64)
+        self.p = X.shape[1]
+        self.n = X.shape[0]
+        self._check(self.lib.ba_quantile_set_data(self._h, X.shape[0], X.shape[1], _p(X), _p(_f64(y)),
+                                                  float(quantile)))
+
+    def quantile_sweep(self, nsweeps=1, sync=True):
+        self._check(self.lib.ba_quantile_sweep(self._h, nsweeps))
+        if sync:
+            self.sync()
+
+    def quantile_get_weights(self, chain):
+        """the last imputation's weights lambda_inv of one chain (0 where the residual was 0)"""
+        out = np.zeros(getattr(self, "n", 1))   # (without quantile data the call is refused before it writes)
+        self._check(self.lib.ba_quantile_get_weights(self._h, int(chain), _p(out)))
         return out
 
     def logit_set_imputer(self, kind):

@@ -42,6 +42,9 @@ const char *status_message(int st) {
       return "The slice sampler of nu failed in ScalarSliceSampler (an infinite "
              "log density at the current value, an infinite upper limit, more than "
              "100 doublings or more than 100 contractions).";
+    case QUANTILE_WEIGHT_ERROR:
+      return "An inverse-Gaussian weight of the quantile regression imputation came out "
+             "non-finite or not positive.";
     default:
       return "unknown chain status";
   }
@@ -56,6 +59,7 @@ int status_code(int st) {
     case CHAIN_FORECAST_VARIANCE: return BA_E_FORECAST_VARIANCE;
     case CHAIN_MODEL_TOO_LARGE: return BA_E_MODEL_TOO_LARGE;
     case STUDENT_SLICE_ERROR: return BA_E_RNG_BRANCH;
+    case QUANTILE_WEIGHT_ERROR: return BA_E_RNG_BRANCH;
     default: return BA_E_INVALID;
   }
 }
@@ -368,7 +372,7 @@ void fill_params(ba_engine *e, SsvsParams &P) {
   if (e->cur_mode == 1 && column_service(e->data_kind) && e->dlogit_V.count) {
     // BinomialLogitSpikeSlabSampler: the sampler's own shuffle, every chain's own V
     // (which moves with the latent data: factors and tables are rebuilt)
-    P.mode = e->data_kind == DATA_LOGIT ? 2 : 1;   // (the Poisson and Student samplers drive the plain SpikeSlabSampler)
+    P.mode = e->data_kind == DATA_LOGIT ? 2 : 1;   // (the Poisson, Student and quantile samplers drive the plain SpikeSlabSampler)
     P.V = e->dlogit_V.ptr;
     P.v_chain_stride = (int64_t)e->p * e->p;
     P.model_keep = 0;
@@ -995,7 +999,8 @@ const char *ba_kernel_class_name(int32_t cls) {
       "ssm_simsmooth_kernel", "atb_mfma_kernel", "probit_impute_kernel", "logit_impute_kernel",
       "xtwx_cols_kernel<false>+plain_reduce_kernel", "xtwx_cols_kernel<true>+xtwx_cols_reduce_kernel",
       "xtx_mfma_kernel+plane_sum_kernel+col_reduce_kernel", "poisson_impute_kernel",
-      "kalman_prepare_kernel", "ss_round_kernel", "student_impute_kernel", "student_sigma_nu_kernel"};
+      "kalman_prepare_kernel", "ss_round_kernel", "student_impute_kernel", "student_sigma_nu_kernel",
+      "quantile_impute_kernel"};
   return (cls >= 0 && cls < KT_CLASSES) ? names[cls] : "";
 }
 
@@ -1571,14 +1576,16 @@ static const char *const kSetDataFirst[] = {nullptr,
                                             "call ba_probit_set_data first",
                                             "call ba_logit_set_data first",
                                             "call ba_poisson_set_data first",
-                                            "call ba_student_set_data first"};
+                                            "call ba_student_set_data first",
+                                            "call ba_quantile_set_data first"};
 // ... and where the data in hand send a caller of another family's entry point
 static const char *const kUseSweep[] = {nullptr,
                                         "state-space data are set: use ba_ss_sweep",
                                         "binomial data are set: use ba_probit_sweep",
                                         "binomial data are set: use ba_logit_sweep",
                                         "Poisson data are set: use ba_poisson_sweep",
-                                        "Student-t regression data are set: use ba_student_sweep"};
+                                        "Student-t regression data are set: use ba_student_sweep",
+                                        "quantile regression data are set: use ba_quantile_sweep"};
 
 const char *set_data_first(DataKind wants) { return kSetDataFirst[wants]; }
 
@@ -1586,7 +1593,10 @@ const char *set_data_first(DataKind wants) { return kSetDataFirst[wants]; }
 int sweep_refusal(const ba_engine *e, DataKind wants, bool sss) {
   const DataKind have = e->data_kind;
   if (have == wants) return BA_OK;
-  if (wants == DATA_STATE_SPACE) return fail(BA_E_STATE, kSetDataFirst[wants]);
+  // (the quantile sampler's column and row: every other sweep names ba_quantile_sweep, and
+  // ba_quantile_sweep asks for its own data whatever else is set)
+  if (have == DATA_QUANTILE) return fail(BA_E_STATE, kUseSweep[have]);
+  if (wants == DATA_STATE_SPACE || wants == DATA_QUANTILE) return fail(BA_E_STATE, kSetDataFirst[wants]);
   if (have == DATA_STUDENT) return fail(BA_E_STATE, kUseSweep[have]);
   if (wants == DATA_REGRESSION) {   // ba_sweep, ba_draw_next, ba_adaptive_sweep; ba_sss_sweep
     if (have == DATA_STATE_SPACE) return fail(BA_E_STATE, kUseSweep[have]);

@@ -1,8 +1,9 @@
-// Host side of the latent-data families: BinomialProbit-, BinomialLogit-, PoissonRegression-
-// and TRegressionSpikeSlabSampler.  Each imputes its latent data (probit_kernel.hip,
-// student_kernel.hip) and lets the SpikeSlabSampler sweep draw indicators and coefficients on
-// the imputed regression; the logit, Poisson and Student-t samplers keep every chain's own
-// V = slab precision + X'WX, built a vector at a time (the column service, xtwx_cols_kernel.hip).
+// Host side of the latent-data families: BinomialProbit-, BinomialLogit-, PoissonRegression-,
+// TRegression- and QuantileRegressionSpikeSlabSampler.  Each imputes its latent data
+// (probit_kernel.hip, student_kernel.hip, quantile_kernel.hip) and lets the SpikeSlabSampler
+// sweep draw indicators and coefficients on the imputed regression; the logit, Poisson,
+// Student-t and quantile samplers keep every chain's own V = slab precision + X'WX, built a
+// vector at a time (the column service, xtwx_cols_kernel.hip).
 #include "engine_internal.h"
 
 namespace boom_amd {
@@ -144,6 +145,25 @@ static void fill_student_params(ba_engine *e, StudentParams &T) {
   T.acc = e->dacc.ptr;
 }
 
+static void fill_quantile_params(ba_engine *e, QuantileParams &U) {
+  std::memset(&U, 0, sizeof(U));
+  U.n = (int32_t)e->probit_n;
+  U.p = (int32_t)e->p;
+  U.chains = (int32_t)e->cfg.chains;
+  U.slot_limit = e->slot_limit;
+  U.chain_offset = e->cfg.chain_offset;
+  U.X = e->dprob_X.ptr;
+  U.y = e->dprob_y.ptr;
+  U.gamma = e->dgamma.ptr;
+  U.beta = e->dbeta.ptr;
+  U.z = e->dprob_z.ptr;
+  U.w = e->dlogit_w.ptr;
+  U.shift = 1.0 - 2.0 * e->quantile_q;
+  U.seed_lo = (uint32_t)e->seed;
+  U.seed_hi = (uint32_t)(e->seed >> 32);
+  U.status = e->dstatus.ptr;
+}
+
 // the Student sampler's per-chain state: nu = 30 (TRegression.cpp:35-45), suggested_dx = 1
 // (TRegressionSampler.cpp:88-107), no slice comparison seen yet
 static int student_prepare(ba_engine *e) {
@@ -162,14 +182,16 @@ static int student_prepare(ba_engine *e) {
   return BA_OK;
 }
 
-// the sweep loop shared by the logit, the Poisson and the Student-t samplers: imputation (per
-// family), X'Wz and the diagonal, the vectors of V the sweep starts from, the inclusion /
-// coefficient draws with park-and-replay for vectors requested mid-sweep
+// the sweep loop shared by the logit, the Poisson, the Student-t and the quantile samplers:
+// imputation (per family), X'Wz and the diagonal, the vectors of V the sweep starts from, the
+// inclusion / coefficient draws with park-and-replay for vectors requested mid-sweep
 static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
-  const bool student = e->data_kind == DATA_STUDENT;
+  const bool student = e->data_kind == DATA_STUDENT, quantile = e->data_kind == DATA_QUANTILE;
   if (!e->have_slab) return fail(BA_E_STATE, "call ba_sss_set_slab first");
   if (student && !e->sss_slab_scales)
     return fail(BA_E_INVALID, "the Student-t sampler takes a slab whose precision scales with sigma^2 (scales_with_sigsq = 1)");
+  if (quantile && e->sss_slab_scales)
+    return fail(BA_E_INVALID, "the quantile regression sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
   if (!student && e->sss_slab_scales) return fail(BA_E_INVALID, "the logit sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
   int rc = alloc_chain_state(e);
   if (rc) return rc;
@@ -214,16 +236,22 @@ static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
   const int imputer = e->data_kind == DATA_POISSON ? 2 : e->logit_imputer;
   StudentParams T;
   fill_student_params(e, T);   // (read by the Student-t launches only)
+  QuantileParams U;
+  fill_quantile_params(e, U);  // (read by the quantile launch only)
   // (the draws recorded are those of the last ba_student_sweep call)
   if (student && e->trace_stride > 0) HIP_TRY(hipMemsetAsync(e->dtrace_idx.ptr, 0, C * 4, e->stream));
   // BinomialLogitSpikeSlabSampler::draw (BinomialLogitSpikeSlabSampler.cpp:50-54) /
-  // PoissonRegressionSpikeSlabSampler::draw (PoissonRegressionSpikeSlabSampler.cpp:55-59)
+  // PoissonRegressionSpikeSlabSampler::draw (PoissonRegressionSpikeSlabSampler.cpp:55-59) /
+  // QuantileRegressionSpikeSlabSampler::draw (QuantileRegressionPosteriorSampler.cpp:77-91)
   for (int i = 0; i < nsweeps; ++i) {
-    Q.sweep = T.sweep = e->probit_sweep++;
+    Q.sweep = T.sweep = U.sweep = e->probit_sweep++;
     // impute_latent_data: z, w, X'Wz and the diagonal of V = slab precision + X'WX ...
     if (student)
       HIP_TRY(launch_student_impute(e->stream, T, e->dlogit_Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->dlogit_vdiag.ptr,
                                     e->dlogit_planes.ptr));
+    else if (quantile)
+      HIP_TRY(launch_quantile_impute(e->stream, U, e->dlogit_Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->dlogit_vdiag.ptr,
+                                     e->dlogit_planes.ptr));
     else
       HIP_TRY(launch_logit_impute(e->stream, Q, e->dlogit_Xsq.ptr, e->dA.ptr, e->dlogit_vdiag.ptr,
                                   e->dlogit_planes.ptr, imputer));
@@ -579,6 +607,47 @@ int ba_student_sweep(ba_engine *e, int32_t nsweeps) {
     HIP_TRY(e->dstu_nu_rec.resize((size_t)e->cfg.chains * e->trace_stride));
   }
   return logit_family_sweep(e, nsweeps);
+}
+
+// ------------------------ QuantileRegressionSpikeSlabSampler
+int ba_quantile_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y, double quantile) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!X || !y) return fail(BA_E_INVALID, "null argument");
+  if (n <= 0 || p <= 0) return fail(BA_E_INVALID, "n and p must be positive");
+  if (!(quantile > 0 && quantile < 1)) return fail(BA_E_INVALID, "quantile must be strictly between 0 and 1");
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(y[i])) return fail(BA_E_INVALID, "responses must be finite");
+  std::vector<double> zero((size_t)n, 0.0);
+  int rc = ba_build_suf_from_xy(e, n, p, X, zero.data());   // (dimensions and the shared buffers)
+  if (rc) return rc;
+  rc = upload_latent_data(e, n, p, X, y, nullptr, /*squared=*/true, 0);
+  if (rc) return rc;
+  e->quantile_q = quantile;
+  e->data_kind = DATA_QUANTILE;
+  return BA_OK;
+}
+
+int ba_quantile_sweep(ba_engine *e, int32_t nsweeps) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
+  int rc = sweep_refusal(e, DATA_QUANTILE);
+  if (rc) return rc;
+  return logit_family_sweep(e, nsweeps);
+}
+
+int ba_quantile_get_weights(ba_engine *e, int64_t chain, double *w) {
+  ENGINE_PROLOGUE(e);
+  if (!w) return fail(BA_E_INVALID, "null argument");
+  if (e->data_kind != DATA_QUANTILE) return fail(BA_E_STATE, set_data_first(DATA_QUANTILE));
+  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  const size_t n = (size_t)e->probit_n;
+  if (e->dlogit_w.count != (size_t)e->cfg.chains * n || e->probit_sweep == 0)
+    return fail(BA_E_STATE, "no imputation has run yet: call ba_quantile_sweep first");
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(w, e->dlogit_w.ptr + (size_t)chain * n, n * 8, hipMemcpyDeviceToHost));
+  return BA_OK;
 }
 
 }  // extern "C"

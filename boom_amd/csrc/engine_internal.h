@@ -3,7 +3,7 @@
 //   engine.hip      creation, timing, regression data, priors, state, the BregVs / SpikeSlab /
 //                   adaptive sweeps, pipelined launches, ba_draw_next's look-ahead, summaries,
 //                   traces, prediction, check_chain_status
-//   engine_glm.hip  probit, logit, Poisson, Student-t (the latent-data families)
+//   engine_glm.hip  probit, logit, Poisson, Student-t, quantile (the latent-data families)
 //   engine_ss.hip   state space: ba_ss_*, its look-ahead, the round kernel's launches
 #pragma once
 #include <hip/hip_runtime.h>
@@ -22,6 +22,7 @@
 #include "kalman_params.h"
 #include "ktimer.h"
 #include "probit_params.h"
+#include "quantile_params.h"
 #include "ssvs_params.h"
 #include "student_params.h"
 
@@ -52,6 +53,9 @@ hipError_t launch_probit_impute(hipStream_t stream, const ProbitParams &P, doubl
 hipError_t launch_student_impute(hipStream_t stream, const StudentParams &P, const double *Xsq,
                                  const double *slab_precision, double *xtz, double *v_diag, double *planes);
 hipError_t launch_student_sigma_nu(hipStream_t stream, const StudentParams &P);
+// quantile_kernel.hip
+hipError_t launch_quantile_impute(hipStream_t stream, const QuantileParams &P, const double *Xsq,
+                                  const double *slab_precision, double *xtz, double *v_diag, double *planes);
 hipError_t launch_logit_impute(hipStream_t stream, const ProbitParams &P, const double *Xsq,
                                const double *slab_precision, double *v_diag, double *planes,
                                int polya_gamma);
@@ -118,12 +122,12 @@ struct DevBuf {
 // last step; DATA_REGRESSION is also the state of a fresh engine (have_suf says whether
 // anything was uploaded).  Every sweep entry point serves one kind and refuses the others
 // (sweep_refusal, engine.hip).
-enum DataKind { DATA_REGRESSION, DATA_STATE_SPACE, DATA_PROBIT, DATA_LOGIT, DATA_POISSON, DATA_STUDENT };
+enum DataKind { DATA_REGRESSION, DATA_STATE_SPACE, DATA_PROBIT, DATA_LOGIT, DATA_POISSON, DATA_STUDENT, DATA_QUANTILE };
 // the latent-data families: the regression runs on every chain's own imputed responses
-inline bool latent_data(DataKind k) { return k == DATA_PROBIT || k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT; }
+inline bool latent_data(DataKind k) { return k == DATA_PROBIT || k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE; }
 // ... and those of them whose V = slab precision + X'WX is every chain's own, built a vector
 // at a time (serve_columns, engine_glm.hip)
-inline bool column_service(DataKind k) { return k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT; }
+inline bool column_service(DataKind k) { return k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE; }
 
 }  // namespace boom_amd
 
@@ -330,6 +334,9 @@ struct ba_engine {
   int student_nu_kind = STUDENT_NU_UNIFORM;
   double student_nu_a = 0.1, student_nu_b = 100.0;
   DevBuf<double> dstu_nu, dstu_dx, dstu_margin, dstu_u, dstu_nu_rec;
+  // QuantileRegressionSpikeSlabSampler (quantile_kernel.hip): the Poisson path with its own
+  // imputation; the model's quantile
+  double quantile_q = 0.5;
   int slot_limit = 0;              // (ba_set_slot_limit)
   DevBuf<double> dlogit_w, dlogit_V;
   // ... V built a vector at a time (xtwx_cols_kernel.hip): the squared design matrix

@@ -28,6 +28,7 @@ enum KernelClass {
   KT_SS_ROUND,      // ss_round_kernel (the local-level bsts rounds of a call, one persistent launch)
   KT_STUDENT_IMPUTE,   // student_impute_kernel
   KT_STUDENT_SIGMA_NU, // student_sigma_nu_kernel
+  KT_QUANTILE_IMPUTE,  // quantile_impute_kernel
   KT_CLASSES
 };
 

@@ -557,4 +557,38 @@ PYBIND11_MODULE(_boom, boom) {
       .def("set_sigma_upper_limit", &TRegressionSpikeSlabSampler::set_sigma_upper_limit)
       .def("limit_model_selection", &TRegressionSpikeSlabSampler::limit_model_selection)
       .def("allow_model_selection", &TRegressionSpikeSlabSampler::allow_model_selection);
+
+  // ---- quantile regression spike and slab (QuantileRegressionModel,
+  // QuantileRegressionSpikeSlabSampler) -----------------------------------------------------
+  py::class_<QuantileRegressionModel, Ptr<QuantileRegressionModel>>(boom, "QuantileRegressionModel")
+      .def(py::init<int, double, int, uint64_t, int>(), py::arg("xdim"), py::arg("quantile"),
+           py::arg("chains") = 1, py::arg("seed") = 8675309ull, py::arg("device") = 0)
+      .def_property_readonly("xdim", &QuantileRegressionModel::xdim)
+      .def_property_readonly("quantile", &QuantileRegressionModel::quantile)
+      .def("set_data", [](QuantileRegressionModel &m, const NpArray &X, const NpArray &y) {
+             m.set_data(matrix_from(X), vector_from(y));
+           },
+           py::arg("predictors"), py::arg("response"))
+      .def("drop_all", &QuantileRegressionModel::drop_all)
+      .def("add", &QuantileRegressionModel::add)
+      .def("drop", &QuantileRegressionModel::drop)
+      .def_property_readonly("inc", [](const QuantileRegressionModel &m) {
+        std::vector<bool> g(m.xdim());
+        for (int j = 0; j < m.xdim(); ++j) g[j] = m.inc()[j];
+        return g;
+      })
+      .def_property_readonly("Beta", [](const QuantileRegressionModel &m) { return to_numpy(m.Beta()); })
+      .def("set_Beta", [](QuantileRegressionModel &m, const NpArray &b) { m.set_Beta(vector_from(b)); })
+      .def("set_method", [](QuantileRegressionModel &m, const Ptr<PosteriorSampler> &s) { m.set_method(s); })
+      .def("sample_posterior", &QuantileRegressionModel::sample_posterior);
+  py::class_<QuantileRegressionSpikeSlabSampler, PosteriorSampler, Ptr<QuantileRegressionSpikeSlabSampler>>(
+      boom, "QuantileRegressionSpikeSlabSampler")
+      .def(py::init([](QuantileRegressionModel *model, const Ptr<MvnModel> &slab,
+                       const Ptr<VariableSelectionPrior> &spike, py::object) {
+             return new QuantileRegressionSpikeSlabSampler(model, slab, spike);
+           }),
+           py::arg("model"), py::arg("slab"), py::arg("spike"), py::arg("seeding_rng") = py::none(),
+           py::keep_alive<1, 2>())
+      .def("draw", &QuantileRegressionSpikeSlabSampler::draw)
+      .def("limit_model_selection", &QuantileRegressionSpikeSlabSampler::limit_model_selection);
 }

@@ -373,6 +373,30 @@ int ba_student_get_nu_draws(ba_engine *e, int64_t chain, int32_t nsweeps, double
 int ba_student_get_margin(ba_engine *e, int64_t chain, double *margin);
 int ba_student_allow_model_selection(ba_engine *e, int32_t allow);
 
+/* ---- QuantileRegressionSpikeSlabSampler (qreg.spike) ----------------------------------------
+ * Models/Glm/PosteriorSamplers/QuantileRegressionPosteriorSampler.cpp:30-39, :77-91: per sweep,
+ * for every observation with residual r_i = |y_i - x_i'beta| > 0 the weight
+ * w_i = lambda_inv ~ InverseGaussian(mean 1 / r_i, shape 1) (rig_mt), the weighted regression
+ * of y*_i = y_i - (2 (1 - quantile) - 1) / w_i on x_i with weights w_i, then SpikeSlabSampler's
+ * inclusion / coefficient draws at sigma^2 = 1 -- the Poisson path's machinery with another
+ * imputation.  An observation with a zero residual is left out of that sweep's regression
+ * (weight 0, no random numbers read).  There is no sigma^2 and no nu.  The chains target
+ * the density proportional to prior(beta) exp(-2 sum_i rho_q(y_i - x_i'beta)), rho_q the check loss.
+ *   ba_quantile_set_data     X n x p column-major, y n, 0 < quantile < 1
+ *   priors, state            ba_sss_set_slab(mu, precision, 0, max_flips), ba_set_spike,
+ *                            ba_set_state / ba_get_state(s) as for the Poisson sampler (sigma^2 is 1)
+ *   ba_quantile_sweep        nsweeps x draw() on every chain
+ *   ba_quantile_get_weights  the last imputation's n weights lambda_inv of one chain, 0 where
+ *                            the residual was 0
+ * The smaller root of rig_mt's quadratic is evaluated as mu / (1 + t + sqrt(t (2 + t))),
+ * t = mu y / (2 lambda): the reference's form cancels at small residuals.
+ * RNG: stream 3 for the inclusion / coefficient draws; stream 32 from position
+ * (s n + i) * 256 for the weight of observation i in sweep s (one normal, then one uniform). */
+int ba_quantile_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y,
+                         double quantile);
+int ba_quantile_sweep(ba_engine *e, int32_t nsweeps);
+int ba_quantile_get_weights(ba_engine *e, int64_t chain, double *w);
+
 /* ---- posterior summaries --------------------------------------------------- */
 /* Running sums over every sweep since the last ba_reset_summaries(), reduced
  * over this engine's chains on the device:

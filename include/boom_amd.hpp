@@ -1023,4 +1023,87 @@ class TRegressionSpikeSlabSampler : public PosteriorSampler {
   double sigma_max_ = std::numeric_limits<double>::infinity();
 };
 
+// ---- Quantile regression spike and slab --------------------------------------------------
+// QuantileRegressionModel + QuantileRegressionSpikeSlabSampler (Models/Glm/
+// QuantileRegressionModel.hpp, PosteriorSamplers/QuantileRegressionPosteriorSampler.cpp:30-39,
+// :77-91; qreg.spike's quantile_spike_wrapper.cc:31-47): the inverse-Gaussian weights and the
+// inclusion / coefficient draws at sigma^2 = 1, on the device (ba_quantile_*).  The model is
+// built from its dimension and quantile; set_data hands over the observations (the
+// reference's add_data, all at once).  Chain 0 backs the model's accessors.
+class QuantileRegressionModel : public Model {
+ public:
+  QuantileRegressionModel(int xdim, double quantile, int chains = 1, uint64_t seed = 8675309, int device = 0)
+      : eng_(new Engine(chains, seed, device)), p_(xdim), quantile_(quantile), inc_(xdim, true), beta_(xdim, 0.0) {
+    if (xdim <= 0) report_error("The dimension of a QuantileRegressionModel must be positive.");
+    if (!(quantile > 0 && quantile < 1)) report_error("Quantile must be strictly between 0 and 1.");
+  }
+  double quantile() const { return quantile_; }
+  void set_data(const Matrix &X, const Vector &y) {
+    if (X.nrow() != (int)y.size() || X.ncol() != p_)
+      report_error("X and y are incompatible with the QuantileRegressionModel.");
+    eng_->check(ba_quantile_set_data(eng_->get(), X.nrow(), X.ncol(), X.data(), y.data(), quantile_));
+    dirty_ = true;
+  }
+  int xdim() const { return p_; }
+  const Selector &inc() const { return inc_; }
+  void drop_all() { inc_.drop_all(); dirty_ = true; }
+  void add(int i) { inc_.add(i); dirty_ = true; }
+  void drop(int i) { inc_.drop(i); dirty_ = true; }
+  const Vector &Beta() const { return beta_; }
+  void set_Beta(const Vector &b) { beta_ = b; dirty_ = true; }
+  bool dirty() const { return dirty_; }
+  const Ptr<Engine> &engine() const { return eng_; }
+  void push_state() {
+    eng_->check(ba_set_state(eng_->get(), -1, inc_.bytes().data(), beta_.data(), 1.0));
+    dirty_ = false;
+  }
+  void pull_chain0() {
+    eng_->check(ba_get_state(eng_->get(), 0, inc_.bytes().data(), beta_.data(), nullptr));
+    dirty_ = false;
+  }
+ private:
+  Ptr<Engine> eng_;
+  int p_;
+  double quantile_;
+  Selector inc_;
+  Vector beta_;
+  bool dirty_ = true;
+};
+// QuantileRegressionSpikeSlabSampler(model, slab, spike, seeding_rng); the slab and the
+// spike are kept and handed to the engine with the first draw after the data
+class QuantileRegressionSpikeSlabSampler : public PosteriorSampler {
+ public:
+  QuantileRegressionSpikeSlabSampler(QuantileRegressionModel *model, const Ptr<MvnModel> &slab,
+                                     const Ptr<VariableSelectionPrior> &spike)
+      : model_(model), slab_(slab), spike_(spike) {
+    if (slab->dim() != model->xdim()) report_error("Slab does not match model dimension.");
+    if ((int)spike->potential_nvars() != model->xdim()) report_error("Spike does not match model dimension.");
+  }
+  void draw() override {
+    if (!priors_set_) {
+      check(ba_sss_set_slab(h(), slab_->mu().data(), slab_->siginv().data(), 0, max_flips_));
+      check(ba_set_spike(h(), spike_->prior_inclusion_probabilities().data(), spike_->max_model_size()));
+      priors_set_ = true;
+    }
+    if (model_->dirty()) model_->push_state();
+    check(ba_quantile_sweep(h(), 1));
+    check(ba_sync(h()));
+    model_->pull_chain0();
+  }
+  double logpri() const override { report_error("logpri() is not implemented for the quantile regression sampler"); return 0; }
+  void set_seed(unsigned long s) override { check(ba_seed(h(), s)); }
+  void limit_model_selection(int max_flips) {
+    max_flips_ = max_flips;
+    priors_set_ = false;
+  }
+ private:
+  ba_engine *h() const { return model_->engine()->get(); }
+  void check(int rc) const { model_->engine()->check(rc); }
+  QuantileRegressionModel *model_;
+  Ptr<MvnModel> slab_;
+  Ptr<VariableSelectionPrior> spike_;
+  int max_flips_ = -1;
+  bool priors_set_ = false;
+};
+
 }  // namespace boom_amd_api
