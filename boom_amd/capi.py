@@ -139,6 +139,13 @@ SIGNATURES = {
     "ba_quantile_set_data": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp, C.c_double]),
     "ba_quantile_sweep": (C.c_int, [C.c_void_p, C.c_int32]),
     "ba_quantile_get_weights": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
+    "ba_mlogit_set_data": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                     C.POINTER(C.c_int32), _dp, _dp]),
+    "ba_mlogit_set_flip_order": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "ba_mlogit_allow_model_selection": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ba_mlogit_sweep": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ba_mlogit_get_latent": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp]),
+    "ba_mlogit_get_wss": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
     "ba_ss_set_structural": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [_dp] * 6),
     "ba_ss_get_structural": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp]),
     "ba_ss_add_ar": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double,
@@ -583,6 +590,52 @@ class Engine:
         out = np.zeros(getattr(self, "n", 1))   # (without quantile data the call is refused before it writes)
         self._check(self.lib.ba_quantile_get_weights(self._h, int(chain), _p(out)))
         return out
+
+    # ---- MLVS (multinomial logit spike and slab) -----------------------------------
+    def mlogit_set_data(self, y, Xsubject, Xchoice, nchoices):
+        """y n in 0 .. nchoices - 1; Xsubject n x psub or None; Xchoice (n nchoices) x pch, row
+        i nchoices + m, or None"""
+        y = np.ascontiguousarray(y, dtype=np.int32)
+        n = y.shape[0]
+        xs = None if Xsubject is None else np.asfortranarray(Xsubject, dtype=np.float64)
+        xc = None if Xchoice is None else np.asfortranarray(Xchoice, dtype=np.float64)
+        psub = 0 if xs is None else xs.shape[1]
+        pch = 0 if xc is None else xc.shape[1]
+        if xs is not None and xs.shape[0] != n:
+            raise ValueError("Xsubject must have one row per observation")
+        if xc is not None and xc.shape[0] != n * int(nchoices):
+            raise ValueError("Xchoice must have nchoices rows per observation")
+        self._check(self.lib.ba_mlogit_set_data(self._h, n, int(nchoices), psub, pch,
+                                                y.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                None if xs is None else _p(xs), None if xc is None else _p(xc)))
+        self.n = n * int(nchoices)
+        self.p = (int(nchoices) - 1) * psub + pch
+
+    def mlogit_set_flip_order(self, order):
+        o = np.ascontiguousarray(order, dtype=np.int32)
+        if o.ndim != 1:
+            raise ValueError("the flip order is a vector, one entry per coefficient")
+        self._check(self.lib.ba_mlogit_set_flip_order(self._h, o.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    def mlogit_allow_model_selection(self, allow=True):
+        self._check(self.lib.ba_mlogit_allow_model_selection(self._h, 1 if allow else 0))
+
+    def mlogit_sweep(self, nsweeps=1, sync=True):
+        self._check(self.lib.ba_mlogit_sweep(self._h, nsweeps))
+        if sync:
+            self.sync()
+
+    def mlogit_get_latent(self, chain):
+        """(u, w) of the last imputation of one chain, n nchoices each, row i nchoices + m"""
+        N = getattr(self, "n", 1)   # (without multinomial logit data the call is refused before it writes)
+        u, w = np.zeros(N), np.zeros(N)
+        self._check(self.lib.ba_mlogit_get_latent(self._h, int(chain), _p(u), _p(w)))
+        return u, w
+
+    def mlogit_get_wss(self, chain):
+        out = np.zeros(1)
+        self._check(self.lib.ba_mlogit_get_wss(self._h, int(chain), _p(out)))
+        return float(out[0])
 
     def logit_set_imputer(self, kind):
         """0: the reference's auxiliary mixture (default); 1: Polya-Gamma"""

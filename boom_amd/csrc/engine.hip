@@ -45,6 +45,11 @@ const char *status_message(int st) {
     case QUANTILE_WEIGHT_ERROR:
       return "An inverse-Gaussian weight of the quantile regression imputation came out "
              "non-finite or not positive.";
+    case MLOGIT_IMPUTE_ERROR:
+      return "A linear predictor or a utility of the multinomial logit imputation came out "
+             "non-finite, or the mixture component scan of rmulti fell off its end.";
+    case MLVS_ILLEGAL_START:
+      return "MLVS did not start with a legal configuration.";
     default:
       return "unknown chain status";
   }
@@ -60,6 +65,8 @@ int status_code(int st) {
     case CHAIN_MODEL_TOO_LARGE: return BA_E_MODEL_TOO_LARGE;
     case STUDENT_SLICE_ERROR: return BA_E_RNG_BRANCH;
     case QUANTILE_WEIGHT_ERROR: return BA_E_RNG_BRANCH;
+    case MLOGIT_IMPUTE_ERROR: return BA_E_RNG_BRANCH;
+    case MLVS_ILLEGAL_START: return BA_E_ILLEGAL_START;
     default: return BA_E_INVALID;
   }
 }
@@ -373,6 +380,13 @@ void fill_params(ba_engine *e, SsvsParams &P) {
     // BinomialLogitSpikeSlabSampler: the sampler's own shuffle, every chain's own V
     // (which moves with the latent data: factors and tables are rebuilt)
     P.mode = e->data_kind == DATA_LOGIT ? 2 : 1;   // (the Poisson, Student and quantile samplers drive the plain SpikeSlabSampler)
+    if (e->data_kind == DATA_MLOGIT) {
+      // MLVS::draw_inclusion_vector: its own fixed order, acceptance and empty model (mode 3)
+      P.mode = 3;
+      P.flip_order = e->dml_order.ptr;
+      P.wss = e->dml_wss.ptr;
+      if (!e->mlogit_select) P.max_flips = 0;   // MLVS::suppress_model_selection
+    }
     P.V = e->dlogit_V.ptr;
     P.v_chain_stride = (int64_t)e->p * e->p;
     P.model_keep = 0;
@@ -495,6 +509,8 @@ static int escalate(ba_engine *e, std::vector<int32_t> &st) {
     if (!any) return BA_OK;
     if (e->cfg.max_model_size_hint > 0) return BA_OK;  // stays an error
     if (e->kcap >= cap_limit(*e)) {
+      // (MLVS has no large-model sweep: more than 64 included variables stay an error)
+      if (e->data_kind == DATA_MLOGIT) return BA_OK;
       // beyond the LDS kernel: the parked chains go to the HBM-resident one
       int stuck = 0;
       int rc = grow_big(e, &stuck);
@@ -606,6 +622,9 @@ int check_chain_status(ba_engine *e) {
           std::fprintf(stderr, "\n");
         }
       }
+      if (e->data_kind == DATA_MLOGIT && st[c] == CHAIN_MODEL_TOO_LARGE)
+        return fail(BA_E_MODEL_TOO_LARGE, std::string("The multinomial logit sampler holds models of up to 64 included "
+                                                      "variables; a chain needs more.") + buf);
       return fail(status_code(st[c]), std::string(status_message(st[c])) + buf);
     }
   }
@@ -1000,7 +1019,7 @@ const char *ba_kernel_class_name(int32_t cls) {
       "xtwx_cols_kernel<false>+plain_reduce_kernel", "xtwx_cols_kernel<true>+xtwx_cols_reduce_kernel",
       "xtx_mfma_kernel+plane_sum_kernel+col_reduce_kernel", "poisson_impute_kernel",
       "kalman_prepare_kernel", "ss_round_kernel", "student_impute_kernel", "student_sigma_nu_kernel",
-      "quantile_impute_kernel"};
+      "quantile_impute_kernel", "mlogit_impute_kernel"};
   return (cls >= 0 && cls < KT_CLASSES) ? names[cls] : "";
 }
 
@@ -1577,7 +1596,8 @@ static const char *const kSetDataFirst[] = {nullptr,
                                             "call ba_logit_set_data first",
                                             "call ba_poisson_set_data first",
                                             "call ba_student_set_data first",
-                                            "call ba_quantile_set_data first"};
+                                            "call ba_quantile_set_data first",
+                                            "call ba_mlogit_set_data first"};
 // ... and where the data in hand send a caller of another family's entry point
 static const char *const kUseSweep[] = {nullptr,
                                         "state-space data are set: use ba_ss_sweep",
@@ -1585,7 +1605,8 @@ static const char *const kUseSweep[] = {nullptr,
                                         "binomial data are set: use ba_logit_sweep",
                                         "Poisson data are set: use ba_poisson_sweep",
                                         "Student-t regression data are set: use ba_student_sweep",
-                                        "quantile regression data are set: use ba_quantile_sweep"};
+                                        "quantile regression data are set: use ba_quantile_sweep",
+                                        "multinomial logit data are set: use ba_mlogit_sweep"};
 
 const char *set_data_first(DataKind wants) { return kSetDataFirst[wants]; }
 
@@ -1595,8 +1616,10 @@ int sweep_refusal(const ba_engine *e, DataKind wants, bool sss) {
   if (have == wants) return BA_OK;
   // (the quantile sampler's column and row: every other sweep names ba_quantile_sweep, and
   // ba_quantile_sweep asks for its own data whatever else is set)
-  if (have == DATA_QUANTILE) return fail(BA_E_STATE, kUseSweep[have]);
-  if (wants == DATA_STATE_SPACE || wants == DATA_QUANTILE) return fail(BA_E_STATE, kSetDataFirst[wants]);
+  // (so with the multinomial logit sampler's)
+  if (have == DATA_QUANTILE || have == DATA_MLOGIT) return fail(BA_E_STATE, kUseSweep[have]);
+  if (wants == DATA_STATE_SPACE || wants == DATA_QUANTILE || wants == DATA_MLOGIT)
+    return fail(BA_E_STATE, kSetDataFirst[wants]);
   if (have == DATA_STUDENT) return fail(BA_E_STATE, kUseSweep[have]);
   if (wants == DATA_REGRESSION) {   // ba_sweep, ba_draw_next, ba_adaptive_sweep; ba_sss_sweep
     if (have == DATA_STATE_SPACE) return fail(BA_E_STATE, kUseSweep[have]);

@@ -1,9 +1,10 @@
 // Host side of the latent-data families: BinomialProbit-, BinomialLogit-, PoissonRegression-,
-// TRegression- and QuantileRegressionSpikeSlabSampler.  Each imputes its latent data
-// (probit_kernel.hip, student_kernel.hip, quantile_kernel.hip) and lets the SpikeSlabSampler
-// sweep draw indicators and coefficients on the imputed regression; the logit, Poisson,
-// Student-t and quantile samplers keep every chain's own V = slab precision + X'WX, built a
-// vector at a time (the column service, xtwx_cols_kernel.hip).
+// TRegression- and QuantileRegressionSpikeSlabSampler, and MLVS (multinomial logit).  Each
+// imputes its latent data (probit_kernel.hip, student_kernel.hip, quantile_kernel.hip,
+// mlogit_kernel.hip) and lets the SpikeSlabSampler sweep -- MLVS: its own variant of it, the
+// sweep's mode 3 -- draw indicators and coefficients on the imputed regression; the logit,
+// Poisson, Student-t, quantile and multinomial logit samplers keep every chain's own
+// V = slab precision + X'WX, built a vector at a time (the column service, xtwx_cols_kernel.hip).
 #include "engine_internal.h"
 
 namespace boom_amd {
@@ -164,6 +165,42 @@ static void fill_quantile_params(ba_engine *e, QuantileParams &U) {
   U.status = e->dstatus.ptr;
 }
 
+static void fill_mlogit_params(ba_engine *e, MlogitParams &G) {
+  std::memset(&G, 0, sizeof(G));
+  G.n = (int32_t)e->mlogit_n;
+  G.nchoices = e->mlogit_choices;
+  G.p = (int32_t)e->p;
+  G.chains = (int32_t)e->cfg.chains;
+  G.slot_limit = e->slot_limit;
+  G.chain_offset = e->cfg.chain_offset;
+  G.X = e->dprob_X.ptr;
+  G.y = e->dml_y.ptr;
+  G.gamma = e->dgamma.ptr;
+  G.beta = e->dbeta.ptr;
+  G.z = e->dprob_z.ptr;
+  G.w = e->dlogit_w.ptr;
+  G.u = e->dml_u.ptr;
+  G.wss_part = e->dml_wss_part.ptr;
+  G.wss = e->dml_wss.ptr;
+  // The normal mixture for the extreme value distribution, the three literal vectors of
+  // MLVS_data_imputer.cpp:39-43 (means, variances, weights), and what the constructor there
+  // derives from them: sigsq_inv_ = pow(variances, -1), sd_ = pow(sigsq_inv_, -0.5),
+  // log_mixing_weights_ = log(weights).
+  static const double kMu[MLOGIT_NCOMP] = {5.09, 3.29, 1.82, 1.24, 0.76, 0.39, 0.04, -0.31, -0.67, -1.06};
+  static const double kVar[MLOGIT_NCOMP] = {4.5, 2.02, 1.1, 0.42, 0.2, 0.11, 0.08, 0.08, 0.09, 0.15};
+  static const double kWeight[MLOGIT_NCOMP] = {0.004, 0.04, 0.168, 0.147, 0.125, 0.101, 0.104, 0.116, 0.107, 0.088};
+  for (int c = 0; c < MLOGIT_NCOMP; ++c) {
+    G.mix_mu[c] = kMu[c];
+    G.mix_prec[c] = std::pow(kVar[c], -1.0);
+    G.mix_sd[c] = std::pow(G.mix_prec[c], -0.5);
+    G.mix_logsd[c] = std::log(G.mix_sd[c]);
+    G.mix_logw[c] = std::log(kWeight[c]);
+  }
+  G.seed_lo = (uint32_t)e->seed;
+  G.seed_hi = (uint32_t)(e->seed >> 32);
+  G.status = e->dstatus.ptr;
+}
+
 // the Student sampler's per-chain state: nu = 30 (TRegression.cpp:35-45), suggested_dx = 1
 // (TRegressionSampler.cpp:88-107), no slice comparison seen yet
 static int student_prepare(ba_engine *e) {
@@ -187,11 +224,14 @@ static int student_prepare(ba_engine *e) {
 // inclusion / coefficient draws with park-and-replay for vectors requested mid-sweep
 static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
   const bool student = e->data_kind == DATA_STUDENT, quantile = e->data_kind == DATA_QUANTILE;
+  const bool mlogit = e->data_kind == DATA_MLOGIT;
   if (!e->have_slab) return fail(BA_E_STATE, "call ba_sss_set_slab first");
   if (student && !e->sss_slab_scales)
     return fail(BA_E_INVALID, "the Student-t sampler takes a slab whose precision scales with sigma^2 (scales_with_sigsq = 1)");
   if (quantile && e->sss_slab_scales)
     return fail(BA_E_INVALID, "the quantile regression sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
+  if (mlogit && e->sss_slab_scales)
+    return fail(BA_E_INVALID, "the multinomial logit sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
   if (!student && e->sss_slab_scales) return fail(BA_E_INVALID, "the logit sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
   int rc = alloc_chain_state(e);
   if (rc) return rc;
@@ -202,6 +242,21 @@ static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
     if (e->trace_stride > 0 && nsweeps > e->trace_stride)
       return fail(BA_E_INVALID, "nsweeps exceeds the enabled trace length");
     if (e->dstu_u.count != C * n) HIP_TRY(e->dstu_u.resize(C * n));
+  }
+  if (mlogit) {
+    const size_t nb = (size_t)((e->mlogit_n + 255) / 256);
+    if (e->dml_u.count != C * n) HIP_TRY(e->dml_u.resize(C * n));
+    if (e->dml_wss_part.count != C * nb) HIP_TRY(e->dml_wss_part.resize(C * nb));
+    if (e->dml_wss.count != C) {
+      HIP_TRY(e->dml_wss.resize(C));
+      HIP_TRY(hipMemset(e->dml_wss.ptr, 0, C * 8));
+    }
+    if (e->dml_order.count != p) {   // (default: the identity)
+      std::vector<uint16_t> id(p);
+      for (size_t j = 0; j < p; ++j) id[j] = (uint16_t)j;
+      HIP_TRY(e->dml_order.resize(p));
+      HIP_TRY(hipMemcpy(e->dml_order.ptr, id.data(), p * 2, hipMemcpyHostToDevice));
+    }
   }
   if (e->dprob_z.count != C * n || e->dlogit_V.count != C * p * p) {
     HIP_TRY(e->dprob_z.resize(C * n));
@@ -238,13 +293,16 @@ static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
   fill_student_params(e, T);   // (read by the Student-t launches only)
   QuantileParams U;
   fill_quantile_params(e, U);  // (read by the quantile launch only)
+  MlogitParams G;
+  fill_mlogit_params(e, G);    // (read by the multinomial logit launch only)
   // (the draws recorded are those of the last ba_student_sweep call)
   if (student && e->trace_stride > 0) HIP_TRY(hipMemsetAsync(e->dtrace_idx.ptr, 0, C * 4, e->stream));
   // BinomialLogitSpikeSlabSampler::draw (BinomialLogitSpikeSlabSampler.cpp:50-54) /
   // PoissonRegressionSpikeSlabSampler::draw (PoissonRegressionSpikeSlabSampler.cpp:55-59) /
-  // QuantileRegressionSpikeSlabSampler::draw (QuantileRegressionPosteriorSampler.cpp:77-91)
+  // QuantileRegressionSpikeSlabSampler::draw (QuantileRegressionPosteriorSampler.cpp:77-91) /
+  // MLVS::draw (MLVS.cpp:71-75)
   for (int i = 0; i < nsweeps; ++i) {
-    Q.sweep = T.sweep = U.sweep = e->probit_sweep++;
+    Q.sweep = T.sweep = U.sweep = G.sweep = e->probit_sweep++;
     // impute_latent_data: z, w, X'Wz and the diagonal of V = slab precision + X'WX ...
     if (student)
       HIP_TRY(launch_student_impute(e->stream, T, e->dlogit_Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->dlogit_vdiag.ptr,
@@ -252,6 +310,9 @@ static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
     else if (quantile)
       HIP_TRY(launch_quantile_impute(e->stream, U, e->dlogit_Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->dlogit_vdiag.ptr,
                                      e->dlogit_planes.ptr));
+    else if (mlogit)
+      HIP_TRY(launch_mlogit_impute(e->stream, G, e->dlogit_Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->dlogit_vdiag.ptr,
+                                   e->dlogit_planes.ptr));
     else
       HIP_TRY(launch_logit_impute(e->stream, Q, e->dlogit_Xsq.ptr, e->dA.ptr, e->dlogit_vdiag.ptr,
                                   e->dlogit_planes.ptr, imputer));
@@ -647,6 +708,122 @@ int ba_quantile_get_weights(ba_engine *e, int64_t chain, double *w) {
     return fail(BA_E_STATE, "no imputation has run yet: call ba_quantile_sweep first");
   HIP_TRY(hipStreamSynchronize(e->stream));
   HIP_TRY(hipMemcpy(w, e->dlogit_w.ptr + (size_t)chain * n, n * 8, hipMemcpyDeviceToHost));
+  return BA_OK;
+}
+
+// ------------------------ MLVS (multinomial logit spike and slab)
+int ba_mlogit_set_data(ba_engine *e, int64_t n, int32_t nchoices, int32_t psub, int32_t pch, const int32_t *y,
+                       const double *Xsubject, const double *Xchoice) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!y) return fail(BA_E_INVALID, "null argument");
+  if (n <= 0) return fail(BA_E_INVALID, "n must be positive");
+  if (nchoices < 2 || nchoices > MLOGIT_MAX_CHOICES)
+    return fail(BA_E_INVALID, "the number of choices must be between 2 and 16");
+  if (psub < 0 || pch < 0 || (psub == 0 && pch == 0))
+    return fail(BA_E_INVALID, "subject and choice dimensions must be non-negative and not both zero");
+  if ((psub > 0) != (Xsubject != nullptr)) return fail(BA_E_INVALID, "Xsubject must be given iff psub > 0");
+  if ((pch > 0) != (Xchoice != nullptr)) return fail(BA_E_INVALID, "Xchoice must be given iff pch > 0");
+  for (int64_t i = 0; i < n; ++i)
+    if (y[i] < 0 || y[i] >= nchoices) return fail(BA_E_INVALID, "responses must be choices 0 .. nchoices - 1");
+  const int64_t N = n * nchoices, D = (int64_t)(nchoices - 1) * psub + pch;
+  if (D > 65535) return fail(BA_E_INVALID, "number of predictors must be in [1, 65535]");
+  if (N > (int64_t)0x7fffffff) return fail(BA_E_INVALID, "n times the number of choices must fit 31 bits");
+  // the expanded design and its element-wise square stay on the device: 16 N D bytes
+  if ((double)N * (double)D * 16.0 > 8.0 * 1073741824.0)
+    return fail(BA_E_INVALID, "the expanded design (n nchoices rows by (nchoices - 1) psub + pch columns, 16 bytes "
+                              "an element with its square) exceeds 8 GiB");
+  DevBuf<double> dxs, dxc, zero;
+  if (psub > 0) {
+    HIP_TRY(dxs.resize((size_t)n * psub));
+    HIP_TRY(hipMemcpy(dxs.ptr, Xsubject, (size_t)n * psub * 8, hipMemcpyHostToDevice));
+  }
+  if (pch > 0) {
+    HIP_TRY(dxc.resize((size_t)N * pch));
+    HIP_TRY(hipMemcpy(dxc.ptr, Xchoice, (size_t)N * pch * 8, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(e->dprob_X.resize((size_t)N * D));
+  HIP_TRY(e->dlogit_Xsq.resize((size_t)N * D));
+  HIP_TRY(launch_mlogit_expand(e->stream, n, nchoices, psub, pch, dxs.ptr, dxc.ptr, e->dprob_X.ptr, e->dlogit_Xsq.ptr));
+  HIP_TRY(zero.resize((size_t)N));
+  HIP_TRY(hipMemsetAsync(zero.ptr, 0, (size_t)N * 8, e->stream));
+  int rc = ba_build_suf_from_xy_device(e, N, (int32_t)D, e->dprob_X.ptr, zero.ptr);   // (dimensions and the shared buffers)
+  if (rc) return rc;
+  HIP_TRY(e->dml_y.resize((size_t)n));
+  HIP_TRY(hipMemcpy(e->dml_y.ptr, y, (size_t)n * 4, hipMemcpyHostToDevice));
+  e->dprob_z.release();
+  e->dml_u.release();
+  e->dml_order.release();   // (the identity until ba_mlogit_set_flip_order)
+  e->probit_n = N;
+  e->probit_clt = 0;
+  e->probit_sweep = 0;
+  e->mlogit_n = n;
+  e->mlogit_choices = nchoices;
+  e->mlogit_psub = psub;
+  e->mlogit_pch = pch;
+  e->data_kind = DATA_MLOGIT;
+  return BA_OK;
+}
+
+int ba_mlogit_set_flip_order(ba_engine *e, const int32_t *order) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!order) return fail(BA_E_INVALID, "null argument");
+  if (e->data_kind != DATA_MLOGIT) return fail(BA_E_STATE, set_data_first(DATA_MLOGIT));
+  const size_t p = (size_t)e->p;
+  std::vector<uint16_t> o(p);
+  std::vector<uint8_t> seen(p, 0);
+  for (size_t j = 0; j < p; ++j) {
+    if (order[j] < 0 || (size_t)order[j] >= p || seen[(size_t)order[j]])
+      return fail(BA_E_INVALID, "the flip order must be a permutation of 0 .. D - 1");
+    seen[(size_t)order[j]] = 1;
+    o[j] = (uint16_t)order[j];
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(e->dml_order.resize(p));
+  HIP_TRY(hipMemcpy(e->dml_order.ptr, o.data(), p * 2, hipMemcpyHostToDevice));
+  return BA_OK;
+}
+
+int ba_mlogit_allow_model_selection(ba_engine *e, int32_t allow) {
+  if (!e) return fail(BA_E_INVALID, "null engine");
+  MUTATE(e);
+  e->mlogit_select = allow != 0;
+  return BA_OK;
+}
+
+int ba_mlogit_sweep(ba_engine *e, int32_t nsweeps) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
+  int rc = sweep_refusal(e, DATA_MLOGIT);
+  if (rc) return rc;
+  return logit_family_sweep(e, nsweeps);
+}
+
+int ba_mlogit_get_latent(ba_engine *e, int64_t chain, double *u, double *w) {
+  ENGINE_PROLOGUE(e);
+  if (!u || !w) return fail(BA_E_INVALID, "null argument");
+  if (e->data_kind != DATA_MLOGIT) return fail(BA_E_STATE, set_data_first(DATA_MLOGIT));
+  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  const size_t N = (size_t)e->probit_n;
+  if (e->dml_u.count != (size_t)e->cfg.chains * N || e->probit_sweep == 0)
+    return fail(BA_E_STATE, "no imputation has run yet: call ba_mlogit_sweep first");
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(u, e->dml_u.ptr + (size_t)chain * N, N * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(w, e->dlogit_w.ptr + (size_t)chain * N, N * 8, hipMemcpyDeviceToHost));
+  return BA_OK;
+}
+
+int ba_mlogit_get_wss(ba_engine *e, int64_t chain, double *wss) {
+  ENGINE_PROLOGUE(e);
+  if (!wss) return fail(BA_E_INVALID, "null argument");
+  if (e->data_kind != DATA_MLOGIT) return fail(BA_E_STATE, set_data_first(DATA_MLOGIT));
+  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  if (e->dml_wss.count != (size_t)e->cfg.chains || e->probit_sweep == 0)
+    return fail(BA_E_STATE, "no imputation has run yet: call ba_mlogit_sweep first");
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(wss, e->dml_wss.ptr + (size_t)chain, 8, hipMemcpyDeviceToHost));
   return BA_OK;
 }
 

@@ -3,7 +3,8 @@
 //   engine.hip      creation, timing, regression data, priors, state, the BregVs / SpikeSlab /
 //                   adaptive sweeps, pipelined launches, ba_draw_next's look-ahead, summaries,
 //                   traces, prediction, check_chain_status
-//   engine_glm.hip  probit, logit, Poisson, Student-t, quantile (the latent-data families)
+//   engine_glm.hip  probit, logit, Poisson, Student-t, quantile, multinomial logit (the
+//                   latent-data families)
 //   engine_ss.hip   state space: ba_ss_*, its look-ahead, the round kernel's launches
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,6 +22,7 @@
 #include "../../include/boom_amd.h"
 #include "kalman_params.h"
 #include "ktimer.h"
+#include "mlogit_params.h"
 #include "probit_params.h"
 #include "quantile_params.h"
 #include "ssvs_params.h"
@@ -56,6 +58,11 @@ hipError_t launch_student_sigma_nu(hipStream_t stream, const StudentParams &P);
 // quantile_kernel.hip
 hipError_t launch_quantile_impute(hipStream_t stream, const QuantileParams &P, const double *Xsq,
                                   const double *slab_precision, double *xtz, double *v_diag, double *planes);
+// mlogit_kernel.hip
+hipError_t launch_mlogit_expand(hipStream_t stream, int64_t n, int M, int psub, int pch, const double *Xs,
+                                const double *Xc, double *X, double *Xsq);
+hipError_t launch_mlogit_impute(hipStream_t stream, const MlogitParams &P, const double *Xsq,
+                                const double *slab_precision, double *xtz, double *v_diag, double *planes);
 hipError_t launch_logit_impute(hipStream_t stream, const ProbitParams &P, const double *Xsq,
                                const double *slab_precision, double *v_diag, double *planes,
                                int polya_gamma);
@@ -122,12 +129,13 @@ struct DevBuf {
 // last step; DATA_REGRESSION is also the state of a fresh engine (have_suf says whether
 // anything was uploaded).  Every sweep entry point serves one kind and refuses the others
 // (sweep_refusal, engine.hip).
-enum DataKind { DATA_REGRESSION, DATA_STATE_SPACE, DATA_PROBIT, DATA_LOGIT, DATA_POISSON, DATA_STUDENT, DATA_QUANTILE };
+enum DataKind { DATA_REGRESSION, DATA_STATE_SPACE, DATA_PROBIT, DATA_LOGIT, DATA_POISSON, DATA_STUDENT, DATA_QUANTILE,
+                DATA_MLOGIT };
 // the latent-data families: the regression runs on every chain's own imputed responses
-inline bool latent_data(DataKind k) { return k == DATA_PROBIT || k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE; }
+inline bool latent_data(DataKind k) { return k == DATA_PROBIT || k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT; }
 // ... and those of them whose V = slab precision + X'WX is every chain's own, built a vector
 // at a time (serve_columns, engine_glm.hip)
-inline bool column_service(DataKind k) { return k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE; }
+inline bool column_service(DataKind k) { return k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT; }
 
 }  // namespace boom_amd
 
@@ -337,6 +345,14 @@ struct ba_engine {
   // QuantileRegressionSpikeSlabSampler (quantile_kernel.hip): the Poisson path with its own
   // imputation; the model's quantile
   double quantile_q = 0.5;
+  // MLVS (mlogit_kernel.hip): the Poisson path on the expanded design (N = n M rows, D columns;
+  // probit_n = N, p = D) with its own imputation and the sweep's mode 3
+  int64_t mlogit_n = 0;
+  int32_t mlogit_choices = 0, mlogit_psub = 0, mlogit_pch = 0;
+  bool mlogit_select = true;       // (ba_mlogit_allow_model_selection)
+  DevBuf<int32_t> dml_y;
+  DevBuf<uint16_t> dml_order;      // the sweep's visiting order, D entries
+  DevBuf<double> dml_u, dml_wss_part, dml_wss;
   int slot_limit = 0;              // (ba_set_slot_limit)
   DevBuf<double> dlogit_w, dlogit_V;
   // ... V built a vector at a time (xtwx_cols_kernel.hip): the squared design matrix

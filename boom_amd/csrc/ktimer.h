@@ -29,6 +29,7 @@ enum KernelClass {
   KT_STUDENT_IMPUTE,   // student_impute_kernel
   KT_STUDENT_SIGMA_NU, // student_sigma_nu_kernel
   KT_QUANTILE_IMPUTE,  // quantile_impute_kernel
+  KT_MLOGIT_IMPUTE,    // mlogit_impute_kernel + mlogit_wss_kernel
   KT_CLASSES
 };
 

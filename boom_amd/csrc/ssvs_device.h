@@ -153,6 +153,7 @@ struct Chain {
   // (all 1 for BregVsSampler, where sigma^2 is integrated out)
   int mode;
   double sv, sa, sx;
+  double k0add;   // MLVS instantiations only: wss / 2, what the empty model's value adds (MLVS.cpp:166-168)
 };
 
 __device__ __forceinline__ void bind_lds(Chain &ch, unsigned char *smem,
@@ -272,7 +273,7 @@ __device__ __forceinline__ void chol_blocks2(const Chain &ch, lds_f64 *LA, lds_f
 // already in LDS / M -- restored from the chain's block at the start of a
 // launch -- and only what depends on the sufficient statistics X'y, y'y is
 // recomputed (state-space path: they move every sweep).
-template <bool REUSE>
+template <bool REUSE, bool MLVS = false>
 __device__ __forceinline__ void refactor(const SsvsParams &P, Chain &ch, Model &M, StampCtx &sx) {
   const int lane = ch.lane, p = ch.p, k = ch.k;
   M.bad = 0;
@@ -327,7 +328,8 @@ __device__ __forceinline__ void refactor(const SsvsParams &P, Chain &ch, Model &
   M.SS = ch.ss0q;
   if (k == 0) {
     // empty model: BregVsSampler.cpp:217-227 / SpikeSlabSampler.cpp:173-183
-    M.logp = ch.mode ? lp : lp - (0.5 * ch.DF - 1.0) * log(ch.ss0q);
+    if constexpr (MLVS) M.logp = lp + ch.k0add;   // (the sign is the reference's: num -= -.5 wss)
+    else M.logp = ch.mode ? lp : lp - (0.5 * ch.DF - 1.0) * log(ch.ss0q);
     return;
   }
   if (lp == -BA_INF) {
@@ -591,7 +593,7 @@ struct Proposal {
 // (g_m, j) of the symmetric matrix is read down column j of row g_m and the 64
 // lanes share four cache lines; otherwise (arbitrary j per lane) it is read
 // as element (j, g_m), the lane's k elements sharing a few lines of its row.
-template <int NB, bool NAT>
+template <int NB, bool NAT, bool MLVS = false>
 __device__ __forceinline__ Proposal eval_proposal(const SsvsParams &P, Chain &ch,
                                                   const Model &M, int j,
                                                   bool valid, StampCtx &sx, int jbase = 0) {
@@ -626,7 +628,8 @@ __device__ __forceinline__ Proposal eval_proposal(const SsvsParams &P, Chain &ch
   const bool fast = live && !empty_after && !slow;
   out.slow = slow;
   if (empty_after) {
-    out.logp = ch.mode ? lpn : lpn - (0.5 * ch.DF - 1.0) * log(ch.ss0q);
+    if constexpr (MLVS) out.logp = lpn + ch.k0add;
+    else out.logp = ch.mode ? lpn : lpn - (0.5 * ch.DF - 1.0) * log(ch.ss0q);
   }
   const double vjj = (fast && add) ? vjj_raw * ch.sv : 0.0;
   const double ajj = (fast && add) ? ajj_raw * ch.sa : 0.0;
@@ -1193,7 +1196,12 @@ enum : int { EVM_BATCH = 0, EVM_FILL = 1 };
 //   EVM_FILL    lane = variable i0 + 64 wave + lane: evaluate it against the
 //               current model and store the result in the chain's table;
 // (Decisions by table look-up are decide_walk below.)
-template <int NB>
+// MLVS: a flip is kept iff u < logit_inv(logp' - logp) (keep_flip, MLVS.cpp:120-125), i.e.
+// log(u) - log1p(-u) <= logp' - logp: the uniform's logit takes the place of its logarithm,
+// and the table holds logit_inv of the difference instead of its exponential (the table walk's
+// margin |u / E - 1| is then in that scale; the multinomial logit round launches one sweep at
+// a time without keeping tables, so its decisions are the batch path's).
+template <int NB, bool MLVS = false>
 __device__ __forceinline__ void eval_share(const SsvsParams &P, Chain &ch,
                                            const Model &M, const PhiloxKey &key,
                                            uint64_t flip_pos, int nflips, int i0,
@@ -1204,12 +1212,13 @@ __device__ __forceinline__ void eval_share(const SsvsParams &P, Chain &ch,
   const int idx = i0 + WAVE * wave + lane;
   if (evmode == EVM_FILL) {
     const bool valid = idx < ch.p;
-    const Proposal pr = eval_proposal<NB, true>(P, ch, M, valid ? idx : 0, valid, sx, idx - lane);
+    const Proposal pr = eval_proposal<NB, true, MLVS>(P, ch, M, valid ? idx : 0, valid, sx, idx - lane);
     if (valid) {
       // acceptance threshold in the uniform's own scale: log u <= logp' - logp
       // <=> u <= exp(logp' - logp)   (0 for an impossible model, inf / NaN --
       // never exceeded -- when the current model itself is impossible)
-      ch.tab_lp[idx] = exp(pr.logp - M.logp);
+      if constexpr (MLVS) ch.tab_lp[idx] = 1.0 / (1.0 + exp(M.logp - pr.logp));
+      else ch.tab_lp[idx] = exp(pr.logp - M.logp);
       ch.tab_kind[idx] = (uint8_t)(pr.bad_ss ? STOP_BAD : (pr.slow ? STOP_SLOW : 0));
     }
     SUBSTAMP(sx, 6);
@@ -1218,12 +1227,12 @@ __device__ __forceinline__ void eval_share(const SsvsParams &P, Chain &ch,
   const bool valid = idx < nflips;
   const int j = valid ? (int)ch.perm[idx] : 0;
   const double u = philox_uniform(key, flip_pos + (uint64_t)idx);
-  const double logu = log(u);
+  const double logu = MLVS ? log(u) - log1p(-u) : log(u);
 #if defined(BA_STAMPS2)
   asm volatile("" :: "v"(logu) : "memory");
 #endif
   SUBSTAMP(sx, 7);
-  const Proposal pr = eval_proposal<NB, false>(P, ch, M, j, valid, sx);
+  const Proposal pr = eval_proposal<NB, false, MLVS>(P, ch, M, j, valid, sx);
   const double lpj = pr.logp;
   const bool slow = valid && pr.slow;
   const bool bad = valid && pr.bad_ss;
@@ -1281,6 +1290,7 @@ __device__ __forceinline__ unsigned long long walk_pos_stop(WalkPos &w) {
   w.acc = w.val && !special && !(w.u > w.e);
   return __ballot(w.val && (special || w.acc));
 }
+template <bool MLVS = false>
 __device__ __forceinline__ void decide_walk(const Chain &ch, const PhiloxKey &key,
                                             uint64_t flip_pos, int i0, int nflips,
                                             DecideResult &out) {
@@ -1354,7 +1364,10 @@ __device__ __forceinline__ void decide_walk(const Chain &ch, const PhiloxKey &ke
     out.spos = qb + fr * 2 * WAVE + f;
     out.j = __builtin_amdgcn_readlane(sj, fl);
     out.kind = __builtin_amdgcn_readlane(sk, fl);
-    out.logu = log(bcast_u(su, fl));
+    {
+      const double us = bcast_u(su, fl);
+      out.logu = MLVS ? log(us) - log1p(-us) : log(us);
+    }
     break;
   }
   out.margin = wave_min(lane_margin);

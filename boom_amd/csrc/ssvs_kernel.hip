@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void ssvs_reduce_summaries_kernel(SsvsParams P
 // early finishers leave, each taking over a chain that IS done (in the order the chains
 // finish), so nothing idles between two launches and no chain is ever in two places.
 enum : int { Q_PUSH = 0, Q_POP = 1, Q_READY = 2 };
-template <int NB, int W, int WPE>
+template <int NB, int W, int WPE, bool MLVS = false>
 __global__ __launch_bounds__(64 * W, WPE) void ssvs_sweep_kernel(SsvsParams P, int nsweeps) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int s_chain;
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(64 * W, WPE) void ssvs_sweep_kernel(SsvsParams P, i
       P.snap_fail[chain] = P.failures[chain];
     }
   }
-  ssvs_sweep_body<NB, W, WPE>(P, nsweeps, chain, smem);
+  ssvs_sweep_body<NB, W, WPE, MLVS>(P, nsweeps, chain, smem);
   if (P.q_out) {
     __syncthreads();
     __threadfence();
@@ -214,16 +214,16 @@ __global__ __launch_bounds__(64 * W, WPE) void ssvs_sweep_kernel(SsvsParams P, i
 // (NB, W, WPE): model capacity 8 NB; W wavefronts per chain; WPE = waves per
 // SIMD the register budget is sized for (W = 4 needs 4 resident waves per SIMD
 // for 4 chains per CU, i.e. <= 128 VGPRs, which only the small capacities reach)
-template <int NB, int W, int WPE>
+template <int NB, int W, int WPE, bool MLVS = false>
 static hipError_t launch_sweep_t(hipStream_t stream, const SsvsParams &P,
                                  int nsweeps) {
   const SsvsLds lay = ssvs_lds_layout(P.p, NB * 8);
-  hipError_t e = hipFuncSetAttribute((const void *)ssvs_sweep_kernel<NB, W, WPE>,
+  hipError_t e = hipFuncSetAttribute((const void *)ssvs_sweep_kernel<NB, W, WPE, MLVS>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)lay.total);
   if (e != hipSuccess) return e;
   KtScope kt(stream, KT_SSVS);
-  hipLaunchKernelGGL((ssvs_sweep_kernel<NB, W, WPE>), dim3(P.chain_count), dim3(WAVE * W),
+  hipLaunchKernelGGL((ssvs_sweep_kernel<NB, W, WPE, MLVS>), dim3(P.chain_count), dim3(WAVE * W),
                      lay.total, stream, P, nsweeps);
   return hipGetLastError();
 }
@@ -231,6 +231,20 @@ static hipError_t launch_sweep_t(hipStream_t stream, const SsvsParams &P,
 hipError_t launch_ssvs_sweep(hipStream_t stream, const SsvsParams &P,
                              int nsweeps) {
   const int key = P.kcap * 10 + P.waves;
+#ifndef BA_ONLY_322
+  if (P.mode == 3) {
+    // MLVS: one wavefront per chain at every capacity (a launch is one sweep of a round whose
+    // time is the imputation's and the GEMMs': DESIGN 3.12)
+    if (!P.flip_order || !P.wss) return hipErrorInvalidValue;
+    switch (P.kcap) {
+      case 16: return launch_sweep_t<2, 1, 1, true>(stream, P, nsweeps);
+      case 32: return launch_sweep_t<4, 1, 1, true>(stream, P, nsweeps);
+      case 48: return launch_sweep_t<6, 1, 1, true>(stream, P, nsweeps);
+      case 64: return launch_sweep_t<8, 1, 1, true>(stream, P, nsweeps);
+      default: return hipErrorInvalidValue;
+    }
+  }
+#endif
   switch (key) {
 #ifdef BA_ONLY_322   // (compile-time experiments on the hot instance only)
     case 322: return launch_sweep_t<4, 2, 2>(stream, P, nsweeps);

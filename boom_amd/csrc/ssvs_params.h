@@ -19,7 +19,12 @@ enum ChainStatus : int32_t {
   // the host computes it (col_request names it) and the sweep is replayed
   CHAIN_NEED_COLUMN = 7,
   CHAIN_NEED_COLUMN_BIG = 8   // the same, from the large-model kernel
+  // (9: STUDENT_SLICE_ERROR, 10: QUANTILE_WEIGHT_ERROR, 11: MLOGIT_IMPUTE_ERROR -- the
+  // imputation kernels' own, student_params.h, quantile_params.h, mlogit_params.h)
 };
+// MLVS::draw_inclusion_vector found a start whose log_model_prob is not finite (MLVS.cpp:130-138;
+// the other samplers call make_valid there)
+enum { MLVS_ILLEGAL_START = 12 };
 
 // number of doubles in the reduced summary block: 3p + SUMMARY_SCALARS
 enum { SUMMARY_SCALARS = 16 };
@@ -50,7 +55,10 @@ struct SsvsParams {
   int32_t waves; // wavefronts per chain (1, 2 or 4)
   // 0: BregVsSampler (sigma^2 integrated out); 1: SpikeSlabSampler (given sigma^2);
   // 2: BinomialLogitSpikeSlabSampler -- as 1, with its own way of shuffling the visiting
-  // order (every position swaps with one drawn from the whole range: p uniforms) and V per chain
+  // order (every position swaps with one drawn from the whole range: p uniforms) and V per chain;
+  // 3: MLVS (MLVS.cpp:120-190) -- as 2, but the visiting order is the fixed flip_order (no
+  // shuffle uniforms), a flip is kept iff u < logit_inv(logp' - logp), and the empty model's
+  // value adds wss / 2.  Compiled as its own instantiation of the sweep body (the MLVS flag).
   int32_t mode;
   int64_t v_chain_stride;  // doubles between the chains' V matrices (0: one shared V)
   // A chain's own V computed column by column, as the sweep needs it (the logit
@@ -200,6 +208,10 @@ struct SsvsParams {
   const double *xty_planes;
   int32_t xty_nplanes;
   int64_t xty_plane_stride;
+  // ---- MLVS (mode 3; nullptr in the other modes): the sweep's visiting order, p entries
+  // shared by the chains, and every chain's weighted_sum_of_squares of this sweep's imputation
+  const uint16_t *flip_order;
+  const double *wss;       // chains
 };
 
 // ---- LDS layout of one chain (one wavefront) --------------------------------

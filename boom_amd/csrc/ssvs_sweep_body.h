@@ -6,7 +6,13 @@
 
 namespace boom_amd {
 
-template <int NB, int W, int WPE>
+// MLVS: the instantiation that serves SsvsParams::mode 3 (MLVS::draw_inclusion_vector,
+// MLVS.cpp:127-153) -- a compile-time flag, so that the other instantiations are the code they
+// were: the fixed visiting order P.flip_order instead of a shuffle (no shuffle uniforms:
+// flip_pos = pos), the uniform's logit where the others take its logarithm (eval_share,
+// decide_walk), wss / 2 in the empty model's value (refactor, eval_proposal), and a stop
+// where the others call make_valid.  Like mode 2 it never forks.
+template <int NB, int W, int WPE, bool MLVS = false>
 __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const int chain,
                                                 unsigned char *smem) {
   // (the shuffle's mask of finished blocks, ssvs_device.h: the multi-wave instances of capacity
@@ -123,6 +129,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
   ch.ss0q = P.prior_ss + yty;
   ch.mode = P.mode;
   ch.sv = ch.sa = ch.sx = 1.0;
+  if constexpr (MLVS) ch.k0add = 0.5 * P.wss[chain];
   if (P.mode) {
     // SpikeSlabSampler works given this chain's sigma^2
     const double inv = 1.0 / P.sigsq[chain];
@@ -156,8 +163,8 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
         unsigned long long a = (unsigned long long)ch.sc_store;
         asm volatile("" : "+s"(a) : : "memory");
         ch.sc = (c_f64 *)a;
-        eval_share<NB>(P, ch, M, key, upos, (int)ctl[CT_NFLIPS], (int)ctl[CT_I0],
-                       (int)ctl[CT_EVMODE], wave, ctl, sx_unused);
+        eval_share<NB, MLVS>(P, ch, M, key, upos, (int)ctl[CT_NFLIPS], (int)ctl[CT_I0],
+                             (int)ctl[CT_EVMODE], wave, ctl, sx_unused);
         HSTAMP(sx_unused, 6);
       } else if (cmd == CMD_DECIDE || cmd == CMD_SHUFFLE_DECIDE) {
         if (cmd == CMD_SHUFFLE_DECIDE) {
@@ -180,7 +187,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
             fpos = upos + (uint64_t)(p - 1);
           }
           DecideResult dr;
-          decide_walk(ch, key, fpos, (int)ctl[CT_I0], (int)ctl[CT_NFLIPS], dr);
+          decide_walk<MLVS>(ch, key, fpos, (int)ctl[CT_I0], (int)ctl[CT_NFLIPS], dr);
           HSTAMP(sx_unused, 4);
           if (lane == 0) {
             lds_f64 *sl = ctl + CT_SLOT0 + CT_SLOT_STRIDE * 1;
@@ -324,7 +331,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
       ch.sc = (c_f64 *)u;
     }
     if (P.suf_changed) {
-      refactor<true>(P, ch, M, sx);
+      refactor<true, MLVS>(P, ch, M, sx);
       if (M.bad) status = M.bad;
       else publish_model<NB>(ch, M);
     }
@@ -401,7 +408,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
       bool rejected = false;
       {
         Model Mn;
-        refactor<false>(P, ch, Mn, sx);
+        refactor<false, MLVS>(P, ch, Mn, sx);
         if (Mn.bad) {
           status = Mn.bad;
         } else {
@@ -470,7 +477,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
       {
         const bool ut = (P.walk_policy != 0) && (stops_prev <= 1 || P.walk_policy == 2);
         const bool mc = model_checked || (M.logp > -BA_INF && M.logp < BA_INF);
-        const bool will_fork = nflips > 0 && W > 1 && ut && table_valid && mc && p > 1 && P.walk_policy != 3 && P.mode != 2;
+        const bool will_fork = nflips > 0 && W > 1 && ut && table_valid && mc && p > 1 && P.walk_policy != 3 && P.mode != 2 && !MLVS;
         if (commit_pending && !will_fork) {
           phase = PH_COMMIT;  // nothing to overlap with: commit first
           continue;
@@ -486,7 +493,9 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
             ch.gam0[j] = ch.gam[j];
             // SpikeSlabSampler shuffles a fresh identity permutation every call
             // (SpikeSlabSampler.cpp:48-57); BregVsSampler's indx persists
-            if (P.mode) ch.perm[j] = (uint16_t)j;
+            // ... and MLVS visits in its one fixed order (MLVS.cpp:140-141)
+            if constexpr (MLVS) ch.perm[j] = P.flip_order[j];
+            else if (P.mode) ch.perm[j] = (uint16_t)j;
           }
           gam0_fresh = true;
         }
@@ -496,7 +505,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
         use_table = (P.walk_policy != 0) && (stops_prev <= 1 || P.walk_policy == 2);
         stops_prev = stops_now;
         stops_now = 0;
-        if (W > 1 && use_table && table_valid && model_checked && p > 1 && P.walk_policy != 3 && P.mode != 2) {
+        if (W > 1 && use_table && table_valid && model_checked && p > 1 && P.walk_policy != 3 && P.mode != 2 && !MLVS) {
           // ---- fork: wave 1 takes the permutation side of the sweep
           wave_sync();
           if (lane == 0) {
@@ -532,6 +541,15 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
           STAMP(1);
           continue;
         }
+        if constexpr (MLVS) {
+          // ---- MLVS: no shuffle and no uniforms for one, the order is in ch.perm already.  A
+          // start that is not legal stops the chain here (the reference's report_error,
+          // MLVS.cpp:130-138), at every sweep's start.
+          wave_sync();
+          flip_pos = pos;
+          pos = flip_pos + (uint64_t)nflips;
+          if (!(M.logp > -BA_INF && M.logp < BA_INF)) { status = MLVS_ILLEGAL_START; aborted = true; }
+        } else {   // (the other modes; not re-indented)
         // ---- shuffle(indx): cpputil/shuffle.hpp:36-46, in place on the
         // persistent permutation.  Uniform t (t = 0..p-2) belongs to i = p-1-t.
         if (W > 1) {
@@ -579,6 +597,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
             pe.check_legal = true;
           }
         }
+        }   // (!MLVS)
       }
       i0 = 0;
       phase = PH_FLIPS;
@@ -617,7 +636,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
           dr.logu = uni((double)sl[SL_LOGU]);
           dr.margin = uni((double)sl[SL_MARGIN]);
         } else {
-          decide_walk(ch, key, flip_pos, i0, nflips, dr);
+          decide_walk<MLVS>(ch, key, flip_pos, i0, nflips, dr);
         }
         ACC_MIN(dr.margin);
         STAMP(3);
@@ -675,7 +694,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
         Model Me;
         Me.logp = M.logp; Me.lp = ctl[CT_LP]; Me.ldv = ctl[CT_LDV]; Me.lda = ctl[CT_LDA];
         Me.Q = ctl[CT_Q]; Me.c = ctl[CT_C]; Me.SS = 0; Me.pd = true; Me.bad = 0;
-        eval_share<NB>(P, ch, Me, key, flip_pos, nflips, base, evmode, 0, ctl, sx);
+        eval_share<NB, MLVS>(P, ch, Me, key, flip_pos, nflips, base, evmode, 0, ctl, sx);
       }
       if (W > 1) __syncthreads(); else wave_sync();
       if (evmode == EVM_FILL) {

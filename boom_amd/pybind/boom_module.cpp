@@ -591,4 +591,47 @@ PYBIND11_MODULE(_boom, boom) {
            py::keep_alive<1, 2>())
       .def("draw", &QuantileRegressionSpikeSlabSampler::draw)
       .def("limit_model_selection", &QuantileRegressionSpikeSlabSampler::limit_model_selection);
+  // ---- multinomial logit spike and slab (MultinomialLogitModel, MLVS: the names of the
+  // reference's Models/Glm) ----------------------------------------------------------------
+  boom.def("mlvs_flip_order", [](int n) { return mlvs_flip_order(n); }, py::arg("n"),
+           "the order MLVS::draw_inclusion_vector visits n coefficients in: the shuffle of 0 .. n - 1 "
+           "by a freshly constructed std::default_random_engine");
+  py::class_<MultinomialLogitModel, Ptr<MultinomialLogitModel>>(boom, "MultinomialLogitModel")
+      .def(py::init<int, int, int, int, uint64_t, int>(), py::arg("nchoices"), py::arg("subject_xdim"),
+           py::arg("choice_xdim"), py::arg("chains") = 1, py::arg("seed") = 8675309ull, py::arg("device") = 0)
+      .def_property_readonly("Nchoices", &MultinomialLogitModel::Nchoices)
+      .def_property_readonly("subject_nvars", &MultinomialLogitModel::subject_nvars)
+      .def_property_readonly("choice_nvars", &MultinomialLogitModel::choice_nvars)
+      .def_property_readonly("beta_size", &MultinomialLogitModel::beta_size)
+      .def("set_data", [](MultinomialLogitModel &m, const std::vector<int32_t> &y, py::object Xs, py::object Xc) {
+             const Matrix xs = Xs.is_none() ? Matrix() : matrix_from(Xs.cast<NpArray>());
+             const Matrix xc = Xc.is_none() ? Matrix() : matrix_from(Xc.cast<NpArray>());
+             m.set_data(y, xs, xc);
+           },
+           py::arg("response"), py::arg("subject_predictors"), py::arg("choice_predictors"))
+      .def("drop_all", &MultinomialLogitModel::drop_all)
+      .def("add", &MultinomialLogitModel::add)
+      .def("drop", &MultinomialLogitModel::drop)
+      .def_property_readonly("inc", [](const MultinomialLogitModel &m) {
+        std::vector<bool> g(m.beta_size());
+        for (int j = 0; j < m.beta_size(); ++j) g[j] = m.coef().inc()[j];
+        return g;
+      })
+      .def_property_readonly("beta", [](const MultinomialLogitModel &m) { return to_numpy(m.beta()); })
+      .def("set_beta", [](MultinomialLogitModel &m, const NpArray &b) { m.set_beta(vector_from(b)); })
+      .def("set_method", [](MultinomialLogitModel &m, const Ptr<PosteriorSampler> &s) { m.set_method(s); })
+      .def("sample_posterior", &MultinomialLogitModel::sample_posterior);
+  py::class_<MLVS, PosteriorSampler, Ptr<MLVS>>(boom, "MLVS")
+      .def(py::init([](MultinomialLogitModel *model, const Ptr<MvnModel> &slab,
+                       const Ptr<VariableSelectionPrior> &spike, py::object) {
+             return new MLVS(model, slab, spike);
+           }),
+           py::arg("model"), py::arg("slab"), py::arg("spike"), py::arg("seeding_rng") = py::none(),
+           py::keep_alive<1, 2>())
+      .def("draw", &MLVS::draw)
+      .def("suppress_model_selection", &MLVS::suppress_model_selection)
+      .def("allow_model_selection", &MLVS::allow_model_selection)
+      .def("limit_model_selection", &MLVS::limit_model_selection)
+      .def("max_nflips", &MLVS::max_nflips)
+      .def("logpri", &MLVS::logpri);
 }

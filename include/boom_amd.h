@@ -397,6 +397,56 @@ int ba_quantile_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, co
 int ba_quantile_sweep(ba_engine *e, int32_t nsweeps);
 int ba_quantile_get_weights(ba_engine *e, int64_t chain, double *w);
 
+/* ---- MLVS: multinomial logit spike and slab (mlm.spike's data-augmentation move) -------------
+ * Models/Glm/PosteriorSamplers/MLVS.cpp:71-75 (draw), :101-118 (draw_beta), :120-153
+ * (keep_flip, draw_inclusion_vector), :163-190 (log_model_prob); the imputation is
+ * MLVS_data_imputer.cpp:51-82.  n observations choose among M = nchoices alternatives; the
+ * model's D = (M - 1) psub + pch coefficients are laid out as ChoiceData::write_x(false) does
+ * (Models/Glm/ChoiceData.cpp:93-115): expanded row i M + m holds xsubject_i in columns
+ * [(m - 1) psub, m psub) for m >= 1 -- choice 0 is the baseline -- and xchoice_{i, m} in the
+ * last pch columns.  Per sweep and observation: eta_m = row (i, m) times beta, the
+ * Fruhwirth-Schnatter / Fruhwirth utilities u_m (u_y = -rlexp(lse(eta)); the others
+ * -lse2(logzmin, rlexp(eta_m))), for every m the component k of the ten-component normal
+ * mixture given u_m - eta_m, u_m -= mu_k and w_m = 1 / sigma_k^2; then X'WX, X'Wu and
+ * weighted_sum_of_squares = sum w u^2 (MultinomialLogitCompleteDataSuf.cpp:41-50), the
+ * inclusion sweep and beta ~ N(V_g^{-1}(X'Wu_g + Omega^{-1}_g mu_g), V_g^{-1}).  The sweep is
+ * not SpikeSlabSampler's: it visits the first min(D, max_flips) entries of one fixed order,
+ * keeps a flip iff u < logit_inv(logp_new - logp_old), the empty model's value is
+ * log prior + weighted_sum_of_squares / 2 (the reference's sign, MLVS.cpp:166-168), and a start
+ * whose value is not finite is an error (BA_E_ILLEGAL_START, "MLVS did not start with a legal
+ * configuration.") -- there is no make_valid.  Every flip consumes its uniform (the reference
+ * skips it when logp_new is not finite).
+ *   ba_mlogit_set_data        y n int32 in 0 .. M - 1; Xsubject n x psub column-major (NULL iff
+ *                             psub == 0); Xchoice (n M) x pch column-major, row i M + m (NULL
+ *                             iff pch == 0); 2 <= M <= 16.  The expanded design and its square
+ *                             are built on the device: 16 n M D bytes, refused above 8 GiB
+ *   ba_mlogit_set_flip_order  the sweep's visiting order, D int32, a permutation (default: the
+ *                             identity).  The reference's is std::shuffle(seq, std::default_random_engine())
+ *                             with a fresh engine on every draw, i.e. always the same one: a
+ *                             caller computes it with that very call (boom_amd.hpp does)
+ *   priors, state             ba_sss_set_slab(mu, precision, 0, max_flips), ba_set_spike,
+ *                             ba_set_state / ba_get_state(s) as for the Poisson sampler (sigma^2 is 1)
+ *   ba_mlogit_allow_model_selection  0: suppress_model_selection (beta only); 1: the default
+ *   ba_mlogit_sweep           nsweeps x draw() on every chain
+ *   ba_mlogit_get_latent      the last imputation's N = n M utilities (less their component's
+ *                             mean) and weights of one chain, row i M + m
+ *   ba_mlogit_get_wss         weighted_sum_of_squares of the last imputation of one chain
+ * Models of more than 64 included variables are not served (BA_E_MODEL_TOO_LARGE).  Not
+ * covered: log_sampling_probs (downsampling), restricted choice sets, the composite
+ * sampler's RWM / TIM moves (mlm.spike's proposal.weights beyond DA), the ba_group_* wrappers.
+ * RNG: stream 3 for the flips (max_flips uniforms a sweep, no shuffle uniforms) and the
+ * coefficient draw; stream 48 from position (s n + i) * 64 for observation i in sweep s: one
+ * uniform for rlexp(loglam), then for m = 0 .. M - 1 one for rlexp(eta_m) unless m = y_i and
+ * one for the component -- 2 M in all, plus one per redraw of an rlexp whose log(-log(U)) is
+ * not finite. */
+int ba_mlogit_set_data(ba_engine *e, int64_t n, int32_t nchoices, int32_t psub, int32_t pch,
+                       const int32_t *y, const double *Xsubject, const double *Xchoice);
+int ba_mlogit_set_flip_order(ba_engine *e, const int32_t *order);
+int ba_mlogit_allow_model_selection(ba_engine *e, int32_t allow);
+int ba_mlogit_sweep(ba_engine *e, int32_t nsweeps);
+int ba_mlogit_get_latent(ba_engine *e, int64_t chain, double *u, double *w);
+int ba_mlogit_get_wss(ba_engine *e, int64_t chain, double *wss);
+
 /* ---- posterior summaries --------------------------------------------------- */
 /* Running sums over every sweep since the last ba_reset_summaries(), reduced
  * over this engine's chains on the device:

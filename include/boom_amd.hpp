@@ -17,10 +17,12 @@
 // independent chains on one MI355X; draw() advances all of them; chain 0 backs
 // the model's classic single-chain accessors; Ptr<T> is std::shared_ptr<T>.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <limits>
 #include <memory>
+#include <random>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -1104,6 +1106,119 @@ class QuantileRegressionSpikeSlabSampler : public PosteriorSampler {
   Ptr<VariableSelectionPrior> spike_;
   int max_flips_ = -1;
   bool priors_set_ = false;
+};
+
+// ---- Multinomial logit spike and slab ----------------------------------------------------
+// MultinomialLogitModel + MLVS (Models/Glm/MultinomialLogitModel.hpp, PosteriorSamplers/MLVS.cpp:
+// 71-75, :101-190; mlm.spike's data-augmentation move, proposal.weights = c(DA = 1, 0, 0)): the
+// utilities, mixture components and the inclusion / coefficient draws on the device
+// (ba_mlogit_*).  The model is built from its dimensions; set_data hands over the responses, the
+// subject predictors and the choice predictors (row i Nchoices + m), all at once.  Chain 0
+// backs the model's accessors.  Not covered: log_sampling_probs, restricted choice sets, the
+// composite sampler's RWM / TIM moves.
+//
+// The order MLVS::draw_inclusion_vector visits the coefficients in (MLVS.cpp:140-141): the
+// shuffle of 0 .. n - 1 by a freshly constructed std::default_random_engine -- the same
+// permutation every draw, and the one the caller's own standard library gives their BOOM build.
+inline std::vector<int32_t> mlvs_flip_order(int n) {
+  std::vector<int32_t> v((size_t)n);
+  for (int i = 0; i < n; ++i) v[(size_t)i] = i;
+  std::shuffle(v.begin(), v.end(), std::default_random_engine());
+  return v;
+}
+class MultinomialLogitModel : public Model {
+ public:
+  // (coef() of the reference: the GlmCoefs' inclusion indicators)
+  struct Coefs {
+    const Selector &inc() const { return inc_; }
+    Selector inc_;
+  };
+  MultinomialLogitModel(int nchoices, int subject_xdim, int choice_xdim, int chains = 1, uint64_t seed = 8675309,
+                        int device = 0)
+      : eng_(new Engine(chains, seed, device)), M_(nchoices), psub_(subject_xdim), pch_(choice_xdim),
+        coef_{Selector((nchoices - 1) * subject_xdim + choice_xdim, true)},
+        beta_((size_t)((nchoices - 1) * subject_xdim + choice_xdim), 0.0) {
+    if (nchoices < 2) report_error("A MultinomialLogitModel needs at least two choices.");
+    if (subject_xdim < 0 || choice_xdim < 0 || beta_size() <= 0)
+      report_error("The dimensions of a MultinomialLogitModel must be non-negative and not both zero.");
+  }
+  int Nchoices() const { return M_; }
+  int subject_nvars() const { return psub_; }
+  int choice_nvars() const { return pch_; }
+  int beta_size() const { return (M_ - 1) * psub_ + pch_; }
+  void set_data(const std::vector<int32_t> &y, const Matrix &Xsubject, const Matrix &Xchoice) {
+    const int n = (int)y.size();
+    if ((psub_ > 0 && (Xsubject.nrow() != n || Xsubject.ncol() != psub_)) ||
+        (pch_ > 0 && (Xchoice.nrow() != n * M_ || Xchoice.ncol() != pch_)))
+      report_error("The data are incompatible with the MultinomialLogitModel.");
+    eng_->check(ba_mlogit_set_data(eng_->get(), n, M_, psub_, pch_, y.data(), psub_ > 0 ? Xsubject.data() : nullptr,
+                                   pch_ > 0 ? Xchoice.data() : nullptr));
+    dirty_ = true;
+    data_set_ = true;
+  }
+  bool data_set() const { return data_set_; }
+  const Coefs &coef() const { return coef_; }
+  const Selector &inc() const { return coef_.inc_; }
+  void drop_all() { coef_.inc_.drop_all(); dirty_ = true; }
+  void add(int i) { coef_.inc_.add(i); dirty_ = true; }
+  void drop(int i) { coef_.inc_.drop(i); dirty_ = true; }
+  const Vector &beta() const { return beta_; }
+  void set_beta(const Vector &b) { beta_ = b; dirty_ = true; }
+  bool dirty() const { return dirty_; }
+  const Ptr<Engine> &engine() const { return eng_; }
+  void push_state() {
+    eng_->check(ba_set_state(eng_->get(), -1, coef_.inc_.bytes().data(), beta_.data(), 1.0));
+    dirty_ = false;
+  }
+  void pull_chain0() {
+    eng_->check(ba_get_state(eng_->get(), 0, coef_.inc_.bytes().data(), beta_.data(), nullptr));
+    dirty_ = false;
+  }
+ private:
+  Ptr<Engine> eng_;
+  int M_, psub_, pch_;
+  Coefs coef_;
+  Vector beta_;
+  bool dirty_ = true, data_set_ = false;
+};
+// MLVS(model, slab, spike); the slab, the spike and the visiting order are handed to the
+// engine with the first draw after the data
+class MLVS : public PosteriorSampler {
+ public:
+  MLVS(MultinomialLogitModel *model, const Ptr<MvnModel> &slab, const Ptr<VariableSelectionPrior> &spike)
+      : model_(model), slab_(slab), spike_(spike), max_nflips_(model->beta_size()) {
+    if (slab->dim() != model->beta_size()) report_error("Slab does not match model dimension.");
+    if ((int)spike->potential_nvars() != model->beta_size()) report_error("Spike does not match model dimension.");
+  }
+  void draw() override {
+    if (!priors_set_) {
+      // (ba_sss_set_slab limits only if max_flips > 0; limit_model_selection(0) is suppress)
+      check(ba_sss_set_slab(h(), slab_->mu().data(), slab_->siginv().data(), 0, max_nflips_ > 0 ? max_nflips_ : -1));
+      check(ba_set_spike(h(), spike_->prior_inclusion_probabilities().data(), spike_->max_model_size()));
+      const std::vector<int32_t> order = mlvs_flip_order(model_->beta_size());
+      check(ba_mlogit_set_flip_order(h(), order.data()));
+      check(ba_mlogit_allow_model_selection(h(), (select_ && max_nflips_ > 0) ? 1 : 0));
+      priors_set_ = true;
+    }
+    if (model_->dirty()) model_->push_state();
+    check(ba_mlogit_sweep(h(), 1));
+    check(ba_sync(h()));
+    model_->pull_chain0();
+  }
+  double logpri() const override { report_error("logpri() is not implemented for the multinomial logit sampler"); return 0; }
+  void set_seed(unsigned long s) override { check(ba_seed(h(), s)); }
+  void suppress_model_selection() { select_ = false; priors_set_ = false; }
+  void allow_model_selection() { select_ = true; priors_set_ = false; }
+  void limit_model_selection(unsigned n) { max_nflips_ = (int)n; priors_set_ = false; }
+  unsigned max_nflips() const { return (unsigned)max_nflips_; }
+ private:
+  ba_engine *h() const { return model_->engine()->get(); }
+  void check(int rc) const { model_->engine()->check(rc); }
+  MultinomialLogitModel *model_;
+  Ptr<MvnModel> slab_;
+  Ptr<VariableSelectionPrior> spike_;
+  int max_nflips_;
+  bool select_ = true, priors_set_ = false;
 };
 
 }  // namespace boom_amd_api
