@@ -127,6 +127,11 @@ SIGNATURES = {
     "ba_poisson_set_mixtures": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64),
                                           C.POINTER(C.c_int32), _dp, _dp, _dp, C.c_int64]),
     "ba_poisson_sweep": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ba_ss_student_set_data": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _u8p]),
+    "ba_ss_student_sweep": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ba_ss_student_get_weights": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
+    "ba_ss_student_set_weights": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
+    "ba_ss_student_impute_state": (C.c_int, [C.c_void_p]),
     "ba_student_set_data": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp]),
     "ba_student_set_nu_prior": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double]),
     "ba_student_set_nu": (C.c_int, [C.c_void_p, C.c_int64, C.c_double]),
@@ -571,6 +576,31 @@ class Engine:
         out = np.zeros(int(nsweeps))
         self._check(self.lib.ba_student_get_nu_draws(self._h, int(chain), int(nsweeps), _p(out)))
         return out
+
+    # ---- StateSpaceStudentPosteriorSampler (bsts family = "student") ---------------
+    def ss_student_set_data(self, y, X, observed=None):
+        T, p = X.shape
+        obs = None if observed is None else np.ascontiguousarray(observed, np.uint8)
+        self._check(self.lib.ba_ss_student_set_data(self._h, T, p, _p(_f64(y)), _p(_fcol(X)), _b(obs)))
+        self.p = p
+        self.T = T
+
+    def ss_student_sweep(self, nsweeps=1, sync=True):
+        self._check(self.lib.ba_ss_student_sweep(self._h, nsweeps))
+        if sync:
+            self.sync()
+
+    def ss_student_get_weights(self, chain):
+        out = np.zeros(getattr(self, "T", 1))   # (without the family's data the call is refused before it writes)
+        self._check(self.lib.ba_ss_student_get_weights(self._h, int(chain), _p(out)))
+        return out
+
+    def ss_student_set_weights(self, w, chain=-1):
+        self._check(self.lib.ba_ss_student_set_weights(self._h, int(chain), _p(_f64(w))))
+
+    def ss_student_impute_state(self):
+        self._check(self.lib.ba_ss_student_impute_state(self._h))
+        self.sync()
 
     # ---- QuantileRegressionSpikeSlabSampler --------------------------------------
     def quantile_set_data(self, X, y, quantile):

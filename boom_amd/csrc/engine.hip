@@ -50,6 +50,8 @@ const char *status_message(int st) {
              "non-finite, or the mixture component scan of rmulti fell off its end.";
     case MLVS_ILLEGAL_START:
       return "MLVS did not start with a legal configuration.";
+    case STUDENT_BAD_WEIGHT:
+      return "Weights must be finite and non-negative.";
     default:
       return "unknown chain status";
   }
@@ -67,6 +69,7 @@ int status_code(int st) {
     case QUANTILE_WEIGHT_ERROR: return BA_E_RNG_BRANCH;
     case MLOGIT_IMPUTE_ERROR: return BA_E_RNG_BRANCH;
     case MLVS_ILLEGAL_START: return BA_E_ILLEGAL_START;
+    case STUDENT_BAD_WEIGHT: return BA_E_INVALID;
     default: return BA_E_INVALID;
   }
 }
@@ -374,7 +377,7 @@ void fill_params(ba_engine *e, SsvsParams &P) {
     P.cm_start = nullptr;
     P.max_flips = (e->sss_max_flips > 0) ? std::min(e->sss_max_flips, e->p) : e->p;
   }
-  if (e->cur_mode == 1 && e->data_kind == DATA_STUDENT && !e->student_allow_selection)
+  if (e->cur_mode == 1 && student_kind(e->data_kind) && !e->student_allow_selection)
     P.max_flips = 0;   // SpikeSlabSampler::allow_model_selection(false): no indicator draws
   if (e->cur_mode == 1 && column_service(e->data_kind) && e->dlogit_V.count) {
     // BinomialLogitSpikeSlabSampler: the sampler's own shuffle, every chain's own V
@@ -1019,7 +1022,7 @@ const char *ba_kernel_class_name(int32_t cls) {
       "xtwx_cols_kernel<false>+plain_reduce_kernel", "xtwx_cols_kernel<true>+xtwx_cols_reduce_kernel",
       "xtx_mfma_kernel+plane_sum_kernel+col_reduce_kernel", "poisson_impute_kernel",
       "kalman_prepare_kernel", "ss_round_kernel", "student_impute_kernel", "student_sigma_nu_kernel",
-      "quantile_impute_kernel", "mlogit_impute_kernel"};
+      "quantile_impute_kernel", "mlogit_impute_kernel", "student_ss_kernels"};
   return (cls >= 0 && cls < KT_CLASSES) ? names[cls] : "";
 }
 
@@ -1364,7 +1367,7 @@ int ba_set_state(ba_engine *e, int64_t chain, const uint8_t *gamma,
   if (!gamma) return fail(BA_E_INVALID, "null argument");
   const int64_t C = e->cfg.chains;
   if (chain < -1 || chain >= C) return fail(BA_E_INVALID, "chain index out of range");
-  if (latent_data(e->data_kind) && e->data_kind != DATA_STUDENT && sigsq != 1.0)
+  if (latent_data(e->data_kind) && !student_kind(e->data_kind) && sigsq != 1.0)
     return fail(BA_E_INVALID, "the binomial samplers' latent data have unit variance: sigsq must be 1");
   if (chain < 0) la_discard(e);  // every chain is overwritten: nothing to rewind to
   MUTATE(e);
@@ -1597,7 +1600,8 @@ static const char *const kSetDataFirst[] = {nullptr,
                                             "call ba_poisson_set_data first",
                                             "call ba_student_set_data first",
                                             "call ba_quantile_set_data first",
-                                            "call ba_mlogit_set_data first"};
+                                            "call ba_mlogit_set_data first",
+                                            "call ba_ss_student_set_data first"};
 // ... and where the data in hand send a caller of another family's entry point
 static const char *const kUseSweep[] = {nullptr,
                                         "state-space data are set: use ba_ss_sweep",
@@ -1606,7 +1610,8 @@ static const char *const kUseSweep[] = {nullptr,
                                         "Poisson data are set: use ba_poisson_sweep",
                                         "Student-t regression data are set: use ba_student_sweep",
                                         "quantile regression data are set: use ba_quantile_sweep",
-                                        "multinomial logit data are set: use ba_mlogit_sweep"};
+                                        "multinomial logit data are set: use ba_mlogit_sweep",
+                                        "Student-t state-space data are set: use ba_ss_student_sweep"};
 
 const char *set_data_first(DataKind wants) { return kSetDataFirst[wants]; }
 
@@ -1617,8 +1622,9 @@ int sweep_refusal(const ba_engine *e, DataKind wants, bool sss) {
   // (the quantile sampler's column and row: every other sweep names ba_quantile_sweep, and
   // ba_quantile_sweep asks for its own data whatever else is set)
   // (so with the multinomial logit sampler's)
-  if (have == DATA_QUANTILE || have == DATA_MLOGIT) return fail(BA_E_STATE, kUseSweep[have]);
-  if (wants == DATA_STATE_SPACE || wants == DATA_QUANTILE || wants == DATA_MLOGIT)
+  // (and the state space Student family's)
+  if (have == DATA_QUANTILE || have == DATA_MLOGIT || have == DATA_SS_STUDENT) return fail(BA_E_STATE, kUseSweep[have]);
+  if (wants == DATA_STATE_SPACE || wants == DATA_QUANTILE || wants == DATA_MLOGIT || wants == DATA_SS_STUDENT)
     return fail(BA_E_STATE, kSetDataFirst[wants]);
   if (have == DATA_STUDENT) return fail(BA_E_STATE, kUseSweep[have]);
   if (wants == DATA_REGRESSION) {   // ba_sweep, ba_draw_next, ba_adaptive_sweep; ba_sss_sweep
@@ -1907,7 +1913,7 @@ int ba_log_model_prob(ba_engine *e, int32_t ngamma, const uint8_t *gammas,
   if (!gammas || !out || ngamma <= 0) return fail(BA_E_INVALID, "bad argument");
   // the regression model's own sufficient statistics: in state-space mode they
   // are per chain and move every sweep, so there is no one answer
-  if (e->data_kind == DATA_STATE_SPACE)
+  if (e->data_kind == DATA_STATE_SPACE || e->data_kind == DATA_SS_STUDENT)
     return fail(BA_E_STATE, "ba_log_model_prob is not defined once state-space data are set (per-chain sufficient statistics)");
   // BregVsSampler's V = Omega^{-1} + XtX (a SpikeSlabSampler launch with a fixed
   // slab precision leaves XtX / sigma^2 in it)
@@ -2206,7 +2212,7 @@ int ba_set_sigsq(ba_engine *e, int64_t chain, double sigsq) {
   ENGINE_PROLOGUE(e);
   MUTATE(e);
   if (!(sigsq > 0)) return fail(BA_E_INVALID, "sigsq must be positive");
-  if (latent_data(e->data_kind) && e->data_kind != DATA_STUDENT && sigsq != 1.0)
+  if (latent_data(e->data_kind) && !student_kind(e->data_kind) && sigsq != 1.0)
     return fail(BA_E_INVALID, "the binomial samplers' latent data have unit variance: sigsq must be 1");
   int rc = alloc_chain_state(e);
   if (rc) return rc;

@@ -10,7 +10,7 @@
 namespace boom_amd {
 
 // the vectors of V named by dlogit_req[0, R), in batches the planes can hold
-static int build_columns(ba_engine *e, int64_t R) {
+int build_columns(ba_engine *e, int64_t R) {
   const int64_t n = e->probit_n;
   for (int64_t r0 = 0; r0 < R; r0 += e->logit_req_batch) {
     const int64_t nr = std::min<int64_t>(e->logit_req_batch, R - r0);
@@ -61,7 +61,7 @@ int serve_columns(ba_engine *e, std::vector<int32_t> &st, bool *served) {
 // A family's data on the device: X, the responses, the family's third vector (trial counts /
 // exposures; none for Student-t), X squared for the families of the column service (the
 // diagonal of X'WX).  The imputation starts over: no latent data, sweep 0.
-static int upload_latent_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y,
+int upload_latent_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y,
                               const double *third, bool squared, int clt_threshold) {
   HIP_TRY(e->dprob_X.resize((size_t)n * p));
   HIP_TRY(e->dprob_y.resize((size_t)n));
@@ -112,7 +112,7 @@ static void fill_probit_params(ba_engine *e, ProbitParams &Q) {
   Q.mix_one = e->poisson_mix_one;
 }
 
-static void fill_student_params(ba_engine *e, StudentParams &T) {
+void fill_student_params(ba_engine *e, StudentParams &T) {
   std::memset(&T, 0, sizeof(T));
   T.n = (int32_t)e->probit_n;
   T.p = (int32_t)e->p;
@@ -203,7 +203,7 @@ static void fill_mlogit_params(ba_engine *e, MlogitParams &G) {
 
 // the Student sampler's per-chain state: nu = 30 (TRegression.cpp:35-45), suggested_dx = 1
 // (TRegressionSampler.cpp:88-107), no slice comparison seen yet
-static int student_prepare(ba_engine *e) {
+int student_prepare(ba_engine *e) {
   int rc = alloc_chain_state(e);
   if (rc) return rc;
   const size_t C = (size_t)e->cfg.chains;
@@ -216,6 +216,30 @@ static int student_prepare(ba_engine *e) {
   HIP_TRY(hipMemcpy(e->dstu_nu.ptr, nu.data(), C * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->dstu_dx.ptr, dx.data(), C * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->dstu_margin.ptr, m.data(), C * 8, hipMemcpyHostToDevice));
+  return BA_OK;
+}
+
+// the buffers of the families whose V is every chain's own (chains x n latent responses and
+// weights, V, its diagonal, the column service's lists and planes)
+int column_buffers(ba_engine *e) {
+  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, n = (size_t)e->probit_n;
+  if (e->dprob_z.count != C * n || e->dlogit_V.count != C * p * p) {
+    HIP_TRY(e->dprob_z.resize(C * n));
+    HIP_TRY(e->dlogit_w.resize(C * n));
+    HIP_TRY(e->dlogit_V.resize(C * p * p));
+    HIP_TRY(e->dxty_c.resize(C * p));
+    e->logit_words = (int)((p + 31) / 32);
+    HIP_TRY(e->dlogit_vdiag.resize(C * p));
+    HIP_TRY(e->dlogit_valid.resize(C * (size_t)e->logit_words));
+    HIP_TRY(e->dlogit_req.resize(2 * C * p));
+    HIP_TRY(e->dlogit_cnt.resize(1));
+    HIP_TRY(e->dcol_request.resize(C));
+    // the planes of one GEMM launch: at most 1 GiB, at least one request tile
+    const size_t per_req = (size_t)xtwx_cols_planes((int64_t)n) * p * 8;
+    e->logit_req_batch = (int64_t)std::min<size_t>(std::max<size_t>(((size_t)1 << 30) / per_req, 64), 32768);
+    e->logit_req_batch = std::min<int64_t>(e->logit_req_batch, (int64_t)(C * p));
+    HIP_TRY(e->dlogit_planes.resize((size_t)e->logit_req_batch * per_req / 8));
+  }
   return BA_OK;
 }
 
@@ -258,23 +282,8 @@ static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
       HIP_TRY(hipMemcpy(e->dml_order.ptr, id.data(), p * 2, hipMemcpyHostToDevice));
     }
   }
-  if (e->dprob_z.count != C * n || e->dlogit_V.count != C * p * p) {
-    HIP_TRY(e->dprob_z.resize(C * n));
-    HIP_TRY(e->dlogit_w.resize(C * n));
-    HIP_TRY(e->dlogit_V.resize(C * p * p));
-    HIP_TRY(e->dxty_c.resize(C * p));
-    e->logit_words = (int)((p + 31) / 32);
-    HIP_TRY(e->dlogit_vdiag.resize(C * p));
-    HIP_TRY(e->dlogit_valid.resize(C * (size_t)e->logit_words));
-    HIP_TRY(e->dlogit_req.resize(2 * C * p));
-    HIP_TRY(e->dlogit_cnt.resize(1));
-    HIP_TRY(e->dcol_request.resize(C));
-    // the planes of one GEMM launch: at most 1 GiB, at least one request tile
-    const size_t per_req = (size_t)xtwx_cols_planes((int64_t)n) * p * 8;
-    e->logit_req_batch = (int64_t)std::min<size_t>(std::max<size_t>(((size_t)1 << 30) / per_req, 64), 32768);
-    e->logit_req_batch = std::min<int64_t>(e->logit_req_batch, (int64_t)(C * p));
-    HIP_TRY(e->dlogit_planes.resize((size_t)e->logit_req_batch * per_req / 8));
-  }
+  rc = column_buffers(e);
+  if (rc) return rc;
   if (!student) {
     rc = set_unit_sigsq(e);
     if (rc) return rc;

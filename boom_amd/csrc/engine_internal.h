@@ -55,6 +55,9 @@ hipError_t launch_probit_impute(hipStream_t stream, const ProbitParams &P, doubl
 hipError_t launch_student_impute(hipStream_t stream, const StudentParams &P, const double *Xsq,
                                  const double *slab_precision, double *xtz, double *v_diag, double *planes);
 hipError_t launch_student_sigma_nu(hipStream_t stream, const StudentParams &P);
+hipError_t launch_student_ss_weights(hipStream_t stream, const StudentParams &P, int draw);
+hipError_t launch_student_ss_suf(hipStream_t stream, const StudentParams &P, const double *Xsq,
+                                 const double *slab_precision, double *xtz, double *v_diag, double *planes);
 // quantile_kernel.hip
 hipError_t launch_quantile_impute(hipStream_t stream, const QuantileParams &P, const double *Xsq,
                                   const double *slab_precision, double *xtz, double *v_diag, double *planes);
@@ -130,12 +133,17 @@ struct DevBuf {
 // anything was uploaded).  Every sweep entry point serves one kind and refuses the others
 // (sweep_refusal, engine.hip).
 enum DataKind { DATA_REGRESSION, DATA_STATE_SPACE, DATA_PROBIT, DATA_LOGIT, DATA_POISSON, DATA_STUDENT, DATA_QUANTILE,
-                DATA_MLOGIT };
+                DATA_MLOGIT,
+                // bsts family = "student": the state space data with the Student-t observation model
+                // (StateSpaceStudentRegressionModel); the Student path's buffers with n = T
+                DATA_SS_STUDENT };
 // the latent-data families: the regression runs on every chain's own imputed responses
-inline bool latent_data(DataKind k) { return k == DATA_PROBIT || k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT; }
+inline bool latent_data(DataKind k) { return k == DATA_PROBIT || k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT || k == DATA_SS_STUDENT; }
 // ... and those of them whose V = slab precision + X'WX is every chain's own, built a vector
 // at a time (serve_columns, engine_glm.hip)
-inline bool column_service(DataKind k) { return k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT; }
+inline bool column_service(DataKind k) { return k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT || k == DATA_SS_STUDENT; }
+// the two families whose sigma^2 is every chain's own draw on latent data
+inline bool student_kind(DataKind k) { return k == DATA_STUDENT || k == DATA_SS_STUDENT; }
 
 }  // namespace boom_amd
 
@@ -342,6 +350,12 @@ struct ba_engine {
   int student_nu_kind = STUDENT_NU_UNIFORM;
   double student_nu_a = 0.1, student_nu_b = 100.0;
   DevBuf<double> dstu_nu, dstu_dx, dstu_margin, dstu_u, dstu_nu_rec;
+  // StateSpaceStudentPosteriorSampler (DATA_SS_STUDENT): the filter's H_t = sigma^2 / w_t
+  // (chains x T); rounds done (positions the sigma^2 / nu substream; probit_sweep counts the
+  // weight imputations); the weights and statistics in hand are those of a state draw
+  DevBuf<double> dsst_h;
+  uint64_t sst_round = 0;
+  bool sst_ready = false;
   // QuantileRegressionSpikeSlabSampler (quantile_kernel.hip): the Poisson path with its own
   // imputation; the model's quantile
   double quantile_q = 0.5;
@@ -457,6 +471,12 @@ int write_per_chain(ba_engine *e, double *dev, int64_t chain, double value);
 int read_per_chain(ba_engine *e, const double *dev, int64_t chain, double *out);
 // engine_glm.hip
 int serve_columns(ba_engine *e, std::vector<int32_t> &st, bool *served);
+int student_prepare(ba_engine *e);
+void fill_student_params(ba_engine *e, StudentParams &T);
+int build_columns(ba_engine *e, int64_t R);
+int column_buffers(ba_engine *e);
+int upload_latent_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y,
+                       const double *third, bool squared, int clt_threshold);
 // engine_ss.hip
 int ss_escalate(ba_engine *e, std::vector<int32_t> &st);
 int ss_la_settle(ba_engine *e);

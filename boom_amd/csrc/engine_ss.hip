@@ -42,6 +42,9 @@ static void ssg_template_shape(const SsgSpec &q, int32_t *trend, int32_t *nseaso
 
 // the local-level path of a series of at most LM_TP steps runs lane-major
 // (kalman_lm_kernel): its scratch arrays have pitch LM_TP
+// the two kinds that hold a series and a state (the Gaussian and the Student-t observation model)
+static bool ss_kind(DataKind k) { return k == DATA_STATE_SPACE || k == DATA_SS_STUDENT; }
+
 static bool ss_lane_major(const ba_engine &e) { return !e.ssm_set && e.T <= LM_TP; }
 static size_t ss_pitch(const ba_engine &e) { return ss_lane_major(e) ? (size_t)LM_TP : (size_t)e.T; }
 
@@ -499,8 +502,8 @@ static void ss_la_want_state(ba_engine *e, int64_t c) {
 extern "C" {
 
 // --------------------------------------------------- state space (kalman)
-static int ss_prepare(ba_engine *e) {
-  int rc = sweep_refusal(e, DATA_STATE_SPACE);
+static int ss_prepare(ba_engine *e, DataKind kind = DATA_STATE_SPACE) {
+  int rc = sweep_refusal(e, kind);
   if (rc) return rc;
   if (!e->ss_level_set && !e->ssm_set)
     return fail(BA_E_STATE, "call ba_ss_set_local_level or ba_ss_set_structural first");
@@ -971,7 +974,7 @@ int ba_ss_get_state_model(ba_engine *e, int64_t chain, int32_t block, double *va
                           double *suf_ss, double *phi, double *ar_xtx, double *ar_xty, double *ar_yty,
                           double *ar_n) {
   ENGINE_ACCESSOR_SERVED(e);
-  if (e->data_kind != DATA_STATE_SPACE || !e->ssm_set || e->dssm_work.count == 0)
+  if (!ss_kind(e->data_kind) || !e->ssm_set || e->dssm_work.count == 0)
     return fail(BA_E_STATE, "no structural state-space run yet");
   if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
   if (block < 0 || block >= e->ssg.nblocks) return fail(BA_E_INVALID, "state model index out of range");
@@ -1040,7 +1043,7 @@ int ba_ss_get_state_model(ba_engine *e, int64_t chain, int32_t block, double *va
 int ba_ss_get_ar(ba_engine *e, int64_t chain, double *phi, double *sigsq, double *suf_xtx,
                  double *suf_xty, double *suf_yty, double *suf_n) {
   if (!e) return fail(BA_E_INVALID, "null engine");
-  if (e->data_kind != DATA_STATE_SPACE || !e->ssm_set || e->ssg_template_ar < 0 || e->dar_phi.count == 0)
+  if (!ss_kind(e->data_kind) || !e->ssm_set || e->ssg_template_ar < 0 || e->dar_phi.count == 0)
     return fail(BA_E_STATE, "no structural run with an autoregression block yet");
   return ba_ss_get_state_model(e, chain, e->ssg_template_ar, sigsq, nullptr, nullptr, phi, suf_xtx, suf_xty,
                                suf_yty, suf_n);
@@ -1049,7 +1052,7 @@ int ba_ss_get_ar(ba_engine *e, int64_t chain, double *phi, double *sigsq, double
 // one chain's state draw, T x m (step t at [t * m, (t + 1) * m))
 int ba_ss_get_state_draw(ba_engine *e, int64_t chain, double *state) {
   ENGINE_ACCESSOR_SERVED(e);
-  if (e->data_kind != DATA_STATE_SPACE || !e->ssm_set || e->dssm_work.count == 0)
+  if (!ss_kind(e->data_kind) || !e->ssm_set || e->dssm_work.count == 0)
     return fail(BA_E_STATE, "no structural state-space run yet");
   if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
   if (!state) return fail(BA_E_INVALID, "null argument");
@@ -1080,7 +1083,7 @@ int ba_ss_get_state_draw(ba_engine *e, int64_t chain, double *state) {
 int ba_ss_get_structural(ba_engine *e, int64_t chain, double *state, double *variances,
                          double *suf_n, double *suf_ss) {
   ENGINE_ACCESSOR_SERVED(e);
-  if (e->data_kind != DATA_STATE_SPACE || !e->ssm_set || e->dssm_work.count == 0)
+  if (!ss_kind(e->data_kind) || !e->ssm_set || e->dssm_work.count == 0)
     return fail(BA_E_STATE, "no structural state-space run yet");
   if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
   if ((variances || suf_n || suf_ss) && e->ssg_template_var[0] < 0)
@@ -1417,6 +1420,8 @@ int ba_ss_draw_next(ba_engine *e) {
 
 int ba_ss_forecast(ba_engine *e, int32_t horizon, const double *newX, double *out) {
   ENGINE_PROLOGUE(e);
+  if (e->data_kind == DATA_SS_STUDENT)
+    return fail(BA_E_STATE, "forecasts with Student-t observation noise are not implemented");
   if (!newX || !out || horizon <= 0) return fail(BA_E_INVALID, "bad argument");
   if (e->data_kind != DATA_STATE_SPACE || e->dss_scratch.count == 0 || !e->ss_initialized)
     return fail(BA_E_STATE, "no state draw yet: run ba_ss_sweep or ba_ss_impute_state first");
@@ -1513,6 +1518,230 @@ int ba_ss_get_chain_suf(ba_engine *e, int64_t chain, double *xty, double *yty,
   if (yty) HIP_TRY(hipMemcpy(yty, e->dyty_c.ptr + chain, 8, hipMemcpyDeviceToHost));
   if (n) HIP_TRY(hipMemcpy(n, e->dnobs_c.ptr + chain, 8, hipMemcpyDeviceToHost));
   return BA_OK;
+}
+
+}  // extern "C"
+
+// ---- bsts family = "student": StateSpaceStudentRegressionModel + StateSpaceStudentPosteriorSampler
+// (Models/StateSpace/StateSpaceStudentRegressionModel.cpp, PosteriorSamplers/
+// StateSpaceStudentPosteriorSampler.cpp:56-126, StateSpacePosteriorSampler.cpp:41-63).  The
+// observation model is the Student path's (student_kernel.hip: weights, sigma^2, nu; the
+// SpikeSlabSampler sweep on every chain's own V = slab precision + X'WX through the column
+// service), the state draw the general structural kernel with H_t = sigma^2 / w_t.
+namespace boom_amd {
+
+// the buffers of the kind beyond ss_prepare's and the Student path's: H_t; new weights are 1
+// (the first impute_state of StateSpacePosteriorSampler::draw runs before any weight is drawn)
+static int sst_buffers(ba_engine *e) {
+  int rc = student_prepare(e);
+  if (rc) return rc;
+  const size_t C = (size_t)e->cfg.chains, T = (size_t)e->T;
+  const bool fresh = e->dlogit_w.count != C * T || e->dsst_h.count != C * T;
+  rc = column_buffers(e);
+  if (rc) return rc;
+  if (e->dstu_u.count != C * T) HIP_TRY(e->dstu_u.resize(C * T));
+  if (fresh) {
+    HIP_TRY(e->dsst_h.resize(C * T));
+    std::vector<double> one(C * T, 1.0);
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(e->dlogit_w.ptr, one.data(), C * T * 8, hipMemcpyHostToDevice));
+    e->sst_ready = false;
+  }
+  return BA_OK;
+}
+
+static int sst_prepare(ba_engine *e) {
+  int rc = sweep_refusal(e, DATA_SS_STUDENT);
+  if (rc) return rc;
+  if (!e->ssm_set)
+    return fail(BA_E_STATE, e->ss_level_set
+                                ? "the Student-t state-space family takes a list of state models: call ba_ss_add_state_model "
+                                  "(a local level is the one-block list), not ba_ss_set_local_level"
+                                : "call ba_ss_add_state_model first");
+  if (!e->have_slab) return fail(BA_E_STATE, "call ba_sss_set_slab first");
+  if (!e->sss_slab_scales)
+    return fail(BA_E_INVALID, "the Student-t state-space sampler takes a slab whose precision scales with sigma^2 (scales_with_sigsq = 1)");
+  rc = switch_mode(e, 1, 1.0);
+  if (rc) return rc;
+  rc = ss_prepare(e, DATA_SS_STUDENT);
+  if (rc) return rc;
+  if (!e->ss_initialized) e->sst_ready = false;
+  return sst_buffers(e);
+}
+
+static void fill_sst_params(ba_engine *e, SsParams &S, StudentParams &U) {
+  fill_ss_params(e, S);
+  S.ssm.tpl_trend = S.ssm.tpl_nseasons = S.ssm.tpl_ar_lags = 0;   // always the general kernel
+  S.h = e->dsst_h.ptr;
+  S.h_stride = e->T;
+  fill_student_params(e, U);
+  U.offset = S.scratch + S.T;   // (array 1 of a chain's scratch block: the kernel's last pass leaves Z_t'alpha_t there)
+  U.offset_stride = S.scratch_stride;
+  U.observed = e->dss_obs.ptr;
+  U.h = e->dsst_h.ptr;
+}
+
+// Base::impute_state with the weights in hand: H_t, the state draw (the state models' parameters
+// as they stand when draw == 0), then the offsets' consequences -- z, X'Wz, the diagonal of V
+static int sst_impute_state(ba_engine *e, const SsParams &S, const StudentParams &U, int draw) {
+  HIP_TRY(launch_student_ss_weights(e->stream, U, 0));
+  HIP_TRY(launch_ssm_simsmooth(e->stream, S, draw));
+  HIP_TRY(launch_student_ss_suf(e->stream, U, e->dlogit_Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->dlogit_vdiag.ptr,
+                                e->dlogit_planes.ptr));
+  e->ss_initialized = true;
+  e->sst_ready = true;
+  return BA_OK;
+}
+
+}  // namespace boom_amd
+
+extern "C" {
+
+int ba_ss_student_set_data(ba_engine *e, int32_t T, int32_t p, const double *y, const double *X,
+                           const uint8_t *observed) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!y || !X) return fail(BA_E_INVALID, "null argument");
+  if (T <= 0 || p <= 0) return fail(BA_E_INVALID, "T and p must be positive");
+  for (int32_t t = 0; t < T; ++t)
+    if ((!observed || observed[t]) && !std::isfinite(y[t])) return fail(BA_E_INVALID, "observed responses must be finite");
+  int rc = ba_ss_set_data(e, T, p, y, X, observed);
+  if (rc) return rc;
+  // the Student path's view of the same data (n = T): X, y, X squared
+  std::vector<double> yo((size_t)T);
+  for (int32_t t = 0; t < T; ++t) yo[(size_t)t] = (!observed || observed[t]) ? y[t] : 0.0;
+  rc = upload_latent_data(e, T, p, X, yo.data(), nullptr, /*squared=*/true, 0);
+  if (rc) return rc;
+  // a new TRegressionModel and a sampler whose latent data are not initialised
+  e->dstu_u.release();
+  e->dstu_nu.release();
+  e->dstu_dx.release();
+  e->dstu_margin.release();
+  e->dlogit_w.release();
+  e->dsst_h.release();
+  e->sst_round = 0;
+  e->sst_ready = false;
+  e->data_kind = DATA_SS_STUDENT;
+  return BA_OK;
+}
+
+int ba_ss_student_get_weights(ba_engine *e, int64_t chain, double *w) {
+  ENGINE_PROLOGUE(e);
+  if (!w) return fail(BA_E_INVALID, "null argument");
+  if (e->data_kind != DATA_SS_STUDENT) return fail(BA_E_STATE, set_data_first(DATA_SS_STUDENT));
+  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  int rc = sst_buffers(e);
+  if (rc) return rc;
+  const size_t T = (size_t)e->T;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(w, e->dlogit_w.ptr + (size_t)chain * T, T * 8, hipMemcpyDeviceToHost));
+  return BA_OK;
+}
+
+int ba_ss_student_set_weights(ba_engine *e, int64_t chain, const double *w) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!w) return fail(BA_E_INVALID, "null argument");
+  if (e->data_kind != DATA_SS_STUDENT) return fail(BA_E_STATE, set_data_first(DATA_SS_STUDENT));
+  if (chain < -1 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  const size_t T = (size_t)e->T, C = (size_t)e->cfg.chains;
+  for (size_t t = 0; t < T; ++t)
+    if (!(w[t] >= 0.0) || !std::isfinite(w[t])) return fail(BA_E_INVALID, "Weights must be finite and non-negative.");
+  int rc = sst_buffers(e);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (size_t c = chain < 0 ? 0 : (size_t)chain; c < (chain < 0 ? C : (size_t)chain + 1); ++c)
+    HIP_TRY(hipMemcpy(e->dlogit_w.ptr + c * T, w, T * 8, hipMemcpyHostToDevice));
+  e->sst_ready = false;   // (the statistics in hand are not these weights': the next call draws the state first)
+  return BA_OK;
+}
+
+int ba_ss_student_impute_state(ba_engine *e) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  int rc = sst_prepare(e);
+  if (rc) return rc;
+  SsParams S;
+  StudentParams U;
+  fill_sst_params(e, S, U);
+  rc = sst_impute_state(e, S, U, 0);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return check_chain_status(e);
+}
+
+// nsweeps x StateSpacePosteriorSampler::draw (StateSpacePosteriorSampler.cpp:41-63) with the
+// Student observation model, every chain
+int ba_ss_student_sweep(ba_engine *e, int32_t nsweeps) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
+  int rc = sst_prepare(e);
+  if (rc) return rc;
+  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p;
+  if (e->trace_stride > 0 && nsweeps > e->trace_stride)
+    return fail(BA_E_INVALID, "nsweeps exceeds the enabled trace length");
+  if (e->trace_stride > 0 && e->dstu_nu_rec.count != C * e->trace_stride) {
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(e->dstu_nu_rec.resize(C * e->trace_stride));
+  }
+  SsvsParams P;
+  fill_params(e, P);
+  SsParams S;
+  StudentParams U;
+  fill_sst_params(e, S, U);
+  if (e->trace_stride > 0) HIP_TRY(hipMemsetAsync(e->dtrace_idx.ptr, 0, C * 4, e->stream));
+  if (nsweeps == 0) return BA_OK;
+  if (!e->sst_ready) {
+    // the sampler's first draw(): impute_state with the weights as they stand (1 unless the
+    // caller set them), then -- latent data not initialised yet -- impute_nonstate_latent_data.
+    // Those weights are replaced by the round's own before any statistic reads them (the
+    // statistics are taken at impute_state): they go to the z buffer, which the X'Wz GEMM has
+    // finished with, and w stays what the statistics in hand were built from.
+    const bool first = !e->ss_initialized;
+    rc = sst_impute_state(e, S, U, 0);
+    if (rc) return rc;
+    if (first) {
+      StudentParams W = U;
+      W.w = e->dprob_z.ptr;
+      W.sweep = e->probit_sweep++;
+      HIP_TRY(launch_student_ss_weights(e->stream, W, 1));
+    }
+  }
+  for (int i = 0; i < nsweeps; ++i) {
+    // 1. the observation model's sampler with fix_latent_data(true)
+    // (TRegressionSpikeSlabSampler::draw, TRegressionSpikeSlabSampler.cpp:41-47): indicators and
+    // beta on the statistics of the last impute_state ...
+    HIP_TRY(launch_xtwx_cols_start(e->stream, e->dgamma.ptr, (int)C, (int)p, e->dlogit_req.ptr, e->dlogit_cnt.ptr,
+                                   e->dlogit_valid.ptr, e->logit_words));
+    int32_t R = 0;
+    HIP_TRY(hipMemcpyAsync(&R, e->dlogit_cnt.ptr, 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    rc = build_columns(e, R);
+    if (rc) return rc;
+    e->logit_cols_built += R;
+    HIP_TRY(launch_sweeps(e, P, 1));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    rc = check_chain_status(e);   // (park-and-replay for vectors of V asked for mid-sweep)
+    if (rc) return rc;
+    // 2. ... sigma^2, nu
+    U.sweep = e->sst_round++;
+    HIP_TRY(launch_student_sigma_nu(e->stream, U));
+    // 3. - 5. impute_nonstate_latent_data, then the state models' samplers and impute_state (one
+    // kernel: the samplers read their own streams and the statistics of the last state draw, so
+    // their place before or after the weights does not show)
+    U.sweep = e->probit_sweep++;
+    HIP_TRY(launch_student_ss_weights(e->stream, U, 1));
+    HIP_TRY(launch_ssm_simsmooth(e->stream, S, 1));
+    // 6. the complete-data statistics of the next round's observation draw
+    HIP_TRY(launch_student_ss_suf(e->stream, U, e->dlogit_Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->dlogit_vdiag.ptr,
+                                  e->dlogit_planes.ptr));
+    fill_params(e, P);
+  }
+  e->table_ok = false;
+  e->model_ok = false;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return check_chain_status(e);
 }
 
 }  // extern "C"

@@ -132,6 +132,11 @@ struct SsParams {
   // the prepare step draws ahead); nullptr: not wanted.  Read by the look-ahead's record.
   double *level_used;
   SsmParams ssm;            // (ssm_kernel.hip only)
+  // the Student-t family (StateSpaceStudentRegressionModel): every chain's per-step observation
+  // variance H_t = sigma^2 / w_t, h_stride doubles apart (nullptr: the scalar sigsq[chain]);
+  // the general structural kernel's HT instances read it
+  const double *h;
+  int64_t h_stride;
 };
 
 // The round kernel (ss_round_kernel.hip): every chain's workgroup loops over the rounds of a

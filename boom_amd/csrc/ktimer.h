@@ -30,6 +30,7 @@ enum KernelClass {
   KT_STUDENT_SIGMA_NU, // student_sigma_nu_kernel
   KT_QUANTILE_IMPUTE,  // quantile_impute_kernel
   KT_MLOGIT_IMPUTE,    // mlogit_impute_kernel + mlogit_wss_kernel
+  KT_SS_STUDENT,       // student_impute_kernel<true> / student_ss_h_kernel / student_ss_suf_kernel (bsts family = student)
   KT_CLASSES
 };
 

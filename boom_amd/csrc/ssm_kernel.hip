@@ -93,7 +93,12 @@ __host__ __device__ inline int ssg_pass_lds_doubles(int m, int ld, int bl, int n
 // GLOB: the list holds a trig or a semilocal-linear-trend block (round 6): their per-step code
 // (pair rotations, the 3 x 3 trend block, the symmetrisation of their rows of P) is compiled into
 // the GLOB = true instances only -- carried by every list it cost the round-4 lists 6 - 12 %.
-template <bool SMALL, int LDC, bool GLOB>
+// HT: a per-step observation variance H_t (P.h, T doubles per chain: the Student-t family's
+// sigma^2 / w_t, StateSpaceStudentRegressionModel::observation_variance) instead of the scalar
+// sigma^2.  A block's H_t sit one step per lane beside the observed flags; wave 1 reads them
+// into F_t, wave 0 into y+_t.  H_t > 0 always, so every step draws its observation normal.  The
+// last pass leaves Z_t'alpha_t (every step) where the HT = false instances leave the residuals.
+template <bool SMALL, int LDC, bool GLOB, bool HT = false>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void ssg_simsmooth_kernel(SsParams P, int draw_variances) {
   constexpr int SSG_BATCH = SMALL ? 4 : 8;   // entries of a column / row of P asked of the LDS together
   extern __shared__ __align__(16) unsigned char s_raw[];
@@ -299,8 +304,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
   const double sig_l = (mylane && var_l >= 0) ? s_sig2[var_l] : 0.0;
   const double sd_l = sqrt(sig_l);
 
-  const double H = P.sigsq[chain], sqrtH = sqrt(H);
-  const int dH = (sqrtH != 0.0);
+  const double H = HT ? 0.0 : P.sigsq[chain], sqrtH = sqrt(H);
+  const int dH = HT ? 1 : (sqrtH != 0.0);
+  const double *hser = HT ? P.h + (size_t)chain * P.h_stride : nullptr;
   const double *beta = P.beta + (size_t)chain * p;
   double *w0 = P.scratch + (size_t)chain * P.scratch_stride;   // y* -> w = y* - y+ -> (v - v+) / F
   double *sres = w0 + T;                                       // F_t, then residuals (input of the X'e GEMM)
@@ -376,6 +382,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       const int tt = tb + lane;
       const int nstep = (T - tb < BL) ? T - tb : BL;
       const int ob_l = (lane < nstep && P.observed[tt]) ? 1 : 0;
+      double h_l = 1.0;
+      if (HT) h_l = lane < nstep ? hser[tt] : 1.0;
       double F_l = 1.0;
 #pragma nounroll
       for (int s = 0; s < nstep; ++s) {
@@ -414,7 +422,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
               if (mylane) PZ += s_P[(f + i) * ld + lane];
           }
         }
-        const double F = zdot<SMALL, GLOB>(LI, PZ, lane) + H;
+        const double F = zdot<SMALL, GLOB>(LI, PZ, lane) + (HT ? rl(h_l, s) : H);
         if (!(F > 0.0)) { status = CHAIN_FORECAST_VARIANCE; break; }
         if (lane == s) F_l = F;
         const double Finv = 1.0 / F;
@@ -663,6 +671,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       const int nstep = (T - tb < BL) ? T - tb : BL;
       const bool in_l = lane < nstep;
       const double ys_l = in_l ? w0[tt] : 0.0;
+      double sh_l = 1.0;   // (HT: sqrt(H_t) of the block's steps, one per lane)
+      if (HT) sh_l = in_l ? sqrt(hser[tt]) : 1.0;
       // the block's normals, in stream order
       const int zstart = tb == 0 ? 0 : zoffset(tb);
       const int zend = (tb + nstep >= T) ? N : zoffset(tb + nstep);
@@ -696,7 +706,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
         }
         const double zh = dH ? s_z[zo] : 0.0;
         zo += dH;
-        const double yplus = zdot<SMALL, GLOB>(LI, alpha, lane) + sqrtH * zh;   // simulate_adjusted_observation
+        const double yplus = zdot<SMALL, GLOB>(LI, alpha, lane) + (HT ? rl(sh_l, s) : sqrtH) * zh;   // simulate_adjusted_observation
         const double w = rl(ys_l, s) - yplus;
         if (lane == s) w_l = w;
         if (mylane) blk[s * m + lane] = alpha;
@@ -954,7 +964,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
           buf[s * m + LI.first + (q >= c ? q - c : q - c + LI.dim)] = st;
         }
         const bool obs = __builtin_amdgcn_readlane(ob_l, s) != 0;
-        const double resid = obs ? rl(y_l, s) - zdot<SMALL, GLOB>(LI, st, lane) : 0.0;
+        // (HT: Z_t'alpha_t itself, every step: the Student family's offset)
+        const double resid = HT ? zdot<SMALL, GLOB>(LI, st, lane) : (obs ? rl(y_l, s) - zdot<SMALL, GLOB>(LI, st, lane) : 0.0);
         if (lane == s) res_l = resid;
         if (obs) { yty += resid * resid; nobs += 1.0; }
       }
@@ -1145,7 +1156,7 @@ hipError_t launch_ssm_simsmooth(hipStream_t stream, const SsParams &P, int draw_
   hipError_t err;
   {
     KtScope kt(stream, KT_SSM);
-    if (P.ssm.tpl_trend > 0) {
+    if (P.ssm.tpl_trend > 0 && !P.h) {
       err = launch_ssm_template(stream, P, draw_variances);
       if (err != hipSuccess) return err;
     } else {
@@ -1159,6 +1170,15 @@ hipError_t launch_ssm_simsmooth(hipStream_t stream, const SsParams &P, int draw_
         return hipSuccess;
       };
       const bool glob = P.ssm.glob != 0;   // (a trig or semilocal block in the list)
+      if (P.h) {   // the per-step observation variance's instances
+        switch (P.ssm.ld) {
+          case 17: err = glob ? go(ssg_simsmooth_kernel<true, 17, true, true>) : go(ssg_simsmooth_kernel<true, 17, false, true>); break;
+          case 33: err = glob ? go(ssg_simsmooth_kernel<false, 33, true, true>) : go(ssg_simsmooth_kernel<false, 33, false, true>); break;
+          case 61: err = glob ? go(ssg_simsmooth_kernel<false, 61, true, true>) : go(ssg_simsmooth_kernel<false, 61, false, true>); break;
+          case 65: err = glob ? go(ssg_simsmooth_kernel<false, 65, true, true>) : go(ssg_simsmooth_kernel<false, 65, false, true>); break;
+          default: return hipErrorInvalidValue;
+        }
+      } else
       switch (P.ssm.ld) {   // ssg_leading_dimension(m)
         case 17: err = glob ? go(ssg_simsmooth_kernel<true, 17, true>) : go(ssg_simsmooth_kernel<true, 17, false>); break;
         case 33: err = glob ? go(ssg_simsmooth_kernel<false, 33, true>) : go(ssg_simsmooth_kernel<false, 33, false>); break;
@@ -1171,6 +1191,7 @@ hipError_t launch_ssm_simsmooth(hipStream_t stream, const SsParams &P, int draw_
     err = hipGetLastError();
   }
   if (err != hipSuccess) return err;
+  if (P.h) return hipSuccess;   // (the Student family builds X'W(y - Z alpha) itself, student_kernel.hip)
   // xty[chain, j] = x_j' e_chain (the residual series are array 1 of every chain's scratch block)
   return launch_xte_tiled(stream, P.scratch + (size_t)P.chain_first * P.scratch_stride + P.T, P.scratch_stride,
                           P.chain_count, P.X, (int64_t)P.T, P.p, P.xty + (size_t)P.chain_first * P.p,

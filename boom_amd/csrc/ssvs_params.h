@@ -25,6 +25,7 @@ enum ChainStatus : int32_t {
 // MLVS::draw_inclusion_vector found a start whose log_model_prob is not finite (MLVS.cpp:130-138;
 // the other samplers call make_valid there)
 enum { MLVS_ILLEGAL_START = 12 };
+// (13: STUDENT_BAD_WEIGHT of the state space Student family, student_params.h)
 
 // number of doubles in the reduced summary block: 3p + SUMMARY_SCALARS
 enum { SUMMARY_SCALARS = 16 };

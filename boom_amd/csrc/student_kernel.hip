@@ -86,6 +86,13 @@ __device__ __forceinline__ double stu_block_sum(double v, double *s_red) {
 
 }  // namespace
 
+// SS: the state space Student family (StateSpaceStudentPosteriorSampler::
+// impute_nonstate_latent_data, StateSpaceStudentPosteriorSampler.cpp:60-80): the residual is
+// y_t - x_t'beta - offset_t (the chain's Z_t'alpha_t), a missing step keeps weight 0 and reads no
+// random numbers, and beside w_t the kernel writes the filter's H_t = sigma^2 / w_t -- the model's
+// student_marginal_variance() where the step is missing or w_t = 0 (StateSpaceStudentRegressionModel::
+// observation_variance).  z is left to student_ss_suf_kernel (after the state draw).
+template <bool SS>
 __global__ __launch_bounds__(256) void student_impute_kernel(StudentParams P) {
   const int chain = (int)blockIdx.y, i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   __shared__ int s_status;
@@ -102,8 +109,17 @@ __global__ __launch_bounds__(256) void student_impute_kernel(StudentParams P) {
   if (i >= P.n) return;
   double eta = 0.0;
   for (int m = 0; m < k; ++m) eta += P.X[(size_t)s_idx[m] * P.n + i] * s_beta[m];
-  const double yi = P.y[i];
+  double yi = P.y[i];
   const double nu = P.nu[chain];
+  if (SS) {
+    const double sigsq = P.sigsq[chain];
+    if (!P.observed[i]) {
+      P.w[(size_t)chain * P.n + i] = 0.0;
+      P.h[(size_t)chain * P.n + i] = nu > 2 ? sigsq * nu / (nu - 2) : sigsq * 1e8;
+      return;
+    }
+    yi -= P.offset[(size_t)chain * P.offset_stride + i];
+  }
   const double delta = (yi - eta) / sqrt(P.sigsq[chain]);
   SeqRng rng = SeqRng::slot(PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), STUDENT_IMPUTE_STREAM},
                             P.sweep * (uint64_t)P.n + (uint64_t)i, STUDENT_IMPUTE_STRIDE,
@@ -114,17 +130,52 @@ __global__ __launch_bounds__(256) void student_impute_kernel(StudentParams P) {
   const double w = d_rgamma_scale(rng, 0.5 * (nu + 1), 1.0 / (0.5 * (nu + delta * delta)), &bad);
   if (bad || rng.overran()) P.status[chain] = CHAIN_RNG_BRANCH;
   P.w[(size_t)chain * P.n + i] = w;
-  P.z[(size_t)chain * P.n + i] = w * yi;
+  if (SS) {
+    const double sigsq = P.sigsq[chain];
+    // (the reference throws "Weights must be finite and non-negative." from set_weight)
+    if (!(w >= 0.0) || !isfinite(w)) P.status[chain] = STUDENT_BAD_WEIGHT;
+    P.h[(size_t)chain * P.n + i] = w > 0.0 ? sigsq / w : (nu > 2 ? sigsq * nu / (nu - 2) : sigsq * 1e8);
+  } else {
+    P.z[(size_t)chain * P.n + i] = w * yi;
+  }
+}
+
+// the state space Student family's H_t from weights the caller set (ba_ss_student_set_weights,
+// all weights 1 of the first round): the same rule as student_impute_kernel<true>
+__global__ __launch_bounds__(256) void student_ss_h_kernel(StudentParams P) {
+  const int chain = (int)blockIdx.y, i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= P.n || P.status[chain] != CHAIN_OK) return;
+  const double nu = P.nu[chain], sigsq = P.sigsq[chain];
+  const double w = P.observed[i] ? P.w[(size_t)chain * P.n + i] : 0.0;
+  if (!(w >= 0.0) || !isfinite(w)) { P.status[chain] = STUDENT_BAD_WEIGHT; return; }
+  P.h[(size_t)chain * P.n + i] = w > 0.0 ? sigsq / w : (nu > 2 ? sigsq * nu / (nu - 2) : sigsq * 1e8);
+}
+
+// ... and after the state draw the complete-data response z_t = w_t (y_t - offset_t), 0 where
+// the step is missing (update_complete_data_sufficient_statistics,
+// StateSpaceStudentPosteriorSampler.cpp:113-124): the rows of the X'Wz GEMM
+__global__ __launch_bounds__(256) void student_ss_suf_kernel(StudentParams P) {
+  const int chain = (int)blockIdx.y, i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= P.n) return;
+  const size_t at = (size_t)chain * P.n + i;
+  if (!P.observed[i]) {
+    P.w[at] = 0.0;
+    P.z[at] = 0.0;
+    return;
+  }
+  P.z[at] = P.w[at] * (P.y[i] - P.offset[(size_t)chain * P.offset_stride + i]);
 }
 
 namespace {
 
+template <bool SS>
 struct StuSlice {
   const StudentParams *P;
   const double *u;   // this chain's u_i
   double n_log_sigma;
   double *s_red;
   double margin;
+  double nobs;   // (SS: the observed steps; else unused, n)
   // log f(nu): the prior's logp, then (unless that is -inf) the observed-data likelihood
   __device__ double logf(double nu) {
     double lp;
@@ -139,7 +190,7 @@ struct StuSlice {
     const double inv = 1.0 / nu;
     for (int i = threadIdx.x; i < P->n; i += STUDENT_SN_BLOCK) part += log1p(u[i] * inv);
     const double s = stu_block_sum(part, s_red);
-    const double nn = (double)P->n;
+    const double nn = SS ? nobs : (double)P->n;
     const double c = lgamma(0.5 * (nu + 1)) - lgamma(0.5 * nu) - 0.5 * log(nu * 3.141592653589793);
     return lp + (nn * c - n_log_sigma) - 0.5 * (nu + 1) * s;
   }
@@ -152,6 +203,11 @@ struct StuSlice {
 
 }  // namespace
 
+// SS: the state space Student family -- residuals y_t - offset_t - x_t'beta over the observed
+// steps only (the observation model holds the observed steps' data with the time series
+// residual as its response, StateSpaceStudentPosteriorSampler.cpp:90-124): DF = observed + prior df,
+// the nu likelihood over the observed steps (a missing step's u_t = 0 adds log1p(0) = 0).
+template <bool SS>
 __global__ __launch_bounds__(STUDENT_SN_BLOCK) void student_sigma_nu_kernel(StudentParams P) {
   const int chain = (int)blockIdx.x, tid = (int)threadIdx.x;
   __shared__ int s_status;
@@ -170,20 +226,24 @@ __global__ __launch_bounds__(STUDENT_SN_BLOCK) void student_sigma_nu_kernel(Stud
   const double *w = P.w + (size_t)chain * n;
   double *u = P.u + (size_t)chain * n;
   // 1. residuals at the new beta, the weighted sum of squared errors
-  double part = 0.0;
+  double part = 0.0, cnt = 0.0;
   for (int i = tid; i < n; i += STUDENT_SN_BLOCK) {
+    if (SS && !P.observed[i]) { u[i] = 0.0; continue; }
     double eta = 0.0;
     for (int m = 0; m < k; ++m) eta += P.X[(size_t)s_idx[m] * n + i] * s_beta[m];
-    const double r = P.y[i] - eta;
+    double yi = P.y[i];
+    if (SS) { yi -= P.offset[(size_t)chain * P.offset_stride + i]; cnt += 1.0; }
+    const double r = yi - eta;
     u[i] = r;
     part += w[i] * (r * r);
   }
   const double wsse = stu_block_sum(part, s_red);
+  const double nobs = SS ? stu_block_sum(cnt, s_red) : (double)n;
   // 2. sigma^2 (GenericGaussianVarianceSampler::draw: n observations, not sum w)
   SeqRng rng = SeqRng::slot(PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), STUDENT_SN_STREAM},
                             P.sweep, STUDENT_SN_STRIDE, stu_serve(P, STUDENT_SN_STRIDE));
   int bad = 0;
-  const double sigsq = d_draw_variance(rng, (double)n + P.prior_df, wsse + P.prior_ss, P.sigma_max, &bad);
+  const double sigsq = d_draw_variance(rng, nobs + P.prior_df, wsse + P.prior_ss, P.sigma_max, &bad);
   if (bad) {
     if (tid == 0) P.status[chain] = CHAIN_RNG_BRANCH;
     return;
@@ -196,7 +256,7 @@ __global__ __launch_bounds__(STUDENT_SN_BLOCK) void student_sigma_nu_kernel(Stud
   }
   __syncthreads();   // (every thread reads every u_i from here on)
   // 4. nu: ScalarSliceSampler::draw with lower limit 0 (find_limits -> find_upper_limit)
-  StuSlice S{&P, u, (double)n * log(sigma), s_red, __builtin_inf()};
+  StuSlice<SS> S{&P, u, nobs * log(sigma), s_red, __builtin_inf(), nobs};
   const double x = P.nu[chain];
   const double sigsq_in = P.sigsq[chain];   // (the sweep's: its summaries hold this one)
   double dx = P.dx[chain];
@@ -266,7 +326,7 @@ hipError_t launch_student_impute(hipStream_t stream, const StudentParams &P, con
   hipError_t err;
   {
     KtScope kt(stream, KT_STUDENT_IMPUTE);
-    hipLaunchKernelGGL(student_impute_kernel, dim3((P.n + 255) / 256, P.chains), dim3(256), 0, stream, P);
+    hipLaunchKernelGGL(student_impute_kernel<false>, dim3((P.n + 255) / 256, P.chains), dim3(256), 0, stream, P);
     err = hipGetLastError();
   }
   if (err != hipSuccess) return err;
@@ -277,8 +337,34 @@ hipError_t launch_student_impute(hipStream_t stream, const StudentParams &P, con
 
 hipError_t launch_student_sigma_nu(hipStream_t stream, const StudentParams &P) {
   KtScope kt(stream, KT_STUDENT_SIGMA_NU);
-  hipLaunchKernelGGL(student_sigma_nu_kernel, dim3(P.chains), dim3(STUDENT_SN_BLOCK), 0, stream, P);
+  if (P.offset) hipLaunchKernelGGL(student_sigma_nu_kernel<true>, dim3(P.chains), dim3(STUDENT_SN_BLOCK), 0, stream, P);
+  else hipLaunchKernelGGL(student_sigma_nu_kernel<false>, dim3(P.chains), dim3(STUDENT_SN_BLOCK), 0, stream, P);
   return hipGetLastError();
+}
+
+// the state space Student family's weight step: w_t and H_t (draw = 0: H_t from the weights as they stand)
+hipError_t launch_student_ss_weights(hipStream_t stream, const StudentParams &P, int draw) {
+  KtScope kt(stream, KT_SS_STUDENT);
+  const dim3 grid((P.n + 255) / 256, P.chains);
+  if (draw) hipLaunchKernelGGL(student_impute_kernel<true>, grid, dim3(256), 0, stream, P);
+  else hipLaunchKernelGGL(student_ss_h_kernel, grid, dim3(256), 0, stream, P);
+  return hipGetLastError();
+}
+
+// ... and its complete-data statistics after a state draw: z, X'Wz and the diagonal of
+// V = slab precision + X'WX
+hipError_t launch_student_ss_suf(hipStream_t stream, const StudentParams &P, const double *Xsq,
+                                 const double *slab_precision, double *xtz, double *v_diag, double *planes) {
+  hipError_t err;
+  {
+    KtScope kt(stream, KT_SS_STUDENT);
+    hipLaunchKernelGGL(student_ss_suf_kernel, dim3((P.n + 255) / 256, P.chains), dim3(256), 0, stream, P);
+    err = hipGetLastError();
+  }
+  if (err != hipSuccess) return err;
+  err = launch_rows_times_columns(stream, P.z, P.chains, P.X, (int64_t)P.n, P.p, nullptr, xtz, planes);
+  if (err != hipSuccess) return err;
+  return launch_rows_times_columns(stream, P.w, P.chains, Xsq, (int64_t)P.n, P.p, slab_precision, v_diag, planes);
 }
 
 }  // namespace boom_amd

@@ -15,6 +15,9 @@ enum : uint32_t { STUDENT_IMPUTE_STREAM = 31u, STUDENT_SN_STREAM = 15u };
 enum { STUDENT_IMPUTE_STRIDE = 256, STUDENT_SN_STRIDE = 4096, STUDENT_KMAX = 1024, STUDENT_SN_BLOCK = 256 };
 // the slice sampler's error exits (ScalarSliceSampler.cpp), as chain status words
 enum { STUDENT_SLICE_ERROR = 9 };
+// a weight of the state space Student family that is negative or not finite ("Weights must be
+// finite and non-negative.", StateSpaceStudentRegressionModel.cpp set_weight)
+enum { STUDENT_BAD_WEIGHT = 13 };
 // the nu prior: Uniform(a, b) or Gamma(a, b) (shape, rate)
 enum { STUDENT_NU_UNIFORM = 0, STUDENT_NU_GAMMA = 1 };
 
@@ -47,6 +50,13 @@ struct StudentParams {
   // the running summaries (chains x ACC_COUNT): the sweep added the sigma^2 it was given,
   // the sigma^2 / nu kernel puts the new draw in its place
   double *acc;
+  // the state space Student family (nullptr: plain Student-t regression): the chain's
+  // Z_t'alpha_t of the last state draw, offset_stride doubles apart; which steps are observed;
+  // the filter's H_t = sigma^2 / w_t (chains x n)
+  const double *offset;
+  int64_t offset_stride;
+  const uint8_t *observed;
+  double *h;
 };
 
 }  // namespace boom_amd

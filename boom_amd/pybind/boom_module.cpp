@@ -558,6 +558,40 @@ PYBIND11_MODULE(_boom, boom) {
       .def("limit_model_selection", &TRegressionSpikeSlabSampler::limit_model_selection)
       .def("allow_model_selection", &TRegressionSpikeSlabSampler::allow_model_selection);
 
+  // ---- bsts family = "student" (StateSpaceStudentRegressionModel,
+  // StateSpaceStudentPosteriorSampler): the state space model's bindings, inherited, + the
+  // Student-t observation model's ----------------------------------------------------------
+  py::class_<StateSpaceStudentRegressionModel, StateSpaceRegressionModel, Ptr<StateSpaceStudentRegressionModel>>(
+      boom, "StateSpaceStudentRegressionModel")
+      .def(py::init([](const NpArray &response, const NpArray &predictors, const std::vector<bool> &is_observed,
+                       int chains, uint64_t seed, int device) {
+             return new StateSpaceStudentRegressionModel(vector_from(response), matrix_from(predictors), is_observed,
+                                                         chains, seed, device);
+           }),
+           py::arg("response"), py::arg("predictors"), py::arg("is_observed") = std::vector<bool>(),
+           py::arg("chains") = 1, py::arg("seed") = 8675309ull, py::arg("device") = 0)
+      .def("nu", &StateSpaceStudentRegressionModel::nu, py::arg("chain") = 0)
+      .def("set_nu", &StateSpaceStudentRegressionModel::set_nu)
+      .def("sigsq", &StateSpaceStudentRegressionModel::sigsq, py::arg("chain") = 0)
+      .def("weights", [](const StateSpaceStudentRegressionModel &m, int chain) { return to_numpy(m.weights(chain)); },
+           py::arg("chain") = 0, "the latent gamma weights of one chain (0 at a missing step)")
+      .def("set_weights", [](StateSpaceStudentRegressionModel &m, const NpArray &w, int chain) {
+             m.set_weights(vector_from(w), chain);
+           }, py::arg("weights"), py::arg("chain") = -1)
+      .def("impute_state", &StateSpaceStudentRegressionModel::impute_state);
+  py::class_<StateSpaceStudentPosteriorSampler, PosteriorSampler, Ptr<StateSpaceStudentPosteriorSampler>>(
+      boom, "StateSpaceStudentPosteriorSampler")
+      .def(py::init([](StateSpaceStudentRegressionModel *model, const Ptr<MvnGivenScalarSigma> &slab,
+                       const Ptr<VariableSelectionPrior> &spike, const Ptr<ChisqModel> &siginv_prior,
+                       const Ptr<DoubleModel> &nu_prior, py::object) {
+             return new StateSpaceStudentPosteriorSampler(model, slab, spike, siginv_prior, nu_prior);
+           }),
+           py::arg("model"), py::arg("coefficient_slab"), py::arg("coefficient_spike"),
+           py::arg("siginv_prior"), py::arg("nu_prior"), py::arg("seeding_rng") = py::none(),
+           py::keep_alive<1, 2>())
+      .def("draw", &StateSpaceStudentPosteriorSampler::draw)
+      .def("set_sigma_upper_limit", &StateSpaceStudentPosteriorSampler::set_sigma_upper_limit);
+
   // ---- quantile regression spike and slab (QuantileRegressionModel,
   // QuantileRegressionSpikeSlabSampler) -----------------------------------------------------
   py::class_<QuantileRegressionModel, Ptr<QuantileRegressionModel>>(boom, "QuantileRegressionModel")

@@ -372,6 +372,8 @@ int ba_student_get_weights(ba_engine *e, int64_t chain, double *w);
 int ba_student_get_nu_draws(ba_engine *e, int64_t chain, int32_t nsweeps, double *out);
 int ba_student_get_margin(ba_engine *e, int64_t chain, double *margin);
 int ba_student_allow_model_selection(ba_engine *e, int32_t allow);
+/* (ba_student_set_nu_prior, _set_nu, _get_nu, _get_nu_draws, _get_margin and
+ * _allow_model_selection serve the state space Student-t family, ba_ss_student_*, too) */
 
 /* ---- QuantileRegressionSpikeSlabSampler (qreg.spike) ----------------------------------------
  * Models/Glm/PosteriorSamplers/QuantileRegressionPosteriorSampler.cpp:30-39, :77-91: per sweep,
@@ -630,6 +632,8 @@ int ba_ss_get_state_model(ba_engine *e, int64_t chain, int32_t block, double *va
 /* one chain's state draw (T x m, step t at [t * m, (t + 1) * m), the models' components
  * in the order the models were added) */
 int ba_ss_get_state_draw(ba_engine *e, int64_t chain, double *state);
+/* (ba_ss_add_state_model, ba_ss_get_state_model, ba_ss_get_state_draw and ba_ss_get_ar serve the
+ * Student-t family, ba_ss_student_*, too) */
 /* The template of rounds 2-3, kept: a trend state model -- trend = 1: local level; 2:
  * local linear trend -- plus an optional SeasonalStateModel(nseasons, season_duration =
  * 1); nseasons = 0: none.  Equivalent to ba_ss_add_state_model(trend) [+ (seasonal)].
@@ -690,6 +694,46 @@ int ba_ss_sweep(ba_engine *e, int32_t nsweeps);
 /* one Base::impute_state (StateSpaceModelBase.cpp:278-291) with the current
  * parameters, on every chain */
 int ba_ss_impute_state(ba_engine *e);
+
+/* ---- bsts(family = "student"): StateSpaceStudentRegressionModel with
+ * StateSpaceStudentPosteriorSampler (Models/StateSpace/StateSpaceStudentRegressionModel.cpp,
+ * PosteriorSamplers/StateSpaceStudentPosteriorSampler.cpp:56-126) ----------------------------
+ * One observation per time step.  The observation model is TRegressionSpikeSlabSampler with its
+ * latent data fixed (the kernels of ba_student_sweep on the response y_t - Z_t'alpha_t over the
+ * observed steps); the state draw is the general structural kernel with the per-step observation
+ * variance H_t = sigma^2 / w_t (sigma^2 nu / (nu - 2), or 1e8 sigma^2 for nu <= 2, where a step
+ * is missing or its weight is 0).
+ *   ba_ss_student_set_data   as ba_ss_set_data; starts a new model (nu = 30, all weights 1, no
+ *                            state draw yet)
+ *   state models             ba_ss_add_state_model (a plain local level is the one-block list;
+ *                            after ba_ss_set_local_level alone the family is refused); the general
+ *                            kernel always, whatever ba_ss_set_tuning says
+ *   priors                   ba_sss_set_slab(mu, precision, 1, max_flips), ba_set_spike,
+ *                            ba_set_sigma_prior, ba_student_set_nu_prior, ba_student_set_nu
+ *   ba_ss_student_sweep      nsweeps x StateSpacePosteriorSampler::draw (StateSpacePosteriorSampler.cpp:
+ *                            41-63): indicators and beta given sigma^2, sigma^2, nu, the state models'
+ *                            parameters, the weights, the state.  A sampler that has drawn no state yet
+ *                            first draws it with the weights in hand (1 unless set) and imputes the
+ *                            weights once, as the reference's first draw() does.
+ *   ba_ss_student_impute_state   one impute_state with the current parameters and weights
+ *   ba_ss_student_get_weights / _set_weights   one chain's T weights (set: chain -1 = every chain;
+ *                            AugmentedStudentRegressionData::set_weight: "Weights must be finite and
+ *                            non-negative."; a missing step's weight is not read).  After _set_weights
+ *                            the next sweep starts with an impute_state on the new weights.
+ * Also served for this kind: ba_set_state / ba_get_state(s), ba_enable_draws with ba_get_draws and
+ * ba_student_get_nu_draws, ba_student_get_nu / _get_margin / _allow_model_selection,
+ * ba_ss_get_state_draw, ba_ss_get_state_model, ba_ss_get_ar, ba_ss_state_dimension.  Not served:
+ * ba_ss_forecast, ba_ss_draw_next, ba_ss_sweep, ba_ss_impute_state (refused).
+ * RNG: stream 3 indicators / beta; stream 15 from position r * 4096 for sigma^2, then nu, of round
+ * r; stream 31 from position (s T + t) * 256 for the weight of step t in the sampler's s-th
+ * weight imputation (the first draw() makes two); stream 2 the state; the state models' streams
+ * as on the Gaussian path. */
+int ba_ss_student_set_data(ba_engine *e, int32_t T, int32_t p, const double *y,
+                           const double *X, const uint8_t *observed);
+int ba_ss_student_sweep(ba_engine *e, int32_t nsweeps);
+int ba_ss_student_get_weights(ba_engine *e, int64_t chain, double *w);
+int ba_ss_student_set_weights(ba_engine *e, int64_t chain, const double *w);
+int ba_ss_student_impute_state(ba_engine *e);
 /* StateSpaceRegressionModel::simulate_forecast(rng, newX, final_state)
  * (StateSpaceRegressionModel.cpp:214-219, :256-278; what bsts' predict does for
  * every saved draw): one draw from the predictive distribution of the next

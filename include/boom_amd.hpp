@@ -541,8 +541,9 @@ class StateSpaceRegressionModel : public Model {
   void add_state(const Ptr<TrigStateModel> &s) { Entry e; e.kind = 6; e.trig = s; models_.push_back(e); finalized_ = false; }
   void add_state(const Ptr<SemilocalLinearTrendStateModel> &s) { Entry e; e.kind = 7; e.semilocal = s; models_.push_back(e); finalized_ = false; }
   int number_of_state_models() const { return (int)models_.size(); }
-  // anything but a lone local level (which runs the local-level kernels)
-  bool structural() const { return !(models_.size() == 1 && models_[0].kind == 1); }
+  // anything but a lone local level (which runs the local-level kernels; the Student-t family
+  // always sends the list)
+  bool structural() const { return list_always_ || !(models_.size() == 1 && models_[0].kind == 1); }
   int state_dimension() const {
     int m = 0;
     for (const Entry &e : models_)
@@ -656,6 +657,17 @@ class StateSpaceRegressionModel : public Model {
     eng_->check(ba_ss_get_state(eng_->get(), chain, nullptr, &v, nullptr, nullptr));
     return v;
   }
+ protected:
+  // StateSpaceStudentRegressionModel: the same state, the Student-t observation model
+  struct StudentFamily {};
+  StateSpaceRegressionModel(StudentFamily, const Vector &y, const Matrix &X, const std::vector<bool> &observed,
+                            int chains, uint64_t seed, int device)
+      : eng_(new Engine(chains, seed, device)), T_((int)y.size()), p_(X.ncol()), list_always_(true) {
+    if (X.nrow() != T_) report_error("X and y are incompatible in constructor for StateSpaceStudentRegressionModel.");
+    std::vector<uint8_t> obs;
+    if (!observed.empty()) { obs.resize(T_); for (int t = 0; t < T_; ++t) obs[t] = observed[t]; }
+    eng_->check(ba_ss_student_set_data(eng_->get(), T_, p_, y.data(), X.data(), obs.empty() ? nullptr : obs.data()));
+  }
  private:
   struct Entry {
     int kind = 0;   // 1 local level, 2 local linear trend, 3 seasonal, 4 autoregression, 5 static intercept, 6 trig, 7 semilocal linear trend
@@ -678,6 +690,7 @@ class StateSpaceRegressionModel : public Model {
   int T_, p_;
   std::vector<Entry> models_;
   bool finalized_ = false;
+  bool list_always_ = false;
 };
 
 // regression priors are set through the same three pieces as BregVsSampler
@@ -1023,6 +1036,75 @@ class TRegressionSpikeSlabSampler : public PosteriorSampler {
   Ptr<MvnGivenScalarSigma> slab_;
   Ptr<ChisqModel> siginv_;
   double sigma_max_ = std::numeric_limits<double>::infinity();
+};
+
+// ---- bsts family = "student" --------------------------------------------------------------
+// StateSpaceStudentRegressionModel + StateSpaceStudentPosteriorSampler (Models/StateSpace/
+// StateSpaceStudentRegressionModel.hpp, PosteriorSamplers/StateSpaceStudentPosteriorSampler.cpp:
+// 56-126): the state of StateSpaceRegressionModel with TRegressionModel's observation noise, on
+// the device (ba_ss_student_*).  One observation per time step.  Chain 0 backs the accessors'
+// defaults.
+class StateSpaceStudentRegressionModel : public StateSpaceRegressionModel {
+ public:
+  StateSpaceStudentRegressionModel(const Vector &y, const Matrix &X, const std::vector<bool> &observed,
+                                   int chains = 1, uint64_t seed = 8675309, int device = 0)
+      : StateSpaceRegressionModel(StudentFamily(), y, X, observed, chains, seed, device) {}
+  double nu(int chain = 0) const {
+    double v;
+    engine()->check(ba_student_get_nu(engine()->get(), chain, &v));
+    return v;
+  }
+  void set_nu(double nu) { engine()->check(ba_student_set_nu(engine()->get(), -1, nu)); }
+  double sigsq(int chain = 0) const {
+    double v;
+    engine()->check(ba_get_state(engine()->get(), chain, nullptr, nullptr, &v));
+    return v;
+  }
+  // the latent weights of one chain (AugmentedStudentRegressionData::weight); 0 at a missing step
+  Vector weights(int chain = 0) const {
+    Vector w(time_dimension());
+    engine()->check(ba_ss_student_get_weights(engine()->get(), chain, w.data()));
+    return w;
+  }
+  void set_weights(const Vector &w, int chain = -1) {   // set_weight, every step (chain -1: every chain)
+    if ((int)w.size() != time_dimension()) report_error("One weight per time step is needed.");
+    engine()->check(ba_ss_student_set_weights(engine()->get(), chain, w.data()));
+  }
+  void impute_state() {   // Base::impute_state with the current parameters and weights
+    finalize_state();
+    engine()->check(ba_ss_student_impute_state(engine()->get()));
+  }
+};
+// StateSpaceStudentPosteriorSampler(model, observation model sampler's priors): slab, spike,
+// siginv prior and nu prior as TRegressionSpikeSlabSampler takes them
+class StateSpaceStudentPosteriorSampler : public PosteriorSampler {
+ public:
+  StateSpaceStudentPosteriorSampler(StateSpaceStudentRegressionModel *model, const Ptr<MvnGivenScalarSigma> &slab,
+                                    const Ptr<VariableSelectionPrior> &spike, const Ptr<ChisqModel> &siginv_prior,
+                                    const Ptr<DoubleModel> &nu_prior)
+      : model_(model), siginv_(siginv_prior) {
+    if (slab->dim() != model->xdim()) report_error("Slab does not match model dimension.");
+    if ((int)spike->potential_nvars() != model->xdim()) report_error("Spike does not match model dimension.");
+    check(ba_sss_set_slab(h(), slab->mu().data(), slab->unscaled_precision().data(), 1, -1));
+    check(ba_set_spike(h(), spike->prior_inclusion_probabilities().data(), spike->max_model_size()));
+    check(ba_set_sigma_prior(h(), siginv_prior->df(), siginv_prior->sigma(), infinity()));
+    check(ba_student_set_nu_prior(h(), nu_prior->kind_, nu_prior->a_, nu_prior->b_));
+    std::vector<uint8_t> g0(model->xdim(), 0);
+    check(ba_set_state(h(), -1, g0.data(), nullptr, 1.0));
+  }
+  void draw() override {                     // StateSpacePosteriorSampler.cpp:41-63
+    model_->finalize_state();
+    check(ba_ss_student_sweep(h(), 1));
+    check(ba_sync(h()));
+  }
+  double logpri() const override { report_error("logpri() is not implemented for the Student-t state space sampler"); return 0; }
+  void set_seed(unsigned long s) override { check(ba_seed(h(), s)); }
+  void set_sigma_upper_limit(double max_sigma) { check(ba_set_sigma_prior(h(), siginv_->df(), siginv_->sigma(), max_sigma)); }
+ private:
+  ba_engine *h() const { return model_->engine()->get(); }
+  void check(int rc) const { model_->engine()->check(rc); }
+  StateSpaceStudentRegressionModel *model_;
+  Ptr<ChisqModel> siginv_;
 };
 
 // ---- Quantile regression spike and slab --------------------------------------------------

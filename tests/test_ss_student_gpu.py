@@ -1,0 +1,355 @@
+"""bsts family = "student" on the device (ba_ss_student_*): StateSpaceStudentRegressionModel with
+StateSpaceStudentPosteriorSampler -- the general structural kernel with the per-step observation
+variance H_t = sigma^2 / w_t, the Student kernels on the response y - Z alpha over the observed
+steps, the round's order.
+
+  identities    the H_t instances of the kernel against the scalar ones, bit for bit
+  filter edges  one impute_state against the restatement (tests/ss_student_oracle.py): weights
+                over six decades, missing steps, a weight of exactly 0, nu <= 2
+  whole rounds  against the restatement on the same substreams: inclusion indicators bit-exact;
+                beta, sigma^2, nu, the weights, the state, the state models' variances and
+                sufficient statistics within 1e-8 relative (the bars of tests/test_student_gpu.py
+                and tests/test_structural_general_gpu.py)
+  distribution  4096 chains' state draws against the dense Gaussian posterior
+  interface     refusals and their texts, recorded draws, ba_get_state
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import ss_student_oracle as sso
+from cases import bsts_priors, general_data, general_spec
+
+gpu = pytest.mark.gpu
+RTOL = 1e-8
+
+
+def relerr(a, b, floor=1e-3):
+    a, b = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
+    return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), floor)))
+
+
+def slab_of(p):
+    return np.zeros(p), 0.1 * np.eye(p), np.full(p, min(0.9, 2.5 / p))
+
+
+def student_engine(chains, seed, y, X, obs, blocks, g0, nu_prior=(0, 0.1, 100.0), sigma_prior=(1.0, 1.0),
+                   sigma_max=np.inf):
+    import boom_amd
+    p = X.shape[1]
+    mu, prec, pi = slab_of(p)
+    eng = boom_amd.Engine(chains, seed=seed)
+    eng.ss_student_set_data(y, X, obs)
+    eng.sss_set_slab(mu, prec, scales_with_sigsq=True)
+    eng.set_spike(pi)
+    eng.set_sigma_prior(sigma_prior[0], sigma_prior[1], sigma_max)
+    eng.student_set_nu_prior(*nu_prior)
+    eng.ss_set_state_models(blocks)
+    eng.set_state(g0)
+    return eng
+
+
+def gaussian_engine(chains, seed, y, X, obs, blocks, g0):
+    import boom_amd
+    prior, _, sig_up = bsts_priors(X, y, 2)
+    eng = boom_amd.Engine(chains, seed=seed)
+    eng.ss_set_data(y, X, obs)
+    eng.set_priors(prior["b"], prior["ominv"], prior["pi"], prior["df"], prior["sigma_guess"],
+                   sigma_upper_limit=sig_up)
+    eng.ss_set_state_models(blocks)
+    eng.ss_set_tuning(kernel=0)   # the general kernel: the one the H_t instances are instances of
+    eng.set_state(g0)
+    return eng
+
+
+def chain_parameters(p, chains, seed):
+    rs = np.random.Generator(np.random.PCG64(seed))
+    gam = (rs.uniform(size=(chains, p)) < 0.6).astype(np.uint8)
+    gam[:, 0] = 1
+    return gam, rs.standard_normal((chains, p)) * gam
+
+
+# ---- 3. identities ---------------------------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("desc,T,missing", [
+    ([("trend",), ("seasonal", 4, 1)], 70, 0.05),     # a 64-step block boundary, a partial last block
+    ([("level",), ("seasonal", 20, 1)], 40, 0.0),     # m = 20 > 16: blocks of 32 steps
+])
+@pytest.mark.parametrize("weight", [1.0, 4.0])
+def test_constant_weights_equal_the_scalar_kernel(desc, T, missing, weight):
+    """w = 1: the Gaussian engine's impute_state at the same sigma^2, bit for bit; w = 4: at
+    sigma^2 / 4 (exact in binary)"""
+    p, chains, seed, sigsq = 3, 4, 77, 0.5
+    seas = [(b[1], b[2]) for b in desc if b[0] == "seasonal"]
+    X, y, _, obs = general_data(T, p, 2, seas, seed=T, missing_frac=missing)
+    blocks = general_spec(y, desc)
+    gam, beta = chain_parameters(p, chains, 3)
+    a = student_engine(chains, seed, y, X, obs, blocks, gam[0])
+    b = gaussian_engine(chains, seed, y, X, obs, blocks, gam[0])
+    for c in range(chains):
+        a.set_state(gam[c], beta[c], sigsq, chain=c)
+        b.set_state(gam[c], beta[c], sigsq / weight, chain=c)
+    a.ss_student_set_weights(np.full(T, weight))
+    a.ss_student_impute_state()
+    b.ss_impute_state()
+    for c in range(chains):
+        assert np.array_equal(a.ss_get_state_draw(c), b.ss_get_state_draw(c)), c
+        for k in range(len(blocks)):
+            u, v = a.ss_get_state_model(c, k), b.ss_get_state_model(c, k)
+            assert np.array_equal(u["suf_ss"], v["suf_ss"]) and np.array_equal(u["suf_n"], v["suf_n"]), (c, k)
+
+
+# ---- 4. filter edges ---------------------------------------------------------------------------
+def state_stream(oracle, seed, chain):
+    L = oracle.lib
+    L.bo_rnorm.argtypes = [C.c_void_p, C.c_double, C.c_double]
+    L.bo_rnorm.restype = C.c_double
+    rng = oracle.rng_philox(seed, chain, 2, 0)
+    return lambda mu, sd: L.bo_rnorm(C.byref(rng), float(mu), float(sd))
+
+
+@gpu
+@pytest.mark.parametrize("nu", [5.0, 2.0, 1.5])
+def test_impute_state_matches_restatement_at_the_edges(oracle, nu):
+    """weights from 1e-3 to 1e3, the first step missing, a missing step in the second block of
+    64, a weight of exactly 0 on an observed step (H_t = the marginal variance), nu <= 2 (the
+    1e8 sigma^2 arm)"""
+    desc, T, p, chains, seed, sigsq = [("trend",), ("seasonal", 4, 1)], 70, 3, 4, 41, 0.8
+    X, y, _, _ = general_data(T, p, 2, [(4, 1)], seed=12)
+    obs = np.ones(T, np.uint8)
+    obs[[0, 66]] = 0
+    blocks = general_spec(y, desc)
+    gam, beta = chain_parameters(p, chains, 8)
+    eng = student_engine(chains, seed, y, X, obs, blocks, gam[0])
+    eng.student_set_nu(nu)
+    rs = np.random.Generator(np.random.PCG64(2))
+    W = np.exp(rs.uniform(np.log(1e-3), np.log(1e3), (chains, T)))
+    W[:, 10] = 0.0
+    W[:, [1, 65]] = [1e-3, 1e3]
+    for c in range(chains):
+        eng.set_state(gam[c], beta[c], sigsq, chain=c)
+        eng.ss_student_set_weights(W[c], chain=c)
+    eng.ss_student_impute_state()
+    S = sso.Structure(blocks)
+    var = [np.asarray(b["initial_sigma"], float) ** 2 for b in blocks]
+    ob = obs.astype(bool)
+    for c in range(chains):
+        H = sso.observation_variances(W[c], ob, sigsq, nu)
+        assert H[10] == sso.marginal_variance(sigsq, nu) and H[0] == H[10]
+        inc = np.flatnonzero(gam[c])
+        want = sso.impute_state(S, var, y - X[:, inc] @ beta[c][inc], ob, H, state_stream(oracle, seed, c))
+        got = eng.ss_get_state_draw(c)
+        assert np.max(np.abs(got - want)) < 1e-8 * np.abs(want).max(), c
+        w = eng.ss_student_get_weights(c)
+        assert np.array_equal(w, np.where(ob, W[c], 0.0)), c
+
+
+# ---- 5. whole rounds ----------------------------------------------------------------------------
+ROUND_CASES = [
+    # blocks, missing steps, sigma upper limit, nu prior
+    ([("trend",), ("seasonal", 4, 1)], [], 1.5, (1, 2.0, 0.1)),
+    ([("level",)], [5, 23], np.inf, (0, 0.1, 100.0)),
+]
+
+
+def round_case(k):
+    desc, miss, smax, nup = ROUND_CASES[k]
+    T, p, chains, seed, rounds = 40, 5, 4, 57 + k, 12
+    seas = [(b[1], b[2]) for b in desc if b[0] == "seasonal"]
+    X, y, _, _ = general_data(T, p, 2, seas, seed=31 + k)
+    rs = np.random.Generator(np.random.PCG64(9 + k))
+    y = y + np.where(rs.uniform(size=T) < 0.1, 6.0 * rs.standard_normal(T), 0.0)   # a few outliers
+    obs = np.ones(T, np.uint8)
+    obs[miss] = 0
+    blocks = general_spec(y, desc)
+    g0 = np.zeros(p, np.uint8)
+    g0[0] = 1
+    mu, prec, pi = slab_of(p)
+
+    def make_oracle(o, chain):
+        return sso.SsStudentOracle(o, y, X, obs, blocks, mu, prec, pi, seed, chain, g0, nu_prior=nup,
+                                   sigma_max=smax)
+    return dict(T=T, p=p, chains=chains, seed=seed, rounds=rounds, X=X, y=y, obs=obs, blocks=blocks, g0=g0,
+                smax=smax, nup=nup, check=[0, chains - 1], oracle=make_oracle)
+
+
+@gpu
+@pytest.mark.parametrize("k", range(len(ROUND_CASES)))
+def test_rounds_match_restatement(oracle, k):
+    c = round_case(k)
+    eng = student_engine(c["chains"], c["seed"], c["y"], c["X"], c["obs"], c["blocks"], c["g0"],
+                         nu_prior=c["nup"], sigma_max=c["smax"])
+    ora = {ch: c["oracle"](oracle, ch) for ch in c["check"]}
+    for r in range(c["rounds"]):
+        eng.ss_student_sweep(1)   # (round 0: the start from all weights 1, two weight imputations)
+        gam, beta, sig = eng.get_states()
+        nu = eng.student_get_nu()
+        for ch, o in ora.items():
+            g, b, s2, v = o.draw()
+            tag = (k, ch, r)
+            assert np.array_equal(gam[ch], g), tag
+            assert relerr(beta[ch], b) < RTOL, tag
+            assert relerr(sig[ch], s2, 1e-300) < RTOL and relerr(nu[ch], v, 1e-300) < RTOL, tag
+            assert sig[ch] <= c["smax"] ** 2
+            assert relerr(eng.ss_student_get_weights(ch), o.w, 1e-300) < RTOL, tag
+            st = eng.ss_get_state_draw(ch)
+            assert np.max(np.abs(st - o.state)) < 1e-8 * np.abs(o.state).max(), tag
+            for j, blk in enumerate(c["blocks"]):
+                sm = eng.ss_get_state_model(ch, j)
+                nv = len(sm["variances"])
+                assert relerr(sm["variances"], o.var[j], 1e-300) < RTOL, tag + (j,)
+                assert np.array_equal(sm["suf_n"], o.suf_n[j][:nv]), tag + (j,)
+                assert relerr(sm["suf_ss"], o.suf_ss[j][:nv], 1e-300) < RTOL, tag + (j,)
+    margin = eng.student_get_margin()
+    for ch, o in ora.items():
+        assert o.margin > 1e-9 and margin[ch] > 1e-9, (ch, o.margin, margin[ch])
+    # several rounds in one call: the same draws
+    eng2 = student_engine(c["chains"], c["seed"], c["y"], c["X"], c["obs"], c["blocks"], c["g0"],
+                          nu_prior=c["nup"], sigma_max=c["smax"])
+    eng2.ss_student_sweep(c["rounds"])
+    for u, v in zip(eng.get_states(), eng2.get_states()):
+        assert np.array_equal(u, v)
+    assert np.array_equal(eng.student_get_nu(), eng2.student_get_nu())
+    assert np.array_equal(eng.ss_get_state_draw(1), eng2.ss_get_state_draw(1))
+
+
+# ---- 6. distribution ----------------------------------------------------------------------------
+@gpu
+def test_state_draws_have_the_dense_posterior_moments():
+    blocks, S, var, y, obs, w, sigsq, nu, H = sso.fixed_case()
+    T, chains = len(y), 4096
+    X = np.ones((T, 1))
+    g0 = np.zeros(1, np.uint8)
+    eng = student_engine(chains, 20262, y, X, obs.astype(np.uint8), blocks, g0)
+    eng.set_state(g0, np.zeros(1), sigsq)
+    eng.student_set_nu(nu)
+    eng.ss_student_set_weights(w)
+    eng.ss_student_impute_state()
+    draws = np.stack([eng.ss_get_state_draw(c).reshape(-1) for c in range(chains)])
+    mean, cov = sso.dense_posterior(S, var, y, obs, H)
+    d = len(mean)
+    bound = sso.bonferroni_bound(d + d * (d + 1) // 2)   # (fixed with the seed before any run)
+    zm, zc = sso.moment_z(draws, mean, cov)
+    print("largest |z|: mean %.3f covariance %.3f, bound %.3f" % (np.abs(zm).max(), np.abs(zc).max(), bound))
+    assert np.abs(zm).max() < bound
+    assert np.abs(zc).max() < bound
+
+
+# ---- 7. interface -------------------------------------------------------------------------------
+def small_problem():
+    T, p = 30, 3
+    X, y, _, _ = general_data(T, p, 1, [], seed=2)
+    return T, p, X, y, general_spec(y, [("level",)])
+
+
+def refused(fn, text):
+    import boom_amd
+    with pytest.raises(boom_amd.BoomAmdError) as e:
+        fn()
+    assert text in str(e.value), str(e.value)
+
+
+@gpu
+def test_refusals_and_their_texts():
+    import boom_amd
+    T, p, X, y, blocks = small_problem()
+    mu, prec, pi = slab_of(p)
+    g0 = np.zeros(p, np.uint8)
+    eng = boom_amd.Engine(2, seed=1)
+    # the family's calls on an engine without its data
+    refused(lambda: eng.ss_student_sweep(1), "call ba_ss_student_set_data first")
+    refused(lambda: eng.ss_student_get_weights(0), "call ba_ss_student_set_data first")
+    eng.ss_set_data(y, X, None)
+    refused(lambda: eng.ss_student_sweep(1), "call ba_ss_student_set_data first")
+    refused(lambda: eng.ss_student_impute_state(), "call ba_ss_student_set_data first")
+    refused(lambda: eng.ss_student_set_weights(np.ones(T)), "call ba_ss_student_set_data first")
+    # no state list
+    eng.ss_student_set_data(y, X, None)
+    eng.sss_set_slab(mu, prec, scales_with_sigsq=True)
+    eng.set_spike(pi)
+    eng.set_sigma_prior(1.0, 1.0)
+    refused(lambda: eng.ss_student_sweep(1), "call ba_ss_add_state_model first")
+    eng.ss_set_local_level(0.01, 0.1, 1.0, float(y[0]), 1.0, 1.0)
+    refused(lambda: eng.ss_student_sweep(1), "not ba_ss_set_local_level")
+    eng.ss_set_state_models(blocks)
+    eng.set_state(g0)
+    # sweeps of other kinds
+    for call in (lambda: eng.ss_sweep(1), lambda: eng.ss_impute_state(), lambda: eng.student_sweep(1),
+                 lambda: eng.sweep(1), lambda: eng.sss_sweep(1), lambda: eng.quantile_sweep(1)):
+        refused(call, "Student-t state-space data are set: use ba_ss_student_sweep")
+    refused(lambda: eng.ss_forecast(np.zeros((2, p))), "forecasts with Student-t observation noise are not implemented")
+    # weights
+    for bad in (-1.0, np.nan, np.inf):
+        w = np.ones(T)
+        w[4] = bad
+        refused(lambda: eng.ss_student_set_weights(w), "Weights must be finite and non-negative.")
+    # a slab that does not scale with sigma^2
+    eng.sss_set_slab(mu, prec, scales_with_sigsq=False)
+    refused(lambda: eng.ss_student_sweep(1), "scales with sigma^2 (scales_with_sigsq = 1)")
+    eng.sss_set_slab(mu, prec, scales_with_sigsq=True)
+    eng.ss_student_sweep(2)
+    assert eng.ss_get_state_draw(0).shape == (T, 1)
+
+
+@gpu
+def test_recorded_draws_and_get_state():
+    T, p, X, y, blocks = small_problem()
+    g0 = np.zeros(p, np.uint8)
+    g0[0] = 1
+    chains, seed, n = 3, 19, 6
+    a = student_engine(chains, seed, y, X, None, blocks, g0)
+    a.enable_draws(n)
+    a.ss_student_sweep(n)
+    g, b, s = a.get_draws(0, n)
+    nus = a.student_get_nu_draws(0, n)
+    b1 = student_engine(chains, seed, y, X, None, blocks, g0)
+    for r in range(n):
+        b1.ss_student_sweep(1)
+        gg, bb, ss = b1.get_state(0)
+        assert np.array_equal(g[r], gg) and np.array_equal(b[r], bb) and s[r] == ss, r
+        assert nus[r] == b1.student_get_nu(0), r
+    gg, bb, ss = a.get_state(0)
+    assert np.array_equal(g[-1], gg) and np.array_equal(b[-1], bb) and s[-1] == ss
+
+
+@gpu
+def test_pybind_classes_agree_with_the_c_abi():
+    """boom.StateSpaceStudentRegressionModel + StateSpaceStudentPosteriorSampler (the façade of
+    include/boom_amd.hpp behind them): three rounds == the engine through the C-ABI on the same
+    seed, bit for bit"""
+    import boom_amd._boom as boom
+    T, p, chains, seed = 40, 4, 3, 23
+    X, y, _, obs = general_data(T, p, 2, [(4, 1)], seed=6, missing_frac=0.05)
+    desc = [("level",), ("seasonal", 4, 1)]
+    blocks = general_spec(y, desc)
+    mu, prec, pi = slab_of(p)
+    model = boom.StateSpaceStudentRegressionModel(y, X, [bool(o) for o in obs], chains=chains, seed=seed)
+    b = blocks[0]
+    level = boom.LocalLevelStateModel(float(b["initial_sigma"][0]))
+    level.set_initial_state_mean(float(b["a0"][0]))
+    level.set_initial_state_variance(float(b["P0"][0]))
+    level.set_prior(b["df"][0], b["sigma_guess"][0], b["sigma_upper_limit"][0])
+    b = blocks[1]
+    seas = boom.SeasonalStateModel(4)
+    seas.set_sigsq(b["initial_sigma"][0] ** 2)
+    seas.set_prior(b["df"][0], b["sigma_guess"][0], b["sigma_upper_limit"][0])
+    seas.set_initial_state_mean(b["a0"])
+    seas.set_initial_state_variance(b["P0"][0])
+    model.add_state(level)
+    model.add_state(seas)
+    sampler = boom.StateSpaceStudentPosteriorSampler(model, boom.MvnGivenScalarSigma(mu, prec),
+                                                     boom.VariableSelectionPrior(pi), boom.ChisqModel(1.0, 1.0),
+                                                     boom.UniformModel(0.1, 100.0))
+    model.set_method(sampler)
+    assert model.state_dimension == 4
+    eng = student_engine(chains, seed, y, X, obs, blocks, np.zeros(p, np.uint8))
+    for _ in range(3):
+        model.sample_posterior()
+        eng.ss_student_sweep(1)
+    for u, v in zip(model.chain_states(), eng.get_states()):
+        assert np.array_equal(u, v)
+    for c in range(chains):
+        assert model.nu(c) == eng.student_get_nu(c) and model.sigsq(c) == eng.get_state(c)[2]
+        assert np.array_equal(model.weights(c), eng.ss_student_get_weights(c))
+        assert np.array_equal(model.state(c), eng.ss_get_state_draw(c).T)
