@@ -2184,6 +2184,12 @@ int ba_get_coefficient_traces(ba_engine *e, int32_t nsweeps, int32_t nvars,
         if (v >= 0) out[(c * nvars + v) * nsweeps + s] = b[(size_t)s * cap + m];
       }
     }
+    // a variable named more than once: slot[] holds its last place, the others get that path too
+    for (int v = 0; v < nvars; ++v) {
+      const int last = slot[vars[v]];
+      if (last != v)
+        std::memcpy(out + (c * nvars + v) * nsweeps, out + (c * nvars + last) * nsweeps, (size_t)nsweeps * 8);
+    }
   }
   return BA_OK;
 }

@@ -6,6 +6,7 @@
 // Poisson, Student-t, quantile and multinomial logit samplers keep every chain's own
 // V = slab precision + X'WX, built a vector at a time (the column service, xtwx_cols_kernel.hip).
 #include "engine_internal.h"
+#include "planes_sizing.h"
 
 namespace boom_amd {
 
@@ -234,11 +235,10 @@ int column_buffers(ba_engine *e) {
     HIP_TRY(e->dlogit_req.resize(2 * C * p));
     HIP_TRY(e->dlogit_cnt.resize(1));
     HIP_TRY(e->dcol_request.resize(C));
-    // the planes of one GEMM launch: at most 1 GiB, at least one request tile
-    const size_t per_req = (size_t)xtwx_cols_planes((int64_t)n) * p * 8;
-    e->logit_req_batch = (int64_t)std::min<size_t>(std::max<size_t>(((size_t)1 << 30) / per_req, 64), 32768);
-    e->logit_req_batch = std::min<int64_t>(e->logit_req_batch, (int64_t)(C * p));
-    HIP_TRY(e->dlogit_planes.resize((size_t)e->logit_req_batch * per_req / 8));
+    // the planes of one column GEMM launch: at most 1 GiB, at least one request tile; the
+    // workspace also holds the planes of the rows products, one set per chain (planes_sizing.h)
+    e->logit_req_batch = column_request_batch(C, (int64_t)n, p);
+    HIP_TRY(e->dlogit_planes.resize(column_planes_doubles(C, (int64_t)n, p)));
   }
   return BA_OK;
 }

@@ -28,6 +28,7 @@
 // that the 16 x 4 fragment reads are conflict-free.
 #include <hip/hip_runtime.h>
 #include "ktimer.h"
+#include "planes_sizing.h"
 #include <stdint.h>
 
 namespace boom_amd {
@@ -60,6 +61,7 @@ constexpr int JT = 128;       // variables per tile
 constexpr int KS = 16;        // rows per staging step
 constexpr int LDS_LD = KS + 2;
 constexpr int KCHUNK = 2048;  // rows per plane (fixed: see above)
+static_assert(KCHUNK == COLS_PLANE_ROWS, "planes_sizing.h sizes the workspace by this plane length");
 
 // GATHER: row r of the left operand is w_{c_r} o x_{g_r} (the requests); otherwise it
 // is row r of w as it stands (R rows of n: the plain product w X, e.g. X'Wz of every

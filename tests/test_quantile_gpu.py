@@ -212,6 +212,28 @@ def test_quantile_many_chains(oracle):
     check_parity(eng, ora, 10)
 
 
+def test_quantile_more_chains_than_the_request_batch(oracle):
+    """33 000 chains: more than the 32 768 requests of one column launch, so the planes workspace
+    is sized by its other user, the rows products of every chain at once (planes_sizing.h; sized
+    by the batch alone it was 232 chains short here).  The first chain, the first one past the
+    batch and the last against the restatement at the file's bars; chains 0 and 1023 bit for bit
+    those of a 1024-chain engine on the same data and seed."""
+    n, p = 64, 4
+    X, y, _ = make_data(n, p, 2, 33000)
+    mu, prec, pi = np.zeros(p), 0.1 * np.eye(p), np.full(p, 0.5)
+    g0 = np.zeros(p, np.uint8)
+    g0[:2] = 1
+    chains, seed, nsw = 33000, 93, 3
+    eng = make_engine(chains, seed, X, y, 0.4, mu, prec, pi, g0)
+    ora = {c: QuantileOracle(oracle, X, y, 0.4, mu, prec, pi, seed, c, g0) for c in (0, 32768, chains - 1)}
+    check_parity(eng, ora, nsw)
+    small = make_engine(1024, seed, X, y, 0.4, mu, prec, pi, g0)
+    small.quantile_sweep(nsw)
+    a, b = eng.get_states(), small.get_states()
+    for c in (0, 1023):
+        assert np.array_equal(a[0][c], b[0][c]) and np.array_equal(a[1][c].view(np.uint64), b[1][c].view(np.uint64)), c
+
+
 def test_quantile_chain_offset(oracle):
     """an engine whose chains are 5 and 6 of a larger run reads those chains' substreams"""
     n, p = 200, 6
