@@ -379,7 +379,7 @@ void fill_params(ba_engine *e, SsvsParams &P) {
   }
   if (e->cur_mode == 1 && student_kind(e->data_kind) && !e->student_allow_selection)
     P.max_flips = 0;   // SpikeSlabSampler::allow_model_selection(false): no indicator draws
-  if (e->cur_mode == 1 && column_service(e->data_kind) && e->dlogit_V.count) {
+  if (e->cur_mode == 1 && column_service(e->data_kind) && e->cols.V.count) {
     // BinomialLogitSpikeSlabSampler: the sampler's own shuffle, every chain's own V
     // (which moves with the latent data: factors and tables are rebuilt)
     P.mode = e->data_kind == DATA_LOGIT ? 2 : 1;   // (the Poisson, Student and quantile samplers drive the plain SpikeSlabSampler)
@@ -390,14 +390,14 @@ void fill_params(ba_engine *e, SsvsParams &P) {
       P.wss = e->dml_wss.ptr;
       if (!e->mlogit_select) P.max_flips = 0;   // MLVS::suppress_model_selection
     }
-    P.V = e->dlogit_V.ptr;
+    P.V = e->cols.V.ptr;
     P.v_chain_stride = (int64_t)e->p * e->p;
     P.model_keep = 0;
     P.table_keep = 0;
-    P.col_valid = e->dlogit_valid.ptr;
-    P.col_words = e->logit_words;
-    P.col_request = e->dcol_request.ptr;
-    P.v_diag = e->dlogit_vdiag.ptr;
+    P.col_valid = e->cols.valid.ptr;
+    P.col_words = e->cols.words;
+    P.col_request = e->cols.wanted.ptr;
+    P.v_diag = e->cols.vdiag.ptr;
   }
   if (e->cur_mode == 2) {
     // AdaptiveSpikeSlabRegressionSampler: own stream, no swap move
@@ -1562,7 +1562,7 @@ int ba_seed(ba_engine *e, uint64_t seed) {
   if (e->dpos_ada.ptr) HIP_TRY(hipMemsetAsync(e->dpos_ada.ptr, 0, C * 8, s));
   if (e->dpos_level.ptr) HIP_TRY(hipMemsetAsync(e->dpos_level.ptr, 0, C * 8, s));
   if (e->dpos_var.ptr) HIP_TRY(hipMemsetAsync(e->dpos_var.ptr, 0, C * SSG_MAX_VAR * 8, s));
-  e->probit_sweep = 0;
+  e->lat.draws = 0;
   if (e->dpos_state.ptr) HIP_TRY(hipMemsetAsync(e->dpos_state.ptr, 0, C * 8, s));
   if (e->dpos_forecast.ptr) HIP_TRY(hipMemsetAsync(e->dpos_forecast.ptr, 0, C * 8, s));
   HIP_TRY(hipStreamSynchronize(s));

@@ -10,14 +10,14 @@
 
 namespace boom_amd {
 
-// the vectors of V named by dlogit_req[0, R), in batches the planes can hold
+// the vectors of V named by cols.req[0, R), in batches the planes can hold
 int build_columns(ba_engine *e, int64_t R) {
-  const int64_t n = e->probit_n;
-  for (int64_t r0 = 0; r0 < R; r0 += e->logit_req_batch) {
-    const int64_t nr = std::min<int64_t>(e->logit_req_batch, R - r0);
-    HIP_TRY(launch_xtwx_cols(e->stream, e->dprob_X.ptr, n, e->p, e->dlogit_w.ptr,
-                             e->dlogit_req.ptr + 2 * r0, (int)nr, e->dA.ptr, e->dlogit_V.ptr,
-                             e->dlogit_valid.ptr, e->logit_words, e->dlogit_planes.ptr));
+  const int64_t n = e->lat.n;
+  for (int64_t r0 = 0; r0 < R; r0 += e->cols.batch) {
+    const int64_t nr = std::min<int64_t>(e->cols.batch, R - r0);
+    HIP_TRY(launch_xtwx_cols(e->stream, e->lat.X.ptr, n, e->p, e->lat.w.ptr,
+                             e->cols.req.ptr + 2 * r0, (int)nr, e->dA.ptr, e->cols.V.ptr,
+                             e->cols.valid.ptr, e->cols.words, e->cols.planes.ptr));
   }
   return BA_OK;
 }
@@ -28,13 +28,13 @@ int build_columns(ba_engine *e, int64_t R) {
 // same draws, now finding the vector.  *served: something was replayed (st is fresh).
 int serve_columns(ba_engine *e, std::vector<int32_t> &st, bool *served) {
   *served = false;
-  if (!column_service(e->data_kind) || !e->dcol_request.count) return BA_OK;
+  if (!column_service(e->data_kind) || !e->cols.wanted.count) return BA_OK;
   const size_t C = (size_t)e->cfg.chains;
   bool any = false;
   for (size_t c = 0; c < C; ++c) any = any || st[c] == CHAIN_NEED_COLUMN || st[c] == CHAIN_NEED_COLUMN_BIG;
   if (!any) return BA_OK;
   std::vector<int32_t> want(C), req;
-  HIP_TRY(hipMemcpy(want.data(), e->dcol_request.ptr, C * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(want.data(), e->cols.wanted.ptr, C * 4, hipMemcpyDeviceToHost));
   for (size_t c = 0; c < C; ++c) {
     if (st[c] != CHAIN_NEED_COLUMN && st[c] != CHAIN_NEED_COLUMN_BIG) continue;
     if (want[c] < 0 || want[c] >= e->p) return fail(BA_E_STATE, "a parked chain names no variable");
@@ -44,12 +44,10 @@ int serve_columns(ba_engine *e, std::vector<int32_t> &st, bool *served) {
     st[c] = (st[c] == CHAIN_NEED_COLUMN) ? CHAIN_OK : CHAIN_MODEL_TOO_LARGE;
   }
   const int64_t R = (int64_t)req.size() / 2;
-  HIP_TRY(hipMemcpyAsync(e->dlogit_req.ptr, req.data(), req.size() * 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->cols.req.ptr, req.data(), req.size() * 4, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(e->dstatus.ptr, st.data(), C * 4, hipMemcpyHostToDevice, e->stream));
   int rc = build_columns(e, R);
   if (rc) return rc;
-  e->logit_cols_requested += R;
-  ++e->logit_replays;
   SsvsParams P;
   fill_params(e, P);
   HIP_TRY(launch_sweeps(e, P, 0));   // the sweep still owed
@@ -64,20 +62,20 @@ int serve_columns(ba_engine *e, std::vector<int32_t> &st, bool *served) {
 // diagonal of X'WX).  The imputation starts over: no latent data, sweep 0.
 int upload_latent_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y,
                               const double *third, bool squared, int clt_threshold) {
-  HIP_TRY(e->dprob_X.resize((size_t)n * p));
-  HIP_TRY(e->dprob_y.resize((size_t)n));
-  if (third) HIP_TRY(e->dprob_nt.resize((size_t)n));
-  HIP_TRY(hipMemcpy(e->dprob_X.ptr, X, (size_t)n * p * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->dprob_y.ptr, y, (size_t)n * 8, hipMemcpyHostToDevice));
-  if (third) HIP_TRY(hipMemcpy(e->dprob_nt.ptr, third, (size_t)n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(e->lat.X.resize((size_t)n * p));
+  HIP_TRY(e->lat.y.resize((size_t)n));
+  if (third) HIP_TRY(e->lat.aux.resize((size_t)n));
+  HIP_TRY(hipMemcpy(e->lat.X.ptr, X, (size_t)n * p * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->lat.y.ptr, y, (size_t)n * 8, hipMemcpyHostToDevice));
+  if (third) HIP_TRY(hipMemcpy(e->lat.aux.ptr, third, (size_t)n * 8, hipMemcpyHostToDevice));
   if (squared) {
-    HIP_TRY(e->dlogit_Xsq.resize((size_t)n * p));
-    HIP_TRY(launch_square(e->stream, e->dprob_X.ptr, (size_t)n * p, e->dlogit_Xsq.ptr));
+    HIP_TRY(e->lat.Xsq.resize((size_t)n * p));
+    HIP_TRY(launch_square(e->stream, e->lat.X.ptr, (size_t)n * p, e->lat.Xsq.ptr));
   }
-  e->dprob_z.release();
-  e->probit_n = n;
-  e->probit_clt = clt_threshold;
-  e->probit_sweep = 0;
+  e->lat.z.release();
+  e->lat.n = n;
+  e->lat.clt = clt_threshold;
+  e->lat.draws = 0;
   return BA_OK;
 }
 
@@ -85,26 +83,31 @@ int upload_latent_data(ba_engine *e, int64_t n, int32_t p, const double *X, cons
 // every chain, whatever a caller left there before the data were set
 static int set_unit_sigsq(ba_engine *e) { return write_per_chain(e, e->dsigsq.ptr, -1, 1.0); }
 
-// the imputation kernels' view of the data (the probit kernel reads neither w nor the mixtures)
+// the imputation kernels' view of the data: what every family's kernel reads ...
+static void fill_latent_params(ba_engine *e, LatentParams &L) {
+  L.n = (int32_t)e->lat.n;
+  L.p = (int32_t)e->p;
+  L.chains = (int32_t)e->cfg.chains;
+  L.slot_limit = e->slot_limit;
+  L.chain_offset = e->cfg.chain_offset;
+  L.X = e->lat.X.ptr;
+  L.gamma = e->dgamma.ptr;
+  L.beta = e->dbeta.ptr;
+  L.z = e->lat.z.ptr;
+  L.w = e->lat.w.ptr;
+  L.seed_lo = (uint32_t)e->seed;
+  L.seed_hi = (uint32_t)(e->seed >> 32);
+  L.status = e->dstatus.ptr;
+}
+
+// ... and each family's own (the probit kernel reads neither w nor the mixtures)
 static void fill_probit_params(ba_engine *e, ProbitParams &Q) {
   std::memset(&Q, 0, sizeof(Q));
-  Q.n = (int32_t)e->probit_n;
-  Q.p = (int32_t)e->p;
-  Q.chains = (int32_t)e->cfg.chains;
-  Q.clt_threshold = e->probit_clt;
-  Q.slot_limit = e->slot_limit;
-  Q.chain_offset = e->cfg.chain_offset;
-  Q.X = e->dprob_X.ptr;
-  Q.y = e->dprob_y.ptr;
-  Q.ntrials = e->dprob_nt.ptr;
-  Q.gamma = e->dgamma.ptr;
-  Q.beta = e->dbeta.ptr;
-  Q.z = e->dprob_z.ptr;
-  Q.w = e->dlogit_w.ptr;
+  fill_latent_params(e, Q);
+  Q.clt_threshold = e->lat.clt;
+  Q.y = e->lat.y.ptr;
+  Q.ntrials = e->lat.aux.ptr;
   Q.xtz = e->dxty_c.ptr;
-  Q.seed_lo = (uint32_t)e->seed;
-  Q.seed_hi = (uint32_t)(e->seed >> 32);
-  Q.status = e->dstatus.ptr;
   Q.mix_off = e->dpois_off.ptr;
   Q.mix_mu = e->dpois_mu.ptr;
   Q.mix_sigma = e->dpois_sigma.ptr;
@@ -115,25 +118,13 @@ static void fill_probit_params(ba_engine *e, ProbitParams &Q) {
 
 void fill_student_params(ba_engine *e, StudentParams &T) {
   std::memset(&T, 0, sizeof(T));
-  T.n = (int32_t)e->probit_n;
-  T.p = (int32_t)e->p;
-  T.chains = (int32_t)e->cfg.chains;
-  T.slot_limit = e->slot_limit;
-  T.chain_offset = e->cfg.chain_offset;
-  T.X = e->dprob_X.ptr;
-  T.y = e->dprob_y.ptr;
-  T.gamma = e->dgamma.ptr;
-  T.beta = e->dbeta.ptr;
+  fill_latent_params(e, T);
+  T.y = e->lat.y.ptr;
   T.sigsq = e->dsigsq.ptr;
   T.nu = e->dstu_nu.ptr;
   T.dx = e->dstu_dx.ptr;
   T.margin = e->dstu_margin.ptr;
-  T.z = e->dprob_z.ptr;
-  T.w = e->dlogit_w.ptr;
   T.u = e->dstu_u.ptr;
-  T.seed_lo = (uint32_t)e->seed;
-  T.seed_hi = (uint32_t)(e->seed >> 32);
-  T.status = e->dstatus.ptr;
   T.prior_df = e->prior_df;
   T.prior_ss = e->prior_ss;
   T.sigma_max = e->sigma_max;
@@ -149,37 +140,17 @@ void fill_student_params(ba_engine *e, StudentParams &T) {
 
 static void fill_quantile_params(ba_engine *e, QuantileParams &U) {
   std::memset(&U, 0, sizeof(U));
-  U.n = (int32_t)e->probit_n;
-  U.p = (int32_t)e->p;
-  U.chains = (int32_t)e->cfg.chains;
-  U.slot_limit = e->slot_limit;
-  U.chain_offset = e->cfg.chain_offset;
-  U.X = e->dprob_X.ptr;
-  U.y = e->dprob_y.ptr;
-  U.gamma = e->dgamma.ptr;
-  U.beta = e->dbeta.ptr;
-  U.z = e->dprob_z.ptr;
-  U.w = e->dlogit_w.ptr;
+  fill_latent_params(e, U);
+  U.y = e->lat.y.ptr;
   U.shift = 1.0 - 2.0 * e->quantile_q;
-  U.seed_lo = (uint32_t)e->seed;
-  U.seed_hi = (uint32_t)(e->seed >> 32);
-  U.status = e->dstatus.ptr;
 }
 
 static void fill_mlogit_params(ba_engine *e, MlogitParams &G) {
   std::memset(&G, 0, sizeof(G));
-  G.n = (int32_t)e->mlogit_n;
+  fill_latent_params(e, G);
+  G.n = (int32_t)e->mlogit_n;   // (the subjects: the rows are lat.n = n * nchoices)
   G.nchoices = e->mlogit_choices;
-  G.p = (int32_t)e->p;
-  G.chains = (int32_t)e->cfg.chains;
-  G.slot_limit = e->slot_limit;
-  G.chain_offset = e->cfg.chain_offset;
-  G.X = e->dprob_X.ptr;
   G.y = e->dml_y.ptr;
-  G.gamma = e->dgamma.ptr;
-  G.beta = e->dbeta.ptr;
-  G.z = e->dprob_z.ptr;
-  G.w = e->dlogit_w.ptr;
   G.u = e->dml_u.ptr;
   G.wss_part = e->dml_wss_part.ptr;
   G.wss = e->dml_wss.ptr;
@@ -197,9 +168,6 @@ static void fill_mlogit_params(ba_engine *e, MlogitParams &G) {
     G.mix_logsd[c] = std::log(G.mix_sd[c]);
     G.mix_logw[c] = std::log(kWeight[c]);
   }
-  G.seed_lo = (uint32_t)e->seed;
-  G.seed_hi = (uint32_t)(e->seed >> 32);
-  G.status = e->dstatus.ptr;
 }
 
 // the Student sampler's per-chain state: nu = 30 (TRegression.cpp:35-45), suggested_dx = 1
@@ -223,22 +191,22 @@ int student_prepare(ba_engine *e) {
 // the buffers of the families whose V is every chain's own (chains x n latent responses and
 // weights, V, its diagonal, the column service's lists and planes)
 int column_buffers(ba_engine *e) {
-  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, n = (size_t)e->probit_n;
-  if (e->dprob_z.count != C * n || e->dlogit_V.count != C * p * p) {
-    HIP_TRY(e->dprob_z.resize(C * n));
-    HIP_TRY(e->dlogit_w.resize(C * n));
-    HIP_TRY(e->dlogit_V.resize(C * p * p));
+  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, n = (size_t)e->lat.n;
+  if (e->lat.z.count != C * n || e->cols.V.count != C * p * p) {
+    HIP_TRY(e->lat.z.resize(C * n));
+    HIP_TRY(e->lat.w.resize(C * n));
+    HIP_TRY(e->cols.V.resize(C * p * p));
     HIP_TRY(e->dxty_c.resize(C * p));
-    e->logit_words = (int)((p + 31) / 32);
-    HIP_TRY(e->dlogit_vdiag.resize(C * p));
-    HIP_TRY(e->dlogit_valid.resize(C * (size_t)e->logit_words));
-    HIP_TRY(e->dlogit_req.resize(2 * C * p));
-    HIP_TRY(e->dlogit_cnt.resize(1));
-    HIP_TRY(e->dcol_request.resize(C));
+    e->cols.words = (int)((p + 31) / 32);
+    HIP_TRY(e->cols.vdiag.resize(C * p));
+    HIP_TRY(e->cols.valid.resize(C * (size_t)e->cols.words));
+    HIP_TRY(e->cols.req.resize(2 * C * p));
+    HIP_TRY(e->cols.count.resize(1));
+    HIP_TRY(e->cols.wanted.resize(C));
     // the planes of one column GEMM launch: at most 1 GiB, at least one request tile; the
     // workspace also holds the planes of the rows products, one set per chain (planes_sizing.h)
-    e->logit_req_batch = column_request_batch(C, (int64_t)n, p);
-    HIP_TRY(e->dlogit_planes.resize(column_planes_doubles(C, (int64_t)n, p)));
+    e->cols.batch = column_request_batch(C, (int64_t)n, p);
+    HIP_TRY(e->cols.planes.resize(column_planes_doubles(C, (int64_t)n, p)));
   }
   return BA_OK;
 }
@@ -247,19 +215,19 @@ int column_buffers(ba_engine *e) {
 // imputation (per family), X'Wz and the diagonal, the vectors of V the sweep starts from, the
 // inclusion / coefficient draws with park-and-replay for vectors requested mid-sweep
 static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
-  const bool student = e->data_kind == DATA_STUDENT, quantile = e->data_kind == DATA_QUANTILE;
-  const bool mlogit = e->data_kind == DATA_MLOGIT;
+  const DataKind kind = e->data_kind;
+  const bool student = kind == DATA_STUDENT;
   if (!e->have_slab) return fail(BA_E_STATE, "call ba_sss_set_slab first");
   if (student && !e->sss_slab_scales)
     return fail(BA_E_INVALID, "the Student-t sampler takes a slab whose precision scales with sigma^2 (scales_with_sigsq = 1)");
-  if (quantile && e->sss_slab_scales)
+  if (kind == DATA_QUANTILE && e->sss_slab_scales)
     return fail(BA_E_INVALID, "the quantile regression sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
-  if (mlogit && e->sss_slab_scales)
+  if (kind == DATA_MLOGIT && e->sss_slab_scales)
     return fail(BA_E_INVALID, "the multinomial logit sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
   if (!student && e->sss_slab_scales) return fail(BA_E_INVALID, "the logit sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
   int rc = alloc_chain_state(e);
   if (rc) return rc;
-  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, n = (size_t)e->probit_n;
+  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, n = (size_t)e->lat.n;
   if (student) {
     rc = student_prepare(e);
     if (rc) return rc;
@@ -267,7 +235,7 @@ static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
       return fail(BA_E_INVALID, "nsweeps exceeds the enabled trace length");
     if (e->dstu_u.count != C * n) HIP_TRY(e->dstu_u.resize(C * n));
   }
-  if (mlogit) {
+  if (kind == DATA_MLOGIT) {
     const size_t nb = (size_t)((e->mlogit_n + 255) / 256);
     if (e->dml_u.count != C * n) HIP_TRY(e->dml_u.resize(C * n));
     if (e->dml_wss_part.count != C * nb) HIP_TRY(e->dml_wss_part.resize(C * nb));
@@ -295,15 +263,20 @@ static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
   HIP_TRY(e->dmodel.resize(2 * C * ssvs_scalar_layout(64).total));
   SsvsParams P;
   fill_params(e, P);
+  // the imputation kernel's parameters: the struct of the family in hand
   ProbitParams Q;
-  fill_probit_params(e, Q);
-  const int imputer = e->data_kind == DATA_POISSON ? 2 : e->logit_imputer;
   StudentParams T;
-  fill_student_params(e, T);   // (read by the Student-t launches only)
   QuantileParams U;
-  fill_quantile_params(e, U);  // (read by the quantile launch only)
   MlogitParams G;
-  fill_mlogit_params(e, G);    // (read by the multinomial logit launch only)
+  LatentParams *L;
+  switch (kind) {
+    case DATA_STUDENT: fill_student_params(e, T); L = &T; break;
+    case DATA_QUANTILE: fill_quantile_params(e, U); L = &U; break;
+    case DATA_MLOGIT: fill_mlogit_params(e, G); L = &G; break;
+    default: fill_probit_params(e, Q); L = &Q; break;   // (logit, Poisson)
+  }
+  double *const Xsq = e->lat.Xsq.ptr, *const xtz = e->dxty_c.ptr, *const vdiag = e->cols.vdiag.ptr,
+               *const planes = e->cols.planes.ptr;
   // (the draws recorded are those of the last ba_student_sweep call)
   if (student && e->trace_stride > 0) HIP_TRY(hipMemsetAsync(e->dtrace_idx.ptr, 0, C * 4, e->stream));
   // BinomialLogitSpikeSlabSampler::draw (BinomialLogitSpikeSlabSampler.cpp:50-54) /
@@ -311,29 +284,23 @@ static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
   // QuantileRegressionSpikeSlabSampler::draw (QuantileRegressionPosteriorSampler.cpp:77-91) /
   // MLVS::draw (MLVS.cpp:71-75)
   for (int i = 0; i < nsweeps; ++i) {
-    Q.sweep = T.sweep = U.sweep = G.sweep = e->probit_sweep++;
+    L->sweep = e->lat.draws++;
     // impute_latent_data: z, w, X'Wz and the diagonal of V = slab precision + X'WX ...
-    if (student)
-      HIP_TRY(launch_student_impute(e->stream, T, e->dlogit_Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->dlogit_vdiag.ptr,
-                                    e->dlogit_planes.ptr));
-    else if (quantile)
-      HIP_TRY(launch_quantile_impute(e->stream, U, e->dlogit_Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->dlogit_vdiag.ptr,
-                                     e->dlogit_planes.ptr));
-    else if (mlogit)
-      HIP_TRY(launch_mlogit_impute(e->stream, G, e->dlogit_Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->dlogit_vdiag.ptr,
-                                   e->dlogit_planes.ptr));
-    else
-      HIP_TRY(launch_logit_impute(e->stream, Q, e->dlogit_Xsq.ptr, e->dA.ptr, e->dlogit_vdiag.ptr,
-                                  e->dlogit_planes.ptr, imputer));
+    switch (kind) {
+      case DATA_STUDENT: HIP_TRY(launch_student_impute(e->stream, T, Xsq, e->dA.ptr, xtz, vdiag, planes)); break;
+      case DATA_QUANTILE: HIP_TRY(launch_quantile_impute(e->stream, U, Xsq, e->dA.ptr, xtz, vdiag, planes)); break;
+      case DATA_MLOGIT: HIP_TRY(launch_mlogit_impute(e->stream, G, Xsq, e->dA.ptr, xtz, vdiag, planes)); break;
+      case DATA_POISSON: HIP_TRY(launch_logit_impute(e->stream, Q, Xsq, e->dA.ptr, vdiag, planes, 2)); break;
+      default: HIP_TRY(launch_logit_impute(e->stream, Q, Xsq, e->dA.ptr, vdiag, planes, e->logit_imputer)); break;
+    }
     // ... and the vectors of V the sweep starts from: those of the included variables
-    HIP_TRY(launch_xtwx_cols_start(e->stream, e->dgamma.ptr, (int)C, (int)p, e->dlogit_req.ptr,
-                                   e->dlogit_cnt.ptr, e->dlogit_valid.ptr, e->logit_words));
+    HIP_TRY(launch_xtwx_cols_start(e->stream, e->dgamma.ptr, (int)C, (int)p, e->cols.req.ptr,
+                                   e->cols.count.ptr, e->cols.valid.ptr, e->cols.words));
     int32_t R = 0;
-    HIP_TRY(hipMemcpyAsync(&R, e->dlogit_cnt.ptr, 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(&R, e->cols.count.ptr, 4, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     rc = build_columns(e, R);
     if (rc) return rc;
-    e->logit_cols_built += R;
     HIP_TRY(launch_sweeps(e, P, 1));                                         // draw_model_indicators, draw_beta
     // (a chain that stopped for a missing vector of V, or outgrew the launch's
     // capacity, replays THIS sweep's draws on this sweep's latent data before the
@@ -351,6 +318,22 @@ static int logit_family_sweep(ba_engine *e, int32_t nsweeps) {
   }
   e->table_ok = false;
   e->model_ok = false;
+  return BA_OK;
+}
+
+// the sweep entry points that are nothing but the loop above on their own kind of data
+static int latent_sweep_entry(ba_engine *e, DataKind kind, int32_t nsweeps) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
+  int rc = sweep_refusal(e, kind);
+  if (rc) return rc;
+  return logit_family_sweep(e, nsweeps);
+}
+
+// the getters' refusal while `buf` does not hold `count` doubles of an imputation
+static int imputed(const ba_engine *e, const DevBuf<double> &buf, size_t count, const char *sweep_first) {
+  if (buf.count != count || e->lat.draws == 0) return fail(BA_E_STATE, sweep_first);
   return BA_OK;
 }
 
@@ -403,11 +386,11 @@ int ba_probit_sweep(ba_engine *e, int32_t nsweeps) {
   if (e->sss_slab_scales) return fail(BA_E_INVALID, "the probit sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
   rc = alloc_chain_state(e);
   if (rc) return rc;
-  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, n = (size_t)e->probit_n;
-  if (e->dprob_z.count != C * n) {
-    HIP_TRY(e->dprob_z.resize(C * n));
+  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, n = (size_t)e->lat.n;
+  if (e->lat.z.count != C * n) {
+    HIP_TRY(e->lat.z.resize(C * n));
     HIP_TRY(e->dxty_c.resize(C * p));
-    HIP_TRY(e->dlogit_planes.resize((size_t)xtwx_cols_planes((int64_t)n) * C * p));   // (split-K planes of X'z)
+    HIP_TRY(e->cols.planes.resize((size_t)xtwx_cols_planes((int64_t)n) * C * p));   // (split-K planes of X'z)
   }
   rc = set_unit_sigsq(e);
   if (rc) return rc;
@@ -422,8 +405,8 @@ int ba_probit_sweep(ba_engine *e, int32_t nsweeps) {
   fill_probit_params(e, Q);
   // BinomialProbitSpikeSlabSampler::draw (BinomialProbitSpikeSlabSampler.cpp:40-46)
   for (int i = 0; i < nsweeps; ++i) {
-    Q.sweep = e->probit_sweep++;
-    HIP_TRY(launch_probit_impute(e->stream, Q, e->dlogit_planes.ptr));   // impute_latent_data, X'z
+    Q.sweep = e->lat.draws++;
+    HIP_TRY(launch_probit_impute(e->stream, Q, e->cols.planes.ptr));   // impute_latent_data, X'z
     HIP_TRY(launch_sweeps(e, P, 1));               // draw_model_indicators, draw_beta
     // (a chain that outgrew the launch's capacity replays THIS sweep's draws on
     // this sweep's latent data before the next imputation)
@@ -473,14 +456,7 @@ int ba_logit_set_imputer(ba_engine *e, int32_t kind) {
   return BA_OK;
 }
 
-int ba_logit_sweep(ba_engine *e, int32_t nsweeps) {
-  ENGINE_PROLOGUE(e);
-  MUTATE(e);
-  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
-  int rc = sweep_refusal(e, DATA_LOGIT);
-  if (rc) return rc;
-  return logit_family_sweep(e, nsweeps);
-}
+int ba_logit_sweep(ba_engine *e, int32_t nsweeps) { return latent_sweep_entry(e, DATA_LOGIT, nsweeps); }
 
 // ------------------------ PoissonRegressionSpikeSlabSampler
 int ba_poisson_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y,
@@ -644,13 +620,10 @@ int ba_student_get_weights(ba_engine *e, int64_t chain, double *w) {
   ENGINE_PROLOGUE(e);
   if (!w) return fail(BA_E_INVALID, "null argument");
   if (e->data_kind != DATA_STUDENT) return fail(BA_E_STATE, set_data_first(DATA_STUDENT));
-  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
-  const size_t n = (size_t)e->probit_n;
-  if (e->dlogit_w.count != (size_t)e->cfg.chains * n || e->probit_sweep == 0)
-    return fail(BA_E_STATE, "no imputation has run yet: call ba_student_sweep first");
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  HIP_TRY(hipMemcpy(w, e->dlogit_w.ptr + (size_t)chain * n, n * 8, hipMemcpyDeviceToHost));
-  return BA_OK;
+  const size_t n = (size_t)e->lat.n;
+  return read_chain_row(e, chain, e->lat.w, n, w, [&] {
+    return imputed(e, e->lat.w, (size_t)e->cfg.chains * n, "no imputation has run yet: call ba_student_sweep first");
+  });
 }
 
 int ba_student_get_nu_draws(ba_engine *e, int64_t chain, int32_t nsweeps, double *out) {
@@ -698,26 +671,16 @@ int ba_quantile_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, co
   return BA_OK;
 }
 
-int ba_quantile_sweep(ba_engine *e, int32_t nsweeps) {
-  ENGINE_PROLOGUE(e);
-  MUTATE(e);
-  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
-  int rc = sweep_refusal(e, DATA_QUANTILE);
-  if (rc) return rc;
-  return logit_family_sweep(e, nsweeps);
-}
+int ba_quantile_sweep(ba_engine *e, int32_t nsweeps) { return latent_sweep_entry(e, DATA_QUANTILE, nsweeps); }
 
 int ba_quantile_get_weights(ba_engine *e, int64_t chain, double *w) {
   ENGINE_PROLOGUE(e);
   if (!w) return fail(BA_E_INVALID, "null argument");
   if (e->data_kind != DATA_QUANTILE) return fail(BA_E_STATE, set_data_first(DATA_QUANTILE));
-  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
-  const size_t n = (size_t)e->probit_n;
-  if (e->dlogit_w.count != (size_t)e->cfg.chains * n || e->probit_sweep == 0)
-    return fail(BA_E_STATE, "no imputation has run yet: call ba_quantile_sweep first");
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  HIP_TRY(hipMemcpy(w, e->dlogit_w.ptr + (size_t)chain * n, n * 8, hipMemcpyDeviceToHost));
-  return BA_OK;
+  const size_t n = (size_t)e->lat.n;
+  return read_chain_row(e, chain, e->lat.w, n, w, [&] {
+    return imputed(e, e->lat.w, (size_t)e->cfg.chains * n, "no imputation has run yet: call ba_quantile_sweep first");
+  });
 }
 
 // ------------------------ MLVS (multinomial logit spike and slab)
@@ -751,21 +714,21 @@ int ba_mlogit_set_data(ba_engine *e, int64_t n, int32_t nchoices, int32_t psub, 
     HIP_TRY(dxc.resize((size_t)N * pch));
     HIP_TRY(hipMemcpy(dxc.ptr, Xchoice, (size_t)N * pch * 8, hipMemcpyHostToDevice));
   }
-  HIP_TRY(e->dprob_X.resize((size_t)N * D));
-  HIP_TRY(e->dlogit_Xsq.resize((size_t)N * D));
-  HIP_TRY(launch_mlogit_expand(e->stream, n, nchoices, psub, pch, dxs.ptr, dxc.ptr, e->dprob_X.ptr, e->dlogit_Xsq.ptr));
+  HIP_TRY(e->lat.X.resize((size_t)N * D));
+  HIP_TRY(e->lat.Xsq.resize((size_t)N * D));
+  HIP_TRY(launch_mlogit_expand(e->stream, n, nchoices, psub, pch, dxs.ptr, dxc.ptr, e->lat.X.ptr, e->lat.Xsq.ptr));
   HIP_TRY(zero.resize((size_t)N));
   HIP_TRY(hipMemsetAsync(zero.ptr, 0, (size_t)N * 8, e->stream));
-  int rc = ba_build_suf_from_xy_device(e, N, (int32_t)D, e->dprob_X.ptr, zero.ptr);   // (dimensions and the shared buffers)
+  int rc = ba_build_suf_from_xy_device(e, N, (int32_t)D, e->lat.X.ptr, zero.ptr);   // (dimensions and the shared buffers)
   if (rc) return rc;
   HIP_TRY(e->dml_y.resize((size_t)n));
   HIP_TRY(hipMemcpy(e->dml_y.ptr, y, (size_t)n * 4, hipMemcpyHostToDevice));
-  e->dprob_z.release();
+  e->lat.z.release();
   e->dml_u.release();
   e->dml_order.release();   // (the identity until ba_mlogit_set_flip_order)
-  e->probit_n = N;
-  e->probit_clt = 0;
-  e->probit_sweep = 0;
+  e->lat.n = N;
+  e->lat.clt = 0;
+  e->lat.draws = 0;
   e->mlogit_n = n;
   e->mlogit_choices = nchoices;
   e->mlogit_psub = psub;
@@ -801,39 +764,28 @@ int ba_mlogit_allow_model_selection(ba_engine *e, int32_t allow) {
   return BA_OK;
 }
 
-int ba_mlogit_sweep(ba_engine *e, int32_t nsweeps) {
-  ENGINE_PROLOGUE(e);
-  MUTATE(e);
-  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
-  int rc = sweep_refusal(e, DATA_MLOGIT);
-  if (rc) return rc;
-  return logit_family_sweep(e, nsweeps);
-}
+int ba_mlogit_sweep(ba_engine *e, int32_t nsweeps) { return latent_sweep_entry(e, DATA_MLOGIT, nsweeps); }
 
 int ba_mlogit_get_latent(ba_engine *e, int64_t chain, double *u, double *w) {
   ENGINE_PROLOGUE(e);
   if (!u || !w) return fail(BA_E_INVALID, "null argument");
   if (e->data_kind != DATA_MLOGIT) return fail(BA_E_STATE, set_data_first(DATA_MLOGIT));
-  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
-  const size_t N = (size_t)e->probit_n;
-  if (e->dml_u.count != (size_t)e->cfg.chains * N || e->probit_sweep == 0)
-    return fail(BA_E_STATE, "no imputation has run yet: call ba_mlogit_sweep first");
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  HIP_TRY(hipMemcpy(u, e->dml_u.ptr + (size_t)chain * N, N * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(w, e->dlogit_w.ptr + (size_t)chain * N, N * 8, hipMemcpyDeviceToHost));
-  return BA_OK;
+  const size_t N = (size_t)e->lat.n;
+  auto ready = [&] {
+    return imputed(e, e->dml_u, (size_t)e->cfg.chains * N, "no imputation has run yet: call ba_mlogit_sweep first");
+  };
+  int rc = read_chain_row(e, chain, e->dml_u, N, u, ready);
+  if (rc) return rc;
+  return read_chain_row(e, chain, e->lat.w, N, w, ready);
 }
 
 int ba_mlogit_get_wss(ba_engine *e, int64_t chain, double *wss) {
   ENGINE_PROLOGUE(e);
   if (!wss) return fail(BA_E_INVALID, "null argument");
   if (e->data_kind != DATA_MLOGIT) return fail(BA_E_STATE, set_data_first(DATA_MLOGIT));
-  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
-  if (e->dml_wss.count != (size_t)e->cfg.chains || e->probit_sweep == 0)
-    return fail(BA_E_STATE, "no imputation has run yet: call ba_mlogit_sweep first");
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  HIP_TRY(hipMemcpy(wss, e->dml_wss.ptr + (size_t)chain, 8, hipMemcpyDeviceToHost));
-  return BA_OK;
+  return read_chain_row(e, chain, e->dml_wss, 1, wss, [&] {
+    return imputed(e, e->dml_wss, (size_t)e->cfg.chains, "no imputation has run yet: call ba_mlogit_sweep first");
+  });
 }
 
 }  // extern "C"

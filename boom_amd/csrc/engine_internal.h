@@ -6,6 +6,9 @@
 //   engine_glm.hip  probit, logit, Poisson, Student-t, quantile, multinomial logit (the
 //                   latent-data families)
 //   engine_ss.hip   state space: ba_ss_*, its look-ahead, the round kernel's launches
+// The launchers' declarations: of the products in products.h, of the rest below.  The
+// imputation kernels' parameters are latent_params.h (the common head) and one header per
+// family; their shared device code is latent_device.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,6 +27,7 @@
 #include "ktimer.h"
 #include "mlogit_params.h"
 #include "probit_params.h"
+#include "products.h"
 #include "quantile_params.h"
 #include "ssvs_params.h"
 #include "student_params.h"
@@ -69,21 +73,10 @@ hipError_t launch_mlogit_impute(hipStream_t stream, const MlogitParams &P, const
 hipError_t launch_logit_impute(hipStream_t stream, const ProbitParams &P, const double *Xsq,
                                const double *slab_precision, double *v_diag, double *planes,
                                int polya_gamma);
-// xtwx_cols_kernel.hip
+// xtwx_cols_kernel.hip (the products: products.h)
 hipError_t launch_ssvs_big_logp(hipStream_t stream, const SsvsParams &P, int kcap, const uint8_t *gammas,
                                 const int *which, int nwhich, double *model_ws, double *xs_ws, double *out,
                                 int *status_out);
-hipError_t launch_predict(hipStream_t stream, const double *trace_k, const uint16_t *rec_idx,
-                          const double *rec_beta, int stride, int cap, int first_draw, int ndraws,
-                          int chains, int p, const double *newX, int nnew, double *out);
-int xtwx_cols_planes(int64_t n);
-int xte_planes(int64_t n);
-hipError_t launch_xtwx_cols(hipStream_t stream, const double *X, int64_t n, int p, const double *w,
-                            const int32_t *req, int R, const double *base, double *V,
-                            uint32_t *valid, int words, double *planes);
-hipError_t launch_xtwx_cols_start(hipStream_t stream, const uint8_t *gamma, int chains, int p,
-                                  int32_t *req, int32_t *count, uint32_t *valid, int words);
-hipError_t launch_square(hipStream_t stream, const double *x, size_t count, double *out);
 hipError_t launch_kalman_simsmooth(hipStream_t stream, const SsParams &P,
                                    int draw_level);
 hipError_t launch_kalman_main(hipStream_t stream, const SsParams &P, int draw_level);
@@ -325,60 +318,61 @@ struct ba_engine {
   double level_prior_df = 0, level_prior_ss = 0;
   double level_sigma_max = std::numeric_limits<double>::infinity();
   double ss_a0 = 0, ss_P0 = 1, ss_initial_level_sigsq = 1;
-  // BinomialProbitSpikeSlabSampler (probit_kernel.hip): data on the device, the
-  // latent sums z (chains x n), imputations done so far
-  int64_t probit_n = 0;
-  int probit_clt = 5;
-  uint64_t probit_sweep = 0;
-  DevBuf<double> dprob_X, dprob_y, dprob_nt, dprob_z;
-  // BinomialLogitSpikeSlabSampler: the same buffers plus the observations' total
-  // precisions (chains x n) and every chain's own V = slab precision + X'WX
+  // ---- the latent-data families (latent_data(data_kind), engine_glm.hip; DATA_SS_STUDENT
+  // borrows the same buffers with n = T).  What every family holds:
+  struct LatentData {
+    int64_t n = 0;          // rows of X (MLVS: subjects x choices; the state space Student family: T)
+    int clt = 5;            // the binomial imputers' central-limit threshold
+    uint64_t draws = 0;     // imputations done so far (positions the imputers' substreams)
+    DevBuf<double> X, y;    // the design (n x p column-major) and the response (MLVS keeps its own, dml_y)
+    DevBuf<double> aux;     // trial counts (probit, logit) or exposures (Poisson)
+    DevBuf<double> z, w;    // chains x n: every chain's latent responses and weights (probit: z alone)
+    DevBuf<double> Xsq;     // X squared element-wise, for the diagonal of X'WX (the column service's families)
+  } lat;
+  // The column service (column_service(data_kind), xtwx_cols_kernel.hip): every chain's own
+  // V = slab precision + X'WX, built a vector at a time as the sweep asks for it.
+  struct ColumnService {
+    DevBuf<double> V, vdiag;     // chains x p x p, and the diagonals (chains x p)
+    DevBuf<double> planes;       // the split-K planes of the column and rows products (the probit sampler's X'z too)
+    DevBuf<uint32_t> valid;      // which vectors hold this sweep's values: bits, `words` words per chain
+    DevBuf<int32_t> req, count;  // the request list (chain, variable) and its length
+    DevBuf<int32_t> wanted;      // the variable a parked chain waits for
+    int words = 0;
+    int64_t batch = 0;           // requests per GEMM launch (bounds the planes)
+  } cols;
+  int slot_limit = 0;              // (ba_set_slot_limit)
+  // BinomialLogitSpikeSlabSampler
   int logit_imputer = 0;           // 0: the reference's auxiliary mixture, 1: Polya-Gamma
-  // PoissonRegressionSpikeSlabSampler: the logit path's machinery (every chain's own V a
-  // vector at a time) with its own imputation kernel and SpikeSlabSampler's shuffle;
-  // dprob_nt holds the exposures; the reference table's mixtures by count
+  // PoissonRegressionSpikeSlabSampler: its own imputation kernel and SpikeSlabSampler's shuffle;
+  // the reference table's mixtures by count
   bool poisson_mix_set = false;
   std::vector<int64_t> poisson_y;             // host copy of the counts (to map them to mixtures)
   DevBuf<int32_t> dpois_off, dpois_obs;
   DevBuf<double> dpois_mu, dpois_sigma, dpois_logw;
   int poisson_mix_one = -1;
-  // TRegressionSpikeSlabSampler (student_kernel.hip): the logit path's machinery (its
-  // column service too) with its own imputation, sigma^2 per chain and the nu draw; per chain nu,
-  // the slice sampler's suggested_dx, the smallest slice margin, the recorded nu path; the
-  // u_i = (r_i / sigma)^2 of the last draw (chains x n)
+  // TRegressionSpikeSlabSampler (student_kernel.hip): its own imputation, sigma^2 per chain and
+  // the nu draw; per chain nu, the slice sampler's suggested_dx, the smallest slice margin, the
+  // recorded nu path; the u_i = (r_i / sigma)^2 of the last draw (chains x n)
   bool student_allow_selection = true;   // (ba_student_allow_model_selection)
   int student_nu_kind = STUDENT_NU_UNIFORM;
   double student_nu_a = 0.1, student_nu_b = 100.0;
   DevBuf<double> dstu_nu, dstu_dx, dstu_margin, dstu_u, dstu_nu_rec;
   // StateSpaceStudentPosteriorSampler (DATA_SS_STUDENT): the filter's H_t = sigma^2 / w_t
-  // (chains x T); rounds done (positions the sigma^2 / nu substream; probit_sweep counts the
+  // (chains x T); rounds done (positions the sigma^2 / nu substream; lat.draws counts the
   // weight imputations); the weights and statistics in hand are those of a state draw
   DevBuf<double> dsst_h;
   uint64_t sst_round = 0;
   bool sst_ready = false;
-  // QuantileRegressionSpikeSlabSampler (quantile_kernel.hip): the Poisson path with its own
-  // imputation; the model's quantile
+  // QuantileRegressionSpikeSlabSampler (quantile_kernel.hip): the model's quantile
   double quantile_q = 0.5;
-  // MLVS (mlogit_kernel.hip): the Poisson path on the expanded design (N = n M rows, D columns;
-  // probit_n = N, p = D) with its own imputation and the sweep's mode 3
+  // MLVS (mlogit_kernel.hip): the expanded design (lat.n = N = n M rows, p = D columns), its
+  // own imputation and the sweep's mode 3
   int64_t mlogit_n = 0;
   int32_t mlogit_choices = 0, mlogit_psub = 0, mlogit_pch = 0;
   bool mlogit_select = true;       // (ba_mlogit_allow_model_selection)
   DevBuf<int32_t> dml_y;
   DevBuf<uint16_t> dml_order;      // the sweep's visiting order, D entries
   DevBuf<double> dml_u, dml_wss_part, dml_wss;
-  int slot_limit = 0;              // (ba_set_slot_limit)
-  DevBuf<double> dlogit_w, dlogit_V;
-  // ... V built a vector at a time (xtwx_cols_kernel.hip): the squared design matrix
-  // (for the diagonal), the diagonals (chains x p), which vectors hold this sweep's
-  // values (bits, logit_words words per chain), the request list (chain, variable) and
-  // its length, the variable a parked chain waits for, the GEMM's split-K planes
-  DevBuf<double> dlogit_Xsq, dlogit_vdiag, dlogit_planes;
-  DevBuf<uint32_t> dlogit_valid;
-  DevBuf<int32_t> dlogit_req, dlogit_cnt, dcol_request;
-  int logit_words = 0;
-  int64_t logit_req_batch = 0;     // requests per GEMM launch (bounds the planes)
-  int64_t logit_cols_built = 0, logit_cols_requested = 0, logit_replays = 0;   // (diagnostics)
   // structural state (a list of state models, ssm_kernel.hip) instead of the local level
   bool ssm_set = false;
   SsgSpec ssg{};                   // the host's copy of the specification
@@ -469,6 +463,18 @@ const char *set_data_first(DataKind wants);   // "call ba_<family>_set_data firs
 // wait for the stream first
 int write_per_chain(ba_engine *e, double *dev, int64_t chain, double value);
 int read_per_chain(ba_engine *e, const double *dev, int64_t chain, double *out);
+// One chain's row of a chains x n buffer to the host, for the getters of weights and latent
+// data: validates `chain`, lets `ready` refuse or prepare (BA_OK to go on), waits for the
+// stream and copies.
+template <class Ready>
+int read_chain_row(ba_engine *e, int64_t chain, const DevBuf<double> &buf, size_t n, double *out, Ready ready) {
+  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  int rc = ready();
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(out, buf.ptr + (size_t)chain * n, n * 8, hipMemcpyDeviceToHost));
+  return BA_OK;
+}
 // engine_glm.hip
 int serve_columns(ba_engine *e, std::vector<int32_t> &st, bool *served);
 int student_prepare(ba_engine *e);

@@ -1536,7 +1536,7 @@ static int sst_buffers(ba_engine *e) {
   int rc = student_prepare(e);
   if (rc) return rc;
   const size_t C = (size_t)e->cfg.chains, T = (size_t)e->T;
-  const bool fresh = e->dlogit_w.count != C * T || e->dsst_h.count != C * T;
+  const bool fresh = e->lat.w.count != C * T || e->dsst_h.count != C * T;
   rc = column_buffers(e);
   if (rc) return rc;
   if (e->dstu_u.count != C * T) HIP_TRY(e->dstu_u.resize(C * T));
@@ -1544,7 +1544,7 @@ static int sst_buffers(ba_engine *e) {
     HIP_TRY(e->dsst_h.resize(C * T));
     std::vector<double> one(C * T, 1.0);
     HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(e->dlogit_w.ptr, one.data(), C * T * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->lat.w.ptr, one.data(), C * T * 8, hipMemcpyHostToDevice));
     e->sst_ready = false;
   }
   return BA_OK;
@@ -1586,8 +1586,8 @@ static void fill_sst_params(ba_engine *e, SsParams &S, StudentParams &U) {
 static int sst_impute_state(ba_engine *e, const SsParams &S, const StudentParams &U, int draw) {
   HIP_TRY(launch_student_ss_weights(e->stream, U, 0));
   HIP_TRY(launch_ssm_simsmooth(e->stream, S, draw));
-  HIP_TRY(launch_student_ss_suf(e->stream, U, e->dlogit_Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->dlogit_vdiag.ptr,
-                                e->dlogit_planes.ptr));
+  HIP_TRY(launch_student_ss_suf(e->stream, U, e->lat.Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->cols.vdiag.ptr,
+                                e->cols.planes.ptr));
   e->ss_initialized = true;
   e->sst_ready = true;
   return BA_OK;
@@ -1617,7 +1617,7 @@ int ba_ss_student_set_data(ba_engine *e, int32_t T, int32_t p, const double *y, 
   e->dstu_nu.release();
   e->dstu_dx.release();
   e->dstu_margin.release();
-  e->dlogit_w.release();
+  e->lat.w.release();
   e->dsst_h.release();
   e->sst_round = 0;
   e->sst_ready = false;
@@ -1629,13 +1629,7 @@ int ba_ss_student_get_weights(ba_engine *e, int64_t chain, double *w) {
   ENGINE_PROLOGUE(e);
   if (!w) return fail(BA_E_INVALID, "null argument");
   if (e->data_kind != DATA_SS_STUDENT) return fail(BA_E_STATE, set_data_first(DATA_SS_STUDENT));
-  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
-  int rc = sst_buffers(e);
-  if (rc) return rc;
-  const size_t T = (size_t)e->T;
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  HIP_TRY(hipMemcpy(w, e->dlogit_w.ptr + (size_t)chain * T, T * 8, hipMemcpyDeviceToHost));
-  return BA_OK;
+  return read_chain_row(e, chain, e->lat.w, (size_t)e->T, w, [&] { return sst_buffers(e); });
 }
 
 int ba_ss_student_set_weights(ba_engine *e, int64_t chain, const double *w) {
@@ -1651,7 +1645,7 @@ int ba_ss_student_set_weights(ba_engine *e, int64_t chain, const double *w) {
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));
   for (size_t c = chain < 0 ? 0 : (size_t)chain; c < (chain < 0 ? C : (size_t)chain + 1); ++c)
-    HIP_TRY(hipMemcpy(e->dlogit_w.ptr + c * T, w, T * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->lat.w.ptr + c * T, w, T * 8, hipMemcpyHostToDevice));
   e->sst_ready = false;   // (the statistics in hand are not these weights': the next call draws the state first)
   return BA_OK;
 }
@@ -1703,8 +1697,8 @@ int ba_ss_student_sweep(ba_engine *e, int32_t nsweeps) {
     if (rc) return rc;
     if (first) {
       StudentParams W = U;
-      W.w = e->dprob_z.ptr;
-      W.sweep = e->probit_sweep++;
+      W.w = e->lat.z.ptr;
+      W.sweep = e->lat.draws++;
       HIP_TRY(launch_student_ss_weights(e->stream, W, 1));
     }
   }
@@ -1712,14 +1706,13 @@ int ba_ss_student_sweep(ba_engine *e, int32_t nsweeps) {
     // 1. the observation model's sampler with fix_latent_data(true)
     // (TRegressionSpikeSlabSampler::draw, TRegressionSpikeSlabSampler.cpp:41-47): indicators and
     // beta on the statistics of the last impute_state ...
-    HIP_TRY(launch_xtwx_cols_start(e->stream, e->dgamma.ptr, (int)C, (int)p, e->dlogit_req.ptr, e->dlogit_cnt.ptr,
-                                   e->dlogit_valid.ptr, e->logit_words));
+    HIP_TRY(launch_xtwx_cols_start(e->stream, e->dgamma.ptr, (int)C, (int)p, e->cols.req.ptr, e->cols.count.ptr,
+                                   e->cols.valid.ptr, e->cols.words));
     int32_t R = 0;
-    HIP_TRY(hipMemcpyAsync(&R, e->dlogit_cnt.ptr, 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(&R, e->cols.count.ptr, 4, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     rc = build_columns(e, R);
     if (rc) return rc;
-    e->logit_cols_built += R;
     HIP_TRY(launch_sweeps(e, P, 1));
     HIP_TRY(hipStreamSynchronize(e->stream));
     rc = check_chain_status(e);   // (park-and-replay for vectors of V asked for mid-sweep)
@@ -1730,12 +1723,12 @@ int ba_ss_student_sweep(ba_engine *e, int32_t nsweeps) {
     // 3. - 5. impute_nonstate_latent_data, then the state models' samplers and impute_state (one
     // kernel: the samplers read their own streams and the statistics of the last state draw, so
     // their place before or after the weights does not show)
-    U.sweep = e->probit_sweep++;
+    U.sweep = e->lat.draws++;
     HIP_TRY(launch_student_ss_weights(e->stream, U, 1));
     HIP_TRY(launch_ssm_simsmooth(e->stream, S, 1));
     // 6. the complete-data statistics of the next round's observation draw
-    HIP_TRY(launch_student_ss_suf(e->stream, U, e->dlogit_Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->dlogit_vdiag.ptr,
-                                  e->dlogit_planes.ptr));
+    HIP_TRY(launch_student_ss_suf(e->stream, U, e->lat.Xsq.ptr, e->dA.ptr, e->dxty_c.ptr, e->cols.vdiag.ptr,
+                                  e->cols.planes.ptr));
     fill_params(e, P);
   }
   e->table_ok = false;

@@ -35,6 +35,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ktimer.h"
+#include "products.h"
 
 #include "kalman_lm_device.h"
 
@@ -673,9 +674,6 @@ hipError_t launch_ss_forecast(hipStream_t stream, const SsParams &P, int horizon
                      pos_forecast, out);
   return hipGetLastError();
 }
-
-hipError_t launch_xte_tiled(hipStream_t stream, const double *U, int64_t ldu, int R, const double *B, int64_t n,
-                            int p, double *out, double *planes);
 
 hipError_t launch_kalman_prepare(hipStream_t stream, const SsParams &P, int draw_level) {
   KtScope kt(stream, KT_KALMAN_PREPARE);

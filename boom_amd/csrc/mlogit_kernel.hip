@@ -29,46 +29,14 @@
 #include "ktimer.h"
 
 #include "device_rng.h"
+#include "latent_device.h"
 #include "mlogit_params.h"
+#include "products.h"
 #include "ssvs_params.h"
 
 namespace boom_amd {
 
 namespace {
-
-__device__ __forceinline__ uint32_t ml_serve(const MlogitParams &P, uint32_t stride) {
-  return (P.slot_limit > 0 && (uint32_t)P.slot_limit < stride) ? (uint32_t)P.slot_limit : stride;
-}
-
-// the chain's included variables and their coefficients, in index order, into LDS (256 threads)
-__device__ __forceinline__ int ml_included(const MlogitParams &P, int chain, int *s_idx, double *s_beta) {
-  __shared__ int s_wave_count[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint8_t *g = P.gamma + (size_t)chain * P.p;
-  const double *b = P.beta + (size_t)chain * P.p;
-  int base = 0;
-  for (int j0 = 0; j0 < P.p; j0 += 256) {
-    const int j = j0 + tid;
-    const bool inc = j < P.p && g[j] != 0;
-    const unsigned long long m = __ballot(inc);
-    if (lane == 0) s_wave_count[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const int c = s_wave_count[w];
-      before += (w < wave) ? c : 0;
-      total += c;
-    }
-    if (inc) {
-      const int pos = base + before + __popcll(m & ((1ull << lane) - 1ull));
-      if (pos < MLOGIT_KMAX) { s_idx[pos] = j; s_beta[pos] = b[j]; }
-    }
-    base += total;
-    __syncthreads();
-  }
-  return base;
-}
 
 // rlexp_mt: log(-log(U)) - loglam, U redrawn while the double logarithm is not finite (the
 // reference has no bound on the redraws; 32 in a row do not happen -- *bad if they do)
@@ -147,7 +115,7 @@ __global__ __launch_bounds__(256) void mlogit_impute_kernel(MlogitParams P) {
   if (s_status != CHAIN_OK) return;
   __shared__ int s_idx[MLOGIT_KMAX];
   __shared__ double s_beta[MLOGIT_KMAX];
-  const int k = ml_included(P, chain, s_idx, s_beta);
+  const int k = included_coefficients<MLOGIT_KMAX>(P.gamma, P.beta, P.p, chain, s_idx, s_beta);
   if (k > MLOGIT_KMAX) {
     if (threadIdx.x == 0 && blockIdx.x == 0) P.status[chain] = CHAIN_MODEL_TOO_LARGE;
     return;
@@ -186,7 +154,7 @@ __global__ __launch_bounds__(256) void mlogit_impute_kernel(MlogitParams P) {
       if (m < M) bad = bad || !isfinite(eta[m]);
     SeqRng rng = SeqRng::slot(PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), MLOGIT_IMPUTE_STREAM},
                               P.sweep * (uint64_t)P.n + (uint64_t)i, MLOGIT_IMPUTE_STRIDE,
-                              ml_serve(P, MLOGIT_IMPUTE_STRIDE));
+                              slot_serve(P.slot_limit, MLOGIT_IMPUTE_STRIDE));
     double logzmin = 0.0;
     if (!bad) logzmin = ml_rlexp(rng, loglam, &bad);
     double *wo = P.w + (size_t)chain * N + row0, *zo = P.z + (size_t)chain * N + row0,
@@ -239,9 +207,6 @@ __global__ __launch_bounds__(256) void mlogit_wss_kernel(MlogitParams P, int nbl
   P.wss[chain] = a;
 }
 
-hipError_t launch_rows_times_columns(hipStream_t stream, const double *U, int R, const double *B, int64_t n,
-                                     int p, const double *diag_base, double *out, double *planes);
-
 hipError_t launch_mlogit_expand(hipStream_t stream, int64_t n, int M, int psub, int pch, const double *Xs,
                                 const double *Xc, double *X, double *Xsq) {
   const int64_t total = n * M * ((int64_t)(M - 1) * psub + pch);
@@ -266,9 +231,8 @@ hipError_t launch_mlogit_impute(hipStream_t stream, const MlogitParams &P, const
   }
   if (err != hipSuccess) return err;
   const int64_t N = (int64_t)P.n * P.nchoices;
-  err = launch_rows_times_columns(stream, P.z, P.chains, P.X, N, P.p, nullptr, xtz, planes);
-  if (err != hipSuccess) return err;
-  return launch_rows_times_columns(stream, P.w, P.chains, Xsq, N, P.p, slab_precision, v_diag, planes);
+  return launch_latent_products(stream, P.z, P.w, P.chains, P.X, Xsq, N, P.p, slab_precision, xtz, v_diag,
+                                planes);
 }
 
 }  // namespace boom_amd

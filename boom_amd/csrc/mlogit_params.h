@@ -3,6 +3,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "latent_params.h"
+
 namespace boom_amd {
 
 // Substream of MLVS:
@@ -17,15 +19,12 @@ enum { MLOGIT_IMPUTE_STRIDE = 64, MLOGIT_KMAX = 1024, MLOGIT_MAX_CHOICES = 16, M
 // status word
 enum { MLOGIT_IMPUTE_ERROR = 11 };
 
-struct MlogitParams {
-  int32_t n, nchoices, p, chains, slot_limit;   // p = D = (M - 1) psub + pch columns
-  int64_t chain_offset;
-  const double *X;        // N x D column-major, N = n M, row i M + m (ChoiceData::write_x(false))
+// n is the number of SUBJECTS: the rows of X, z, w and u are N = n * nchoices (row i M + m,
+// ChoiceData::write_x(false)), p = D = (M - 1) psub + pch columns.  z: w u; w: sigsq_inv of the
+// drawn mixture component.
+struct MlogitParams : LatentParams {
+  int32_t nchoices;
   const int32_t *y;       // n, 0 .. M - 1
-  const uint8_t *gamma;   // chains x D
-  const double *beta;     // chains x D
-  double *z;              // chains x N: w u
-  double *w;              // chains x N: sigsq_inv of the drawn mixture component
   double *u;              // chains x N: the utilities less the component's mean
   double *wss_part;       // chains x blocks: the workgroups' shares of sum w u^2
   double *wss;            // chains: their sum in block order
@@ -33,9 +32,6 @@ struct MlogitParams {
   // the constructor there derives it: mu_, sd_, sigsq_inv_, log_mixing_weights_ plus log(sd_)
   double mix_mu[MLOGIT_NCOMP], mix_sd[MLOGIT_NCOMP], mix_prec[MLOGIT_NCOMP], mix_logw[MLOGIT_NCOMP],
       mix_logsd[MLOGIT_NCOMP];
-  uint32_t seed_lo, seed_hi;
-  uint64_t sweep;         // draws done so far (positions the substream)
-  int32_t *status;
 };
 
 }  // namespace boom_amd

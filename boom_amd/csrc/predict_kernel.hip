@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "products.h"
+
 namespace boom_amd {
 
 // grid = (ceil(nnew / 256), ndraws, chains).  out[chain][draw][i] = sum_m beta_m

@@ -24,17 +24,14 @@
 #include "ktimer.h"
 
 #include "device_rng.h"
+#include "latent_device.h"
 #include "probit_params.h"
+#include "products.h"
 
 namespace boom_amd {
 
 namespace {
 
-// how many uniforms a slot of an imputer's substream hands out before the draw goes on in the
-// spill stream (device_rng.h): the whole stride, or what ba_set_slot_limit asked for (tests)
-__device__ __forceinline__ uint32_t slot_serve(const ProbitParams &P, uint32_t stride) {
-  return (P.slot_limit > 0 && (uint32_t)P.slot_limit < stride) ? (uint32_t)P.slot_limit : stride;
-}
 // TnSampler (Samplers/TnSampler.cpp): bounded adaptive rejection for a standard normal given
 // x > a, a > 0 (logf = -x^2 / 2).  The hull's points are x_0 = a < x_1 < ...; after every
 // rejected candidate the reference recomputes all knots and all segment integrals
@@ -291,40 +288,6 @@ __device__ __forceinline__ void d_rmultinom9(SeqRng &rng, int n, const double (&
   rN[8] = n;
 }
 
-// The chain's included variables and their coefficients, in ascending order (the
-// order x_i'beta is summed in), to LDS; returns how many there are (beyond
-// PROBIT_KMAX only counted).  All 256 threads: 256 variables per round, a
-// variable's place = included ones in earlier rounds + earlier waves + earlier lanes.
-__device__ __forceinline__ int included_coefficients(const ProbitParams &P, int chain, int *s_idx,
-                                                     double *s_beta) {
-  __shared__ int s_wave_count[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint8_t *g = P.gamma + (size_t)chain * P.p;
-  const double *b = P.beta + (size_t)chain * P.p;
-  int base = 0;
-  for (int j0 = 0; j0 < P.p; j0 += 256) {
-    const int j = j0 + tid;
-    const bool inc = j < P.p && g[j] != 0;
-    const unsigned long long m = __ballot(inc);
-    if (lane == 0) s_wave_count[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const int c = s_wave_count[w];
-      before += (w < wave) ? c : 0;
-      total += c;
-    }
-    if (inc) {
-      const int pos = base + before + __popcll(m & ((1ull << lane) - 1ull));
-      if (pos < PROBIT_KMAX) { s_idx[pos] = j; s_beta[pos] = b[j]; }
-    }
-    base += total;
-    __syncthreads();
-  }
-  return base;
-}
-
 }  // namespace
 
 // One observation's latent sum (BinomialProbitDataImputer::impute, .cpp:30-73).  ARS false:
@@ -333,7 +296,8 @@ template <bool ARS>
 __device__ __forceinline__ double probit_impute_one(const ProbitParams &P, int chain, int i, double eta, long nt,
                                                     long y, const TnHull &H, bool *overflow, bool *bad) {
   SeqRng rng = SeqRng::slot(PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), 8u},
-                            P.sweep * (uint64_t)P.n + (uint64_t)i, PROBIT_STRIDE, slot_serve(P, PROBIT_STRIDE));
+                            P.sweep * (uint64_t)P.n + (uint64_t)i, PROBIT_STRIDE,
+                            slot_serve(P.slot_limit, PROBIT_STRIDE));
   double mean, variance, ans = 0.0;
   if (y > P.clt_threshold) {
     trun_norm_moments(eta, true, &mean, &variance);
@@ -389,7 +353,7 @@ __global__ __launch_bounds__(256) void probit_impute_kernel(ProbitParams P) {
   double *s_hull = reinterpret_cast<double *>(s_mem);
   double *s_big = s_hull + 3 * TN_LDS_CAP * TN_SLOTS;
   if (threadIdx.x == 0) { s_nqueue = 0; s_nnear = 0; s_nagain = 0; }
-  const int k = included_coefficients(P, chain, s_idx, s_beta);
+  const int k = included_coefficients<PROBIT_KMAX>(P.gamma, P.beta, P.p, chain, s_idx, s_beta);
   if (k > PROBIT_KMAX) {
     if (threadIdx.x == 0 && blockIdx.x == 0) P.status[chain] = CHAIN_MODEL_TOO_LARGE;
     return;
@@ -412,12 +376,13 @@ __global__ __launch_bounds__(256) void probit_impute_kernel(ProbitParams P) {
       // for its unluckiest lane: an observation that meets one goes to the queue and is done
       // from its first draw there (the stream is positional: the same numbers)
       SeqRng rng = SeqRng::slot(PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), 8u},
-                                P.sweep * (uint64_t)P.n + (uint64_t)i, PROBIT_STRIDE, slot_serve(P, PROBIT_STRIDE));
+                                P.sweep * (uint64_t)P.n + (uint64_t)i, PROBIT_STRIDE,
+                                slot_serve(P.slot_limit, PROBIT_STRIDE));
       const bool gt = y == 1;
       const double cut = gt ? 0.0 - eta : eta - 0.0;   // (rtrun_norm: a - mu / mu - a)
       // (ONE candidate: a second and third straight-line try settle another tenth of the
       // observations and measured no gain -- 5.96 vs 5.89 ms per round)
-      for (int c = 0; c < 1 && slot_serve(P, PROBIT_STRIDE) >= 2; ++c) {
+      for (int c = 0; c < 1 && slot_serve(P.slot_limit, PROBIT_STRIDE) >= 2; ++c) {
         const double u1 = rng();
         if (!(u1 < 0.884070402298758)) break;
         const double u2 = rng();
@@ -514,7 +479,7 @@ __global__ __launch_bounds__(256) void logit_impute_kernel(ProbitParams P) {
   if (s_status != CHAIN_OK) return;
   __shared__ int s_idx[PROBIT_KMAX];
   __shared__ double s_beta[PROBIT_KMAX];
-  const int k = included_coefficients(P, chain, s_idx, s_beta);
+  const int k = included_coefficients<PROBIT_KMAX>(P.gamma, P.beta, P.p, chain, s_idx, s_beta);
   if (k > PROBIT_KMAX) {
     if (threadIdx.x == 0 && blockIdx.x == 0) P.status[chain] = CHAIN_MODEL_TOO_LARGE;
     return;
@@ -524,7 +489,7 @@ __global__ __launch_bounds__(256) void logit_impute_kernel(ProbitParams P) {
   for (int m = 0; m < k; ++m) eta += P.X[(size_t)s_idx[m] * P.n + i] * s_beta[m];
   const long nt = lround(P.ntrials[i]), ys = lround(P.y[i]);
   SeqRng rng = SeqRng::slot(PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), 9u},
-                            P.sweep * (uint64_t)P.n + (uint64_t)i, LOGIT_STRIDE, slot_serve(P, LOGIT_STRIDE));
+                            P.sweep * (uint64_t)P.n + (uint64_t)i, LOGIT_STRIDE, slot_serve(P.slot_limit, LOGIT_STRIDE));
   double sum = 0.0, info = 0.0;
   if (nt > P.clt_threshold) {
     // BinomialLogitCltDataImputer::impute_large_sample (BinomialLogitDataImputer.cpp:
@@ -696,7 +661,7 @@ __global__ __launch_bounds__(256) void logit_pg_impute_kernel(ProbitParams P) {
   if (s_status != CHAIN_OK) return;
   __shared__ int s_idx[PROBIT_KMAX];
   __shared__ double s_beta[PROBIT_KMAX];
-  const int k = included_coefficients(P, chain, s_idx, s_beta);
+  const int k = included_coefficients<PROBIT_KMAX>(P.gamma, P.beta, P.p, chain, s_idx, s_beta);
   if (k > PROBIT_KMAX) {
     if (threadIdx.x == 0 && blockIdx.x == 0) P.status[chain] = CHAIN_MODEL_TOO_LARGE;
     return;
@@ -706,7 +671,7 @@ __global__ __launch_bounds__(256) void logit_pg_impute_kernel(ProbitParams P) {
   for (int m = 0; m < k; ++m) eta += P.X[(size_t)s_idx[m] * P.n + i] * s_beta[m];
   const long nt = lround(P.ntrials[i]), ys = lround(P.y[i]);
   SeqRng rng = SeqRng::slot(PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), 10u},
-                            P.sweep * (uint64_t)P.n + (uint64_t)i, PG_STRIDE, slot_serve(P, PG_STRIDE));
+                            P.sweep * (uint64_t)P.n + (uint64_t)i, PG_STRIDE, slot_serve(P.slot_limit, PG_STRIDE));
   int bad = 0;
   double omega = 0.0;
   if (nt > P.clt_threshold) {
@@ -824,7 +789,7 @@ __global__ __launch_bounds__(256) void poisson_impute_kernel(ProbitParams P) {
   if (s_status != CHAIN_OK) return;
   __shared__ int s_idx[PROBIT_KMAX];
   __shared__ double s_beta[PROBIT_KMAX];
-  const int k = included_coefficients(P, chain, s_idx, s_beta);
+  const int k = included_coefficients<PROBIT_KMAX>(P.gamma, P.beta, P.p, chain, s_idx, s_beta);
   if (k > PROBIT_KMAX) {
     if (threadIdx.x == 0 && blockIdx.x == 0) P.status[chain] = CHAIN_MODEL_TOO_LARGE;
     return;
@@ -835,7 +800,7 @@ __global__ __launch_bounds__(256) void poisson_impute_kernel(ProbitParams P) {
   const long long y = llround(P.y[i]);
   const double exposure = P.ntrials[i];
   SeqRng rng = SeqRng::slot(PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), 11u},
-                            P.sweep * (uint64_t)P.n + (uint64_t)i, POISSON_STRIDE, slot_serve(P, POISSON_STRIDE));
+                            P.sweep * (uint64_t)P.n + (uint64_t)i, POISSON_STRIDE, slot_serve(P.slot_limit, POISSON_STRIDE));
   int bad = 0;
   const double t_final = y > 0 ? exposure * d_rbeta_a_1(rng, (double)y) : 0.0;
   const double delta = exposure - t_final;
@@ -873,9 +838,6 @@ __global__ __launch_bounds__(256) void poisson_impute_kernel(ProbitParams P) {
   P.w[(size_t)chain * P.n + i] = info;
 }
 
-hipError_t launch_rows_times_columns(hipStream_t stream, const double *U, int R, const double *B, int64_t n,
-                                     int p, const double *diag_base, double *out, double *planes);
-
 // impute + X'z for every chain
 hipError_t launch_probit_impute(hipStream_t stream, const ProbitParams &P, double *planes) {
   hipError_t err;
@@ -906,9 +868,8 @@ hipError_t launch_logit_impute(hipStream_t stream, const ProbitParams &P, const 
     err = hipGetLastError();
   }
   if (err != hipSuccess) return err;
-  err = launch_rows_times_columns(stream, P.z, P.chains, P.X, (int64_t)P.n, P.p, nullptr, P.xtz, planes);
-  if (err != hipSuccess) return err;
-  return launch_rows_times_columns(stream, P.w, P.chains, Xsq, (int64_t)P.n, P.p, slab_precision, v_diag, planes);
+  return launch_latent_products(stream, P.z, P.w, P.chains, P.X, Xsq, (int64_t)P.n, P.p, slab_precision, P.xtz, v_diag,
+                                planes);
 }
 
 }  // namespace boom_amd

@@ -25,48 +25,12 @@
 #include "ktimer.h"
 
 #include "device_rng.h"
+#include "latent_device.h"
+#include "products.h"
 #include "quantile_params.h"
 #include "ssvs_params.h"
 
 namespace boom_amd {
-
-namespace {
-
-__device__ __forceinline__ uint32_t qr_serve(const QuantileParams &P, uint32_t stride) {
-  return (P.slot_limit > 0 && (uint32_t)P.slot_limit < stride) ? (uint32_t)P.slot_limit : stride;
-}
-
-// the chain's included variables and their coefficients, in index order, into LDS (256 threads)
-__device__ __forceinline__ int qr_included(const QuantileParams &P, int chain, int *s_idx, double *s_beta) {
-  __shared__ int s_wave_count[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint8_t *g = P.gamma + (size_t)chain * P.p;
-  const double *b = P.beta + (size_t)chain * P.p;
-  int base = 0;
-  for (int j0 = 0; j0 < P.p; j0 += 256) {
-    const int j = j0 + tid;
-    const bool inc = j < P.p && g[j] != 0;
-    const unsigned long long m = __ballot(inc);
-    if (lane == 0) s_wave_count[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const int c = s_wave_count[w];
-      before += (w < wave) ? c : 0;
-      total += c;
-    }
-    if (inc) {
-      const int pos = base + before + __popcll(m & ((1ull << lane) - 1ull));
-      if (pos < QUANTILE_KMAX) { s_idx[pos] = j; s_beta[pos] = b[j]; }
-    }
-    base += total;
-    __syncthreads();
-  }
-  return base;
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(256) void quantile_impute_kernel(QuantileParams P) {
   const int chain = (int)blockIdx.y, i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -76,7 +40,7 @@ __global__ __launch_bounds__(256) void quantile_impute_kernel(QuantileParams P) 
   if (s_status != CHAIN_OK) return;
   __shared__ int s_idx[QUANTILE_KMAX];
   __shared__ double s_beta[QUANTILE_KMAX];
-  const int k = qr_included(P, chain, s_idx, s_beta);
+  const int k = included_coefficients<QUANTILE_KMAX>(P.gamma, P.beta, P.p, chain, s_idx, s_beta);
   if (k > QUANTILE_KMAX) {
     if (threadIdx.x == 0 && blockIdx.x == 0) P.status[chain] = CHAIN_MODEL_TOO_LARGE;
     return;
@@ -91,7 +55,7 @@ __global__ __launch_bounds__(256) void quantile_impute_kernel(QuantileParams P) 
   if (r > 0.0 && isfinite(mu)) {
     SeqRng rng = SeqRng::slot(PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), QUANTILE_IMPUTE_STREAM},
                               P.sweep * (uint64_t)P.n + (uint64_t)i, QUANTILE_IMPUTE_STRIDE,
-                              qr_serve(P, QUANTILE_IMPUTE_STRIDE));
+                              slot_serve(P.slot_limit, QUANTILE_IMPUTE_STRIDE));
     // rig_mt(rng, mu, 1.0) with the smaller root in its stable form
     const double nz = d_norm_rand(rng);
     const double yy = nz * nz;
@@ -112,9 +76,6 @@ __global__ __launch_bounds__(256) void quantile_impute_kernel(QuantileParams P) 
   P.z[(size_t)chain * P.n + i] = z;
 }
 
-hipError_t launch_rows_times_columns(hipStream_t stream, const double *U, int R, const double *B, int64_t n,
-                                     int p, const double *diag_base, double *out, double *planes);
-
 // impute, X'Wz and the diagonal of V = slab precision + X'WX for every chain
 hipError_t launch_quantile_impute(hipStream_t stream, const QuantileParams &P, const double *Xsq,
                                   const double *slab_precision, double *xtz, double *v_diag, double *planes) {
@@ -125,9 +86,8 @@ hipError_t launch_quantile_impute(hipStream_t stream, const QuantileParams &P, c
     err = hipGetLastError();
   }
   if (err != hipSuccess) return err;
-  err = launch_rows_times_columns(stream, P.z, P.chains, P.X, (int64_t)P.n, P.p, nullptr, xtz, planes);
-  if (err != hipSuccess) return err;
-  return launch_rows_times_columns(stream, P.w, P.chains, Xsq, (int64_t)P.n, P.p, slab_precision, v_diag, planes);
+  return launch_latent_products(stream, P.z, P.w, P.chains, P.X, Xsq, (int64_t)P.n, P.p, slab_precision, xtz, v_diag,
+                                planes);
 }
 
 }  // namespace boom_amd

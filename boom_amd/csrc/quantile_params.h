@@ -3,6 +3,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "latent_params.h"
+
 namespace boom_amd {
 
 // Substream of QuantileRegressionSpikeSlabSampler:
@@ -15,19 +17,10 @@ enum { QUANTILE_IMPUTE_STRIDE = 256, QUANTILE_KMAX = 1024 };
 // an inverse-Gaussian draw that came out non-finite or not positive, as a chain status word
 enum { QUANTILE_WEIGHT_ERROR = 10 };
 
-struct QuantileParams {
-  int32_t n, p, chains, slot_limit;
-  int64_t chain_offset;
-  const double *X;        // n x p column-major
+// z: w_i y*_i = w_i y_i - (1 - 2 q); w: the imputed weights lambda_inv (0 where the residual is 0)
+struct QuantileParams : LatentParams {
   const double *y;        // n
-  const uint8_t *gamma;   // chains x p
-  const double *beta;     // chains x p
-  double *z;              // chains x n: w_i y*_i = w_i y_i - (1 - 2 q)
-  double *w;              // chains x n: the imputed weights lambda_inv (0 where the residual is 0)
   double shift;           // 1 - 2 q = 2 (1 - q) - 1
-  uint32_t seed_lo, seed_hi;
-  uint64_t sweep;         // draws done so far (positions the substream)
-  int32_t *status;
 };
 
 }  // namespace boom_amd

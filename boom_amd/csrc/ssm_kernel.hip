@@ -69,6 +69,7 @@
 
 #include "device_rng.h"
 #include "kalman_params.h"
+#include "products.h"
 #include "stream_normals.h"
 
 #include "ssg_device.h"
@@ -1137,9 +1138,6 @@ hipError_t launch_ssm_forecast(hipStream_t stream, const SsParams &P, int horizo
                      pos_forecast, out);
   return hipGetLastError();
 }
-
-hipError_t launch_xte_tiled(hipStream_t stream, const double *U, int64_t ldu, int R, const double *B, int64_t n,
-                            int p, double *out, double *planes);
 
 size_t ssm_dynamic_lds(const SsmParams &M) {
   size_t need = (size_t)ssg_pass_lds_doubles(M.m, M.ld, M.bl, M.nerr, M.nar) * sizeof(double);

@@ -32,46 +32,14 @@
 #include "ktimer.h"
 
 #include "device_rng.h"
+#include "latent_device.h"
+#include "products.h"
 #include "ssvs_params.h"
 #include "student_params.h"
 
 namespace boom_amd {
 
 namespace {
-
-__device__ __forceinline__ uint32_t stu_serve(const StudentParams &P, uint32_t stride) {
-  return (P.slot_limit > 0 && (uint32_t)P.slot_limit < stride) ? (uint32_t)P.slot_limit : stride;
-}
-
-// the chain's included variables and their coefficients, in index order, into LDS (256 threads)
-__device__ __forceinline__ int stu_included(const StudentParams &P, int chain, int *s_idx, double *s_beta) {
-  __shared__ int s_wave_count[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint8_t *g = P.gamma + (size_t)chain * P.p;
-  const double *b = P.beta + (size_t)chain * P.p;
-  int base = 0;
-  for (int j0 = 0; j0 < P.p; j0 += 256) {
-    const int j = j0 + tid;
-    const bool inc = j < P.p && g[j] != 0;
-    const unsigned long long m = __ballot(inc);
-    if (lane == 0) s_wave_count[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const int c = s_wave_count[w];
-      before += (w < wave) ? c : 0;
-      total += c;
-    }
-    if (inc) {
-      const int pos = base + before + __popcll(m & ((1ull << lane) - 1ull));
-      if (pos < STUDENT_KMAX) { s_idx[pos] = j; s_beta[pos] = b[j]; }
-    }
-    base += total;
-    __syncthreads();
-  }
-  return base;
-}
 
 // sum over the workgroup's 256 threads, in a fixed order; every thread gets the result
 __device__ __forceinline__ double stu_block_sum(double v, double *s_red) {
@@ -101,7 +69,7 @@ __global__ __launch_bounds__(256) void student_impute_kernel(StudentParams P) {
   if (s_status != CHAIN_OK) return;
   __shared__ int s_idx[STUDENT_KMAX];
   __shared__ double s_beta[STUDENT_KMAX];
-  const int k = stu_included(P, chain, s_idx, s_beta);
+  const int k = included_coefficients<STUDENT_KMAX>(P.gamma, P.beta, P.p, chain, s_idx, s_beta);
   if (k > STUDENT_KMAX) {
     if (threadIdx.x == 0 && blockIdx.x == 0) P.status[chain] = CHAIN_MODEL_TOO_LARGE;
     return;
@@ -123,7 +91,7 @@ __global__ __launch_bounds__(256) void student_impute_kernel(StudentParams P) {
   const double delta = (yi - eta) / sqrt(P.sigsq[chain]);
   SeqRng rng = SeqRng::slot(PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), STUDENT_IMPUTE_STREAM},
                             P.sweep * (uint64_t)P.n + (uint64_t)i, STUDENT_IMPUTE_STRIDE,
-                            stu_serve(P, STUDENT_IMPUTE_STRIDE));
+                            slot_serve(P.slot_limit, STUDENT_IMPUTE_STRIDE));
   // rgamma_mt(rng, (nu + 1) / 2, (nu + delta^2) / 2): shape, rate.  The shape is above 1/2,
   // so the small-shape branch (wave-uniform only) is never taken.
   int bad = 0;
@@ -217,7 +185,7 @@ __global__ __launch_bounds__(STUDENT_SN_BLOCK) void student_sigma_nu_kernel(Stud
   if (s_status != CHAIN_OK) return;
   __shared__ int s_idx[STUDENT_KMAX];
   __shared__ double s_beta[STUDENT_KMAX];
-  const int k = stu_included(P, chain, s_idx, s_beta);
+  const int k = included_coefficients<STUDENT_KMAX>(P.gamma, P.beta, P.p, chain, s_idx, s_beta);
   if (k > STUDENT_KMAX) {
     if (tid == 0) P.status[chain] = CHAIN_MODEL_TOO_LARGE;
     return;
@@ -241,7 +209,7 @@ __global__ __launch_bounds__(STUDENT_SN_BLOCK) void student_sigma_nu_kernel(Stud
   const double nobs = SS ? stu_block_sum(cnt, s_red) : (double)n;
   // 2. sigma^2 (GenericGaussianVarianceSampler::draw: n observations, not sum w)
   SeqRng rng = SeqRng::slot(PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), STUDENT_SN_STREAM},
-                            P.sweep, STUDENT_SN_STRIDE, stu_serve(P, STUDENT_SN_STRIDE));
+                            P.sweep, STUDENT_SN_STRIDE, slot_serve(P.slot_limit, STUDENT_SN_STRIDE));
   int bad = 0;
   const double sigsq = d_draw_variance(rng, nobs + P.prior_df, wsse + P.prior_ss, P.sigma_max, &bad);
   if (bad) {
@@ -317,9 +285,6 @@ __global__ __launch_bounds__(STUDENT_SN_BLOCK) void student_sigma_nu_kernel(Stud
   }
 }
 
-hipError_t launch_rows_times_columns(hipStream_t stream, const double *U, int R, const double *B, int64_t n,
-                                     int p, const double *diag_base, double *out, double *planes);
-
 // impute, X'Wz and the diagonal of V = slab precision + X'WX for every chain
 hipError_t launch_student_impute(hipStream_t stream, const StudentParams &P, const double *Xsq,
                                  const double *slab_precision, double *xtz, double *v_diag, double *planes) {
@@ -330,9 +295,8 @@ hipError_t launch_student_impute(hipStream_t stream, const StudentParams &P, con
     err = hipGetLastError();
   }
   if (err != hipSuccess) return err;
-  err = launch_rows_times_columns(stream, P.z, P.chains, P.X, (int64_t)P.n, P.p, nullptr, xtz, planes);
-  if (err != hipSuccess) return err;
-  return launch_rows_times_columns(stream, P.w, P.chains, Xsq, (int64_t)P.n, P.p, slab_precision, v_diag, planes);
+  return launch_latent_products(stream, P.z, P.w, P.chains, P.X, Xsq, (int64_t)P.n, P.p, slab_precision, xtz, v_diag,
+                                planes);
 }
 
 hipError_t launch_student_sigma_nu(hipStream_t stream, const StudentParams &P) {
@@ -362,9 +326,8 @@ hipError_t launch_student_ss_suf(hipStream_t stream, const StudentParams &P, con
     err = hipGetLastError();
   }
   if (err != hipSuccess) return err;
-  err = launch_rows_times_columns(stream, P.z, P.chains, P.X, (int64_t)P.n, P.p, nullptr, xtz, planes);
-  if (err != hipSuccess) return err;
-  return launch_rows_times_columns(stream, P.w, P.chains, Xsq, (int64_t)P.n, P.p, slab_precision, v_diag, planes);
+  return launch_latent_products(stream, P.z, P.w, P.chains, P.X, Xsq, (int64_t)P.n, P.p, slab_precision, xtz, v_diag,
+                                planes);
 }
 
 }  // namespace boom_amd

@@ -3,6 +3,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "latent_params.h"
+
 namespace boom_amd {
 
 // Substreams of TRegressionSpikeSlabSampler:
@@ -21,27 +23,20 @@ enum { STUDENT_BAD_WEIGHT = 13 };
 // the nu prior: Uniform(a, b) or Gamma(a, b) (shape, rate)
 enum { STUDENT_NU_UNIFORM = 0, STUDENT_NU_GAMMA = 1 };
 
-struct StudentParams {
-  int32_t n, p, chains, slot_limit;
-  int64_t chain_offset;
-  const double *X;        // n x p column-major
-  const double *y;        // n
-  const uint8_t *gamma;   // chains x p
-  const double *beta;     // chains x p
-  double *sigsq;          // chains
-  double *nu;             // chains
-  double *dx;             // chains: the slice sampler's suggested_dx
-  double *margin;         // chains: smallest relative gap of a slice comparison (running min)
-  double *z;              // chains x n: w_i y_i
-  double *w;              // chains x n: the imputed weights
-  double *u;              // chains x n: (r_i / sigma)^2 at the new beta and sigma
-  uint32_t seed_lo, seed_hi;
-  uint64_t sweep;         // draws done so far (positions the substreams)
-  int32_t *status;
+// z: w_i y_i; w: the imputed weights; sweep: draws done so far.  (The priors come first: with
+// this order of the fields every kernel of student_kernel.hip keeps the register counts it had
+// before the structs got their common head)
+struct StudentParams : LatentParams {
   // sigma^2 | beta, w: GenericGaussianVarianceSampler (DF = n + prior_df, SS = wsse + prior_ss)
   double prior_df, prior_ss, sigma_max;
   int32_t nu_kind;
   double nu_a, nu_b;
+  const double *y;        // n
+  double *sigsq;          // chains
+  double *nu;             // chains
+  double *dx;             // chains: the slice sampler's suggested_dx
+  double *margin;         // chains: smallest relative gap of a slice comparison (running min)
+  double *u;              // chains x n: (r_i / sigma)^2 at the new beta and sigma
   // recorded draws (ba_enable_draws): row trace_idx[c] - 1 of chain c gets sigma^2 and nu
   const int32_t *trace_idx;
   double *trace_sigsq;

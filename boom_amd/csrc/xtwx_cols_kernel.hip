@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include "ktimer.h"
 #include "planes_sizing.h"
+#include "products.h"
 #include <stdint.h>
 
 namespace boom_amd {
@@ -317,6 +318,14 @@ hipError_t launch_rows_times_columns(hipStream_t stream, const double *U, int R,
   hipLaunchKernelGGL(plain_reduce_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, planes, np, R,
                      p, diag_base, out);
   return hipGetLastError();
+}
+
+hipError_t launch_latent_products(hipStream_t stream, const double *z, const double *w, int rows,
+                                  const double *X, const double *Xsq, int64_t n, int p,
+                                  const double *slab_precision, double *xtz, double *v_diag, double *planes) {
+  hipError_t err = launch_rows_times_columns(stream, z, rows, X, n, p, nullptr, xtz, planes);
+  if (err != hipSuccess) return err;
+  return launch_rows_times_columns(stream, w, rows, Xsq, n, p, slab_precision, v_diag, planes);
 }
 
 // The same product for SHORT rows (the bsts path's X'e: chains x p x T with T a few

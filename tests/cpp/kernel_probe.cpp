@@ -1,10 +1,10 @@
 // Host-only probe of the product library's kernel launchers, for tests/test_split_k_products_gpu.py.
 //
 // The launchers of xtwx_cols_kernel.hip and predict_kernel.hip are ordinary exported functions
-// of libboomamd.so; their prototypes are re-declared here as boom_amd/csrc/engine_internal.h has
-// them.  Every wrapper takes host arrays with explicit lengths (in elements), allocates device
-// buffers of exactly those lengths, copies everything in -- outputs and workspaces too, which
-// the caller has filled with a sentinel and extended by a guard band --, launches on the null
+// of libboomamd.so, declared in boom_amd/csrc/products.h.  Every wrapper takes host arrays with
+// explicit lengths (in elements), allocates device buffers of exactly those lengths, copies
+// everything in -- outputs and workspaces too, which the caller has filled with a sentinel and
+// extended by a guard band --, launches on the null
 // stream, synchronises, copies every writable buffer back whole and returns the hipError_t.
 // No device code of its own.
 #include <hip/hip_runtime_api.h>
@@ -12,23 +12,7 @@
 #include <cstddef>
 #include <cstdint>
 
-namespace boom_amd {
-hipError_t launch_predict(hipStream_t stream, const double *trace_k, const uint16_t *rec_idx,
-                          const double *rec_beta, int stride, int cap, int first_draw, int ndraws,
-                          int chains, int p, const double *newX, int nnew, double *out);
-int xtwx_cols_planes(int64_t n);
-int xte_planes(int64_t n);
-hipError_t launch_xtwx_cols(hipStream_t stream, const double *X, int64_t n, int p, const double *w,
-                            const int32_t *req, int R, const double *base, double *V,
-                            uint32_t *valid, int words, double *planes);
-hipError_t launch_xtwx_cols_start(hipStream_t stream, const uint8_t *gamma, int chains, int p,
-                                  int32_t *req, int32_t *count, uint32_t *valid, int words);
-hipError_t launch_square(hipStream_t stream, const double *x, size_t count, double *out);
-hipError_t launch_rows_times_columns(hipStream_t stream, const double *U, int R, const double *B, int64_t n,
-                                     int p, const double *diag_base, double *out, double *planes);
-hipError_t launch_xte_tiled(hipStream_t stream, const double *U, int64_t ldu, int R, const double *B, int64_t n,
-                            int p, double *out, double *planes);
-}  // namespace boom_amd
+#include "../../boom_amd/csrc/products.h"
 
 namespace {
 

@@ -30,6 +30,17 @@ def make_engine(chains, seed, X, y, nt, slab, pi, g0, clt=5, max_flips=-1, **kw)
     return eng
 
 
+def check_sweeps(eng, ora, nsw):
+    """nsw single sweeps of the engine against the oracle's runs (chain -> run) at the file's bar"""
+    for s in range(nsw):
+        eng.logit_sweep(1)
+        gam, beta, _ = eng.get_states()
+        for c, o in ora.items():
+            assert o["status"] == 0
+            assert np.array_equal(gam[c], o["gamma"][s]), (c, s)
+            assert relerr(beta[c], o["beta"][s]) < RTOL, (c, s)
+
+
 @pytest.mark.parametrize("n,p,nsig,max_trials,max_flips",
                          [(300, 10, 3, 1, -1), (300, 10, 3, 4, -1), (777, 24, 5, 1, 9),
                           (500, 70, 6, 1, -1), (64, 5, 2, 3, -1)])
@@ -40,22 +51,40 @@ def test_logit_sweeps_match_oracle(oracle, n, p, nsig, max_trials, max_flips):
     g0[0] = 1
     chains, seed, nsw = 6, 17, 25
     eng = make_engine(chains, seed, X, y, nt, slab, pi, g0, max_flips=max_flips)
-    check = [0, chains - 1]
     ora = {c: oracle.logit_run(X, y, nt, slab, pi, ("philox", seed, c), g0, np.zeros(p), nsw,
-                               max_flips=max_flips) for c in check}
-    for s in range(nsw):
-        eng.logit_sweep(1)
-        gam, beta, _ = eng.get_states()
-        for c in check:
-            o = ora[c]
-            assert o["status"] == 0
-            assert np.array_equal(gam[c], o["gamma"][s]), (c, s)
-            assert relerr(beta[c], o["beta"][s]) < RTOL, (c, s)
+                               max_flips=max_flips) for c in (0, chains - 1)}
+    check_sweeps(eng, ora, nsw)
     # several sweeps in one call are the same draws
     eng2 = make_engine(chains, seed, X, y, nt, slab, pi, g0, max_flips=max_flips)
     eng2.logit_sweep(nsw)
     a, b = eng.get_states(), eng2.get_states()
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+
+
+def test_logit_included_variables_past_256(oracle):
+    """p = 260, the model {0, 255, 256, 259} with coefficients: the compaction of the included
+    variables (shared by the probit, logit and Poisson imputation kernels) runs its second round
+    of 256, and both sweeps' imputations read coefficients from it"""
+    n, p = 70, 260
+    idx = [0, 255, 256, 259]
+    rng = np.random.Generator(np.random.PCG64(260))
+    X = rng.standard_normal((n, p))
+    X[:, 0] = 1.0
+    beta0 = np.zeros(p)
+    beta0[idx] = [0.4, 1.5, -1.2, 1.0]
+    y = rng.binomial(1, 1 / (1 + np.exp(-(X @ beta0)))).astype(float)
+    nt = np.ones(n)
+    slab, pi = probit_slab(X, nt, 4)
+    pi[idx] = 0.9
+    g0 = np.zeros(p, np.uint8)
+    g0[idx] = 1
+    chains, seed, nsw = 2, 17, 2
+    eng = make_engine(chains, seed, X, y, nt, slab, pi, g0)
+    eng.set_state(g0, beta0)
+    ora = {c: oracle.logit_run(X, y, nt, slab, pi, ("philox", seed, c), g0, beta0, nsw) for c in range(chains)}
+    check_sweeps(eng, ora, nsw)
+    for o in ora.values():   # (the second sweep's imputation read a coefficient past 256 too)
+        assert o["gamma"][0][256:].any()
 
 
 def test_logit_capacity_escalation_and_recovery(oracle):
