@@ -689,7 +689,16 @@ int ba_ss_draw_next(ba_engine *e);
  * at most 2048 steps, models of at most 48 variables: the rounds of the call run as ONE
  * persistent launch per 64 rounds (every chain loops over its rounds by itself; chains
  * meet in tiles of 16 for X'(y - state)); otherwise three launches per round (regression
- * sweep, state draw, X'(y - state)).  The same draws either way: ba_ss_set_tuning(e, 4 | 5). */
+ * sweep, state draw, X'(y - state)).  The same draws either way: ba_ss_set_tuning(e, 4 | 5).
+ * The state draw's standard normals (RNG stream 2) are Box-Muller pairs on per-draw
+ * substreams -- draws 2 j and 2 j + 1 of a chain are R cos(2 pi u2), R sin(2 pi u2) of the two
+ * uniforms at stream position 512 j, R = sqrt(-2 log(1 - u1)) --, not the reference's
+ * sequential Kinderman-Ramage normals.  A same-seed comparison with BOOM can therefore show
+ * the same posterior (within Monte Carlo error) and cannot show the same draws, state paths or
+ * stream positions, for any seed.  The link is carried by tests/test_philox_ref.py (reference
+ * of the pairs == the oracle), tests/test_stream_normals_gpu.py and
+ * tests/test_stream_views_gpu.py (the device's generator and stream readers against that
+ * reference directly) and tests/test_substream_bridge.py (substreams vs sequential vs MT). */
 int ba_ss_sweep(ba_engine *e, int32_t nsweeps);
 /* one Base::impute_state (StateSpaceModelBase.cpp:278-291) with the current
  * parameters, on every chain */
