@@ -690,25 +690,62 @@ int concurrent_stream(ba_engine *e, hipStream_t *out) {
 // enqueued next comes after every sweep launch; a workgroup that waited for its chain in
 // vain (it cannot happen while the chains fit the machine; bounded all the same) is an error.
 int pipe_join(ba_engine *e) {
-  if (!e->pipe_on) return BA_OK;
-  e->pipe_on = false;
-  e->pipe_k = 0;
-  e->pipe_groups = false;
-  HIP_TRY(hipEventRecord(e->pipe_join_ev, e->pipe_stream));
-  HIP_TRY(hipStreamWaitEvent(e->stream, e->pipe_join_ev, 0));
+  if (!e->pipe.on) return BA_OK;
+  e->pipe.on = false;
+  e->pipe.k = 0;
+  e->pipe.groups = false;
+  HIP_TRY(hipEventRecord(e->pipe.join_ev, e->pipe.stream));
+  HIP_TRY(hipStreamWaitEvent(e->stream, e->pipe.join_ev, 0));
   return BA_OK;
 }
 // (force: read the word whatever the flag says -- the look-ahead's batches, whose launches
 // and checks interleave)
 static int pipe_check(ba_engine *e, bool force = false) {
-  if (e->dpipe_err.count == 0 || (!force && !e->pipe_unchecked)) return BA_OK;
-  e->pipe_unchecked = false;
+  if (e->pipe.err.count == 0 || (!force && !e->pipe.unchecked)) return BA_OK;
+  e->pipe.unchecked = false;
   int32_t err = 0;
-  HIP_TRY(hipMemcpy(&err, e->dpipe_err.ptr, 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&err, e->pipe.err.ptr, 4, hipMemcpyDeviceToHost));
   if (err) {
-    HIP_TRY(hipMemset(e->dpipe_err.ptr, 0, 4));
+    HIP_TRY(hipMemset(e->pipe.err.ptr, 0, 4));
     return fail(BA_E_HIP, "a pipelined sweep launch waited for a chain in vain");
   }
+  return BA_OK;
+}
+// the second stream and its events, at the first launch that needs them
+static int pipe_open(ba_engine *e) {
+  if (e->pipe.stream) return BA_OK;
+  int rc = concurrent_stream(e, &e->pipe.stream);
+  if (rc) return rc;
+  for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreateWithFlags(&e->pipe.ev[i], hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&e->pipe.join_ev, hipEventDisableTiming));
+  return BA_OK;
+}
+// How many chains' workgroups the device holds at once for a sweep launch of `lds` bytes per
+// workgroup (*resident; 0: not even one fits a CU), and whether that is every chain of the
+// engine: what lets consecutive launches hand chains over.
+static bool chains_fit(const ba_engine *e, size_t lds, int *resident = nullptr) {
+  const int r = lds > e->lds_per_cu ? 0 : (int)std::min<size_t>(4, e->lds_per_cu / lds) * e->cu_count;
+  if (resident) *resident = r;
+  return e->cfg.chains <= r;
+}
+
+int all_chains_ok(ba_engine *e, bool *ok) {
+  const size_t C = (size_t)e->cfg.chains;
+  std::vector<int32_t> st(C);
+  HIP_TRY(hipMemcpy(st.data(), e->dstatus.ptr, C * 4, hipMemcpyDeviceToHost));
+  *ok = true;
+  for (size_t c = 0; c < C; ++c) *ok = *ok && st[c] == CHAIN_OK;
+  return BA_OK;
+}
+// (the statuses and the sweeps booked as owed belong to the dropped launches -- a chain that
+// stopped in them stopped after the point the chains go back to -- and so do the proposal
+// tables and the models' factors)
+int drop_launched_ahead(ba_engine *e) {
+  const size_t C = (size_t)e->cfg.chains;
+  HIP_TRY(hipMemsetAsync(e->dstatus.ptr, 0, C * 4, e->stream));
+  HIP_TRY(hipMemsetAsync(e->dtodo.ptr, 0, C * 4, e->stream));
+  e->table_ok = false;
+  e->model_ok = false;
   return BA_OK;
 }
 
@@ -719,9 +756,9 @@ static int read_record(ba_engine *e, int64_t c, int row0, int nrows, uint8_t *ga
 static int read_record_row_all(ba_engine *e, int row, uint8_t *gamma, double *beta, double *sigsq);
 
 static void la_discard(ba_engine *e) {
-  e->la_avail = e->la_served = 0;
-  e->la_cache.clear();
-  e->la_synced = false;
+  e->la.avail = e->la.served = 0;
+  e->la.cache.clear();
+  e->la.synced = false;
 }
 
 static int la_redo_batch(ba_engine *e);
@@ -729,50 +766,42 @@ static int la_redo_batch(ba_engine *e);
 // the batch being served is complete and sound; a pipelined batch in which a chain stopped
 // (capacity, an error) is run again the old way -- same draws -- where those are dealt with
 static int la_wait(ba_engine *e) {
-  if (e->la_synced) return BA_OK;
-  if (e->la_cur_piped) {
-    HIP_TRY(hipEventSynchronize(e->la_done[e->la_slot]));
+  if (e->la.synced) return BA_OK;
+  if (e->la.cur_piped) {
+    HIP_TRY(hipEventSynchronize(e->la.done[e->la.slot]));
     int rc = pipe_check(e, true);
-    if (rc) return rc;
-    const size_t C = (size_t)e->cfg.chains;
-    std::vector<int32_t> st(C);
-    HIP_TRY(hipMemcpy(st.data(), e->dstatus.ptr, C * 4, hipMemcpyDeviceToHost));
     bool ok = true;
-    for (size_t c = 0; c < C; ++c) ok = ok && st[c] == CHAIN_OK;
-    if (!ok) {
-      rc = la_redo_batch(e);
-      if (rc) return rc;
-    }
+    if (!rc) rc = all_chains_ok(e, &ok);
+    if (!rc && !ok) rc = la_redo_batch(e);
+    if (rc) return rc;
   } else {
     HIP_TRY(hipStreamSynchronize(e->stream));
     int rc = check_chain_status(e);
     if (rc) return rc;
   }
-  e->la_synced = true;
+  e->la.synced = true;
   return BA_OK;
 }
 
 // the draw ba_draw_next is serving, for one chain: from the host copy of the
 // chain's rows of the batch (fetched at the chain's first read in the batch)
 static int la_read(ba_engine *e, int64_t c, uint8_t *gamma, double *beta, double *sigsq) {
-  {
-    int rc = la_wait(e);
-    if (rc) return rc;
-  }
-  const size_t p = (size_t)e->p, cap = (size_t)e->rec_cap, n = (size_t)e->la_avail;
-  auto it = e->la_cache.find(c);
-  if (it == e->la_cache.end()) {
-    ba_engine::LaRows r;
+  int rc = la_wait(e);
+  if (rc) return rc;
+  const size_t p = (size_t)e->p, cap = (size_t)e->rec_cap, n = (size_t)e->la.avail;
+  auto it = e->la.cache.find(c);
+  if (it == e->la.cache.end()) {
+    ba_engine::La::Rows r;
     r.k.resize(n); r.sig.resize(n); r.beta.resize(n * cap); r.idx.resize(n * cap);
-    const size_t base = (size_t)c * e->trace_stride + (size_t)e->la_slot * (size_t)e->la_len;
+    const size_t base = (size_t)c * e->trace_stride + (size_t)e->la.slot * (size_t)e->la.len;
     HIP_TRY(hipMemcpy(r.k.data(), e->dtr_k.ptr + base, n * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(r.sig.data(), e->dtr_sig.ptr + base, n * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(r.idx.data(), e->drec_idx.ptr + base * cap, n * cap * 2, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(r.beta.data(), e->drec_beta.ptr + base * cap, n * cap * 8, hipMemcpyDeviceToHost));
-    it = e->la_cache.emplace(c, std::move(r)).first;
+    it = e->la.cache.emplace(c, std::move(r)).first;
   }
-  const ba_engine::LaRows &r = it->second;
-  const size_t row = (size_t)e->la_served - 1;
+  const ba_engine::La::Rows &r = it->second;
+  const size_t row = (size_t)e->la.served - 1;
   const int k = (int)r.k[row];
   if (k < 0 || (size_t)k > cap) return fail(BA_E_STATE, "corrupt draw record");
   if (gamma) std::memset(gamma, 0, p);
@@ -787,52 +816,53 @@ static int la_read(ba_engine *e, int64_t c, uint8_t *gamma, double *beta, double
   return BA_OK;
 }
 
-// snapshot set `set` (0 / 1) <-> the live chain state
-static int la_snap_alloc(ba_engine *e) {
-  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p;
-  HIP_TRY(e->snap_gamma.resize(2 * C * p));
-  HIP_TRY(e->snap_beta.resize(2 * C * p));
-  HIP_TRY(e->snap_sigsq.resize(2 * C));
-  HIP_TRY(e->snap_perm.resize(2 * C * p));
-  HIP_TRY(e->snap_pos.resize(2 * C));
-  HIP_TRY(e->snap_fail.resize(2 * C));
-  HIP_TRY(e->snap_inc.resize(2 * C * p));
-  HIP_TRY(e->snap_bsum.resize(2 * C * p));
-  HIP_TRY(e->snap_bsumsq.resize(2 * C * p));
-  HIP_TRY(e->snap_acc.resize(2 * C * ACC_COUNT));
+// What a chain's state is, so that a snapshot of it can be rewound to -- THE list: the live
+// array, its two snapshot sets, the elements per chain and the SsvsParams member through which
+// a pipelined batch's workgroups save the same array on entry (ssvs_kernel.hip).  A per-chain
+// array that a sweep changes belongs here, and nowhere else on the host.
+template <class F>
+static int la_snap_fields(ba_engine *e, F f) {
+  const size_t p = (size_t)e->p;
+  ba_engine::La::Snap &S = e->la.snap;
+  hipError_t la_snapshot = hipSuccess;
+  auto field = [&](auto &live, auto &snap, size_t n, auto member) {
+    if (la_snapshot == hipSuccess) la_snapshot = f(live, snap, n, member);
+  };
+  field(e->dgamma, S.gamma, p, &SsvsParams::snap_gamma);
+  field(e->dbeta, S.beta, p, &SsvsParams::snap_beta);
+  field(e->dsigsq, S.sigsq, 1, &SsvsParams::snap_sigsq);
+  field(e->dperm, S.perm, p, &SsvsParams::snap_perm);
+  field(e->dpos, S.pos, 1, &SsvsParams::snap_pos);
+  field(e->dfail, S.fail, 1, &SsvsParams::snap_fail);
+  field(e->dinc, S.inc, p, &SsvsParams::snap_inc);
+  field(e->dbsum, S.bsum, p, &SsvsParams::snap_bsum);
+  field(e->dbsumsq, S.bsumsq, p, &SsvsParams::snap_bsumsq);
+  field(e->dacc, S.acc, ACC_COUNT, &SsvsParams::snap_acc);
+  HIP_TRY(la_snapshot);
   return BA_OK;
 }
+static int la_snap_alloc(ba_engine *e) {
+  const size_t C = (size_t)e->cfg.chains;
+  return la_snap_fields(e, [&](auto &, auto &snap, size_t n, auto) { return snap.resize(2 * C * n); });
+}
+// snapshot set `set` (0 / 1) <-> the live chain state
 int la_copy(ba_engine *e, bool save, int set) {
-  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p;
-  hipStream_t s = e->stream;
+  const size_t C = (size_t)e->cfg.chains;
   if (save) {
     int rc = la_snap_alloc(e);
     if (rc) return rc;
   }
-  const size_t o1 = (size_t)set * C, op = (size_t)set * C * p;
-#define LA_CP(snap, live, bytes)                                                      \
-  HIP_TRY(hipMemcpyAsync(save ? (void *)(snap) : (void *)(live),                       \
-                         save ? (const void *)(live) : (const void *)(snap), (bytes), \
-                         hipMemcpyDeviceToDevice, s))
-  LA_CP(e->snap_gamma.ptr + op, e->dgamma.ptr, C * p);
-  LA_CP(e->snap_beta.ptr + op, e->dbeta.ptr, C * p * 8);
-  LA_CP(e->snap_sigsq.ptr + o1, e->dsigsq.ptr, C * 8);
-  LA_CP(e->snap_perm.ptr + op, e->dperm.ptr, C * p * 2);
-  LA_CP(e->snap_pos.ptr + o1, e->dpos.ptr, C * 8);
-  LA_CP(e->snap_fail.ptr + o1, e->dfail.ptr, C * 4);
-  LA_CP(e->snap_inc.ptr + op, e->dinc.ptr, C * p * 4);
-  LA_CP(e->snap_bsum.ptr + op, e->dbsum.ptr, C * p * 8);
-  LA_CP(e->snap_bsumsq.ptr + op, e->dbsumsq.ptr, C * p * 8);
-  LA_CP(e->snap_acc.ptr + (size_t)set * C * ACC_COUNT, e->dacc.ptr, C * ACC_COUNT * 8);
-#undef LA_CP
-  return BA_OK;
+  return la_snap_fields(e, [&](auto &live, auto &snap, size_t n, auto) {
+    auto *held = snap.ptr + (size_t)set * C * n;
+    return hipMemcpyAsync(save ? held : live.ptr, save ? live.ptr : held, C * n * sizeof(*held),
+                          hipMemcpyDeviceToDevice, e->stream);
+  });
 }
 
 // every launch of the look-ahead has finished (the main stream has caught up with the other
-// one) and nothing is ahead any more; *ahead_was: a batch beyond the one being served ran
-static int la_quiesce(ba_engine *e, bool *ahead_was) {
-  *ahead_was = e->la_ahead;
-  e->la_ahead = false;
+// one) and nothing is ahead any more
+static int la_quiesce(ba_engine *e) {
+  e->la.ahead = false;
   int rc = pipe_join(e);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -844,28 +874,21 @@ static int la_quiesce(ba_engine *e, bool *ahead_was) {
 // start and the batch runs again the way batches ran before they overlapped -- the same
 // draws, with the escalation / error report of that path.  Overlap stays off afterwards.
 static int la_redo_batch(ba_engine *e) {
-  bool ahead = false;
-  int rc = la_quiesce(e, &ahead);
+  int rc = la_quiesce(e);
   if (rc) return rc;
-  const int served = e->la_served;
-  rc = la_copy(e, false, e->la_slot);
+  const int served = e->la.served;
+  rc = la_copy(e, false, e->la.slot);
+  if (!rc) rc = drop_launched_ahead(e);
   if (rc) return rc;
-  {  // (the statuses and the sweeps booked as owed belong to the dropped launches)
-    const size_t C = (size_t)e->cfg.chains;
-    HIP_TRY(hipMemsetAsync(e->dstatus.ptr, 0, C * 4, e->stream));
-    HIP_TRY(hipMemsetAsync(e->dtodo.ptr, 0, C * 4, e->stream));
-  }
-  e->la_pipe = false;
-  e->la_cur_piped = false;
-  e->la_slot = 0;
-  e->table_ok = false;
-  e->model_ok = false;
+  e->la.pipe = false;
+  e->la.cur_piped = false;
+  e->la.slot = 0;
   rc = la_copy(e, true, 0);
-  if (!rc) rc = sweep_impl(e, e->la_len);
+  if (!rc) rc = sweep_impl(e, e->la.len);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));
-  e->la_cache.clear();
-  e->la_served = served;
+  e->la.cache.clear();
+  e->la.served = served;
   return check_chain_status(e);
 }
 
@@ -874,37 +897,32 @@ static int la_redo_batch(ba_engine *e) {
 // seen them -- the batch's start, replayed up to the last draw handed out (same
 // stream positions, so the same draws).
 int la_rewind(ba_engine *e) {
-  if (e->la_served >= e->la_avail && !e->la_ahead) {
+  if (e->la.served >= e->la.avail && !e->la.ahead) {
     la_discard(e);
     return BA_OK;
   }
   HIP_TRY(hipSetDevice(e->cfg.device));
-  bool ahead = false;
-  int rc = la_quiesce(e, &ahead);
+  int rc = la_quiesce(e);
   if (rc) return rc;
-  const bool all_served = e->la_served >= e->la_avail;
-  const int replay = all_served ? 0 : e->la_served;
+  const bool all_served = e->la.served >= e->la.avail;
+  const int replay = all_served ? 0 : e->la.served;
   // where to go back to: the start of the batch being served, or -- every draw of it
   // served, the next one already run -- the start of that next one
-  const int set = all_served ? (e->la_slot ^ 1) : e->la_slot;
-  const bool piped = e->la_cur_piped;
+  const int set = all_served ? (e->la.slot ^ 1) : e->la.slot;
+  const bool piped = e->la.cur_piped;
   la_discard(e);
   if (piped) {
     rc = pipe_check(e, true);
-    if (rc) return rc;
-    const size_t C = (size_t)e->cfg.chains;
-    // (a chain that stopped in the dropped launches stopped after the point we return to)
-    HIP_TRY(hipMemsetAsync(e->dstatus.ptr, 0, C * 4, e->stream));
-    HIP_TRY(hipMemsetAsync(e->dtodo.ptr, 0, C * 4, e->stream));
+    if (!rc) rc = drop_launched_ahead(e);
   } else {
-    rc = check_chain_status(e);
-    if (rc) return rc;
+    rc = check_chain_status(e);   // (one launch, run to its end: its stops are dealt with, not dropped)
   }
+  if (rc) return rc;
   rc = la_copy(e, false, piped ? set : 0);
   if (rc) return rc;
-  e->la_cur_piped = false;
-  e->la_slot = 0;
-  e->table_ok = false;
+  e->la.cur_piped = false;
+  e->la.slot = 0;
+  e->table_ok = false;   // (either way the chains are no longer where the launch left them)
   e->model_ok = false;
   if (replay > 0) {
     rc = sweep_impl(e, replay, /*record=*/false);
@@ -974,14 +992,14 @@ void ba_engine_destroy(ba_engine *e) {
     (void)hipStreamDestroy(e->stream2);
   }
   for (int i = 0; i < 2; ++i) {
-    if (e->la_done[i]) (void)hipEventDestroy(e->la_done[i]);
+    if (e->la.done[i]) (void)hipEventDestroy(e->la.done[i]);
     if (e->ssla.done[i]) (void)hipEventDestroy(e->ssla.done[i]);
   }
-  if (e->pipe_stream) {
-    (void)hipStreamSynchronize(e->pipe_stream);
-    (void)hipStreamDestroy(e->pipe_stream);
-    for (int i = 0; i < 4; ++i) (void)hipEventDestroy(e->pipe_ev[i]);
-    (void)hipEventDestroy(e->pipe_join_ev);
+  if (e->pipe.stream) {
+    (void)hipStreamSynchronize(e->pipe.stream);
+    (void)hipStreamDestroy(e->pipe.stream);
+    for (int i = 0; i < 4; ++i) (void)hipEventDestroy(e->pipe.ev[i]);
+    (void)hipEventDestroy(e->pipe.join_ev);
   }
   if (e->ev_state) (void)hipEventDestroy(e->ev_state);
   if (e->pinned) (void)hipHostFree(e->pinned);
@@ -1416,7 +1434,7 @@ int ba_get_state(ba_engine *e, int64_t chain, uint8_t *gamma, double *beta,
   ENGINE_ACCESSOR_NOJOIN(e);
   if (!e->state_ready) return fail(BA_E_STATE, "no chain state yet");
   if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
-  if (e->la_served > 0 && e->la_served <= e->la_avail)  // the draw ba_draw_next is serving
+  if (e->la.served > 0 && e->la.served <= e->la.avail)  // the draw ba_draw_next is serving
     return la_read(e, chain, gamma, beta, sigsq);
   {
     int rcj = pipe_join(e);
@@ -1529,11 +1547,11 @@ int ba_get_states(ba_engine *e, uint8_t *gamma, double *beta, double *sigsq) {
     if (sigsq) HIP_TRY(hipMemcpy2D(sigsq, 8, A.rsig.ptr + at, L * 8, 8, C, hipMemcpyDeviceToHost));
     return BA_OK;
   }
-  if (e->la_served > 0 && e->la_served <= e->la_avail && (e->la_served < e->la_avail || e->la_ahead)) {
+  if (e->la.served > 0 && e->la.served <= e->la.avail && (e->la.served < e->la.avail || e->la.ahead)) {
     // the draw being served, every chain: from the record (the chains themselves are ahead)
     int rcw = la_wait(e);
     if (rcw) return rcw;
-    return read_record_row_all(e, e->la_slot * e->la_len + e->la_served - 1, gamma, beta, sigsq);
+    return read_record_row_all(e, e->la.slot * e->la.len + e->la.served - 1, gamma, beta, sigsq);
   }
   int rc = ba_sync(e);
   if (rc) return rc;
@@ -1693,19 +1711,11 @@ static int sweep_impl(ba_engine *e, int32_t nsweeps, bool record, int la_half) {
   if (record && e->trace_stride > 0 && la_half < 0)  // traces are those of the last ba_sweep call
     HIP_TRY(hipMemsetAsync(e->dtrace_idx.ptr, 0, (size_t)e->cfg.chains * 4, e->stream));
   if (la_half >= 0) {
-    const size_t C = (size_t)e->cfg.chains, pp = (size_t)e->p;
-    const size_t o1 = (size_t)la_half * C, op = (size_t)la_half * C * pp;
-    P.trace_row0 = la_half * e->la_len;
-    P.snap_gamma = e->snap_gamma.ptr + op;
-    P.snap_beta = e->snap_beta.ptr + op;
-    P.snap_sigsq = e->snap_sigsq.ptr + o1;
-    P.snap_perm = e->snap_perm.ptr + op;
-    P.snap_pos = e->snap_pos.ptr + o1;
-    P.snap_fail = e->snap_fail.ptr + o1;
-    P.snap_inc = e->snap_inc.ptr + op;
-    P.snap_bsum = e->snap_bsum.ptr + op;
-    P.snap_bsumsq = e->snap_bsumsq.ptr + op;
-    P.snap_acc = e->snap_acc.ptr + (size_t)la_half * C * ACC_COUNT;
+    P.trace_row0 = la_half * e->la.len;
+    (void)la_snap_fields(e, [&](auto &, auto &snap, size_t n, auto member) {   // (saved into set la_half)
+      P.*member = snap.ptr + (size_t)la_half * (size_t)e->cfg.chains * n;
+      return hipSuccess;
+    });
   }
 #ifndef BA_PIPELINE
 #define BA_PIPELINE 1
@@ -1715,9 +1725,10 @@ static int sweep_impl(ba_engine *e, int32_t nsweeps, bool record, int la_half) {
   // fills the slots the current one's early finishers leave instead of waiting for its
   // slowest chain.  Only while every chain's workgroup is resident at once, no trace is
   // recorded (its cursor is reset per call) and no chain lives in the large-model kernel.
-  const int resident_per_cu = (int)std::min<size_t>(4, e->lds_per_cu / lay.total);
+  int group = 0;   // chains resident at once
+  const bool all_fit = chains_fit(e, lay.total, &group);
   const bool pipelined = BA_PIPELINE && nsweeps > 0 && (e->trace_stride == 0 || la_half >= 0) && !e->big_active &&
-                         e->cfg.chains <= resident_per_cu * e->cu_count && (!e->kt_enabled || e->kt_overlap);
+                         all_fit && (!e->kt_enabled || e->kt_overlap);
   if (la_half >= 0 && !pipelined) return fail(BA_E_STATE, "look-ahead batch cannot overlap");
   if (!pipelined) {
     // More chains than the machine holds (round 4).  The chains go out in GROUPS of what fits
@@ -1728,34 +1739,28 @@ static int sweep_impl(ba_engine *e, int32_t nsweeps, bool record, int la_half) {
     // of the last round then start a whole round late on this machine, 53 ms per
     // 2048-chain launch where two launches of 1024 take 46 -- or, for exactly two or three
     // groups, separate launches one after the other, each as long as its slowest chain.)
-    const int C = e->cfg.chains, group = resident_per_cu * e->cu_count;
-    const bool groups = BA_PIPELINE && nsweeps > 0 && e->cur_mode != 2 && !e->big_active && C > group &&
+    const int C = e->cfg.chains;
+    const bool groups = BA_PIPELINE && nsweeps > 0 && e->cur_mode != 2 && !e->big_active && !all_fit &&
                         e->trace_stride == 0 && (!e->kt_enabled || e->kt_overlap);
     if (groups) {
-      if (!e->pipe_stream) {
-        {
-          int rcs = concurrent_stream(e, &e->pipe_stream);
-          if (rcs) return rcs;
-        }
-        for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreateWithFlags(&e->pipe_ev[i], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&e->pipe_join_ev, hipEventDisableTiming));
-      }
-      if (!(e->pipe_on && e->pipe_groups)) {
+      int rco = pipe_open(e);
+      if (rco) return rco;
+      if (!(e->pipe.on && e->pipe.groups)) {
         int rcj = pipe_join(e);
         if (rcj) return rcj;
         // (the other stream behind everything the main stream holds so far: uploads, mutators)
-        HIP_TRY(hipEventRecord(e->pipe_ev[0], e->stream));
-        HIP_TRY(hipStreamWaitEvent(e->pipe_stream, e->pipe_ev[0], 0));
+        HIP_TRY(hipEventRecord(e->pipe.ev[0], e->stream));
+        HIP_TRY(hipStreamWaitEvent(e->pipe.stream, e->pipe.ev[0], 0));
       }
       SsvsParams Pg = P;
       int g = 0;
       for (int first = 0; first < C; first += group, ++g) {
         Pg.chain_first = first;
         Pg.chain_count = std::min(group, C - first);
-        HIP_TRY(launch_ssvs_sweep((g & 1) ? e->pipe_stream : e->stream, Pg, (int)nsweeps));
+        HIP_TRY(launch_ssvs_sweep((g & 1) ? e->pipe.stream : e->stream, Pg, (int)nsweeps));
       }
-      e->pipe_on = true;
-      e->pipe_groups = true;
+      e->pipe.on = true;
+      e->pipe.groups = true;
     } else {
       int rcj = pipe_join(e);
       if (rcj) return rcj;
@@ -1763,40 +1768,34 @@ static int sweep_impl(ba_engine *e, int32_t nsweeps, bool record, int la_half) {
     }
   } else {
     const size_t C = (size_t)e->cfg.chains, qlen = C + 2;
-    if (!e->pipe_stream) {
-      {
-        int rcs = concurrent_stream(e, &e->pipe_stream);
-        if (rcs) return rcs;
-      }
-      for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreateWithFlags(&e->pipe_ev[i], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&e->pipe_join_ev, hipEventDisableTiming));
-    }
-    if (e->dpipe_q.count != 4 * qlen) {
+    int rco = pipe_open(e);
+    if (rco) return rco;
+    if (e->pipe.q.count != 4 * qlen) {
       HIP_TRY(hipStreamSynchronize(e->stream));
-      HIP_TRY(e->dpipe_q.resize(4 * qlen));
-      HIP_TRY(e->dpipe_err.resize(1));
-      HIP_TRY(hipMemset(e->dpipe_err.ptr, 0, 4));
+      HIP_TRY(e->pipe.q.resize(4 * qlen));
+      HIP_TRY(e->pipe.err.resize(1));
+      HIP_TRY(hipMemset(e->pipe.err.ptr, 0, 4));
     }
-    const int k = e->pipe_on ? e->pipe_k : 0;     // (a new pipeline starts on the main stream)
-    hipStream_t st = (k & 1) ? e->pipe_stream : e->stream;
-    int32_t *qout = e->dpipe_q.ptr + (size_t)(k & 3) * qlen;
+    const int k = e->pipe.on ? e->pipe.k : 0;     // (a new pipeline starts on the main stream)
+    hipStream_t st = (k & 1) ? e->pipe.stream : e->stream;
+    int32_t *qout = e->pipe.q.ptr + (size_t)(k & 3) * qlen;
     // the queue this launch fills: emptied on its own stream (after the launch two before
     // it, whose hand-over to the launch before it used the queue four back at the latest)
     HIP_TRY(hipMemsetAsync(qout, 0, 8, st));
     HIP_TRY(hipMemsetAsync(qout + 2, 0xFF, C * 4, st));
-    HIP_TRY(hipEventRecord(e->pipe_ev[k & 3], st));
+    HIP_TRY(hipEventRecord(e->pipe.ev[k & 3], st));
     P.q_out = qout;
-    P.q_error = e->dpipe_err.ptr;
+    P.q_error = e->pipe.err.ptr;
     if (k > 0) {
-      P.q_in = e->dpipe_q.ptr + (size_t)((k - 1) & 3) * qlen;
+      P.q_in = e->pipe.q.ptr + (size_t)((k - 1) & 3) * qlen;
       // (... which the previous launch's stream has emptied before that launch)
-      HIP_TRY(hipStreamWaitEvent(st, e->pipe_ev[(k - 1) & 3], 0));
+      HIP_TRY(hipStreamWaitEvent(st, e->pipe.ev[(k - 1) & 3], 0));
     }
     HIP_TRY(launch_ssvs_sweep(st, P, (int)nsweeps));
-    if (la_half >= 0) HIP_TRY(hipEventRecord(e->la_done[la_half], st));
-    e->pipe_on = true;
-    e->pipe_unchecked = true;
-    e->pipe_k = k + 1;
+    if (la_half >= 0) HIP_TRY(hipEventRecord(e->la.done[la_half], st));
+    e->pipe.on = true;
+    e->pipe.unchecked = true;
+    e->pipe.k = k + 1;
   }
   e->table_ok = true;  // until anything but another ba_sweep touches the engine
   e->model_ok = true;
@@ -1808,14 +1807,14 @@ extern "C" {
 
 int ba_sweep(ba_engine *e, int32_t nsweeps) {
   ENGINE_PROLOGUE_NOJOIN(e);
-  if (e->la_served < e->la_avail || e->data_kind != DATA_REGRESSION || e->cur_mode != 0) {
+  if (e->la.served < e->la.avail || e->data_kind != DATA_REGRESSION || e->cur_mode != 0) {
     int rcj = pipe_join(e);   // (anything but a plain continuation)
     if (rcj) return rcj;
   }
   // unserved look-ahead draws: the sweeps asked for here come after the last one served
   int rc = la_rewind(e);
   if (rc) return rc;
-  return sweep_impl(e, nsweeps, /*record=*/e->la_len <= 1);
+  return sweep_impl(e, nsweeps, /*record=*/e->la.len <= 1);
 }
 
 int ba_set_lookahead(ba_engine *e, int32_t lookahead) {
@@ -1827,33 +1826,28 @@ int ba_set_lookahead(ba_engine *e, int32_t lookahead) {
     int rc = ba_enable_draws(e, 2 * lookahead);
     if (rc) return rc;
   }
-  e->la_len = lookahead;
-  e->la_pipe = true;
+  e->la.len = lookahead;
+  e->la.pipe = true;
   return BA_OK;
 }
 
 // can the next look-ahead batch overlap its neighbours (sweep_impl's conditions)
 static bool la_can_overlap(const ba_engine *e) {
-  if (!BA_PIPELINE || !e->la_pipe || e->big_active || (e->kt_enabled && !e->kt_overlap) || e->kcap <= 0) return false;
-  const size_t lds = ssvs_lds_layout(e->p, e->kcap).total;
-  if (lds > e->lds_per_cu) return false;
-  const int resident_per_cu = (int)std::min<size_t>(4, e->lds_per_cu / lds);
-  return e->cfg.chains <= resident_per_cu * e->cu_count;
+  if (!BA_PIPELINE || !e->la.pipe || e->big_active || (e->kt_enabled && !e->kt_overlap) || e->kcap <= 0) return false;
+  return chains_fit(e, ssvs_lds_layout(e->p, e->kcap).total);
 }
 
 int ba_draw_next(ba_engine *e) {
   ENGINE_PROLOGUE_NOJOIN(e);
-  if (e->la_len <= 1) return ba_sweep(e, 1);
-  if (e->la_served == e->la_avail) {
+  if (e->la.len <= 1) return ba_sweep(e, 1);
+  if (e->la.served == e->la.avail) {
     // the record is used up: on to the next batch
-    if (e->la_ahead) {
+    if (e->la.ahead) {
       // ... which is already running (or done): the other half of the record
-      e->la_slot ^= 1;
-      e->la_ahead = false;
-      e->la_avail = e->la_served = 0;
-      e->la_cache.clear();
-      e->la_synced = false;
-      e->la_cur_piped = true;
+      e->la.slot ^= 1;
+      e->la.ahead = false;
+      la_discard(e);
+      e->la.cur_piped = true;
     } else {
       // ... from the chains' current state
       int rc = pipe_join(e);
@@ -1863,31 +1857,26 @@ int ba_draw_next(ba_engine *e) {
       if (!rc) rc = upload_shared(e);
       if (!rc) rc = alloc_chain_state(e);
       if (rc) return rc;
-      if (!e->la_done[0]) {
-        HIP_TRY(hipEventCreateWithFlags(&e->la_done[0], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&e->la_done[1], hipEventDisableTiming));
+      if (!e->la.done[0]) {
+        HIP_TRY(hipEventCreateWithFlags(&e->la.done[0], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&e->la.done[1], hipEventDisableTiming));
       }
-      e->la_slot = 0;
-      if (la_can_overlap(e)) {
-        rc = la_snap_alloc(e);
-        if (!rc) rc = sweep_impl(e, e->la_len, true, 0);
-        e->la_cur_piped = true;
-      } else {
-        rc = la_copy(e, true, 0);
-        if (!rc) rc = sweep_impl(e, e->la_len);
-        e->la_cur_piped = false;
-      }
+      e->la.slot = 0;
+      // (a batch that overlaps: its workgroups take the snapshot themselves)
+      e->la.cur_piped = la_can_overlap(e);
+      rc = e->la.cur_piped ? la_snap_alloc(e) : la_copy(e, true, 0);
+      if (!rc) rc = sweep_impl(e, e->la.len, true, e->la.cur_piped ? 0 : -1);
       if (rc) return rc;
     }
-    e->la_avail = e->la_len;
+    e->la.avail = e->la.len;
     // the batch after this one goes out now, into the other half
-    if (e->la_cur_piped && la_can_overlap(e)) {
-      int rc = sweep_impl(e, e->la_len, true, e->la_slot ^ 1);
+    if (e->la.cur_piped && la_can_overlap(e)) {
+      int rc = sweep_impl(e, e->la.len, true, e->la.slot ^ 1);
       if (rc) return rc;
-      e->la_ahead = true;
+      e->la.ahead = true;
     }
   }
-  ++e->la_served;
+  ++e->la.served;
   return BA_OK;
 }
 
@@ -2028,7 +2017,7 @@ int ba_enable_traces(ba_engine *e, int32_t max_sweeps) {
   {  // (the recording buffers are the look-ahead's as well)
     int rc = la_rewind(e);
     if (rc) return rc;
-    e->la_len = 1;
+    e->la.len = 1;
   }
   const size_t C = (size_t)e->cfg.chains;
   HIP_TRY(hipStreamSynchronize(e->stream));

@@ -228,33 +228,39 @@ struct ba_engine {
 
   int kcap = 0;
   int waves = 1;  // wavefronts per chain
-  // ba_draw_next: the look-ahead batch.  la_avail draws are recorded on the
-  // device, la_served of them have been handed out; the snapshot is the chains'
+  // ba_draw_next: the look-ahead batch.  `avail` draws are recorded on the
+  // device, `served` of them have been handed out; the snapshot is the chains'
   // state (and the running summaries) at the start of the batch, which is what
-  // a rewind restores before replaying the la_served draws already seen.
-  int la_len = 1, la_avail = 0, la_served = 0;
-  // host copies of the batch's record for the chains the caller reads (the
-  // per-iteration loop reads chain 0 after every draw: one set of copies per
-  // batch instead of per call); la_synced: the batch's launch has been waited for
-  // and its chain statuses checked
-  struct LaRows { std::vector<double> k, sig, beta; std::vector<uint16_t> idx; };
-  std::unordered_map<int64_t, LaRows> la_cache;
-  bool la_synced = false;
-  // Overlapping look-ahead batches: the record holds two batches (halves la_slot and
-  // la_slot ^ 1 of 2 la_len rows), the batch after the one being served is launched as soon
-  // as serving starts (la_ahead) and the launches hand chains over (pipelined sweeps); each
-  // batch's workgroups save their chain's state on entry (snapshot set = half) for rewinds.
-  bool la_pipe = true;        // allowed (off for good after a batch had to be redone the old way)
-  bool la_cur_piped = false;  // the batch being served was launched that way
-  bool la_ahead = false;
-  int la_slot = 0;
-  hipEvent_t la_done[2] = {nullptr, nullptr};
-  DevBuf<uint8_t> snap_gamma;
-  DevBuf<double> snap_beta, snap_sigsq, snap_bsum, snap_bsumsq, snap_acc;
-  DevBuf<uint16_t> snap_perm;
-  DevBuf<uint64_t> snap_pos;
-  DevBuf<int32_t> snap_fail;
-  DevBuf<uint32_t> snap_inc;
+  // a rewind restores before replaying the `served` draws already seen.
+  struct La {
+    int len = 1, avail = 0, served = 0;
+    // host copies of the batch's record for the chains the caller reads (the
+    // per-iteration loop reads chain 0 after every draw: one set of copies per
+    // batch instead of per call); synced: the batch's launch has been waited for
+    // and its chain statuses checked
+    struct Rows { std::vector<double> k, sig, beta; std::vector<uint16_t> idx; };
+    std::unordered_map<int64_t, Rows> cache;
+    bool synced = false;
+    // Overlapping look-ahead batches: the record holds two batches (halves slot and
+    // slot ^ 1 of 2 len rows), the batch after the one being served is launched as soon
+    // as serving starts (ahead) and the launches hand chains over (pipelined sweeps); each
+    // batch's workgroups save their chain's state on entry (snapshot set = half) for rewinds.
+    bool pipe = true;        // allowed (off for good after a batch had to be redone the old way)
+    bool cur_piped = false;  // the batch being served was launched that way
+    bool ahead = false;
+    int slot = 0;
+    hipEvent_t done[2] = {nullptr, nullptr};
+    // two sets of every per-chain array a sweep changes; which live array, how many elements
+    // per chain and which SsvsParams member each goes with: la_snap_fields (engine.hip)
+    struct Snap {
+      DevBuf<uint8_t> gamma;
+      DevBuf<double> beta, sigsq, bsum, bsumsq, acc;
+      DevBuf<uint16_t> perm;
+      DevBuf<uint64_t> pos;
+      DevBuf<int32_t> fail;
+      DevBuf<uint32_t> inc;
+    } snap;
+  } la;
   int rec_cap = 64;  // variables per recorded draw (ba_enable_draws)
   // HBM-resident path for models of more than 64 variables (ssvs_big_kernel.hip):
   // active once a chain has outgrown the LDS kernel, capacity grows on demand
@@ -303,14 +309,16 @@ struct ba_engine {
   hipEvent_t ev_state = nullptr, ev_prep[2] = {nullptr, nullptr};
   int ss_zbuf = 0;   // the normals buffer the next state draw reads
   // pipelined sweeps: consecutive ba_sweep launches alternate between `stream` and
-  // pipe_stream and hand chains over through a ring of four queues (ssvs_kernel.hip)
-  hipStream_t pipe_stream = nullptr;
-  hipEvent_t pipe_ev[4] = {}, pipe_join_ev = nullptr;
-  DevBuf<int32_t> dpipe_q, dpipe_err;
-  bool pipe_on = false;      // the last thing enqueued was a pipelined sweep launch
-  bool pipe_unchecked = false;   // a pipelined launch has gone out since the error word was last read
-  int pipe_k = 0;            // launches in the current pipeline
-  bool pipe_groups = false;  // ... which are the chain GROUPS of an engine of more chains than the machine holds
+  // pipe.stream and hand chains over through a ring of four queues (ssvs_kernel.hip)
+  struct Pipe {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[4] = {}, join_ev = nullptr;
+    DevBuf<int32_t> q, err;
+    bool on = false;         // the last thing enqueued was a pipelined sweep launch
+    bool unchecked = false;  // a pipelined launch has gone out since the error word was last read
+    int k = 0;               // launches in the current pipeline
+    bool groups = false;     // ... which are the chain GROUPS of an engine of more chains than the machine holds
+  } pipe;
   DevBuf<int32_t> dprep_n;
   DevBuf<uint64_t> dprep_pos_state, dprep_pos_level;
   DevBuf<double> dprep_level;
@@ -455,6 +463,10 @@ int concurrent_stream(ba_engine *e, hipStream_t *out);
 int pipe_join(ba_engine *e);
 int la_rewind(ba_engine *e);
 int la_copy(ba_engine *e, bool save, int set = 0);
+// what both look-aheads do with launches that ran ahead of the caller: read every chain's
+// status word (*ok: all CHAIN_OK), and forget what dropped launches left behind
+int all_chains_ok(ba_engine *e, bool *ok);
+int drop_launched_ahead(ba_engine *e);
 // BA_OK when the engine holds the data the entry point samples (`wants`; sss: ba_sss_sweep,
 // the other sweep of plain regression data), else the entry point's refusal for the kind held
 int sweep_refusal(const ba_engine *e, DataKind wants, bool sss = false);

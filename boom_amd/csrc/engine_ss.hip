@@ -213,6 +213,12 @@ static __global__ __launch_bounds__(256) void ss_record_kernel(SsRecParams R) {
 }
 
 static bool ss_la_on(const ba_engine *e) { return e->ssla.len > 1; }
+// (while the look-ahead itself calls entry points: they do not settle it again)
+struct SsLaBusy {
+  ba_engine::SsLa &a;
+  explicit SsLaBusy(ba_engine::SsLa &la) : a(la) { a.busy = true; }
+  ~SsLaBusy() { a.busy = false; }
+};
 bool ss_la_serving(const ba_engine *e) { return e->ssla.len > 1 && e->ssla.avail > 0 && !e->ssla.busy; }
 
 static hipError_t ss_la_record(ba_engine *e, int slot, int round) {
@@ -255,6 +261,40 @@ static hipError_t ss_la_record(ba_engine *e, int slot, int round) {
   return hipGetLastError();
 }
 
+// The state-space half of what a snapshot holds -- THE list: f(live array, elements, words),
+// the doubles (into SsLa::snap) in this order, then the stream positions (words: into
+// SsLa::snap_pos).  ss_la_alloc sizes the two buffers by a pass over it, ss_la_copy walks
+// them by the same pass (a field whose live array is not allocated keeps its place).
+//   level (sigsq, n, sumsq) | xty | yty | nobs [| state models: sigsq, n, ss | phi | ar suf]
+template <class F>
+static int ss_snap_fields(const ba_engine *e, F f) {
+  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p;
+  hipError_t ss_snapshot = hipSuccess;
+  auto field = [&](auto *live, size_t n) {
+    static_assert(sizeof(*live) == 8, "doubles and 64-bit stream positions");
+    if (ss_snapshot == hipSuccess)
+      ss_snapshot = f((void *)live, n, std::is_integral<std::remove_pointer_t<decltype(live)>>::value);
+  };
+  field(e->dlev_sigsq.ptr, C);
+  field(e->dlev_n.ptr, C);
+  field(e->dlev_sumsq.ptr, C);
+  field(e->dxty_c.ptr, C * p);
+  field(e->dyty_c.ptr, C);
+  field(e->dnobs_c.ptr, C);
+  if (e->ssm_set) {
+    field(e->dssm_sigsq.ptr, C * SSG_MAX_VAR);
+    field(e->dssm_n.ptr, C * SSG_MAX_VAR);
+    field(e->dssm_ss.ptr, C * SSG_MAX_VAR);
+    field(e->dar_phi.ptr, e->ssg.nar > 0 ? C * SSG_MAX_AR * AR_MAX : 0);
+    field(e->dar_suf.ptr, e->ssg.nar > 0 ? C * SSG_MAX_AR * AR_SUF_STRIDE : 0);
+  }
+  field(e->dpos_level.ptr, C);
+  field(e->dpos_state.ptr, C);
+  if (e->ssm_set) field(e->dpos_var.ptr, C * SSG_MAX_VAR);
+  HIP_TRY(ss_snapshot);
+  return BA_OK;
+}
+
 // the record's and the snapshots' buffers for the current specification
 static int ss_la_alloc(ba_engine *e) {
   ba_engine::SsLa &A = e->ssla;
@@ -287,13 +327,11 @@ static int ss_la_alloc(ba_engine *e) {
     HIP_TRY(e->dround_reg.resize(C));
     HIP_TRY(hipMemcpy(e->dround_reg.ptr, of.data(), C * 4, hipMemcpyHostToDevice));
   }
-  // snapshot: level (sigsq, n, sumsq) | xty | yty | nobs [| state models: sigsq, n, ss | phi | ar suf]
-  A.snap_doubles = C * (3 + p + 2);
-  A.snap_words = 2 * C;
-  if (e->ssm_set) {
-    A.snap_doubles += C * (3 * SSG_MAX_VAR + SSG_MAX_AR * AR_MAX + SSG_MAX_AR * AR_SUF_STRIDE);
-    A.snap_words += C * SSG_MAX_VAR;
-  }
+  A.snap_doubles = A.snap_words = 0;
+  (void)ss_snap_fields(e, [&](void *, size_t n, bool words) {
+    (words ? A.snap_words : A.snap_doubles) += n;
+    return hipSuccess;
+  });
   HIP_TRY(A.snap.resize(2 * A.snap_doubles));
   HIP_TRY(A.snap_pos.resize(2 * A.snap_words));
   for (int i = 0; i < 2; ++i)
@@ -306,52 +344,22 @@ static int ss_la_copy(ba_engine *e, bool save, int set) {
   ba_engine::SsLa &A = e->ssla;
   int rc = la_copy(e, save, set);
   if (rc) return rc;
-  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p;
-  hipStream_t s = e->stream;
-  double *d = A.snap.ptr + (size_t)set * A.snap_doubles;
-  uint64_t *w = A.snap_pos.ptr + (size_t)set * A.snap_words;
-#define SS_CP(live, n, T_)                                                                     \
-  do {                                                                                          \
-    const size_t bytes__ = (size_t)(n) * sizeof(T_);                                            \
-    if ((live) && bytes__)                                                                      \
-      HIP_TRY(hipMemcpyAsync(save ? (void *)cur__ : (void *)(live), save ? (const void *)(live) : (const void *)cur__, \
-                             bytes__, hipMemcpyDeviceToDevice, s));                             \
-    cur__ += (n);                                                                               \
-  } while (0)
-  {
-    double *cur__ = d;
-    SS_CP(e->dlev_sigsq.ptr, C, double);
-    SS_CP(e->dlev_n.ptr, C, double);
-    SS_CP(e->dlev_sumsq.ptr, C, double);
-    SS_CP(e->dxty_c.ptr, C * p, double);
-    SS_CP(e->dyty_c.ptr, C, double);
-    SS_CP(e->dnobs_c.ptr, C, double);
-    if (e->ssm_set) {
-      SS_CP(e->dssm_sigsq.ptr, C * SSG_MAX_VAR, double);
-      SS_CP(e->dssm_n.ptr, C * SSG_MAX_VAR, double);
-      SS_CP(e->dssm_ss.ptr, C * SSG_MAX_VAR, double);
-      SS_CP(e->dar_phi.ptr, e->ssg.nar > 0 ? C * SSG_MAX_AR * AR_MAX : 0, double);
-      SS_CP(e->dar_suf.ptr, e->ssg.nar > 0 ? C * SSG_MAX_AR * AR_SUF_STRIDE : 0, double);
-    }
-  }
-  {
-    uint64_t *cur__ = w;
-    SS_CP(e->dpos_level.ptr, C, uint64_t);
-    SS_CP(e->dpos_state.ptr, C, uint64_t);
-    if (e->ssm_set) SS_CP(e->dpos_var.ptr, C * SSG_MAX_VAR, uint64_t);
-  }
-#undef SS_CP
-  return BA_OK;
+  char *held[2] = {(char *)(A.snap.ptr + (size_t)set * A.snap_doubles), (char *)(A.snap_pos.ptr + (size_t)set * A.snap_words)};
+  return ss_snap_fields(e, [&](void *live, size_t n, bool words) {
+    void *cur = held[words];
+    held[words] += n * 8;
+    if (!live || !n) return hipSuccess;
+    return hipMemcpyAsync(save ? cur : live, save ? live : cur, n * 8, hipMemcpyDeviceToDevice, e->stream);
+  });
 }
 
 // enqueue one batch into half `slot`: the snapshot of where it starts, then `len` rounds,
 // each followed by its record
 static int ss_la_launch(ba_engine *e, int slot) {
   ba_engine::SsLa &A = e->ssla;
-  A.busy = true;
+  SsLaBusy busy(A);
   int rc = ss_la_copy(e, true, slot);
   if (!rc) rc = ss_sweep_impl(e, A.cur, slot);
-  A.busy = false;
   if (rc) return rc;
   HIP_TRY(hipEventRecord(A.done[slot], e->stream));
   return BA_OK;
@@ -372,8 +380,7 @@ static void ss_la_reset(ba_engine *e) {
 int ss_la_settle(ba_engine *e) {
   ba_engine::SsLa &A = e->ssla;
   if (A.len <= 1 || A.busy || A.avail == 0) return BA_OK;
-  A.busy = true;
-  struct Unbusy { ba_engine::SsLa &a; ~Unbusy() { a.busy = false; } } unbusy{A};
+  SsLaBusy busy(A);
   HIP_TRY(hipSetDevice(e->cfg.device));
   HIP_TRY(hipStreamSynchronize(e->stream));
   if (e->stream2) HIP_TRY(hipStreamSynchronize(e->stream2));
@@ -392,14 +399,8 @@ int ss_la_settle(ba_engine *e) {
   A.cur = std::max(1, A.cur / 2);
   A.calm = 0;
   int rc = ss_la_copy(e, false, slot);
+  if (!rc) rc = drop_launched_ahead(e);
   if (rc) return rc;
-  {  // (a chain that stopped in the dropped rounds stopped after the point we return to)
-    const size_t C = (size_t)e->cfg.chains;
-    HIP_TRY(hipMemsetAsync(e->dstatus.ptr, 0, C * 4, e->stream));
-    HIP_TRY(hipMemsetAsync(e->dtodo.ptr, 0, C * 4, e->stream));
-  }
-  e->table_ok = false;
-  e->model_ok = false;
   if (served > 0) {
     rc = ss_sweep_impl(e, served, -1);
     if (rc) return rc;
@@ -415,24 +416,18 @@ int ss_la_wait(ba_engine *e) {
   ba_engine::SsLa &A = e->ssla;
   if (A.synced) return BA_OK;
   HIP_TRY(hipEventSynchronize(A.done[A.slot]));
-  const size_t C = (size_t)e->cfg.chains;
-  std::vector<int32_t> st(C);
-  HIP_TRY(hipMemcpy(st.data(), e->dstatus.ptr, C * 4, hipMemcpyDeviceToHost));
   bool ok = true;
-  for (size_t c = 0; c < C; ++c) ok = ok && st[c] == CHAIN_OK;
+  int rc = all_chains_ok(e, &ok);
+  if (rc) return rc;
   if (!ok) {
-    A.busy = true;
-    struct Unbusy { ba_engine::SsLa &a; ~Unbusy() { a.busy = false; } } unbusy{A};
+    SsLaBusy busy(A);
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (e->stream2) HIP_TRY(hipStreamSynchronize(e->stream2));
     const int slot = A.slot;
     A.ahead = false;
-    int rc = ss_la_copy(e, false, slot);
+    rc = ss_la_copy(e, false, slot);
+    if (!rc) rc = drop_launched_ahead(e);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(e->dstatus.ptr, 0, C * 4, e->stream));
-    HIP_TRY(hipMemsetAsync(e->dtodo.ptr, 0, C * 4, e->stream));
-    e->table_ok = false;
-    e->model_ok = false;
     rc = ss_la_copy(e, true, slot);   // (the same starting point, for a later settle)
     for (int i = 0; i < A.avail && !rc; ++i) {
       rc = ss_sweep_impl(e, 1, -1);

@@ -353,6 +353,53 @@ def test_overlapping_lookahead_batches_survive_a_capacity_stop():
     assert gam.sum(axis=1).max() > 16       # the models did outgrow the first capacity
 
 
+def test_non_overlapping_lookahead_batches_rewind():
+    """timing without overlap: the look-ahead's batches cannot overlap, so the copy of the
+    chains taken before a batch is the only snapshot and every mutator goes back through it
+    -- mid-batch, exactly at a batch's last served draw, before plain sweeps and before a
+    state write; the draws stay those of one launch per call"""
+    suf, prior, g0 = _case()
+    chains, L = 6, 10
+    a = make_engine(chains, 8, suf=suf, prior=prior, g0=g0)
+    b = make_engine(chains, 8, suf=suf, prior=prior, g0=g0)
+    b.set_lookahead(L)
+    b.set_kernel_timing(True)
+    a.reset_summaries()
+    b.reset_summaries()
+
+    def draws(n):
+        for _ in range(n):
+            a.sweep(1)
+            b.draw_next()
+            assert _same(a.get_state(0), b.get_state(0))
+            assert _same(a.get_states(), b.get_states())
+
+    draws(L + 3)                 # 3 draws into the second batch
+    a.set_options(max_flips=17)
+    b.set_options(max_flips=17)  # rewinds 7 unserved draws, replays 3
+    assert _same(a.get_states(), b.get_states())
+    draws(L)                     # a whole batch: its last draw is the one being served
+    a.set_options(max_flips=-1)
+    b.set_options(max_flips=-1)
+    assert _same(a.get_states(), b.get_states())
+    draws(2)
+    a.sweep(4)
+    b.sweep(4)                   # plain sweeps continue after the last SERVED draw
+    assert _same(a.get_states(), b.get_states())
+    draws(3)
+    g1 = np.zeros(len(g0), np.uint8)
+    g1[[0, 2, 5]] = 1
+    beta1 = np.linspace(0, 1, len(g0)) * g1
+    a.set_state(g1, beta1, 0.7, chain=2)
+    b.set_state(g1, beta1, 0.7, chain=2)
+    draws(8)
+    for x in (a, b):
+        x.set_options(max_flips=-1)  # (a mutator: the look-ahead engine drops what it ran ahead)
+    sa, sb = a.get_summaries(), b.get_summaries()
+    assert sa["sweeps"] == sb["sweeps"] > 0
+    assert np.array_equal(sa["inclusion_count"], sb["inclusion_count"])
+
+
 def test_twice_as_many_chains_as_fit_go_out_as_two_launches(oracle):
     """exactly 2 x (4 chains per CU) chains: the engine issues the sweep as two launches of
     resident size (one multi-round launch starts a few workgroups a round late on this
