@@ -63,6 +63,7 @@ SIGNATURES = {
     "ba_get_priors": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _dp]),
     "ba_set_options": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_int32]),
     "ba_set_tuning": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "ba_set_rebuild_policy": (C.c_int, [C.c_void_p, C.c_int32]),
     "ba_set_lookahead": (C.c_int, [C.c_void_p, C.c_int32]),
     "ba_draw_next": (C.c_int, [C.c_void_p]),
     "ba_set_state": (C.c_int, [C.c_void_p, C.c_int64, _u8p, _dp, C.c_double]),
@@ -317,6 +318,11 @@ class Engine:
     def set_tuning(self, waves_per_chain=0, walk_policy=-1, kcap_start=0):
         self._check(self.lib.ba_set_tuning(self._h, waves_per_chain, walk_policy, kcap_start))
 
+    def set_rebuild_policy(self, policy):
+        """how an accepted (or exactly evaluated) single flip rebuilds the factors: 0 keeps
+        the columns the flip leaves unchanged, 1 factors from scratch; same draws either way"""
+        self._check(self.lib.ba_set_rebuild_policy(self._h, int(policy)))
+
     # ---- state --------------------------------------------------------------
     def set_state(self, gamma, beta=None, sigsq=1.0, chain=-1):
         g = np.ascontiguousarray(gamma, dtype=np.uint8)
@@ -411,7 +417,11 @@ class Engine:
                     slot_hits=float(sc[7]), phase_cycles=sc[8:16].copy(),
                     # after adaptive sweeps: closest approach of a weighted-draw
                     # uniform to a boundary of the cumulative rates
-                    min_multi_margin=float(sc[8]))
+                    min_multi_margin=float(sc[8]),
+                    # after plain sweeps of the product library: rebuilds that kept the
+                    # leading factor columns, and how many columns they kept (the
+                    # diagnostic stamp builds use these slots for cycles)
+                    partial_rebuilds=float(sc[9]), columns_kept=float(sc[10]))
 
     def summaries_device(self, ptr):
         self._check(self.lib.ba_summaries_device(self._h, ptr))

@@ -15,6 +15,12 @@
 //                                              rounds, 2 links, 3 walks, 4 table walk, 5
 //                                              waiting for commands, 6 its share of proposal
 //                                              rounds, 7 other                                core
+//   -DBA_STAMPS -DBA_STAMPS5  FSTAMP(c, i)     a model rebuild (refactor and its site): 0
+//                                              gathers, prior sum, row shift, r and c, 1 the
+//                                              inserted row, 2 the column loop and the log
+//                                              determinants, 3 w and the model's value, 4
+//                                              publish / restore; 5 and 6 are COUNTS (rebuilds,
+//                                              columns kept); 7 everything else               core
 //   -DBA_PSTAMPS              PSTAMP(i)        the sweep kernel's prologue (absolute stamps)  core
 //   -DBA_KSTAMPS              KSTAMP(i)        the local-level Kalman kernel's phases, and
 //                             SSTAMP(i)        the structural kernels' (chain 0 prints)       core
@@ -52,6 +58,13 @@ struct StampCtx { long long last; double ph[8]; };
 #define HSTAMP(c, i) BA_STAMP_ADD((c).ph, (c).last, i, BA_CORE_CLOCK, double)
 #else
 #define HSTAMP(c, i) BA_STAMP_OFF
+#endif
+#if defined(BA_STAMPS) && defined(BA_STAMPS5)
+#define FSTAMP(c, i) BA_STAMP_ADD((c).ph, (c).last, i, BA_CORE_CLOCK, double)
+#define FCOUNT(c, i, x) do { (c).ph[i] += (double)(x); } while (0)
+#else
+#define FSTAMP(c, i) BA_STAMP_OFF
+#define FCOUNT(c, i, x) BA_STAMP_OFF
 #endif
 #ifdef BA_PSTAMPS
 #define PSTAMP(i) pst[i] = (long long)BA_CORE_CLOCK

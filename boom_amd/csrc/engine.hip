@@ -367,6 +367,7 @@ void fill_params(ba_engine *e, SsvsParams &P) {
   P.stream = 0;
   P.mode = e->cur_mode;
   P.walk_policy = e->tune_walk_policy >= 0 ? e->tune_walk_policy : 1;  // (see ssvs_params.h)
+  P.rebuild_policy = e->tune_rebuild_policy;
   if (e->cur_mode == 1) {
     // SpikeSlabSampler: given sigma^2, no sigma draw, no swap move, own stream
     P.slab_scales = e->sss_slab_scales;
@@ -1364,6 +1365,16 @@ int ba_set_tuning(ba_engine *e, int32_t waves_per_chain, int32_t walk_policy,
   e->tune_walk_policy = walk_policy;
   e->tune_kcap_start = kcap_start;
   e->device_dirty = true;  // capacity and waves are chosen again
+  return BA_OK;
+}
+
+// How the sweep kernels rebuild the factors after a single flip (ssvs_params.h).  Either way
+// computes the same numbers, so nothing kept on the device -- tables, model blocks, a
+// look-ahead batch -- is dropped: the next launch simply reads the new value.
+int ba_set_rebuild_policy(ba_engine *e, int32_t policy) {
+  if (!e) return fail(BA_E_INVALID, "null engine");
+  if (policy != 0 && policy != 1) return fail(BA_E_INVALID, "rebuild_policy must be 0 or 1");
+  e->tune_rebuild_policy = policy;
   return BA_OK;
 }
 

@@ -269,6 +269,7 @@ struct ba_engine {
   DevBuf<double> dbig_model, dbig_xs;
   // ba_set_tuning overrides (0 / -1: the engine chooses)
   int tune_waves = 0, tune_walk_policy = -1, tune_kcap_start = 0;
+  int tune_rebuild_policy = 0;   // SsvsParams::rebuild_policy (ba_set_rebuild_policy)
   // SpikeSlabSampler (sigma^2 given) mode
   int cur_mode = 0;          // mode of the launches in flight (0 BregVs, 1 SSS)
   int sss_slab_scales = 1;   // slab precision = Omega^{-1} / sigma^2

@@ -185,12 +185,14 @@ __device__ __forceinline__ void bind_lds(Chain &ch, unsigned char *smem,
 // chains (dot product, sqrt, divide) interleave, which is what a single
 // wavefront per SIMD needs.  A failed factorisation stops advancing (its
 // remaining columns are never used); the other one carries on.
+// j0: the first column to compute -- columns < j0 of both triangles already hold the
+// factors' (positive pivots, rdA / rdV filled), columns >= j0 the matrices' elements.
 __device__ __forceinline__ void chol_blocks2(const Chain &ch, lds_f64 *LA, lds_f64 *rdA,
                                              lds_f64 *LV, lds_f64 *rdV, bool *okA,
-                                             bool *okV, double *ldA, double *ldV) {
+                                             bool *okV, double *ldA, double *ldV, int j0 = 0) {
   const int k = ch.k, i = ch.lane;
   bool oa = true, ov = true;
-  for (int j = 0; j < k && (oa || ov); ++j) {
+  for (int j = j0; j < k && (oa || ov); ++j) {
     const bool mine = (i >= j) && (i < k);
     const int ii = mine ? i : j;  // lanes without a row read row j (discarded)
     const int jb = j >> 3;
@@ -273,9 +275,21 @@ __device__ __forceinline__ void chol_blocks2(const Chain &ch, lds_f64 *LA, lds_f
 // already in LDS / M -- restored from the chain's block at the start of a
 // launch -- and only what depends on the sufficient statistics X'y, y'y is
 // recomputed (state-space path: they move every sweep).
+// q >= 0 (wave-uniform; the sweep body's rebuild site only): gamma is the model whose factors
+// LDS holds -- both positive definite -- with ONE variable inserted at (ins) or dropped from
+// position q of the sorted list.  A left-looking column j reads rows and columns <= j of the
+// matrix and columns < j of the factor, so columns < q of both new factors are the old ones
+// bit for bit -- the same products subtracted in the same order -- with the rows from q on
+// moved by one.  They are kept: rows shifted in place, the new row q by one forward
+// substitution, columns q.. by the column loop.  Everything summed over all of g in column
+// order (log determinants, r, c, w, Q) is recomputed in full, as an inserted term changes
+// the rounding.
 template <bool REUSE, bool MLVS = false>
-__device__ __forceinline__ void refactor(const SsvsParams &P, Chain &ch, Model &M, StampCtx &sx) {
+__device__ __forceinline__ void refactor(const SsvsParams &P, Chain &ch, Model &M, StampCtx &sx,
+                                         int q = -1, bool ins = false) {
   const int lane = ch.lane, p = ch.p, k = ch.k;
+  const bool part = !REUSE && q >= 0;
+  const int q0 = part ? q : 0;   // first column to compute
   M.bad = 0;
   M.pd = true;
   double lp;
@@ -288,7 +302,11 @@ __device__ __forceinline__ void refactor(const SsvsParams &P, Chain &ch, Model &
   // one-sweep launch is the chain the whole launch waits for.
   wave_sync();
   const int kpad = (k + 7) & ~7;
-  const int nelem = REUSE ? 0 : kpad * (kpad + 1) / 2;
+  // what is gathered: rows and columns q0.. of the triangles -- from scratch all kpad rows
+  // (the padding rows as zeros), after one flip rows q0..k-1 (the padding rows are zeroed
+  // below), element e <-> (q0 + m, q0 + n) -- and, for an insertion, row q0's columns < q0
+  const int kt = part ? k - q0 : kpad;
+  const int nelem = REUSE ? 0 : kt * (kt + 1) / 2;
   const int gm = (lane < k) ? ch.g[lane] : 0;
   const double bm = (lane < k) ? P.b[gm] : 0.0;
   const double xg = (lane < k) ? ch.xty[gm] : 0.0;
@@ -300,13 +318,19 @@ __device__ __forceinline__ void refactor(const SsvsParams &P, Chain &ch, Model &
     int m = (int)((sqrtf(8.0f * (float)lane + 1.0f) - 1.0f) * 0.5f);
     while ((m + 1) * (m + 2) / 2 <= lane) ++m;
     while (m * (m + 1) / 2 > lane) --m;
-    m0 = m;
-    n0 = lane - m * (m + 1) / 2;
-    if (m < k) {
-      const size_t o = (size_t)ch.g[m] * p + ch.g[n0];
+    m0 = m + q0;
+    n0 = lane - m * (m + 1) / 2 + q0;
+    if (m0 < k) {
+      const size_t o = (size_t)ch.g[m0] * p + ch.g[n0];
       v0 = P.V[o] * ch.sv;
       a0 = P.A[o] * ch.sa;
     }
+  }
+  double xv = 0.0, xa = 0.0;   // lane n < q0: element (q0, n) of an inserted row
+  if (part && ins && lane < q0) {
+    const size_t o = (size_t)ch.g[q0] * p + gm;
+    xv = P.V[o] * ch.sv;
+    xa = P.A[o] * ch.sa;
   }
   if (REUSE) {
     lp = M.lp;
@@ -337,6 +361,33 @@ __device__ __forceinline__ void refactor(const SsvsParams &P, Chain &ch, Model &
     M.pd = false;
     return;
   }
+  if (part) {
+    // Columns < q0 of the rows from q0 on move down (insertion) or up (drop) by one row, in
+    // place: eight columns of a lane's source row are read, then written (the lanes of a
+    // wavefront read before any of them writes).  Lanes that move nothing read row q0.
+    const bool mv = lane < k && (ins ? lane > q0 : lane >= q0);
+    const int rs = mv ? (ins ? lane - 1 : lane + 1) : q0, rw = mv ? lane : q0;
+    for (int cb = 0; cb * 8 < q0; ++cb) {
+      const int so = bidx(rs, cb * 8), wo = bidx(rw, cb * 8);
+      double tv[8], ta[8];
+#pragma unroll
+      for (int t = 0; t < 8; ++t) { tv[t] = ch.Lv[so + t]; ta[t] = ch.La[so + t]; }
+      wave_sync();
+#pragma unroll
+      for (int t = 0; t < 8; ++t)
+        if (mv && cb * 8 + t < q0) { ch.Lv[wo + t] = tv[t]; ch.La[wo + t] = ta[t]; }
+      wave_sync();
+    }
+    // the padding rows of the last block row: the row a drop vacates, a block row an
+    // insertion opens (k: 8 -> 9, ...) -- zeros, as a factorisation from scratch leaves them
+    if (lane >= k && lane < kpad) {
+      for (int cb = 0; cb * 8 < kpad; ++cb) {
+        const int wo = bidx(lane, cb * 8);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) { ch.Lv[wo + t] = 0.0; ch.La[wo + t] = 0.0; }
+      }
+    }
+  }
   if (!REUSE && lane < nelem) {
     ch.Lv[bidx(m0, n0)] = v0;
     ch.La[bidx(m0, n0)] = a0;
@@ -345,7 +396,8 @@ __device__ __forceinline__ void refactor(const SsvsParams &P, Chain &ch, Model &
     int m = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
     while ((m + 1) * (m + 2) / 2 <= e) ++m;
     while (m * (m + 1) / 2 > e) --m;
-    const int n = e - m * (m + 1) / 2;
+    const int n = e - m * (m + 1) / 2 + q0;
+    m += q0;
     double v = 0.0, a = 0.0;
     if (m < k) {
       const size_t o = (size_t)ch.g[m] * p + ch.g[n];
@@ -375,14 +427,54 @@ __device__ __forceinline__ void refactor(const SsvsParams &P, Chain &ch, Model &
   }
   const double r = (lane < k) ? ab + xg * ch.sx : 0.0;
   M.c = wave_sum(lane < k ? bm * ab : 0.0);
+  FSTAMP(sx, 0);
+  if (part && ins) {
+    // The inserted row: L[q0][n] = (M[q0][n] - sum_{t < n} L[q0][t] L[n][t]) / L[n][n], n < q0,
+    // for both factors side by side -- lane n holds element n of the row and, once column j
+    // is final, subtracts L[n][j] L[q0][j] (its own row's columns, eight per LDS trip).  That
+    // is the product column step n of the factorisation subtracts for row q0, in the same
+    // ascending order and the same s -= a * b form, then the same division by the stored
+    // diagonal: the row is bitwise the one a factorisation from scratch computes.
+    const double dgv = (lane < q0) ? ch.Lv[bidx(lane, lane)] : 1.0;
+    const double dga = (lane < q0) ? ch.La[bidx(lane, lane)] : 1.0;
+#pragma nounroll
+    for (int jb = 0; jb * 8 < q0; ++jb) {
+      double lv[8], la[8];
+      const int rowm = (lane >= jb * 8 && lane < q0) ? lane : jb * 8;
+      const int base = bidx(rowm, jb * 8);
+#pragma unroll
+      for (int t = 0; t < 8; ++t) { lv[t] = ch.Lv[base + t]; la[t] = ch.La[base + t]; }
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        const int j = jb * 8 + t;
+        if (j < q0) {
+          const double ev = bcast_u(xv, j) / bcast_u(dgv, j);
+          const double ea = bcast_u(xa, j) / bcast_u(dga, j);
+          if (lane == j) {
+            xv = ev;
+            xa = ea;
+          } else if (lane > j && lane < q0) {
+            xv -= lv[t] * ev;
+            xa -= la[t] * ea;
+          }
+        }
+      }
+    }
+    if (lane < q0) {
+      ch.Lv[bidx(q0, lane)] = xv;
+      ch.La[bidx(q0, lane)] = xa;
+    }
+  }
   wave_sync();
+  FSTAMP(sx, 1);
   bool okv = true, oka = true;
   if (REUSE) {
     M.lda = lda_in;
     M.ldv = ldv_in;
   } else {
-    chol_blocks2(ch, ch.La, ch.rda, ch.Lv, ch.rdv, &oka, &okv, &M.lda, &M.ldv);
+    chol_blocks2(ch, ch.La, ch.rda, ch.Lv, ch.rdv, &oka, &okv, &M.lda, &M.ldv, q0);
   }
+  FSTAMP(sx, 2);
   if (!okv) {
     M.pd = false;
     M.logp = -BA_INF;
@@ -438,8 +530,9 @@ __device__ __forceinline__ void refactor(const SsvsParams &P, Chain &ch, Model &
   M.logp = lp + 0.5 * (M.lda - M.ldv) - (0.5 * ch.DF - 1.0) * log(M.SS);
 }
 
-// flip variable j in the LDS copy of gamma and in the sorted list g
-__device__ __forceinline__ void apply_flip(Chain &ch, int j) {
+// flip variable j in the LDS copy of gamma and in the sorted list g; returns j's position
+// in the list (where it was put, or where it was taken from)
+__device__ __forceinline__ int apply_flip(Chain &ch, int j) {
   const int lane = ch.lane, k = ch.k;
   const int gm = (lane < k) ? ch.g[lane] : 0x7fffffff;
   const int below = __popcll(__ballot(lane < k && gm < j));
@@ -458,6 +551,7 @@ __device__ __forceinline__ void apply_flip(Chain &ch, int j) {
     ch.k = k - 1;
   }
   wave_sync();
+  return below;
 }
 
 // point the chain at one of its two (table, model block) slots

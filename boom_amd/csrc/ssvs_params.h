@@ -41,8 +41,12 @@ enum {
   ACC_SLOT_HITS = 7,  // accepted flips served from the chain's other slot (diagnostic stamp builds: slowest chain's cycles)
   // 8..15: per-phase cycle counters, filled only by the -DBA_STAMPS diagnostic
   // build (shuffle uniforms, shuffle serial, refactor, proposal batches, swap,
-  // sigma, beta, rest); zero in the production library
+  // sigma, beta, rest).  The production library's LDS sweep kernels count in two of them:
+  // rebuilds that kept leading factor columns, and the columns they kept
+  // (SsvsParams::rebuild_policy; not slot 8, where the adaptive sampler keeps a margin)
   ACC_PHASE0 = 8,
+  ACC_PARTIAL_REBUILDS = 9,
+  ACC_COLUMNS_KEPT = 10,
   ACC_COUNT = 16
 };
 
@@ -213,6 +217,13 @@ struct SsvsParams {
   // shared by the chains, and every chain's weighted_sum_of_squares of this sweep's imputation
   const uint16_t *flip_order;
   const double *wss;       // chains
+  // How the sweep body rebuilds the factors when one variable enters or leaves the model at
+  // position q of the sorted list: 0 keeps columns < q of both factors (bitwise what a
+  // factorisation from scratch gives: a left-looking column reads nothing right of itself)
+  // and computes the new row and the columns from q on; 1 always factors from scratch.
+  // (Last on purpose: a field added in the middle of this struct moved the kernel arguments
+  // the quiet sweep reads and cost the headline 1.7 %, docs/TRIED.md round 3.)
+  int32_t rebuild_policy;
 };
 
 // ---- LDS layout of one chain (one wavefront) --------------------------------

@@ -256,7 +256,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
   AS_LDS int *sum_n = to_lds<int>(smem + lay.park + 1536);   // sweeps counted
   AS_LDS int *sum_g = to_lds<int>(smem + lay.park + 1792);   // variable (-1: none)
   sum_b[lane] = 0.0; sum_b2[lane] = 0.0; sum_n[lane] = 0; sum_g[lane] = -1;
-  if (lane < 8) ctl[CT_ACC + lane] = (lane == ACC_MIN_MARGIN) ? BA_INF : 0.0;
+  if (lane < 11) ctl[CT_ACC + lane] = (lane == ACC_MIN_MARGIN) ? BA_INF : 0.0;
   wave_sync();
 #define ACC_ADD(slot, x) do { if (lane == 0) ctl[CT_ACC + (slot)] += (double)(x); } while (0)
 #define ACC_MIN(x) do { if (lane == 0) ctl[CT_ACC + ACC_MIN_MARGIN] = fmin(ctl[CT_ACC + ACC_MIN_MARGIN], (x)); } while (0)
@@ -345,9 +345,11 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
 
   PSTAMP(4);
   while (status == CHAIN_OK) {
-    if constexpr ((W > 1 && !(NB == 4 && W == 2)) || (W == 1 && NB >= 4)) {
+    if constexpr ((W > 1 && !(NB == 4 && W == 2)) || (W == 1 && NB >= 4) || (MLVS && NB == 2)) {
       // (every multi-wave instance but the headline's <4, 2, 2>, which needs no scratch as it
-      // is: what the compiler derives from the lane number once before this loop
+      // is -- and the MLVS instance <2, 1, 1>, which took 68 B/lane of scratch when the rebuild
+      // site grew the partial rebuild and needs none this way: what the compiler derives
+      // from the lane number once before this loop
       // -- two dozen per-lane addresses -- it then keeps in scratch memory for the whole launch;
       // made opaque per pass of the state machine, they are recomputed where they are used)
       asm volatile("" : "+v"(lane));
@@ -403,12 +405,34 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
       keep.logp = M.logp; keep.SS = M.SS; keep.pd = M.pd; keep.bad = M.bad;
       keep.lp = ctl[CT_LP]; keep.ldv = ctl[CT_LDV]; keep.lda = ctl[CT_LDA];
       keep.Q = ctl[CT_Q]; keep.c = ctl[CT_C];
-      if (pe.f1 >= 0) apply_flip(ch, pe.f1);
+      FSTAMP(sx, 7);
+      // One variable entering or leaving the model whose factors LDS holds keeps the factor
+      // columns left of its position (refactor).  "LDS holds valid factors of the current
+      // gamma" is read off the model itself: whatever last put factors there -- a rebuild
+      // that was accepted, a slot switch, restore_model after a rejection or at the launch's
+      // start -- left pd and a finite log|A_g| behind exactly when both factorisations ran
+      // through, and every failure leaves pd false or log|A_g| = -inf.
+      const int kold = ch.k;
+      int fq = -1;
+      if (pe.f1 >= 0) fq = apply_flip(ch, pe.f1);
       if (pe.f2 >= 0) apply_flip(ch, pe.f2);
+      const bool fins = ch.k > kold;
+      if (!(P.rebuild_policy == 0 && pe.kind != EV_INIT && pe.f2 < 0 && kold > 0 && ch.k > 0 &&
+            keep.pd && uni(keep.lda) > -BA_INF))
+        fq = -1;
+#ifndef BA_STAMPS
+      if (fq >= 0) {
+        ACC_ADD(ACC_PARTIAL_REBUILDS, 1);
+        ACC_ADD(ACC_COLUMNS_KEPT, fq);
+      }
+#endif
+      FCOUNT(sx, 5, 1);
+      FCOUNT(sx, 6, fq >= 0 ? fq : 0);
       bool rejected = false;
       {
         Model Mn;
-        refactor<false, MLVS>(P, ch, Mn, sx);
+        refactor<false, MLVS>(P, ch, Mn, sx, fq, fins);
+        FSTAMP(sx, 3);
         if (Mn.bad) {
           status = Mn.bad;
         } else {
@@ -465,6 +489,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
       pe.lfw = pe.lrev = 0.0;
       pe.check_legal = false;
       STAMP(2);
+      FSTAMP(sx, 4);
       continue;
     }
 
@@ -945,7 +970,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
   // (the chain's scalar accumulators, lane i <-> slot i: read here, with the summaries'
   // loads, written at the end -- not a round trip of lane 0's own after everything else)
   double *acc_row = P.acc + (size_t)chain * ACC_COUNT;
-  const double acc_old = (lane < 8) ? acc_row[lane] : 0.0;
+  const double acc_old = (lane < 11) ? acc_row[lane] : 0.0;
 #endif
   if (sum_g[lane] >= 0 && sum_n[lane]) {
     const size_t o = (size_t)chain * p + sum_g[lane];
@@ -1010,15 +1035,16 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
 #endif
 #if defined(BA_STAMPS) && defined(BA_STAMPS4)
     // (phases are wave 1's)
-#elif defined(BA_STAMPS) && (defined(BA_STAMPS2) || defined(BA_STAMPS3))
+#elif defined(BA_STAMPS) && (defined(BA_STAMPS2) || defined(BA_STAMPS3) || defined(BA_STAMPS5))
     SUBSTAMP(sx, 7);
+    FSTAMP(sx, 7);
     for (int i = 0; i < 8; ++i) a[ACC_PHASE0 + i] += sx.ph[i];
 #elif defined(BA_STAMPS)
     for (int i = 0; i < 8; ++i) { a[ACC_PHASE0 + i] += st_ph[i]; a[ACC_SLOT_HITS] += st_ph[i]; }
 #endif
   }
 #ifndef BA_STAMPS
-  if (lane < 8) {
+  if (lane < 11) {
     const double inc = (lane == ACC_SWEEPS) ? (double)done : ctl[CT_ACC + lane];
     acc_row[lane] = (lane == ACC_MIN_MARGIN) ? fmin(acc_old, inc) : acc_old + inc;
   }

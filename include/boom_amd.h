@@ -150,6 +150,12 @@ int ba_set_options(ba_engine *e, int32_t max_flips, double swap_threshold,
  *   kcap_start       0 = default; first model capacity tried (16, 32, ...) */
 int ba_set_tuning(ba_engine *e, int32_t waves_per_chain, int32_t walk_policy,
                   int32_t kcap_start);
+/* A further override of the same kind (same chains either way, bit for bit): how the sweep
+ * kernels rebuild the two Cholesky factors when ONE variable enters or leaves the model.
+ *   0 = keep the leading columns the flip leaves unchanged and compute the rest (default)
+ *   1 = always factor from scratch
+ * Drops nothing the engine keeps between calls; takes effect with the next launch. */
+int ba_set_rebuild_policy(ba_engine *e, int32_t policy);
 /* The samplers that give every draw its own slot of a stream (the bsts state draw's normals:
  * 256 positions a normal; the probit / logit / Polya-Gamma / Poisson imputers: 4096 / 256 /
  * 4096 / 256 positions an observation) let a draw that needs more uniforms than its slot

@@ -18,3 +18,6 @@ g0 = np.zeros(p, np.uint8); g0[0] = 1
 eng.set_state(g0); eng.sweep(200); eng.reset_summaries(); eng.sweep(1000)
 sm = eng.get_summaries()
 print("accepts %d, slot hits %d (%.1f %%)" % (sm["accepts"], sm["slot_hits"], 100 * sm["slot_hits"] / sm["accepts"]))
+print("partial rebuilds %d (%.1f %% of accepts), columns kept per partial rebuild %.2f (mean model size %.2f)"
+      % (sm["partial_rebuilds"], 100 * sm["partial_rebuilds"] / sm["accepts"],
+         sm["columns_kept"] / max(sm["partial_rebuilds"], 1), sm["k_sum"] / sm["sweeps"]))

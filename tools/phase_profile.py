@@ -7,7 +7,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SUBN = os.environ.get("SUBSTAMPS", "0")
 SUB = SUBN != "0"
-os.environ["BOOM_AMD_LIB"] = os.path.join(ROOT, "tools", "build", {"0": "libboomamd_stamps.so", "1": "libboomamd_stamps2.so", "2": "libboomamd_stamps3.so", "3": "libboomamd_stamps4.so"}[SUBN])
+os.environ["BOOM_AMD_LIB"] = os.path.join(ROOT, "tools", "build", {"0": "libboomamd_stamps.so", "1": "libboomamd_stamps2.so", "2": "libboomamd_stamps3.so", "3": "libboomamd_stamps4.so", "4": "libboomamd_stamps5.so"}[SUBN])
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import time
@@ -21,6 +21,7 @@ chains = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
 X, y, _ = regression_data(n, p, nsig, seed=8675309)
 eng = boom_amd.Engine(chains, seed=1, max_model_size_hint=int(os.environ.get('KCAP_HINT', '0')))
 eng.set_tuning(waves_per_chain=int(os.environ.get("WAVES", "0")), walk_policy=int(os.environ.get("WALK", "-1")))
+eng.set_rebuild_policy(int(os.environ.get("REBUILD", "0")))
 eng.build_suf_from_xy(X, y)
 s = eng.get_suf()
 suf = dict(xtx=s["xtx"], xty=s["xty"], yty=s["yty"], n=s["n"],
@@ -48,9 +49,20 @@ if SUBN == "2":
 elif SUBN == "3":
     names = ["wave 1: shuffle uniforms", "wave 1: matching rounds", "wave 1: links", "wave 1: walks",
              "wave 1: table walk", "wave 1: waiting", "wave 1: proposal rounds", "wave 1: other"]
+elif SUBN == "4":
+    names = ["rebuild: gathers, prior, shift, r, c", "rebuild: inserted row", "rebuild: column loop, log dets",
+             "rebuild: w, model value", "rebuild: publish / restore", None, None, "everything else"]
 elif SUB:
     names = ["batch: index fetch", "batch: classify", "batch: V gather", "batch: V solve",
              "batch: A gather", "batch: A solve", "batch: epilogue", "outside batches"]
+if SUBN == "4":
+    # (slots 5 and 6 of this build are counts, not cycles)
+    nreb, kept = ph[5], ph[6]
+    ph = ph.copy()
+    ph[5] = ph[6] = 0.0
+    print("rebuilds/sweep %.4f, cycles/rebuild %.0f (column loop %.0f = %.1f %%), columns kept/rebuild %.2f"
+          % (nreb / sm["sweeps"], ph[:5].sum() / max(nreb, 1), ph[2] / max(nreb, 1),
+             100 * ph[2] / max(ph[:5].sum(), 1), kept / max(nreb, 1)))
 tot = ph.sum()
 if not SUB:
     print("  per chain: mean %.0f cycles, slowest %.0f cycles (%.2fx)" % (tot / chains, sm["slot_hits"], sm["slot_hits"] * chains / tot))
@@ -58,4 +70,6 @@ print("waves=%s hint=%s" % (os.environ.get("WAVES","auto"), os.environ.get("KCAP
       % (nsig, chains, dt / (NSW * NL) * 1e6, sm["k_sum"] / sm["sweeps"], sm["accepts"] / sm["sweeps"],
          sm["proposals"] / sm["sweeps"]))
 for nm, v in zip(names, ph):
+    if nm is None:
+        continue
     print("  %-26s %6.2f %%   %10.0f cycles/sweep" % (nm, 100 * v / tot, v / sm["sweeps"]))
