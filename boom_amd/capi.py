@@ -133,6 +133,11 @@ SIGNATURES = {
     "ba_ss_student_get_weights": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
     "ba_ss_student_set_weights": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
     "ba_ss_student_impute_state": (C.c_int, [C.c_void_p]),
+    "ba_ss_poisson_set_data": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, _u8p]),
+    "ba_ss_poisson_sweep": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ba_ss_poisson_impute_state": (C.c_int, [C.c_void_p]),
+    "ba_ss_poisson_get_latent": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp]),
+    "ba_ss_poisson_set_latent": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp]),
     "ba_student_set_data": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp]),
     "ba_student_set_nu_prior": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double]),
     "ba_student_set_nu": (C.c_int, [C.c_void_p, C.c_int64, C.c_double]),
@@ -529,6 +534,9 @@ class Engine:
         self.p = X.shape[1]
         self._check(self.lib.ba_poisson_set_data(self._h, X.shape[0], X.shape[1], _p(X), _p(_f64(y)),
                                                  _p(_f64(exposure))))
+        self._poisson_set_mixtures(mix)
+
+    def _poisson_set_mixtures(self, mix):
         counts = np.ascontiguousarray(mix["counts"], dtype=np.int64)
         ncomp = np.ascontiguousarray(mix["ncomp"], dtype=np.int32)
         self._check(self.lib.ba_poisson_set_mixtures(
@@ -611,6 +619,36 @@ class Engine:
     def ss_student_impute_state(self):
         self._check(self.lib.ba_ss_student_impute_state(self._h))
         self.sync()
+
+    # ---- StateSpacePoissonPosteriorSampler (bsts family = "poisson") ---------------
+    def ss_poisson_set_data(self, counts, exposure, X, mix, observed=None):
+        """mix: the dict poisson_set_data takes (the mixtures of 1 and of the positive counts at
+        the observed steps)"""
+        T, p = X.shape
+        obs = None if observed is None else np.ascontiguousarray(observed, np.uint8)
+        self._check(self.lib.ba_ss_poisson_set_data(self._h, T, p, _p(_f64(counts)), _p(_f64(exposure)),
+                                                    _p(_fcol(X)), _b(obs)))
+        self.p = p
+        self.T = T
+        self._poisson_set_mixtures(mix)
+
+    def ss_poisson_sweep(self, nsweeps=1, sync=True):
+        self._check(self.lib.ba_ss_poisson_sweep(self._h, nsweeps))
+        if sync:
+            self.sync()
+
+    def ss_poisson_impute_state(self):
+        self._check(self.lib.ba_ss_poisson_impute_state(self._h))
+        self.sync()
+
+    def ss_poisson_get_latent(self, chain):
+        n = getattr(self, "T", 1)   # (without the family's data the call is refused before it writes)
+        value, precision = np.zeros(n), np.zeros(n)
+        self._check(self.lib.ba_ss_poisson_get_latent(self._h, int(chain), _p(value), _p(precision)))
+        return value, precision
+
+    def ss_poisson_set_latent(self, value, precision, chain=-1):
+        self._check(self.lib.ba_ss_poisson_set_latent(self._h, int(chain), _p(_f64(value)), _p(_f64(precision))))
 
     # ---- QuantileRegressionSpikeSlabSampler --------------------------------------
     def quantile_set_data(self, X, y, quantile):

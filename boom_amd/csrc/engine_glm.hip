@@ -81,7 +81,7 @@ int upload_latent_data(ba_engine *e, int64_t n, int32_t p, const double *X, cons
 
 // the latent data of the binomial and Poisson samplers have unit variance: sigma^2 = 1 in
 // every chain, whatever a caller left there before the data were set
-static int set_unit_sigsq(ba_engine *e) { return write_per_chain(e, e->dsigsq.ptr, -1, 1.0); }
+int set_unit_sigsq(ba_engine *e) { return write_per_chain(e, e->dsigsq.ptr, -1, 1.0); }
 
 // the imputation kernels' view of the data: what every family's kernel reads ...
 static void fill_latent_params(ba_engine *e, LatentParams &L) {
@@ -101,7 +101,7 @@ static void fill_latent_params(ba_engine *e, LatentParams &L) {
 }
 
 // ... and each family's own (the probit kernel reads neither w nor the mixtures)
-static void fill_probit_params(ba_engine *e, ProbitParams &Q) {
+void fill_probit_params(ba_engine *e, ProbitParams &Q) {
   std::memset(&Q, 0, sizeof(Q));
   fill_latent_params(e, Q);
   Q.clt_threshold = e->lat.clt;
@@ -486,7 +486,8 @@ int ba_poisson_set_mixtures(ba_engine *e, int32_t ncounts, const int64_t *counts
                             int64_t largest_index) {
   ENGINE_PROLOGUE(e);
   MUTATE(e);
-  if (e->data_kind != DATA_POISSON) return fail(BA_E_STATE, set_data_first(DATA_POISSON));
+  // (the state space Poisson family too: ba_ss_poisson_set_data fills poisson_y from the observed steps)
+  if (e->data_kind != DATA_POISSON && e->data_kind != DATA_SS_POISSON) return fail(BA_E_STATE, set_data_first(DATA_POISSON));
   if (ncounts <= 0 || !counts || !ncomp || !mu || !sigma || !weight) return fail(BA_E_INVALID, "null argument");
   std::vector<int32_t> off((size_t)ncounts + 1, 0);
   for (int i = 0; i < ncounts; ++i) {

@@ -62,6 +62,10 @@ hipError_t launch_student_sigma_nu(hipStream_t stream, const StudentParams &P);
 hipError_t launch_student_ss_weights(hipStream_t stream, const StudentParams &P, int draw);
 hipError_t launch_student_ss_suf(hipStream_t stream, const StudentParams &P, const double *Xsq,
                                  const double *slab_precision, double *xtz, double *v_diag, double *planes);
+// probit_kernel.hip: the state space Poisson family
+hipError_t launch_poisson_ss_latent(hipStream_t stream, const ProbitParams &P, int draw);
+hipError_t launch_poisson_ss_suf(hipStream_t stream, const ProbitParams &P, const double *Xsq,
+                                 const double *slab_precision, double *v_diag, double *planes);
 // quantile_kernel.hip
 hipError_t launch_quantile_impute(hipStream_t stream, const QuantileParams &P, const double *Xsq,
                                   const double *slab_precision, double *xtz, double *v_diag, double *planes);
@@ -129,12 +133,15 @@ enum DataKind { DATA_REGRESSION, DATA_STATE_SPACE, DATA_PROBIT, DATA_LOGIT, DATA
                 DATA_MLOGIT,
                 // bsts family = "student": the state space data with the Student-t observation model
                 // (StateSpaceStudentRegressionModel); the Student path's buffers with n = T
-                DATA_SS_STUDENT };
+                DATA_SS_STUDENT,
+                // bsts family = "poisson": the state space data with the Poisson observation model
+                // (StateSpacePoissonModel); the Poisson path's buffers with n = T
+                DATA_SS_POISSON };
 // the latent-data families: the regression runs on every chain's own imputed responses
-inline bool latent_data(DataKind k) { return k == DATA_PROBIT || k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT || k == DATA_SS_STUDENT; }
+inline bool latent_data(DataKind k) { return k == DATA_PROBIT || k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT || k == DATA_SS_STUDENT || k == DATA_SS_POISSON; }
 // ... and those of them whose V = slab precision + X'WX is every chain's own, built a vector
 // at a time (serve_columns, engine_glm.hip)
-inline bool column_service(DataKind k) { return k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT || k == DATA_SS_STUDENT; }
+inline bool column_service(DataKind k) { return k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT || k == DATA_SS_STUDENT || k == DATA_SS_POISSON; }
 // the two families whose sigma^2 is every chain's own draw on latent data
 inline bool student_kind(DataKind k) { return k == DATA_STUDENT || k == DATA_SS_STUDENT; }
 
@@ -372,6 +379,13 @@ struct ba_engine {
   DevBuf<double> dsst_h;
   uint64_t sst_round = 0;
   bool sst_ready = false;
+  // StateSpacePoissonPosteriorSampler (DATA_SS_POISSON): every chain's latent values v_t (the
+  // series the filter reads; lat.w holds their precisions q_t) and H_t = 1 / q_t, chains x T
+  // each; which steps are observed (host copy); the latent data and statistics in hand are those
+  // of a state draw (lat.draws counts the imputations)
+  DevBuf<double> dssp_value, dssp_h;
+  std::vector<uint8_t> ssp_observed;
+  bool ssp_ready = false;
   // QuantileRegressionSpikeSlabSampler (quantile_kernel.hip): the model's quantile
   double quantile_q = 0.5;
   // MLVS (mlogit_kernel.hip): the expanded design (lat.n = N = n M rows, p = D columns), its
@@ -492,6 +506,8 @@ int read_chain_row(ba_engine *e, int64_t chain, const DevBuf<double> &buf, size_
 int serve_columns(ba_engine *e, std::vector<int32_t> &st, bool *served);
 int student_prepare(ba_engine *e);
 void fill_student_params(ba_engine *e, StudentParams &T);
+void fill_probit_params(ba_engine *e, ProbitParams &Q);
+int set_unit_sigsq(ba_engine *e);
 int build_columns(ba_engine *e, int64_t R);
 int column_buffers(ba_engine *e);
 int upload_latent_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y,

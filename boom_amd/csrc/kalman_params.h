@@ -137,6 +137,10 @@ struct SsParams {
   // the general structural kernel's HT instances read it
   const double *h;
   int64_t h_stride;
+  // the Poisson family (StateSpacePoissonModel): the filtered series is every chain's own latent
+  // value, y_stride doubles apart (0: the one series shared by all chains).  Read by the HT
+  // instances only.
+  int64_t y_stride;
 };
 
 // The round kernel (ss_round_kernel.hip): every chain's workgroup loops over the rounds of a

@@ -781,6 +781,14 @@ __device__ __forceinline__ void poisson_unmix(const ProbitParams &P, SeqRng &rng
 }
 }  // namespace
 
+// SS: the state space Poisson family (StateSpacePoissonPosteriorSampler::
+// impute_nonstate_latent_data, StateSpacePoissonPosteriorSampler.cpp:79-128): one thread per
+// (chain, step).  eta_t = x_t'beta + offset_t (the chain's Z_t'alpha_t); the two points are
+// combined the external one first, and the step's latent value v_t = sum / q_t, its precision
+// q_t and the filter's H_t = 1 / q_t are written (z is left to poisson_ss_suf_kernel, after the
+// state draw).  A missing step reads neither count, exposure, mixture nor random number: q = 0,
+// v = 0, H = pi^2 / 6 (AugmentedPoissonRegressionData::latent_data_overall_variance).
+template <bool SS>
 __global__ __launch_bounds__(256) void poisson_impute_kernel(ProbitParams P) {
   const int chain = (int)blockIdx.y, i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   __shared__ int s_status;   // (one decision per workgroup: see probit_impute_kernel)
@@ -797,6 +805,16 @@ __global__ __launch_bounds__(256) void poisson_impute_kernel(ProbitParams P) {
   if (i >= P.n) return;
   double eta = 0.0;
   for (int m = 0; m < k; ++m) eta += P.X[(size_t)s_idx[m] * P.n + i] * s_beta[m];
+  if (SS) {
+    if (!P.observed[i]) {
+      const size_t at = (size_t)chain * P.n + i;
+      P.w[at] = 0.0;
+      P.value[at] = 0.0;
+      P.h[at] = POISSON_MISSING_VARIANCE;
+      return;
+    }
+    eta = P.offset[(size_t)chain * P.offset_stride + i] + eta;   // (state_contribution + regression_contribution)
+  }
   const long long y = llround(P.y[i]);
   const double exposure = P.ntrials[i];
   SeqRng rng = SeqRng::slot(PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), 11u},
@@ -821,6 +839,24 @@ __global__ __launch_bounds__(256) void poisson_impute_kernel(ProbitParams P) {
     z_int = -log(t_final);
     poisson_unmix(P, rng, z_int - eta, P.obs_mix[i], (double)y, &mu_i, &sig_i, &bad);
   }
+  if (SS) {
+    // the external point first, then the internal one (StateSpacePoissonPosteriorSampler.cpp:112-123)
+    double info = 1.0 / sig_e;
+    double sum = (z_ext - mu_e) * info;
+    if (y > 0) {
+      const double w = 1.0 / sig_i;
+      sum += (z_int - mu_i) * w;
+      info += w;
+    }
+    if (bad || rng.overran()) P.status[chain] = CHAIN_RNG_BRANCH;
+    // (the reference's latent_data_overall_variance is -infinity for such a precision)
+    if (!(info > 0.0) || !isfinite(info)) P.status[chain] = CHAIN_FORECAST_VARIANCE;
+    const size_t at = (size_t)chain * P.n + i;
+    P.value[at] = sum / info;
+    P.w[at] = info;
+    P.h[at] = 1.0 / info;
+    return;
+  }
   // the internal point first, then the external one (the order the reference adds them in)
   double sum = 0.0, info = 0.0;
   if (y > 0) {
@@ -836,6 +872,36 @@ __global__ __launch_bounds__(256) void poisson_impute_kernel(ProbitParams P) {
   if (bad || rng.overran()) P.status[chain] = CHAIN_RNG_BRANCH;
   P.z[(size_t)chain * P.n + i] = sum;
   P.w[(size_t)chain * P.n + i] = info;
+}
+
+// the state space Poisson family's H_t from the latent data in hand (all precisions 1 of the first
+// round, ba_ss_poisson_set_latent): the same rule as poisson_impute_kernel<true>
+__global__ __launch_bounds__(256) void poisson_ss_h_kernel(ProbitParams P) {
+  const int chain = (int)blockIdx.y, i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= P.n || P.status[chain] != CHAIN_OK) return;
+  const size_t at = (size_t)chain * P.n + i;
+  if (!P.observed[i]) {
+    P.h[at] = POISSON_MISSING_VARIANCE;
+    return;
+  }
+  const double q = P.w[at];
+  if (!(q > 0.0) || !isfinite(q)) { P.status[chain] = CHAIN_FORECAST_VARIANCE; return; }
+  P.h[at] = 1.0 / q;
+}
+
+// ... and after the state draw the complete-data response z_t = (v_t - offset_t) q_t, 0 (and
+// weight 0) where the step is missing (update_complete_data_sufficient_statistics,
+// StateSpacePoissonPosteriorSampler.cpp:134-147): the rows of the X'Qz GEMM
+__global__ __launch_bounds__(256) void poisson_ss_suf_kernel(ProbitParams P) {
+  const int chain = (int)blockIdx.y, i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= P.n) return;
+  const size_t at = (size_t)chain * P.n + i;
+  if (!P.observed[i]) {
+    P.w[at] = 0.0;
+    P.z[at] = 0.0;
+    return;
+  }
+  P.z[at] = (P.value[at] - P.offset[(size_t)chain * P.offset_stride + i]) * P.w[at];
 }
 
 // impute + X'z for every chain
@@ -860,11 +926,35 @@ hipError_t launch_logit_impute(hipStream_t stream, const ProbitParams &P, const 
   {
     KtScope kt(stream, polya_gamma == 2 ? KT_POISSON_IMPUTE : KT_LOGIT_IMPUTE);
     if (polya_gamma == 2)   // (the Poisson member of the family: same outputs, its own imputation)
-      hipLaunchKernelGGL(poisson_impute_kernel, dim3((P.n + 255) / 256, P.chains), dim3(256), 0, stream, P);
+      hipLaunchKernelGGL(poisson_impute_kernel<false>, dim3((P.n + 255) / 256, P.chains), dim3(256), 0, stream, P);
     else if (polya_gamma)
       hipLaunchKernelGGL(logit_pg_impute_kernel, dim3((P.n + 255) / 256, P.chains), dim3(256), 0, stream, P);
     else
       hipLaunchKernelGGL(logit_impute_kernel, dim3((P.n + 255) / 256, P.chains), dim3(256), 0, stream, P);
+    err = hipGetLastError();
+  }
+  if (err != hipSuccess) return err;
+  return launch_latent_products(stream, P.z, P.w, P.chains, P.X, Xsq, (int64_t)P.n, P.p, slab_precision, P.xtz, v_diag,
+                                planes);
+}
+
+// the state space Poisson family: the latent data (draw != 0: a new imputation, else H_t from the
+// data in hand) ...
+hipError_t launch_poisson_ss_latent(hipStream_t stream, const ProbitParams &P, int draw) {
+  KtScope kt(stream, KT_SS_POISSON);
+  const dim3 grid((P.n + 255) / 256, P.chains);
+  if (draw) hipLaunchKernelGGL(poisson_impute_kernel<true>, grid, dim3(256), 0, stream, P);
+  else hipLaunchKernelGGL(poisson_ss_h_kernel, grid, dim3(256), 0, stream, P);
+  return hipGetLastError();
+}
+
+// ... and after the state draw z, X'Qz and the diagonal of V = slab precision + X'QX
+hipError_t launch_poisson_ss_suf(hipStream_t stream, const ProbitParams &P, const double *Xsq,
+                                 const double *slab_precision, double *v_diag, double *planes) {
+  hipError_t err;
+  {
+    KtScope kt(stream, KT_SS_POISSON);
+    hipLaunchKernelGGL(poisson_ss_suf_kernel, dim3((P.n + 255) / 256, P.chains), dim3(256), 0, stream, P);
     err = hipGetLastError();
   }
   if (err != hipSuccess) return err;

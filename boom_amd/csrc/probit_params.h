@@ -10,6 +10,9 @@ namespace boom_amd {
 
 enum { PROBIT_STRIDE = 4096, PROBIT_KMAX = 1024, LOGIT_STRIDE = 256, PG_STRIDE = 4096, POISSON_STRIDE = 256,
        POISSON_MAX_COMP = 32 };
+// the variance of the negative log of an exponential, pi^2 / 6: what the state space Poisson
+// family's filter uses at a missing step (Constants::pi_squared_over_6)
+#define POISSON_MISSING_VARIANCE 1.6449340668482264
 
 // z: the observations' sums of latent normals; w: their total precision (logit and Poisson only)
 struct ProbitParams : LatentParams {
@@ -26,6 +29,15 @@ struct ProbitParams : LatentParams {
   const double *mix_mu, *mix_sigma, *mix_logw;
   const int32_t *obs_mix;
   int32_t mix_one;
+  // the state space Poisson family (poisson_impute_kernel<true>, poisson_ss_h_kernel,
+  // poisson_ss_suf_kernel; nullptr elsewhere): which steps are observed; the chain's
+  // Z_t'alpha_t of the last state draw, offset_stride doubles apart; the latent values v_t
+  // (chains x n; w holds their precisions q_t) and the filter's H_t = 1 / q_t (chains x n)
+  const uint8_t *observed;
+  const double *offset;
+  int64_t offset_stride;
+  double *value;
+  double *h;
 };
 
 }  // namespace boom_amd

@@ -99,6 +99,8 @@ __host__ __device__ inline int ssg_pass_lds_doubles(int m, int ld, int bl, int n
 // sigma^2.  A block's H_t sit one step per lane beside the observed flags; wave 1 reads them
 // into F_t, wave 0 into y+_t.  H_t > 0 always, so every step draws its observation normal.  The
 // last pass leaves Z_t'alpha_t (every step) where the HT = false instances leave the residuals.
+// The HT instances also read the series from P.y + chain * P.y_stride (the Poisson family's
+// latent values, one series per chain; the Student-t family passes stride 0).
 template <bool SMALL, int LDC, bool GLOB, bool HT = false>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void ssg_simsmooth_kernel(SsParams P, int draw_variances) {
   constexpr int SSG_BATCH = SMALL ? 4 : 8;   // entries of a column / row of P asked of the LDS together
@@ -333,7 +335,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
         pred += P.X[(size_t)(base + l) * T + (t < T ? t : T - 1)] * bb;
       }
     }
-    if (t < T) w0[t] = P.y[t] - pred;
+    if (t < T) w0[t] = (HT ? P.y[(size_t)chain * P.y_stride + t] : P.y[t]) - pred;   // (HT: the chain's own series, if it has one)
   }
 
   SSTAMP(1);

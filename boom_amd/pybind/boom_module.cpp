@@ -592,6 +592,47 @@ PYBIND11_MODULE(_boom, boom) {
       .def("draw", &StateSpaceStudentPosteriorSampler::draw)
       .def("set_sigma_upper_limit", &StateSpaceStudentPosteriorSampler::set_sigma_upper_limit);
 
+  // ---- bsts family = "poisson" (StateSpacePoissonModel, StateSpacePoissonPosteriorSampler): the
+  // state space model's bindings, inherited, + the Poisson observation model's ------------------
+  py::class_<StateSpacePoissonModel, StateSpaceRegressionModel, Ptr<StateSpacePoissonModel>>(boom, "StateSpacePoissonModel")
+      .def(py::init([](const NpArray &counts, const NpArray &exposure, const NpArray &predictors,
+                       const std::vector<bool> &is_observed, int chains, uint64_t seed, int device) {
+             return new StateSpacePoissonModel(vector_from(counts), vector_from(exposure), matrix_from(predictors),
+                                               is_observed, chains, seed, device);
+           }),
+           py::arg("counts"), py::arg("exposure"), py::arg("predictors"), py::arg("is_observed") = std::vector<bool>(),
+           py::arg("chains") = 1, py::arg("seed") = 8675309ull, py::arg("device") = 0)
+      .def("set_mixture_table", [](StateSpacePoissonModel &m, const std::vector<int64_t> &counts,
+                                   const std::vector<int32_t> &ncomp, const NpArray &mu, const NpArray &sigma,
+                                   const NpArray &weight, int64_t largest_index) {
+             NormalMixtureTable t;
+             t.counts = counts; t.ncomp = ncomp;
+             t.mu = vector_from(mu); t.sigma = vector_from(sigma); t.weight = vector_from(weight);
+             t.largest_index = largest_index;
+             m.set_mixture_table(t);
+           },
+           py::arg("counts"), py::arg("ncomp"), py::arg("mu"), py::arg("sigma"), py::arg("weight"),
+           py::arg("largest_index"),
+           "the reference's normal mixtures for the negative log-gamma densities (its data)")
+      .def("latent_values", [](const StateSpacePoissonModel &m, int chain) { return to_numpy(m.latent_values(chain)); },
+           py::arg("chain") = 0, "the latent values of one chain (0 at a missing step)")
+      .def("latent_precisions", [](const StateSpacePoissonModel &m, int chain) { return to_numpy(m.latent_precisions(chain)); },
+           py::arg("chain") = 0, "the latent values' precisions in one chain (0 at a missing step)")
+      .def("set_latent_data", [](StateSpacePoissonModel &m, const NpArray &value, const NpArray &precision, int chain) {
+             m.set_latent_data(vector_from(value), vector_from(precision), chain);
+           }, py::arg("value"), py::arg("precision"), py::arg("chain") = -1)
+      .def("impute_state", &StateSpacePoissonModel::impute_state);
+  py::class_<StateSpacePoissonPosteriorSampler, PosteriorSampler, Ptr<StateSpacePoissonPosteriorSampler>>(
+      boom, "StateSpacePoissonPosteriorSampler")
+      .def(py::init([](StateSpacePoissonModel *model, const Ptr<MvnModel> &slab,
+                       const Ptr<VariableSelectionPrior> &spike, py::object) {
+             return new StateSpacePoissonPosteriorSampler(model, slab, spike);
+           }),
+           py::arg("model"), py::arg("slab"), py::arg("spike"), py::arg("seeding_rng") = py::none(),
+           py::keep_alive<1, 2>())
+      .def("draw", &StateSpacePoissonPosteriorSampler::draw)
+      .def("limit_model_selection", &StateSpacePoissonPosteriorSampler::limit_model_selection);
+
   // ---- quantile regression spike and slab (QuantileRegressionModel,
   // QuantileRegressionSpikeSlabSampler) -----------------------------------------------------
   py::class_<QuantileRegressionModel, Ptr<QuantileRegressionModel>>(boom, "QuantileRegressionModel")

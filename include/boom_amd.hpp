@@ -668,6 +668,18 @@ class StateSpaceRegressionModel : public Model {
     if (!observed.empty()) { obs.resize(T_); for (int t = 0; t < T_; ++t) obs[t] = observed[t]; }
     eng_->check(ba_ss_student_set_data(eng_->get(), T_, p_, y.data(), X.data(), obs.empty() ? nullptr : obs.data()));
   }
+  // StateSpacePoissonModel: the same state, the Poisson observation model
+  struct PoissonFamily {};
+  StateSpaceRegressionModel(PoissonFamily, const Vector &counts, const Vector &exposure, const Matrix &X,
+                            const std::vector<bool> &observed, int chains, uint64_t seed, int device)
+      : eng_(new Engine(chains, seed, device)), T_((int)counts.size()), p_(X.ncol()), list_always_(true) {
+    if (X.nrow() != T_ || (int)exposure.size() != T_)
+      report_error("counts, exposure and X are incompatible in constructor for StateSpacePoissonModel.");
+    std::vector<uint8_t> obs;
+    if (!observed.empty()) { obs.resize(T_); for (int t = 0; t < T_; ++t) obs[t] = observed[t]; }
+    eng_->check(ba_ss_poisson_set_data(eng_->get(), T_, p_, counts.data(), exposure.data(), X.data(),
+                                       obs.empty() ? nullptr : obs.data()));
+  }
  private:
   struct Entry {
     int kind = 0;   // 1 local level, 2 local linear trend, 3 seasonal, 4 autoregression, 5 static intercept, 6 trig, 7 semilocal linear trend
@@ -1105,6 +1117,75 @@ class StateSpaceStudentPosteriorSampler : public PosteriorSampler {
   void check(int rc) const { model_->engine()->check(rc); }
   StateSpaceStudentRegressionModel *model_;
   Ptr<ChisqModel> siginv_;
+};
+
+// ---- bsts family = "poisson" --------------------------------------------------------------
+// StateSpacePoissonModel + StateSpacePoissonPosteriorSampler (Models/StateSpace/
+// StateSpacePoissonModel.hpp, PosteriorSamplers/StateSpacePoissonPosteriorSampler.cpp:79-147): the
+// state of StateSpaceRegressionModel under PoissonRegressionModel's observations, on the device
+// (ba_ss_poisson_*).  One observation per time step, regression present.  The mixture table is
+// handed over as PoissonRegressionModel's is.  Chain 0 backs the accessors' defaults.
+class StateSpacePoissonModel : public StateSpaceRegressionModel {
+ public:
+  StateSpacePoissonModel(const Vector &counts, const Vector &exposure, const Matrix &X,
+                         const std::vector<bool> &observed, int chains = 1, uint64_t seed = 8675309, int device = 0)
+      : StateSpaceRegressionModel(PoissonFamily(), counts, exposure, X, observed, chains, seed, device) {}
+  void set_mixture_table(const NormalMixtureTable &t) {
+    if (t.counts.size() != t.ncomp.size()) report_error("the mixture table's counts and ncomp differ in length");
+    engine()->check(ba_poisson_set_mixtures(engine()->get(), (int32_t)t.counts.size(), t.counts.data(), t.ncomp.data(),
+                                            t.mu.data(), t.sigma.data(), t.weight.data(), t.largest_index));
+  }
+  // one chain's latent data (AugmentedPoissonRegressionData::latent_data_value and the
+  // precisions behind latent_data_variance); 0 at a missing step
+  Vector latent_values(int chain = 0) const {
+    Vector v(time_dimension()), q(time_dimension());
+    engine()->check(ba_ss_poisson_get_latent(engine()->get(), chain, v.data(), q.data()));
+    return v;
+  }
+  Vector latent_precisions(int chain = 0) const {
+    Vector v(time_dimension()), q(time_dimension());
+    engine()->check(ba_ss_poisson_get_latent(engine()->get(), chain, v.data(), q.data()));
+    return q;
+  }
+  void set_latent_data(const Vector &value, const Vector &precision, int chain = -1) {   // set_latent_data, every step (chain -1: every chain)
+    if ((int)value.size() != time_dimension() || (int)precision.size() != time_dimension())
+      report_error("One latent value and one precision per time step are needed.");
+    engine()->check(ba_ss_poisson_set_latent(engine()->get(), chain, value.data(), precision.data()));
+  }
+  void impute_state() {   // Base::impute_state with the current parameters and latent data
+    finalize_state();
+    engine()->check(ba_ss_poisson_impute_state(engine()->get()));
+  }
+};
+// StateSpacePoissonPosteriorSampler(model, observation model sampler's priors): slab and spike as
+// PoissonRegressionSpikeSlabSampler takes them
+class StateSpacePoissonPosteriorSampler : public PosteriorSampler {
+ public:
+  StateSpacePoissonPosteriorSampler(StateSpacePoissonModel *model, const Ptr<MvnModel> &slab,
+                                    const Ptr<VariableSelectionPrior> &spike)
+      : model_(model), slab_(slab) {
+    if (slab->dim() != model->xdim()) report_error("Slab does not match model dimension.");
+    if ((int)spike->potential_nvars() != model->xdim()) report_error("Spike does not match model dimension.");
+    check(ba_sss_set_slab(h(), slab->mu().data(), slab->siginv().data(), 0, -1));
+    check(ba_set_spike(h(), spike->prior_inclusion_probabilities().data(), spike->max_model_size()));
+    std::vector<uint8_t> g0(model->xdim(), 0);
+    check(ba_set_state(h(), -1, g0.data(), nullptr, 1.0));
+  }
+  void draw() override {                     // StateSpacePosteriorSampler.cpp:42-64
+    model_->finalize_state();
+    check(ba_ss_poisson_sweep(h(), 1));
+    check(ba_sync(h()));
+  }
+  double logpri() const override { report_error("logpri() is not implemented for the Poisson state space sampler"); return 0; }
+  void set_seed(unsigned long s) override { check(ba_seed(h(), s)); }
+  void limit_model_selection(int max_flips) {
+    check(ba_sss_set_slab(h(), slab_->mu().data(), slab_->siginv().data(), 0, max_flips));
+  }
+ private:
+  ba_engine *h() const { return model_->engine()->get(); }
+  void check(int rc) const { model_->engine()->check(rc); }
+  StateSpacePoissonModel *model_;
+  Ptr<MvnModel> slab_;
 };
 
 // ---- Quantile regression spike and slab --------------------------------------------------
