@@ -138,6 +138,11 @@ SIGNATURES = {
     "ba_ss_poisson_impute_state": (C.c_int, [C.c_void_p]),
     "ba_ss_poisson_get_latent": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp]),
     "ba_ss_poisson_set_latent": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp]),
+    "ba_ss_logit_set_data": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, _u8p, C.c_int32]),
+    "ba_ss_logit_sweep": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ba_ss_logit_impute_state": (C.c_int, [C.c_void_p]),
+    "ba_ss_logit_get_latent": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp]),
+    "ba_ss_logit_set_latent": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp]),
     "ba_student_set_data": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp]),
     "ba_student_set_nu_prior": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double]),
     "ba_student_set_nu": (C.c_int, [C.c_void_p, C.c_int64, C.c_double]),
@@ -649,6 +654,33 @@ class Engine:
 
     def ss_poisson_set_latent(self, value, precision, chain=-1):
         self._check(self.lib.ba_ss_poisson_set_latent(self._h, int(chain), _p(_f64(value)), _p(_f64(precision))))
+
+    # ---- StateSpaceLogitPosteriorSampler (bsts family = "logit") -------------------
+    def ss_logit_set_data(self, successes, trials, X, observed=None, clt_threshold=5):
+        T, p = X.shape
+        obs = None if observed is None else np.ascontiguousarray(observed, np.uint8)
+        self._check(self.lib.ba_ss_logit_set_data(self._h, T, p, _p(_f64(successes)), _p(_f64(trials)),
+                                                  _p(_fcol(X)), _b(obs), int(clt_threshold)))
+        self.p = p
+        self.T = T
+
+    def ss_logit_sweep(self, nsweeps=1, sync=True):
+        self._check(self.lib.ba_ss_logit_sweep(self._h, nsweeps))
+        if sync:
+            self.sync()
+
+    def ss_logit_impute_state(self):
+        self._check(self.lib.ba_ss_logit_impute_state(self._h))
+        self.sync()
+
+    def ss_logit_get_latent(self, chain):
+        n = getattr(self, "T", 1)   # (without the family's data the call is refused before it writes)
+        value, precision = np.zeros(n), np.zeros(n)
+        self._check(self.lib.ba_ss_logit_get_latent(self._h, int(chain), _p(value), _p(precision)))
+        return value, precision
+
+    def ss_logit_set_latent(self, value, precision, chain=-1):
+        self._check(self.lib.ba_ss_logit_set_latent(self._h, int(chain), _p(_f64(value)), _p(_f64(precision))))
 
     # ---- QuantileRegressionSpikeSlabSampler --------------------------------------
     def quantile_set_data(self, X, y, quantile):

@@ -383,7 +383,9 @@ void fill_params(ba_engine *e, SsvsParams &P) {
   if (e->cur_mode == 1 && column_service(e->data_kind) && e->cols.V.count) {
     // BinomialLogitSpikeSlabSampler: the sampler's own shuffle, every chain's own V
     // (which moves with the latent data: factors and tables are rebuilt)
-    P.mode = e->data_kind == DATA_LOGIT ? 2 : 1;   // (the Poisson, Student and quantile samplers drive the plain SpikeSlabSampler)
+    // (the Poisson, Student and quantile samplers drive the plain SpikeSlabSampler; the state space
+    // logit family's observation model is BinomialLogitSpikeSlabSampler itself)
+    P.mode = (e->data_kind == DATA_LOGIT || e->data_kind == DATA_SS_LOGIT) ? 2 : 1;
     if (e->data_kind == DATA_MLOGIT) {
       // MLVS::draw_inclusion_vector: its own fixed order, acceptance and empty model (mode 3)
       P.mode = 3;
@@ -1041,7 +1043,7 @@ const char *ba_kernel_class_name(int32_t cls) {
       "xtwx_cols_kernel<false>+plain_reduce_kernel", "xtwx_cols_kernel<true>+xtwx_cols_reduce_kernel",
       "xtx_mfma_kernel+plane_sum_kernel+col_reduce_kernel", "poisson_impute_kernel",
       "kalman_prepare_kernel", "ss_round_kernel", "student_impute_kernel", "student_sigma_nu_kernel",
-      "quantile_impute_kernel", "mlogit_impute_kernel", "student_ss_kernels", "poisson_ss_kernels"};
+      "quantile_impute_kernel", "mlogit_impute_kernel", "student_ss_kernels", "poisson_ss_kernels", "logit_ss_kernels"};
   return (cls >= 0 && cls < KT_CLASSES) ? names[cls] : "";
 }
 
@@ -1631,7 +1633,8 @@ static const char *const kSetDataFirst[] = {nullptr,
                                             "call ba_quantile_set_data first",
                                             "call ba_mlogit_set_data first",
                                             "call ba_ss_student_set_data first",
-                                            "call ba_ss_poisson_set_data first"};
+                                            "call ba_ss_poisson_set_data first",
+                                            "call ba_ss_logit_set_data first"};
 // ... and where the data in hand send a caller of another family's entry point
 static const char *const kUseSweep[] = {nullptr,
                                         "state-space data are set: use ba_ss_sweep",
@@ -1642,7 +1645,8 @@ static const char *const kUseSweep[] = {nullptr,
                                         "quantile regression data are set: use ba_quantile_sweep",
                                         "multinomial logit data are set: use ba_mlogit_sweep",
                                         "Student-t state-space data are set: use ba_ss_student_sweep",
-                                        "Poisson state-space data are set: use ba_ss_poisson_sweep"};
+                                        "Poisson state-space data are set: use ba_ss_poisson_sweep",
+                                        "logit state-space data are set: use ba_ss_logit_sweep"};
 
 const char *set_data_first(DataKind wants) { return kSetDataFirst[wants]; }
 
@@ -1653,11 +1657,12 @@ int sweep_refusal(const ba_engine *e, DataKind wants, bool sss) {
   // (the quantile sampler's column and row: every other sweep names ba_quantile_sweep, and
   // ba_quantile_sweep asks for its own data whatever else is set)
   // (so with the multinomial logit sampler's)
-  // (and the state space Student and Poisson families')
-  if (have == DATA_QUANTILE || have == DATA_MLOGIT || have == DATA_SS_STUDENT || have == DATA_SS_POISSON)
+  // (and the state space Student, Poisson and logit families')
+  if (have == DATA_QUANTILE || have == DATA_MLOGIT || have == DATA_SS_STUDENT || have == DATA_SS_POISSON ||
+      have == DATA_SS_LOGIT)
     return fail(BA_E_STATE, kUseSweep[have]);
   if (wants == DATA_STATE_SPACE || wants == DATA_QUANTILE || wants == DATA_MLOGIT || wants == DATA_SS_STUDENT ||
-      wants == DATA_SS_POISSON)
+      wants == DATA_SS_POISSON || wants == DATA_SS_LOGIT)
     return fail(BA_E_STATE, kSetDataFirst[wants]);
   if (have == DATA_STUDENT) return fail(BA_E_STATE, kUseSweep[have]);
   if (wants == DATA_REGRESSION) {   // ba_sweep, ba_draw_next, ba_adaptive_sweep; ba_sss_sweep
@@ -1917,7 +1922,8 @@ int ba_log_model_prob(ba_engine *e, int32_t ngamma, const uint8_t *gammas,
   if (!gammas || !out || ngamma <= 0) return fail(BA_E_INVALID, "bad argument");
   // the regression model's own sufficient statistics: in state-space mode they
   // are per chain and move every sweep, so there is no one answer
-  if (e->data_kind == DATA_STATE_SPACE || e->data_kind == DATA_SS_STUDENT || e->data_kind == DATA_SS_POISSON)
+  if (e->data_kind == DATA_STATE_SPACE || e->data_kind == DATA_SS_STUDENT || e->data_kind == DATA_SS_POISSON ||
+      e->data_kind == DATA_SS_LOGIT)
     return fail(BA_E_STATE, "ba_log_model_prob is not defined once state-space data are set (per-chain sufficient statistics)");
   // BregVsSampler's V = Omega^{-1} + XtX (a SpikeSlabSampler launch with a fixed
   // slab precision leaves XtX / sigma^2 in it)

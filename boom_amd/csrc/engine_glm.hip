@@ -451,6 +451,9 @@ int ba_logit_set_data(ba_engine *e, int64_t n, int32_t p, const double *X, const
 int ba_logit_set_imputer(ba_engine *e, int32_t kind) {
   if (!e) return fail(BA_E_INVALID, "null engine");
   if (kind != 0 && kind != 1) return fail(BA_E_INVALID, "imputer must be 0 (auxiliary mixture) or 1 (Polya-Gamma)");
+  // (StateSpaceLogitPosteriorSampler has the auxiliary-mixture imputer only)
+  if (e->data_kind == DATA_SS_LOGIT)
+    return fail(BA_E_STATE, "logit state-space data are set: the imputer is the auxiliary mixture's");
   MUTATE(e);
   e->logit_imputer = kind;
   return BA_OK;

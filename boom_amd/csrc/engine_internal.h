@@ -62,10 +62,10 @@ hipError_t launch_student_sigma_nu(hipStream_t stream, const StudentParams &P);
 hipError_t launch_student_ss_weights(hipStream_t stream, const StudentParams &P, int draw);
 hipError_t launch_student_ss_suf(hipStream_t stream, const StudentParams &P, const double *Xsq,
                                  const double *slab_precision, double *xtz, double *v_diag, double *planes);
-// probit_kernel.hip: the state space Poisson family
-hipError_t launch_poisson_ss_latent(hipStream_t stream, const ProbitParams &P, int draw);
-hipError_t launch_poisson_ss_suf(hipStream_t stream, const ProbitParams &P, const double *Xsq,
-                                 const double *slab_precision, double *v_diag, double *planes);
+// probit_kernel.hip: the state space Poisson (family 0) and logit (family 1) families
+hipError_t launch_latent_ss_h(hipStream_t stream, const ProbitParams &P, int family, int draw);
+hipError_t launch_latent_ss_suf(hipStream_t stream, const ProbitParams &P, int family, const double *Xsq,
+                                const double *slab_precision, double *v_diag, double *planes);
 // quantile_kernel.hip
 hipError_t launch_quantile_impute(hipStream_t stream, const QuantileParams &P, const double *Xsq,
                                   const double *slab_precision, double *xtz, double *v_diag, double *planes);
@@ -136,12 +136,17 @@ enum DataKind { DATA_REGRESSION, DATA_STATE_SPACE, DATA_PROBIT, DATA_LOGIT, DATA
                 DATA_SS_STUDENT,
                 // bsts family = "poisson": the state space data with the Poisson observation model
                 // (StateSpacePoissonModel); the Poisson path's buffers with n = T
-                DATA_SS_POISSON };
+                DATA_SS_POISSON,
+                // bsts family = "logit": the state space data with the binomial logit observation model
+                // (StateSpaceLogitModel); the logit path's buffers with n = T
+                DATA_SS_LOGIT };
+// the two state space families whose latent data are a value and a precision per step
+inline bool latent_ss_kind(DataKind k) { return k == DATA_SS_POISSON || k == DATA_SS_LOGIT; }
 // the latent-data families: the regression runs on every chain's own imputed responses
-inline bool latent_data(DataKind k) { return k == DATA_PROBIT || k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT || k == DATA_SS_STUDENT || k == DATA_SS_POISSON; }
+inline bool latent_data(DataKind k) { return k == DATA_PROBIT || k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT || k == DATA_SS_STUDENT || k == DATA_SS_POISSON || k == DATA_SS_LOGIT; }
 // ... and those of them whose V = slab precision + X'WX is every chain's own, built a vector
 // at a time (serve_columns, engine_glm.hip)
-inline bool column_service(DataKind k) { return k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT || k == DATA_SS_STUDENT || k == DATA_SS_POISSON; }
+inline bool column_service(DataKind k) { return k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT || k == DATA_SS_STUDENT || k == DATA_SS_POISSON || k == DATA_SS_LOGIT; }
 // the two families whose sigma^2 is every chain's own draw on latent data
 inline bool student_kind(DataKind k) { return k == DATA_STUDENT || k == DATA_SS_STUDENT; }
 
@@ -379,12 +384,14 @@ struct ba_engine {
   DevBuf<double> dsst_h;
   uint64_t sst_round = 0;
   bool sst_ready = false;
-  // StateSpacePoissonPosteriorSampler (DATA_SS_POISSON): every chain's latent values v_t (the
+  // StateSpacePoissonPosteriorSampler and StateSpaceLogitPosteriorSampler (DATA_SS_POISSON,
+  // DATA_SS_LOGIT; the names are the first family's): every chain's latent values v_t (the
   // series the filter reads; lat.w holds their precisions q_t) and H_t = 1 / q_t, chains x T
   // each; which steps are observed (host copy); the latent data and statistics in hand are those
   // of a state draw (lat.draws counts the imputations)
   DevBuf<double> dssp_value, dssp_h;
   std::vector<uint8_t> ssp_observed;
+  std::vector<double> ssp_trials;   // (DATA_SS_LOGIT: n_t, the new model's q_t = 4 / n_t; 1 at a missing step)
   bool ssp_ready = false;
   // QuantileRegressionSpikeSlabSampler (quantile_kernel.hip): the model's quantile
   double quantile_q = 0.5;

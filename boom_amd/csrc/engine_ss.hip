@@ -42,8 +42,8 @@ static void ssg_template_shape(const SsgSpec &q, int32_t *trend, int32_t *nseaso
 
 // the local-level path of a series of at most LM_TP steps runs lane-major
 // (kalman_lm_kernel): its scratch arrays have pitch LM_TP
-// the kinds that hold a series and a state (the Gaussian, the Student-t and the Poisson observation model)
-static bool ss_kind(DataKind k) { return k == DATA_STATE_SPACE || k == DATA_SS_STUDENT || k == DATA_SS_POISSON; }
+// the kinds that hold a series and a state (the Gaussian, the Student-t, the Poisson and the logit observation model)
+static bool ss_kind(DataKind k) { return k == DATA_STATE_SPACE || k == DATA_SS_STUDENT || k == DATA_SS_POISSON || k == DATA_SS_LOGIT; }
 
 static bool ss_lane_major(const ba_engine &e) { return !e.ssm_set && e.T <= LM_TP; }
 static size_t ss_pitch(const ba_engine &e) { return ss_lane_major(e) ? (size_t)LM_TP : (size_t)e.T; }
@@ -1419,6 +1419,8 @@ int ba_ss_forecast(ba_engine *e, int32_t horizon, const double *newX, double *ou
     return fail(BA_E_STATE, "forecasts with Student-t observation noise are not implemented");
   if (e->data_kind == DATA_SS_POISSON)
     return fail(BA_E_STATE, "forecasts with Poisson observation noise are not implemented");
+  if (e->data_kind == DATA_SS_LOGIT)
+    return fail(BA_E_STATE, "forecasts with binomial observation noise are not implemented");
   if (!newX || !out || horizon <= 0) return fail(BA_E_INVALID, "bad argument");
   if (e->data_kind != DATA_STATE_SPACE || e->dss_scratch.count == 0 || !e->ss_initialized)
     return fail(BA_E_STATE, "no state draw yet: run ba_ss_sweep or ba_ss_impute_state first");
@@ -1736,16 +1738,26 @@ int ba_ss_student_sweep(ba_engine *e, int32_t nsweeps) {
 
 }  // extern "C"
 
-// ---- bsts family = "poisson": StateSpacePoissonModel + StateSpacePoissonPosteriorSampler
+// ---- bsts family = "poisson" and family = "logit": StateSpacePoissonModel + StateSpacePoissonPosteriorSampler
 // (Models/StateSpace/StateSpacePoissonModel.cpp, PosteriorSamplers/StateSpacePoissonPosteriorSampler.cpp:
-// 79-147, StateSpacePosteriorSampler.cpp:42-64).  The observation model is the Poisson path's
-// (probit_kernel.hip: the auxiliary-mixture imputation; the SpikeSlabSampler sweep at sigma^2 = 1 on
-// every chain's own V = slab precision + X'QX through the column service), the state draw the
-// general structural kernel on every chain's own series v_t with H_t = 1 / q_t.
+// 79-147), StateSpaceLogitModel + StateSpaceLogitPosteriorSampler (StateSpaceLogitModel.cpp,
+// StateSpaceLogitPosteriorSampler.cpp:49-123), both under StateSpacePosteriorSampler.cpp:42-64.  The
+// observation model is the family's regression path's (probit_kernel.hip: the auxiliary-mixture
+// imputation; the SpikeSlabSampler sweep at sigma^2 = 1 on every chain's own V = slab precision +
+// X'QX through the column service), the state draw the general structural kernel on every chain's
+// own series v_t with H_t = 1 / q_t.  One set of helpers serves both kinds; what differs is here:
 namespace boom_amd {
 
+// the kind's family number for the launchers (probit_kernel.hip), its name in a refusal, and the
+// precision a new model gives an observed step: 1 (AugmentedPoissonRegressionData::add_data), or
+// 4 / n_t (AugmentedBinomialRegressionData::add_data, StateSpaceLogitModel.cpp:67-74)
+static int ssp_family(const ba_engine *e) { return e->data_kind == DATA_SS_LOGIT ? 1 : 0; }
+static double ssp_initial_precision(const ba_engine *e, size_t t) {
+  return e->data_kind == DATA_SS_LOGIT ? 4.0 / e->ssp_trials[t] : 1.0;
+}
+
 // the buffers of the kind beyond ss_prepare's and the column service's: v_t and H_t; new latent
-// data are v = 0, q = 1 (AugmentedPoissonRegressionData::add_data; 0 where the step is missing)
+// data are v = 0, q = the family's initial precision (0 where the step is missing)
 static int ssp_buffers(ba_engine *e) {
   int rc = alloc_chain_state(e);
   if (rc) return rc;
@@ -1758,7 +1770,7 @@ static int ssp_buffers(ba_engine *e) {
     HIP_TRY(e->dssp_h.resize(C * T));
     std::vector<double> q(C * T);
     for (size_t c = 0; c < C; ++c)
-      for (size_t t = 0; t < T; ++t) q[c * T + t] = e->ssp_observed[t] ? 1.0 : 0.0;
+      for (size_t t = 0; t < T; ++t) q[c * T + t] = e->ssp_observed[t] ? ssp_initial_precision(e, t) : 0.0;
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(e->lat.w.ptr, q.data(), C * T * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(e->dssp_value.ptr, 0, C * T * 8));
@@ -1767,21 +1779,25 @@ static int ssp_buffers(ba_engine *e) {
   return BA_OK;
 }
 
-static int ssp_prepare(ba_engine *e) {
-  int rc = sweep_refusal(e, DATA_SS_POISSON);
+static int ssp_prepare(ba_engine *e, DataKind kind) {
+  int rc = sweep_refusal(e, kind);
   if (rc) return rc;
-  if (!e->poisson_mix_set) return fail(BA_E_STATE, "call ba_poisson_set_mixtures first");
-  if (!e->ssm_set)
-    return fail(BA_E_STATE, e->ss_level_set
-                                ? "the Poisson state-space family takes a list of state models: call ba_ss_add_state_model "
-                                  "(a local level is the one-block list), not ba_ss_set_local_level"
-                                : "call ba_ss_add_state_model first");
+  const bool logit = kind == DATA_SS_LOGIT;
+  if (!logit && !e->poisson_mix_set) return fail(BA_E_STATE, "call ba_poisson_set_mixtures first");
+  if (!e->ssm_set) {
+    if (!e->ss_level_set) return fail(BA_E_STATE, "call ba_ss_add_state_model first");
+    return fail(BA_E_STATE, logit ? "the logit state-space family takes a list of state models: call ba_ss_add_state_model "
+                                    "(a local level is the one-block list), not ba_ss_set_local_level"
+                                  : "the Poisson state-space family takes a list of state models: call ba_ss_add_state_model "
+                                    "(a local level is the one-block list), not ba_ss_set_local_level");
+  }
   if (!e->have_slab) return fail(BA_E_STATE, "call ba_sss_set_slab first");
   if (e->sss_slab_scales)
-    return fail(BA_E_INVALID, "the Poisson state-space sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
+    return fail(BA_E_INVALID, logit ? "the logit state-space sampler takes a fixed-precision slab (scales_with_sigsq = 0)"
+                                    : "the Poisson state-space sampler takes a fixed-precision slab (scales_with_sigsq = 0)");
   rc = switch_mode(e, 1, 1.0);
   if (rc) return rc;
-  rc = ss_prepare(e, DATA_SS_POISSON);
+  rc = ss_prepare(e, kind);
   if (rc) return rc;
   rc = set_unit_sigsq(e);   // (the latent data have unit variance, as in logit_family_sweep)
   if (rc) return rc;
@@ -1807,12 +1823,125 @@ static void fill_ssp_params(ba_engine *e, SsParams &S, ProbitParams &Q) {
 // Base::impute_state with the latent data in hand: H_t, the state draw (the state models'
 // parameters as they stand when draw == 0), then the offsets' consequences -- z, X'Qz, the diagonal of V
 static int ssp_impute_state(ba_engine *e, const SsParams &S, const ProbitParams &Q, int draw) {
-  HIP_TRY(launch_poisson_ss_latent(e->stream, Q, 0));
+  const int family = ssp_family(e);
+  HIP_TRY(launch_latent_ss_h(e->stream, Q, family, 0));
   HIP_TRY(launch_ssm_simsmooth(e->stream, S, draw));
-  HIP_TRY(launch_poisson_ss_suf(e->stream, Q, e->lat.Xsq.ptr, e->dA.ptr, e->cols.vdiag.ptr, e->cols.planes.ptr));
+  HIP_TRY(launch_latent_ss_suf(e->stream, Q, family, e->lat.Xsq.ptr, e->dA.ptr, e->cols.vdiag.ptr, e->cols.planes.ptr));
   e->ss_initialized = true;
   e->ssp_ready = true;
   return BA_OK;
+}
+
+// ba_ss_poisson_get_latent / ba_ss_logit_get_latent
+static int ssp_get_latent(ba_engine *e, DataKind kind, int64_t chain, double *value, double *precision) {
+  if (!value || !precision) return fail(BA_E_INVALID, "null argument");
+  if (e->data_kind != kind) return fail(BA_E_STATE, set_data_first(kind));
+  int rc = read_chain_row(e, chain, e->dssp_value, (size_t)e->T, value, [&] { return ssp_buffers(e); });
+  if (rc) return rc;
+  return read_chain_row(e, chain, e->lat.w, (size_t)e->T, precision, [&] { return BA_OK; });
+}
+
+// ba_ss_poisson_set_latent / ba_ss_logit_set_latent
+static int ssp_set_latent(ba_engine *e, DataKind kind, int64_t chain, const double *value, const double *precision) {
+  if (!value || !precision) return fail(BA_E_INVALID, "null argument");
+  if (e->data_kind != kind) return fail(BA_E_STATE, set_data_first(kind));
+  if (chain < -1 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  const size_t T = (size_t)e->T, C = (size_t)e->cfg.chains;
+  std::vector<double> v(T, 0.0), q(T, 0.0);   // (a missing step's entries are not read)
+  for (size_t t = 0; t < T; ++t) {
+    if (!e->ssp_observed[t]) continue;
+    if (precision[t] < 0) return fail(BA_E_INVALID, "precision must be non-negative.");
+    // (the reference takes these and then filters with a variance of -infinity)
+    if (!(precision[t] > 0) || !std::isfinite(precision[t]))
+      return fail(BA_E_INVALID, "the precision of an observed step must be positive and finite");
+    if (!std::isfinite(value[t])) return fail(BA_E_INVALID, "the latent value of an observed step must be finite");
+    v[t] = value[t];
+    q[t] = precision[t];
+  }
+  int rc = ssp_buffers(e);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (size_t c = chain < 0 ? 0 : (size_t)chain; c < (chain < 0 ? C : (size_t)chain + 1); ++c) {
+    HIP_TRY(hipMemcpy(e->dssp_value.ptr + c * T, v.data(), T * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->lat.w.ptr + c * T, q.data(), T * 8, hipMemcpyHostToDevice));
+  }
+  e->ssp_ready = false;   // (the statistics in hand are not these data's: the next call draws the state first)
+  return BA_OK;
+}
+
+// ba_ss_poisson_impute_state / ba_ss_logit_impute_state
+static int ssp_impute_state_entry(ba_engine *e, DataKind kind) {
+  int rc = ssp_prepare(e, kind);
+  if (rc) return rc;
+  SsParams S;
+  ProbitParams Q;
+  fill_ssp_params(e, S, Q);
+  rc = ssp_impute_state(e, S, Q, 0);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return check_chain_status(e);
+}
+
+// ba_ss_poisson_sweep / ba_ss_logit_sweep: nsweeps x StateSpacePosteriorSampler::draw
+// (StateSpacePosteriorSampler.cpp:42-64) with the kind's observation model, every chain
+static int ssp_sweep(ba_engine *e, DataKind kind, int32_t nsweeps) {
+  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
+  int rc = ssp_prepare(e, kind);
+  if (rc) return rc;
+  const int family = ssp_family(e);
+  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p;
+  if (e->trace_stride > 0 && nsweeps > e->trace_stride)
+    return fail(BA_E_INVALID, "nsweeps exceeds the enabled trace length");
+  SsvsParams P;
+  fill_params(e, P);
+  SsParams S;
+  ProbitParams Q;
+  fill_ssp_params(e, S, Q);
+  if (e->trace_stride > 0) HIP_TRY(hipMemsetAsync(e->dtrace_idx.ptr, 0, C * 4, e->stream));
+  if (nsweeps == 0) return BA_OK;
+  if (!e->ssp_ready) {
+    // the sampler's first draw(): impute_state with the latent data as they stand (v = 0, q = the
+    // family's initial precision unless the caller set them), then -- latent data not initialised
+    // yet -- impute_nonstate_latent_data.  Every value that imputation writes is overwritten by the
+    // round's own (step 3 below) before anything reads it -- the statistics are taken at
+    // impute_state -- so it is not launched; only its slots of the imputation stream (11 Poisson,
+    // 9 logit) are used up: the counter moves on, and round r of a fresh sampler imputes with
+    // s = r + 1.
+    const bool first = !e->ss_initialized;
+    rc = ssp_impute_state(e, S, Q, 0);
+    if (rc) return rc;
+    if (first) ++e->lat.draws;
+  }
+  for (int i = 0; i < nsweeps; ++i) {
+    // 1. the observation model's sampler with fix_latent_data(true)
+    // (PoissonRegressionSpikeSlabSampler::draw, PoissonRegressionSpikeSlabSampler.cpp:55-59;
+    // BinomialLogitSpikeSlabSampler::draw): indicators and beta at sigma^2 = 1 on the statistics
+    // of the last impute_state
+    HIP_TRY(launch_xtwx_cols_start(e->stream, e->dgamma.ptr, (int)C, (int)p, e->cols.req.ptr, e->cols.count.ptr,
+                                   e->cols.valid.ptr, e->cols.words));
+    int32_t R = 0;
+    HIP_TRY(hipMemcpyAsync(&R, e->cols.count.ptr, 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    rc = build_columns(e, R);
+    if (rc) return rc;
+    HIP_TRY(launch_sweeps(e, P, 1));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    rc = check_chain_status(e);   // (park-and-replay for vectors of V asked for mid-sweep)
+    if (rc) return rc;
+    // 2. - 4. impute_nonstate_latent_data at the new beta and the last state draw, then the state
+    // models' samplers and impute_state (one kernel: the samplers read their own streams and the
+    // statistics of the last state draw, so their place before or after the imputation does not show)
+    Q.sweep = e->lat.draws++;
+    HIP_TRY(launch_latent_ss_h(e->stream, Q, family, 1));
+    HIP_TRY(launch_ssm_simsmooth(e->stream, S, 1));
+    // 5. the complete-data statistics of the next round's observation draw
+    HIP_TRY(launch_latent_ss_suf(e->stream, Q, family, e->lat.Xsq.ptr, e->dA.ptr, e->cols.vdiag.ptr, e->cols.planes.ptr));
+    fill_params(e, P);
+  }
+  e->table_ok = false;
+  e->model_ok = false;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return check_chain_status(e);
 }
 
 }  // namespace boom_amd
@@ -1855,115 +1984,88 @@ int ba_ss_poisson_set_data(ba_engine *e, int32_t T, int32_t p, const double *cou
 
 int ba_ss_poisson_get_latent(ba_engine *e, int64_t chain, double *value, double *precision) {
   ENGINE_PROLOGUE(e);
-  if (!value || !precision) return fail(BA_E_INVALID, "null argument");
-  if (e->data_kind != DATA_SS_POISSON) return fail(BA_E_STATE, set_data_first(DATA_SS_POISSON));
-  int rc = read_chain_row(e, chain, e->dssp_value, (size_t)e->T, value, [&] { return ssp_buffers(e); });
-  if (rc) return rc;
-  return read_chain_row(e, chain, e->lat.w, (size_t)e->T, precision, [&] { return BA_OK; });
+  return ssp_get_latent(e, DATA_SS_POISSON, chain, value, precision);
 }
 
 int ba_ss_poisson_set_latent(ba_engine *e, int64_t chain, const double *value, const double *precision) {
   ENGINE_PROLOGUE(e);
   MUTATE(e);
-  if (!value || !precision) return fail(BA_E_INVALID, "null argument");
-  if (e->data_kind != DATA_SS_POISSON) return fail(BA_E_STATE, set_data_first(DATA_SS_POISSON));
-  if (chain < -1 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
-  const size_t T = (size_t)e->T, C = (size_t)e->cfg.chains;
-  std::vector<double> v(T, 0.0), q(T, 0.0);   // (a missing step's entries are not read)
-  for (size_t t = 0; t < T; ++t) {
-    if (!e->ssp_observed[t]) continue;
-    if (precision[t] < 0) return fail(BA_E_INVALID, "precision must be non-negative.");
-    // (the reference takes these and then filters with a variance of -infinity)
-    if (!(precision[t] > 0) || !std::isfinite(precision[t]))
-      return fail(BA_E_INVALID, "the precision of an observed step must be positive and finite");
-    if (!std::isfinite(value[t])) return fail(BA_E_INVALID, "the latent value of an observed step must be finite");
-    v[t] = value[t];
-    q[t] = precision[t];
-  }
-  int rc = ssp_buffers(e);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  for (size_t c = chain < 0 ? 0 : (size_t)chain; c < (chain < 0 ? C : (size_t)chain + 1); ++c) {
-    HIP_TRY(hipMemcpy(e->dssp_value.ptr + c * T, v.data(), T * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->lat.w.ptr + c * T, q.data(), T * 8, hipMemcpyHostToDevice));
-  }
-  e->ssp_ready = false;   // (the statistics in hand are not these data's: the next call draws the state first)
-  return BA_OK;
+  return ssp_set_latent(e, DATA_SS_POISSON, chain, value, precision);
 }
 
 int ba_ss_poisson_impute_state(ba_engine *e) {
   ENGINE_PROLOGUE(e);
   MUTATE(e);
-  int rc = ssp_prepare(e);
-  if (rc) return rc;
-  SsParams S;
-  ProbitParams Q;
-  fill_ssp_params(e, S, Q);
-  rc = ssp_impute_state(e, S, Q, 0);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return check_chain_status(e);
+  return ssp_impute_state_entry(e, DATA_SS_POISSON);
 }
 
-// nsweeps x StateSpacePosteriorSampler::draw (StateSpacePosteriorSampler.cpp:42-64) with the
-// Poisson observation model, every chain
 int ba_ss_poisson_sweep(ba_engine *e, int32_t nsweeps) {
   ENGINE_PROLOGUE(e);
   MUTATE(e);
-  if (nsweeps < 0) return fail(BA_E_INVALID, "nsweeps must be non-negative");
-  int rc = ssp_prepare(e);
+  return ssp_sweep(e, DATA_SS_POISSON, nsweeps);
+}
+
+// ---- bsts family = "logit"
+int ba_ss_logit_set_data(ba_engine *e, int32_t T, int32_t p, const double *successes, const double *trials,
+                         const double *X, const uint8_t *observed, int32_t clt_threshold) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!successes || !trials || !X) return fail(BA_E_INVALID, "null argument");
+  if (T <= 0 || p <= 0) return fail(BA_E_INVALID, "T and p must be positive");
+  // (as in ba_logit_set_data: two uniforms per trial of the step's substream of LOGIT_STRIDE)
+  if (clt_threshold < 1 || 4 * clt_threshold > LOGIT_STRIDE)
+    return fail(BA_E_INVALID, "clt_threshold must be between 1 and 64");
+  // (a missing step's successes and trials are never read: 0 and 1 stand in for them on the device)
+  std::vector<double> yo((size_t)T, 0.0), nt((size_t)T, 1.0);
+  std::vector<uint8_t> obs((size_t)T, 1);
+  for (int32_t t = 0; t < T; ++t) {
+    if (observed && !observed[t]) { obs[(size_t)t] = 0; continue; }
+    // (the reference takes n_t = 0 and then filters with a latent value that is not a number)
+    if (!(trials[t] >= 1) || trials[t] != std::floor(trials[t]) || !(trials[t] <= 2147483647.0))
+      return fail(BA_E_INVALID, "trials must be integers of at least 1 at the observed steps");
+    if (!(successes[t] >= 0) || successes[t] != std::floor(successes[t]))
+      return fail(BA_E_INVALID, "successes must be non-negative integers");
+    if (successes[t] > trials[t]) return fail(BA_E_INVALID, "The number of successes must not exceed the number of trials.");
+    yo[(size_t)t] = successes[t];
+    nt[(size_t)t] = trials[t];
+  }
+  int rc = ba_ss_set_data(e, T, p, yo.data(), X, observed);
   if (rc) return rc;
-  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p;
-  if (e->trace_stride > 0 && nsweeps > e->trace_stride)
-    return fail(BA_E_INVALID, "nsweeps exceeds the enabled trace length");
-  SsvsParams P;
-  fill_params(e, P);
-  SsParams S;
-  ProbitParams Q;
-  fill_ssp_params(e, S, Q);
-  if (e->trace_stride > 0) HIP_TRY(hipMemsetAsync(e->dtrace_idx.ptr, 0, C * 4, e->stream));
-  if (nsweeps == 0) return BA_OK;
-  if (!e->ssp_ready) {
-    // the sampler's first draw(): impute_state with the latent data as they stand (v = 0, q = 1
-    // unless the caller set them), then -- latent data not initialised yet --
-    // impute_nonstate_latent_data.  Every value that imputation writes is overwritten by the
-    // round's own (step 3 below) before anything reads it -- the statistics are taken at
-    // impute_state -- so it is not launched; only its slots of stream 11 are used up: the
-    // counter moves on, and round r of a fresh sampler imputes with s = r + 1.
-    const bool first = !e->ss_initialized;
-    rc = ssp_impute_state(e, S, Q, 0);
-    if (rc) return rc;
-    if (first) ++e->lat.draws;
-  }
-  for (int i = 0; i < nsweeps; ++i) {
-    // 1. the observation model's sampler with fix_latent_data(true)
-    // (PoissonRegressionSpikeSlabSampler::draw, PoissonRegressionSpikeSlabSampler.cpp:55-59):
-    // indicators and beta at sigma^2 = 1 on the statistics of the last impute_state
-    HIP_TRY(launch_xtwx_cols_start(e->stream, e->dgamma.ptr, (int)C, (int)p, e->cols.req.ptr, e->cols.count.ptr,
-                                   e->cols.valid.ptr, e->cols.words));
-    int32_t R = 0;
-    HIP_TRY(hipMemcpyAsync(&R, e->cols.count.ptr, 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    rc = build_columns(e, R);
-    if (rc) return rc;
-    HIP_TRY(launch_sweeps(e, P, 1));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    rc = check_chain_status(e);   // (park-and-replay for vectors of V asked for mid-sweep)
-    if (rc) return rc;
-    // 2. - 4. impute_nonstate_latent_data at the new beta and the last state draw, then the state
-    // models' samplers and impute_state (one kernel: the samplers read their own streams and the
-    // statistics of the last state draw, so their place before or after the imputation does not show)
-    Q.sweep = e->lat.draws++;
-    HIP_TRY(launch_poisson_ss_latent(e->stream, Q, 1));
-    HIP_TRY(launch_ssm_simsmooth(e->stream, S, 1));
-    // 5. the complete-data statistics of the next round's observation draw
-    HIP_TRY(launch_poisson_ss_suf(e->stream, Q, e->lat.Xsq.ptr, e->dA.ptr, e->cols.vdiag.ptr, e->cols.planes.ptr));
-    fill_params(e, P);
-  }
-  e->table_ok = false;
-  e->model_ok = false;
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return check_chain_status(e);
+  // the logit path's view of the same data (n = T): X, successes, trials, X squared
+  rc = upload_latent_data(e, T, p, X, yo.data(), nt.data(), /*squared=*/true, clt_threshold);
+  if (rc) return rc;
+  // a new model (v = 0, q = 4 / n_t) and a sampler whose latent data are not initialised
+  e->ssp_observed = obs;
+  e->ssp_trials = nt;
+  e->lat.w.release();
+  e->dssp_value.release();
+  e->dssp_h.release();
+  e->ssp_ready = false;
+  e->data_kind = DATA_SS_LOGIT;
+  return BA_OK;
+}
+
+int ba_ss_logit_get_latent(ba_engine *e, int64_t chain, double *value, double *precision) {
+  ENGINE_PROLOGUE(e);
+  return ssp_get_latent(e, DATA_SS_LOGIT, chain, value, precision);
+}
+
+int ba_ss_logit_set_latent(ba_engine *e, int64_t chain, const double *value, const double *precision) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  return ssp_set_latent(e, DATA_SS_LOGIT, chain, value, precision);
+}
+
+int ba_ss_logit_impute_state(ba_engine *e) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  return ssp_impute_state_entry(e, DATA_SS_LOGIT);
+}
+
+int ba_ss_logit_sweep(ba_engine *e, int32_t nsweeps) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  return ssp_sweep(e, DATA_SS_LOGIT, nsweeps);
 }
 
 }  // extern "C"

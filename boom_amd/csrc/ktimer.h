@@ -31,7 +31,8 @@ enum KernelClass {
   KT_QUANTILE_IMPUTE,  // quantile_impute_kernel
   KT_MLOGIT_IMPUTE,    // mlogit_impute_kernel + mlogit_wss_kernel
   KT_SS_STUDENT,       // student_impute_kernel<true> / student_ss_h_kernel / student_ss_suf_kernel (bsts family = student)
-  KT_SS_POISSON,       // poisson_impute_kernel<true> / poisson_ss_h_kernel / poisson_ss_suf_kernel (bsts family = poisson)
+  KT_SS_POISSON,       // poisson_impute_kernel<true> / latent_ss_h_kernel / latent_ss_suf_kernel (bsts family = poisson)
+  KT_SS_LOGIT,         // logit_impute_kernel<true> / latent_ss_h_kernel / latent_ss_suf_kernel (bsts family = logit)
   KT_CLASSES
 };
 

@@ -465,6 +465,13 @@ __global__ __launch_bounds__(256) void probit_impute_kernel(ProbitParams P) {
 // clt_threshold trials takes the large-sample branch below (16 binomial draws and a
 // normal one, a data-dependent number of uniforms).  Observation i of sweep s reads
 // the chain's worker stream (id 9) from position (s n + i) * LOGIT_STRIDE.
+// SS: the state space logit family (StateSpaceLogitPosteriorSampler::impute_nonstate_latent_data,
+// StateSpaceLogitPosteriorSampler.cpp:82-105): one thread per (chain, step).  eta_t = x_t'beta +
+// offset_t (the chain's Z_t'alpha_t); the step's latent value v_t = sum / info, its precision
+// q_t = info and the filter's H_t = 1 / q_t are written (z is left to latent_ss_suf_kernel, after
+// the state draw).  A missing step reads neither successes, trials nor random number: q = 0,
+// v = 0, H = pi^2 / 3 (AugmentedBinomialRegressionData::latent_data_overall_variance).
+template <bool SS>
 __global__ __launch_bounds__(256) void logit_impute_kernel(ProbitParams P) {
   const double MIX_SIGMA[9] = {0.88437229872213, 1.16097607474416, 1.28021991084306,
                                1.3592552924727,  1.67589879794907, 2.20287232043947,
@@ -487,6 +494,16 @@ __global__ __launch_bounds__(256) void logit_impute_kernel(ProbitParams P) {
   if (i >= P.n) return;
   double eta = 0.0;
   for (int m = 0; m < k; ++m) eta += P.X[(size_t)s_idx[m] * P.n + i] * s_beta[m];
+  if (SS) {
+    if (!P.observed[i]) {
+      const size_t at = (size_t)chain * P.n + i;
+      P.w[at] = 0.0;
+      P.value[at] = 0.0;
+      P.h[at] = LOGIT_MISSING_VARIANCE;
+      return;
+    }
+    eta = P.offset[(size_t)chain * P.offset_stride + i] + eta;   // (state_contribution + regression_contribution)
+  }
   const long nt = lround(P.ntrials[i]), ys = lround(P.y[i]);
   SeqRng rng = SeqRng::slot(PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), 9u},
                             P.sweep * (uint64_t)P.n + (uint64_t)i, LOGIT_STRIDE, slot_serve(P.slot_limit, LOGIT_STRIDE));
@@ -565,6 +582,17 @@ __global__ __launch_bounds__(256) void logit_impute_kernel(ProbitParams P) {
       info += wgt;
       sum += latent * wgt;
     }
+  }
+  if (SS) {
+    // (one epilogue behind both branches: the stores add nothing to the branches' live ranges)
+    if (rng.overran()) P.status[chain] = CHAIN_RNG_BRANCH;
+    // (the reference's latent_data_overall_variance is not a variance for such a precision)
+    if (!(info > 0.0) || !isfinite(info)) P.status[chain] = CHAIN_FORECAST_VARIANCE;
+    const size_t at = (size_t)chain * P.n + i;
+    P.value[at] = sum / info;
+    P.w[at] = info;
+    P.h[at] = 1.0 / info;
+    return;
   }
   P.z[(size_t)chain * P.n + i] = sum;
   P.w[(size_t)chain * P.n + i] = info;
@@ -785,7 +813,7 @@ __device__ __forceinline__ void poisson_unmix(const ProbitParams &P, SeqRng &rng
 // impute_nonstate_latent_data, StateSpacePoissonPosteriorSampler.cpp:79-128): one thread per
 // (chain, step).  eta_t = x_t'beta + offset_t (the chain's Z_t'alpha_t); the two points are
 // combined the external one first, and the step's latent value v_t = sum / q_t, its precision
-// q_t and the filter's H_t = 1 / q_t are written (z is left to poisson_ss_suf_kernel, after the
+// q_t and the filter's H_t = 1 / q_t are written (z is left to latent_ss_suf_kernel, after the
 // state draw).  A missing step reads neither count, exposure, mixture nor random number: q = 0,
 // v = 0, H = pi^2 / 6 (AugmentedPoissonRegressionData::latent_data_overall_variance).
 template <bool SS>
@@ -874,14 +902,15 @@ __global__ __launch_bounds__(256) void poisson_impute_kernel(ProbitParams P) {
   P.w[(size_t)chain * P.n + i] = info;
 }
 
-// the state space Poisson family's H_t from the latent data in hand (all precisions 1 of the first
-// round, ba_ss_poisson_set_latent): the same rule as poisson_impute_kernel<true>
-__global__ __launch_bounds__(256) void poisson_ss_h_kernel(ProbitParams P) {
+// the state space Poisson and logit families' H_t from the latent data in hand (the precisions a
+// new model starts with, ba_ss_poisson_set_latent / ba_ss_logit_set_latent): the same rule as the
+// <true> imputation kernels'; a missing step gets the family's variance
+__global__ __launch_bounds__(256) void latent_ss_h_kernel(ProbitParams P, double missing_variance) {
   const int chain = (int)blockIdx.y, i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (i >= P.n || P.status[chain] != CHAIN_OK) return;
   const size_t at = (size_t)chain * P.n + i;
   if (!P.observed[i]) {
-    P.h[at] = POISSON_MISSING_VARIANCE;
+    P.h[at] = missing_variance;
     return;
   }
   const double q = P.w[at];
@@ -891,8 +920,9 @@ __global__ __launch_bounds__(256) void poisson_ss_h_kernel(ProbitParams P) {
 
 // ... and after the state draw the complete-data response z_t = (v_t - offset_t) q_t, 0 (and
 // weight 0) where the step is missing (update_complete_data_sufficient_statistics,
-// StateSpacePoissonPosteriorSampler.cpp:134-147): the rows of the X'Qz GEMM
-__global__ __launch_bounds__(256) void poisson_ss_suf_kernel(ProbitParams P) {
+// StateSpacePoissonPosteriorSampler.cpp:134-147, StateSpaceLogitPosteriorSampler.cpp:111-123):
+// the rows of the X'Qz GEMM
+__global__ __launch_bounds__(256) void latent_ss_suf_kernel(ProbitParams P) {
   const int chain = (int)blockIdx.y, i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (i >= P.n) return;
   const size_t at = (size_t)chain * P.n + i;
@@ -930,7 +960,7 @@ hipError_t launch_logit_impute(hipStream_t stream, const ProbitParams &P, const 
     else if (polya_gamma)
       hipLaunchKernelGGL(logit_pg_impute_kernel, dim3((P.n + 255) / 256, P.chains), dim3(256), 0, stream, P);
     else
-      hipLaunchKernelGGL(logit_impute_kernel, dim3((P.n + 255) / 256, P.chains), dim3(256), 0, stream, P);
+      hipLaunchKernelGGL(logit_impute_kernel<false>, dim3((P.n + 255) / 256, P.chains), dim3(256), 0, stream, P);
     err = hipGetLastError();
   }
   if (err != hipSuccess) return err;
@@ -938,23 +968,26 @@ hipError_t launch_logit_impute(hipStream_t stream, const ProbitParams &P, const 
                                 planes);
 }
 
-// the state space Poisson family: the latent data (draw != 0: a new imputation, else H_t from the
-// data in hand) ...
-hipError_t launch_poisson_ss_latent(hipStream_t stream, const ProbitParams &P, int draw) {
-  KtScope kt(stream, KT_SS_POISSON);
+// the state space Poisson (family 0) and logit (family 1) families: the latent data (draw != 0: a
+// new imputation, else H_t from the data in hand) ...
+hipError_t launch_latent_ss_h(hipStream_t stream, const ProbitParams &P, int family, int draw) {
+  KtScope kt(stream, family ? KT_SS_LOGIT : KT_SS_POISSON);
   const dim3 grid((P.n + 255) / 256, P.chains);
-  if (draw) hipLaunchKernelGGL(poisson_impute_kernel<true>, grid, dim3(256), 0, stream, P);
-  else hipLaunchKernelGGL(poisson_ss_h_kernel, grid, dim3(256), 0, stream, P);
+  if (!draw)
+    hipLaunchKernelGGL(latent_ss_h_kernel, grid, dim3(256), 0, stream, P,
+                       family ? LOGIT_MISSING_VARIANCE : POISSON_MISSING_VARIANCE);
+  else if (family) hipLaunchKernelGGL(logit_impute_kernel<true>, grid, dim3(256), 0, stream, P);
+  else hipLaunchKernelGGL(poisson_impute_kernel<true>, grid, dim3(256), 0, stream, P);
   return hipGetLastError();
 }
 
 // ... and after the state draw z, X'Qz and the diagonal of V = slab precision + X'QX
-hipError_t launch_poisson_ss_suf(hipStream_t stream, const ProbitParams &P, const double *Xsq,
-                                 const double *slab_precision, double *v_diag, double *planes) {
+hipError_t launch_latent_ss_suf(hipStream_t stream, const ProbitParams &P, int family, const double *Xsq,
+                                const double *slab_precision, double *v_diag, double *planes) {
   hipError_t err;
   {
-    KtScope kt(stream, KT_SS_POISSON);
-    hipLaunchKernelGGL(poisson_ss_suf_kernel, dim3((P.n + 255) / 256, P.chains), dim3(256), 0, stream, P);
+    KtScope kt(stream, family ? KT_SS_LOGIT : KT_SS_POISSON);
+    hipLaunchKernelGGL(latent_ss_suf_kernel, dim3((P.n + 255) / 256, P.chains), dim3(256), 0, stream, P);
     err = hipGetLastError();
   }
   if (err != hipSuccess) return err;

@@ -633,6 +633,35 @@ PYBIND11_MODULE(_boom, boom) {
       .def("draw", &StateSpacePoissonPosteriorSampler::draw)
       .def("limit_model_selection", &StateSpacePoissonPosteriorSampler::limit_model_selection);
 
+  // ---- bsts family = "logit" (StateSpaceLogitModel, StateSpaceLogitPosteriorSampler): the state
+  // space model's bindings, inherited, + the binomial logit observation model's -----------------
+  py::class_<StateSpaceLogitModel, StateSpaceRegressionModel, Ptr<StateSpaceLogitModel>>(boom, "StateSpaceLogitModel")
+      .def(py::init([](const NpArray &successes, const NpArray &trials, const NpArray &predictors,
+                       const std::vector<bool> &is_observed, int chains, uint64_t seed, int device, int clt_threshold) {
+             return new StateSpaceLogitModel(vector_from(successes), vector_from(trials), matrix_from(predictors),
+                                             is_observed, chains, seed, device, clt_threshold);
+           }),
+           py::arg("successes"), py::arg("trials"), py::arg("predictors"), py::arg("is_observed") = std::vector<bool>(),
+           py::arg("chains") = 1, py::arg("seed") = 8675309ull, py::arg("device") = 0, py::arg("clt_threshold") = 5)
+      .def("latent_values", [](const StateSpaceLogitModel &m, int chain) { return to_numpy(m.latent_values(chain)); },
+           py::arg("chain") = 0, "the latent values of one chain (0 at a missing step)")
+      .def("latent_precisions", [](const StateSpaceLogitModel &m, int chain) { return to_numpy(m.latent_precisions(chain)); },
+           py::arg("chain") = 0, "the latent values' precisions in one chain (0 at a missing step)")
+      .def("set_latent_data", [](StateSpaceLogitModel &m, const NpArray &value, const NpArray &precision, int chain) {
+             m.set_latent_data(vector_from(value), vector_from(precision), chain);
+           }, py::arg("value"), py::arg("precision"), py::arg("chain") = -1)
+      .def("impute_state", &StateSpaceLogitModel::impute_state);
+  py::class_<StateSpaceLogitPosteriorSampler, PosteriorSampler, Ptr<StateSpaceLogitPosteriorSampler>>(
+      boom, "StateSpaceLogitPosteriorSampler")
+      .def(py::init([](StateSpaceLogitModel *model, const Ptr<MvnModel> &slab,
+                       const Ptr<VariableSelectionPrior> &spike, py::object) {
+             return new StateSpaceLogitPosteriorSampler(model, slab, spike);
+           }),
+           py::arg("model"), py::arg("slab"), py::arg("spike"), py::arg("seeding_rng") = py::none(),
+           py::keep_alive<1, 2>())
+      .def("draw", &StateSpaceLogitPosteriorSampler::draw)
+      .def("limit_model_selection", &StateSpaceLogitPosteriorSampler::limit_model_selection);
+
   // ---- quantile regression spike and slab (QuantileRegressionModel,
   // QuantileRegressionSpikeSlabSampler) -----------------------------------------------------
   py::class_<QuantileRegressionModel, Ptr<QuantileRegressionModel>>(boom, "QuantileRegressionModel")

@@ -797,6 +797,57 @@ int ba_ss_poisson_sweep(ba_engine *e, int32_t nsweeps);
 int ba_ss_poisson_impute_state(ba_engine *e);
 int ba_ss_poisson_get_latent(ba_engine *e, int64_t chain, double *value, double *precision);
 int ba_ss_poisson_set_latent(ba_engine *e, int64_t chain, const double *value, const double *precision);
+
+/* ---- bsts(family = "logit"): StateSpaceLogitModel with StateSpaceLogitPosteriorSampler
+ * (Models/StateSpace/StateSpaceLogitModel.cpp, PosteriorSamplers/
+ * StateSpaceLogitPosteriorSampler.cpp:49-123) ------------------------------------------------------
+ * One observation per time step, regression present.  An observed step carries successes y_t, trials
+ * n_t, a latent value v_t and a precision q_t (0 and 4 / n_t in a new model); the filter sees
+ * v_t - x_t'beta with the observation variance H_t = 1 / q_t, pi^2 / 3 (the variance of the standard
+ * logistic distribution) where the step is missing.  The observation model is
+ * BinomialLogitSpikeSlabSampler with its latent data fixed (the sweep of ba_logit_sweep at
+ * sigma^2 = 1 on the response v_t - Z_t'alpha_t with weight q_t over the observed steps); the
+ * imputation is BinomialLogitCltDataImputer::impute(n_t, y_t, eta_t) at eta_t = Z_t'alpha_t +
+ * x_t'beta (two uniforms per trial up to clt_threshold trials, the large-sample branch above), then
+ * v_t = sum / information, q_t = information; the state draw is the general structural kernel on
+ * every chain's own series.  There is no Polya-Gamma imputer in this sampler.
+ *   ba_ss_logit_set_data     successes, trials, X (T x p column-major), observed (NULL: all),
+ *                            clt_threshold (1 .. 64, as in ba_logit_set_data).  At the observed steps
+ *                            trials must be integers of at least 1 and successes integers in
+ *                            0 .. n_t (a missing step's are never read).  The reference accepts
+ *                            n_t = 0 at an observed step and then filters with a latent value that is
+ *                            not a number; here it is refused.  Starts a new model (v = 0,
+ *                            q = 4 / n_t, no state draw yet)
+ *   state models             ba_ss_add_state_model (a plain local level is the one-block list;
+ *                            after ba_ss_set_local_level alone the family is refused); the general
+ *                            kernel always, whatever ba_ss_set_tuning says
+ *   priors                   ba_sss_set_slab(mu, precision, 0, max_flips) -- a fixed-precision slab --,
+ *                            ba_set_spike.  There is no sigma^2 (it is 1)
+ *   ba_ss_logit_sweep        nsweeps x StateSpacePosteriorSampler::draw (StateSpacePosteriorSampler.cpp:
+ *                            42-64): indicators and beta, the state models' parameters, the latent
+ *                            data, the state.  A sampler that has drawn no state yet first draws it
+ *                            with the latent data in hand and uses up one imputation's random numbers,
+ *                            as the reference's first draw() does (its values are all overwritten
+ *                            before they are read)
+ *   ba_ss_logit_impute_state   one impute_state with the current parameters and latent data
+ *   ba_ss_logit_get_latent / _set_latent   one chain's T values and precisions (set: chain -1 =
+ *                            every chain; a missing step's entries are not read; a negative precision:
+ *                            "precision must be non-negative."; a zero or non-finite precision at an
+ *                            observed step is refused too).  After _set_latent the next sweep starts
+ *                            with an impute_state on the new data.
+ * Also served for this kind: ba_set_state / ba_get_state(s), ba_enable_draws with ba_get_draws, the
+ * summaries, ba_ss_get_state_draw, ba_ss_get_state_model, ba_ss_get_ar, ba_ss_state_dimension,
+ * ba_set_slot_limit.  Not served: ba_ss_forecast, ba_ss_draw_next, ba_ss_sweep, ba_ss_impute_state,
+ * ba_logit_sweep, ba_logit_set_imputer, ba_ss_student_*, ba_ss_poisson_* (refused).
+ * RNG: stream 3 indicators / beta; stream 9 from position (s T + t) * 256 for step t in the
+ * sampler's s-th imputation (the first draw() makes two: round r of a fresh sampler imputes with
+ * s = r + 1); stream 2 the state; the state models' streams as on the Gaussian path. */
+int ba_ss_logit_set_data(ba_engine *e, int32_t T, int32_t p, const double *successes, const double *trials,
+                         const double *X, const uint8_t *observed, int32_t clt_threshold);
+int ba_ss_logit_sweep(ba_engine *e, int32_t nsweeps);
+int ba_ss_logit_impute_state(ba_engine *e);
+int ba_ss_logit_get_latent(ba_engine *e, int64_t chain, double *value, double *precision);
+int ba_ss_logit_set_latent(ba_engine *e, int64_t chain, const double *value, const double *precision);
 /* StateSpaceRegressionModel::simulate_forecast(rng, newX, final_state)
  * (StateSpaceRegressionModel.cpp:214-219, :256-278; what bsts' predict does for
  * every saved draw): one draw from the predictive distribution of the next

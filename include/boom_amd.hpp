@@ -680,6 +680,18 @@ class StateSpaceRegressionModel : public Model {
     eng_->check(ba_ss_poisson_set_data(eng_->get(), T_, p_, counts.data(), exposure.data(), X.data(),
                                        obs.empty() ? nullptr : obs.data()));
   }
+  // StateSpaceLogitModel: the same state, the binomial logit observation model
+  struct LogitFamily {};
+  StateSpaceRegressionModel(LogitFamily, const Vector &successes, const Vector &trials, const Matrix &X,
+                            const std::vector<bool> &observed, int clt_threshold, int chains, uint64_t seed, int device)
+      : eng_(new Engine(chains, seed, device)), T_((int)successes.size()), p_(X.ncol()), list_always_(true) {
+    if (X.nrow() != T_ || (int)trials.size() != T_)
+      report_error("successes, trials and X are incompatible in constructor for StateSpaceLogitModel.");
+    std::vector<uint8_t> obs;
+    if (!observed.empty()) { obs.resize(T_); for (int t = 0; t < T_; ++t) obs[t] = observed[t]; }
+    eng_->check(ba_ss_logit_set_data(eng_->get(), T_, p_, successes.data(), trials.data(), X.data(),
+                                     obs.empty() ? nullptr : obs.data(), clt_threshold));
+  }
  private:
   struct Entry {
     int kind = 0;   // 1 local level, 2 local linear trend, 3 seasonal, 4 autoregression, 5 static intercept, 6 trig, 7 semilocal linear trend
@@ -1185,6 +1197,71 @@ class StateSpacePoissonPosteriorSampler : public PosteriorSampler {
   ba_engine *h() const { return model_->engine()->get(); }
   void check(int rc) const { model_->engine()->check(rc); }
   StateSpacePoissonModel *model_;
+  Ptr<MvnModel> slab_;
+};
+
+// ---- bsts family = "logit" ----------------------------------------------------------------
+// StateSpaceLogitModel + StateSpaceLogitPosteriorSampler (Models/StateSpace/
+// StateSpaceLogitModel.hpp, PosteriorSamplers/StateSpaceLogitPosteriorSampler.cpp:49-123): the
+// state of StateSpaceRegressionModel under BinomialLogitModel's observations, on the device
+// (ba_ss_logit_*).  One observation per time step, regression present.  Chain 0 backs the
+// accessors' defaults.
+class StateSpaceLogitModel : public StateSpaceRegressionModel {
+ public:
+  StateSpaceLogitModel(const Vector &successes, const Vector &trials, const Matrix &X,
+                       const std::vector<bool> &observed, int chains = 1, uint64_t seed = 8675309, int device = 0,
+                       int clt_threshold = 5)
+      : StateSpaceRegressionModel(LogitFamily(), successes, trials, X, observed, clt_threshold, chains, seed, device) {}
+  // one chain's latent data (AugmentedBinomialRegressionData::latent_data_value and the
+  // precisions behind latent_data_variance); 0 at a missing step
+  Vector latent_values(int chain = 0) const {
+    Vector v(time_dimension()), q(time_dimension());
+    engine()->check(ba_ss_logit_get_latent(engine()->get(), chain, v.data(), q.data()));
+    return v;
+  }
+  Vector latent_precisions(int chain = 0) const {
+    Vector v(time_dimension()), q(time_dimension());
+    engine()->check(ba_ss_logit_get_latent(engine()->get(), chain, v.data(), q.data()));
+    return q;
+  }
+  void set_latent_data(const Vector &value, const Vector &precision, int chain = -1) {   // set_latent_data, every step (chain -1: every chain)
+    if ((int)value.size() != time_dimension() || (int)precision.size() != time_dimension())
+      report_error("One latent value and one precision per time step are needed.");
+    engine()->check(ba_ss_logit_set_latent(engine()->get(), chain, value.data(), precision.data()));
+  }
+  void impute_state() {   // Base::impute_state with the current parameters and latent data
+    finalize_state();
+    engine()->check(ba_ss_logit_impute_state(engine()->get()));
+  }
+};
+// StateSpaceLogitPosteriorSampler(model, observation model sampler's priors): slab and spike as
+// BinomialLogitSpikeSlabSampler takes them
+class StateSpaceLogitPosteriorSampler : public PosteriorSampler {
+ public:
+  StateSpaceLogitPosteriorSampler(StateSpaceLogitModel *model, const Ptr<MvnModel> &slab,
+                                  const Ptr<VariableSelectionPrior> &spike)
+      : model_(model), slab_(slab) {
+    if (slab->dim() != model->xdim()) report_error("Slab does not match model dimension.");
+    if ((int)spike->potential_nvars() != model->xdim()) report_error("Spike does not match model dimension.");
+    check(ba_sss_set_slab(h(), slab->mu().data(), slab->siginv().data(), 0, -1));
+    check(ba_set_spike(h(), spike->prior_inclusion_probabilities().data(), spike->max_model_size()));
+    std::vector<uint8_t> g0(model->xdim(), 0);
+    check(ba_set_state(h(), -1, g0.data(), nullptr, 1.0));
+  }
+  void draw() override {                     // StateSpacePosteriorSampler.cpp:42-64
+    model_->finalize_state();
+    check(ba_ss_logit_sweep(h(), 1));
+    check(ba_sync(h()));
+  }
+  double logpri() const override { report_error("logpri() is not implemented for the logit state space sampler"); return 0; }
+  void set_seed(unsigned long s) override { check(ba_seed(h(), s)); }
+  void limit_model_selection(int max_flips) {
+    check(ba_sss_set_slab(h(), slab_->mu().data(), slab_->siginv().data(), 0, max_flips));
+  }
+ private:
+  ba_engine *h() const { return model_->engine()->get(); }
+  void check(int rc) const { model_->engine()->check(rc); }
+  StateSpaceLogitModel *model_;
   Ptr<MvnModel> slab_;
 };
 
