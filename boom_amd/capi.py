@@ -180,6 +180,9 @@ SIGNATURES = {
     "ba_ss_draw_next": (C.c_int, [C.c_void_p]),
     "ba_ss_impute_state": (C.c_int, [C.c_void_p]),
     "ba_ss_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
+    "ba_ss_student_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
+    "ba_ss_poisson_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp]),
+    "ba_ss_logit_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp]),
     "ba_ss_get_state": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp]),
     "ba_ss_set_level_sigsq": (C.c_int, [C.c_void_p, C.c_int64, C.c_double]),
     "ba_ss_get_chain_suf": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp, _dp]),
@@ -625,6 +628,13 @@ class Engine:
         self._check(self.lib.ba_ss_student_impute_state(self._h))
         self.sync()
 
+    def ss_student_forecast(self, newX):
+        """one predictive draw of the next len(newX) observations per chain (Student-t noise)"""
+        h = newX.shape[0]
+        out = np.zeros((self.chains, h))
+        self._check(self.lib.ba_ss_student_forecast(self._h, h, _p(_fcol(newX)), _p(out)))
+        return out
+
     # ---- StateSpacePoissonPosteriorSampler (bsts family = "poisson") ---------------
     def ss_poisson_set_data(self, counts, exposure, X, mix, observed=None):
         """mix: the dict poisson_set_data takes (the mixtures of 1 and of the positive counts at
@@ -655,6 +665,17 @@ class Engine:
     def ss_poisson_set_latent(self, value, precision, chain=-1):
         self._check(self.lib.ba_ss_poisson_set_latent(self._h, int(chain), _p(_f64(value)), _p(_f64(precision))))
 
+    def ss_poisson_forecast(self, newX, exposure=None):
+        """one predictive draw of the next len(newX) counts per chain; exposure: len(newX) numbers
+        (default: ones)"""
+        h = newX.shape[0]
+        out = np.zeros((self.chains, h))
+        ex = None if exposure is None else _f64(exposure)
+        if ex is not None and ex.shape != (h,):
+            raise ValueError("exposure must have one entry per row of newX")
+        self._check(self.lib.ba_ss_poisson_forecast(self._h, h, _p(_fcol(newX)), _p(ex), _p(out)))
+        return out
+
     # ---- StateSpaceLogitPosteriorSampler (bsts family = "logit") -------------------
     def ss_logit_set_data(self, successes, trials, X, observed=None, clt_threshold=5):
         T, p = X.shape
@@ -681,6 +702,17 @@ class Engine:
 
     def ss_logit_set_latent(self, value, precision, chain=-1):
         self._check(self.lib.ba_ss_logit_set_latent(self._h, int(chain), _p(_f64(value)), _p(_f64(precision))))
+
+    def ss_logit_forecast(self, newX, trials=None):
+        """one predictive draw of the next len(newX) success counts per chain; trials: len(newX)
+        numbers (default: ones)"""
+        h = newX.shape[0]
+        out = np.zeros((self.chains, h))
+        nt = None if trials is None else _f64(trials)
+        if nt is not None and nt.shape != (h,):
+            raise ValueError("trials must have one entry per row of newX")
+        self._check(self.lib.ba_ss_logit_forecast(self._h, h, _p(_fcol(newX)), _p(nt), _p(out)))
+        return out
 
     # ---- QuantileRegressionSpikeSlabSampler --------------------------------------
     def quantile_set_data(self, X, y, quantile):

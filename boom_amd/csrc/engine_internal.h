@@ -55,6 +55,11 @@ int launch_suf_from_xy(hipStream_t stream, int64_t n, int p, const double *X,
 hipError_t launch_ssm_simsmooth(hipStream_t stream, const SsParams &P, int draw_variances);
 hipError_t launch_ssm_forecast(hipStream_t stream, const SsParams &P, int horizon, const double *newX,
                                uint64_t *pos_forecast, double *out);
+// ss_family_forecast_kernel.hip: family = SS_FORECAST_*; scale = the horizon's exposures / rounded trial
+// counts (Poisson, logit), nu = every chain's degrees of freedom (Student-t); the other is not read
+hipError_t launch_ss_family_forecast(hipStream_t stream, const SsParams &P, int family, int horizon,
+                                     const double *newX, const double *scale, const double *nu,
+                                     uint64_t *pos_forecast, double *out);
 hipError_t launch_probit_impute(hipStream_t stream, const ProbitParams &P, double *planes);
 hipError_t launch_student_impute(hipStream_t stream, const StudentParams &P, const double *Xsq,
                                  const double *slab_precision, double *xtz, double *v_diag, double *planes);

@@ -2070,6 +2070,69 @@ int ba_ss_logit_sweep(ba_engine *e, int32_t nsweeps) {
 
 }  // extern "C"
 
+// ---- forecasts of the three families: simulate_forecast of StateSpaceStudentRegressionModel,
+// StateSpacePoissonModel and StateSpaceLogitModel for every chain's current draw
+// (ss_family_forecast_kernel.hip)
+namespace boom_amd {
+
+// scale: the horizon's exposures (Poisson) or trial counts (logit), validated; nullptr: ones
+// (and for the Student-t family, which has none)
+static int ss_family_forecast(ba_engine *e, DataKind kind, int32_t horizon, const double *newX, const double *scale,
+                              double *out) {
+  if (e->data_kind != kind) return fail(BA_E_STATE, set_data_first(kind));
+  if (!newX || !out || horizon <= 0) return fail(BA_E_INVALID, "bad argument");
+  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, h = (size_t)horizon;
+  const bool student = kind == DATA_SS_STUDENT, logit = kind == DATA_SS_LOGIT;
+  std::vector<double> sc(h, 1.0);
+  for (size_t i = 0; scale && i < h; ++i) {
+    if (!(scale[i] >= 0.0) || !std::isfinite(scale[i]))
+      return fail(BA_E_INVALID, logit ? "trial counts of a forecast must be non-negative and finite"
+                                      : "exposures of a forecast must be non-negative and finite");
+    sc[i] = logit ? std::round(scale[i]) : scale[i];   // (lround(trials[i]), StateSpaceLogitModel.cpp:245)
+  }
+  if (!e->ssm_set || e->dssm_work.count == 0 || !e->ss_initialized || (student && e->dstu_nu.count != C))
+    return fail(BA_E_STATE, student ? "no state draw yet: run ba_ss_student_sweep or ba_ss_student_impute_state first"
+                            : logit ? "no state draw yet: run ba_ss_logit_sweep or ba_ss_logit_impute_state first"
+                                    : "no state draw yet: run ba_ss_poisson_sweep or ba_ss_poisson_impute_state first");
+  int rc = ba_sync(e);
+  if (rc) return rc;
+  DevBuf<double> dnx, dsc, dout;
+  HIP_TRY(dnx.resize(h * p));
+  HIP_TRY(dsc.resize(h));
+  HIP_TRY(dout.resize(C * h));
+  HIP_TRY(hipMemcpyAsync(dnx.ptr, newX, h * p * 8, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(dsc.ptr, sc.data(), h * 8, hipMemcpyHostToDevice, e->stream));
+  SsParams S;
+  fill_ss_params(e, S);
+  const int family = student ? SS_FORECAST_STUDENT : logit ? SS_FORECAST_LOGIT : SS_FORECAST_POISSON;
+  HIP_TRY(launch_ss_family_forecast(e->stream, S, family, horizon, dnx.ptr, dsc.ptr, e->dstu_nu.ptr,
+                                    e->dpos_forecast.ptr, dout.ptr));
+  HIP_TRY(hipMemcpyAsync(out, dout.ptr, C * h * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (sc and the pageable copies are done with)
+  return BA_OK;
+}
+
+}  // namespace boom_amd
+
+extern "C" {
+
+int ba_ss_student_forecast(ba_engine *e, int32_t horizon, const double *newX, double *out) {
+  ENGINE_PROLOGUE(e);
+  return ss_family_forecast(e, DATA_SS_STUDENT, horizon, newX, nullptr, out);
+}
+
+int ba_ss_poisson_forecast(ba_engine *e, int32_t horizon, const double *newX, const double *exposure, double *out) {
+  ENGINE_PROLOGUE(e);
+  return ss_family_forecast(e, DATA_SS_POISSON, horizon, newX, exposure, out);
+}
+
+int ba_ss_logit_forecast(ba_engine *e, int32_t horizon, const double *newX, const double *trials, double *out) {
+  ENGINE_PROLOGUE(e);
+  return ss_family_forecast(e, DATA_SS_LOGIT, horizon, newX, trials, out);
+}
+
+}  // extern "C"
+
 #ifdef BA_RSTAMPS
 // diagnostic build only (tools/build/libboomamd_rstamps.so): the round kernel's phase ticks
 // since the last call, chains x 2 x 8, and reset

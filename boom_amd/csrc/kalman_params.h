@@ -25,6 +25,8 @@ enum { SSG_LOCAL_LEVEL = 1, SSG_LOCAL_LINEAR_TREND = 2, SSG_SEASONAL = 3, SSG_AR
        // [0, phi, 1 - phi], [0, 0, 1]]; its (phi, mu) and the slope's Ar1Suf take one of the chain's
        // autoregression slots (ar_phi[0 .. 1]; ar_suf[0 .. 5] = sumsq, sum, cross, n, first, last)
        SSG_SEMILOCAL = 7 };
+// the observation families of ss_family_forecast_kernel.hip (launch_ss_family_forecast)
+enum { SS_FORECAST_STUDENT = 0, SS_FORECAST_POISSON = 1, SS_FORECAST_LOGIT = 2 };
 // a chain's ArModel sufficient statistics (per autoregression block): xtx (lags x lags at
 // leading dimension AR_MAX) | xty | yty | n
 enum { AR_SUF_XTY = AR_MAX * AR_MAX, AR_SUF_YTY = AR_SUF_XTY + AR_MAX, AR_SUF_N = AR_SUF_YTY + 1,

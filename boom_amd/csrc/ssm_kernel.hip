@@ -73,6 +73,7 @@
 #include "stream_normals.h"
 
 #include "ssg_device.h"
+#include "ssg_forecast_device.h"
 
 namespace boom_amd {
 
@@ -1049,7 +1050,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
 // chain's forecast stream (id 5).  One wavefront per chain, lane = state component
 // (logical order; the horizon is short, a seasonal block simply shifts).  As the
 // reference (advance_to_timestamp, StateSpaceModelBase.cpp:455-459) forecast step i
-// uses the transition matrix and state errors of time T - 2 + i.
+// uses the transition matrix and state errors of time T - 2 + i.  The state's step is
+// ssg_forecast_step (ssg_forecast_device.h), which the observation families' forecast kernel
+// (ss_family_forecast_kernel.hip) runs too.
 __global__ __launch_bounds__(64) void ssg_forecast_kernel(SsParams P, int horizon, const double *newX,
                                                           uint64_t *pos_forecast, double *out) {
   const int chain = (int)blockIdx.x + P.chain_first, lane = threadIdx.x;
@@ -1057,74 +1060,15 @@ __global__ __launch_bounds__(64) void ssg_forecast_kernel(SsParams P, int horizo
   if (P.status[chain] != CHAIN_OK) return;
   const SsmParams &M = P.ssm;
   const SsgSpec &Q = *M.spec;
-  const int T = P.T, p = P.p, m = M.m, nb = M.nblocks;
+  const int T = P.T, p = P.p, m = M.m;
   const double *beta = P.beta + (size_t)chain * p;
   const double sd_obs = sqrt(P.sigsq[chain]);
   const double *gst = M.work + (size_t)chain * M.work_stride + (size_t)m * T;
   double st = (lane < m) ? gst[(size_t)(T - 1) * m + lane] : 0.0;
   SeqRng rng{PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), 5u}, pos_forecast[chain]};
   for (int i = 0; i < horizon; ++i) {
-    const int tm = T - 2 + i;   // the transition's index
-    double nx = st;
-    for (int b = 0; b < nb; ++b) {
-      const SsgBlock &K = Q.blk[b];
-      const int f = K.first, n = K.dim;
-      const bool mine = lane >= f && lane < f + n;
-      const double *sg = M.var_sigsq + (size_t)chain * SSG_MAX_VAR + K.var0;
-      if (K.kind == SSG_LOCAL_LEVEL) {
-        const double e0 = d_rnorm(rng, 0.0, sqrt(sg[0]));
-        if (lane == f) nx = st + e0;
-      } else if (K.kind == SSG_LOCAL_LINEAR_TREND) {
-        const double z0 = d_rnorm(rng, 0.0, 1.0), z1 = d_rnorm(rng, 0.0, 1.0);
-        const double x1 = rl(st, f + 1);
-        if (lane == f) nx = (st + x1) + (sqrt(sg[0]) * z0 + 0.0);
-        if (lane == f + 1) nx = st + (sqrt(sg[1]) * z1 + 0.0);
-      } else if (K.kind == SSG_SEMILOCAL) {
-        const double *ph = M.ar_phi + ((size_t)chain * SSG_MAX_AR + K.ar_index) * AR_MAX;
-        const double e0 = d_rnorm(rng, 0.0, sqrt(sg[0])), e1 = d_rnorm(rng, 0.0, sqrt(sg[1]));
-        const double above = from_above(st);
-        if (lane == f) nx = (st + above) + e0;
-        else if (lane == f + 1) nx = (ph[0] * st + (1 - ph[0]) * above) + e1;
-      } else if (K.kind == SSG_TRIG) {
-        // rnorm_mt(rng, 0, sigma) per component, in order (TrigStateModel.cpp:218-223), on the rotated state
-        const double sd = sqrt(sg[0]);
-        const double above = from_above(st), below = from_below(st);
-        const double c = mine ? Q.trig_c[lane] : 0.0, sn = mine ? Q.trig_s[lane] : 0.0;
-        double e4 = 0.0;
-        for (int q = 0; q < n; ++q) {
-          const double eq = d_rnorm(rng, 0.0, sd);
-          if (lane == f + q) e4 = eq;
-        }
-        if (mine) nx = (((lane - f) & 1) ? -sn * below + c * st : c * st + sn * above) + e4;
-      } else if (K.kind == SSG_SEASONAL) {
-        if ((tm + 1) % K.duration == K.phase) {
-          const double e2 = d_rnorm(rng, 0.0, sqrt(sg[0]));
-          // (first = 0 - s_0 - s_1 - ..., SeasonalStateSpaceMatrix::multiply)
-          double firstv = 0.0;
-          for (int q = 0; q < n; ++q) firstv -= rl(st, f + q);
-          const double below = from_below(st);
-          if (lane == f) nx = firstv + e2; else if (mine) nx = below;
-        }
-      } else {
-        const double *ph = M.ar_phi + ((size_t)chain * SSG_MAX_AR + K.ar_index) * AR_MAX;
-        const double e3 = d_rnorm(rng, 0.0, 1.0) * sqrt(sg[0]);
-        // (first = sum of phi_i s_i from the last lag down, AutoRegressionTransitionMatrix::multiply_inplace)
-        double firstv = 0.0;
-        for (int q = n - 1; q >= 0; --q) firstv += ph[q] * rl(st, f + q);
-        const double below = from_below(st);
-        if (lane == f) nx = firstv + e3; else if (mine) nx = below;
-      }
-    }
-    st = (lane < m) ? nx : 0.0;
-    // Z'state: the blocks' first components (a trig block: every pair's first), in state order
-    double zs = 0.0;
-    for (int b = 0; b < nb; ++b) {
-      const SsgBlock &K = Q.blk[b];
-      for (int i = 0; i < (K.kind == SSG_TRIG ? K.dim : 1); i += 2) {
-        const double zv = rl(st, K.first + i);
-        zs = (b == 0 && i == 0) ? zv : zs + zv;
-      }
-    }
+    // (the transition's index is T - 2 + i)
+    const double zs = ssg_forecast_step(M, Q, chain, lane, T - 2 + i, rng, st);
     const double obs = d_rnorm(rng, zs, sd_obs);
     double part = 0.0;
     for (int j = lane; j < p; j += WAVE) part += newX[(size_t)j * horizon + i] * beta[j];

@@ -49,6 +49,15 @@ py::array_t<double> to_numpy(const Vector &v) {
   for (size_t i = 0; i < v.size(); ++i) w((py::ssize_t)i) = v[i];
   return out;
 }
+// a family's simulate_forecast (horizon x chains, column c = chain c) as chains x horizon
+py::array_t<double> forecast_to_numpy(const Matrix &m) {
+  py::array_t<double> out({(py::ssize_t)m.ncol(), (py::ssize_t)m.nrow()});
+  auto w = out.mutable_unchecked<2>();
+  for (int c = 0; c < m.ncol(); ++c)
+    for (int i = 0; i < m.nrow(); ++i) w(c, i) = m(i, c);
+  return out;
+}
+Vector optional_vector(const py::object &a) { return a.is_none() ? Vector() : vector_from(a.cast<NpArray>()); }
 
 // GlmCoefs as the drivers use it: model.coef.drop_all() / add / inc / Beta
 struct CoefView {
@@ -578,7 +587,10 @@ PYBIND11_MODULE(_boom, boom) {
       .def("set_weights", [](StateSpaceStudentRegressionModel &m, const NpArray &w, int chain) {
              m.set_weights(vector_from(w), chain);
            }, py::arg("weights"), py::arg("chain") = -1)
-      .def("impute_state", &StateSpaceStudentRegressionModel::impute_state);
+      .def("impute_state", &StateSpaceStudentRegressionModel::impute_state)
+      .def("simulate_forecast", [](StateSpaceStudentRegressionModel &m, const NpArray &predictors) {
+             return forecast_to_numpy(m.simulate_forecast(matrix_from(predictors)));
+           }, py::arg("predictors"), "one predictive draw of the next observations per chain (chains x horizon)");
   py::class_<StateSpaceStudentPosteriorSampler, PosteriorSampler, Ptr<StateSpaceStudentPosteriorSampler>>(
       boom, "StateSpaceStudentPosteriorSampler")
       .def(py::init([](StateSpaceStudentRegressionModel *model, const Ptr<MvnGivenScalarSigma> &slab,
@@ -621,7 +633,11 @@ PYBIND11_MODULE(_boom, boom) {
       .def("set_latent_data", [](StateSpacePoissonModel &m, const NpArray &value, const NpArray &precision, int chain) {
              m.set_latent_data(vector_from(value), vector_from(precision), chain);
            }, py::arg("value"), py::arg("precision"), py::arg("chain") = -1)
-      .def("impute_state", &StateSpacePoissonModel::impute_state);
+      .def("impute_state", &StateSpacePoissonModel::impute_state)
+      .def("simulate_forecast", [](StateSpacePoissonModel &m, const NpArray &predictors, const py::object &exposure) {
+             return forecast_to_numpy(m.simulate_forecast(matrix_from(predictors), optional_vector(exposure)));
+           }, py::arg("predictors"), py::arg("exposure") = py::none(),
+           "one predictive draw of the next counts per chain (chains x horizon); exposure: default ones");
   py::class_<StateSpacePoissonPosteriorSampler, PosteriorSampler, Ptr<StateSpacePoissonPosteriorSampler>>(
       boom, "StateSpacePoissonPosteriorSampler")
       .def(py::init([](StateSpacePoissonModel *model, const Ptr<MvnModel> &slab,
@@ -650,7 +666,11 @@ PYBIND11_MODULE(_boom, boom) {
       .def("set_latent_data", [](StateSpaceLogitModel &m, const NpArray &value, const NpArray &precision, int chain) {
              m.set_latent_data(vector_from(value), vector_from(precision), chain);
            }, py::arg("value"), py::arg("precision"), py::arg("chain") = -1)
-      .def("impute_state", &StateSpaceLogitModel::impute_state);
+      .def("impute_state", &StateSpaceLogitModel::impute_state)
+      .def("simulate_forecast", [](StateSpaceLogitModel &m, const NpArray &predictors, const py::object &trials) {
+             return forecast_to_numpy(m.simulate_forecast(matrix_from(predictors), optional_vector(trials)));
+           }, py::arg("predictors"), py::arg("trials") = py::none(),
+           "one predictive draw of the next success counts per chain (chains x horizon); trials: default ones");
   py::class_<StateSpaceLogitPosteriorSampler, PosteriorSampler, Ptr<StateSpaceLogitPosteriorSampler>>(
       boom, "StateSpaceLogitPosteriorSampler")
       .def(py::init([](StateSpaceLogitModel *model, const Ptr<MvnModel> &slab,

@@ -735,10 +735,15 @@ int ba_ss_impute_state(ba_engine *e);
  *                            AugmentedStudentRegressionData::set_weight: "Weights must be finite and
  *                            non-negative."; a missing step's weight is not read).  After _set_weights
  *                            the next sweep starts with an impute_state on the new weights.
+ *   ba_ss_student_forecast   simulate_forecast (StateSpaceStudentRegressionModel.cpp:205-251): newX and
+ *                            out as in ba_ss_forecast; step i is rstudent_mt(Z'state + x_i'beta, sigma,
+ *                            nu) after the state errors of the step, the reference's draws on the
+ *                            chain's forecast stream (id 5), which goes on from call to call
  * Also served for this kind: ba_set_state / ba_get_state(s), ba_enable_draws with ba_get_draws and
  * ba_student_get_nu_draws, ba_student_get_nu / _get_margin / _allow_model_selection,
  * ba_ss_get_state_draw, ba_ss_get_state_model, ba_ss_get_ar, ba_ss_state_dimension.  Not served:
- * ba_ss_forecast, ba_ss_draw_next, ba_ss_sweep, ba_ss_impute_state (refused).
+ * ba_ss_forecast (use ba_ss_student_forecast), ba_ss_draw_next, ba_ss_sweep, ba_ss_impute_state
+ * (refused).
  * RNG: stream 3 indicators / beta; stream 15 from position r * 4096 for sigma^2, then nu, of round
  * r; stream 31 from position (s T + t) * 256 for the weight of step t in the sampler's s-th
  * weight imputation (the first draw() makes two); stream 2 the state; the state models' streams
@@ -749,6 +754,7 @@ int ba_ss_student_sweep(ba_engine *e, int32_t nsweeps);
 int ba_ss_student_get_weights(ba_engine *e, int64_t chain, double *w);
 int ba_ss_student_set_weights(ba_engine *e, int64_t chain, const double *w);
 int ba_ss_student_impute_state(ba_engine *e);
+int ba_ss_student_forecast(ba_engine *e, int32_t horizon, const double *newX, double *out);
 
 /* ---- bsts(family = "poisson"): StateSpacePoissonModel with StateSpacePoissonPosteriorSampler
  * (Models/StateSpace/StateSpacePoissonModel.cpp, PosteriorSamplers/
@@ -784,10 +790,18 @@ int ba_ss_student_impute_state(ba_engine *e);
  *                            observed step is refused too -- the reference's variance is -infinity
  *                            there).  After _set_latent the next sweep starts with an impute_state on
  *                            the new data.
+ *   ba_ss_poisson_forecast   simulate_forecast (StateSpacePoissonModel.cpp:215-242): newX and out as in
+ *                            ba_ss_forecast, exposure `horizon` non-negative finite numbers (NULL:
+ *                            ones); step i is a Poisson(exposure_i exp(Z'state + x_i'beta)) count after
+ *                            the state errors of the step, on the chain's forecast stream (id 5), which
+ *                            goes on from call to call.  The state errors are the reference's draws; the
+ *                            count is an exact Poisson draw (inversion below a mean of 10, Hoermann's
+ *                            PTRS above: device_rng_counts.h), not the number Bmath's rpois makes of the
+ *                            stream.  A cell whose mean overflows is NaN
  * Also served for this kind: ba_set_state / ba_get_state(s), ba_enable_draws with ba_get_draws, the
  * summaries, ba_ss_get_state_draw, ba_ss_get_state_model, ba_ss_get_ar, ba_ss_state_dimension,
- * ba_set_slot_limit.  Not served: ba_ss_forecast, ba_ss_draw_next, ba_ss_sweep, ba_ss_impute_state,
- * ba_poisson_sweep, ba_ss_student_* (refused).
+ * ba_set_slot_limit.  Not served: ba_ss_forecast (use ba_ss_poisson_forecast), ba_ss_draw_next,
+ * ba_ss_sweep, ba_ss_impute_state, ba_poisson_sweep, ba_ss_student_* (refused).
  * RNG: stream 3 indicators / beta; stream 11 from position (s T + t) * 256 for step t in the
  * sampler's s-th imputation (the first draw() makes two: round r of a fresh sampler imputes with
  * s = r + 1); stream 2 the state; the state models' streams as on the Gaussian path. */
@@ -797,6 +811,8 @@ int ba_ss_poisson_sweep(ba_engine *e, int32_t nsweeps);
 int ba_ss_poisson_impute_state(ba_engine *e);
 int ba_ss_poisson_get_latent(ba_engine *e, int64_t chain, double *value, double *precision);
 int ba_ss_poisson_set_latent(ba_engine *e, int64_t chain, const double *value, const double *precision);
+int ba_ss_poisson_forecast(ba_engine *e, int32_t horizon, const double *newX, const double *exposure,
+                           double *out);
 
 /* ---- bsts(family = "logit"): StateSpaceLogitModel with StateSpaceLogitPosteriorSampler
  * (Models/StateSpace/StateSpaceLogitModel.cpp, PosteriorSamplers/
@@ -835,10 +851,20 @@ int ba_ss_poisson_set_latent(ba_engine *e, int64_t chain, const double *value, c
  *                            "precision must be non-negative."; a zero or non-finite precision at an
  *                            observed step is refused too).  After _set_latent the next sweep starts
  *                            with an impute_state on the new data.
+ *   ba_ss_logit_forecast     simulate_forecast (StateSpaceLogitModel.cpp:221-248): newX and out as in
+ *                            ba_ss_forecast, trials `horizon` non-negative finite numbers, rounded to
+ *                            the nearest integer as the reference's lround does (NULL: ones); step i is
+ *                            a Binomial(trials_i, plogis(Z'state + x_i'beta)) count after the state
+ *                            errors of the step, on the chain's forecast stream (id 5), which goes on
+ *                            from call to call.  The state errors are the reference's draws; the count
+ *                            is an exact binomial draw (inversion below n min(p, 1 - p) = 10, Hoermann's
+ *                            BTRS above: device_rng_counts.h), not the number Bmath's rbinom makes of
+ *                            the stream
  * Also served for this kind: ba_set_state / ba_get_state(s), ba_enable_draws with ba_get_draws, the
  * summaries, ba_ss_get_state_draw, ba_ss_get_state_model, ba_ss_get_ar, ba_ss_state_dimension,
- * ba_set_slot_limit.  Not served: ba_ss_forecast, ba_ss_draw_next, ba_ss_sweep, ba_ss_impute_state,
- * ba_logit_sweep, ba_logit_set_imputer, ba_ss_student_*, ba_ss_poisson_* (refused).
+ * ba_set_slot_limit.  Not served: ba_ss_forecast (use ba_ss_logit_forecast), ba_ss_draw_next,
+ * ba_ss_sweep, ba_ss_impute_state, ba_logit_sweep, ba_logit_set_imputer, ba_ss_student_*,
+ * ba_ss_poisson_* (refused).
  * RNG: stream 3 indicators / beta; stream 9 from position (s T + t) * 256 for step t in the
  * sampler's s-th imputation (the first draw() makes two: round r of a fresh sampler imputes with
  * s = r + 1); stream 2 the state; the state models' streams as on the Gaussian path. */
@@ -848,13 +874,17 @@ int ba_ss_logit_sweep(ba_engine *e, int32_t nsweeps);
 int ba_ss_logit_impute_state(ba_engine *e);
 int ba_ss_logit_get_latent(ba_engine *e, int64_t chain, double *value, double *precision);
 int ba_ss_logit_set_latent(ba_engine *e, int64_t chain, const double *value, const double *precision);
+int ba_ss_logit_forecast(ba_engine *e, int32_t horizon, const double *newX, const double *trials,
+                         double *out);
 /* StateSpaceRegressionModel::simulate_forecast(rng, newX, final_state)
  * (StateSpaceRegressionModel.cpp:214-219, :256-278; what bsts' predict does for
  * every saved draw): one draw from the predictive distribution of the next
  * `horizon` observations for EVERY chain's current parameters and final state.
  * newX is horizon x p column-major (host); out is chains x horizon (host),
  * row-major.  Each call continues the chains' forecast streams.  Works for the
- * local level model and for the structural (trend + seasonal) one. */
+ * local level model and for every list of state models, with Gaussian observation
+ * noise.  The Student-t, Poisson and logit families are refused here: their forecasts
+ * are ba_ss_student_forecast, ba_ss_poisson_forecast and ba_ss_logit_forecast. */
 int ba_ss_forecast(ba_engine *e, int32_t horizon, const double *newX, double *out);
 /* state(): T doubles of one chain; level sigsq; level suf (n, sumsq) */
 int ba_ss_get_state(ba_engine *e, int64_t chain, double *state,

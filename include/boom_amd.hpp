@@ -1098,6 +1098,15 @@ class StateSpaceStudentRegressionModel : public StateSpaceRegressionModel {
     finalize_state();
     engine()->check(ba_ss_student_impute_state(engine()->get()));
   }
+  // simulate_forecast(rng, predictors, final_state) for EVERY chain's current draw: column c is
+  // chain c's draw of the next predictors.nrow() observations (the chains' forecast streams go on
+  // from call to call)
+  Matrix simulate_forecast(const Matrix &predictors) {
+    if (predictors.ncol() != xdim()) report_error("The forecast predictors do not match the model dimension.");
+    Matrix ans(predictors.nrow(), engine()->chains());
+    engine()->check(ba_ss_student_forecast(engine()->get(), predictors.nrow(), predictors.data(), ans.data()));
+    return ans;
+  }
 };
 // StateSpaceStudentPosteriorSampler(model, observation model sampler's priors): slab, spike,
 // siginv prior and nu prior as TRegressionSpikeSlabSampler takes them
@@ -1168,6 +1177,17 @@ class StateSpacePoissonModel : public StateSpaceRegressionModel {
     finalize_state();
     engine()->check(ba_ss_poisson_impute_state(engine()->get()));
   }
+  // simulate_forecast(rng, forecast_predictors, exposure, final_state) for EVERY chain's current
+  // draw: column c is chain c's draw of the next counts (an empty exposure: ones)
+  Matrix simulate_forecast(const Matrix &predictors, const Vector &exposure = Vector()) {
+    if (predictors.ncol() != xdim()) report_error("The forecast predictors do not match the model dimension.");
+    if (!exposure.empty() && (int)exposure.size() != predictors.nrow())
+      report_error("One exposure per forecast step is needed.");
+    Matrix ans(predictors.nrow(), engine()->chains());
+    engine()->check(ba_ss_poisson_forecast(engine()->get(), predictors.nrow(), predictors.data(),
+                                           exposure.empty() ? nullptr : exposure.data(), ans.data()));
+    return ans;
+  }
 };
 // StateSpacePoissonPosteriorSampler(model, observation model sampler's priors): slab and spike as
 // PoissonRegressionSpikeSlabSampler takes them
@@ -1232,6 +1252,17 @@ class StateSpaceLogitModel : public StateSpaceRegressionModel {
   void impute_state() {   // Base::impute_state with the current parameters and latent data
     finalize_state();
     engine()->check(ba_ss_logit_impute_state(engine()->get()));
+  }
+  // simulate_forecast(rng, forecast_predictors, trials, final_state) for EVERY chain's current
+  // draw: column c is chain c's draw of the next success counts (an empty trials: ones)
+  Matrix simulate_forecast(const Matrix &predictors, const Vector &trials = Vector()) {
+    if (predictors.ncol() != xdim()) report_error("The forecast predictors do not match the model dimension.");
+    if (!trials.empty() && (int)trials.size() != predictors.nrow())
+      report_error("One trial count per forecast step is needed.");
+    Matrix ans(predictors.nrow(), engine()->chains());
+    engine()->check(ba_ss_logit_forecast(engine()->get(), predictors.nrow(), predictors.data(),
+                                         trials.empty() ? nullptr : trials.data(), ans.data()));
+    return ans;
   }
 };
 // StateSpaceLogitPosteriorSampler(model, observation model sampler's priors): slab and spike as
