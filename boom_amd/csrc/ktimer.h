@@ -17,7 +17,7 @@ enum KernelClass {
   KT_SSVS_ADAPTIVE, // ssvs_adaptive_kernel
   KT_KALMAN,        // kalman_simsmooth_kernel
   KT_SSM,           // ssm_simsmooth_kernel
-  KT_XTE_GEMM,      // atb_mfma_kernel (X'e of every chain)
+  KT_XTE_GEMM,      // xtwx_cols_kernel<false, XTE_KCHUNK> + plain_reduce_kernel (launch_xte_tiled: X'e of every chain)
   KT_PROBIT_IMPUTE, // probit_impute_kernel
   KT_LOGIT_IMPUTE,  // logit_impute_kernel
   KT_ROWS_GEMM,     // xtwx_cols_kernel<false> + plain_reduce_kernel (X'z, diagonal)
