@@ -179,6 +179,10 @@ SIGNATURES = {
     "ba_ss_lookahead_chains": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
     "ba_ss_draw_next": (C.c_int, [C.c_void_p]),
     "ba_ss_impute_state": (C.c_int, [C.c_void_p]),
+    "ba_ss_trend_get_weights": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp]),
+    "ba_ss_trend_set_weights": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp]),
+    "ba_ss_trend_get_weight_suf": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
+    "ba_ss_trend_draw_parameters": (C.c_int, [C.c_void_p]),
     "ba_ss_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
     "ba_ss_student_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
     "ba_ss_poisson_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp]),
@@ -826,7 +830,8 @@ class Engine:
     def ss_set_state_models(self, blocks):
         """a general list of state models, in the order they are added: dicts with kind
         (1 local level, 2 local linear trend, 3 seasonal, 4 autoregression, 5 static intercept,
-        6 trig), nseasons, duration, t0, lags, df, sigma_guess, sigma_upper_limit, initial_sigma
+        6 trig, 7 semilocal linear trend, 8 Student local linear trend: nu_priors = ((kind, a, b) of
+        level and slope), initial_nu = (level, slope)), nseasons, duration, t0, lags, df, sigma_guess, sigma_upper_limit, initial_sigma
         (one entry per variance parameter; none for kind 5), initial_phi, rotations (kind 6: the
         (cos, sin) pairs of the transition matrix), a0, P0 (tests/cases.py: general_spec)"""
         self._check(self.lib.ba_ss_clear_state_models(self._h))
@@ -844,6 +849,9 @@ class Engine:
                 ip[0], ip[1] = int(b.get("force_stationary", 1)), int(b.get("force_positive", 0))
             arrs = [np.ascontiguousarray(b[k], dtype=np.float64) for k in
                     ("df", "sigma_guess", "sigma_upper_limit", "initial_sigma")]
+            if kind == 8 and "nu_priors" in b and "initial_nu" in b:   # (without them: the engine's "null argument")
+                b = dict(b, initial_phi=np.concatenate([np.ravel(np.asarray(b["nu_priors"], dtype=np.float64)),
+                                                        np.asarray(b["initial_nu"], dtype=np.float64)]))
             ph = np.ascontiguousarray(b["rotations"] if kind == 6 else
                                       (b["slope_priors"] if kind == 7 else b.get("initial_phi", np.zeros(0))),
                                       dtype=np.float64)
@@ -852,8 +860,8 @@ class Engine:
             self._check(self.lib.ba_ss_add_state_model(
                 self._h, kind, ip.ctypes.data_as(C.POINTER(C.c_int32)),
                 *[(_p(a) if a.size else None) for a in arrs],
-                _p(ph) if (kind in (4, 6, 7) and ph.size) else None, _p(a0), _p(p0)))
-            self._blocks.append(dict(kind=kind, nvar=2 if kind in (2, 7) else (0 if kind == 5 else 1),
+                _p(ph) if (kind in (4, 6, 7, 8) and ph.size) else None, _p(a0), _p(p0)))
+            self._blocks.append(dict(kind=kind, nvar=2 if kind in (2, 7, 8) else (0 if kind == 5 else 1),
                                      lags=int(ip[0]) if kind == 4 else 0))
         m, nb = C.c_int32(), C.c_int32()
         self._check(self.lib.ba_ss_state_dimension(self._h, C.byref(m), C.byref(nb)))
@@ -888,6 +896,13 @@ class Engine:
             out["phi"] = phi
             if suf:
                 out["ar1_suf"] = a1
+            return out
+        if b["kind"] == 8:
+            # a Student local linear trend: phi = (nu_level, nu_slope)
+            nu = np.zeros(2)
+            self._check(self.lib.ba_ss_get_state_model(self._h, chain, block, _p(var), _p(n) if suf else None,
+                                                       _p(ss) if suf else None, _p(nu), None, None, None, None))
+            out["nu"] = nu
             return out
         if not suf:
             phi = np.zeros(L) if L else None
@@ -938,6 +953,30 @@ class Engine:
 
     def ss_impute_state(self):
         self._check(self.lib.ba_ss_impute_state(self._h))
+        self.sync()
+
+    def ss_trend_get_weights(self, chain):
+        """the Student local linear trend's weights of one chain: (level, slope), T each"""
+        lw, sw = np.zeros(self.T), np.zeros(self.T)
+        self._check(self.lib.ba_ss_trend_get_weights(self._h, chain, _p(lw), _p(sw)))
+        return lw, sw
+
+    def ss_trend_set_weights(self, level_w, slope_w, chain=-1):
+        lw = np.ascontiguousarray(level_w, dtype=np.float64)
+        sw = np.ascontiguousarray(slope_w, dtype=np.float64)
+        if lw.shape != (self.T,) or sw.shape != (self.T,):
+            raise ValueError("the weights have T entries each")
+        self._check(self.lib.ba_ss_trend_set_weights(self._h, chain, _p(lw), _p(sw)))
+
+    def ss_trend_get_weight_suf(self, chain):
+        """(n, sum w, sum log w) of the level weights, then of the slope weights"""
+        out = np.zeros(6)
+        self._check(self.lib.ba_ss_trend_get_weight_suf(self._h, chain, _p(out)))
+        return out
+
+    def ss_trend_draw_parameters(self):
+        """the Student local linear trend's sample_posterior() alone, every chain"""
+        self._check(self.lib.ba_ss_trend_draw_parameters(self._h))
         self.sync()
 
     def ss_forecast(self, newX):

@@ -1043,7 +1043,8 @@ const char *ba_kernel_class_name(int32_t cls) {
       "xtwx_cols_kernel<false>+plain_reduce_kernel", "xtwx_cols_kernel<true>+xtwx_cols_reduce_kernel",
       "xtx_mfma_kernel+plane_sum_kernel+col_reduce_kernel", "poisson_impute_kernel",
       "kalman_prepare_kernel", "ss_round_kernel", "student_impute_kernel", "student_sigma_nu_kernel",
-      "quantile_impute_kernel", "mlogit_impute_kernel", "student_ss_kernels", "poisson_ss_kernels", "logit_ss_kernels"};
+      "quantile_impute_kernel", "mlogit_impute_kernel", "student_ss_kernels", "poisson_ss_kernels", "logit_ss_kernels",
+      "student_trend_kernels"};
   return (cls >= 0 && cls < KT_CLASSES) ? names[cls] : "";
 }
 
@@ -1596,6 +1597,8 @@ int ba_seed(ba_engine *e, uint64_t seed) {
   e->lat.draws = 0;
   if (e->dpos_state.ptr) HIP_TRY(hipMemsetAsync(e->dpos_state.ptr, 0, C * 8, s));
   if (e->dpos_forecast.ptr) HIP_TRY(hipMemsetAsync(e->dpos_forecast.ptr, 0, C * 8, s));
+  if (e->dslt_pos.ptr) HIP_TRY(hipMemsetAsync(e->dslt_pos.ptr, 0, C * 8, s));
+  if (e->dslt_count.ptr) HIP_TRY(hipMemsetAsync(e->dslt_count.ptr, 0, C * 8, s));
   HIP_TRY(hipStreamSynchronize(s));
   return BA_OK;
 }

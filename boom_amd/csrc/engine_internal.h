@@ -55,6 +55,9 @@ int launch_suf_from_xy(hipStream_t stream, int64_t n, int p, const double *X,
 hipError_t launch_ssm_simsmooth(hipStream_t stream, const SsParams &P, int draw_variances);
 hipError_t launch_ssm_forecast(hipStream_t stream, const SsParams &P, int horizon, const double *newX,
                                uint64_t *pos_forecast, double *out);
+// slt_kernel.hip: the Student local linear trend's sampler (before a state draw) and its observe_state (after it)
+hipError_t launch_slt_params(hipStream_t stream, const SsParams &P, const SltParams &U);
+hipError_t launch_slt_weights(hipStream_t stream, const SsParams &P, const SltParams &U);
 // ss_family_forecast_kernel.hip: family = SS_FORECAST_*; scale = the horizon's exposures / rounded trial
 // counts (Poisson, logit), nu = every chain's degrees of freedom (Student-t); the other is not read
 hipError_t launch_ss_family_forecast(hipStream_t stream, const SsParams &P, int family, int horizon,
@@ -429,6 +432,13 @@ struct ba_engine {
   DevBuf<double> dssm_sigsq, dssm_n, dssm_ss, dssm_work;   // chains x SSG_MAX_VAR (sigsq, n, ss)
   DevBuf<double> dar_phi, dar_suf;                         // chains x SSG_MAX_AR x (AR_MAX | AR_SUF_STRIDE)
   DevBuf<uint64_t> dpos_var;                               // chains x SSG_MAX_VAR
+  // StudentLocalLinearTrendStateModel (ssg.student_block; slt_kernel.hip): the nu priors (kind, a, b)
+  // and initial values of level and slope; per chain the weights and the kept residuals (2 x T each),
+  // nu (2), the weights' GammaSuf (6), the sampler's stream position and the state draws observed
+  int slt_nu_kind[2] = {STUDENT_NU_UNIFORM, STUDENT_NU_UNIFORM};
+  double slt_nu_a[2] = {1.0, 1.0}, slt_nu_b[2] = {500.0, 500.0}, slt_initial_nu[2] = {10.0, 10.0};
+  DevBuf<double> dslt_w, dslt_res, dslt_nu, dslt_wsuf;
+  DevBuf<uint64_t> dslt_pos, dslt_count;
   // ---- look-ahead on the bsts path (ba_ss_set_lookahead / ba_ss_draw_next): a batch of
   // `len` sweep rounds per enqueue, every round's draw recorded on the device -- gamma,
   // beta, sigma^2, the state models' variances and coefficients for EVERY chain, the

@@ -18,6 +18,7 @@ static int64_t ssm_work_stride(const ba_engine &e) {
 static void ssg_template_shape(const SsgSpec &q, int32_t *trend, int32_t *nseasons, int32_t *ar_lags) {
   *trend = *nseasons = *ar_lags = 0;
   if (q.nblocks < 1 || q.nblocks > 3 || q.m > 16) return;
+  if (q.student_block) return;   // (a Student local linear trend: the general kernel's QT instances)
   for (int i = 0; i < q.nblocks; ++i)
     if (q.blk[i].nvar == 0) return;   // (a static intercept: the general kernel)
   int b = 0, tr = 0, ns = 0, lags = 0;
@@ -116,12 +117,44 @@ static void fill_ss_params(ba_engine *e, SsParams &S) {
     S.ssm.ar_suf = e->dar_suf.ptr;
     S.ssm.work = e->dssm_work.ptr;
     S.ssm.work_stride = ssm_work_stride(*e);
+    if (e->ssg.student_block) {
+      S.qw = e->dslt_w.ptr;
+      S.qw_stride = 2 * (int64_t)e->T;
+    }
+  }
+}
+
+static const char *const SLT_FAMILY_REFUSAL =
+    "the Student local linear trend is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)";
+
+static void fill_slt_params(ba_engine *e, SltParams &U) {
+  U.w = e->dslt_w.ptr;
+  U.res = e->dslt_res.ptr;
+  U.nu = e->dslt_nu.ptr;
+  U.wsuf = e->dslt_wsuf.ptr;
+  U.pos = e->dslt_pos.ptr;
+  U.count = e->dslt_count.ptr;
+  for (int c = 0; c < 2; ++c) {
+    U.nu_kind[c] = e->slt_nu_kind[c];
+    U.nu_a[c] = e->slt_nu_a[c];
+    U.nu_b[c] = e->slt_nu_b[c];
   }
 }
 
 // the state half of a state-space sweep: the structural kernel when a trend /
 // seasonal specification is set, the local-level kernel otherwise
 static hipError_t launch_state_kernel(ba_engine *e, const SsParams &S, int draw) {
+  if (e->ssm_set && e->ssg.student_block) {
+    // a Student local linear trend: its sampler with the other state models' (they are drawn at the
+    // head of the state kernel, every one from its own stream), and observe_state -- the new weights
+    // and the block's statistics -- once the state draw is there
+    SltParams U;
+    fill_slt_params(e, U);
+    hipError_t err = draw ? launch_slt_params(e->stream, S, U) : hipSuccess;
+    if (err == hipSuccess) err = launch_ssm_simsmooth(e->stream, S, draw);
+    if (err == hipSuccess) err = launch_slt_weights(e->stream, S, U);
+    return err;
+  }
   return e->ssm_set ? launch_ssm_simsmooth(e->stream, S, draw)
                     : launch_kalman_simsmooth(e->stream, S, draw);
 }
@@ -502,6 +535,7 @@ static int ss_prepare(ba_engine *e, DataKind kind = DATA_STATE_SPACE) {
   if (rc) return rc;
   if (!e->ss_level_set && !e->ssm_set)
     return fail(BA_E_STATE, "call ba_ss_set_local_level or ba_ss_set_structural first");
+  if (kind != DATA_STATE_SPACE && e->ssm_set && e->ssg.student_block) return fail(BA_E_STATE, SLT_FAMILY_REFUSAL);
   rc = upload_shared(e);
   if (rc) return rc;
   rc = alloc_chain_state(e);
@@ -566,6 +600,24 @@ static int ss_prepare(ba_engine *e, DataKind kind = DATA_STATE_SPACE) {
             for (int i = 0; i < AR_MAX; ++i) ph[(c * SSG_MAX_AR + a) * AR_MAX + i] = e->ssg_initial_phi[a][i];
         HIP_TRY(hipMemcpy(e->dar_phi.ptr, ph.data(), ph.size() * 8, hipMemcpyHostToDevice));
         HIP_TRY(hipMemsetAsync(e->dar_suf.ptr, 0, C * SSG_MAX_AR * AR_SUF_STRIDE * 8, s));
+      }
+      if (e->ssg.student_block) {
+        // a new StudentLocalLinearTrendStateModel: weights 1, no residuals, empty statistics
+        const size_t TT = (size_t)e->T;
+        HIP_TRY(e->dslt_w.resize(C * 2 * TT));
+        HIP_TRY(e->dslt_res.resize(C * 2 * TT));
+        HIP_TRY(e->dslt_nu.resize(C * 2));
+        HIP_TRY(e->dslt_wsuf.resize(C * 6));
+        HIP_TRY(e->dslt_pos.resize(C));
+        HIP_TRY(e->dslt_count.resize(C));
+        std::vector<double> one(C * 2 * TT, 1.0), nu0(C * 2);
+        for (size_t c = 0; c < C; ++c) { nu0[2 * c] = e->slt_initial_nu[0]; nu0[2 * c + 1] = e->slt_initial_nu[1]; }
+        HIP_TRY(hipMemcpy(e->dslt_w.ptr, one.data(), one.size() * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->dslt_nu.ptr, nu0.data(), nu0.size() * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(e->dslt_res.ptr, 0, C * 2 * TT * 8, s));
+        HIP_TRY(hipMemsetAsync(e->dslt_wsuf.ptr, 0, C * 6 * 8, s));
+        HIP_TRY(hipMemsetAsync(e->dslt_pos.ptr, 0, C * 8, s));
+        HIP_TRY(hipMemsetAsync(e->dslt_count.ptr, 0, C * 8, s));
       }
     }
     HIP_TRY(hipStreamSynchronize(s));  // (the host vectors above go out of scope)
@@ -708,6 +760,7 @@ static int ssg_stream_id(const SsgSpec &q, int kind, int v) {
   for (int i = 0; i < q.nblocks; ++i) {
     const int k = q.blk[i].kind;
     if (q.blk[i].nvar == 0) continue;   // (a static intercept has no sampler: it is in no family)
+    if (i == q.student_block - 1) continue;   // (a Student trend's sampler reads SLT_PARAM_STREAM: in no family either)
     if (family(k) == fam) ++occ;
   }
   const int base = kind == SSG_SEASONAL ? 7 : (kind == SSG_AR ? 12 : (kind == SSG_TRIG ? 13 : (v == 0 ? 1 : 6)));
@@ -724,6 +777,7 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
       !initial_state_mean || !initial_state_variance)
     return fail(BA_E_INVALID, "null argument");
   if (q.nblocks >= SSG_MAX_BLOCKS) return fail(BA_E_INVALID, "more than 8 state models");
+  const bool is_student = kind == SSG_STUDENT_TREND;
   SsgBlock k{};
   k.kind = kind;
   k.nvar = 1;
@@ -778,6 +832,27 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
       k.sl_truncate = iparams[0] != 0;
       k.sl_positive = iparams[1] != 0;
       break;
+    case SSG_STUDENT_TREND: {
+      // StudentLocalLinearTrendStateModel(sigma_level, nu_level, sigma_slope, nu_slope): initial_phi =
+      // {nu_level prior kind, a, b, nu_slope prior kind, a, b, initial nu_level, initial nu_slope}; on
+      // the device a local linear trend block (SsgSpec::student_block names it) with weights
+      if (!initial_phi) return fail(BA_E_INVALID, "null argument");
+      if (q.student_block) return fail(BA_E_INVALID, "at most one Student local linear trend per list of state models");
+      if (e->data_kind == DATA_SS_STUDENT || e->data_kind == DATA_SS_POISSON || e->data_kind == DATA_SS_LOGIT)
+        return fail(BA_E_STATE, SLT_FAMILY_REFUSAL);
+      for (int c = 0; c < 2; ++c) {
+        const double pk = initial_phi[3 * c], a = initial_phi[3 * c + 1], b = initial_phi[3 * c + 2], nu = initial_phi[6 + c];
+        if (pk != STUDENT_NU_UNIFORM && pk != STUDENT_NU_GAMMA) return fail(BA_E_INVALID, "nu prior kind must be 0 (uniform) or 1 (gamma)");
+        if (pk == STUDENT_NU_UNIFORM ? !(a < b) || !std::isfinite(a) || !std::isfinite(b) : !(a > 0) || !(b > 0))
+          return fail(BA_E_INVALID, "nu prior: uniform needs a < b, gamma needs positive shape and rate");
+        const bool ok = std::isfinite(nu) && nu > 0 && (pk != STUDENT_NU_UNIFORM || (nu >= a && nu <= b));
+        if (!ok) return fail(BA_E_INVALID, "the initial nu must be positive and have positive prior density");
+      }
+      k.kind = SSG_LOCAL_LINEAR_TREND;
+      k.dim = 2;
+      k.nvar = 2;
+      break;
+    }
     case SSG_AR:
       if (!iparams) return fail(BA_E_INVALID, "null argument");
       if (iparams[0] < 1) return fail(BA_E_INVALID, "lags must be positive");
@@ -788,14 +863,14 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
       k.ar_index = q.nar;
       break;
     default:
-      return fail(BA_E_INVALID, "state model kind must be 1 (local level), 2 (local linear trend), 3 (seasonal), 4 (autoregression), 5 (static intercept), 6 (trig) or 7 (semilocal linear trend)");
+      return fail(BA_E_INVALID, "state model kind must be 1 (local level), 2 (local linear trend), 3 (seasonal), 4 (autoregression), 5 (static intercept), 6 (trig), 7 (semilocal linear trend) or 8 (Student local linear trend)");
   }
   const int nslot = is_static ? 1 : k.nvar;   // variance slots the block takes
   if (q.m + k.dim > SSG_MAX_STATE) return fail(BA_E_INVALID, "state dimension exceeds 64");
   if (q.nvar + nslot > SSG_MAX_VAR) return fail(BA_E_INVALID, "more than 16 variance parameters");
   for (int v = 0; v < k.nvar; ++v) {
     if (var_sigma_upper_limit[v] < 0) return fail(BA_E_INVALID, "sigma_max must be non-negative.");
-    if ((kind == SSG_AR || kind == SSG_SEMILOCAL) && !(var_initial_sigma[v] > 0))
+    if ((kind == SSG_AR || kind == SSG_SEMILOCAL || is_student) && !(var_initial_sigma[v] > 0))
       return fail(BA_E_INVALID, "initial sigma must be positive");
   }
   for (int i = 0; i < k.dim; ++i) {
@@ -817,7 +892,7 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
     q.prior_ss[vi] = 2 * (var_df[v] * var_sigma_guess[v] * var_sigma_guess[v] / 2.0);
     q.sigma_max[vi] = var_sigma_upper_limit[v];
     e->ssg_initial_sigsq[vi] = var_initial_sigma[v] * var_initial_sigma[v];
-    k.sid[v] = ssg_stream_id(q, kind, v);
+    k.sid[v] = is_student ? (int)SLT_PARAM_STREAM : ssg_stream_id(q, kind, v);
   }
   if (is_static) {
     // (the slot: variance 0, a sampler that is never run)
@@ -846,6 +921,15 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
     q.a0[k.first + 2] = initial_phi[4];
     q.P0[k.first + 2] = 0.0;
     q.nar += 1;
+  }
+  if (is_student) {
+    q.student_block = q.nblocks + 1;
+    for (int c = 0; c < 2; ++c) {
+      e->slt_nu_kind[c] = (int)initial_phi[3 * c];
+      e->slt_nu_a[c] = initial_phi[3 * c + 1];
+      e->slt_nu_b[c] = initial_phi[3 * c + 2];
+      e->slt_initial_nu[c] = initial_phi[6 + c];
+    }
   }
   q.blk[q.nblocks] = k;
   q.nblocks += 1;
@@ -976,7 +1060,8 @@ int ba_ss_get_state_model(ba_engine *e, int64_t chain, int32_t block, double *va
   const SsgBlock &k = e->ssg.blk[block];
   const bool is_sl = k.kind == SSG_SEMILOCAL;
   const bool is_ar = k.kind == SSG_AR || is_sl;   // (both keep coefficients and statistics in an autoregression slot)
-  if (!is_ar && (phi || ar_xtx || ar_xty || ar_yty || ar_n))
+  const bool is_student = block == e->ssg.student_block - 1;   // (phi: nu_level, nu_slope)
+  if (!is_ar && ((phi && !is_student) || ar_xtx || ar_xty || ar_yty || ar_n))
     return fail(BA_E_INVALID, "not an autoregression state model");
   if (is_sl && (ar_xty || ar_yty))
     return fail(BA_E_INVALID, "a semilocal linear trend's Ar1Suf comes back through ar_xtx (six doubles) and ar_n");
@@ -1010,7 +1095,10 @@ int ba_ss_get_state_model(ba_engine *e, int64_t chain, int32_t block, double *va
     HIP_TRY(hipMemcpyAsync(hsuf, e->dar_suf.ptr + slot * AR_SUF_STRIDE, AR_SUF_STRIDE * 8, hipMemcpyDeviceToHost,
                            e->stream));
   }
+  if (is_student && phi)
+    HIP_TRY(hipMemcpyAsync(hphi, e->dslt_nu.ptr + (size_t)chain * 2, 2 * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
+  if (is_student && phi) { phi[0] = hphi[0]; phi[1] = hphi[1]; }
   for (int v = 0; v < k.nvar; ++v) {
     if (variances) variances[v] = hv[v];
     if (suf_n) suf_n[v] = hv[2 + v];
@@ -1134,6 +1222,72 @@ int ba_ss_impute_state(ba_engine *e) {
   fill_ss_params(e, S);
   HIP_TRY(launch_state_kernel(e, S, 0));
   e->ss_initialized = true;
+  return BA_OK;
+}
+
+// ---- the Student local linear trend's own state (slt_kernel.hip)
+static int slt_ready(ba_engine *e) {
+  if (e->data_kind != DATA_STATE_SPACE) return fail(BA_E_STATE, set_data_first(DATA_STATE_SPACE));
+  if (!e->ssm_set || !e->ssg.student_block)
+    return fail(BA_E_STATE, "the list of state models holds no Student local linear trend");
+  return ss_prepare(e);
+}
+
+int ba_ss_trend_get_weights(ba_engine *e, int64_t chain, double *level_w, double *slope_w) {
+  ENGINE_PROLOGUE(e);
+  if (!level_w || !slope_w) return fail(BA_E_INVALID, "null argument");
+  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  int rc = slt_ready(e);
+  if (rc) return rc;
+  const size_t T = (size_t)e->T;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(level_w, e->dslt_w.ptr + (size_t)chain * 2 * T, T * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(slope_w, e->dslt_w.ptr + (size_t)chain * 2 * T + T, T * 8, hipMemcpyDeviceToHost));
+  return BA_OK;
+}
+
+int ba_ss_trend_set_weights(ba_engine *e, int64_t chain, const double *level_w, const double *slope_w) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!level_w || !slope_w) return fail(BA_E_INVALID, "null argument");
+  if (chain < -1 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  int rc = slt_ready(e);
+  if (rc) return rc;
+  const size_t T = (size_t)e->T, C = (size_t)e->cfg.chains;
+  for (size_t t = 0; t < T; ++t)
+    if (!(level_w[t] > 0.0) || !std::isfinite(level_w[t]) || !(slope_w[t] > 0.0) || !std::isfinite(slope_w[t]))
+      return fail(BA_E_INVALID, "Weights must be finite and positive.");
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (size_t c = chain < 0 ? 0 : (size_t)chain; c < (chain < 0 ? C : (size_t)chain + 1); ++c) {
+    HIP_TRY(hipMemcpy(e->dslt_w.ptr + c * 2 * T, level_w, T * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->dslt_w.ptr + c * 2 * T + T, slope_w, T * 8, hipMemcpyHostToDevice));
+  }
+  return BA_OK;
+}
+
+// the GammaSuf of the weights the last observe_state drew: (n, sum, sum of logs) of the level, then of the slope
+int ba_ss_trend_get_weight_suf(ba_engine *e, int64_t chain, double *out) {
+  ENGINE_PROLOGUE(e);
+  if (!out) return fail(BA_E_INVALID, "null argument");
+  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  int rc = slt_ready(e);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(out, e->dslt_wsuf.ptr + (size_t)chain * 6, 6 * 8, hipMemcpyDeviceToHost));
+  return BA_OK;
+}
+
+// the block's sample_posterior() alone: sigma_level^2, nu_level, sigma_slope^2, nu_slope
+int ba_ss_trend_draw_parameters(ba_engine *e) {
+  ENGINE_PROLOGUE(e);
+  e->table_ok = false;
+  int rc = slt_ready(e);
+  if (rc) return rc;
+  SsParams S;
+  fill_ss_params(e, S);
+  SltParams U;
+  fill_slt_params(e, U);
+  HIP_TRY(launch_slt_params(e->stream, S, U));
   return BA_OK;
 }
 
@@ -1325,6 +1479,8 @@ int ba_ss_sweep(ba_engine *e, int32_t nsweeps) {
 int ba_ss_set_lookahead(ba_engine *e, int32_t lookahead) {
   ENGINE_PROLOGUE(e);
   if (lookahead < 1) return fail(BA_E_INVALID, "lookahead must be at least 1");
+  if (lookahead > 1 && e->ssm_set && e->ssg.student_block)
+    return fail(BA_E_STATE, "the look-ahead does not carry a Student local linear trend's weights: use a look-ahead of 1");
   MUTATE(e);
   {
     // the record: two halves x chains x rounds x (gamma + beta [+ variances, coefficients]);
@@ -1364,6 +1520,8 @@ int ba_ss_draw_next(ba_engine *e) {
     if (rcj) return rcj;
   }
   ba_engine::SsLa &A = e->ssla;
+  if (A.len > 1 && e->ssm_set && e->ssg.student_block)
+    return fail(BA_E_STATE, "the look-ahead does not carry a Student local linear trend's weights: use a look-ahead of 1");
   if (A.len <= 1) return ss_sweep_impl(e, 1, -1);
   if (A.cur <= 1) {
     // (every draw of late was followed by something the record could not serve: one round
@@ -1421,6 +1579,8 @@ int ba_ss_forecast(ba_engine *e, int32_t horizon, const double *newX, double *ou
     return fail(BA_E_STATE, "forecasts with Poisson observation noise are not implemented");
   if (e->data_kind == DATA_SS_LOGIT)
     return fail(BA_E_STATE, "forecasts with binomial observation noise are not implemented");
+  if (e->ssm_set && e->ssg.student_block)
+    return fail(BA_E_STATE, "forecasts with a Student local linear trend are not implemented");
   if (!newX || !out || horizon <= 0) return fail(BA_E_INVALID, "bad argument");
   if (e->data_kind != DATA_STATE_SPACE || e->dss_scratch.count == 0 || !e->ss_initialized)
     return fail(BA_E_STATE, "no state draw yet: run ba_ss_sweep or ba_ss_impute_state first");

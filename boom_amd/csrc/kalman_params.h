@@ -24,7 +24,15 @@ enum { SSG_LOCAL_LEVEL = 1, SSG_LOCAL_LINEAR_TREND = 2, SSG_SEASONAL = 3, SSG_AR
        // SemilocalLinearTrendStateModel: (level, slope, the slope's long-run mean mu); T = [[1, 1, 0],
        // [0, phi, 1 - phi], [0, 0, 1]]; its (phi, mu) and the slope's Ar1Suf take one of the chain's
        // autoregression slots (ar_phi[0 .. 1]; ar_suf[0 .. 5] = sumsq, sum, cross, n, first, last)
-       SSG_SEMILOCAL = 7 };
+       SSG_SEMILOCAL = 7,
+       // StudentLocalLinearTrendStateModel (the C-ABI's number): a local linear trend whose two state
+       // errors have the per-step variances sigma^2 / w_t.  Stored as SSG_LOCAL_LINEAR_TREND --
+       // SsgSpec::student_block says which block it is -- and served by the QT instances of the
+       // general kernel and the two kernels of slt_kernel.hip
+       SSG_STUDENT_TREND = 8 };
+// the Student trend's streams: its sampler's four draws (read in sequence) and the weights' slots
+enum : uint32_t { SLT_PARAM_STREAM = 160u, SLT_WEIGHT_STREAM = 161u };
+enum { SLT_WEIGHT_STRIDE = 256, SLT_BLOCK = 256 };
 // the observation families of ss_family_forecast_kernel.hip (launch_ss_family_forecast)
 enum { SS_FORECAST_STUDENT = 0, SS_FORECAST_POISSON = 1, SS_FORECAST_LOGIT = 2 };
 // a chain's ArModel sufficient statistics (per autoregression block): xtx (lags x lags at
@@ -47,7 +55,7 @@ struct SsgSpec {
   int32_t ld;          // leading dimension of the state variance in LDS (odd)
   int32_t bl;          // steps per block of the passes (64 for m <= 16, ... 16 for m <= 64)
   int32_t nerr;        // rows of the state that carry state error (one per variance slot; a trig block: every component)
-  int32_t pad;
+  int32_t student_block;   // 1 + the index of the Student local linear trend block (0: the list has none)
   SsgBlock blk[SSG_MAX_BLOCKS];
   double prior_df[SSG_MAX_VAR], prior_ss[SSG_MAX_VAR], sigma_max[SSG_MAX_VAR];
   double a0[SSG_MAX_STATE], P0[SSG_MAX_STATE];   // initial state mean, variance (diagonal)
@@ -143,6 +151,23 @@ struct SsParams {
   // value, y_stride doubles apart (0: the one series shared by all chains).  Read by the HT
   // instances only.
   int64_t y_stride;
+  // the Student local linear trend (SsgSpec::student_block): every chain's weights, qw_stride doubles
+  // apart -- the level's T, then the slope's T; entry t scales the state error of the step t -> t + 1
+  // (nullptr: no such block).  Read by the QT instances only.
+  const double *qw;
+  int64_t qw_stride;
+};
+
+// The Student local linear trend's own chain state (slt_kernel.hip).  c = 0 the level, 1 the slope.
+struct SltParams {
+  double *w;          // chains x 2 x T: the weights (SsParams::qw)
+  double *res;        // chains x 2 x T: the residuals of the last state draw, entries 0 .. T - 2
+  double *nu;         // chains x 2
+  double *wsuf;       // chains x 6: the GammaSuf of the new weights (n, sum, sum of logs), level then slope
+  uint64_t *pos;      // chains: position in SLT_PARAM_STREAM
+  uint64_t *count;    // chains: state draws observed so far (the s of the weights' slots)
+  int32_t nu_kind[2]; // the nu priors: STUDENT_NU_UNIFORM (a, b) / STUDENT_NU_GAMMA (a, b)
+  double nu_a[2], nu_b[2];
 };
 
 // The round kernel (ss_round_kernel.hip): every chain's workgroup loops over the rounds of a

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_rng.h"
+
 namespace boom_amd {
 
 // how many uniforms a slot of an imputer's substream hands out before the draw goes on in the
@@ -50,6 +52,61 @@ __device__ __forceinline__ int included_coefficients(const uint8_t *gamma, const
     __syncthreads();
   }
   return base;
+}
+
+// sum over the workgroup's 256 threads, in a fixed order; every thread gets the result
+// (s_red: four doubles of LDS)
+__device__ __forceinline__ double stu_block_sum(double v, double *s_red) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();   // (s_red may still be read from the previous call)
+  if (lane == 0) s_red[wave] = v;
+  __syncthreads();
+  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+}
+
+// ScalarSliceSampler::draw (Samplers/ScalarSliceSampler.cpp:75-253) for a target bounded below at 0:
+// find_limits -> find_upper_limit from x + dx, then draw / contract.  S.logf(x) is the log density
+// (every thread of the workgroup calls it: it may reduce over the workgroup), S.note(a, b) is told
+// every pair the sampler compares.  unimodal: the sampler's switch -- true doubles the upper limit
+// only while it is inside the slice, false adds the random doublings (a uniform each).  x: the
+// current value; dx: the suggested width, in and out; out: the draw.  Returns 0, or 1 where the
+// reference reports an error.  Every thread reads the same numbers from its own copy of rng.
+template <class Target, class R>
+__device__ __forceinline__ int slice_draw_lower0(Target &S, R &rng, const bool unimodal, const double x, double &dx,
+                                                 double &out) {
+  int err = 0;
+  const double logp_slice = S.logf(x) - d_rexp(rng, 1.0);
+  if (!isfinite(logp_slice)) err = 1;                        // check_finite
+  double lo = 0.0, hi = 0.0;
+  if (!err) {
+    hi = x + dx;
+    double logphi = S.logf(hi);
+    S.note(logphi, logp_slice);
+    int doublings = 0;
+    while (logphi >= logp_slice || (!unimodal && d_runif(rng, 0.0, 1.0) > .5)) {
+      hi = x + 2 * (hi - x);                                   // double_hi
+      if (!isfinite(hi)) { err = 1; break; }
+      logphi = S.logf(hi);
+      S.note(logphi, logp_slice);
+      if (++doublings > 100) { err = 1; break; }
+    }
+    if (!err && (!isfinite(hi) || isnan(logphi))) err = 1;   // check_upper_limit
+  }
+  if (!err) {
+    int tries = 0;
+    for (;;) {
+      const double cand = d_runif(rng, lo, hi);
+      const double lp = S.logf(cand);
+      S.note(lp, logp_slice);
+      if (!(lp < logp_slice)) { out = cand; break; }
+      if (cand > x) hi = cand; else lo = cand;                 // contract
+      dx = hi - lo;
+      if (++tries > 100) { err = 1; break; }
+    }
+  }
+  return err;
 }
 
 }  // namespace boom_amd

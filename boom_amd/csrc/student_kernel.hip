@@ -39,21 +39,6 @@
 
 namespace boom_amd {
 
-namespace {
-
-// sum over the workgroup's 256 threads, in a fixed order; every thread gets the result
-__device__ __forceinline__ double stu_block_sum(double v, double *s_red) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();   // (s_red may still be read from the previous call)
-  if (lane == 0) s_red[wave] = v;
-  __syncthreads();
-  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-}
-
-}  // namespace
-
 // SS: the state space Student family (StateSpaceStudentPosteriorSampler::
 // impute_nonstate_latent_data, StateSpaceStudentPosteriorSampler.cpp:60-80): the residual is
 // y_t - x_t'beta - offset_t (the chain's Z_t'alpha_t), a missing step keeps weight 0 and reads no
@@ -228,37 +213,8 @@ __global__ __launch_bounds__(STUDENT_SN_BLOCK) void student_sigma_nu_kernel(Stud
   const double x = P.nu[chain];
   const double sigsq_in = P.sigsq[chain];   // (the sweep's: its summaries hold this one)
   double dx = P.dx[chain];
-  int err = 0;
   double nu = x;
-  const double logp_slice = S.logf(x) - d_rexp(rng, 1.0);
-  if (!isfinite(logp_slice)) err = 1;                        // check_finite
-  double lo = 0.0, hi = 0.0;
-  if (!err) {
-    hi = x + dx;
-    double logphi = S.logf(hi);
-    S.note(logphi, logp_slice);
-    int doublings = 0;
-    while (logphi >= logp_slice || d_runif(rng, 0.0, 1.0) > .5) {
-      hi = x + 2 * (hi - x);                                   // double_hi
-      if (!isfinite(hi)) { err = 1; break; }
-      logphi = S.logf(hi);
-      S.note(logphi, logp_slice);
-      if (++doublings > 100) { err = 1; break; }
-    }
-    if (!err && (!isfinite(hi) || isnan(logphi))) err = 1;   // check_upper_limit
-  }
-  if (!err) {
-    int tries = 0;
-    for (;;) {
-      const double cand = d_runif(rng, lo, hi);
-      const double lp = S.logf(cand);
-      S.note(lp, logp_slice);
-      if (!(lp < logp_slice)) { nu = cand; break; }
-      if (cand > x) hi = cand; else lo = cand;                 // contract
-      dx = hi - lo;
-      if (++tries > 100) { err = 1; break; }
-    }
-  }
+  int err = slice_draw_lower0(S, rng, false, x, dx, nu);
   if (rng.overran()) err = 2;
   if (tid == 0) {
     P.sigsq[chain] = sigsq;

@@ -334,6 +334,18 @@ PYBIND11_MODULE(_boom, boom) {
       .def("set_prior", &LocalLinearTrendStateModel::set_prior, py::arg("which_variable"), py::arg("df"),
            py::arg("sigma_guess"), py::arg("sigma_upper_limit") = std::numeric_limits<double>::infinity(),
            "ZeroMeanMvnIndependenceSampler(model, df, sigma_guess, which_variable) + set_sigma_upper_limit");
+  py::class_<StudentLocalLinearTrendStateModel, Ptr<StudentLocalLinearTrendStateModel>>(boom, "StudentLocalLinearTrendStateModel")
+      .def(py::init<double, double, double, double>(), py::arg("sigma_level") = 1.0, py::arg("nu_level") = 1000.0,
+           py::arg("sigma_slope") = 1.0, py::arg("nu_slope") = 1000.0)
+      .def("set_initial_state_mean", [](StudentLocalLinearTrendStateModel &m, const NpArray &v) { m.set_initial_state_mean(vector_from(v)); })
+      .def("set_initial_state_variance", [](StudentLocalLinearTrendStateModel &m, const NpArray &diag) { m.set_initial_state_variance(vector_from(diag)); })
+      .def("set_initial_sigma", &StudentLocalLinearTrendStateModel::set_initial_sigma)
+      .def("set_initial_nu", &StudentLocalLinearTrendStateModel::set_initial_nu)
+      .def("set_prior", &StudentLocalLinearTrendStateModel::set_prior, py::arg("which"), py::arg("df"),
+           py::arg("sigma_guess"), py::arg("sigma_upper_limit") = std::numeric_limits<double>::infinity(),
+           "which = 0: level, 1: slope; ChisqModel(df, sigma_guess) on sigma^2 + the sigma upper limit")
+      .def("set_nu_prior", &StudentLocalLinearTrendStateModel::set_nu_prior, py::arg("which"), py::arg("kind"),
+           py::arg("a"), py::arg("b"), "kind 0: uniform(a, b); 1: gamma(a, b)");
   py::class_<SeasonalStateModel, Ptr<SeasonalStateModel>>(boom, "SeasonalStateModel")
       .def(py::init<int, int>(), py::arg("nseasons"), py::arg("season_duration") = 1)
       .def_property_readonly("state_dimension", &SeasonalStateModel::state_dimension)
@@ -423,6 +435,17 @@ PYBIND11_MODULE(_boom, boom) {
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<StaticInterceptStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<TrigStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<SemilocalLinearTrendStateModel> &s) { m.add_state(s); })
+      .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<StudentLocalLinearTrendStateModel> &s) { m.add_state(s); })
+      .def("student_trend_nu", [](const StateSpaceRegressionModel &m, int chain) { return to_numpy(m.student_trend_nu(chain)); },
+           py::arg("chain") = 0, "(nu_level, nu_slope) of the StudentLocalLinearTrendStateModel in one chain's draw")
+      .def("student_trend_weights", [](const StateSpaceRegressionModel &m, int chain) {
+        const Matrix w = m.student_trend_weights(chain);
+        py::array_t<double> out({(py::ssize_t)w.nrow(), (py::ssize_t)w.ncol()});
+        auto o = out.mutable_unchecked<2>();
+        for (int i = 0; i < w.nrow(); ++i)
+          for (int j = 0; j < w.ncol(); ++j) o(i, j) = w(i, j);
+        return out;
+      }, py::arg("chain") = 0, "the StudentLocalLinearTrendStateModel's weights in one chain: (2, T), level then slope")
       .def("semilocal_slope", [](const StateSpaceRegressionModel &m, int chain, int which) { return to_numpy(m.semilocal_slope(chain, which)); },
            py::arg("chain") = 0, py::arg("which") = 0,
            "(AR(1) coefficient, long-run mean) of the which-th SemilocalLinearTrendStateModel's slope in one chain's draw")

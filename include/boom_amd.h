@@ -590,6 +590,22 @@ int ba_ss_set_local_level(ba_engine *e, double level_df,
  *           initial_phi = {mu's prior mean, sd, phi's prior mean, sd, initial mu, initial phi};
  *           initial_state_mean / _variance have three entries, the third is not read (the
  *           component IS mu: mean mu, variance 0).  Takes one of the 4 autoregression slots.  3
+ *   kind 8  StudentLocalLinearTrendStateModel (StateModels/StudentLocalLinearTrend.cpp, bsts
+ *           AddStudentLocalLinearTrend): state (level, slope) as kind 2, but the level and slope
+ *           errors of the step t -> t + 1 have the variances sigma_c^2 / w_c[t] with latent weights
+ *           w_c[t] ~ Gamma(nu_c / 2, nu_c / 2): Student-t errors with nu_c degrees of freedom.  Its
+ *           StudentLocalLinearTrendPosteriorSampler draws sigma_level^2, nu_level, sigma_slope^2,
+ *           nu_slope (sigma^2 from the weighted sum of squares, nu by a new unimodal
+ *           ScalarSliceSampler per draw); observe_state redraws the weights after every state
+ *           draw.  The var_* arrays have two entries (level, slope); initial_phi = {nu_level prior
+ *           kind, a, b, nu_slope prior kind, a, b, initial nu_level, initial nu_slope}, the prior
+ *           kinds as ba_student_set_nu_prior's (0: uniform(a, b) -- bsts's default is (1, 500);
+ *           1: gamma(a, b)).  Refused: an initial nu that is not positive or has zero prior
+ *           density, a second such model in the list, the Student-t / Poisson / logit observation
+ *           families.  With it ba_ss_forecast ("forecasts with a Student local linear trend are not
+ *           implemented") and a look-ahead above 1 (ba_ss_set_lookahead, ba_ss_draw_next: the
+ *           snapshots do not carry the weights) are refused.  A drawn weight that is not finite
+ *           and positive stops the chain with status 13 (BA_E_INVALID).                     2
  * iparams is ignored for kinds 1, 2 and 5 (may be NULL).  The var_* arrays hold one entry
  * per variance parameter of the model (two for kinds 2 and 7: level, slope; one otherwise):
  * ChisqModel(df, sigma_guess) prior, sigma upper limit (infinity: none), initial sigma.
@@ -603,7 +619,10 @@ int ba_ss_set_local_level(ba_engine *e, double level_df,
  * 6 (slope), 7 (seasonal), 13 (trig), 14 (a semilocal slope: NonzeroMeanAr1Sampler) or 12 (ArPosteriorSampler: the proposals' normals, then the
  * sigma draw -- the reference takes the proposals from GlobalRng::rng and the rest from
  * the sampler's generator) + 16 for every earlier model of the same family (local level
- * and local linear trend are one family); the state draw reads stream 2. */
+ * and local linear trend are one family); the state draw reads stream 2.  A Student local linear
+ * trend (kind 8) is in no family: its sampler's four draws read sampler id 160 in sequence, and
+ * weight c (0 level, 1 slope) of the step t -> t + 1 in the chain's s-th state draw reads id 161 at
+ * slot (s T + t) 2 + c of 256 uniforms (then the slot's spill stream; ba_set_slot_limit applies). */
 int ba_ss_clear_state_models(ba_engine *e);
 int ba_ss_add_state_model(ba_engine *e, int32_t kind, const int32_t *iparams,
                           const double *var_df, const double *var_sigma_guess,
@@ -631,7 +650,9 @@ int ba_ss_state_dimension(ba_engine *e, int32_t *state_dimension, int32_t *nbloc
  * variances = (level, slope), phi[0..1] = (phi, mu) of the slope's NonzeroMeanAr1Model, ar_xtx
  * [0..5] = its Ar1Suf (sum of squares, sum, cross product of successive values, n, first value,
  * last value; Models/TimeSeries/NonzeroMeanAr1Model.cpp:33-91), ar_n = n; ar_xty / ar_yty are
- * refused.  Any pointer may be NULL */
+ * refused.  A Student local linear trend (kind 8): variances = (level, slope), suf_n = T - 1 and
+ * suf_ss = sum_t r_t^2 w_old[t] (the WeightedGaussianSuf of the last state draw's residuals with the
+ * weights that draw was made with), phi[0..1] = (nu_level, nu_slope).  Any pointer may be NULL */
 int ba_ss_get_state_model(ba_engine *e, int64_t chain, int32_t block, double *variances,
                           double *suf_n, double *suf_ss, double *phi, double *ar_xtx,
                           double *ar_xty, double *ar_yty, double *ar_n);
@@ -709,6 +730,18 @@ int ba_ss_sweep(ba_engine *e, int32_t nsweeps);
 /* one Base::impute_state (StateSpaceModelBase.cpp:278-291) with the current
  * parameters, on every chain */
 int ba_ss_impute_state(ba_engine *e);
+/* The Student local linear trend (kind 8 above) of the list of state models.
+ * ba_ss_trend_get_weights: one chain's weights, T each; entry t scales the state errors of the step
+ * t -> t + 1, entry T - 1 is never drawn and stays 1.  ba_ss_trend_set_weights: of one chain or
+ * (chain = -1) of all; every entry finite and > 0, else "Weights must be finite and positive.".
+ * ba_ss_trend_get_weight_suf: out[0..5] = the GammaSuf (n, sum, sum of logs) of the level weights
+ * the last state draw's observe_state drew, then the slope's.  ba_ss_trend_draw_parameters: the
+ * model's sample_posterior() alone (sigma_level^2, nu_level, sigma_slope^2, nu_slope on every
+ * chain), as ba_ss_impute_state is impute_state alone. */
+int ba_ss_trend_get_weights(ba_engine *e, int64_t chain, double *level_w, double *slope_w);
+int ba_ss_trend_set_weights(ba_engine *e, int64_t chain, const double *level_w, const double *slope_w);
+int ba_ss_trend_get_weight_suf(ba_engine *e, int64_t chain, double *out);
+int ba_ss_trend_draw_parameters(ba_engine *e);
 
 /* ---- bsts(family = "student"): StateSpaceStudentRegressionModel with
  * StateSpaceStudentPosteriorSampler (Models/StateSpace/StateSpaceStudentRegressionModel.cpp,

@@ -370,6 +370,31 @@ class LocalLinearTrendStateModel {
   Vector a0_ = Vector(2, 0.0), P0_ = Vector(2, 1.0);
   double sigma_[2] = {1.0, 1.0}, df_[2] = {1.0, 1.0}, guess_[2] = {1.0, 1.0}, upper_[2] = {infinity(), infinity()};
 };
+// StudentLocalLinearTrendStateModel with its StudentLocalLinearTrendPosteriorSampler
+// (StateModels/StudentLocalLinearTrend.cpp; bsts' AddStudentLocalLinearTrend): a local linear trend
+// whose level and slope errors are Student-t -- per-step weights, two degrees-of-freedom parameters.
+// which = 0: level, 1: slope
+class StudentLocalLinearTrendStateModel {
+ public:
+  explicit StudentLocalLinearTrendStateModel(double sigma_level = 1.0, double nu_level = 1000.0, double sigma_slope = 1.0,
+                                             double nu_slope = 1000.0) {
+    sigma_[0] = sigma_level; sigma_[1] = sigma_slope; nu_[0] = nu_level; nu_[1] = nu_slope;
+  }
+  void set_initial_state_mean(const Vector &m) { a0_ = m; }
+  void set_initial_state_variance(const Vector &diagonal) { P0_ = diagonal; }
+  void set_initial_sigma(double level_sigma, double slope_sigma) { sigma_[0] = level_sigma; sigma_[1] = slope_sigma; }
+  void set_initial_nu(double level_nu, double slope_nu) { nu_[0] = level_nu; nu_[1] = slope_nu; }
+  // ChisqModel(df, sigma_guess) on sigma^2 + set_sigma_{level, slope}_upper_limit
+  void set_prior(int which, double df, double sigma_guess, double sigma_upper_limit = infinity()) {
+    df_[which] = df; guess_[which] = sigma_guess; upper_[which] = sigma_upper_limit;
+  }
+  // the prior on nu: kind 0 = UniformModel(a, b) (bsts: (1, 500)), 1 = GammaModel(a, b)
+  void set_nu_prior(int which, int kind, double a, double b) { nu_kind_[which] = kind; nu_a_[which] = a; nu_b_[which] = b; }
+  Vector a0_ = Vector(2, 0.0), P0_ = Vector(2, 1.0);
+  double sigma_[2], nu_[2], df_[2] = {1.0, 1.0}, guess_[2] = {1.0, 1.0}, upper_[2] = {infinity(), infinity()};
+  int nu_kind_[2] = {0, 0};
+  double nu_a_[2] = {1.0, 1.0}, nu_b_[2] = {500.0, 500.0};
+};
 // SeasonalStateModel(nseasons, season_duration) with a ZeroMeanGaussianConjSampler: the
 // transition is the seasonal matrix on the steps INTO a new season and the identity
 // inside one (StateModels/SeasonalStateModel.cpp:89-104, :248-258)
@@ -540,14 +565,19 @@ class StateSpaceRegressionModel : public Model {
   void add_state(const Ptr<StaticInterceptStateModel> &s) { Entry e; e.kind = 5; e.intercept = s; models_.push_back(e); finalized_ = false; }
   void add_state(const Ptr<TrigStateModel> &s) { Entry e; e.kind = 6; e.trig = s; models_.push_back(e); finalized_ = false; }
   void add_state(const Ptr<SemilocalLinearTrendStateModel> &s) { Entry e; e.kind = 7; e.semilocal = s; models_.push_back(e); finalized_ = false; }
+  void add_state(const Ptr<StudentLocalLinearTrendStateModel> &s) { Entry e; e.kind = 8; e.student_trend = s; models_.push_back(e); finalized_ = false; }
   int number_of_state_models() const { return (int)models_.size(); }
+  bool has_student_trend() const {
+    for (const Entry &e : models_) if (e.kind == 8) return true;
+    return false;
+  }
   // anything but a lone local level (which runs the local-level kernels; the Student-t family
   // always sends the list)
   bool structural() const { return list_always_ || !(models_.size() == 1 && models_[0].kind == 1); }
   int state_dimension() const {
     int m = 0;
     for (const Entry &e : models_)
-      m += (e.kind == 1 || e.kind == 5) ? 1 : e.kind == 2 ? 2 : e.kind == 3 ? e.seasonal->state_dimension()
+      m += (e.kind == 1 || e.kind == 5) ? 1 : (e.kind == 2 || e.kind == 8) ? 2 : e.kind == 3 ? e.seasonal->state_dimension()
            : e.kind == 6 ? e.trig->state_dimension() : e.kind == 7 ? 3 : e.ar->lags_;
     return m;
   }
@@ -580,6 +610,12 @@ class StateSpaceRegressionModel : public Model {
           const double sig[2] = {s.level_->sigma_, s.slope_->sigma_};
           const double pp[6] = {s.prior_[0], s.prior_[1], s.prior_[2], s.prior_[3], s.slope_->mu_, s.slope_->phi_};
           eng_->check(ba_ss_add_state_model(h, 7, ip, s.df_, s.guess_, s.upper_, sig, pp, s.a0_, s.P0_));
+        } else if (e.kind == 8) {
+          const StudentLocalLinearTrendStateModel &s = *e.student_trend;
+          const double pp[8] = {(double)s.nu_kind_[0], s.nu_a_[0], s.nu_b_[0], (double)s.nu_kind_[1], s.nu_a_[1], s.nu_b_[1],
+                                s.nu_[0], s.nu_[1]};
+          eng_->check(ba_ss_set_lookahead(h, 1));   // (the engine refuses a look-ahead with this model)
+          eng_->check(ba_ss_add_state_model(h, 8, nullptr, s.df_, s.guess_, s.upper_, s.sigma_, pp, s.a0_.data(), s.P0_.data()));
         } else if (e.kind == 6) {
           const TrigStateModel &s = *e.trig;
           const int32_t ip[3] = {(int32_t)s.frequencies_.size(), 0, 0};
@@ -618,6 +654,21 @@ class StateSpaceRegressionModel : public Model {
     report_error("The model has no such SemilocalLinearTrendStateModel.");
     return Vector();
   }
+  // the StudentLocalLinearTrendStateModel in one chain's current draw: (nu_level, nu_slope), and its
+  // weights, 2 x time_dimension (row 0 the level's, row 1 the slope's)
+  Vector student_trend_nu(int chain = 0) const {
+    Vector v(2);
+    eng_->check(ba_ss_get_state_model(eng_->get(), chain, student_trend_block(), nullptr, nullptr, nullptr, v.data(), nullptr, nullptr, nullptr, nullptr));
+    return v;
+  }
+  Matrix student_trend_weights(int chain = 0) const {
+    student_trend_block();
+    Vector lw(T_), sw(T_);
+    eng_->check(ba_ss_trend_get_weights(eng_->get(), chain, lw.data(), sw.data()));
+    Matrix w(2, T_);
+    for (int t = 0; t < T_; ++t) { w(0, t) = lw[t]; w(1, t) = sw[t]; }
+    return w;
+  }
   // one chain's state draw: state_dimension x time_dimension, the models' components in
   // the order the models were added
   Matrix structural_state(int chain = 0) const {
@@ -637,7 +688,7 @@ class StateSpaceRegressionModel : public Model {
       double v[2] = {0, 0};
       eng_->check(ba_ss_get_state_model(eng_->get(), chain, (int32_t)b, v, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
       out.push_back(v[0]);
-      if (models_[b].kind == 2 || models_[b].kind == 7) out.push_back(v[1]);
+      if (models_[b].kind == 2 || models_[b].kind == 7 || models_[b].kind == 8) out.push_back(v[1]);
     }
     Vector ans(out.size());
     for (size_t i = 0; i < out.size(); ++i) ans[i] = out[i];
@@ -694,7 +745,7 @@ class StateSpaceRegressionModel : public Model {
   }
  private:
   struct Entry {
-    int kind = 0;   // 1 local level, 2 local linear trend, 3 seasonal, 4 autoregression, 5 static intercept, 6 trig, 7 semilocal linear trend
+    int kind = 0;   // 1 local level, 2 local linear trend, 3 seasonal, 4 autoregression, 5 static intercept, 6 trig, 7 semilocal linear trend, 8 Student local linear trend
     Ptr<LocalLevelStateModel> level;
     Ptr<LocalLinearTrendStateModel> trend;
     Ptr<SeasonalStateModel> seasonal;
@@ -702,7 +753,14 @@ class StateSpaceRegressionModel : public Model {
     Ptr<StaticInterceptStateModel> intercept;
     Ptr<TrigStateModel> trig;
     Ptr<SemilocalLinearTrendStateModel> semilocal;
+    Ptr<StudentLocalLinearTrendStateModel> student_trend;
   };
+  int student_trend_block() const {
+    for (size_t b = 0; b < models_.size(); ++b)
+      if (models_[b].kind == 8) return (int)b;
+    report_error("The model has no StudentLocalLinearTrendStateModel.");
+    return -1;
+  }
   int ar_block(int which) const {
     int seen = 0;
     for (size_t b = 0; b < models_.size(); ++b)
@@ -733,7 +791,8 @@ class StateSpacePosteriorSampler : public PosteriorSampler {
     model->engine()->check(ba_set_state(h, -1, g0.data(), nullptr, 1.0));
     // the callers' per-iteration loop at the device's rate (ba_ss_draw_next serves the
     // rounds from batches enqueued ahead; nothing a caller does can observe it)
-    model->engine()->check(ba_ss_set_lookahead(h, 64));
+    // (a StudentLocalLinearTrendStateModel's weights are not in the look-ahead's snapshots: one round per draw)
+    model->engine()->check(ba_ss_set_lookahead(h, model->has_student_trend() ? 1 : 64));
   }
   void set_lookahead(int rounds) { model_->engine()->check(ba_ss_set_lookahead(model_->engine()->get(), rounds)); }
   void draw() override {                     // StateSpacePosteriorSampler.cpp:42-64
