@@ -52,6 +52,18 @@ struct TnHull {
   int stride;     // slots side by side
   int cap;        // points
 };
+// update_cdf's exponent y - d z + d knot, every product and sum rounded as the reference rounds
+// them (the intrinsics __dmul_rn / __dadd_rn are plain operators here and contract like them:
+// only the pragma keeps the compiler from it).  The three terms are x^2 large and cancel to x
+// times a neighbour: as fused multiply-adds the exponent came out tens away from the reference's
+// wherever the cut is within 1e-9 of the mean (candidates 1 / a large), the next uniform fell
+// into another segment and the hull took other points -- another draw than the reference's
+// (tests/test_imputer_kernels_gpu.py, probit-phase3).
+__device__ __forceinline__ double tn_exponent(double y, double d, double z, double knot) {
+#pragma clang fp contract(off)
+  const double dz = d * z, dk = d * knot;
+  return (y - dz) + dk;
+}
 // returns false when the hull outgrew its capacity (the caller redoes the observation)
 __device__ __forceinline__ bool tn_draw_lds(SeqRng &rng, double a, const TnHull &H, double *out) {
   auto yv = [](double x) { return __dmul_rn(__dmul_rn(-.5, x), x); };   // (a stored value in the reference: rounded)
@@ -66,13 +78,18 @@ __device__ __forceinline__ bool tn_draw_lds(SeqRng &rng, double a, const TnHull 
       double last = 0;
       for (int k = 0; k < n; ++k) {
         const double z = AT(xs, k), d = -z, y = yv(z) - y0, dinv = 1.0 / d;
-        const double inc1 = (k == n - 1) ? 0 : dinv * exp(y - d * z + d * AT(kn, k + 1));
-        const double inc2 = dinv * exp(y - d * z + d * AT(kn, k));
+        const double inc1 = (k == n - 1) ? 0 : dinv * exp(tn_exponent(y, d, z, AT(kn, k + 1)));
+        const double inc2 = dinv * exp(tn_exponent(y, d, z, AT(kn, k)));
         last = last + inc1 - inc2;
         AT(cdf, k) = last;
       }
     }
     const double u = d_runif(rng, 0.0, AT(cdf, n - 1));
+    // (Below a = 1e-15 the integrals, 1 / a large, cancel to a total that can be negative or not
+    // a number; lower_bound then answers k = n, where the reference reads past its arrays.  Here
+    // xs[n], kn[n] and kn[n + 1] are entries of this slot's own three arrays -- n <= cap, and kn
+    // and cdf follow xs and kn -- stale ones: the read is bounded and the draw is noise, as the
+    // reference's is; such a hull goes on to outgrow its capacity and is reported.)
     int k = 0;
     {  // std::lower_bound(cdf, cdf + n, u)
       int count = n;

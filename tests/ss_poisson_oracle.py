@@ -67,6 +67,13 @@ def _copy(rng):
     return r
 
 
+def _fused(v):
+    """an a + b c the device may round once: tests/imputer_ref.py's replays move it by an ulp
+    (this module's `math` is then their table); the value itself otherwise"""
+    f = getattr(math, "fused", None)
+    return v if f is None else f(v)
+
+
 def _gap(a, b):
     return abs(a - b) / max(1.0, abs(a), abs(b))
 
@@ -167,9 +174,9 @@ def unmix(L, rng, M, u, nevents):
     return mu[ind], sigma[ind] * sigma[ind], margin
 
 
-def impute_point(L, rng, M, y, exposure, eta):
-    """PoissonDataImputer::impute (PoissonDataImputer.cpp:36-96) and the combination of
-    StateSpacePoissonPosteriorSampler.cpp:112-123: (v, q, margin)"""
+def impute_parts(L, rng, M, y, exposure, eta):
+    """PoissonDataImputer::impute (PoissonDataImputer.cpp:36-96): the external point (z_ext, mu_e,
+    sigsq_e), the internal one (z_int, mu_i, sigsq_i; None where y = 0) and the smallest margin"""
     y = int(round(y))
     margin = np.inf
     t_final = 0.0
@@ -181,7 +188,7 @@ def impute_point(L, rng, M, y, exposure, eta):
         t_final = exposure * draw
     delta = exposure - t_final
     if abs(eta) < 600:
-        z_ext = -math.log(delta + (1.0 / math.exp(eta)) * L.bo_exp_rand(C.byref(rng)))
+        z_ext = -math.log(_fused(delta + (1.0 / math.exp(eta)) * L.bo_exp_rand(C.byref(rng))))
     elif delta > 0:
         err = -math.log(L.bo_exp_rand(C.byref(rng)))          # rexv_mt(rng, 0, 1)
         xx, yy = math.log(delta), -err - eta
@@ -191,13 +198,24 @@ def impute_point(L, rng, M, y, exposure, eta):
         z_ext = eta + -math.log(L.bo_exp_rand(C.byref(rng)))
     mu_e, sig_e, m = unmix(L, rng, M, z_ext - eta, 1)
     margin = min(margin, m)
-    q = 1.0 / sig_e
-    s = (z_ext - mu_e) * q
+    internal = None
     if y > 0:
         z_int = -math.log(t_final)
         mu_i, sig_i, m = unmix(L, rng, M, z_int - eta, y)
         margin = min(margin, m)
-        s += (z_int - mu_i) * (1.0 / sig_i)
+        internal = (z_int, mu_i, sig_i)
+    return (z_ext, mu_e, sig_e), internal, margin
+
+
+def impute_point(L, rng, M, y, exposure, eta):
+    """PoissonDataImputer::impute and the combination of StateSpacePoissonPosteriorSampler.cpp:
+    112-123, the external point first: (v, q, margin)"""
+    (z_ext, mu_e, sig_e), internal, margin = impute_parts(L, rng, M, y, exposure, eta)
+    q = 1.0 / sig_e
+    s = (z_ext - mu_e) * q
+    if internal is not None:
+        z_int, mu_i, sig_i = internal
+        s += _fused((z_int - mu_i) * (1.0 / sig_i))   # (sum + weight x residual: fusable on the device)
         q += 1.0 / sig_i
     return s / q, q, margin
 
