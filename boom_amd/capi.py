@@ -184,6 +184,7 @@ SIGNATURES = {
     "ba_ss_trend_get_weight_suf": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
     "ba_ss_trend_draw_parameters": (C.c_int, [C.c_void_p]),
     "ba_ss_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
+    "ba_ss_prediction_errors": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp]),
     "ba_ss_student_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
     "ba_ss_poisson_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp]),
     "ba_ss_logit_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp]),
@@ -984,6 +985,34 @@ class Engine:
         h = newX.shape[0]
         out = np.zeros((self.chains, h))
         self._check(self.lib.ba_ss_forecast(self._h, h, _p(_fcol(newX)), _p(out)))
+        return out
+
+    def ss_prediction_errors(self, standardize=False, chains=None, variances=False, log_likelihood=False):
+        """bsts's one.step.prediction.errors of every chain's current draw (chains: a (first, count)
+        pair or a range; None: all): chains x T, row c = chain first + c.  With variances or
+        log_likelihood: a dict of errors, variances (F_t, the same shape) and log_likelihood (one per
+        chain), the ones asked for"""
+        if chains is None:
+            first, count = 0, self.chains
+        elif isinstance(chains, range):
+            if chains.step != 1:
+                raise ValueError("chains: a contiguous range")
+            first, count = chains.start, len(chains)
+        else:
+            first, count = (int(v) for v in chains)
+        rows = max(count, 0)
+        err = np.zeros((rows, self.T))
+        var = np.zeros((rows, self.T)) if variances else None
+        ll = np.zeros(rows) if log_likelihood else None
+        self._check(self.lib.ba_ss_prediction_errors(self._h, first, count, 1 if standardize else 0,
+                                                     _p(err), _p(var), _p(ll)))
+        if not variances and not log_likelihood:
+            return err
+        out = dict(errors=err)
+        if variances:
+            out["variances"] = var
+        if log_likelihood:
+            out["log_likelihood"] = ll
         return out
 
     def ss_get_state(self, chain, state=True, suf=True):

@@ -994,6 +994,10 @@ void ba_engine_destroy(ba_engine *e) {
     (void)hipStreamSynchronize(e->stream2);
     (void)hipStreamDestroy(e->stream2);
   }
+  if (e->ssf_stream) {
+    (void)hipStreamSynchronize(e->ssf_stream);
+    (void)hipStreamDestroy(e->ssf_stream);
+  }
   for (int i = 0; i < 2; ++i) {
     if (e->la.done[i]) (void)hipEventDestroy(e->la.done[i]);
     if (e->ssla.done[i]) (void)hipEventDestroy(e->ssla.done[i]);
@@ -1044,7 +1048,7 @@ const char *ba_kernel_class_name(int32_t cls) {
       "xtx_mfma_kernel+plane_sum_kernel+col_reduce_kernel", "poisson_impute_kernel",
       "kalman_prepare_kernel", "ss_round_kernel", "student_impute_kernel", "student_sigma_nu_kernel",
       "quantile_impute_kernel", "mlogit_impute_kernel", "student_ss_kernels", "poisson_ss_kernels", "logit_ss_kernels",
-      "student_trend_kernels"};
+      "student_trend_kernels", "ss_filter_kernel"};
   return (cls >= 0 && cls < KT_CLASSES) ? names[cls] : "";
 }
 

@@ -29,6 +29,7 @@
 #include "probit_params.h"
 #include "products.h"
 #include "quantile_params.h"
+#include "ss_filter_params.h"
 #include "ssvs_params.h"
 #include "student_params.h"
 
@@ -439,6 +440,14 @@ struct ba_engine {
   double slt_nu_a[2] = {1.0, 1.0}, slt_nu_b[2] = {500.0, 500.0}, slt_initial_nu[2] = {10.0, 10.0};
   DevBuf<double> dslt_w, dslt_res, dslt_nu, dslt_wsuf;
   DevBuf<uint64_t> dslt_pos, dslt_count;
+  // ba_ss_prediction_errors (ss_filter_kernel.hip): its outputs on the device (errors, forecast
+  // variances, log likelihoods, the forecast-variance flag), the local-level path's one-block
+  // list, and the stream the filter of a look-ahead's recorded draw runs on beside the batch
+  // that is running ahead
+  DevBuf<double> dssf_err, dssf_var, dssf_ll;
+  DevBuf<int32_t> dssf_flag;
+  DevBuf<uint8_t> dssf_spec;
+  hipStream_t ssf_stream = nullptr;
   // ---- look-ahead on the bsts path (ba_ss_set_lookahead / ba_ss_draw_next): a batch of
   // `len` sweep rounds per enqueue, every round's draw recorded on the device -- gamma,
   // beta, sigma^2, the state models' variances and coefficients for EVERY chain, the

@@ -1602,6 +1602,129 @@ int ba_ss_forecast(ba_engine *e, int32_t horizon, const double *newX, double *ou
   return BA_OK;
 }
 
+// One-step prediction errors, forecast variances and the log likelihood of the chains' current
+// draw (ss_filter_kernel.hip).  An observer: it enqueues its own kernel and copies, and changes
+// no stream position, state path, sufficient statistic or snapshot.  While ba_ss_draw_next
+// serves a batch the parameters are the served row of the record, and the filter runs on a
+// stream of its own behind the batch's event -- beside the batch that is running ahead.
+int ba_ss_prediction_errors(ba_engine *e, int64_t chain_first, int64_t chain_count, int32_t standardize,
+                            double *errors, double *variances, double *log_likelihood) {
+  ENGINE_PROLOGUE_NOJOIN(e);
+  {
+    int rcj = pipe_join(e);
+    if (rcj) return rcj;
+  }
+  if (e->data_kind == DATA_SS_STUDENT || e->data_kind == DATA_SS_POISSON || e->data_kind == DATA_SS_LOGIT)
+    return fail(BA_E_STATE, "one-step prediction errors are built for the Gaussian observation model only");
+  if (e->data_kind != DATA_STATE_SPACE) return fail(BA_E_STATE, set_data_first(DATA_STATE_SPACE));
+  if (!errors && !variances && !log_likelihood) return fail(BA_E_INVALID, "null argument");
+  if (chain_first < 0 || chain_count <= 0 || chain_first >= e->cfg.chains || chain_count > e->cfg.chains - chain_first)
+    return fail(BA_E_INVALID, "chain range out of bounds");
+  const bool served = ss_la_serving(e);
+  int rc = BA_OK;
+  if (served) {
+    rc = ss_la_wait(e);
+  } else {
+    rc = ss_prepare(e);
+    if (!rc) rc = ba_sync(e);   // (a stopped chain: its error, as ba_ss_forecast)
+  }
+  if (rc) return rc;
+  const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, T = (size_t)e->T, n = (size_t)chain_count;
+  hipStream_t s = e->stream;
+  if (served) {
+    if (!e->ssf_stream) HIP_TRY(hipStreamCreateWithFlags(&e->ssf_stream, hipStreamNonBlocking));
+    s = e->ssf_stream;   // (ss_la_wait has waited for the batch's event on the host)
+  }
+  if (e->dssf_err.count < n * T) HIP_TRY(e->dssf_err.resize(n * T));
+  if (variances && e->dssf_var.count < n * T) HIP_TRY(e->dssf_var.resize(n * T));
+  if (e->dssf_ll.count < n) HIP_TRY(e->dssf_ll.resize(n));
+  if (e->dssf_flag.count == 0) HIP_TRY(e->dssf_flag.resize(1));
+  SsFilterParams F{};
+  F.T = e->T;
+  F.p = e->p;
+  F.chain_first = (int32_t)chain_first;
+  F.chain_count = (int32_t)chain_count;
+  F.standardize = standardize ? 1 : 0;
+  F.y = e->dss_y.ptr;
+  F.X = e->dss_X.ptr;
+  F.observed = e->dss_obs.ptr;
+  if (e->ssm_set) {
+    F.spec = reinterpret_cast<const SsgSpec *>(e->dssg_spec.ptr);
+    F.m = e->ssg.m;
+    F.nblocks = e->ssg.nblocks;
+    F.nvar = e->ssg.nvar;
+    F.nar = e->ssg.nar;
+    if (e->ssg.student_block) {
+      F.qw = e->dslt_w.ptr;   // (a look-ahead above 1 is refused with such a block: always live)
+      F.qw_stride = 2 * (int64_t)T;
+    }
+  } else {
+    // the local-level path: the same kernel on a one-block list
+    SsgSpec one{};
+    one.m = one.nblocks = one.nvar = 1;
+    one.blk[0].kind = SSG_LOCAL_LEVEL;
+    one.blk[0].dim = 1;
+    one.blk[0].nvar = 1;
+    one.blk[0].duration = 1;
+    one.blk[0].ar_index = -1;
+    one.a0[0] = e->ss_a0;
+    one.P0[0] = e->ss_P0;
+    if (e->dssf_spec.count == 0) HIP_TRY(e->dssf_spec.resize(sizeof(SsgSpec)));
+    HIP_TRY(hipMemcpy(e->dssf_spec.ptr, &one, sizeof(SsgSpec), hipMemcpyHostToDevice));
+    F.spec = reinterpret_cast<const SsgSpec *>(e->dssf_spec.ptr);
+    F.m = F.nblocks = F.nvar = 1;
+    F.nar = 0;
+  }
+  F.ld = (F.m + 1) | 1;
+  if (served) {
+    // the draw being served: row served - 1 of every chain, [slot][chain][round][...]
+    const ba_engine::SsLa &A = e->ssla;
+    const size_t L = (size_t)A.len, at0 = (size_t)A.slot * C * L + (size_t)A.served - 1;
+    F.src.gamma = A.rgamma.ptr + at0 * p;
+    F.src.beta = A.rbeta.ptr + at0 * p;
+    F.src.sigsq = A.rsig.ptr + at0;
+    F.src.var = A.rvar.ptr + at0 * A.nvar;
+    F.src.phi = A.nphi ? A.rphi.ptr + at0 * A.nphi : nullptr;
+    F.src.gamma_stride = F.src.beta_stride = (int64_t)(L * p);
+    F.src.sigsq_stride = (int64_t)L;
+    F.src.var_stride = (int64_t)(L * A.nvar);
+    F.src.phi_stride = (int64_t)(L * A.nphi);
+  } else {
+    F.src.gamma = e->dgamma.ptr;
+    F.src.beta = e->dbeta.ptr;
+    F.src.sigsq = e->dsigsq.ptr;
+    F.src.gamma_stride = F.src.beta_stride = (int64_t)p;
+    F.src.sigsq_stride = 1;
+    if (e->ssm_set) {
+      F.src.var = e->dssm_sigsq.ptr;
+      F.src.var_stride = SSG_MAX_VAR;
+      F.src.phi = e->ssg.nar > 0 ? e->dar_phi.ptr : nullptr;
+      F.src.phi_stride = SSG_MAX_AR * AR_MAX;
+    } else {
+      F.src.var = e->dlev_sigsq.ptr;   // (between calls the live value is the one the last state draw used)
+      F.src.var_stride = 1;
+    }
+  }
+  F.errors = e->dssf_err.ptr;
+  F.variances = variances ? e->dssf_var.ptr : nullptr;
+  F.loglik = e->dssf_ll.ptr;
+  F.flag = e->dssf_flag.ptr;
+  int32_t flag = 0;
+  HIP_TRY(hipMemsetAsync(e->dssf_flag.ptr, 0x7f, 4, s));
+  HIP_TRY(launch_ss_filter(s, F));
+  if (errors) HIP_TRY(hipMemcpyAsync(errors, e->dssf_err.ptr, n * T * 8, hipMemcpyDeviceToHost, s));
+  if (variances) HIP_TRY(hipMemcpyAsync(variances, e->dssf_var.ptr, n * T * 8, hipMemcpyDeviceToHost, s));
+  if (log_likelihood) HIP_TRY(hipMemcpyAsync(log_likelihood, e->dssf_ll.ptr, n * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&flag, e->dssf_flag.ptr, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (flag >= 0 && flag < e->cfg.chains) {
+    char buf[64];
+    std::snprintf(buf, sizeof buf, " (chain %lld)", (long long)(e->cfg.chain_offset + (int64_t)flag));
+    return fail(BA_E_FORECAST_VARIANCE, std::string("Found a zero (or negative) forecast variance!") + buf);
+  }
+  return BA_OK;
+}
+
 int ba_ss_get_state(ba_engine *e, int64_t chain, double *state,
                     double *level_sigsq, double *level_n, double *level_sumsq) {
   ENGINE_ACCESSOR_SERVED(e);

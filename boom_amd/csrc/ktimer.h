@@ -34,6 +34,7 @@ enum KernelClass {
   KT_SS_POISSON,       // poisson_impute_kernel<true> / latent_ss_h_kernel / latent_ss_suf_kernel (bsts family = poisson)
   KT_SS_LOGIT,         // logit_impute_kernel<true> / latent_ss_h_kernel / latent_ss_suf_kernel (bsts family = logit)
   KT_SS_STUDENT_TREND, // slt_params_kernel / slt_weights_kernel (the Student local linear trend state model)
+  KT_SS_FILTER,        // ss_filter_kernel (ba_ss_prediction_errors: the forward-only filter of the chains' current draw)
   KT_CLASSES
 };
 

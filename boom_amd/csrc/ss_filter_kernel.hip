@@ -1,0 +1,308 @@
+// One-step prediction errors and log likelihood of every chain's current draw:
+// ScalarStateSpaceModelBase::one_step_prediction_errors (StateSpaceModelBase.cpp:682-691) and
+// the log likelihood bsts stores beside it -- a forward-only scalar Kalman filter
+// (ScalarMarginalDistribution::update, ScalarKalmanFilter.cpp:41-83) at the chain's parameters,
+// for any list of state models of state dimension <= 64 and for the local-level path (a
+// one-block list).  The kernel observes: it writes its outputs and nothing else, reads no
+// random stream and does not touch the chains' status.
+//
+// One wavefront per chain.  The state variance P (m x m) sits in LDS at an odd leading
+// dimension ld > m, column m of every row carries the state mean a.  Per step
+//   PZ = P Z, F = Z'PZ + sigma^2, v = y* - Z'a;
+//   observed: a += PZ v / F, P -= PZ PZ' / F  (the filtered form; (PZ_i PZ_j) / F is symmetric to the bit)
+//   P <- T P T' + RQR, a <- T a: T is applied by ONE lane per column (rows of the blocks that
+//   move, in place; the a column with them), then by one lane per row -- no cross-lane moves,
+//   rows of blocks whose transition is the identity at this step are not touched -- and the
+//   upper triangle is mirrored into the lower one where a transition moved.
+// y*_t = y_t - x_t'beta (included coefficients) is computed first, a step per lane, into the
+// chain's output row; the serial pass reads it back 64 steps at a time and overwrites it.
+// log F, v^2 / F and v / sqrt F are taken after every block of 64 steps, a step per lane, and
+// the log likelihood's terms summed in step order: the logarithm is off the serial path.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "ktimer.h"
+#include "ss_filter_params.h"
+
+namespace boom_amd {
+
+namespace {
+
+constexpr int SSF_WAVE = 64;
+
+__device__ __forceinline__ void ssf_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// value of lane `src` (wave-uniform src)
+__device__ __forceinline__ double ssf_rl(double x, int src) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, src);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), src);
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// block b's words: kind (3 bits) | first (7) | dim (7) | first variance slot (5) | autoregression slot (3) | has a variance (1)
+struct SsfBlocks {
+  unsigned desc;   // lane b: block b
+  int nb;
+  static __device__ __forceinline__ int kind_of(unsigned d) { return (int)(d & 7u); }
+  static __device__ __forceinline__ int first_of(unsigned d) { return (int)((d >> 3) & 127u); }
+  static __device__ __forceinline__ int dim_of(unsigned d) { return (int)((d >> 10) & 127u); }
+  static __device__ __forceinline__ int var0_of(unsigned d) { return (int)((d >> 17) & 31u); }
+  static __device__ __forceinline__ int arx_of(unsigned d) { return (int)((d >> 22) & 7u); }
+  static __device__ __forceinline__ bool has_var(unsigned d) { return ((d >> 25) & 1u) != 0; }
+  __device__ __forceinline__ unsigned at(int b) const { return (unsigned)__builtin_amdgcn_readlane((int)desc, b); }
+};
+
+// x <- T_t x for a state vector in LDS, component k at x[k * s], by one lane.  mv: bit b =
+// seasonal block b steps into a new season.  Rows of identity transitions are not read.
+__device__ __forceinline__ void ssf_apply_T(const SsfBlocks &B, unsigned mv, const double *s_phi, const double *s_tc,
+                                            const double *s_ts, double *x, int s) {
+  for (int b = 0; b < B.nb; ++b) {
+    const unsigned d = B.at(b);
+    const int kd = SsfBlocks::kind_of(d), f = SsfBlocks::first_of(d), n = SsfBlocks::dim_of(d);
+    double *xb = x + f * s;
+    if (kd == SSG_LOCAL_LINEAR_TREND) {
+      xb[0] = xb[0] + xb[s];
+    } else if (kd == SSG_SEMILOCAL) {
+      // (level, slope, mean) -> (level + slope, phi slope + (1 - phi) mean, mean)
+      const double ph = s_phi[SsfBlocks::arx_of(d) * AR_MAX];
+      const double v0 = xb[0], v1 = xb[s], v2 = xb[2 * s];
+      xb[0] = v0 + v1;
+      xb[s] = ph * v1 + (1 - ph) * v2;
+    } else if (kd == SSG_TRIG) {
+      for (int q = 0; q < n; q += 2) {
+        const double c = s_tc[f + q], sn = s_ts[f + q];
+        const double x0 = xb[q * s], x1 = xb[(q + 1) * s];
+        xb[q * s] = c * x0 + sn * x1;
+        xb[(q + 1) * s] = -sn * x0 + c * x1;
+      }
+    } else if (kd == SSG_SEASONAL) {
+      if ((mv >> b) & 1u) {
+        // first = -(sum over the block), the others move down one place
+        double prev = xb[0], tot = prev;
+        for (int q = 1; q < n; ++q) {
+          const double cur = xb[q * s];
+          tot += cur;
+          xb[q * s] = prev;
+          prev = cur;
+        }
+        xb[0] = -tot;
+      }
+    } else if (kd == SSG_AR) {
+      // first = phi'x, the others move down one place
+      const double *ph = s_phi + SsfBlocks::arx_of(d) * AR_MAX;
+      double prev = xb[0], tot = ph[0] * prev;
+      for (int q = 1; q < n; ++q) {
+        const double cur = xb[q * s];
+        tot += ph[q] * cur;
+        xb[q * s] = prev;
+        prev = cur;
+      }
+      xb[0] = tot;
+    }
+  }
+}
+
+__global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
+  extern __shared__ double s_P[];   // m x ld
+  __shared__ double s_phi[SSG_MAX_AR * AR_MAX], s_var[SSG_MAX_VAR], s_tc[SSG_MAX_STATE], s_ts[SSG_MAX_STATE];
+  const int lane = (int)threadIdx.x, row = (int)blockIdx.x;
+  if (row >= P.chain_count) return;
+  const int64_t chain = (int64_t)P.chain_first + row;
+  const int T = P.T, p = P.p, m = P.m, ld = P.ld;
+  const SsgSpec &Q = *P.spec;
+  double *err = P.errors + (size_t)row * T;
+  double *var_out = P.variances ? P.variances + (size_t)row * T : nullptr;
+
+  // ---- y* = y - X beta over the included coefficients, a step per lane; the included columns
+  // are listed 64 candidates at a time (lane k: the k-th of them and its coefficient)
+  {
+    const uint8_t *gam = P.src.gamma + chain * P.src.gamma_stride;
+    const double *bet = P.src.beta + chain * P.src.beta_stride;
+    for (int t0 = 0; t0 < T; t0 += SSF_WAVE)
+      if (t0 + lane < T) err[t0 + lane] = P.y[t0 + lane];
+    for (int j0 = 0; j0 < p; j0 += SSF_WAVE) {
+      const int jl = j0 + lane;
+      const bool inc = jl < p && gam[jl] != 0;
+      const unsigned long long incmask = __ballot(inc);
+      if (!incmask) continue;
+      const int cnt = __popcll(incmask);
+      // lane k <- the k-th included column of the batch (ascending)
+      const int rank = __popcll(incmask & ((1ull << lane) - 1ull));
+      __shared__ int s_idx[SSF_WAVE];
+      __shared__ double s_beta[SSF_WAVE];
+      if (inc) { s_idx[rank] = jl; s_beta[rank] = bet[jl]; }
+      ssf_sync();
+      for (int t0 = 0; t0 < T; t0 += SSF_WAVE) {
+        const int t = t0 + lane;
+        if (t < T) {
+          double ys = err[t];
+          for (int k = 0; k < cnt; ++k) ys -= P.X[(size_t)s_idx[k] * T + t] * s_beta[k];
+          err[t] = ys;
+        }
+      }
+      ssf_sync();
+    }
+  }
+
+  // ---- the chain's parameters and the block list
+  if (lane < P.nvar) s_var[lane] = P.src.var[chain * P.src.var_stride + lane];
+  if (P.src.phi && lane < P.nar * AR_MAX) s_phi[lane] = P.src.phi[chain * P.src.phi_stride + lane];
+  s_tc[lane] = lane < m ? Q.trig_c[lane] : 0.0;
+  s_ts[lane] = lane < m ? Q.trig_s[lane] : 0.0;
+  const double sigsq = P.src.sigsq[chain * P.src.sigsq_stride];
+  SsfBlocks B;
+  B.nb = P.nblocks;
+  B.desc = 0;
+  int dur = 1, rc = 1;   // lane b, seasonal block b: its duration; (index of the step's transition + 1 - phase) mod duration (0: it moves)
+  if (lane < P.nblocks) {
+    const SsgBlock &K = Q.blk[lane];
+    B.desc = (unsigned)K.kind | ((unsigned)K.first << 3) | ((unsigned)K.dim << 10) | ((unsigned)K.var0 << 17) |
+             ((unsigned)(K.ar_index < 0 ? 0 : K.ar_index) << 22) | ((unsigned)(K.nvar > 0 ? 1 : 0) << 25);
+    if (K.kind == SSG_SEASONAL) {
+      dur = K.duration;
+      rc = (1 - K.phase) % dur;
+      if (rc < 0) rc += dur;
+    }
+  }
+  const unsigned seasmask = (unsigned)__ballot(SsfBlocks::kind_of(B.desc) == SSG_SEASONAL);
+  // blocks whose transition is never the identity
+  const unsigned always =(unsigned)__ballot(SsfBlocks::kind_of(B.desc) == SSG_LOCAL_LINEAR_TREND ||
+                                            SsfBlocks::kind_of(B.desc) == SSG_AR || SsfBlocks::kind_of(B.desc) == SSG_TRIG ||
+                                            SsfBlocks::kind_of(B.desc) == SSG_SEMILOCAL);
+  ssf_sync();
+  // per lane: is the component one Z selects; the variance its diagonal entry gains every step;
+  // the seasonal block it is the first component of (-1: none); its part in a Student trend (1 level, 2 slope)
+  bool zsel = false;
+  double qdiag = 0.0, seas_var = 0.0, a = 0.0, P0l = 0.0;
+  int seas_first = -1, stu = 0;
+  for (int b = 0; b < B.nb; ++b) {
+    const unsigned d = B.at(b);
+    const int kd = SsfBlocks::kind_of(d), f = SsfBlocks::first_of(d), n = SsfBlocks::dim_of(d), v0 = SsfBlocks::var0_of(d);
+    if (lane < f || lane >= f + n) continue;
+    const int w = lane - f;
+    zsel = kd == SSG_TRIG ? (w & 1) == 0 : w == 0;
+    const bool student = b == Q.student_block - 1;
+    if (kd == SSG_LOCAL_LEVEL) qdiag = SsfBlocks::has_var(d) ? s_var[v0] : 0.0;
+    else if (kd == SSG_LOCAL_LINEAR_TREND) { qdiag = s_var[v0 + w]; if (student) stu = 1 + w; }
+    else if (kd == SSG_SEMILOCAL) qdiag = w < 2 ? s_var[v0 + w] : 0.0;
+    else if (kd == SSG_TRIG) qdiag = s_var[v0];
+    else if (kd == SSG_AR) qdiag = w == 0 ? s_var[v0] : 0.0;
+    else if (kd == SSG_SEASONAL) { if (w == 0) { seas_first = b; seas_var = s_var[v0]; } }
+    a = Q.a0[lane];
+    // (a semilocal trend's third component IS the slope's long-run mean)
+    if (kd == SSG_SEMILOCAL && w == 2) a = s_phi[SsfBlocks::arx_of(d) * AR_MAX + 1];
+    P0l = Q.P0[lane];
+  }
+  const unsigned long long zmask = __ballot(zsel && lane < m);
+  const bool act = lane < m;
+  for (int e = lane; e < m * ld; e += SSF_WAVE) s_P[e] = 0.0;
+  ssf_sync();
+  if (act) s_P[lane * ld + lane] = P0l;
+  ssf_sync();
+
+  const double *qw = P.qw ? P.qw + chain * P.qw_stride : nullptr;
+  const double nan = __builtin_nan("");
+  double ll = 0.0;
+  bool dead = false;
+  for (int tb = 0; tb < T; tb += SSF_WAVE) {
+    const int tt = tb + lane;
+    const double ys_l = tt < T ? err[tt] : 0.0;
+    const unsigned long long obsmask = __ballot(tt < T && P.observed[tt] != 0);
+    double wl_l = 1.0, ws_l = 1.0;
+    if (qw && tt < T) { wl_l = qw[tt]; ws_l = qw[(size_t)T + tt]; }
+    double v_l = 0.0, F_l = 0.0;
+    const int ns = T - tb < SSF_WAVE ? T - tb : SSF_WAVE;
+    for (int s = 0; s < ns; ++s) {
+      const bool obs = ((obsmask >> s) & 1ull) != 0;
+      double vout = nan, F = nan;
+      if (!dead) {
+        // PZ, F, v
+        double pz = 0.0;
+        if (act) {
+          const double *prow = s_P + lane * ld;
+          for (unsigned long long zm = zmask; zm; zm &= zm - 1) pz += prow[__builtin_ctzll(zm)];
+        }
+        double za = 0.0, zpz = 0.0;
+        for (unsigned long long zm = zmask; zm; zm &= zm - 1) {
+          const int j = __builtin_ctzll(zm);
+          za += ssf_rl(a, j);
+          zpz += ssf_rl(pz, j);
+        }
+        F = zpz + sigsq;
+        if (!(F > 0.0) || !(F <= 1.79769313486231570815e308)) {
+          // "Found a zero (or negative) forecast variance!": the chain's outputs are NaN from here on
+          dead = true;
+          F = nan;
+          if (lane == 0) atomicMin(P.flag, (int)chain);
+        } else {
+          const double ys = ssf_rl(ys_l, s);
+          const double v = obs ? ys - za : 0.0;
+          const double Finv = 1.0 / F;
+          if (obs) {
+            if (act) {
+              a += pz * (v * Finv);
+              double *prow = s_P + lane * ld;
+              for (int j = 0; j < m; ++j) prow[j] -= (pz * ssf_rl(pz, j)) * Finv;
+            }
+          }
+          vout = v;
+          // a <- T a, P <- T P T' + RQR
+          const unsigned mv = (unsigned)__ballot(lane < B.nb && SsfBlocks::kind_of(B.desc) == SSG_SEASONAL && rc == 0) & seasmask;
+          if (always | mv) {
+            if (act) s_P[lane * ld + m] = a;
+            ssf_sync();
+            for (int c = lane; c <= m; c += SSF_WAVE) ssf_apply_T(B, mv, s_phi, s_tc, s_ts, s_P + c, ld);
+            ssf_sync();
+            if (act) {
+              ssf_apply_T(B, mv, s_phi, s_tc, s_ts, s_P + lane * ld, 1);
+              a = s_P[lane * ld + m];
+            }
+            ssf_sync();
+            // (the two passes agree only up to rounding: the upper triangle is the variance)
+            if (act)
+              for (int j = 0; j < lane; ++j) s_P[lane * ld + j] = s_P[j * ld + lane];
+          }
+          // (the step's Student-trend weights: every lane reads them, the trend's two lanes use them)
+          const double wl = ssf_rl(wl_l, s), ws = ssf_rl(ws_l, s);
+          if (act) {
+            double q = qdiag;
+            if (stu) q = qdiag / (stu == 1 ? wl : ws);
+            if (seas_first >= 0 && ((mv >> seas_first) & 1u)) q = seas_var;
+            if (q != 0.0) s_P[lane * ld + lane] += q;
+          }
+          ssf_sync();
+        }
+      }
+      if (lane < B.nb) { rc = rc + 1 == dur ? 0 : rc + 1; }
+      if (lane == s) { v_l = vout; F_l = F; }
+    }
+    // the block's log likelihood terms and standardised errors, a step per lane; the terms are
+    // summed in step order
+    const bool ob_l = ((obsmask >> lane) & 1ull) != 0;
+    const double term = ob_l ? -0.5 * (1.8378770664093454835606594728112 + log(F_l) + v_l * v_l / F_l) : 0.0;
+    for (int s = 0; s < ns; ++s) ll += ssf_rl(term, s);
+    if (tt < T) {
+      err[tt] = (P.standardize && ob_l) ? v_l / sqrt(F_l) : v_l;
+      if (var_out) var_out[tt] = F_l;
+    }
+  }
+  if (lane == 0) P.loglik[row] = dead ? nan : ll;
+}
+
+}  // namespace
+
+size_t ss_filter_lds(int m, int ld) { return (size_t)m * ld * sizeof(double); }
+
+hipError_t launch_ss_filter(hipStream_t stream, const SsFilterParams &P) {
+  if (P.chain_count <= 0) return hipSuccess;
+  KtScope kt(stream, KT_SS_FILTER);
+  hipLaunchKernelGGL(ss_filter_kernel, dim3((unsigned)P.chain_count), dim3(SSF_WAVE), ss_filter_lds(P.m, P.ld), stream, P);
+  return hipGetLastError();
+}
+
+}  // namespace boom_amd

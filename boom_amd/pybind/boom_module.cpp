@@ -57,6 +57,14 @@ py::array_t<double> forecast_to_numpy(const Matrix &m) {
     for (int i = 0; i < m.nrow(); ++i) w(c, i) = m(i, c);
   return out;
 }
+// a Matrix as it stands (rows x columns)
+py::array_t<double> matrix_to_numpy(const Matrix &m) {
+  py::array_t<double> out({(py::ssize_t)m.nrow(), (py::ssize_t)m.ncol()});
+  auto w = out.mutable_unchecked<2>();
+  for (int c = 0; c < m.ncol(); ++c)
+    for (int i = 0; i < m.nrow(); ++i) w(i, c) = m(i, c);
+  return out;
+}
 Vector optional_vector(const py::object &a) { return a.is_none() ? Vector() : vector_from(a.cast<NpArray>()); }
 
 // GlmCoefs as the drivers use it: model.coef.drop_all() / add / inc / Beta
@@ -428,6 +436,12 @@ PYBIND11_MODULE(_boom, boom) {
       .def_property_readonly("xdim", &StateSpaceRegressionModel::xdim)
       .def_property_readonly("time_dimension", &StateSpaceRegressionModel::time_dimension)
       .def_property_readonly("state_dimension", &StateSpaceRegressionModel::state_dimension)
+      .def("one_step_prediction_errors", [](StateSpaceRegressionModel &m, bool standardize) {
+             return matrix_to_numpy(m.one_step_prediction_errors(standardize));
+           }, py::arg("standardize") = false,
+           "the one-step prediction errors of every chain's current draw (time_dimension x chains)")
+      .def("log_likelihood", [](StateSpaceRegressionModel &m) { return to_numpy(m.log_likelihood()); },
+           "the filter's log likelihood of every chain's current draw (one entry per chain)")
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<LocalLevelStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<LocalLinearTrendStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<SeasonalStateModel> &s) { m.add_state(s); })

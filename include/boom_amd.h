@@ -696,7 +696,7 @@ int ba_ss_get_structural(ba_engine *e, int64_t chain, double *state,
  * time (the batch after the one being served goes out as soon as serving starts), every
  * round's draw is recorded on the device and handed out one per call: ba_get_state,
  * ba_get_states, ba_logpri, ba_ss_get_state, ba_ss_get_structural, ba_ss_get_state_model,
- * ba_ss_get_state_draw and ba_ss_get_ar see the draw being served -- gamma, beta, sigma^2
+ * ba_ss_get_state_draw, ba_ss_get_ar and ba_ss_prediction_errors see the draw being served -- gamma, beta, sigma^2
  * and the state models' variances / coefficients of EVERY chain, the state path of the
  * chains named with ba_ss_lookahead_chains (default: chain 0).  Anything else -- a
  * mutator, ba_ss_sweep, a sufficient statistic, the state path of another chain, a
@@ -919,6 +919,26 @@ int ba_ss_logit_forecast(ba_engine *e, int32_t horizon, const double *newX, cons
  * noise.  The Student-t, Poisson and logit families are refused here: their forecasts
  * are ba_ss_student_forecast, ba_ss_poisson_forecast and ba_ss_logit_forecast. */
 int ba_ss_forecast(ba_engine *e, int32_t horizon, const double *newX, double *out);
+/* bsts's one.step.prediction.errors and log.likelihood: ScalarStateSpaceModelBase::
+ * one_step_prediction_errors (StateSpaceModelBase.cpp:682-691) and the filter's log likelihood
+ * for chains [chain_first, chain_first + chain_count) -- a plain Kalman filter
+ * (ScalarMarginalDistribution::update, ScalarKalmanFilter.cpp:41-83) over the series at exactly
+ * the parameters the accessors report at that moment (ba_get_state, ba_ss_get_state_model,
+ * ba_ss_get_state / ba_ss_get_structural, ba_ss_trend_get_weights: a Student local linear trend
+ * is filtered with its per-step variances sigma_c^2 / w_c[t]).  errors: v_t = y_t - x_t'beta -
+ * Z'a_t, 0 at a missing step (standardize != 0: v_t / sqrt(F_t)); variances: F_t; both
+ * chain_count x T, a chain's T values together; log_likelihood: chain_count, the sum over the
+ * observed steps of log N(v_t; 0, F_t).  Any of the three may be NULL, not all.  Valid before
+ * any sweep (the initial values).  An observer: no stream position, state path, sufficient
+ * statistic or snapshot changes, and a look-ahead is neither settled nor shortened.  A chain
+ * whose forecast variance is not positive and finite at some step gets NaN from that step on
+ * and the call returns BA_E_FORECAST_VARIANCE ("Found a zero (or negative) forecast
+ * variance!", the chain's index); the chain itself and its status are unchanged.  Gaussian
+ * observation model only: the Student-t, Poisson and logit families return BA_E_STATE ("one-step
+ * prediction errors are built for the Gaussian observation model only").  A stopped chain is
+ * reported as by ba_ss_forecast. */
+int ba_ss_prediction_errors(ba_engine *e, int64_t chain_first, int64_t chain_count, int32_t standardize,
+                            double *errors, double *variances, double *log_likelihood);
 /* state(): T doubles of one chain; level sigsq; level suf (n, sumsq) */
 int ba_ss_get_state(ba_engine *e, int64_t chain, double *state,
                     double *level_sigsq, double *level_n, double *level_sumsq);

@@ -708,6 +708,23 @@ class StateSpaceRegressionModel : public Model {
     eng_->check(ba_ss_get_state(eng_->get(), chain, nullptr, &v, nullptr, nullptr));
     return v;
   }
+  // ScalarStateSpaceModelBase::one_step_prediction_errors (StateSpaceModelBase.cpp:682-691) for
+  // EVERY chain's current draw: time_dimension x chains, column c = chain c (bsts's
+  // one.step.prediction.errors); standardize: v_t / sqrt(F_t).  Gaussian observation model only:
+  // the Student-t, Poisson and logit families throw the engine's refusal.
+  Matrix one_step_prediction_errors(bool standardize = false) {
+    finalize_state();
+    Matrix ans(T_, eng_->chains());
+    eng_->check(ba_ss_prediction_errors(eng_->get(), 0, eng_->chains(), standardize ? 1 : 0, ans.data(), nullptr, nullptr));
+    return ans;
+  }
+  // the filter's log likelihood of every chain's current draw (bsts's log.likelihood), one entry per chain
+  Vector log_likelihood() {
+    finalize_state();
+    Vector ans(eng_->chains());
+    eng_->check(ba_ss_prediction_errors(eng_->get(), 0, eng_->chains(), 0, nullptr, nullptr, ans.data()));
+    return ans;
+  }
  protected:
   // StateSpaceStudentRegressionModel: the same state, the Student-t observation model
   struct StudentFamily {};
