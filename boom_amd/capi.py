@@ -183,6 +183,8 @@ SIGNATURES = {
     "ba_ss_trend_set_weights": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp]),
     "ba_ss_trend_get_weight_suf": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
     "ba_ss_trend_draw_parameters": (C.c_int, [C.c_void_p]),
+    "ba_ss_autoar_draw_parameters": (C.c_int, [C.c_void_p]),
+    "ba_ss_get_ar_inclusion": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_uint8)]),
     "ba_ss_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
     "ba_ss_prediction_errors": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp]),
     "ba_ss_student_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
@@ -832,18 +834,28 @@ class Engine:
         """a general list of state models, in the order they are added: dicts with kind
         (1 local level, 2 local linear trend, 3 seasonal, 4 autoregression, 5 static intercept,
         6 trig, 7 semilocal linear trend, 8 Student local linear trend: nu_priors = ((kind, a, b) of
-        level and slope), initial_nu = (level, slope)), nseasons, duration, t0, lags, df, sigma_guess, sigma_upper_limit, initial_sigma
+        level and slope), initial_nu = (level, slope), 9 spike-and-slab autoregression: lags, initial_phi,
+        slab_mean, slab_precision, inclusion_probabilities, truncate, max_flips, allow_model_selection), nseasons, duration, t0, lags, df, sigma_guess, sigma_upper_limit, initial_sigma
         (one entry per variance parameter; none for kind 5), initial_phi, rotations (kind 6: the
         (cos, sin) pairs of the transition matrix), a0, P0 (tests/cases.py: general_spec)"""
         self._check(self.lib.ba_ss_clear_state_models(self._h))
         self._blocks = []
         for b in blocks:
             kind = int(b["kind"])
-            ip = np.zeros(3, np.int32)
+            ip = np.zeros(4, np.int32)
             if kind == 3:
-                ip[:] = (b["nseasons"], b["duration"], b.get("t0", 0))
+                ip[:3] = (b["nseasons"], b["duration"], b.get("t0", 0))
             elif kind == 4:
                 ip[0] = b["lags"]
+            elif kind == 9:
+                ip[:] = (b["lags"], int(b.get("truncate", 1)), int(b.get("max_flips", -1)),
+                         int(b.get("allow_model_selection", 1)))
+                L = int(b["lags"])
+                b = dict(b, initial_phi=np.concatenate([
+                    np.asarray(b.get("initial_phi", np.zeros(L)), dtype=np.float64).ravel(),
+                    np.asarray(b["slab_mean"], dtype=np.float64).ravel(),
+                    np.asarray(b["inclusion_probabilities"], dtype=np.float64).ravel(),
+                    np.asarray(b["slab_precision"], dtype=np.float64).ravel(order="F")]))
             elif kind == 6:
                 ip[0] = len(b["rotations"]) // 2
             elif kind == 7:
@@ -861,9 +873,9 @@ class Engine:
             self._check(self.lib.ba_ss_add_state_model(
                 self._h, kind, ip.ctypes.data_as(C.POINTER(C.c_int32)),
                 *[(_p(a) if a.size else None) for a in arrs],
-                _p(ph) if (kind in (4, 6, 7, 8) and ph.size) else None, _p(a0), _p(p0)))
+                _p(ph) if (kind in (4, 6, 7, 8, 9) and ph.size) else None, _p(a0), _p(p0)))
             self._blocks.append(dict(kind=kind, nvar=2 if kind in (2, 7, 8) else (0 if kind == 5 else 1),
-                                     lags=int(ip[0]) if kind == 4 else 0))
+                                     lags=int(ip[0]) if kind in (4, 9) else 0))
         m, nb = C.c_int32(), C.c_int32()
         self._check(self.lib.ba_ss_state_dimension(self._h, C.byref(m), C.byref(nb)))
         self._ssm_dim = m.value
@@ -979,6 +991,17 @@ class Engine:
         """the Student local linear trend's sample_posterior() alone, every chain"""
         self._check(self.lib.ba_ss_trend_draw_parameters(self._h))
         self.sync()
+
+    def ss_autoar_draw_parameters(self):
+        """the ArSpikeSlabSampler::draw() of every spike-and-slab autoregression alone, every chain"""
+        self._check(self.lib.ba_ss_autoar_draw_parameters(self._h))
+        self.sync()
+
+    def ss_get_ar_inclusion(self, chain, block):
+        """the inclusion indicators of a spike-and-slab autoregression (state model `block`) in one chain"""
+        g = np.zeros(max(self._blocks[block]["lags"], 1), np.uint8)
+        self._check(self.lib.ba_ss_get_ar_inclusion(self._h, chain, block, g.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return g[:self._blocks[block]["lags"]]
 
     def ss_forecast(self, newX):
         """one predictive draw of the next len(newX) observations per chain"""

@@ -52,6 +52,8 @@ const char *status_message(int st) {
       return "MLVS did not start with a legal configuration.";
     case STUDENT_BAD_WEIGHT:
       return "Weights must be finite and non-negative.";
+    case AR_SPIKE_BAD_DRAW:
+      return "A coefficient or variance draw of the spike-and-slab autoregression sampler came out non-finite.";
     default:
       return "unknown chain status";
   }
@@ -70,6 +72,7 @@ int status_code(int st) {
     case MLOGIT_IMPUTE_ERROR: return BA_E_RNG_BRANCH;
     case MLVS_ILLEGAL_START: return BA_E_ILLEGAL_START;
     case STUDENT_BAD_WEIGHT: return BA_E_INVALID;
+    case AR_SPIKE_BAD_DRAW: return BA_E_INVALID;
     default: return BA_E_INVALID;
   }
 }
@@ -1048,7 +1051,7 @@ const char *ba_kernel_class_name(int32_t cls) {
       "xtx_mfma_kernel+plane_sum_kernel+col_reduce_kernel", "poisson_impute_kernel",
       "kalman_prepare_kernel", "ss_round_kernel", "student_impute_kernel", "student_sigma_nu_kernel",
       "quantile_impute_kernel", "mlogit_impute_kernel", "student_ss_kernels", "poisson_ss_kernels", "logit_ss_kernels",
-      "student_trend_kernels", "ss_filter_kernel"};
+      "student_trend_kernels", "ss_filter_kernel", "ar_spike_kernel"};
   return (cls >= 0 && cls < KT_CLASSES) ? names[cls] : "";
 }
 

@@ -59,6 +59,8 @@ hipError_t launch_ssm_forecast(hipStream_t stream, const SsParams &P, int horizo
 // slt_kernel.hip: the Student local linear trend's sampler (before a state draw) and its observe_state (after it)
 hipError_t launch_slt_params(hipStream_t stream, const SsParams &P, const SltParams &U);
 hipError_t launch_slt_weights(hipStream_t stream, const SsParams &P, const SltParams &U);
+// ar_spike_kernel.hip: the ArSpikeSlabSampler of every spike-and-slab autoregression block (before a state draw)
+hipError_t launch_ar_spike(hipStream_t stream, const SsParams &P, const ArSpikeParams &U);
 // ss_family_forecast_kernel.hip: family = SS_FORECAST_*; scale = the horizon's exposures / rounded trial
 // counts (Poisson, logit), nu = every chain's degrees of freedom (Student-t); the other is not read
 hipError_t launch_ss_family_forecast(hipStream_t stream, const SsParams &P, int family, int horizon,
@@ -433,6 +435,12 @@ struct ba_engine {
   DevBuf<double> dssm_sigsq, dssm_n, dssm_ss, dssm_work;   // chains x SSG_MAX_VAR (sigsq, n, ss)
   DevBuf<double> dar_phi, dar_suf;                         // chains x SSG_MAX_AR x (AR_MAX | AR_SUF_STRIDE)
   DevBuf<uint64_t> dpos_var;                               // chains x SSG_MAX_VAR
+  // ArStateModel + ArSpikeSlabSampler (SsgBlock::ar_spike; ar_spike_kernel.hip): the priors by
+  // autoregression slot, their device copy, and every chain's inclusion indicators (chains x
+  // SSG_MAX_AR x AR_MAX bytes, held as 64-bit words so that a snapshot takes them as it takes the rest)
+  ArSpikePrior ar_spike_prior[SSG_MAX_AR] = {};
+  DevBuf<uint8_t> dar_spike_prior;
+  DevBuf<uint64_t> dar_gamma;
   // StudentLocalLinearTrendStateModel (ssg.student_block; slt_kernel.hip): the nu priors (kind, a, b)
   // and initial values of level and slope; per chain the weights and the kept residuals (2 x T each),
   // nu (2), the weights' GammaSuf (6), the sampler's stream position and the state draws observed

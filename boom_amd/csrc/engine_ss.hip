@@ -13,12 +13,20 @@ static int64_t ssm_work_stride(const ba_engine &e) {
   return per_step * e.T + SSG_MAX_STATE + 72;
 }
 
+// does the list hold an autoregression with a spike-and-slab prior (ar_spike_kernel.hip)?
+static bool ssg_has_ar_spike(const SsgSpec &q) {
+  for (int i = 0; i < q.nblocks; ++i)
+    if (q.blk[i].ar_spike) return true;
+  return false;
+}
+
 // does the block list have the shape the template kernel is compiled for?
 // [local level | local linear trend] [seasonal, duration 1] [autoregression], m <= 16
 static void ssg_template_shape(const SsgSpec &q, int32_t *trend, int32_t *nseasons, int32_t *ar_lags) {
   *trend = *nseasons = *ar_lags = 0;
   if (q.nblocks < 1 || q.nblocks > 3 || q.m > 16) return;
   if (q.student_block) return;   // (a Student local linear trend: the general kernel's QT instances)
+  if (ssg_has_ar_spike(q)) return;   // (a spike-and-slab autoregression: the general kernel passes its sampler by)
   for (int i = 0; i < q.nblocks; ++i)
     if (q.blk[i].nvar == 0) return;   // (a static intercept: the general kernel)
   int b = 0, tr = 0, ns = 0, lags = 0;
@@ -124,6 +132,20 @@ static void fill_ss_params(ba_engine *e, SsParams &S) {
   }
 }
 
+static const char *const AUTOAR_FAMILY_REFUSAL =
+    "the spike-and-slab autoregression is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)";
+
+// the list's spike-and-slab autoregressions (false: it has none)
+static bool fill_ar_spike_params(ba_engine *e, ArSpikeParams &U) {
+  U = ArSpikeParams{};
+  if (!e->ssm_set) return false;
+  for (int b = 0; b < e->ssg.nblocks; ++b)
+    if (e->ssg.blk[b].ar_spike) U.block[U.nspike++] = b;
+  U.prior = reinterpret_cast<const ArSpikePrior *>(e->dar_spike_prior.ptr);
+  U.gamma = reinterpret_cast<uint8_t *>(e->dar_gamma.ptr);
+  return U.nspike > 0;
+}
+
 static const char *const SLT_FAMILY_REFUSAL =
     "the Student local linear trend is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)";
 
@@ -144,6 +166,13 @@ static void fill_slt_params(ba_engine *e, SltParams &U) {
 // the state half of a state-space sweep: the structural kernel when a trend /
 // seasonal specification is set, the local-level kernel otherwise
 static hipError_t launch_state_kernel(ba_engine *e, const SsParams &S, int draw) {
+  ArSpikeParams V;
+  if (draw && fill_ar_spike_params(e, V)) {
+    // the spike-and-slab autoregressions' samplers, ahead of the state kernel (which draws the
+    // other state models' at its head and passes these by)
+    hipError_t err = launch_ar_spike(e->stream, S, V);
+    if (err != hipSuccess) return err;
+  }
   if (e->ssm_set && e->ssg.student_block) {
     // a Student local linear trend: its sampler with the other state models' (they are drawn at the
     // head of the state kernel, every one from its own stream), and observe_state -- the new weights
@@ -299,6 +328,7 @@ static hipError_t ss_la_record(ba_engine *e, int slot, int round) {
 // SsLa::snap_pos).  ss_la_alloc sizes the two buffers by a pass over it, ss_la_copy walks
 // them by the same pass (a field whose live array is not allocated keeps its place).
 //   level (sigsq, n, sumsq) | xty | yty | nobs [| state models: sigsq, n, ss | phi | ar suf]
+//   positions: level | state [| state models' | the autoregressions' inclusion indicators]
 template <class F>
 static int ss_snap_fields(const ba_engine *e, F f) {
   const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p;
@@ -324,6 +354,8 @@ static int ss_snap_fields(const ba_engine *e, F f) {
   field(e->dpos_level.ptr, C);
   field(e->dpos_state.ptr, C);
   if (e->ssm_set) field(e->dpos_var.ptr, C * SSG_MAX_VAR);
+  // (the spike-and-slab autoregressions' inclusion indicators: bytes, held and copied as words)
+  if (e->ssm_set) field(e->dar_gamma.ptr, ssg_has_ar_spike(e->ssg) ? C * SSG_MAX_AR * AR_MAX / 8 : 0);
   HIP_TRY(ss_snapshot);
   return BA_OK;
 }
@@ -536,6 +568,7 @@ static int ss_prepare(ba_engine *e, DataKind kind = DATA_STATE_SPACE) {
   if (!e->ss_level_set && !e->ssm_set)
     return fail(BA_E_STATE, "call ba_ss_set_local_level or ba_ss_set_structural first");
   if (kind != DATA_STATE_SPACE && e->ssm_set && e->ssg.student_block) return fail(BA_E_STATE, SLT_FAMILY_REFUSAL);
+  if (kind != DATA_STATE_SPACE && e->ssm_set && ssg_has_ar_spike(e->ssg)) return fail(BA_E_STATE, AUTOAR_FAMILY_REFUSAL);
   rc = upload_shared(e);
   if (rc) return rc;
   rc = alloc_chain_state(e);
@@ -600,6 +633,25 @@ static int ss_prepare(ba_engine *e, DataKind kind = DATA_STATE_SPACE) {
             for (int i = 0; i < AR_MAX; ++i) ph[(c * SSG_MAX_AR + a) * AR_MAX + i] = e->ssg_initial_phi[a][i];
         HIP_TRY(hipMemcpy(e->dar_phi.ptr, ph.data(), ph.size() * 8, hipMemcpyHostToDevice));
         HIP_TRY(hipMemsetAsync(e->dar_suf.ptr, 0, C * SSG_MAX_AR * AR_SUF_STRIDE * 8, s));
+      }
+      e->dar_gamma.release();
+      {
+        // ArModel(lags) includes every lag (add_all), whatever the initial coefficients are
+        std::vector<uint8_t> g(C * SSG_MAX_AR * AR_MAX, 0);
+        bool any = false;
+        for (int b = 0; b < e->ssg.nblocks; ++b) {
+          const SsgBlock &k = e->ssg.blk[b];
+          if (!k.ar_spike) continue;
+          any = true;
+          for (size_t c = 0; c < C; ++c)
+            for (int i = 0; i < k.lags; ++i) g[(c * SSG_MAX_AR + k.ar_index) * AR_MAX + i] = 1;
+        }
+        if (any) {
+          HIP_TRY(e->dar_gamma.resize(g.size() / 8));
+          HIP_TRY(hipMemcpy(e->dar_gamma.ptr, g.data(), g.size(), hipMemcpyHostToDevice));
+          HIP_TRY(e->dar_spike_prior.resize(sizeof(e->ar_spike_prior)));
+          HIP_TRY(hipMemcpy(e->dar_spike_prior.ptr, e->ar_spike_prior, sizeof(e->ar_spike_prior), hipMemcpyHostToDevice));
+        }
       }
       if (e->ssg.student_block) {
         // a new StudentLocalLinearTrendStateModel: weights 1, no residuals, empty statistics
@@ -778,6 +830,8 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
     return fail(BA_E_INVALID, "null argument");
   if (q.nblocks >= SSG_MAX_BLOCKS) return fail(BA_E_INVALID, "more than 8 state models");
   const bool is_student = kind == SSG_STUDENT_TREND;
+  const bool is_autoar = kind == SSG_AUTO_AR;
+  if (is_autoar) kind = SSG_AR;   // (stored as an autoregression with SsgBlock::ar_spike set)
   SsgBlock k{};
   k.kind = kind;
   k.nvar = 1;
@@ -861,9 +915,54 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
       k.lags = iparams[0];
       k.dim = k.lags;
       k.ar_index = q.nar;
+      if (is_autoar) {
+        // ArStateModel + ArSpikeSlabSampler: iparams = {lags, truncate, max_flips, allow_model_selection};
+        // initial_phi = {coefficients, slab mean, inclusion probabilities (lags each), slab precision (lags x lags)}
+        if (!initial_phi) return fail(BA_E_INVALID, "null argument");
+        if (e->data_kind == DATA_SS_STUDENT || e->data_kind == DATA_SS_POISSON || e->data_kind == DATA_SS_LOGIT)
+          return fail(BA_E_STATE, AUTOAR_FAMILY_REFUSAL);
+        const int L = k.lags;
+        const double *mu = initial_phi + L, *pi = initial_phi + 2 * L, *om = initial_phi + 3 * L;
+        ArSpikePrior R{};
+        for (int i = 0; i < L; ++i) {
+          if (!std::isfinite(mu[i])) return fail(BA_E_INVALID, "the slab's mean must be finite");
+          if (!(pi[i] >= 0.0 && pi[i] <= 1.0)) return fail(BA_E_INVALID, "prior inclusion probabilities must lie in [0, 1]");
+          R.mu[i] = mu[i];
+          R.pi[i] = pi[i];
+          R.log_pi[i] = std::log(pi[i]);
+          R.log_1mpi[i] = std::log(1 - pi[i]);
+        }
+        double ch[AR_MAX][AR_MAX] = {};
+        for (int i = 0; i < L; ++i)
+          for (int j = 0; j < L; ++j) {
+            const double a = om[(size_t)j * L + i], b = om[(size_t)i * L + j];
+            if (!std::isfinite(a) || !(std::fabs(a - b) <= 1e-12 * (std::fabs(a) + std::fabs(b))))
+              return fail(BA_E_INVALID, "the slab's precision must be symmetric positive definite");
+            R.siginv[i * AR_MAX + j] = a;
+          }
+        for (int j = 0; j < L; ++j) {
+          for (int i = j; i < L; ++i) {
+            double sacc = R.siginv[i * AR_MAX + j];
+            for (int t = 0; t < j; ++t) sacc -= ch[i][t] * ch[j][t];
+            if (i == j) {
+              if (!(sacc > 0.0)) return fail(BA_E_INVALID, "the slab's precision must be symmetric positive definite");
+              ch[j][j] = std::sqrt(sacc);
+            } else {
+              ch[i][j] = sacc / ch[j][j];
+            }
+          }
+        }
+        R.truncate = iparams[1] != 0;
+        R.max_flips = iparams[2];
+        R.select = iparams[3] != 0;
+        if (R.truncate && !ar_stationary_host(initial_phi, L))
+          return fail(BA_E_INVALID, "the initial autoregression coefficients are not stationary");
+        e->ar_spike_prior[k.ar_index] = R;
+        k.ar_spike = 1;
+      }
       break;
     default:
-      return fail(BA_E_INVALID, "state model kind must be 1 (local level), 2 (local linear trend), 3 (seasonal), 4 (autoregression), 5 (static intercept), 6 (trig), 7 (semilocal linear trend) or 8 (Student local linear trend)");
+      return fail(BA_E_INVALID, "state model kind must be 1 (local level), 2 (local linear trend), 3 (seasonal), 4 (autoregression), 5 (static intercept), 6 (trig), 7 (semilocal linear trend), 8 (Student local linear trend) or 9 (spike-and-slab autoregression)");
   }
   const int nslot = is_static ? 1 : k.nvar;   // variance slots the block takes
   if (q.m + k.dim > SSG_MAX_STATE) return fail(BA_E_INVALID, "state dimension exceeds 64");
@@ -881,7 +980,7 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
                     (kind == SSG_SEMILOCAL && i == 2);   // (the slope's long-run mean: a parameter, variance 0 whatever is passed)
     if (!ok) return fail(BA_E_INVALID, "initial state variances must be positive");
   }
-  if (kind == SSG_AR && initial_phi && !ar_stationary_host(initial_phi, k.lags))
+  if (kind == SSG_AR && !is_autoar && initial_phi && !ar_stationary_host(initial_phi, k.lags))
     return fail(BA_E_INVALID, "the initial autoregression coefficients are not stationary");
   k.first = q.m;
   k.var0 = q.nvar;
@@ -1274,6 +1373,37 @@ int ba_ss_trend_get_weight_suf(ba_engine *e, int64_t chain, double *out) {
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));
   HIP_TRY(hipMemcpy(out, e->dslt_wsuf.ptr + (size_t)chain * 6, 6 * 8, hipMemcpyDeviceToHost));
+  return BA_OK;
+}
+
+// the ArSpikeSlabSampler::draw() of every spike-and-slab autoregression alone
+int ba_ss_autoar_draw_parameters(ba_engine *e) {
+  ENGINE_PROLOGUE(e);
+  e->table_ok = false;
+  if (e->data_kind != DATA_STATE_SPACE) return fail(BA_E_STATE, set_data_first(DATA_STATE_SPACE));
+  ArSpikeParams V;
+  if (!fill_ar_spike_params(e, V)) return fail(BA_E_STATE, "the list of state models holds no spike-and-slab autoregression");
+  int rc = ss_prepare(e);
+  if (rc) return rc;
+  SsParams S;
+  fill_ss_params(e, S);
+  fill_ar_spike_params(e, V);
+  HIP_TRY(launch_ar_spike(e->stream, S, V));
+  return BA_OK;
+}
+
+int ba_ss_get_ar_inclusion(ba_engine *e, int64_t chain, int32_t block, uint8_t *gamma) {
+  ENGINE_PROLOGUE(e);   // (under a look-ahead: the chains back at the draw being served)
+  if (!gamma) return fail(BA_E_INVALID, "null argument");
+  if (!ss_kind(e->data_kind) || !e->ssm_set || e->dssm_work.count == 0)
+    return fail(BA_E_STATE, "no structural state-space run yet");
+  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  if (block < 0 || block >= e->ssg.nblocks) return fail(BA_E_INVALID, "state model index out of range");
+  const SsgBlock &k = e->ssg.blk[block];
+  if (!k.ar_spike || e->dar_gamma.count == 0) return fail(BA_E_INVALID, "not a spike-and-slab autoregression state model");
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(gamma, reinterpret_cast<const uint8_t *>(e->dar_gamma.ptr) + ((size_t)chain * SSG_MAX_AR + k.ar_index) * AR_MAX,
+                    (size_t)k.lags, hipMemcpyDeviceToHost));
   return BA_OK;
 }
 

@@ -29,7 +29,13 @@ enum { SSG_LOCAL_LEVEL = 1, SSG_LOCAL_LINEAR_TREND = 2, SSG_SEASONAL = 3, SSG_AR
        // errors have the per-step variances sigma^2 / w_t.  Stored as SSG_LOCAL_LINEAR_TREND --
        // SsgSpec::student_block says which block it is -- and served by the QT instances of the
        // general kernel and the two kernels of slt_kernel.hip
-       SSG_STUDENT_TREND = 8 };
+       SSG_STUDENT_TREND = 8,
+       // ArStateModel with an ArSpikeSlabSampler (bsts AddAutoAr; the C-ABI's number): stored as SSG_AR
+       // with SsgBlock::ar_spike set -- an autoregression whose excluded coefficients are 0; its sampler
+       // is ar_spike_kernel.hip's, the state kernel passes it by
+       SSG_AUTO_AR = 9 };
+// ar_spike_kernel's own chain status: a coefficient or variance draw that is not finite
+enum { AR_SPIKE_BAD_DRAW = 14 };
 // the Student trend's streams: its sampler's four draws (read in sequence) and the weights' slots
 enum : uint32_t { SLT_PARAM_STREAM = 160u, SLT_WEIGHT_STREAM = 161u };
 enum { SLT_WEIGHT_STRIDE = 256, SLT_BLOCK = 256 };
@@ -48,6 +54,7 @@ struct SsgBlock {
   int32_t nfreq;       // trig: frequencies (dim = 2 nfreq)
   int32_t err0;        // index of the block's first state-error row (a trig block has dim of them, a trend two, the others one)
   int32_t sl_truncate, sl_positive;   // semilocal: NonzeroMeanAr1Sampler::force_stationary / force_ar1_positive
+  int32_t ar_spike;    // autoregression: its sampler is the ArSpikeSlabSampler of ar_spike_kernel.hip (0: ArPosteriorSampler, in the state kernel)
 };
 // the specification, in device memory (read through the scalar cache)
 struct SsgSpec {
@@ -168,6 +175,25 @@ struct SltParams {
   uint64_t *count;    // chains: state draws observed so far (the s of the weights' slots)
   int32_t nu_kind[2]; // the nu priors: STUDENT_NU_UNIFORM (a, b) / STUDENT_NU_GAMMA (a, b)
   double nu_a[2], nu_b[2];
+};
+
+// The spike-and-slab autoregressions of a list (ar_spike_kernel.hip).  The prior of the block in
+// autoregression slot a: the slab N(mu, siginv^-1) (siginv full storage at leading dimension AR_MAX),
+// the spike's inclusion probabilities with their logs (VariableSelectionPrior), the sampler's flags.
+struct ArSpikePrior {
+  double mu[AR_MAX];
+  double siginv[AR_MAX * AR_MAX];
+  double pi[AR_MAX], log_pi[AR_MAX], log_1mpi[AR_MAX];
+  int32_t truncate;    // accept stationary coefficients only
+  int32_t max_flips;   // <= 0: every lag is tried in a sweep
+  int32_t select;      // 0: the indicators are not drawn (allow_model_selection(false))
+  int32_t pad;
+};
+struct ArSpikeParams {
+  const ArSpikePrior *prior;   // device, SSG_MAX_AR entries (by autoregression slot)
+  uint8_t *gamma;              // chains x SSG_MAX_AR x AR_MAX: the inclusion indicators
+  int32_t nspike;              // such blocks in the list
+  int32_t block[SSG_MAX_AR];   // ... and which they are
 };
 
 // The round kernel (ss_round_kernel.hip): every chain's workgroup loops over the rounds of a

@@ -35,6 +35,7 @@ enum KernelClass {
   KT_SS_LOGIT,         // logit_impute_kernel<true> / latent_ss_h_kernel / latent_ss_suf_kernel (bsts family = logit)
   KT_SS_STUDENT_TREND, // slt_params_kernel / slt_weights_kernel (the Student local linear trend state model)
   KT_SS_FILTER,        // ss_filter_kernel (ba_ss_prediction_errors: the forward-only filter of the chains' current draw)
+  KT_SS_AUTOAR,        // ar_spike_kernel (the spike-and-slab autoregression state model's sampler)
   KT_CLASSES
 };
 

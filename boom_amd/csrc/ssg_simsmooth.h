@@ -218,7 +218,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
     if (wave == 0) {
       double ph = (lane < L) ? gphi[lane] : 0.0;
       double sig2a = M.var_sigsq[at];
-      if (draw_variances) {
+      // (a spike-and-slab autoregression was drawn by ar_spike_kernel, ahead of this launch)
+      if (draw_variances && !K.ar_spike) {
         SeqRng rng{PhiloxKey{P.seed_lo, P.seed_hi, gchain, (uint32_t)K.sid[0]}, M.pos_var[at]};
         const double *suf = M.ar_suf + ((size_t)chain * SSG_MAX_AR + K.ar_index) * AR_SUF_STRIDE;
         const int st = ar_draw(s_ar, suf, L, Q.prior_df[vi], Q.prior_ss[vi], Q.sigma_max[vi], rng, ph, sig2a, lane);

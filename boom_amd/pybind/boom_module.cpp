@@ -375,6 +375,17 @@ PYBIND11_MODULE(_boom, boom) {
       .def("set_sigsq", &ArStateModel::set_sigsq)
       .def("set_initial_state_mean", [](ArStateModel &m, const NpArray &v) { m.set_initial_state_mean(vector_from(v)); })
       .def("set_initial_state_variance", &ArStateModel::set_initial_state_variance)
+      .def("set_spike_slab_prior",
+           [](ArStateModel &m, const NpArray &mu, const NpArray &siginv, const NpArray &pi, double df, double sigma_guess,
+              double sigma_upper_limit, bool truncate, int max_flips) {
+             m.set_spike_slab_prior(vector_from(mu), matrix_from(siginv), vector_from(pi), df, sigma_guess,
+                                    sigma_upper_limit, truncate, max_flips);
+           },
+           py::arg("mu"), py::arg("siginv"), py::arg("pi"), py::arg("df"), py::arg("sigma_guess"),
+           py::arg("sigma_upper_limit") = std::numeric_limits<double>::infinity(), py::arg("truncate") = true,
+           py::arg("max_flips") = -1,
+           "bsts AddAutoAr: ArSpikeSlabSampler(model, MvnModel(mu, siginv), VariableSelectionPrior(pi), "
+           "ChisqModel(df, sigma_guess), truncate) in place of the ArPosteriorSampler")
       .def("set_prior", &ArStateModel::set_prior, py::arg("df"), py::arg("sigma_guess"),
            py::arg("sigma_upper_limit") = std::numeric_limits<double>::infinity(),
            "ArPosteriorSampler(model, ChisqModel(df, sigma_guess)) + set_sigma_upper_limit");
@@ -468,6 +479,14 @@ PYBIND11_MODULE(_boom, boom) {
            py::arg("chain") = 0, py::arg("which") = 0,
            "the coefficients of the which-th ArStateModel in one chain's current draw")
       .def("ar_sigsq", &StateSpaceRegressionModel::ar_sigsq, py::arg("chain") = 0, py::arg("which") = 0)
+      .def("ar_inclusion", [](const StateSpaceRegressionModel &m, int chain, int which) {
+             const std::vector<bool> g = m.ar_inclusion(chain, which);
+             py::array_t<bool> out((py::ssize_t)g.size());
+             auto o = out.mutable_unchecked<1>();
+             for (size_t i = 0; i < g.size(); ++i) o(i) = g[i];
+             return out;
+           }, py::arg("chain") = 0, py::arg("which") = 0,
+           "the inclusion indicators of the which-th ArStateModel (ArSpikeSlabSampler: set_spike_slab_prior) in one chain's current draw")
       .def("set_method", [](StateSpaceRegressionModel &m, const Ptr<PosteriorSampler> &s) { m.set_method(s); })
       .def("sample_posterior", &StateSpaceRegressionModel::sample_posterior)
       .def("state", [](const StateSpaceRegressionModel &m, int chain) {

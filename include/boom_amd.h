@@ -606,6 +606,22 @@ int ba_ss_set_local_level(ba_engine *e, double level_df,
  *           implemented") and a look-ahead above 1 (ba_ss_set_lookahead, ba_ss_draw_next: the
  *           snapshots do not carry the weights) are refused.  A drawn weight that is not finite
  *           and positive stops the chain with status 13 (BA_E_INVALID).                     2
+ *   kind 9  ArStateModel with an ArSpikeSlabSampler (bsts AddAutoAr; Models/TimeSeries/
+ *           PosteriorSamplers/ArSpikeSlabSampler.cpp): an autoregression (kind 4's state and
+ *           transition) whose coefficients have a spike-and-slab prior -- excluded lags are exactly 0.
+ *           iparams = {lags <= 16, truncate (accept stationary draws only), max_flips (<= 0: no
+ *           limit), allow_model_selection}.  initial_phi holds 3 lags + lags^2 numbers: the initial
+ *           coefficients (stationary when truncate is on), the slab's mean, the prior inclusion
+ *           probabilities in [0, 1], the slab's precision (lags x lags, column-major, symmetric
+ *           positive definite).  The model starts with every lag included.  Takes one of the 4
+ *           autoregression slots and is a member of the autoregression family: its sampler
+ *           (indicators: the shuffle's random_int, one uniform per flip; up to 100 coefficient
+ *           proposals of n normals each, then draw_phi_univariate; the sigma draw) reads the
+ *           family's sampler id in sequence.  ba_ss_get_state_model / ba_ss_get_ar / ba_ss_forecast /
+ *           ba_ss_prediction_errors serve it as they serve kind 4; ba_ss_get_ar_inclusion gives the
+ *           indicators.  Refused: the Student-t / Poisson / logit observation families.  Chain
+ *           status 3: no legal configuration; 1: the coefficient draw's precision did not
+ *           factor; 14 (BA_E_INVALID): a draw that is not finite.                            1
  * iparams is ignored for kinds 1, 2 and 5 (may be NULL).  The var_* arrays hold one entry
  * per variance parameter of the model (two for kinds 2 and 7: level, slope; one otherwise):
  * ChisqModel(df, sigma_guess) prior, sigma upper limit (infinity: none), initial sigma.
@@ -742,6 +758,13 @@ int ba_ss_trend_get_weights(ba_engine *e, int64_t chain, double *level_w, double
 int ba_ss_trend_set_weights(ba_engine *e, int64_t chain, const double *level_w, const double *slope_w);
 int ba_ss_trend_get_weight_suf(ba_engine *e, int64_t chain, double *out);
 int ba_ss_trend_draw_parameters(ba_engine *e);
+/* The spike-and-slab autoregressions (kind 9 above) of the list of state models.
+ * ba_ss_autoar_draw_parameters: the ArSpikeSlabSampler::draw() of all such blocks alone, on every
+ * chain (as ba_ss_trend_draw_parameters is for kind 8).  ba_ss_get_ar_inclusion: the live inclusion
+ * indicators of state model `block` in one chain, `lags` bytes; under a look-ahead the chains are
+ * first put back at the draw being served. */
+int ba_ss_autoar_draw_parameters(ba_engine *e);
+int ba_ss_get_ar_inclusion(ba_engine *e, int64_t chain, int32_t block, uint8_t *gamma);
 
 /* ---- bsts(family = "student"): StateSpaceStudentRegressionModel with
  * StateSpaceStudentPosteriorSampler (Models/StateSpace/StateSpaceStudentRegressionModel.cpp,

@@ -443,9 +443,26 @@ class ArStateModel {
   void set_prior(double df, double sigma_guess, double sigma_upper_limit = infinity()) {
     df_ = df; guess_ = sigma_guess; upper_ = sigma_upper_limit;
   }
+  // bsts AddAutoAr: an ArSpikeSlabSampler(model, MvnModel(mu, siginv) slab, VariableSelectionPrior(pi)
+  // spike, ChisqModel(df, sigma_guess), truncate) [+ set_sigma_upper_limit, limit_model_selection(max_flips)]
+  // in place of the ArPosteriorSampler: state model kind 9, every lag included at the start
+  void set_spike_slab_prior(const Vector &mu, const SpdMatrix &siginv, const Vector &pi, double df, double sigma_guess,
+                            double sigma_upper_limit = infinity(), bool truncate = true, int max_flips = -1) {
+    if ((int)mu.size() != lags_ || siginv.nrow() != lags_ || (int)pi.size() != lags_)
+      report_error("The spike and slab prior does not match the number of lags in ArStateModel.");
+    df_ = df; guess_ = sigma_guess; upper_ = sigma_upper_limit;
+    slab_mu_ = mu; slab_siginv_ = siginv; spike_pi_ = pi;
+    truncate_ = truncate; max_flips_ = max_flips;
+    spike_slab_ = true;
+  }
+  bool spike_slab() const { return spike_slab_; }
   int lags_;
   Vector phi_, a0_, P0_;
   double sigma_ = 1.0, df_ = 1.0, guess_ = 1.0, upper_ = infinity();
+  bool spike_slab_ = false, truncate_ = true;
+  int max_flips_ = -1;
+  Vector slab_mu_, spike_pi_;
+  SpdMatrix slab_siginv_;
 };
 
 // StaticInterceptStateModel (StateModels/StaticInterceptStateModel.hpp:35-131): one component,
@@ -622,6 +639,18 @@ class StateSpaceRegressionModel : public Model {
           eng_->check(ba_ss_add_state_model(h, 6, ip, &s.df_, &s.guess_, &s.upper_, &s.sigma_, s.rotations_.data(), s.a0_.data(), s.P0_.data()));
         } else {
           const ArStateModel &s = *e.ar;
+          if (s.spike_slab_) {
+            // kind 9: initial_phi = coefficients | slab mean | inclusion probabilities | slab precision (column-major)
+            const int32_t ip9[4] = {s.lags_, s.truncate_ ? 1 : 0, s.max_flips_, 1};
+            std::vector<double> ph;
+            for (int i = 0; i < s.lags_; ++i) ph.push_back(s.phi_[i]);
+            for (int i = 0; i < s.lags_; ++i) ph.push_back(s.slab_mu_[i]);
+            for (int i = 0; i < s.lags_; ++i) ph.push_back(s.spike_pi_[i]);
+            for (int j = 0; j < s.lags_; ++j)
+              for (int i = 0; i < s.lags_; ++i) ph.push_back(s.slab_siginv_(i, j));
+            eng_->check(ba_ss_add_state_model(h, 9, ip9, &s.df_, &s.guess_, &s.upper_, &s.sigma_, ph.data(), s.a0_.data(), s.P0_.data()));
+            continue;
+          }
           const int32_t ip[3] = {s.lags_, 0, 0};
           eng_->check(ba_ss_add_state_model(h, 4, ip, &s.df_, &s.guess_, &s.upper_, &s.sigma_, s.phi_.data(), s.a0_.data(), s.P0_.data()));
         }
@@ -635,6 +664,13 @@ class StateSpaceRegressionModel : public Model {
     Vector v(models_[b].ar->lags_);
     eng_->check(ba_ss_get_state_model(eng_->get(), chain, b, nullptr, nullptr, nullptr, v.data(), nullptr, nullptr, nullptr, nullptr));
     return v;
+  }
+  // the inclusion indicators of the `which`-th ArStateModel (one with set_spike_slab_prior) in one chain
+  std::vector<bool> ar_inclusion(int chain = 0, int which = 0) const {
+    const int b = ar_block(which);
+    std::vector<uint8_t> g(models_[b].ar->lags_);
+    eng_->check(ba_ss_get_ar_inclusion(eng_->get(), chain, b, g.data()));
+    return std::vector<bool>(g.begin(), g.end());
   }
   double ar_sigsq(int chain = 0, int which = 0) const {
     double s2;
