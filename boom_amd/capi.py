@@ -185,6 +185,8 @@ SIGNATURES = {
     "ba_ss_trend_draw_parameters": (C.c_int, [C.c_void_p]),
     "ba_ss_autoar_draw_parameters": (C.c_int, [C.c_void_p]),
     "ba_ss_get_ar_inclusion": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_uint8)]),
+    "ba_ss_set_holiday_calendar": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int64]),
+    "ba_ss_get_holiday_calendar": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "ba_ss_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
     "ba_ss_prediction_errors": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp]),
     "ba_ss_student_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
@@ -835,7 +837,8 @@ class Engine:
         (1 local level, 2 local linear trend, 3 seasonal, 4 autoregression, 5 static intercept,
         6 trig, 7 semilocal linear trend, 8 Student local linear trend: nu_priors = ((kind, a, b) of
         level and slope), initial_nu = (level, slope), 9 spike-and-slab autoregression: lags, initial_phi,
-        slab_mean, slab_precision, inclusion_probabilities, truncate, max_flips, allow_model_selection), nseasons, duration, t0, lags, df, sigma_guess, sigma_upper_limit, initial_sigma
+        slab_mean, slab_precision, inclusion_probabilities, truncate, max_flips, allow_model_selection,
+        10 random-walk holiday: width and, optionally, calendar -- ss_set_holiday_calendar's positions), nseasons, duration, t0, lags, df, sigma_guess, sigma_upper_limit, initial_sigma
         (one entry per variance parameter; none for kind 5), initial_phi, rotations (kind 6: the
         (cos, sin) pairs of the transition matrix), a0, P0 (tests/cases.py: general_spec)"""
         self._check(self.lib.ba_ss_clear_state_models(self._h))
@@ -858,6 +861,8 @@ class Engine:
                     np.asarray(b["slab_precision"], dtype=np.float64).ravel(order="F")]))
             elif kind == 6:
                 ip[0] = len(b["rotations"]) // 2
+            elif kind == 10:
+                ip[0] = b["width"]
             elif kind == 7:
                 ip[0], ip[1] = int(b.get("force_stationary", 1)), int(b.get("force_positive", 0))
             arrs = [np.ascontiguousarray(b[k], dtype=np.float64) for k in
@@ -876,6 +881,8 @@ class Engine:
                 _p(ph) if (kind in (4, 6, 7, 8, 9) and ph.size) else None, _p(a0), _p(p0)))
             self._blocks.append(dict(kind=kind, nvar=2 if kind in (2, 7, 8) else (0 if kind == 5 else 1),
                                      lags=int(ip[0]) if kind in (4, 9) else 0))
+            if kind == 10 and b.get("calendar") is not None:
+                self.ss_set_holiday_calendar(len(self._blocks) - 1, b["calendar"])
         m, nb = C.c_int32(), C.c_int32()
         self._check(self.lib.ba_ss_state_dimension(self._h, C.byref(m), C.byref(nb)))
         self._ssm_dim = m.value
@@ -1002,6 +1009,22 @@ class Engine:
         g = np.zeros(max(self._blocks[block]["lags"], 1), np.uint8)
         self._check(self.lib.ba_ss_get_ar_inclusion(self._h, chain, block, g.ctypes.data_as(C.POINTER(C.c_uint8))))
         return g[:self._blocks[block]["lags"]]
+
+    def ss_set_holiday_calendar(self, block, positions):
+        """a random-walk holiday's calendar (state model `block`): entry t is -1 (inactive) or the
+        position of time t in the holiday's window, in [0, width); at least T entries, those past T
+        serve forecasts"""
+        pos = np.ascontiguousarray(positions, dtype=np.int32)
+        self._check(self.lib.ba_ss_set_holiday_calendar(self._h, block, pos.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                        pos.size))
+
+    def ss_get_holiday_calendar(self, block):
+        n = C.c_int64()
+        self._check(self.lib.ba_ss_get_holiday_calendar(self._h, block, None, C.byref(n)))
+        pos = np.zeros(max(n.value, 1), np.int32)
+        self._check(self.lib.ba_ss_get_holiday_calendar(self._h, block, pos.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                        C.byref(n)))
+        return pos[:n.value]
 
     def ss_forecast(self, newX):
         """one predictive draw of the next len(newX) observations per chain"""

@@ -448,6 +448,12 @@ struct ba_engine {
   double slt_nu_a[2] = {1.0, 1.0}, slt_nu_b[2] = {500.0, 500.0}, slt_initial_nu[2] = {10.0, 10.0};
   DevBuf<double> dslt_w, dslt_res, dslt_nu, dslt_wsuf;
   DevBuf<uint64_t> dslt_pos, dslt_count;
+  // RandomWalkHolidayStateModel (SsgBlock::holiday): every such block's calendar as the caller gave it
+  // (entry t: -1 or the position at time t; empty: not set yet), and the list's packed table on the
+  // device (SsParams::cal; hol_cal_count entries -- the shortest calendar's --, 0: to be packed again)
+  std::vector<int32_t> hol_calendar[SSG_MAX_BLOCKS];
+  DevBuf<uint64_t> dhol_cal;
+  int64_t hol_cal_count = 0;
   // ba_ss_prediction_errors (ss_filter_kernel.hip): its outputs on the device (errors, forecast
   // variances, log likelihoods, the forecast-variance flag), the local-level path's one-block
   // list, and the stream the filter of a look-ahead's recorded draw runs on beside the batch

@@ -20,6 +20,13 @@ static bool ssg_has_ar_spike(const SsgSpec &q) {
   return false;
 }
 
+// does the list hold a random-walk holiday (the general kernel's HD instances, a calendar per block)?
+static bool ssg_has_holiday(const SsgSpec &q) {
+  for (int i = 0; i < q.nblocks; ++i)
+    if (q.blk[i].holiday) return true;
+  return false;
+}
+
 // does the block list have the shape the template kernel is compiled for?
 // [local level | local linear trend] [seasonal, duration 1] [autoregression], m <= 16
 static void ssg_template_shape(const SsgSpec &q, int32_t *trend, int32_t *nseasons, int32_t *ar_lags) {
@@ -27,6 +34,7 @@ static void ssg_template_shape(const SsgSpec &q, int32_t *trend, int32_t *nseaso
   if (q.nblocks < 1 || q.nblocks > 3 || q.m > 16) return;
   if (q.student_block) return;   // (a Student local linear trend: the general kernel's QT instances)
   if (ssg_has_ar_spike(q)) return;   // (a spike-and-slab autoregression: the general kernel passes its sampler by)
+  if (ssg_has_holiday(q)) return;    // (a random-walk holiday: the general kernel's HD instances)
   for (int i = 0; i < q.nblocks; ++i)
     if (q.blk[i].nvar == 0) return;   // (a static intercept: the general kernel)
   int b = 0, tr = 0, ns = 0, lags = 0;
@@ -129,7 +137,58 @@ static void fill_ss_params(ba_engine *e, SsParams &S) {
       S.qw = e->dslt_w.ptr;
       S.qw_stride = 2 * (int64_t)e->T;
     }
+    if (ssg_has_holiday(e->ssg)) {
+      S.cal = e->dhol_cal.ptr;   // (packed by hol_prepare, which every entry point that launches passes first)
+      S.cal_count = e->hol_cal_count;
+    }
   }
+}
+
+static const char *const HOLIDAY_FAMILY_REFUSAL =
+    "the random-walk holiday is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)";
+static const char *const HOLIDAY_STUDENT_TREND_REFUSAL =
+    "a list that holds both a random-walk holiday and a Student local linear trend is not built";
+
+// The random-walk holidays' calendars: every such block needs one that covers the series and
+// `extra` steps beyond it (a forecast's horizon); the packed table goes to the device when a
+// calendar has changed.  Nothing runs on a default calendar.
+static int hol_prepare(ba_engine *e, int64_t extra = 0) {
+  if (!e->ssm_set || !ssg_has_holiday(e->ssg)) return BA_OK;
+  int64_t count = -1;
+  for (int b = 0; b < e->ssg.nblocks; ++b) {
+    if (!e->ssg.blk[b].holiday) continue;
+    const int64_t n = (int64_t)e->hol_calendar[b].size();
+    char buf[200];
+    if (n == 0) {
+      std::snprintf(buf, sizeof buf, "state model %d is a random-walk holiday without a calendar: call ba_ss_set_holiday_calendar first", b);
+      return fail(BA_E_STATE, buf);
+    }
+    if (n < (int64_t)e->T) {
+      std::snprintf(buf, sizeof buf, "the holiday calendar of state model %d has %lld entries, the series has %d time points",
+                    b, (long long)n, (int)e->T);
+      return fail(BA_E_STATE, buf);
+    }
+    if (n < (int64_t)e->T + extra) {
+      std::snprintf(buf, sizeof buf, "the holiday calendar of state model %d has %lld entries: a forecast of horizon %lld needs %lld (the series' %d and the horizon)",
+                    b, (long long)n, (long long)extra, (long long)((int64_t)e->T + extra), (int)e->T);
+      return fail(BA_E_INVALID, buf);
+    }
+    count = count < 0 ? n : std::min(count, n);
+  }
+  if (e->hol_cal_count == count && e->dhol_cal.count == (size_t)count) return BA_OK;
+  std::vector<uint64_t> packed((size_t)count, (uint64_t)SSG_CAL_NONE);
+  for (int b = 0; b < e->ssg.nblocks; ++b) {
+    if (!e->ssg.blk[b].holiday) continue;
+    for (int64_t t = 0; t < count; ++t) {
+      const int32_t k = e->hol_calendar[b][(size_t)t];
+      if (k >= 0) packed[(size_t)t] = (packed[(size_t)t] & ~(0xffull << (8 * b))) | ((uint64_t)k << (8 * b));
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (nothing in flight reads the table that is replaced)
+  HIP_TRY(e->dhol_cal.resize((size_t)count));
+  HIP_TRY(hipMemcpy(e->dhol_cal.ptr, packed.data(), (size_t)count * 8, hipMemcpyHostToDevice));
+  e->hol_cal_count = count;
+  return BA_OK;
 }
 
 static const char *const AUTOAR_FAMILY_REFUSAL =
@@ -569,6 +628,9 @@ static int ss_prepare(ba_engine *e, DataKind kind = DATA_STATE_SPACE) {
     return fail(BA_E_STATE, "call ba_ss_set_local_level or ba_ss_set_structural first");
   if (kind != DATA_STATE_SPACE && e->ssm_set && e->ssg.student_block) return fail(BA_E_STATE, SLT_FAMILY_REFUSAL);
   if (kind != DATA_STATE_SPACE && e->ssm_set && ssg_has_ar_spike(e->ssg)) return fail(BA_E_STATE, AUTOAR_FAMILY_REFUSAL);
+  if (kind != DATA_STATE_SPACE && e->ssm_set && ssg_has_holiday(e->ssg)) return fail(BA_E_STATE, HOLIDAY_FAMILY_REFUSAL);
+  rc = hol_prepare(e);
+  if (rc) return rc;
   rc = upload_shared(e);
   if (rc) return rc;
   rc = alloc_chain_state(e);
@@ -806,12 +868,19 @@ static int ssg_stream_id(const SsgSpec &q, int kind, int v) {
     for (int i = 0; i < q.nblocks; ++i) occ += q.blk[i].kind == SSG_SEMILOCAL;
     return 14 + 16 * occ;
   }
+  // (a random-walk holiday's sampler: a family of its own, id 8)
+  if (kind == SSG_HOLIDAY) {
+    int occ = 0;
+    for (int i = 0; i < q.nblocks; ++i) occ += q.blk[i].holiday != 0;
+    return 8 + 16 * occ;
+  }
   auto family = [](int k) { return (k == SSG_LOCAL_LINEAR_TREND || k == SSG_SEMILOCAL) ? (int)SSG_LOCAL_LEVEL : k; };
   const int fam = family(kind);
   int occ = 0;
   for (int i = 0; i < q.nblocks; ++i) {
     const int k = q.blk[i].kind;
     if (q.blk[i].nvar == 0) continue;   // (a static intercept has no sampler: it is in no family)
+    if (q.blk[i].holiday) continue;     // (stored as a local level, but not of the level family)
     if (i == q.student_block - 1) continue;   // (a Student trend's sampler reads SLT_PARAM_STREAM: in no family either)
     if (family(k) == fam) ++occ;
   }
@@ -832,6 +901,7 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
   const bool is_student = kind == SSG_STUDENT_TREND;
   const bool is_autoar = kind == SSG_AUTO_AR;
   if (is_autoar) kind = SSG_AR;   // (stored as an autoregression with SsgBlock::ar_spike set)
+  const bool is_holiday = kind == SSG_HOLIDAY;   // (stored as a local level of dimension width with SsgBlock::holiday set)
   SsgBlock k{};
   k.kind = kind;
   k.nvar = 1;
@@ -854,6 +924,19 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
       k.dim = k.nseasons - 1;
       break;
     }
+    case SSG_HOLIDAY:
+      // RandomWalkHolidayStateModel: iparams = {width}, the holiday's maximum window width; its
+      // calendar comes through ba_ss_set_holiday_calendar
+      if (!iparams) return fail(BA_E_INVALID, "null argument");
+      if (iparams[0] < 1 || iparams[0] > SSG_MAX_STATE - 1)
+        return fail(BA_E_INVALID, "a random-walk holiday's width must lie in [1, 63]");
+      if (e->data_kind == DATA_SS_STUDENT || e->data_kind == DATA_SS_POISSON || e->data_kind == DATA_SS_LOGIT)
+        return fail(BA_E_STATE, HOLIDAY_FAMILY_REFUSAL);
+      if (q.student_block) return fail(BA_E_STATE, HOLIDAY_STUDENT_TREND_REFUSAL);
+      k.kind = SSG_LOCAL_LEVEL;
+      k.dim = iparams[0];
+      k.holiday = 1;
+      break;
     case SSG_STATIC_INTERCEPT:
       // StaticInterceptStateModel: T = 1, RQR = 0, nothing to learn and no sampler -- a local
       // level whose variance (a slot of its own, never drawn) is 0
@@ -892,6 +975,7 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
       // the device a local linear trend block (SsgSpec::student_block names it) with weights
       if (!initial_phi) return fail(BA_E_INVALID, "null argument");
       if (q.student_block) return fail(BA_E_INVALID, "at most one Student local linear trend per list of state models");
+      if (ssg_has_holiday(q)) return fail(BA_E_STATE, HOLIDAY_STUDENT_TREND_REFUSAL);
       if (e->data_kind == DATA_SS_STUDENT || e->data_kind == DATA_SS_POISSON || e->data_kind == DATA_SS_LOGIT)
         return fail(BA_E_STATE, SLT_FAMILY_REFUSAL);
       for (int c = 0; c < 2; ++c) {
@@ -962,7 +1046,7 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
       }
       break;
     default:
-      return fail(BA_E_INVALID, "state model kind must be 1 (local level), 2 (local linear trend), 3 (seasonal), 4 (autoregression), 5 (static intercept), 6 (trig), 7 (semilocal linear trend), 8 (Student local linear trend) or 9 (spike-and-slab autoregression)");
+      return fail(BA_E_INVALID, "state model kind must be 1 (local level), 2 (local linear trend), 3 (seasonal), 4 (autoregression), 5 (static intercept), 6 (trig), 7 (semilocal linear trend), 8 (Student local linear trend), 9 (spike-and-slab autoregression) or 10 (random-walk holiday)");
   }
   const int nslot = is_static ? 1 : k.nvar;   // variance slots the block takes
   if (q.m + k.dim > SSG_MAX_STATE) return fail(BA_E_INVALID, "state dimension exceeds 64");
@@ -976,7 +1060,7 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
     // (a multivariate initial state goes through a Cholesky factor in the reference: it
     // needs a positive variance; the local level model alone does not)
     const bool ok = initial_state_variance[i] > 0.0 ||
-                    ((kind == SSG_LOCAL_LEVEL || is_static) && initial_state_variance[i] == 0.0) ||
+                    ((kind == SSG_LOCAL_LEVEL || is_static) && !is_holiday && initial_state_variance[i] == 0.0) ||
                     (kind == SSG_SEMILOCAL && i == 2);   // (the slope's long-run mean: a parameter, variance 0 whatever is passed)
     if (!ok) return fail(BA_E_INVALID, "initial state variances must be positive");
   }
@@ -1021,6 +1105,7 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
     q.P0[k.first + 2] = 0.0;
     q.nar += 1;
   }
+  if (is_holiday) e->hol_calendar[q.nblocks].clear();   // (no calendar yet)
   if (is_student) {
     q.student_block = q.nblocks + 1;
     for (int c = 0; c < 2; ++c) {
@@ -1042,6 +1127,8 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
 }
 static void ssg_clear(ba_engine *e) {
   e->ssg = SsgSpec{};
+  for (int b = 0; b < SSG_MAX_BLOCKS; ++b) e->hol_calendar[b].clear();
+  e->hol_cal_count = 0;
   for (int i = 0; i < 3; ++i) e->ssg_template_var[i] = -1;
   e->ssg_template_ar = -1;
   e->ssm_set = false;
@@ -1090,6 +1177,38 @@ int ba_ss_state_dimension(ba_engine *e, int32_t *state_dimension, int32_t *nbloc
   if (!e) return fail(BA_E_INVALID, "null engine");
   if (state_dimension) *state_dimension = e->ssm_set ? e->ssg.m : (e->ss_level_set ? 1 : 0);
   if (nblocks) *nblocks = e->ssm_set ? e->ssg.nblocks : (e->ss_level_set ? 1 : 0);
+  return BA_OK;
+}
+
+// a random-walk holiday's calendar: entry t is -1 (time t is not in the holiday's window) or the
+// position of time t in the window, in [0, width)
+int ba_ss_set_holiday_calendar(ba_engine *e, int32_t block, const int32_t *position, int64_t count) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!position || count <= 0) return fail(BA_E_INVALID, "bad argument");
+  if (!e->ssm_set || block < 0 || block >= e->ssg.nblocks) return fail(BA_E_INVALID, "state model index out of range");
+  const SsgBlock &k = e->ssg.blk[block];
+  if (!k.holiday) return fail(BA_E_INVALID, "not a random-walk holiday state model");
+  for (int64_t t = 0; t < count; ++t)
+    if (position[t] < -1 || position[t] >= k.dim) {
+      char buf[160];
+      std::snprintf(buf, sizeof buf, "holiday calendar entry %lld is %d: it must be -1 (inactive) or a position in [0, %d)",
+                    (long long)t, (int)position[t], (int)k.dim);
+      return fail(BA_E_INVALID, buf);
+    }
+  e->hol_calendar[block].assign(position, position + count);
+  e->hol_cal_count = 0;   // (packed again by the next call that launches)
+  return BA_OK;
+}
+
+// position == nullptr: the count alone
+int ba_ss_get_holiday_calendar(ba_engine *e, int32_t block, int32_t *position, int64_t *count) {
+  if (!e) return fail(BA_E_INVALID, "null engine");
+  if (!e->ssm_set || block < 0 || block >= e->ssg.nblocks) return fail(BA_E_INVALID, "state model index out of range");
+  if (!e->ssg.blk[block].holiday) return fail(BA_E_INVALID, "not a random-walk holiday state model");
+  const std::vector<int32_t> &c = e->hol_calendar[block];
+  if (count) *count = (int64_t)c.size();
+  if (position && !c.empty()) std::memcpy(position, c.data(), c.size() * sizeof(int32_t));
   return BA_OK;
 }
 
@@ -1714,7 +1833,9 @@ int ba_ss_forecast(ba_engine *e, int32_t horizon, const double *newX, double *ou
   if (!newX || !out || horizon <= 0) return fail(BA_E_INVALID, "bad argument");
   if (e->data_kind != DATA_STATE_SPACE || e->dss_scratch.count == 0 || !e->ss_initialized)
     return fail(BA_E_STATE, "no state draw yet: run ba_ss_sweep or ba_ss_impute_state first");
-  int rc = ba_sync(e);
+  int rc = hol_prepare(e, horizon);   // (a random-walk holiday: the calendar's entries T .. T + horizon - 1)
+  if (rc) return rc;
+  rc = ba_sync(e);
   if (rc) return rc;
   const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p, h = (size_t)horizon;
   DevBuf<double> dnx, dout;
@@ -1788,6 +1909,7 @@ int ba_ss_prediction_errors(ba_engine *e, int64_t chain_first, int64_t chain_cou
       F.qw = e->dslt_w.ptr;   // (a look-ahead above 1 is refused with such a block: always live)
       F.qw_stride = 2 * (int64_t)T;
     }
+    if (ssg_has_holiday(e->ssg)) F.cal = e->dhol_cal.ptr;   // (one table for every draw: the record needs none)
   } else {
     // the local-level path: the same kernel on a one-block list
     SsgSpec one{};

@@ -33,7 +33,17 @@ enum { SSG_LOCAL_LEVEL = 1, SSG_LOCAL_LINEAR_TREND = 2, SSG_SEASONAL = 3, SSG_AR
        // ArStateModel with an ArSpikeSlabSampler (bsts AddAutoAr; the C-ABI's number): stored as SSG_AR
        // with SsgBlock::ar_spike set -- an autoregression whose excluded coefficients are 0; its sampler
        // is ar_spike_kernel.hip's, the state kernel passes it by
-       SSG_AUTO_AR = 9 };
+       SSG_AUTO_AR = 9,
+       // RandomWalkHolidayStateModel (the C-ABI's number): `width` components, T = I; the step into time
+       // t adds N(0, sigma^2) to component k(t) and Z_t = e_k(t) where the block's calendar says t is
+       // active at position k(t), nothing otherwise.  Stored as SSG_LOCAL_LEVEL of dimension width with
+       // SsgBlock::holiday set; the calendars of a list are one packed table (SsParams::cal), and such a
+       // list is served by the HD instances of the general kernel
+       SSG_HOLIDAY = 10 };
+// the packed calendar: entry t holds block b's position at time t in byte b, SSG_CAL_OFF where the
+// block is inactive at t (or is no holiday block)
+enum : uint64_t { SSG_CAL_NONE = 0x8080808080808080ull };
+enum { SSG_CAL_OFF = 0x80 };
 // ar_spike_kernel's own chain status: a coefficient or variance draw that is not finite
 enum { AR_SPIKE_BAD_DRAW = 14 };
 // the Student trend's streams: its sampler's four draws (read in sequence) and the weights' slots
@@ -55,6 +65,7 @@ struct SsgBlock {
   int32_t err0;        // index of the block's first state-error row (a trig block has dim of them, a trend two, the others one)
   int32_t sl_truncate, sl_positive;   // semilocal: NonzeroMeanAr1Sampler::force_stationary / force_ar1_positive
   int32_t ar_spike;    // autoregression: its sampler is the ArSpikeSlabSampler of ar_spike_kernel.hip (0: ArPosteriorSampler, in the state kernel)
+  int32_t holiday;     // local level of dimension dim: a random-walk holiday (SSG_HOLIDAY), its positions in the packed calendar
 };
 // the specification, in device memory (read through the scalar cache)
 struct SsgSpec {
@@ -163,6 +174,10 @@ struct SsParams {
   // (nullptr: no such block).  Read by the QT instances only.
   const double *qw;
   int64_t qw_stride;
+  // the random-walk holidays' packed calendar (SSG_CAL_NONE ...), cal_count >= T entries, one table
+  // for all chains (nullptr: the list holds no such block).  Read by the HD instances and the forecast.
+  const uint64_t *cal;
+  int64_t cal_count;
 };
 
 // The Student local linear trend's own chain state (slt_kernel.hip).  c = 0 the level, 1 the slope.

@@ -180,6 +180,11 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
   bool zsel = false;
   double qdiag = 0.0, seas_var = 0.0, a = 0.0, P0l = 0.0;
   int seas_first = -1, stu = 0;
+  // a random-walk holiday's lanes: Z_t and the entry that gains the variance move with the calendar
+  // (position of the lane's block = byte hsh / 8 of the step's entry; T is the identity)
+  bool hol = false;
+  int hsh = 0, hfirst = 0;
+  double hvar = 0.0;
   for (int b = 0; b < B.nb; ++b) {
     const unsigned d = B.at(b);
     const int kd = SsfBlocks::kind_of(d), f = SsfBlocks::first_of(d), n = SsfBlocks::dim_of(d), v0 = SsfBlocks::var0_of(d);
@@ -193,6 +198,11 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
     else if (kd == SSG_TRIG) qdiag = s_var[v0];
     else if (kd == SSG_AR) qdiag = w == 0 ? s_var[v0] : 0.0;
     else if (kd == SSG_SEASONAL) { if (w == 0) { seas_first = b; seas_var = s_var[v0]; } }
+    if (kd == SSG_LOCAL_LEVEL && Q.blk[b].holiday) {
+      hol = true; hsh = 8 * b; hfirst = f; hvar = s_var[v0];
+      zsel = false;
+      qdiag = 0.0;
+    }
     a = Q.a0[lane];
     // (a semilocal trend's third component IS the slope's long-run mean)
     if (kd == SSG_SEMILOCAL && w == 2) a = s_phi[SsfBlocks::arx_of(d) * AR_MAX + 1];
@@ -216,19 +226,30 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
     double wl_l = 1.0, ws_l = 1.0;
     if (qw && tt < T) { wl_l = qw[tt]; ws_l = qw[(size_t)T + tt]; }
     double v_l = 0.0, F_l = 0.0;
+    // (the calendar's entries t -- Z_t -- and t + 1 -- RQR_t -- of the block's steps, one per lane)
+    unsigned long long cw_l = SSG_CAL_NONE, cn_l = SSG_CAL_NONE;
+    if (P.cal) { if (tt < T) cw_l = P.cal[tt]; if (tt + 1 < T) cn_l = P.cal[tt + 1]; }
     const int ns = T - tb < SSF_WAVE ? T - tb : SSF_WAVE;
     for (int s = 0; s < ns; ++s) {
       const bool obs = ((obsmask >> s) & 1ull) != 0;
       double vout = nan, F = nan;
+      unsigned long long zmask_t = zmask;
+      bool hgain = false;   // this lane's diagonal entry gains the holiday's variance at this step
+      if (P.cal) {
+        const unsigned long long cw = __builtin_bit_cast(unsigned long long, ssf_rl(__builtin_bit_cast(double, cw_l), s));
+        const unsigned long long cn = __builtin_bit_cast(unsigned long long, ssf_rl(__builtin_bit_cast(double, cn_l), s));
+        zmask_t |= __ballot(hol && lane == hfirst + (int)((cw >> hsh) & 0xffu));
+        hgain = hol && lane == hfirst + (int)((cn >> hsh) & 0xffu);
+      }
       if (!dead) {
         // PZ, F, v
         double pz = 0.0;
         if (act) {
           const double *prow = s_P + lane * ld;
-          for (unsigned long long zm = zmask; zm; zm &= zm - 1) pz += prow[__builtin_ctzll(zm)];
+          for (unsigned long long zm = zmask_t; zm; zm &= zm - 1) pz += prow[__builtin_ctzll(zm)];
         }
         double za = 0.0, zpz = 0.0;
-        for (unsigned long long zm = zmask; zm; zm &= zm - 1) {
+        for (unsigned long long zm = zmask_t; zm; zm &= zm - 1) {
           const int j = __builtin_ctzll(zm);
           za += ssf_rl(a, j);
           zpz += ssf_rl(pz, j);
@@ -273,6 +294,7 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
             double q = qdiag;
             if (stu) q = qdiag / (stu == 1 ? wl : ws);
             if (seas_first >= 0 && ((mv >> seas_first) & 1u)) q = seas_var;
+            if (hgain) q = hvar;
             if (q != 0.0) s_P[lane * ld + lane] += q;
           }
           ssf_sync();

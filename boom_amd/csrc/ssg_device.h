@@ -29,6 +29,12 @@ __device__ __forceinline__ double rl(double x, int src) {
   const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), src);
   return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
+// a 64-bit word of lane `src` (wave-uniform src)
+__device__ __forceinline__ unsigned long long rlw(unsigned long long u, int src) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, src);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), src);
+  return ((unsigned long long)hi << 32) | lo;
+}
 // sum over the first 16 lanes (the others hold 0), everywhere
 __device__ __forceinline__ double row_total(double x) {
   x += sdpp<0x111, 0xf>(x, 0.0);  // row_shr:1
@@ -337,7 +343,8 @@ __device__ __forceinline__ int semilocal_slope_draw(const double *suf, const dou
 // block with v_readlane -- eight unrolled copies of every per-block code path made a kernel
 // of 60 000 instructions that ran out of the instruction cache).
 struct Blocks {
-  unsigned desc;   // kind (3 bits) | first (7) | dim (7) | index of its first variance parameter (5) | autoregression slot (3)
+  unsigned desc;   // kind (3 bits) | first (7) | dim (7) | index of its first variance parameter (5) | autoregression slot (3) |
+                   // a random-walk holiday (1: set and read by the HD instances of ssg_simsmooth_kernel only)
   unsigned dp;     // seasonal: duration (16 bits) | phase (16)
   unsigned rc;     // seasonal: (index of the step's transition + 1 - phase) mod duration (16 bits: 0 = it moves) |
                    //           the rotating layout's cursor (16): physical slot of the block's first component
@@ -352,6 +359,7 @@ struct Blocks {
   static __device__ __forceinline__ int dim_of(unsigned d) { return (int)((d >> 10) & 127u); }
   static __device__ __forceinline__ int var0_of(unsigned d) { return (int)((d >> 17) & 31u); }
   static __device__ __forceinline__ int arx_of(unsigned d) { return (int)((d >> 22) & 7u); }
+  static __device__ __forceinline__ bool holiday_of(unsigned d) { return ((d >> 25) & 1u) != 0; }
   // block b's words, wave-uniform
   __device__ __forceinline__ unsigned udesc(int b) const { return (unsigned)__builtin_amdgcn_readlane((int)desc, b); }
   __device__ __forceinline__ unsigned urc(int b) const { return (unsigned)__builtin_amdgcn_readlane((int)rc, b); }

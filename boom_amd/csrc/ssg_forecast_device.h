@@ -15,9 +15,12 @@ namespace {
 
 // st <- T_tm st + the state errors of time tm (lanes past the state dimension hold 0);
 // returns Z'st of the new state: the blocks' first components (a trig block: every pair's
-// first), in state order
+// first), in state order.  cal: the packed calendar of the list's random-walk holidays (entries up
+// to tm + 2; nullptr: the list has none).  Such a block's error of time tm lands on its position at
+// time tm + 1 -- drawn only where that time is active, as the reference does -- and the returned
+// Z'st is that of time tm + 2, the time simulate_multiplex_forecast observes the new state at.
 __device__ __forceinline__ double ssg_forecast_step(const SsmParams &M, const SsgSpec &Q, int chain, int lane, int tm,
-                                                    SeqRng &rng, double &st) {
+                                                    SeqRng &rng, double &st, const uint64_t *cal = nullptr) {
   const int m = M.m, nb = M.nblocks;
   double nx = st;
   for (int b = 0; b < nb; ++b) {
@@ -25,7 +28,13 @@ __device__ __forceinline__ double ssg_forecast_step(const SsmParams &M, const Ss
     const int f = K.first, n = K.dim;
     const bool mine = lane >= f && lane < f + n;
     const double *sg = M.var_sigsq + (size_t)chain * SSG_MAX_VAR + K.var0;
-    if (K.kind == SSG_LOCAL_LEVEL) {
+    if (K.kind == SSG_LOCAL_LEVEL && K.holiday) {
+      const int k = cal ? (int)((cal[tm + 1] >> (8 * b)) & 0xffu) : SSG_CAL_OFF;
+      if (!(k & SSG_CAL_OFF)) {
+        const double e0 = d_rnorm(rng, 0.0, sqrt(sg[0]));
+        if (lane == f + k) nx = st + e0;
+      }
+    } else if (K.kind == SSG_LOCAL_LEVEL) {
       const double e0 = d_rnorm(rng, 0.0, sqrt(sg[0]));
       if (lane == f) nx = st + e0;
     } else if (K.kind == SSG_LOCAL_LINEAR_TREND) {
@@ -73,6 +82,11 @@ __device__ __forceinline__ double ssg_forecast_step(const SsmParams &M, const Ss
   double zs = 0.0;
   for (int b = 0; b < nb; ++b) {
     const SsgBlock &K = Q.blk[b];
+    if (K.holiday) {   // (the position Z selects at the new state's time, if that time is active)
+      const int k = cal ? (int)((cal[tm + 2] >> (8 * b)) & 0xffu) : SSG_CAL_OFF;
+      if (!(k & SSG_CAL_OFF)) zs += rl(st, K.first + k);
+      continue;
+    }
     for (int i = 0; i < (K.kind == SSG_TRIG ? K.dim : 1); i += 2) {
       const double zv = rl(st, K.first + i);
       zs = (b == 0 && i == 0) ? zv : zs + zv;

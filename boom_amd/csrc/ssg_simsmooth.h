@@ -65,7 +65,7 @@
 // (this header: the kernel template.  ssm_kernel.hip instantiates the scalar and the H_t instances and
 // holds the launcher and the forecast kernel; ssm_qt_kernel.hip instantiates the Q_t instances -- a
 // file of their own so that the two compile side by side: 24 instances in one file took about 5 min
-// against 3 min 06 s for the 16.)
+// against 3 min 06 s for the 16 -- and ssm_hd_kernel.hip, a third, the holiday instances.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -115,7 +115,18 @@ __host__ __device__ inline int ssg_pass_lds_doubles(int m, int ld, int bl, int n
 // sqrt(w), the reference's form), wave 1's + RQR, the last pass's RQR r_t.  The block's four
 // parameters are drawn by slt_params_kernel before this kernel and its statistics are made by
 // slt_weights_kernel after it: the variance loop and the statistics below pass it by.
-template <bool SMALL, int LDC, bool GLOB, bool HT = false, bool QT = false>
+// HD: the list holds a random-walk holiday (SsgBlock::holiday; bit 25 of Blocks::desc, set below): a
+// block of `width` components whose T is the identity, whose Z_t selects component k(t) and whose state
+// error of the step into t lands on component k(t) -- where the block's calendar says t is active;
+// nothing otherwise.  The calendars are one packed table for all chains (P.cal: byte b of entry t =
+// block b's position at t, or SSG_CAL_OFF).  A time block's entries sit one step per lane beside the
+// observed flags and are read with v_readlane: entry t wherever a step needs Z_t or the error INTO t
+// (wave 0's passes, the statistics), entry t + 1 as well where it needs RQR_t (wave 1's + RQR and the
+// backward pass's error rows) -- both are loaded per lane from the table itself, so a time block's
+// edge is no special case.  The lanes of such a block keep k(t) in LaneInfo::cur, which zsel / zdot read.
+// The block draws ONE state-error normal per step, active or not (an inactive step's is not used): the
+// slot map of the normals stays closed-form.
+template <bool SMALL, int LDC, bool GLOB, bool HT = false, bool QT = false, bool HD = false>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void ssg_simsmooth_kernel(SsParams P, int draw_variances) {
   constexpr int SSG_BATCH = SMALL ? 4 : 8;   // entries of a column / row of P asked of the LDS together
   extern __shared__ __align__(16) unsigned char s_raw[];
@@ -248,7 +259,10 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
   // ---- the block list, the lane's own constants
   Blocks B;
   B.load(Q, nb, lane);
+  if (HD && lane < nb && Q.blk[lane].holiday) B.desc |= 1u << 25;
   LaneInfo LI{-1, 0, 0, 0, 0, 0.0};
+  bool hol_l = false;     // (HD) the lane holds a component of a random-walk holiday
+  int hsh_l = 0;          // ... whose positions are the bits from here of a calendar entry
   int var_l = 0;          // the variance parameter behind this lane's state error
   int erow_l = 0;         // which of the state-error rows this lane's is (the smoothed disturbances' series)
   bool sl_mean_lane = false;   // the lane holds a semilocal trend's third component (the slope's long-run mean)
@@ -268,6 +282,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       const unsigned d = B.udesc(b);
       const int f = Blocks::first_of(d), n = Blocks::dim_of(d), kd = Blocks::kind_of(d), v0 = Blocks::var0_of(d);
       const bool mine = lane >= f && lane < f + n;
+      const bool hol = HD && Blocks::holiday_of(d);
+      if (HD && mine && hol) { hol_l = true; hsh_l = 8 * b; }
       const bool second = (kd == SSG_LOCAL_LINEAR_TREND || kd == SSG_SEMILOCAL) && lane == f + 1;
       const int within = kd == SSG_TRIG ? lane - f : (second ? 1 : 0);   // (a trig block: an error term per component)
       if (mine) {
@@ -288,7 +304,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       eb += kd == SSG_TRIG ? n : ((kd == SSG_LOCAL_LINEAR_TREND || kd == SSG_SEMILOCAL) ? 2 : 1);
       // the initial state's normals: a local level draws rnorm(a0, sd0) (nothing when
       // sd0 == 0), every other model rmvn: one per component
-      if (kd == SSG_LOCAL_LEVEL) {
+      if (kd == SSG_LOCAL_LEVEL && !hol) {   // (a holiday: rmvn_mt, one per component)
         const bool drawn = Q.P0[f] != 0.0;
         if (mine) { ipos_l = ip; init_l = drawn; }
         ip += drawn ? 1 : 0;
@@ -304,7 +320,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       // seasonal: one on the steps into a new season if sigma != 0; autoregression: one, always;
       // trig: rnorm_mt(0, sigma) per component, i.e. dim of them if sigma != 0
       const bool nz = s_sig2[v0] != 0.0;
-      if (kd == SSG_LOCAL_LEVEL) cb += nz ? 1 : 0;
+      if (kd == SSG_LOCAL_LEVEL) cb += (nz || hol) ? 1 : 0;   // (a holiday: one every step, see HD above)
       else if (kd == SSG_LOCAL_LINEAR_TREND) cb += 2;
       else if (kd == SSG_SEMILOCAL) cb += 2;   // (rnorm_mt(0, sigma) for level and slope: both sigmas are positive)
       else if (kd == SSG_AR) cb += 1;
@@ -331,6 +347,10 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
   // (its two variances: what a time block's lanes divide by their steps' weights, once per block)
   const double qsig0 = QT ? s_sig2[Q.blk[qtb].var0] : 0.0, qsig1 = QT ? s_sig2[Q.blk[qtb].var0 + 1] : 0.0;
   const double qsd0 = sqrt(qsig0), qsd1 = sqrt(qsig1);
+
+  // HD: a calendar entry's position for this lane's block (holiday lanes only) / for block b (wave-uniform)
+  auto hpos_l = [&](unsigned long long w) -> int { return (int)((w >> hsh_l) & 0xffu); };
+  auto hpos_b = [](unsigned long long w, int b) -> int { return (int)((w >> (8 * b)) & 0xffu); };
 
   const double H = HT ? 0.0 : P.sigsq[chain], sqrtH = sqrt(H);
   const int dH = HT ? 1 : (sqrtH != 0.0);
@@ -414,27 +434,43 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       if (HT) h_l = lane < nstep ? hser[tt] : 1.0;
       double qa_l = 0.0, qb_l = 0.0;   // (QT: sigma^2 / w of the block's steps, one per lane)
       if (QT) { qa_l = lane < nstep ? qsig0 / qw0[tt] : 0.0; qb_l = lane < nstep ? qsig1 / qw1[tt] : 0.0; }
+      // (HD: the calendar's entries t -- Z_t -- and t + 1 -- RQR_t -- of the block's steps, one per lane)
+      unsigned long long cw_l = SSG_CAL_NONE, cn_l = SSG_CAL_NONE;
+      if (HD) { if (lane < nstep) cw_l = P.cal[tt]; if (lane < nstep && tt + 1 < T) cn_l = P.cal[tt + 1]; }
       double F_l = 1.0;
 #pragma nounroll
       for (int s = 0; s < nstep; ++s) {
         const bool obs = __builtin_amdgcn_readlane(ob_l, s) != 0;
         const unsigned mv = B.moving();
         const double qa = QT ? rl(qa_l, s) : 0.0, qb = QT ? rl(qb_l, s) : 0.0;
+        const unsigned long long cw = HD ? rlw(cw_l, s) : 0ull, cn = HD ? rlw(cn_l, s) : 0ull;
+        if (HD && hol_l) LI.cur = hpos_l(cw);
         // PZ_k = sum over the blocks of P(first of the block, k)  [= P(k, first), P symmetric]
         // (the blocks' rows are asked for together: one LDS round trip, not one per block)
         double PZ = 0.0;
         if (SMALL) {
 #pragma nounroll
           for (int b = 0; b < nb; ++b) {
-            const int zl = Blocks::first_of(B.udesc(b)) + (int)(B.urc(b) >> 16);
+            int zl = Blocks::first_of(B.udesc(b)) + (int)(B.urc(b) >> 16);
+            if (HD && Blocks::holiday_of(B.udesc(b))) {   // (the row Z_t selects, if any)
+              const int k = hpos_b(cw, b);
+              if (k & SSG_CAL_OFF) continue;
+              zl += k;
+            }
             if (mylane) PZ += s_P[zl * ld + lane];
           }
         } else {
           double pz[SSG_MAX_BLOCKS];
 #pragma unroll
           for (int b = 0; b < SSG_MAX_BLOCKS; ++b) {
-            const int zl = Blocks::first_of(B.udesc(b)) + (int)(B.urc(b) >> 16);
-            pz[b] = (b < nb && mylane) ? s_P[zl * ld + lane] : 0.0;
+            int zl = Blocks::first_of(B.udesc(b)) + (int)(B.urc(b) >> 16);
+            bool on = b < nb && mylane;
+            if (HD && Blocks::holiday_of(B.udesc(b))) {
+              const int k = hpos_b(cw, b);
+              on = on && !(k & SSG_CAL_OFF);
+              zl += k & (SSG_CAL_OFF - 1);
+            }
+            pz[b] = on ? s_P[zl * ld + lane] : 0.0;
           }
 #pragma unroll
           for (int b = 0; b < SSG_MAX_BLOCKS; ++b)
@@ -472,7 +508,16 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
           const int f = Blocks::first_of(d), n = Blocks::dim_of(d), kd = Blocks::kind_of(d);
           if (!mylane) continue;
           double *col = s_P + f * ld + lane;
-          if (kd == SSG_LOCAL_LEVEL) {
+          if (HD && Blocks::holiday_of(d)) {
+            // T = I: the rank-one term down the block's part of the column, then + RQR_t: sigma^2 on the
+            // diagonal entry of the component the step into t + 1 lands on (its own lane adds it)
+            if (obs) {
+#pragma nounroll
+              for (int i = 0; i < n; ++i) col[i * ld] -= (s_tv[f + i] * PZ) * Finv;
+            }
+            const int kn = hpos_b(cn, b);
+            if (!(kn & SSG_CAL_OFF) && lane == f + kn) col[kn * ld] += s_sig2[Blocks::var0_of(d)];
+          } else if (kd == SSG_LOCAL_LEVEL) {
             double v = col[0];
             if (obs) v -= (s_tv[f] * PZ) * Finv;
             if (lane == f) v += s_sig2[Blocks::var0_of(d)];   // (+ RQR: this block's T is the identity)
@@ -713,6 +758,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       // StudentLocalLinearTrendStateModel::simulate_state_error's form)
       double sq_l0 = 0.0, sq_l1 = 0.0;
       if (QT) { sq_l0 = (in_l && tt > 0) ? qsd0 / sqrt(qw0[tt - 1]) : 0.0; sq_l1 = (in_l && tt > 0) ? qsd1 / sqrt(qw1[tt - 1]) : 0.0; }
+      // (HD: the calendar's entry t of the block's steps -- the error INTO t and Z_t --, one per lane)
+      unsigned long long cw_l = SSG_CAL_NONE;
+      if (HD && in_l) cw_l = P.cal[tt];
       // the block's normals, in stream order
       const int zstart = tb == 0 ? 0 : zoffset(tb);
       const int zend = (tb + nstep >= T) ? N : zoffset(tb + nstep);
@@ -721,6 +769,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       double w_l = 0.0;
 #pragma nounroll
       for (int s = 0; s < nstep; ++s) {
+        if (HD) { const unsigned long long cw = rlw(cw_l, s); if (hol_l) LI.cur = hpos_l(cw); }
         if (tb + s == 0) {
           // simulate_initial_state: mean_i + sd_i z_i
           const double z = (mylane && init_l) ? s_z[ipos_l] : 0.0;
@@ -734,7 +783,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
           alpha = vecT<SMALL, GLOB>(B, LI, alpha, lane, mv);
           advance(B, LI, mv, lane);
           bool err = false;
-          if (LI.kind == SSG_LOCAL_LEVEL) err = sig_l != 0.0;
+          if (HD && hol_l) err = lane == LI.first + LI.cur;   // (the active position, if the step has one)
+          else if (LI.kind == SSG_LOCAL_LEVEL) err = sig_l != 0.0;
           else if (LI.kind == SSG_LOCAL_LINEAR_TREND) err = true;
           else if (LI.kind == SSG_AR) err = lane == LI.first;
           else if (GLOB && LI.kind == SSG_TRIG) err = sig_l != 0.0;
@@ -785,9 +835,12 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       blk_load(blk, gK + (size_t)tb * m, nstep * m, lane);
       const double w_l = in_l ? w0[tt] : 0.0, F_l = in_l ? sres[tt] : 1.0;
       const int ob_l = (in_l && P.observed[tt]) ? 1 : 0;
+      unsigned long long cw_l = SSG_CAL_NONE;
+      if (HD && in_l) cw_l = P.cal[tt];
       double ef_l = 0.0;
 #pragma nounroll
       for (int s = 0; s < nstep; ++s) {
+        if (HD) { const unsigned long long cw = rlw(cw_l, s); if (hol_l) LI.cur = hpos_l(cw); }
         const double K = mylane ? blk[s * m + lane] : 0.0;
         const bool obs = __builtin_amdgcn_readlane(ob_l, s) != 0;
         const unsigned mv = B.moving();
@@ -815,12 +868,21 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
     const bool in_l = lane < nstep;
     blk_load(blk, gK + (size_t)tb * m, nstep * m, lane);
     const double ef_l = in_l ? w0[tt] : 0.0;
+    // (HD: the calendar's entries t -- Z_t -- and t + 1 -- the row the error of t -> t + 1 lands on)
+    unsigned long long cw_l = SSG_CAL_NONE, cn_l = SSG_CAL_NONE;
+    if (HD) { if (in_l) cw_l = P.cal[tt]; if (in_l && tt + 1 < T) cn_l = P.cal[tt + 1]; }
 #pragma nounroll
     for (int s = nstep - 1; s >= 0; --s) {
       const double K = mylane ? blk[s * m + lane] : 0.0;
       const unsigned mv = B.moving();
+      const unsigned long long cw = HD ? rlw(cw_l, s) : 0ull, cn = HD ? rlw(cn_l, s) : 0ull;
       // r_t at the error rows (layout of t + 1), one value per step and variance parameter
-      if (mylane) {
+      if (HD && hol_l) {
+        // (r_t at the component the step into t + 1 lands on; 0, by the block's first lane, where it has none)
+        const int kn = hpos_l(cn);
+        const bool off = (kn & SSG_CAL_OFF) != 0;
+        if (lane == LI.first + (off ? 0 : kn)) s_z[erow_l * BL + s] = off ? 0.0 : r;
+      } else if (mylane) {
         bool carrier;
         if (LI.kind == SSG_SEASONAL) carrier = lane == LI.first + LI.cur;
         else if (LI.kind == SSG_LOCAL_LINEAR_TREND || (GLOB && LI.kind == SSG_TRIG)) carrier = true;
@@ -833,6 +895,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       r = vecTt<GLOB>(B, LI, r, lane, mv);
       retreat(B, LI, mv, lane);
       // + Z coef (layout of t)
+      if (HD && hol_l) LI.cur = hpos_l(cw);
       if (LI.template zsel<GLOB>(lane)) r += coef;
       if (!mylane) r = 0.0;
     }
@@ -867,6 +930,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       for (int e = 0; e < NE; ++e) s_z[e * BL + lane] = (in_l && tt > 0) ? gd[(size_t)e * T + tt - 1] : 0.0;
       double qp_l0 = 0.0, qp_l1 = 0.0;   // (QT: sigma^2 / w of the steps into the block's times)
       if (QT) { qp_l0 = (in_l && tt > 0) ? qsig0 / qw0[tt - 1] : 0.0; qp_l1 = (in_l && tt > 0) ? qsig1 / qw1[tt - 1] : 0.0; }
+      unsigned long long cw_l = SSG_CAL_NONE;   // (HD: entry t, the component the error INTO t lands on)
+      if (HD && in_l) cw_l = P.cal[tt];
       wave_lds_sync();
 #pragma nounroll
       for (int s = 0; s < nstep; ++s) {
@@ -877,7 +942,10 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
           advance(B, LI, mv, lane);
           // + RQR_{t-1} r_{t-1}
           bool carrier = false;
-          if (mylane) {
+          const unsigned long long cw = HD ? rlw(cw_l, s) : 0ull;
+          if (HD && hol_l) {
+            carrier = lane == LI.first + hpos_l(cw);
+          } else if (mylane) {
             if (LI.kind == SSG_SEASONAL) carrier = LI.moves(mv) && lane == LI.first + LI.cur;
             else if (LI.kind == SSG_LOCAL_LINEAR_TREND || (GLOB && LI.kind == SSG_TRIG)) carrier = true;
             else if (GLOB && LI.kind == SSG_SEMILOCAL) carrier = lane < LI.first + 2;
@@ -906,6 +974,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
   }
   double prev = 0.0;            // state_{t-1} (its own layout)
   double suf_l = 0.0;           // local level / seasonal: sum of squared state errors (at the lane that carried them)
+  double hol_n = 0.0;           // (HD) holiday: the active steps t >= 1 that landed on this lane
   double mv_ybar = 0.0, mv_sumsq = 0.0, mv_n = 0.0;   // MvnSuf of a trend block's errors (its two lanes)
   double yty = 0.0, nobs = 0.0;
   // ArModel's NeRegSuf of now[first] on then[first ..]: lane first + i keeps xty_i and row i
@@ -924,6 +993,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       double *buf = (bi & 1) ? s_blk1 : s_blk0;
       const double y_l = in_l ? P.y[tt] : 0.0;
       const int ob_l = (in_l && P.observed[tt]) ? 1 : 0;
+      unsigned long long cw_l = SSG_CAL_NONE;   // (HD: entry t -- the component the step into t landed on, and Z_t)
+      if (HD && in_l) cw_l = P.cal[tt];
       // (wave 0 only leaves early when THIS wave's variance pass failed, and then this wave has left too)
       while (__hip_atomic_load(&s_cprog, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= bi)
         __builtin_amdgcn_s_sleep(8);
@@ -931,6 +1002,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
 #pragma nounroll
       for (int s = 0; s < nstep; ++s) {
         const double st = mylane ? buf[s * m + lane] : 0.0;
+        if (HD) { const unsigned long long cw = rlw(cw_l, s); if (hol_l) LI.cur = hpos_l(cw); }
         unsigned mv = 0;
         double tot_then = 0.0;   // seasonal: sum of the block at t - 1 (kept by the lanes of the block)
         if (tb + s > 0) {
@@ -958,7 +1030,14 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
           a1_last = st;
         }
         if (tb + s > 0) {
-          if (LI.kind == SSG_LOCAL_LEVEL) {
+          if (HD && hol_l) {
+            // observe_state, active steps only: now[k(t)] - then[k(t)], in time order at its own lane
+            if (lane == LI.first + LI.cur) {
+              const double diff = st - prev;
+              suf_l += diff * diff;
+              hol_n += 1.0;
+            }
+          } else if (LI.kind == SSG_LOCAL_LEVEL) {
             const double diff = st - prev;
             suf_l += diff * diff;
           } else if (GLOB && LI.kind == SSG_SEMILOCAL) {
@@ -1031,7 +1110,15 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
     const int f = Blocks::first_of(d), n = Blocks::dim_of(d), kd = Blocks::kind_of(d);
     const size_t at = (size_t)chain * SSG_MAX_VAR + Blocks::var0_of(d);
     if (QT && b == qtb) continue;   // (the weighted statistics: slt_weights_kernel)
-    if (kd == SSG_LOCAL_LEVEL) {
+    if (HD && Blocks::holiday_of(d)) {
+      // (a lane per position: the block's sums, over its lanes in lane order)
+      const double tot = wsum<SMALL>(LI.blk == b ? suf_l : 0.0);
+      const double cnt = wsum<SMALL>(LI.blk == b ? hol_n : 0.0);
+      if (lane == f) {
+        M.var_n[at] = cnt;
+        M.var_ss[at] = tot;
+      }
+    } else if (kd == SSG_LOCAL_LEVEL) {
       if (lane == f) {
         M.var_n[at] = (double)(T - 1);
         M.var_ss[at] = suf_l;
@@ -1092,5 +1179,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
 
 // the Q_t instances' launch (ssm_qt_kernel.hip): `lds` bytes of dynamic LDS as ssm_dynamic_lds sizes them
 hipError_t launch_ssg_qt(hipStream_t stream, const SsParams &P, int draw_variances, size_t lds);
+// the holiday instances' launch (ssm_hd_kernel.hip)
+hipError_t launch_ssg_hd(hipStream_t stream, const SsParams &P, int draw_variances, size_t lds);
 
 }  // namespace boom_amd

@@ -366,6 +366,26 @@ PYBIND11_MODULE(_boom, boom) {
       .def("set_prior", &SeasonalStateModel::set_prior, py::arg("df"), py::arg("sigma_guess"),
            py::arg("sigma_upper_limit") = std::numeric_limits<double>::infinity());
 
+  py::class_<RandomWalkHolidayStateModel, Ptr<RandomWalkHolidayStateModel>>(
+      boom, "RandomWalkHolidayStateModel",
+      "RandomWalkHolidayStateModel(positions, width).  BayesBoom's constructor takes (holiday, time_zero); this "
+      "module has no Date or Holiday classes, so it takes what those two amount to: positions[t] = -1 where "
+      "time t is outside the holiday's influence window, else the day's position in the window (0 .. width - 1), "
+      "and the window's maximum width.  Entries past the length of the series serve forecasts.")
+      .def(py::init([](const std::vector<int32_t> &positions, int width) {
+             return new RandomWalkHolidayStateModel(positions, width);
+           }),
+           py::arg("positions"), py::arg("width"))
+      .def_property_readonly("state_dimension", &RandomWalkHolidayStateModel::state_dimension)
+      .def_property_readonly("positions", [](const RandomWalkHolidayStateModel &m) { return m.positions(); })
+      .def("set_sigsq", &RandomWalkHolidayStateModel::set_sigsq)
+      .def("set_initial_state_mean", [](RandomWalkHolidayStateModel &m, const NpArray &v) { m.set_initial_state_mean(vector_from(v)); })
+      .def("set_initial_state_variance",
+           [](RandomWalkHolidayStateModel &m, const NpArray &v) { m.set_initial_state_variance(vector_from(v)); },
+           "the diagonal of the initial state's variance")
+      .def("set_prior", &RandomWalkHolidayStateModel::set_prior, py::arg("df"), py::arg("sigma_guess"),
+           py::arg("sigma_upper_limit") = std::numeric_limits<double>::infinity());
+
   py::class_<ArStateModel, Ptr<ArStateModel>>(boom, "ArStateModel")
       .def(py::init<int>(), py::arg("number_of_lags"))
       .def_property_readonly("state_dimension", &ArStateModel::state_dimension)
@@ -461,6 +481,7 @@ PYBIND11_MODULE(_boom, boom) {
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<TrigStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<SemilocalLinearTrendStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<StudentLocalLinearTrendStateModel> &s) { m.add_state(s); })
+      .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<RandomWalkHolidayStateModel> &s) { m.add_state(s); })
       .def("student_trend_nu", [](const StateSpaceRegressionModel &m, int chain) { return to_numpy(m.student_trend_nu(chain)); },
            py::arg("chain") = 0, "(nu_level, nu_slope) of the StudentLocalLinearTrendStateModel in one chain's draw")
       .def("student_trend_weights", [](const StateSpaceRegressionModel &m, int chain) {

@@ -622,6 +622,19 @@ int ba_ss_set_local_level(ba_engine *e, double level_df,
  *           indicators.  Refused: the Student-t / Poisson / logit observation families.  Chain
  *           status 3: no legal configuration; 1: the coefficient draw's precision did not
  *           factor; 14 (BA_E_INVALID): a draw that is not finite.                            1
+ *   kind 10 RandomWalkHolidayStateModel (StateModels/RandomWalkHolidayStateModel.cpp, bsts
+ *           AddRandomWalkHoliday) + ZeroMeanGaussianConjSampler(ChisqModel(df, sigma_guess)), as
+ *           bsts builds it (create_state_model.cpp:891-940).  iparams = {width}, the holiday's
+ *           maximum window width, 1 <= width <= 63.  T = I; where the block's calendar says time t
+ *           is active at position k(t), the step into t adds N(0, sigma^2) to component k(t) and
+ *           Z_t selects component k(t); elsewhere the step adds nothing and Z_t = 0.  observe_state
+ *           takes now[k(t)] - then[k(t)] at the active t >= 1.  The initial state is rmvn(mean,
+ *           diagonal variance): the variances must be positive.  The calendar comes through
+ *           ba_ss_set_holiday_calendar (below); a sweep, ba_ss_impute_state, ba_ss_draw_next and
+ *           ba_ss_prediction_errors refuse a list whose holiday has no calendar or one shorter than
+ *           the series, ba_ss_forecast one shorter than the series and the horizon.  Refused: the
+ *           Student-t / Poisson / logit observation families, a list that also holds kind 8.   width
+ * Several kind 10 models may be added, one per holiday, and may be active on the same day.
  * iparams is ignored for kinds 1, 2 and 5 (may be NULL).  The var_* arrays hold one entry
  * per variance parameter of the model (two for kinds 2 and 7: level, slope; one otherwise):
  * ChisqModel(df, sigma_guess) prior, sigma upper limit (infinity: none), initial sigma.
@@ -632,7 +645,7 @@ int ba_ss_set_local_level(ba_engine *e, double level_df,
  * variance's diagonal; positive, a local level's may be 0).  Limits: state dimension
  * <= 64, 8 state models, 16 variance parameters, 4 autoregression models.
  * RNG streams: variance parameter v of a model reads the chain's sampler id 1 (level),
- * 6 (slope), 7 (seasonal), 13 (trig), 14 (a semilocal slope: NonzeroMeanAr1Sampler) or 12 (ArPosteriorSampler: the proposals' normals, then the
+ * 6 (slope), 7 (seasonal), 8 (a random-walk holiday), 13 (trig), 14 (a semilocal slope: NonzeroMeanAr1Sampler) or 12 (ArPosteriorSampler: the proposals' normals, then the
  * sigma draw -- the reference takes the proposals from GlobalRng::rng and the rest from
  * the sampler's generator) + 16 for every earlier model of the same family (local level
  * and local linear trend are one family); the state draw reads stream 2.  A Student local linear
@@ -765,6 +778,19 @@ int ba_ss_trend_draw_parameters(ba_engine *e);
  * first put back at the draw being served. */
 int ba_ss_autoar_draw_parameters(ba_engine *e);
 int ba_ss_get_ar_inclusion(ba_engine *e, int64_t chain, int32_t block, uint8_t *gamma);
+
+/* The calendar of a random-walk holiday (state model `block`, kind 10): entry t of `position` is -1
+ * (time t is outside the holiday's window) or the position of time t in the window, in [0, width)
+ * -- what the reference reads off Holiday::active and days_into_influence_window of time_zero + t.
+ * Any other entry is refused with a text.  `count` must cover the series (count >= T); the entries
+ * past T serve ba_ss_forecast, which needs count >= T + horizon.  One calendar per block, shared by
+ * all chains; a position may recur in a later window (the random walk then continues from its last
+ * incidence).  In the state draw the block takes one state-error normal of stream 2 per step,
+ * whether the step into it is active or not (an inactive step's is not used).  Under a look-ahead the
+ * setter is a mutator like the others.  ba_ss_get_holiday_calendar: *count = the entries set (0: none
+ * yet); position may be NULL to ask for the count alone, else it has room for that many. */
+int ba_ss_set_holiday_calendar(ba_engine *e, int32_t block, const int32_t *position, int64_t count);
+int ba_ss_get_holiday_calendar(ba_engine *e, int32_t block, int32_t *position, int64_t *count);
 
 /* ---- bsts(family = "student"): StateSpaceStudentRegressionModel with
  * StateSpaceStudentPosteriorSampler (Models/StateSpace/StateSpaceStudentRegressionModel.cpp,

@@ -422,6 +422,35 @@ class SeasonalStateModel {
   double sigma_ = 1.0, df_ = 1.0, guess_ = 1.0, upper_ = infinity();
 };
 
+// RandomWalkHolidayStateModel with a ZeroMeanGaussianConjSampler (StateModels/
+// RandomWalkHolidayStateModel.cpp; bsts AddRandomWalkHoliday): state model kind 10.  There is no
+// Date / Holiday layer here: where the reference's constructor takes (holiday, time_zero), this one
+// takes the calendar those two would reveal -- positions[t] = -1 where time t is outside the holiday's
+// window, else days_into_influence_window of time t -- and the maximum window width.  Entries past
+// the series' length serve forecasts.
+class RandomWalkHolidayStateModel {
+ public:
+  RandomWalkHolidayStateModel(const std::vector<int32_t> &positions, int width) : positions_(positions), width_(width) {
+    if (width < 1) report_error("the holiday's maximum window width must be positive");
+    for (int32_t k : positions)
+      if (k < -1 || k >= width) report_error("a calendar entry must be -1 (inactive) or a position in [0, width)");
+    a0_ = Vector(width, 0.0);
+    P0_ = Vector(width, 1.0);
+  }
+  int state_dimension() const { return width_; }
+  const std::vector<int32_t> &positions() const { return positions_; }
+  void set_sigsq(double s) { sigma_ = std::sqrt(s); }
+  void set_initial_state_mean(const Vector &m) { a0_ = m; }
+  void set_initial_state_variance(const Vector &diagonal) { P0_ = diagonal; }
+  void set_prior(double df, double sigma_guess, double sigma_upper_limit = infinity()) {
+    df_ = df; guess_ = sigma_guess; upper_ = sigma_upper_limit;
+  }
+  std::vector<int32_t> positions_;
+  int width_;
+  Vector a0_, P0_;
+  double sigma_ = 1.0, df_ = 1.0, guess_ = 1.0, upper_ = infinity();
+};
+
 // ArStateModel(number_of_lags) with an ArPosteriorSampler (StateModels/ArStateModel.hpp:53,
 // TimeSeries/PosteriorSamplers/ArPosteriorSampler.hpp)
 class ArStateModel {
@@ -583,6 +612,7 @@ class StateSpaceRegressionModel : public Model {
   void add_state(const Ptr<TrigStateModel> &s) { Entry e; e.kind = 6; e.trig = s; models_.push_back(e); finalized_ = false; }
   void add_state(const Ptr<SemilocalLinearTrendStateModel> &s) { Entry e; e.kind = 7; e.semilocal = s; models_.push_back(e); finalized_ = false; }
   void add_state(const Ptr<StudentLocalLinearTrendStateModel> &s) { Entry e; e.kind = 8; e.student_trend = s; models_.push_back(e); finalized_ = false; }
+  void add_state(const Ptr<RandomWalkHolidayStateModel> &s) { Entry e; e.kind = 10; e.holiday = s; models_.push_back(e); finalized_ = false; }
   int number_of_state_models() const { return (int)models_.size(); }
   bool has_student_trend() const {
     for (const Entry &e : models_) if (e.kind == 8) return true;
@@ -595,7 +625,7 @@ class StateSpaceRegressionModel : public Model {
     int m = 0;
     for (const Entry &e : models_)
       m += (e.kind == 1 || e.kind == 5) ? 1 : (e.kind == 2 || e.kind == 8) ? 2 : e.kind == 3 ? e.seasonal->state_dimension()
-           : e.kind == 6 ? e.trig->state_dimension() : e.kind == 7 ? 3 : e.ar->lags_;
+           : e.kind == 6 ? e.trig->state_dimension() : e.kind == 7 ? 3 : e.kind == 10 ? e.holiday->state_dimension() : e.ar->lags_;
     return m;
   }
   void finalize_state() {
@@ -607,8 +637,14 @@ class StateSpaceRegressionModel : public Model {
       eng_->check(ba_ss_set_local_level(h, s.df_, s.guess_, s.upper_, s.a0_, s.P0_, s.sigma_));
     } else {
       eng_->check(ba_ss_clear_state_models(h));
-      for (const Entry &e : models_) {
-        if (e.kind == 1) {
+      for (size_t b = 0; b < models_.size(); ++b) {
+        const Entry &e = models_[b];
+        if (e.kind == 10) {
+          const RandomWalkHolidayStateModel &s = *e.holiday;
+          const int32_t ip[3] = {s.width_, 0, 0};
+          eng_->check(ba_ss_add_state_model(h, 10, ip, &s.df_, &s.guess_, &s.upper_, &s.sigma_, nullptr, s.a0_.data(), s.P0_.data()));
+          eng_->check(ba_ss_set_holiday_calendar(h, (int32_t)b, s.positions_.data(), (int64_t)s.positions_.size()));
+        } else if (e.kind == 1) {
           const LocalLevelStateModel &s = *e.level;
           eng_->check(ba_ss_add_state_model(h, 1, nullptr, &s.df_, &s.guess_, &s.upper_, &s.sigma_, nullptr, &s.a0_, &s.P0_));
         } else if (e.kind == 2) {
@@ -798,7 +834,7 @@ class StateSpaceRegressionModel : public Model {
   }
  private:
   struct Entry {
-    int kind = 0;   // 1 local level, 2 local linear trend, 3 seasonal, 4 autoregression, 5 static intercept, 6 trig, 7 semilocal linear trend, 8 Student local linear trend
+    int kind = 0;   // 1 local level, 2 local linear trend, 3 seasonal, 4 autoregression, 5 static intercept, 6 trig, 7 semilocal linear trend, 8 Student local linear trend, 10 random-walk holiday
     Ptr<LocalLevelStateModel> level;
     Ptr<LocalLinearTrendStateModel> trend;
     Ptr<SeasonalStateModel> seasonal;
@@ -807,6 +843,7 @@ class StateSpaceRegressionModel : public Model {
     Ptr<TrigStateModel> trig;
     Ptr<SemilocalLinearTrendStateModel> semilocal;
     Ptr<StudentLocalLinearTrendStateModel> student_trend;
+    Ptr<RandomWalkHolidayStateModel> holiday;
   };
   int student_trend_block() const {
     for (size_t b = 0; b < models_.size(); ++b)
