@@ -187,6 +187,9 @@ SIGNATURES = {
     "ba_ss_get_ar_inclusion": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_uint8)]),
     "ba_ss_set_holiday_calendar": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int64]),
     "ba_ss_get_holiday_calendar": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "ba_ss_set_season_calendar": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.c_int64]),
+    "ba_ss_get_season_calendar": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_int64)]),
+    "ba_monthly_cycle_calendar": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_uint8)]),
     "ba_ss_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
     "ba_ss_prediction_errors": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp]),
     "ba_ss_student_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
@@ -214,6 +217,18 @@ def load_library():
             fn.argtypes = args
         _lib = lib
     return _lib
+
+
+def monthly_cycle_calendar(year, month, day, count):
+    """MonthlyAnnualCycle's calendar (ba_monthly_cycle_calendar; host only, no device): `count` flags,
+    entry t is 1 where the day t days after the date of the first observation is the first of a month"""
+    lib = load_library()
+    out = np.zeros(max(int(count), 1), np.uint8)
+    rc = lib.ba_monthly_cycle_calendar(int(year), int(month), int(day), int(count),
+                                       out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != 0:
+        raise BoomAmdError(rc, lib.ba_last_error().decode())
+    return out[:int(count)]
 
 
 def _f64(a):
@@ -838,15 +853,26 @@ class Engine:
         6 trig, 7 semilocal linear trend, 8 Student local linear trend: nu_priors = ((kind, a, b) of
         level and slope), initial_nu = (level, slope), 9 spike-and-slab autoregression: lags, initial_phi,
         slab_mean, slab_precision, inclusion_probabilities, truncate, max_flips, allow_model_selection,
-        10 random-walk holiday: width and, optionally, calendar -- ss_set_holiday_calendar's positions), nseasons, duration, t0, lags, df, sigma_guess, sigma_upper_limit, initial_sigma
+        10 random-walk holiday: width and, optionally, calendar -- ss_set_holiday_calendar's positions,
+        11 or "calendar_seasonal": nseasons and, optionally, calendar -- ss_set_season_calendar's flags;
+        "monthly": the calendar seasonal of 12 seasons that start on the first day of a month, with
+        first_date = (year, month, day) of the first observation and, optionally, calendar_length (the
+        series' length and any forecast horizon; default: the series' length + 366)), nseasons, duration, t0, lags, df, sigma_guess, sigma_upper_limit, initial_sigma
         (one entry per variance parameter; none for kind 5), initial_phi, rotations (kind 6: the
         (cos, sin) pairs of the transition matrix), a0, P0 (tests/cases.py: general_spec)"""
         self._check(self.lib.ba_ss_clear_state_models(self._h))
         self._blocks = []
         for b in blocks:
+            if b["kind"] == "monthly":
+                n = int(b.get("calendar_length", self.T + 366))
+                b = dict(b, kind=11, nseasons=12, calendar=monthly_cycle_calendar(*b["first_date"], n))
+            elif b["kind"] == "calendar_seasonal":
+                b = dict(b, kind=11)
             kind = int(b["kind"])
             ip = np.zeros(4, np.int32)
-            if kind == 3:
+            if kind == 11:
+                ip[0] = b["nseasons"]
+            elif kind == 3:
                 ip[:3] = (b["nseasons"], b["duration"], b.get("t0", 0))
             elif kind == 4:
                 ip[0] = b["lags"]
@@ -883,6 +909,8 @@ class Engine:
                                      lags=int(ip[0]) if kind in (4, 9) else 0))
             if kind == 10 and b.get("calendar") is not None:
                 self.ss_set_holiday_calendar(len(self._blocks) - 1, b["calendar"])
+            if kind == 11 and b.get("calendar") is not None:
+                self.ss_set_season_calendar(len(self._blocks) - 1, b["calendar"])
         m, nb = C.c_int32(), C.c_int32()
         self._check(self.lib.ba_ss_state_dimension(self._h, C.byref(m), C.byref(nb)))
         self._ssm_dim = m.value
@@ -1025,6 +1053,24 @@ class Engine:
         self._check(self.lib.ba_ss_get_holiday_calendar(self._h, block, pos.ctypes.data_as(C.POINTER(C.c_int32)),
                                                         C.byref(n)))
         return pos[:n.value]
+
+    def ss_set_season_calendar(self, block, new_season):
+        """a calendar seasonal's calendar (state model `block`): entry t is 1 where time t starts a new
+        season, else 0; at least T entries, those past T serve forecasts"""
+        raw = np.asarray(new_season)
+        if raw.size and (raw.min() < 0 or raw.max() > 255):
+            raise ValueError("a season calendar's entries must be 0 or 1")
+        flags = np.ascontiguousarray(raw, dtype=np.uint8)
+        self._check(self.lib.ba_ss_set_season_calendar(self._h, block, flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                       flags.size))
+
+    def ss_get_season_calendar(self, block):
+        n = C.c_int64()
+        self._check(self.lib.ba_ss_get_season_calendar(self._h, block, None, C.byref(n)))
+        flags = np.zeros(max(n.value, 1), np.uint8)
+        self._check(self.lib.ba_ss_get_season_calendar(self._h, block, flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                       C.byref(n)))
+        return flags[:n.value]
 
     def ss_forecast(self, newX):
         """one predictive draw of the next len(newX) observations per chain"""

@@ -454,6 +454,10 @@ struct ba_engine {
   std::vector<int32_t> hol_calendar[SSG_MAX_BLOCKS];
   DevBuf<uint64_t> dhol_cal;
   int64_t hol_cal_count = 0;
+  // the calendar seasonals (ssg_is_calendar): every such block's flags as the caller gave them
+  // (entry t: 1 where time t starts a new season; empty: not set yet) -- packed into dhol_cal beside the
+  // holidays' positions, with their prefix counts behind the table (SsParams::cal)
+  std::vector<uint8_t> season_calendar[SSG_MAX_BLOCKS];
   // ba_ss_prediction_errors (ss_filter_kernel.hip): its outputs on the device (errors, forecast
   // variances, log likelihoods, the forecast-variance flag), the local-level path's one-block
   // list, and the stream the filter of a look-ahead's recorded draw runs on beside the batch

@@ -27,6 +27,15 @@ static bool ssg_has_holiday(const SsgSpec &q) {
   return false;
 }
 
+// does the list hold a calendar seasonal (ssg_is_calendar: the same instances, the same table)?
+static bool ssg_has_calendar_seasonal(const SsgSpec &q) {
+  for (int i = 0; i < q.nblocks; ++i)
+    if (ssg_is_calendar(q.blk[i])) return true;
+  return false;
+}
+// ... a block of either kind: the list has a calendar
+static bool ssg_has_calendar(const SsgSpec &q) { return ssg_has_holiday(q) || ssg_has_calendar_seasonal(q); }
+
 // does the block list have the shape the template kernel is compiled for?
 // [local level | local linear trend] [seasonal, duration 1] [autoregression], m <= 16
 static void ssg_template_shape(const SsgSpec &q, int32_t *trend, int32_t *nseasons, int32_t *ar_lags) {
@@ -34,7 +43,7 @@ static void ssg_template_shape(const SsgSpec &q, int32_t *trend, int32_t *nseaso
   if (q.nblocks < 1 || q.nblocks > 3 || q.m > 16) return;
   if (q.student_block) return;   // (a Student local linear trend: the general kernel's QT instances)
   if (ssg_has_ar_spike(q)) return;   // (a spike-and-slab autoregression: the general kernel passes its sampler by)
-  if (ssg_has_holiday(q)) return;    // (a random-walk holiday: the general kernel's HD instances)
+  if (ssg_has_calendar(q)) return;   // (a random-walk holiday or a calendar seasonal: the general kernel's HD instances)
   for (int i = 0; i < q.nblocks; ++i)
     if (q.blk[i].nvar == 0) return;   // (a static intercept: the general kernel)
   int b = 0, tr = 0, ns = 0, lags = 0;
@@ -137,7 +146,7 @@ static void fill_ss_params(ba_engine *e, SsParams &S) {
       S.qw = e->dslt_w.ptr;
       S.qw_stride = 2 * (int64_t)e->T;
     }
-    if (ssg_has_holiday(e->ssg)) {
+    if (ssg_has_calendar(e->ssg)) {
       S.cal = e->dhol_cal.ptr;   // (packed by hol_prepare, which every entry point that launches passes first)
       S.cal_count = e->hol_cal_count;
     }
@@ -148,45 +157,74 @@ static const char *const HOLIDAY_FAMILY_REFUSAL =
     "the random-walk holiday is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)";
 static const char *const HOLIDAY_STUDENT_TREND_REFUSAL =
     "a list that holds both a random-walk holiday and a Student local linear trend is not built";
+static const char *const CALSEAS_FAMILY_REFUSAL =
+    "the calendar seasonal is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)";
+static const char *const CALSEAS_STUDENT_TREND_REFUSAL =
+    "a list that holds both a calendar seasonal and a Student local linear trend is not built";
 
-// The random-walk holidays' calendars: every such block needs one that covers the series and
-// `extra` steps beyond it (a forecast's horizon); the packed table goes to the device when a
-// calendar has changed.  Nothing runs on a default calendar.
+// The calendars of the random-walk holidays and the calendar seasonals: every such block needs one
+// that covers the series and `extra` steps beyond it (a forecast's horizon); the packed table -- and
+// the calendar seasonals' prefix counts -- go to the device when a calendar has changed.  Nothing
+// runs on a default calendar.
 static int hol_prepare(ba_engine *e, int64_t extra = 0) {
-  if (!e->ssm_set || !ssg_has_holiday(e->ssg)) return BA_OK;
+  if (!e->ssm_set || !ssg_has_calendar(e->ssg)) return BA_OK;
   int64_t count = -1;
   for (int b = 0; b < e->ssg.nblocks; ++b) {
-    if (!e->ssg.blk[b].holiday) continue;
-    const int64_t n = (int64_t)e->hol_calendar[b].size();
-    char buf[200];
+    const bool seas = ssg_is_calendar(e->ssg.blk[b]);
+    if (!e->ssg.blk[b].holiday && !seas) continue;
+    const int64_t n = seas ? (int64_t)e->season_calendar[b].size() : (int64_t)e->hol_calendar[b].size();
+    const char *what = seas ? "season" : "holiday";
+    char buf[240];
     if (n == 0) {
-      std::snprintf(buf, sizeof buf, "state model %d is a random-walk holiday without a calendar: call ba_ss_set_holiday_calendar first", b);
+      if (seas)
+        std::snprintf(buf, sizeof buf, "state model %d is a calendar seasonal without a calendar: call ba_ss_set_season_calendar first", b);
+      else
+        std::snprintf(buf, sizeof buf, "state model %d is a random-walk holiday without a calendar: call ba_ss_set_holiday_calendar first", b);
       return fail(BA_E_STATE, buf);
     }
     if (n < (int64_t)e->T) {
-      std::snprintf(buf, sizeof buf, "the holiday calendar of state model %d has %lld entries, the series has %d time points",
-                    b, (long long)n, (int)e->T);
+      std::snprintf(buf, sizeof buf, "the %s calendar of state model %d has %lld entries, the series has %d time points",
+                    what, b, (long long)n, (int)e->T);
       return fail(BA_E_STATE, buf);
     }
     if (n < (int64_t)e->T + extra) {
-      std::snprintf(buf, sizeof buf, "the holiday calendar of state model %d has %lld entries: a forecast of horizon %lld needs %lld (the series' %d and the horizon)",
-                    b, (long long)n, (long long)extra, (long long)((int64_t)e->T + extra), (int)e->T);
+      std::snprintf(buf, sizeof buf, "the %s calendar of state model %d has %lld entries: a forecast of horizon %lld needs %lld (the series' %d and the horizon)",
+                    what, b, (long long)n, (long long)extra, (long long)((int64_t)e->T + extra), (int)e->T);
       return fail(BA_E_INVALID, buf);
     }
     count = count < 0 ? n : std::min(count, n);
   }
-  if (e->hol_cal_count == count && e->dhol_cal.count == (size_t)count) return BA_OK;
-  std::vector<uint64_t> packed((size_t)count, (uint64_t)SSG_CAL_NONE);
+  // (the table's words, then -- a calendar seasonal in the list -- nblocks rows of int32 prefix counts)
+  const bool any_seas = ssg_has_calendar_seasonal(e->ssg);
+  const size_t nstarted = any_seas ? (size_t)e->ssg.nblocks * (size_t)count : 0;
+  const size_t words = (size_t)count + (nstarted + 1) / 2;
+  if (e->hol_cal_count == count && e->dhol_cal.count == words) return BA_OK;
+  std::vector<uint64_t> packed(words, 0);
+  std::fill(packed.begin(), packed.begin() + count, (uint64_t)SSG_CAL_NONE);
+  int32_t *started = reinterpret_cast<int32_t *>(packed.data() + count);
   for (int b = 0; b < e->ssg.nblocks; ++b) {
+    if (ssg_is_calendar(e->ssg.blk[b])) {
+      // (entry 0 is never read: no step leads into time 0)
+      int32_t *row = started + (size_t)b * (size_t)count;
+      int32_t run = 0;
+      for (int64_t t = 1; t < count; ++t) {
+        if (e->season_calendar[b][(size_t)t]) {
+          packed[(size_t)t] |= (uint64_t)SSG_CAL_SEASON << (8 * b);
+          ++run;
+        }
+        row[t] = run;
+      }
+      continue;
+    }
     if (!e->ssg.blk[b].holiday) continue;
     for (int64_t t = 0; t < count; ++t) {
       const int32_t k = e->hol_calendar[b][(size_t)t];
       if (k >= 0) packed[(size_t)t] = (packed[(size_t)t] & ~(0xffull << (8 * b))) | ((uint64_t)k << (8 * b));
     }
   }
-  HIP_TRY(hipStreamSynchronize(e->stream));   // (nothing in flight reads the table that is replaced)
-  HIP_TRY(e->dhol_cal.resize((size_t)count));
-  HIP_TRY(hipMemcpy(e->dhol_cal.ptr, packed.data(), (size_t)count * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (nothing in flight reads the tables that are replaced)
+  HIP_TRY(e->dhol_cal.resize(words));
+  HIP_TRY(hipMemcpy(e->dhol_cal.ptr, packed.data(), words * 8, hipMemcpyHostToDevice));
   e->hol_cal_count = count;
   return BA_OK;
 }
@@ -629,6 +667,7 @@ static int ss_prepare(ba_engine *e, DataKind kind = DATA_STATE_SPACE) {
   if (kind != DATA_STATE_SPACE && e->ssm_set && e->ssg.student_block) return fail(BA_E_STATE, SLT_FAMILY_REFUSAL);
   if (kind != DATA_STATE_SPACE && e->ssm_set && ssg_has_ar_spike(e->ssg)) return fail(BA_E_STATE, AUTOAR_FAMILY_REFUSAL);
   if (kind != DATA_STATE_SPACE && e->ssm_set && ssg_has_holiday(e->ssg)) return fail(BA_E_STATE, HOLIDAY_FAMILY_REFUSAL);
+  if (kind != DATA_STATE_SPACE && e->ssm_set && ssg_has_calendar_seasonal(e->ssg)) return fail(BA_E_STATE, CALSEAS_FAMILY_REFUSAL);
   rc = hol_prepare(e);
   if (rc) return rc;
   rc = upload_shared(e);
@@ -902,6 +941,8 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
   const bool is_autoar = kind == SSG_AUTO_AR;
   if (is_autoar) kind = SSG_AR;   // (stored as an autoregression with SsgBlock::ar_spike set)
   const bool is_holiday = kind == SSG_HOLIDAY;   // (stored as a local level of dimension width with SsgBlock::holiday set)
+  const bool is_calendar = kind == SSG_CALENDAR_SEASONAL;
+  if (is_calendar) kind = SSG_SEASONAL;   // (stored as a seasonal with phase SSG_PHASE_CALENDAR: one family, one sampler id)
   SsgBlock k{};
   k.kind = kind;
   k.nvar = 1;
@@ -914,6 +955,17 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
       if (!iparams) return fail(BA_E_INVALID, "null argument");
       // SeasonalStateModelBase: "'nseasons' must be positive"; one season has no state
       if (iparams[0] < 2) return fail(BA_E_INVALID, "nseasons must be at least 2");
+      if (is_calendar) {
+        // the calendar seasonal: iparams = {nseasons}; its season starts come through
+        // ba_ss_set_season_calendar (duration and phase stay 1 and 0 and are not read for it)
+        if (e->data_kind == DATA_SS_STUDENT || e->data_kind == DATA_SS_POISSON || e->data_kind == DATA_SS_LOGIT)
+          return fail(BA_E_STATE, CALSEAS_FAMILY_REFUSAL);
+        if (q.student_block) return fail(BA_E_STATE, CALSEAS_STUDENT_TREND_REFUSAL);
+        k.nseasons = iparams[0];
+        k.dim = k.nseasons - 1;
+        k.phase = SSG_PHASE_CALENDAR;
+        break;
+      }
       if (iparams[1] < 1) return fail(BA_E_INVALID, "season_duration must be positive");
       // (the kernels keep a block's duration and its running phase in 16-bit fields)
       if (iparams[1] > 65535) return fail(BA_E_INVALID, "season_duration exceeds 65535");
@@ -976,6 +1028,7 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
       if (!initial_phi) return fail(BA_E_INVALID, "null argument");
       if (q.student_block) return fail(BA_E_INVALID, "at most one Student local linear trend per list of state models");
       if (ssg_has_holiday(q)) return fail(BA_E_STATE, HOLIDAY_STUDENT_TREND_REFUSAL);
+      if (ssg_has_calendar_seasonal(q)) return fail(BA_E_STATE, CALSEAS_STUDENT_TREND_REFUSAL);
       if (e->data_kind == DATA_SS_STUDENT || e->data_kind == DATA_SS_POISSON || e->data_kind == DATA_SS_LOGIT)
         return fail(BA_E_STATE, SLT_FAMILY_REFUSAL);
       for (int c = 0; c < 2; ++c) {
@@ -1046,7 +1099,7 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
       }
       break;
     default:
-      return fail(BA_E_INVALID, "state model kind must be 1 (local level), 2 (local linear trend), 3 (seasonal), 4 (autoregression), 5 (static intercept), 6 (trig), 7 (semilocal linear trend), 8 (Student local linear trend), 9 (spike-and-slab autoregression) or 10 (random-walk holiday)");
+      return fail(BA_E_INVALID, "state model kind must be 1 (local level), 2 (local linear trend), 3 (seasonal), 4 (autoregression), 5 (static intercept), 6 (trig), 7 (semilocal linear trend), 8 (Student local linear trend), 9 (spike-and-slab autoregression), 10 (random-walk holiday) or 11 (calendar seasonal)");
   }
   const int nslot = is_static ? 1 : k.nvar;   // variance slots the block takes
   if (q.m + k.dim > SSG_MAX_STATE) return fail(BA_E_INVALID, "state dimension exceeds 64");
@@ -1106,6 +1159,7 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
     q.nar += 1;
   }
   if (is_holiday) e->hol_calendar[q.nblocks].clear();   // (no calendar yet)
+  if (is_calendar) e->season_calendar[q.nblocks].clear();
   if (is_student) {
     q.student_block = q.nblocks + 1;
     for (int c = 0; c < 2; ++c) {
@@ -1127,7 +1181,7 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
 }
 static void ssg_clear(ba_engine *e) {
   e->ssg = SsgSpec{};
-  for (int b = 0; b < SSG_MAX_BLOCKS; ++b) e->hol_calendar[b].clear();
+  for (int b = 0; b < SSG_MAX_BLOCKS; ++b) { e->hol_calendar[b].clear(); e->season_calendar[b].clear(); }
   e->hol_cal_count = 0;
   for (int i = 0; i < 3; ++i) e->ssg_template_var[i] = -1;
   e->ssg_template_ar = -1;
@@ -1188,6 +1242,7 @@ int ba_ss_set_holiday_calendar(ba_engine *e, int32_t block, const int32_t *posit
   if (!position || count <= 0) return fail(BA_E_INVALID, "bad argument");
   if (!e->ssm_set || block < 0 || block >= e->ssg.nblocks) return fail(BA_E_INVALID, "state model index out of range");
   const SsgBlock &k = e->ssg.blk[block];
+  if (ssg_is_calendar(k)) return fail(BA_E_INVALID, "not a random-walk holiday state model: a calendar seasonal's calendar goes through ba_ss_set_season_calendar");
   if (!k.holiday) return fail(BA_E_INVALID, "not a random-walk holiday state model");
   for (int64_t t = 0; t < count; ++t)
     if (position[t] < -1 || position[t] >= k.dim) {
@@ -1209,6 +1264,59 @@ int ba_ss_get_holiday_calendar(ba_engine *e, int32_t block, int32_t *position, i
   const std::vector<int32_t> &c = e->hol_calendar[block];
   if (count) *count = (int64_t)c.size();
   if (position && !c.empty()) std::memcpy(position, c.data(), c.size() * sizeof(int32_t));
+  return BA_OK;
+}
+
+// a calendar seasonal's calendar: entry t is 1 where time t starts a new season, else 0 (entry 0 is
+// never read: no step leads into time 0)
+int ba_ss_set_season_calendar(ba_engine *e, int32_t block, const uint8_t *new_season, int64_t count) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!new_season || count <= 0) return fail(BA_E_INVALID, "bad argument");
+  if (!e->ssm_set || block < 0 || block >= e->ssg.nblocks) return fail(BA_E_INVALID, "state model index out of range");
+  if (!ssg_is_calendar(e->ssg.blk[block])) return fail(BA_E_INVALID, "not a calendar seasonal state model");
+  for (int64_t t = 0; t < count; ++t)
+    if (new_season[t] > 1) {
+      char buf[160];
+      std::snprintf(buf, sizeof buf, "season calendar entry %lld is %d: it must be 0 or 1 (time t starts a new season)",
+                    (long long)t, (int)new_season[t]);
+      return fail(BA_E_INVALID, buf);
+    }
+  e->season_calendar[block].assign(new_season, new_season + count);
+  e->hol_cal_count = 0;   // (packed again by the next call that launches)
+  return BA_OK;
+}
+
+// new_season == nullptr: the count alone
+int ba_ss_get_season_calendar(ba_engine *e, int32_t block, uint8_t *new_season, int64_t *count) {
+  if (!e) return fail(BA_E_INVALID, "null engine");
+  if (!e->ssm_set || block < 0 || block >= e->ssg.nblocks) return fail(BA_E_INVALID, "state model index out of range");
+  if (!ssg_is_calendar(e->ssg.blk[block])) return fail(BA_E_INVALID, "not a calendar seasonal state model");
+  const std::vector<uint8_t> &c = e->season_calendar[block];
+  if (count) *count = (int64_t)c.size();
+  if (new_season && !c.empty()) std::memcpy(new_season, c.data(), c.size());
+  return BA_OK;
+}
+
+// MonthlyAnnualCycle's calendar from the date of the first observation (proleptic Gregorian): out[t] = 1
+// where the day `t` days after (year, month, day) is the first of a month
+int ba_monthly_cycle_calendar(int32_t year, int32_t month, int32_t day, int64_t count, uint8_t *out) {
+  if (!out || count < 0) return fail(BA_E_INVALID, "bad argument");
+  auto leap = [](int64_t y) { return (y % 4 == 0 && y % 100 != 0) || y % 400 == 0; };
+  auto days_in = [&](int64_t y, int mo) {
+    static const int len[12] = {31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
+    return len[mo - 1] + ((mo == 2 && leap(y)) ? 1 : 0);
+  };
+  if (month < 1 || month > 12 || day < 1 || day > days_in(year, month)) return fail(BA_E_INVALID, "not a date of the Gregorian calendar");
+  int64_t y = year;
+  int mo = month, d = day;
+  for (int64_t t = 0; t < count; ++t) {
+    out[t] = d == 1 ? 1 : 0;
+    if (++d > days_in(y, mo)) {
+      d = 1;
+      if (++mo > 12) { mo = 1; ++y; }
+    }
+  }
   return BA_OK;
 }
 
@@ -1909,7 +2017,7 @@ int ba_ss_prediction_errors(ba_engine *e, int64_t chain_first, int64_t chain_cou
       F.qw = e->dslt_w.ptr;   // (a look-ahead above 1 is refused with such a block: always live)
       F.qw_stride = 2 * (int64_t)T;
     }
-    if (ssg_has_holiday(e->ssg)) F.cal = e->dhol_cal.ptr;   // (one table for every draw: the record needs none)
+    if (ssg_has_calendar(e->ssg)) F.cal = e->dhol_cal.ptr;   // (one table for every draw: the record needs none)
   } else {
     // the local-level path: the same kernel on a one-block list
     SsgSpec one{};

@@ -39,11 +39,21 @@ enum { SSG_LOCAL_LEVEL = 1, SSG_LOCAL_LINEAR_TREND = 2, SSG_SEASONAL = 3, SSG_AR
        // active at position k(t), nothing otherwise.  Stored as SSG_LOCAL_LEVEL of dimension width with
        // SsgBlock::holiday set; the calendars of a list are one packed table (SsParams::cal), and such a
        // list is served by the HD instances of the general kernel
-       SSG_HOLIDAY = 10 };
+       SSG_HOLIDAY = 10,
+       // The calendar seasonal (the C-ABI's number; MonthlyAnnualCycle is the one of 12 seasons whose
+       // seasons start on the first day of a month): SSG_SEASONAL in everything but this -- whether time
+       // t starts a new season is read from the block's calendar, not computed from a duration.  Stored
+       // as SSG_SEASONAL with duration 1 and phase SSG_PHASE_CALENDAR (ssg_is_calendar; no field of its own);
+       // its flags share the packed table of the holidays (bit SSG_CAL_SEASON of byte b), their prefix
+       // counts sit behind the table (see SsParams::cal), and such a list is served by the HD instances
+       SSG_CALENDAR_SEASONAL = 11 };
 // the packed calendar: entry t holds block b's position at time t in byte b, SSG_CAL_OFF where the
-// block is inactive at t (or is no holiday block)
+// block is inactive at t (or is no holiday block).  A calendar seasonal's byte: SSG_CAL_SEASON where
+// time t starts a new season (its other bits are not read).
 enum : uint64_t { SSG_CAL_NONE = 0x8080808080808080ull };
-enum { SSG_CAL_OFF = 0x80 };
+enum { SSG_CAL_OFF = 0x80, SSG_CAL_SEASON = 0x01 };
+// a calendar seasonal's SsgBlock::phase: no time u has u % 1 == -1, so the closed forms never fire for it
+enum { SSG_PHASE_CALENDAR = -1 };
 // ar_spike_kernel's own chain status: a coefficient or variance draw that is not finite
 enum { AR_SPIKE_BAD_DRAW = 14 };
 // the Student trend's streams: its sampler's four draws (read in sequence) and the weights' slots
@@ -59,6 +69,7 @@ struct SsgBlock {
   int32_t kind, first, dim, nvar;
   int32_t var0;        // index of the block's first variance parameter
   int32_t nseasons, duration, phase;   // seasonal: a new season starts at the times u with u % duration == phase
+                                       // (phase SSG_PHASE_CALENDAR, duration 1: a calendar seasonal -- ssg_is_calendar)
   int32_t lags, ar_index;              // autoregression: which of the chain's coefficient / suf slots
   int32_t sid[2];      // Philox sampler ids of the variance samplers (autoregression: its ArPosteriorSampler's)
   int32_t nfreq;       // trig: frequencies (dim = 2 nfreq)
@@ -67,6 +78,8 @@ struct SsgBlock {
   int32_t ar_spike;    // autoregression: its sampler is the ArSpikeSlabSampler of ar_spike_kernel.hip (0: ArPosteriorSampler, in the state kernel)
   int32_t holiday;     // local level of dimension dim: a random-walk holiday (SSG_HOLIDAY), its positions in the packed calendar
 };
+// is the block a calendar seasonal (SSG_CALENDAR_SEASONAL: its season starts are read from the packed calendar)?
+__host__ __device__ inline bool ssg_is_calendar(const SsgBlock &k) { return k.kind == SSG_SEASONAL && k.phase == SSG_PHASE_CALENDAR; }
 // the specification, in device memory (read through the scalar cache)
 struct SsgSpec {
   int32_t m, nblocks, nvar, nar;
@@ -176,6 +189,9 @@ struct SsParams {
   int64_t qw_stride;
   // the random-walk holidays' packed calendar (SSG_CAL_NONE ...), cal_count >= T entries, one table
   // for all chains (nullptr: the list holds no such block).  Read by the HD instances and the forecast.
+  // A list with a calendar seasonal keeps the blocks' prefix counts behind the table, in the same
+  // allocation: int32 entry b * cal_count + t after the cal_count words = how many of the times 1 .. t
+  // start a new season of block b (rows of other blocks are 0).
   const uint64_t *cal;
   int64_t cal_count;
 };

@@ -159,10 +159,12 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
   B.nb = P.nblocks;
   B.desc = 0;
   int dur = 1, rc = 1;   // lane b, seasonal block b: its duration; (index of the step's transition + 1 - phase) mod duration (0: it moves)
+  bool calb = false;     // lane b: block b is a calendar seasonal -- it moves where the calendar's entry t + 1 says so
   if (lane < P.nblocks) {
     const SsgBlock &K = Q.blk[lane];
     B.desc = (unsigned)K.kind | ((unsigned)K.first << 3) | ((unsigned)K.dim << 10) | ((unsigned)K.var0 << 17) |
              ((unsigned)(K.ar_index < 0 ? 0 : K.ar_index) << 22) | ((unsigned)(K.nvar > 0 ? 1 : 0) << 25);
+    calb = ssg_is_calendar(K);
     if (K.kind == SSG_SEASONAL) {
       dur = K.duration;
       rc = (1 - K.phase) % dur;
@@ -235,9 +237,11 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
       double vout = nan, F = nan;
       unsigned long long zmask_t = zmask;
       bool hgain = false;   // this lane's diagonal entry gains the holiday's variance at this step
+      bool calmove = false; // lane b: calendar seasonal b steps into a new season
       if (P.cal) {
         const unsigned long long cw = __builtin_bit_cast(unsigned long long, ssf_rl(__builtin_bit_cast(double, cw_l), s));
         const unsigned long long cn = __builtin_bit_cast(unsigned long long, ssf_rl(__builtin_bit_cast(double, cn_l), s));
+        calmove = calb && ((cn >> (8 * (lane & 7))) & (unsigned long long)SSG_CAL_SEASON) != 0;
         zmask_t |= __ballot(hol && lane == hfirst + (int)((cw >> hsh) & 0xffu));
         hgain = hol && lane == hfirst + (int)((cn >> hsh) & 0xffu);
       }
@@ -273,7 +277,7 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
           }
           vout = v;
           // a <- T a, P <- T P T' + RQR
-          const unsigned mv = (unsigned)__ballot(lane < B.nb && SsfBlocks::kind_of(B.desc) == SSG_SEASONAL && rc == 0) & seasmask;
+          const unsigned mv = (unsigned)__ballot(lane < B.nb && SsfBlocks::kind_of(B.desc) == SSG_SEASONAL && (calb ? calmove : rc == 0)) & seasmask;
           if (always | mv) {
             if (act) s_P[lane * ld + m] = a;
             ssf_sync();

@@ -34,7 +34,8 @@ struct SsFilterParams {
   double *variances;          // chain_count x T, or nullptr
   double *loglik;             // chain_count
   int32_t *flag;              // the smallest chain of the launch whose forecast variance was not positive (else untouched)
-  // the random-walk holidays' packed calendar (SsParams::cal), at least T entries; nullptr: no such block
+  // the packed calendar of the random-walk holidays and the calendar seasonals (SsParams::cal), at least
+  // T entries; nullptr: no such block
   const uint64_t *cal;
 };
 

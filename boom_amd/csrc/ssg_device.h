@@ -345,7 +345,7 @@ __device__ __forceinline__ int semilocal_slope_draw(const double *suf, const dou
 struct Blocks {
   unsigned desc;   // kind (3 bits) | first (7) | dim (7) | index of its first variance parameter (5) | autoregression slot (3) |
                    // a random-walk holiday (1: set and read by the HD instances of ssg_simsmooth_kernel only)
-  unsigned dp;     // seasonal: duration (16 bits) | phase (16)
+  unsigned dp;     // seasonal: duration (16 bits) | phase (16)  (a calendar seasonal: 1 | 0xffff, its closed forms never fire)
   unsigned rc;     // seasonal: (index of the step's transition + 1 - phase) mod duration (16 bits: 0 = it moves) |
                    //           the rotating layout's cursor (16): physical slot of the block's first component
   int nb;

@@ -19,6 +19,7 @@ namespace {
 // to tm + 2; nullptr: the list has none).  Such a block's error of time tm lands on its position at
 // time tm + 1 -- drawn only where that time is active, as the reference does -- and the returned
 // Z'st is that of time tm + 2, the time simulate_multiplex_forecast observes the new state at.
+// A calendar seasonal steps into a new season where entry tm + 1 carries SSG_CAL_SEASON.
 __device__ __forceinline__ double ssg_forecast_step(const SsmParams &M, const SsgSpec &Q, int chain, int lane, int tm,
                                                     SeqRng &rng, double &st, const uint64_t *cal = nullptr) {
   const int m = M.m, nb = M.nblocks;
@@ -60,7 +61,10 @@ __device__ __forceinline__ double ssg_forecast_step(const SsmParams &M, const Ss
       }
       if (mine) nx = (((lane - f) & 1) ? -sn * below + c * st : c * st + sn * above) + e4;
     } else if (K.kind == SSG_SEASONAL) {
-      if ((tm + 1) % K.duration == K.phase) {
+      // (a calendar seasonal: the season flag of time tm + 1 in the packed calendar)
+      const bool starts = ssg_is_calendar(K) ? (cal && ((cal[tm + 1] >> (8 * b)) & (uint64_t)SSG_CAL_SEASON) != 0)
+                                     : (tm + 1) % K.duration == K.phase;
+      if (starts) {
         const double e2 = d_rnorm(rng, 0.0, sqrt(sg[0]));
         // (first = 0 - s_0 - s_1 - ..., SeasonalStateSpaceMatrix::multiply)
         double firstv = 0.0;

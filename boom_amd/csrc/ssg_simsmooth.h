@@ -65,7 +65,7 @@
 // (this header: the kernel template.  ssm_kernel.hip instantiates the scalar and the H_t instances and
 // holds the launcher and the forecast kernel; ssm_qt_kernel.hip instantiates the Q_t instances -- a
 // file of their own so that the two compile side by side: 24 instances in one file took about 5 min
-// against 3 min 06 s for the 16 -- and ssm_hd_kernel.hip, a third, the holiday instances.)
+// against 3 min 06 s for the 16 -- and ssm_hd_kernel.hip, a third, the calendar instances.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -126,6 +126,19 @@ __host__ __device__ inline int ssg_pass_lds_doubles(int m, int ld, int bl, int n
 // edge is no special case.  The lanes of such a block keep k(t) in LaneInfo::cur, which zsel / zdot read.
 // The block draws ONE state-error normal per step, active or not (an inactive step's is not used): the
 // slot map of the normals stays closed-form.
+// The HD instances also serve the calendar seasonal (ssg_is_calendar, SSG_CALENDAR_SEASONAL): a
+// seasonal block in every operation, whose "the step into time t starts a new season" is bit
+// SSG_CAL_SEASON of its byte of entry t instead of t % duration == phase.  hmoving() below puts that
+// bit where Blocks::moving() has the block's closed form -- entry t + 1 in the passes that walk the
+// transition OUT of t, entry t in those that walk the one INTO t --, and everything downstream (the
+// rotating layout's cursor, T, T', RQR, the carriers) follows the step's `mv` as it does for a
+// seasonal.  The three closed forms that count season starts -- the slot map's seasonal_draws, the
+// cursor of time T the backward pass starts from, and the statistics' n -- read the block's prefix
+// counts (behind the table, see SsParams::cal) instead.  The RNG conventions are the seasonal's
+// exactly: one stream-2 normal per step into a new season and none elsewhere, none at all when
+// sigma = 0; the variance draw reads sampler id 7 + 16 per earlier seasonal block of either kind (one
+// family in ssg_stream_id).  A regular calendar therefore draws what the seasonal of that duration and
+// phase draws, bit for bit.
 template <bool SMALL, int LDC, bool GLOB, bool HT = false, bool QT = false, bool HD = false>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void ssg_simsmooth_kernel(SsParams P, int draw_variances) {
   constexpr int SSG_BATCH = SMALL ? 4 : 8;   // entries of a column / row of P asked of the LDS together
@@ -261,6 +274,42 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
   B.load(Q, nb, lane);
   if (HD && lane < nb && Q.blk[lane].holiday) B.desc |= 1u << 25;
   LaneInfo LI{-1, 0, 0, 0, 0, 0.0};
+  // (HD) lane b: block b is a calendar seasonal; calmask: bit b the same, wave-uniform
+  const bool cals_l = HD && lane < nb && ssg_is_calendar(Q.blk[lane]);
+  const unsigned calmask = HD ? (unsigned)__ballot(cals_l) : 0u;
+  // Blocks::moving() with the calendar seasonals' bits read from the step's calendar entry `w` (wave-uniform)
+  auto hmoving = [&](unsigned long long w) -> unsigned {
+    const unsigned mv = B.moving();
+    const bool on = cals_l && ((w >> (8 * (lane & 7))) & (unsigned long long)SSG_CAL_SEASON) != 0;
+    return (mv & ~calmask) | (unsigned)__ballot(on);
+  };
+  // the entry after step tt's, one per lane: read past T where the table goes on (the last transition's
+  // season flag), with the holidays' bytes switched off there as they always were
+  auto cal_next = [&](int tt, bool in) -> unsigned long long {
+    unsigned long long w = SSG_CAL_NONE;
+    if (in && tt + 1 < P.cal_count) w = P.cal[tt + 1];
+    if (tt + 1 >= T) w |= SSG_CAL_NONE;
+    return w;
+  };
+  // how many of the times 1 .. t start a new season of calendar seasonal b (0 <= t < cal_count)
+  // (the prefix counts sit behind the table's cal_count words)
+  auto cal_started = [&](int b, int t) -> int {
+    return reinterpret_cast<const int32_t *>(P.cal + P.cal_count)[(size_t)b * (size_t)P.cal_count + t];
+  };
+  // after seek(B, LI, T, -1): the calendar seasonals' cursors of time T
+  auto seek_end_calendar = [&]() {
+    if (!HD || !calmask) return;
+    if (cals_l) {
+      const int n = Blocks::dim_of(B.desc);
+      int q = cal_started(lane, T - 1);
+      if (T < P.cal_count && ((P.cal[T] >> (8 * (lane & 7))) & (unsigned long long)SSG_CAL_SEASON)) ++q;
+      q %= n;
+      B.rc = (B.rc & 0xffffu) | ((unsigned)(q == 0 ? 0 : n - q) << 16);
+    }
+    const unsigned mine = (unsigned)__shfl((int)B.rc, LI.blk < 0 ? 0 : LI.blk);
+    __builtin_amdgcn_wave_barrier();
+    if (LI.kind == SSG_SEASONAL) LI.cur = (int)(mine >> 16);
+  };
   bool hol_l = false;     // (HD) the lane holds a component of a random-walk holiday
   int hsh_l = 0;          // ... whose positions are the bits from here of a calendar entry
   int var_l = 0;          // the variance parameter behind this lane's state error
@@ -393,6 +442,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
     while (sm) {
       const int b = __ffs((int)sm) - 1;
       sm &= sm - 1;
+      if (HD && ((calmask >> b) & 1u)) { o += t < 0 ? 0 : cal_started(b, t); continue; }
       const unsigned dpw = (unsigned)__builtin_amdgcn_readlane((int)B.dp, b);
       o += seasons_started(t, (int)(dpw & 0xffffu), (int)(dpw >> 16));
     }
@@ -436,12 +486,12 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       if (QT) { qa_l = lane < nstep ? qsig0 / qw0[tt] : 0.0; qb_l = lane < nstep ? qsig1 / qw1[tt] : 0.0; }
       // (HD: the calendar's entries t -- Z_t -- and t + 1 -- RQR_t -- of the block's steps, one per lane)
       unsigned long long cw_l = SSG_CAL_NONE, cn_l = SSG_CAL_NONE;
-      if (HD) { if (lane < nstep) cw_l = P.cal[tt]; if (lane < nstep && tt + 1 < T) cn_l = P.cal[tt + 1]; }
+      if (HD) { if (lane < nstep) cw_l = P.cal[tt]; cn_l = cal_next(tt, lane < nstep); }
       double F_l = 1.0;
 #pragma nounroll
       for (int s = 0; s < nstep; ++s) {
         const bool obs = __builtin_amdgcn_readlane(ob_l, s) != 0;
-        const unsigned mv = B.moving();
+        const unsigned mv = (HD ? hmoving(rlw(cn_l, s)) : B.moving());   // (the transition OUT of t)
         const double qa = QT ? rl(qa_l, s) : 0.0, qb = QT ? rl(qb_l, s) : 0.0;
         const unsigned long long cw = HD ? rlw(cw_l, s) : 0ull, cn = HD ? rlw(cn_l, s) : 0ull;
         if (HD && hol_l) LI.cur = hpos_l(cw);
@@ -778,7 +828,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
           advance(B, LI, 0u, lane);
         } else {
           // simulate_next_state: T alpha + eta
-          const unsigned mv = B.moving();
+          const unsigned mv = (HD ? hmoving(rlw(cw_l, s)) : B.moving());   // (the transition INTO t)
           const unsigned act = mv & seas_active;
           alpha = vecT<SMALL, GLOB>(B, LI, alpha, lane, mv);
           advance(B, LI, mv, lane);
@@ -835,15 +885,15 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       blk_load(blk, gK + (size_t)tb * m, nstep * m, lane);
       const double w_l = in_l ? w0[tt] : 0.0, F_l = in_l ? sres[tt] : 1.0;
       const int ob_l = (in_l && P.observed[tt]) ? 1 : 0;
-      unsigned long long cw_l = SSG_CAL_NONE;
-      if (HD && in_l) cw_l = P.cal[tt];
+      unsigned long long cw_l = SSG_CAL_NONE, cn_l = SSG_CAL_NONE;
+      if (HD) { if (in_l) cw_l = P.cal[tt]; cn_l = cal_next(tt, in_l); }
       double ef_l = 0.0;
 #pragma nounroll
       for (int s = 0; s < nstep; ++s) {
         if (HD) { const unsigned long long cw = rlw(cw_l, s); if (hol_l) LI.cur = hpos_l(cw); }
         const double K = mylane ? blk[s * m + lane] : 0.0;
         const bool obs = __builtin_amdgcn_readlane(ob_l, s) != 0;
-        const unsigned mv = B.moving();
+        const unsigned mv = (HD ? hmoving(rlw(cn_l, s)) : B.moving());   // (the transition OUT of t)
         const double e = obs ? rl(w_l, s) - zdot<SMALL, GLOB>(LI, delta, lane) : 0.0;
         if (lane == s) ef_l = obs ? e / F_l : 0.0;
         delta = vecT<SMALL, GLOB>(B, LI, delta, lane, mv) + K * e;
@@ -862,6 +912,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
   // layout of step t + 1.  What the correction pass needs of r_t is its value at the rows
   // that carry state error: one series per variance parameter.
   seek(B, LI, T, -1);   // (the layout of time T, the transition T - 1)
+  seek_end_calendar();
   for (int tb = ((T - 1) / BL) * BL; tb >= 0; tb -= BL) {
     const int tt = tb + lane;
     const int nstep = (T - tb < BL) ? T - tb : BL;
@@ -870,11 +921,11 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
     const double ef_l = in_l ? w0[tt] : 0.0;
     // (HD: the calendar's entries t -- Z_t -- and t + 1 -- the row the error of t -> t + 1 lands on)
     unsigned long long cw_l = SSG_CAL_NONE, cn_l = SSG_CAL_NONE;
-    if (HD) { if (in_l) cw_l = P.cal[tt]; if (in_l && tt + 1 < T) cn_l = P.cal[tt + 1]; }
+    if (HD) { if (in_l) cw_l = P.cal[tt]; cn_l = cal_next(tt, in_l); }
 #pragma nounroll
     for (int s = nstep - 1; s >= 0; --s) {
       const double K = mylane ? blk[s * m + lane] : 0.0;
-      const unsigned mv = B.moving();
+      const unsigned mv = (HD ? hmoving(rlw(cn_l, s)) : B.moving());   // (the transition t -> t + 1)
       const unsigned long long cw = HD ? rlw(cw_l, s) : 0ull, cn = HD ? rlw(cn_l, s) : 0ull;
       // r_t at the error rows (layout of t + 1), one value per step and variance parameter
       if (HD && hol_l) {
@@ -937,7 +988,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       for (int s = 0; s < nstep; ++s) {
         const double ap = mylane ? buf[s * m + lane] : 0.0;
         if (tb + s > 0) {
-          const unsigned mv = B.moving();
+          const unsigned mv = (HD ? hmoving(rlw(cw_l, s)) : B.moving());   // (the transition INTO t)
           mc = vecT<SMALL, GLOB>(B, LI, mc, lane, mv);
           advance(B, LI, mv, lane);
           // + RQR_{t-1} r_{t-1}
@@ -1006,7 +1057,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
         unsigned mv = 0;
         double tot_then = 0.0;   // seasonal: sum of the block at t - 1 (kept by the lanes of the block)
         if (tb + s > 0) {
-          mv = B.moving();
+          mv = (HD ? hmoving(rlw(cw_l, s)) : B.moving());   // (the transition INTO t)
           // (the seasonal models' observe_state needs the sum of `then` over the block)
           unsigned sm = mv & B.seasmask;
           while (sm) {
@@ -1153,7 +1204,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       const double tot = wsum<SMALL>(LI.blk == b ? suf_l : 0.0);
       const unsigned dpw = (unsigned)__builtin_amdgcn_readlane((int)B.dp, b);
       if (lane == f) {
-        M.var_n[at] = (double)seasons_started(T - 1, (int)(dpw & 0xffffu), (int)(dpw >> 16));
+        M.var_n[at] = (HD && ((calmask >> b) & 1u)) ? (double)cal_started(b, T - 1)
+                                                     : (double)seasons_started(T - 1, (int)(dpw & 0xffffu), (int)(dpw >> 16));
         M.var_ss[at] = tot;
       }
     } else {

@@ -1,5 +1,6 @@
-// The holiday instances of the general structural kernel (ssg_simsmooth.h): a list that holds a
-// random-walk holiday block, whose observation row and state-error row move with a calendar.
+// The calendar instances of the general structural kernel (ssg_simsmooth.h): a list that holds a
+// random-walk holiday block, whose observation row and state-error row move with a calendar, or a
+// calendar seasonal, whose season starts are read from the same table.
 #include "ssg_simsmooth.h"
 
 namespace boom_amd {

@@ -386,6 +386,26 @@ PYBIND11_MODULE(_boom, boom) {
       .def("set_prior", &RandomWalkHolidayStateModel::set_prior, py::arg("df"), py::arg("sigma_guess"),
            py::arg("sigma_upper_limit") = std::numeric_limits<double>::infinity());
 
+  py::class_<MonthlyAnnualCycle, Ptr<MonthlyAnnualCycle>>(
+      boom, "MonthlyAnnualCycle",
+      "MonthlyAnnualCycle(year, month, day): a month-of-year effect for daily data, 12 seasons that start on the "
+      "first day of a month.  BayesBoom's constructor takes a Date; this module has no Date class, so it takes the "
+      "date of the first observation as three integers.  set_forecast_horizon: the steps past the series that the "
+      "block's calendar covers (366 by default).")
+      .def(py::init<int, int, int>(), py::arg("year"), py::arg("month"), py::arg("day"))
+      .def_property_readonly("state_dimension", &MonthlyAnnualCycle::state_dimension)
+      .def_property_readonly("nseasons", &MonthlyAnnualCycle::nseasons)
+      .def("set_forecast_horizon", &MonthlyAnnualCycle::set_forecast_horizon, py::arg("steps"))
+      .def("calendar", [](const MonthlyAnnualCycle &m, int length) {
+             const std::vector<uint8_t> f = m.calendar(length);
+             return std::vector<int>(f.begin(), f.end());
+           }, py::arg("length"), "the season-start flags of a series of `length` time points and the horizon beyond it")
+      .def("set_sigsq", &MonthlyAnnualCycle::set_sigsq)
+      .def("set_initial_state_mean", [](MonthlyAnnualCycle &m, const NpArray &v) { m.set_initial_state_mean(vector_from(v)); })
+      .def("set_initial_state_variance", &MonthlyAnnualCycle::set_initial_state_variance)
+      .def("set_prior", &MonthlyAnnualCycle::set_prior, py::arg("df"), py::arg("sigma_guess"),
+           py::arg("sigma_upper_limit") = std::numeric_limits<double>::infinity());
+
   py::class_<ArStateModel, Ptr<ArStateModel>>(boom, "ArStateModel")
       .def(py::init<int>(), py::arg("number_of_lags"))
       .def_property_readonly("state_dimension", &ArStateModel::state_dimension)
@@ -482,6 +502,7 @@ PYBIND11_MODULE(_boom, boom) {
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<SemilocalLinearTrendStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<StudentLocalLinearTrendStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<RandomWalkHolidayStateModel> &s) { m.add_state(s); })
+      .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<MonthlyAnnualCycle> &s) { m.add_state(s); })
       .def("student_trend_nu", [](const StateSpaceRegressionModel &m, int chain) { return to_numpy(m.student_trend_nu(chain)); },
            py::arg("chain") = 0, "(nu_level, nu_slope) of the StudentLocalLinearTrendStateModel in one chain's draw")
       .def("student_trend_weights", [](const StateSpaceRegressionModel &m, int chain) {

@@ -635,6 +635,23 @@ int ba_ss_set_local_level(ba_engine *e, double level_df,
  *           the series, ba_ss_forecast one shorter than the series and the horizon.  Refused: the
  *           Student-t / Poisson / logit observation families, a list that also holds kind 8.   width
  * Several kind 10 models may be added, one per holiday, and may be active on the same day.
+ *   kind 11 the calendar seasonal: SeasonalStateModelBase whose new_season(t) is read from a
+ *           calendar -- MonthlyAnnualCycle (StateModels/SeasonalStateModel.hpp, bsts
+ *           AddMonthlyAnnualCycle) is the one of 12 seasons whose seasons start on the first day
+ *           of a month -- + ZeroMeanGaussianConjSampler, as bsts builds it.  iparams =
+ *           {nseasons}, nseasons >= 2; nseasons - 1 components, Z = e_0.  Kind 3 in everything
+ *           (initial state, prior, sigma upper limit, a fixed sigma) but this: the step t -> t + 1
+ *           has the seasonal transition and RQR = sigma^2 e_0 e_0' where the block's calendar says
+ *           time t + 1 starts a new season, and is the identity without error elsewhere;
+ *           observe_state takes now[0] + sum(then) at the t >= 1 that start a season.  The
+ *           calendar comes through ba_ss_set_season_calendar (below); a missing or short one is
+ *           refused as kind 10's is.  RNG: kind 3's conventions exactly -- one stream-2 normal
+ *           per step into a new season, none when sigma = 0; sampler id 7 + 16 per earlier
+ *           seasonal model of kind 3 or 11 -- so a regular calendar (t % duration == phase) draws
+ *           what kind 3 draws, bit for bit.  Refused: the Student-t / Poisson / logit
+ *           observation families, a list that also holds kind 8.                            nseasons
+ * With kinds 1 to 11 every Gaussian Add* component of bsts can be added but the regression-holiday
+ * and dynamic-regression families (state models with data of their own).
  * iparams is ignored for kinds 1, 2 and 5 (may be NULL).  The var_* arrays hold one entry
  * per variance parameter of the model (two for kinds 2 and 7: level, slope; one otherwise):
  * ChisqModel(df, sigma_guess) prior, sigma upper limit (infinity: none), initial sigma.
@@ -645,7 +662,7 @@ int ba_ss_set_local_level(ba_engine *e, double level_df,
  * variance's diagonal; positive, a local level's may be 0).  Limits: state dimension
  * <= 64, 8 state models, 16 variance parameters, 4 autoregression models.
  * RNG streams: variance parameter v of a model reads the chain's sampler id 1 (level),
- * 6 (slope), 7 (seasonal), 8 (a random-walk holiday), 13 (trig), 14 (a semilocal slope: NonzeroMeanAr1Sampler) or 12 (ArPosteriorSampler: the proposals' normals, then the
+ * 6 (slope), 7 (seasonal, kinds 3 and 11: one family), 8 (a random-walk holiday), 13 (trig), 14 (a semilocal slope: NonzeroMeanAr1Sampler) or 12 (ArPosteriorSampler: the proposals' normals, then the
  * sigma draw -- the reference takes the proposals from GlobalRng::rng and the rest from
  * the sampler's generator) + 16 for every earlier model of the same family (local level
  * and local linear trend are one family); the state draw reads stream 2.  A Student local linear
@@ -791,6 +808,22 @@ int ba_ss_get_ar_inclusion(ba_engine *e, int64_t chain, int32_t block, uint8_t *
  * yet); position may be NULL to ask for the count alone, else it has room for that many. */
 int ba_ss_set_holiday_calendar(ba_engine *e, int32_t block, const int32_t *position, int64_t count);
 int ba_ss_get_holiday_calendar(ba_engine *e, int32_t block, int32_t *position, int64_t *count);
+
+/* The calendar of a calendar seasonal (state model `block`, kind 11): entry t of `new_season` is 1
+ * where time t starts a new season, else 0; any other value is refused with a text.  Entry 0 is
+ * accepted and never read (no step leads into time 0).  `count` must cover the series (count >= T)
+ * for a sweep, ba_ss_impute_state, ba_ss_draw_next and ba_ss_prediction_errors; ba_ss_forecast needs
+ * count >= T + horizon: forecast step i uses the transition of time T - 2 + i, that is entry
+ * T - 1 + i.  One calendar per block, shared by all chains.  Under a look-ahead the setter is a
+ * mutator like the others.  The getter is shaped like ba_ss_get_holiday_calendar.  Neither pair
+ * accepts a block of the other kind.
+ * ba_monthly_cycle_calendar fills MonthlyAnnualCycle's calendar: out[t] = 1 where the day t days
+ * after the date (year, month, day) of the first observation is the first day of a month, in the
+ * proleptic Gregorian calendar; a date that does not exist is refused.  Host only: it needs no
+ * engine and no device. */
+int ba_ss_set_season_calendar(ba_engine *e, int32_t block, const uint8_t *new_season, int64_t count);
+int ba_ss_get_season_calendar(ba_engine *e, int32_t block, uint8_t *new_season, int64_t *count);
+int ba_monthly_cycle_calendar(int32_t year, int32_t month, int32_t day, int64_t count, uint8_t *out);
 
 /* ---- bsts(family = "student"): StateSpaceStudentRegressionModel with
  * StateSpaceStudentPosteriorSampler (Models/StateSpace/StateSpaceStudentRegressionModel.cpp,

@@ -422,6 +422,46 @@ class SeasonalStateModel {
   double sigma_ = 1.0, df_ = 1.0, guess_ = 1.0, upper_ = infinity();
 };
 
+// MonthlyAnnualCycle with a ZeroMeanGaussianConjSampler (StateModels/SeasonalStateModel.hpp; bsts
+// AddMonthlyAnnualCycle): state model kind 11 with 12 seasons, a month-of-year effect for daily data.
+// A new season starts where the day is the first of a month.  There is no Date class here: the
+// constructor takes the date of the first observation as (year, month, day), and
+// ba_monthly_cycle_calendar turns it into the block's calendar when the list goes to the device -- the
+// series' length and forecast_horizon() entries beyond it (set_forecast_horizon: as many steps as a
+// forecast will ask for; a year by default).
+class MonthlyAnnualCycle {
+ public:
+  MonthlyAnnualCycle(int year, int month, int day) : year_(year), month_(month), day_(day) {
+    uint8_t probe = 0;
+    if (ba_monthly_cycle_calendar(year, month, day, 1, &probe) != BA_OK) report_error(ba_last_error());
+    a0_ = Vector(11, 0.0);
+    P0_ = Vector(11, 1.0);
+  }
+  int state_dimension() const { return 11; }
+  int nseasons() const { return 12; }
+  int forecast_horizon() const { return horizon_; }
+  void set_forecast_horizon(int steps) {
+    if (steps < 0) report_error("the forecast horizon must not be negative");
+    horizon_ = steps;
+  }
+  // the calendar of a series of `length` time points (and the horizon beyond it)
+  std::vector<uint8_t> calendar(int length) const {
+    std::vector<uint8_t> flags((size_t)length + (size_t)horizon_, 0);
+    if (!flags.empty() && ba_monthly_cycle_calendar(year_, month_, day_, (int64_t)flags.size(), flags.data()) != BA_OK)
+      report_error(ba_last_error());
+    return flags;
+  }
+  void set_sigsq(double s) { sigma_ = std::sqrt(s); }
+  void set_initial_state_mean(const Vector &m) { a0_ = m; }
+  void set_initial_state_variance(double v) { P0_ = Vector(11, v); }
+  void set_prior(double df, double sigma_guess, double sigma_upper_limit = infinity()) {
+    df_ = df; guess_ = sigma_guess; upper_ = sigma_upper_limit;
+  }
+  int year_, month_, day_, horizon_ = 366;
+  Vector a0_, P0_;
+  double sigma_ = 1.0, df_ = 1.0, guess_ = 1.0, upper_ = infinity();
+};
+
 // RandomWalkHolidayStateModel with a ZeroMeanGaussianConjSampler (StateModels/
 // RandomWalkHolidayStateModel.cpp; bsts AddRandomWalkHoliday): state model kind 10.  There is no
 // Date / Holiday layer here: where the reference's constructor takes (holiday, time_zero), this one
@@ -613,6 +653,7 @@ class StateSpaceRegressionModel : public Model {
   void add_state(const Ptr<SemilocalLinearTrendStateModel> &s) { Entry e; e.kind = 7; e.semilocal = s; models_.push_back(e); finalized_ = false; }
   void add_state(const Ptr<StudentLocalLinearTrendStateModel> &s) { Entry e; e.kind = 8; e.student_trend = s; models_.push_back(e); finalized_ = false; }
   void add_state(const Ptr<RandomWalkHolidayStateModel> &s) { Entry e; e.kind = 10; e.holiday = s; models_.push_back(e); finalized_ = false; }
+  void add_state(const Ptr<MonthlyAnnualCycle> &s) { Entry e; e.kind = 11; e.monthly = s; models_.push_back(e); finalized_ = false; }
   int number_of_state_models() const { return (int)models_.size(); }
   bool has_student_trend() const {
     for (const Entry &e : models_) if (e.kind == 8) return true;
@@ -625,7 +666,7 @@ class StateSpaceRegressionModel : public Model {
     int m = 0;
     for (const Entry &e : models_)
       m += (e.kind == 1 || e.kind == 5) ? 1 : (e.kind == 2 || e.kind == 8) ? 2 : e.kind == 3 ? e.seasonal->state_dimension()
-           : e.kind == 6 ? e.trig->state_dimension() : e.kind == 7 ? 3 : e.kind == 10 ? e.holiday->state_dimension() : e.ar->lags_;
+           : e.kind == 6 ? e.trig->state_dimension() : e.kind == 7 ? 3 : e.kind == 10 ? e.holiday->state_dimension() : e.kind == 11 ? e.monthly->state_dimension() : e.ar->lags_;
     return m;
   }
   void finalize_state() {
@@ -644,6 +685,12 @@ class StateSpaceRegressionModel : public Model {
           const int32_t ip[3] = {s.width_, 0, 0};
           eng_->check(ba_ss_add_state_model(h, 10, ip, &s.df_, &s.guess_, &s.upper_, &s.sigma_, nullptr, s.a0_.data(), s.P0_.data()));
           eng_->check(ba_ss_set_holiday_calendar(h, (int32_t)b, s.positions_.data(), (int64_t)s.positions_.size()));
+        } else if (e.kind == 11) {
+          const MonthlyAnnualCycle &s = *e.monthly;
+          const int32_t ip[3] = {s.nseasons(), 0, 0};
+          const std::vector<uint8_t> flags = s.calendar(T_);
+          eng_->check(ba_ss_add_state_model(h, 11, ip, &s.df_, &s.guess_, &s.upper_, &s.sigma_, nullptr, s.a0_.data(), s.P0_.data()));
+          eng_->check(ba_ss_set_season_calendar(h, (int32_t)b, flags.data(), (int64_t)flags.size()));
         } else if (e.kind == 1) {
           const LocalLevelStateModel &s = *e.level;
           eng_->check(ba_ss_add_state_model(h, 1, nullptr, &s.df_, &s.guess_, &s.upper_, &s.sigma_, nullptr, &s.a0_, &s.P0_));
@@ -834,7 +881,7 @@ class StateSpaceRegressionModel : public Model {
   }
  private:
   struct Entry {
-    int kind = 0;   // 1 local level, 2 local linear trend, 3 seasonal, 4 autoregression, 5 static intercept, 6 trig, 7 semilocal linear trend, 8 Student local linear trend, 10 random-walk holiday
+    int kind = 0;   // 1 local level, 2 local linear trend, 3 seasonal, 4 autoregression, 5 static intercept, 6 trig, 7 semilocal linear trend, 8 Student local linear trend, 10 random-walk holiday, 11 monthly annual cycle (a calendar seasonal)
     Ptr<LocalLevelStateModel> level;
     Ptr<LocalLinearTrendStateModel> trend;
     Ptr<SeasonalStateModel> seasonal;
@@ -844,6 +891,7 @@ class StateSpaceRegressionModel : public Model {
     Ptr<SemilocalLinearTrendStateModel> semilocal;
     Ptr<StudentLocalLinearTrendStateModel> student_trend;
     Ptr<RandomWalkHolidayStateModel> holiday;
+    Ptr<MonthlyAnnualCycle> monthly;
   };
   int student_trend_block() const {
     for (size_t b = 0; b < models_.size(); ++b)
