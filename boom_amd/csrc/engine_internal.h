@@ -5,7 +5,13 @@
 //                   traces, prediction, check_chain_status
 //   engine_glm.hip  probit, logit, Poisson, Student-t, quantile, multinomial logit (the
 //                   latent-data families)
-//   engine_ss.hip   state space: ba_ss_*, its look-ahead, the round kernel's launches
+//   engine_ss.hip            state space, the core: launch parameters, ss_prepare, data and local level,
+//                            the rounds of a call and the round kernel's launches, the plain accessors
+//   engine_ss_models.hip     the list of state models (its arithmetic: ssg_spec.h, host only), the
+//                            calendars, the Student trend's and the spike-and-slab autoregression's entry points
+//   engine_ss_lookahead.hip  ba_ss_draw_next's look-ahead: record, snapshots, settle
+//   engine_ss_observe.hip    forecasts and one-step prediction errors
+//   engine_ss_family.hip     bsts family = "student", "poisson", "logit"
 // The launchers' declarations: of the products in products.h, of the rest below.  The
 // imputation kernels' parameters are latent_params.h (the common head) and one header per
 // family; their shared device code is latent_device.h.
@@ -30,6 +36,7 @@
 #include "products.h"
 #include "quantile_params.h"
 #include "ss_filter_params.h"
+#include "ssg_spec.h"
 #include "ssvs_params.h"
 #include "student_params.h"
 
@@ -153,11 +160,19 @@ enum DataKind { DATA_REGRESSION, DATA_STATE_SPACE, DATA_PROBIT, DATA_LOGIT, DATA
                 DATA_SS_LOGIT };
 // the two state space families whose latent data are a value and a precision per step
 inline bool latent_ss_kind(DataKind k) { return k == DATA_SS_POISSON || k == DATA_SS_LOGIT; }
+// the state space data under one of the three observation families with latent data ...
+inline bool ss_family_kind(DataKind k) { return k == DATA_SS_STUDENT || k == DATA_SS_POISSON || k == DATA_SS_LOGIT; }
+// ... as the rule book of the state models names them (ssg_refusal)
+inline SsFamily ss_family(DataKind k) {
+  return k == DATA_SS_STUDENT ? SS_FAMILY_STUDENT : k == DATA_SS_POISSON ? SS_FAMILY_POISSON : k == DATA_SS_LOGIT ? SS_FAMILY_LOGIT : SS_FAMILY_GAUSSIAN;
+}
+// the kinds that hold a series and a state (the Gaussian, the Student-t, the Poisson and the logit observation model)
+inline bool ss_kind(DataKind k) { return k == DATA_STATE_SPACE || ss_family_kind(k); }
 // the latent-data families: the regression runs on every chain's own imputed responses
-inline bool latent_data(DataKind k) { return k == DATA_PROBIT || k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT || k == DATA_SS_STUDENT || k == DATA_SS_POISSON || k == DATA_SS_LOGIT; }
+inline bool latent_data(DataKind k) { return k == DATA_PROBIT || k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT || ss_family_kind(k); }
 // ... and those of them whose V = slab precision + X'WX is every chain's own, built a vector
 // at a time (serve_columns, engine_glm.hip)
-inline bool column_service(DataKind k) { return k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT || k == DATA_SS_STUDENT || k == DATA_SS_POISSON || k == DATA_SS_LOGIT; }
+inline bool column_service(DataKind k) { return k == DATA_LOGIT || k == DATA_POISSON || k == DATA_STUDENT || k == DATA_QUANTILE || k == DATA_MLOGIT || ss_family_kind(k); }
 // the two families whose sigma^2 is every chain's own draw on latent data
 inline bool student_kind(DataKind k) { return k == DATA_STUDENT || k == DATA_SS_STUDENT; }
 
@@ -561,12 +576,41 @@ int build_columns(ba_engine *e, int64_t R);
 int column_buffers(ba_engine *e);
 int upload_latent_data(ba_engine *e, int64_t n, int32_t p, const double *X, const double *y,
                        const double *third, bool squared, int clt_threshold);
+// The rows of chain `chain` of a chains x n buffer from the host, or of every chain when chain == -1
+// (the caller has validated `chain` and waited for the stream).
+inline int write_chain_rows(ba_engine *e, double *buf, int64_t chain, size_t n, const double *src) {
+  const size_t C = (size_t)e->cfg.chains;
+  for (size_t c = chain < 0 ? 0 : (size_t)chain; c < (chain < 0 ? C : (size_t)chain + 1); ++c)
+    HIP_TRY(hipMemcpy(buf + c * n, src, n * 8, hipMemcpyHostToDevice));
+  return BA_OK;
+}
+// the local-level path of a series of at most LM_TP steps runs lane-major
+// (kalman_lm_kernel): its scratch arrays have pitch LM_TP
+inline bool ss_lane_major(const ba_engine &e) { return !e.ssm_set && e.T <= LM_TP; }
+inline size_t ss_pitch(const ba_engine &e) { return ss_lane_major(e) ? (size_t)LM_TP : (size_t)e.T; }
+// the rule book of the state models on this engine's list (ssg_refusal, ssg_spec.h): BA_OK, or the refusal
+inline int ss_refused(const ba_engine *e, DataKind kind, SsgUse use) {
+  const char *text = ssg_refusal(e->ssm_set ? &e->ssg : nullptr, ss_family(kind), use);
+  return text ? fail(BA_E_STATE, text) : BA_OK;
+}
 // engine_ss.hip
+int64_t ssm_work_stride(const ba_engine &e);
+void fill_ss_params(ba_engine *e, SsParams &S);
+bool fill_ar_spike_params(ba_engine *e, ArSpikeParams &U);
+void fill_slt_params(ba_engine *e, SltParams &U);
+int ss_prepare(ba_engine *e, DataKind kind = DATA_STATE_SPACE);
+int ss_sweep_impl(ba_engine *e, int32_t nsweeps, int rec_slot);
 int ss_escalate(ba_engine *e, std::vector<int32_t> &st);
+// engine_ss_models.hip
+int hol_prepare(ba_engine *e, int64_t extra = 0);
+// engine_ss_lookahead.hip
 int ss_la_settle(ba_engine *e);
 bool ss_la_serving(const ba_engine *e);
 int ss_la_wait(ba_engine *e);
 int ss_la_rows(ba_engine *e, int64_t c, bool want_state, const ba_engine::SsLa::Rows **out);
+hipError_t ss_la_record(ba_engine *e, int slot, int round);
+bool ss_la_registered(const ba_engine *e, int64_t c);
+void ss_la_want_state(ba_engine *e, int64_t c);
 }  // namespace boom_amd
 
 struct ApiScope {

@@ -56,7 +56,7 @@ def state_stream(oracle, seed, chain):
 
 # ---- identities ------------------------------------------------------------------------------------
 def steps_per_block(blocks):
-    """ssg_finish's rule (engine_ss.hip): the leading dimension of P and the steps per time block"""
+    """ssg_finish's rule (ssg_spec.h): the leading dimension of P and the steps per time block"""
     m = sum(b["dim"] for b in blocks)
     nerr = sum(b["dim"] if b["kind"] == 6 else (2 if b["kind"] in (2, 7, 8) else 1) for b in blocks)
     nar = sum(b["kind"] in (4, 7) for b in blocks)
