@@ -916,11 +916,20 @@ __device__ __forceinline__ Proposal eval_proposal(const SsvsParams &P, Chain &ch
 // walks are a third of the helper wavefront's sweep and the mask takes a quarter off them.  A
 // template flag, not a run-time choice: the bookkeeping costs the single block of p = 512 one
 // per cent and the headline's instance <4, 2, 2> is compiled without it (docs/TRIED.md).
+// No element is guarded: oth, last, pred and both perm buffers have a spare entry p, the SINK,
+// and a lane whose element is out of range or excluded (t == 0, t >= p, i >= p) takes the sink's
+// INDEX and then reads and writes like every other lane.  (A guard per element becomes an
+// exec-mask block with a wait of its own around every LDS read: section 3.9's serial loads, in
+// LDS.)  The sink is a fixed point of every pass: last[p] = p, pred[p] = NONE.  The groups of
+// reads that are meant to be in flight together are pinned with an empty asm over their registers.
+#define BA_PIN8(a) asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]))
 template <bool MASKED = false>
 __device__ __forceinline__ void parallel_shuffle(Chain &ch, StampCtx &sx) {
   const int p = ch.p, lane = ch.lane;
   constexpr int NONE = 0xFFFF;
-  for (int j = lane; j < p; j += WAVE) ch.last[j] = (uint32_t)NONE;
+  const int SINK = p;
+  for (int j = lane; j <= p; j += WAVE) ch.last[j] = (uint32_t)((j == p) ? SINK : NONE);
+  if (lane == 0) ch.pred[SINK] = (uint16_t)NONE;
   wave_sync();
   HSTAMP(sx, 0);
   // ---- previous step with the same target: rounds of 64 steps over decreasing
@@ -931,33 +940,44 @@ __device__ __forceinline__ void parallel_shuffle(Chain &ch, StampCtx &sx) {
   // left there -- and the array ends up holding each target's smallest step.
   constexpr int RC = 8;
   for (int T0 = p - 1; T0 >= 1; T0 -= RC * WAVE) {
-    int key[RC];
+    // A lane without a step (t < 1) exchanges SINK at last[SINK] and writes pred[SINK] = NONE:
+    // no real target is the sink, so the real targets keep their lane order.  (A round in which
+    // NO lane has a step is skipped, a wave-uniform branch: 64 lanes on one address is the one
+    // exchange that costs more than it saves.)
+    int key[RC], te[RC];
+    uint32_t old[RC];
 #pragma unroll
     for (int r = 0; r < RC; ++r) {
       const int t = T0 - r * WAVE - lane;
-      key[r] = (t >= 1) ? (int)ch.oth[t] : 0;
+      te[r] = (t >= 1) ? t : SINK;
+      key[r] = (int)ch.oth[te[r]];
     }
+    BA_PIN8(key);
 #pragma unroll
     for (int r = 0; r < RC; ++r) {
-      const int t = T0 - r * WAVE - lane;
-      if (t >= 1) {
-        const uint32_t old = __hip_atomic_exchange(&ch.last[key[r]], (uint32_t)t, __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_WAVEFRONT);
-        ch.pred[t] = (uint16_t)old;
-      }
+      key[r] = (te[r] == SINK) ? SINK : key[r];
+      old[r] = (uint32_t)NONE;
+      if (T0 - r * WAVE >= 1)
+        old[r] = __hip_atomic_exchange(&ch.last[key[r]], (uint32_t)te[r], __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WAVEFRONT);
     }
+#pragma unroll
+    for (int r = 0; r < RC; ++r)
+      if (T0 - r * WAVE >= 1) ch.pred[te[r]] = (uint16_t)((te[r] == SINK) ? (uint32_t)NONE : old[r]);
   }
   wave_sync();
   HSTAMP(sx, 1);
   // last[x] = smallest t >= 1 with oth[t] == x.  nxt(t) = smallest t' > t with
-  // oth[t'] == t: last[t] unless that is the self swap t, then pred[t].
-  const int pred0 = ch.last[0];
-  wave_sync();
-  for (int t = lane; t < p; t += WAVE) {
-    if (t >= 1) {
-      const int l = ch.last[t];
-      ch.last[t] = (uint32_t)((l == t) ? (int)ch.pred[t] : l);
-    }
+  // oth[t'] == t: last[t] unless that is the self swap t, then pred[t].  The end of a chain
+  // (NONE) becomes t itself in the same pass.  Entry 0 is not a step: it keeps the first
+  // depositor of position 0 for the gather, and no link points at it.
+  for (int tb = 0; tb < p; tb += WAVE) {
+    const int t = tb + lane;
+    const int te = (t >= 1 && t < p) ? t : SINK;
+    const int l = (int)ch.last[te], pr = (int)ch.pred[te];
+    int nx = (l == te) ? pr : l;
+    nx = (nx == NONE) ? te : nx;
+    ch.last[te] = (uint32_t)nx;
   }
   wave_sync();
   HSTAMP(sx, 2);
@@ -969,37 +989,34 @@ __device__ __forceinline__ void parallel_shuffle(Chain &ch, StampCtx &sx) {
   // (any mix of old and new values still points down the chain).  A lane holds
   // NW steps, their LDS round trips side by side.
   constexpr int NW = 8;
-  for (int t = lane; t < p; t += WAVE) {
-    if (t >= 1) {
-      const uint32_t l = ch.last[t];
-      if (l == (uint32_t)NONE) ch.last[t] = (uint32_t)t;
+  // one pass over block tb: two read groups, NW unconditional writes (r2 is the old value
+  // where nothing moved; the sink stays SINK); true if a link of the block moved
+  auto jump_block = [&](int tb) -> bool {
+    int te[NW], r1[NW], r2[NW];
+#pragma unroll
+    for (int u = 0; u < NW; ++u) {
+      const int t = tb + u * WAVE + lane;
+      te[u] = (t >= 1 && t < p) ? t : SINK;
+      r1[u] = (int)ch.last[te[u]];
     }
-  }
-  wave_sync();
+    BA_PIN8(r1);
+#pragma unroll
+    for (int u = 0; u < NW; ++u) r2[u] = (int)ch.last[r1[u]];
+    BA_PIN8(r2);
+    bool ch_any = false;
+#pragma unroll
+    for (int u = 0; u < NW; ++u) {
+      ch.last[te[u]] = (uint32_t)r2[u];
+      ch_any |= (r2[u] != r1[u]);
+    }
+    const bool any = (__any(ch_any) != 0);
+    wave_sync();
+    return any;
+  };
   if constexpr (!MASKED) {
   for (bool moved = true; moved;) {
     moved = false;
-    for (int tb = 0; tb < p; tb += NW * WAVE) {
-      int r1[NW], r2[NW];
-#pragma unroll
-      for (int u = 0; u < NW; ++u) {
-        const int t = tb + u * WAVE + lane;
-        r1[u] = (t >= 1 && t < p) ? (int)ch.last[t] : 1;
-      }
-#pragma unroll
-      for (int u = 0; u < NW; ++u) r2[u] = (int)ch.last[r1[u]];
-      bool ch_any = false;
-#pragma unroll
-      for (int u = 0; u < NW; ++u) {
-        const int t = tb + u * WAVE + lane;
-        if (t >= 1 && t < p && r2[u] != r1[u]) {
-          ch.last[t] = (uint32_t)r2[u];
-          ch_any = true;
-        }
-      }
-      moved |= (__any(ch_any) != 0);
-      wave_sync();
-    }
+    for (int tb = 0; tb < p; tb += NW * WAVE) moved |= jump_block(tb);
   }
   } else {
   unsigned long long active = ~0ull;   // (bit b: block b still moving; more than 64 blocks share bit 63)
@@ -1008,49 +1025,43 @@ __device__ __forceinline__ void parallel_shuffle(Chain &ch, StampCtx &sx) {
     for (int tb = 0, b = 0; tb < p; tb += NW * WAVE, ++b) {
       const unsigned long long bit = 1ull << (b < 63 ? b : 63);
       if (!(active & bit)) continue;
-      int r1[NW], r2[NW];
-#pragma unroll
-      for (int u = 0; u < NW; ++u) {
-        const int t = tb + u * WAVE + lane;
-        r1[u] = (t >= 1 && t < p) ? (int)ch.last[t] : 1;
-      }
-#pragma unroll
-      for (int u = 0; u < NW; ++u) r2[u] = (int)ch.last[r1[u]];
-      bool ch_any = false;
-#pragma unroll
-      for (int u = 0; u < NW; ++u) {
-        const int t = tb + u * WAVE + lane;
-        if (t >= 1 && t < p && r2[u] != r1[u]) {
-          ch.last[t] = (uint32_t)r2[u];
-          ch_any = true;
-        }
-      }
-      if (__any(ch_any) != 0) still |= bit;
-      wave_sync();
+      if (jump_block(tb)) still |= bit;
     }
     active = still;
   }
   }
+  // The gather, three dependent trips per block of NW x 64 positions: A the first depositor
+  // (pred[i]; position 0's is last[0]) and the partner oth[i]; B the end of the depositor's
+  // chain, last[c0] (at the sink where nobody deposited: then the partner's original content
+  // is the source, and slot 0 keeps its own); C the source's value.  i >= p writes the sink.
+  const int pred0 = (int)ch.last[0];
   for (int ib = 0; ib < p; ib += NW * WAVE) {
-    int c0[NW], src[NW];
+    int ie[NW], c0[NW], direct[NW], src[NW], val[NW];
 #pragma unroll
     for (int u = 0; u < NW; ++u) {
       const int i = ib + u * WAVE + lane;
-      c0[u] = (i >= p) ? NONE : ((i == 0) ? pred0 : (int)ch.pred[i]);
+      ie[u] = (i < p) ? i : SINK;
+      c0[u] = (int)ch.pred[ie[u]];
+      direct[u] = (int)ch.oth[ie[u]];
     }
+    BA_PIN8(c0);
+    BA_PIN8(direct);
 #pragma unroll
     for (int u = 0; u < NW; ++u) {
       const int i = ib + u * WAVE + lane;
-      // nobody deposited anything: the partner's original content (slot 0 keeps its own)
-      const int direct = (i >= p || i == 0) ? 0 : (int)ch.oth[i];
-      const int via = (int)ch.last[c0[u] == NONE ? 0 : c0[u]];
-      src[u] = (c0[u] == NONE) ? direct : via;
+      c0[u] = (i == 0) ? pred0 : ((i < p) ? c0[u] : NONE);
+      direct[u] = (i == 0) ? 0 : ((i < p) ? direct[u] : SINK);
+      src[u] = (int)ch.last[c0[u] == NONE ? SINK : c0[u]];
     }
+    BA_PIN8(src);
 #pragma unroll
     for (int u = 0; u < NW; ++u) {
-      const int i = ib + u * WAVE + lane;
-      if (i < p) dst[i] = src_perm[src[u]];
+      src[u] = (c0[u] == NONE) ? direct[u] : src[u];
+      val[u] = (int)src_perm[src[u]];
     }
+    BA_PIN8(val);
+#pragma unroll
+    for (int u = 0; u < NW; ++u) dst[ie[u]] = (uint16_t)val[u];
   }
   wave_sync();
   lds_u16 *tmp = ch.perm;
@@ -1058,6 +1069,7 @@ __device__ __forceinline__ void parallel_shuffle(Chain &ch, StampCtx &sx) {
   ch.perm_alt = tmp;
   HSTAMP(sx, 3);
 }
+#undef BA_PIN8
 
 // k standard normals in stream order (distributions/mvn.cpp:114-122), lane m
 // receives z_m.  Seven times out of eight Kinderman-Ramage takes its first

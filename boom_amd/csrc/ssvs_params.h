@@ -241,7 +241,9 @@ static inline __host__ __device__ SsvsLds ssvs_lds_layout(int p, int kcap) {
   SsvsLds L;
   const uint32_t nb = (uint32_t)kcap / 8;
   const uint32_t fac = nb * (nb + 1) / 2 * 64 * 8;
-  const uint32_t pv = (((uint32_t)p * 2) + 15u) & ~15u;
+  // (p + 1 entries: the permutation work arrays end in a spare one, the sink that
+  // parallel_shuffle's out-of-range lanes read and write instead of skipping the access)
+  const uint32_t pv = ((((uint32_t)p + 1u) * 2) + 15u) & ~15u;
   uint32_t o = 0;
   L.Lv = o;    o += fac;
   L.La = o;    o += fac;
@@ -275,7 +277,9 @@ struct SsvsBigLds {
 };
 static inline __host__ __device__ SsvsBigLds ssvs_big_lds_layout(int p, int kcap) {
   SsvsBigLds L;
-  const uint32_t pv = (((uint32_t)p * 2) + 15u) & ~15u;
+  // (p + 1 entries: the permutation work arrays end in a spare one, the sink that
+  // parallel_shuffle's out-of-range lanes read and write instead of skipping the access)
+  const uint32_t pv = ((((uint32_t)p + 1u) * 2) + 15u) & ~15u;
   uint32_t o = 0;
   L.tile = o;  o += 36 * 64 * 8;            // lower block-triangle of 8 x 8 blocks
   L.rdt = o;   o += 64 * 8;

@@ -345,10 +345,16 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
 
   PSTAMP(4);
   while (status == CHAIN_OK) {
+#ifdef BA_ROUND_KERNEL   // (the bsts round's <2, 1, 1>: its indices are made opaque per round)
     if constexpr ((W > 1 && !(NB == 4 && W == 2)) || (W == 1 && NB >= 4) || (MLVS && NB == 2)) {
-      // (every multi-wave instance but the headline's <4, 2, 2>, which needs no scratch as it
-      // is -- and the MLVS instance <2, 1, 1>, which took 68 B/lane of scratch when the rebuild
-      // site grew the partial rebuild and needs none this way: what the compiler derives
+#else
+    constexpr bool PLAIN_211 = NB == 2 && W == 1;
+    if constexpr ((W > 1 && !(NB == 4 && W == 2)) || (W == 1 && NB >= 4) || (MLVS && NB == 2) || PLAIN_211) {
+#endif
+      // (every instance but the headline's <4, 2, 2>, which needs no scratch as it
+      // is -- the MLVS instance <2, 1, 1> took 68 B/lane of scratch when the rebuild
+      // site grew the partial rebuild, the plain <2, 1, 1> the same 68 B when the shuffle's
+      // gather took its reads in groups, and neither needs any this way: what the compiler derives
       // from the lane number once before this loop
       // -- two dozen per-lane addresses -- it then keeps in scratch memory for the whole launch;
       // made opaque per pass of the state machine, they are recomputed where they are used)

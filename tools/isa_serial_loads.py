@@ -6,17 +6,49 @@ round trips to L2 / HBM that the source did not ask for -- conditional loads sun
 select that consumes them, loads parked in scratch one at a time, load / store / load / store
 copies.  Round 6 found three in the bsts round kernel (10 us of a 103 us round).
 
-usage: isa_serial_loads.py file.s [min_chain=2]
+usage: isa_serial_loads.py file.s [min_chain=2] [--lds]
 (compile with -gline-tables-only and the chains come with the source lines of their loads)
+
+--lds reports the same thing one level down, and nothing else: LDS reads (ds_read*) that are
+each followed by a full wait (s_waitcnt lgkmcnt(0)) before the next LDS read is issued.  A chain
+is a run of CONSECUTIVE reads of that kind, however far apart they stand: a read that is not
+waited for before the next one goes out (a group of reads in flight together) ends the run, and
+so does the end of a kernel.  A group of N reads with one wait counts one, its last read.
 """
 import bisect
 import re
 import sys
 
 
+def lds_chains(code):
+    """runs of consecutive ds_read* that are each waited for (lgkmcnt(0)) before the next one"""
+    clusters, run, pending = [], [], None
+
+    def close():
+        if run:
+            clusters.append(list(run))
+            del run[:]
+    for i, t in code:
+        if t.startswith("ds_read"):
+            if pending is not None:   # the read before this one is still in flight: no chain through it
+                close()
+            pending = i
+        elif t.startswith("s_waitcnt") and "lgkmcnt(0)" in t:
+            if pending is not None:
+                run.append(pending)
+                pending = None
+        elif t.startswith("s_endpgm"):
+            pending = None
+            close()
+    close()
+    return clusters
+
+
 def main():
-    path = sys.argv[1]
-    min_chain = int(sys.argv[2]) if len(sys.argv) > 2 else 2
+    args = [a for a in sys.argv[1:] if a != "--lds"]
+    lds = "--lds" in sys.argv[1:]
+    path = args[0]
+    min_chain = int(args[1]) if len(args) > 1 else 2
     lines = open(path).read().split("\n")
     kern_at = [i for i, l in enumerate(lines) if l.strip().startswith(".amdhsa_kernel")]
     kern_name = [lines[i].split()[-1] for i in kern_at]
@@ -24,7 +56,7 @@ def main():
     is_load = lambda t: t.startswith(("global_load", "buffer_load", "scratch_load", "flat_load"))
     ev = []
     for n, (i, t) in enumerate(code):
-        if not is_load(t):
+        if lds or not is_load(t):
             continue
         for m in range(n + 1, min(n + 8, len(code))):
             tt = code[m][1]
@@ -39,6 +71,8 @@ def main():
             clusters[-1].append(e)
         else:
             clusters.append([e])
+    if lds:
+        clusters = lds_chains(code)
     depth_re = re.compile(r"Depth=(\d+)")
     # .loc directives: the source line in force at every line of the assembly
     files = {}
