@@ -190,6 +190,9 @@ SIGNATURES = {
     "ba_ss_set_season_calendar": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.c_int64]),
     "ba_ss_get_season_calendar": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_int64)]),
     "ba_monthly_cycle_calendar": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_uint8)]),
+    "ba_ss_add_dynamic_regression": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "ba_ss_set_dynamic_predictors": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int64]),
+    "ba_ss_get_dynamic_predictors": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_int64)]),
     "ba_ss_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
     "ba_ss_prediction_errors": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp]),
     "ba_ss_student_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
@@ -857,7 +860,10 @@ class Engine:
         11 or "calendar_seasonal": nseasons and, optionally, calendar -- ss_set_season_calendar's flags;
         "monthly": the calendar seasonal of 12 seasons that start on the first day of a month, with
         first_date = (year, month, day) of the first observation and, optionally, calendar_length (the
-        series' length and any forecast horizon; default: the series' length + 366)), nseasons, duration, t0, lags, df, sigma_guess, sigma_upper_limit, initial_sigma
+        series' length and any forecast horizon; default: the series' length + 366);
+        "dynamic_regression": predictors (rows x d, row t = x_t; rows past the series serve forecasts) and
+        d entries each of df, sigma_guess, sigma_upper_limit, initial_sigma, a0, P0 -- it goes through
+        ba_ss_add_dynamic_regression, a numeric kind 12 to ba_ss_add_state_model, which refuses it), nseasons, duration, t0, lags, df, sigma_guess, sigma_upper_limit, initial_sigma
         (one entry per variance parameter; none for kind 5), initial_phi, rotations (kind 6: the
         (cos, sin) pairs of the transition matrix), a0, P0 (tests/cases.py: general_spec)"""
         self._check(self.lib.ba_ss_clear_state_models(self._h))
@@ -868,6 +874,19 @@ class Engine:
                 b = dict(b, kind=11, nseasons=12, calendar=monthly_cycle_calendar(*b["first_date"], n))
             elif b["kind"] == "calendar_seasonal":
                 b = dict(b, kind=11)
+            elif b["kind"] == "dynamic_regression":
+                x = np.ascontiguousarray(b["predictors"], dtype=np.float64)
+                if x.ndim != 2:
+                    raise ValueError("predictors: a rows x d array")
+                arrs = [np.ascontiguousarray(b[k], dtype=np.float64) for k in
+                        ("df", "sigma_guess", "sigma_upper_limit", "initial_sigma", "a0", "P0")]
+                if any(a.size != x.shape[1] for a in arrs):
+                    raise ValueError("a dynamic regression takes one entry per predictor of df, sigma_guess, "
+                                     "sigma_upper_limit, initial_sigma, a0 and P0")
+                self._check(self.lib.ba_ss_add_dynamic_regression(self._h, x.shape[1], _p(x), x.shape[0],
+                                                                  *[_p(a) for a in arrs]))
+                self._blocks.append(dict(kind="dynamic_regression", nvar=x.shape[1], lags=0))
+                continue
             kind = int(b["kind"])
             ip = np.zeros(4, np.int32)
             if kind == 11:
@@ -1045,6 +1064,22 @@ class Engine:
         pos = np.ascontiguousarray(positions, dtype=np.int32)
         self._check(self.lib.ba_ss_set_holiday_calendar(self._h, block, pos.ctypes.data_as(C.POINTER(C.c_int32)),
                                                         pos.size))
+
+    def ss_set_dynamic_predictors(self, block, predictors):
+        """a dynamic regression's predictors (state model `block`), rows x d: replaced, or extended with the
+        rows a forecast needs (at least T rows; T + horizon for ss_forecast)"""
+        x = np.ascontiguousarray(predictors, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != self._blocks[block]["nvar"]:
+            raise ValueError("predictors: a rows x d array")
+        self._check(self.lib.ba_ss_set_dynamic_predictors(self._h, block, _p(x), x.shape[0]))
+
+    def ss_get_dynamic_predictors(self, block):
+        n = C.c_int64()
+        self._check(self.lib.ba_ss_get_dynamic_predictors(self._h, block, None, C.byref(n)))
+        d = self._blocks[block]["nvar"]
+        x = np.zeros((max(n.value, 1), d))
+        self._check(self.lib.ba_ss_get_dynamic_predictors(self._h, block, _p(x), C.byref(n)))
+        return x[:n.value]
 
     def ss_get_holiday_calendar(self, block):
         n = C.c_int64()

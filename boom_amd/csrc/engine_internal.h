@@ -473,6 +473,12 @@ struct ba_engine {
   // (entry t: 1 where time t starts a new season; empty: not set yet) -- packed into dhol_cal beside the
   // holidays' positions, with their prefix counts behind the table (SsParams::cal)
   std::vector<uint8_t> season_calendar[SSG_MAX_BLOCKS];
+  // DynamicRegressionStateModel (SsgBlock::dynreg): every such block's predictors as the caller gave
+  // them (rows x dim, row-major), and the list's table on the device (SsParams::dyn; dyn_rows rows -- the
+  // shortest block's --, 0: to be packed again)
+  std::vector<double> dyn_predictors[SSG_MAX_BLOCKS];
+  DevBuf<double> ddyn;
+  int64_t dyn_rows = 0;
   // ba_ss_prediction_errors (ss_filter_kernel.hip): its outputs on the device (errors, forecast
   // variances, log likelihoods, the forecast-variance flag), the local-level path's one-block
   // list, and the stream the filter of a look-ahead's recorded draw runs on beside the batch

@@ -68,6 +68,7 @@ void fill_ss_params(ba_engine *e, SsParams &S) {
     S.ssm.ld = e->ssg.ld;
     S.ssm.bl = e->ssg.bl;
     S.ssm.nerr = e->ssg.nerr;
+    S.ssm.ndyn = ssg_dyn_columns(e->ssg);
     if (e->ssg_kernel_choice == 1 || e->ssg_kernel_choice == 3)
       ssg_template_shape(e->ssg, &S.ssm.tpl_trend, &S.ssm.tpl_nseasons, &S.ssm.tpl_ar_lags);
     S.ssm.glob = 0;
@@ -88,6 +89,11 @@ void fill_ss_params(ba_engine *e, SsParams &S) {
     if (ssg_has(e->ssg, SSG_HAS_CALENDAR)) {
       S.cal = e->dhol_cal.ptr;   // (packed by hol_prepare, which every entry point that launches passes first)
       S.cal_count = e->hol_cal_count;
+    }
+    if (ssg_has(e->ssg, SSG_HAS_DYNREG)) {
+      S.dyn = e->ddyn.ptr;   // (packed by hol_prepare too)
+      S.dyn_rows = e->dyn_rows;
+      S.dyn_cols = ssg_dyn_columns(e->ssg);
     }
   }
 }

@@ -94,6 +94,8 @@ hipError_t ss_la_record(ba_engine *e, int slot, int round) {
 // them by the same pass (a field whose live array is not allocated keeps its place).
 //   level (sigsq, n, sumsq) | xty | yty | nobs [| state models: sigsq, n, ss | phi | ar suf]
 //   positions: level | state [| state models' | the autoregressions' inclusion indicators]
+// (a dynamic regression adds nothing: its d variances, statistics and positions sit in the state
+// models' slots, and its predictors are one table for all chains and all draws)
 template <class F>
 static int ss_snap_fields(const ba_engine *e, F f) {
   const size_t C = (size_t)e->cfg.chains, p = (size_t)e->p;

@@ -9,7 +9,38 @@ namespace boom_amd {
 // that covers the series and `extra` steps beyond it (a forecast's horizon); the packed table -- and
 // the calendar seasonals' prefix counts -- go to the device when a calendar has changed.  Nothing
 // runs on a default calendar.
+// The dynamic regressions' predictors the same way: every block's rows cover the series and `extra`
+// steps beyond it; the list's table goes to the device when a block's predictors have changed.
+static int dyn_prepare(ba_engine *e, int64_t extra) {
+  if (!e->ssm_set || !ssg_has(e->ssg, SSG_HAS_DYNREG)) return BA_OK;
+  for (int b = 0; b < e->ssg.nblocks; ++b) {
+    if (!e->ssg.blk[b].dynreg) continue;
+    const int64_t n = (int64_t)e->dyn_predictors[b].size() / e->ssg.blk[b].dim;
+    char buf[240];
+    if (n < (int64_t)e->T) {
+      std::snprintf(buf, sizeof buf, "the predictors of state model %d have %lld rows, the series has %d time points",
+                    b, (long long)n, (int)e->T);
+      return fail(BA_E_STATE, buf);
+    }
+    if (n < (int64_t)e->T + extra) {
+      std::snprintf(buf, sizeof buf, "the predictors of state model %d have %lld rows: a forecast of horizon %lld needs %lld (the series' %d and the horizon)",
+                    b, (long long)n, (long long)extra, (long long)((int64_t)e->T + extra), (int)e->T);
+      return fail(BA_E_INVALID, buf);
+    }
+  }
+  const int64_t rows = ssg_dyn_rows(e->ssg, e->dyn_predictors);   // (the shortest)
+  const size_t count = (size_t)rows * (size_t)ssg_dyn_columns(e->ssg);
+  if (e->dyn_rows == rows && e->ddyn.count == count) return BA_OK;
+  const std::vector<double> table = ssg_pack_predictors(e->ssg, e->dyn_predictors, rows);
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (nothing in flight reads the table that is replaced)
+  HIP_TRY(e->ddyn.resize(count));
+  HIP_TRY(hipMemcpy(e->ddyn.ptr, table.data(), count * 8, hipMemcpyHostToDevice));
+  e->dyn_rows = rows;
+  return BA_OK;
+}
+
 int hol_prepare(ba_engine *e, int64_t extra) {
+  if (int rc = dyn_prepare(e, extra)) return rc;
   if (!e->ssm_set || !ssg_has(e->ssg, SSG_HAS_CALENDAR)) return BA_OK;
   for (int b = 0; b < e->ssg.nblocks; ++b) {
     const bool seas = ssg_is_calendar(e->ssg.blk[b]);
@@ -50,16 +81,20 @@ int hol_prepare(ba_engine *e, int64_t extra) {
 static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const double *var_df,
                    const double *var_sigma_guess, const double *var_sigma_upper_limit,
                    const double *var_initial_sigma, const double *initial_phi,
-                   const double *initial_state_mean, const double *initial_state_variance) {
+                   const double *initial_state_mean, const double *initial_state_variance, int32_t dyn_xdim = 0) {
   const SsgInitial initial{e->ssg_initial_sigsq, e->ssg_initial_phi, e->ar_spike_prior,
                            e->slt_nu_kind, e->slt_nu_a, e->slt_nu_b, e->slt_initial_nu};
   const SsgModelArgs args{iparams, var_df, var_sigma_guess, var_sigma_upper_limit, var_initial_sigma,
                           initial_phi, initial_state_mean, initial_state_variance};
-  const SsgRefusal r = ssg_append(e->ssg, initial, ss_family(e->data_kind), kind, args);
+  // (dyn_xdim > 0: a dynamic regression of that many coefficients, ba_ss_add_dynamic_regression's)
+  const SsgRefusal r = dyn_xdim > 0 ? ssg_append_dynreg(e->ssg, initial, ss_family(e->data_kind), dyn_xdim, args)
+                                    : ssg_append(e->ssg, initial, ss_family(e->data_kind), kind, args);
   if (r.text) return fail(r.code, r.text);
-  // (no calendar yet)
+  // (no calendar and no predictors yet)
   e->hol_calendar[e->ssg.nblocks - 1].clear();
   e->season_calendar[e->ssg.nblocks - 1].clear();
+  e->dyn_predictors[e->ssg.nblocks - 1].clear();
+  e->dyn_rows = 0;
   e->ssm_set = true;
   e->ss_level_set = false;
   e->dss_scratch.release();
@@ -67,8 +102,9 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
 }
 static void ssg_clear(ba_engine *e) {
   e->ssg = SsgSpec{};
-  for (int b = 0; b < SSG_MAX_BLOCKS; ++b) { e->hol_calendar[b].clear(); e->season_calendar[b].clear(); }
+  for (int b = 0; b < SSG_MAX_BLOCKS; ++b) { e->hol_calendar[b].clear(); e->season_calendar[b].clear(); e->dyn_predictors[b].clear(); }
   e->hol_cal_count = 0;
+  e->dyn_rows = 0;
   for (int i = 0; i < 3; ++i) e->ssg_template_var[i] = -1;
   e->ssg_template_ar = -1;
   e->ssm_set = false;
@@ -166,6 +202,53 @@ int ba_ss_get_season_calendar(ba_engine *e, int32_t block, uint8_t *new_season, 
   const std::vector<uint8_t> &c = e->season_calendar[block];
   if (count) *count = (int64_t)c.size();
   if (new_season && !c.empty()) std::memcpy(new_season, c.data(), c.size());
+  return BA_OK;
+}
+
+// DynamicRegressionStateModel(X) with the independent random-walk sampler: a block of its own call,
+// since it cannot exist without its data.  predictors: rows x xdim row-major, row t = x_t.
+int ba_ss_add_dynamic_regression(ba_engine *e, int32_t xdim, const double *predictors, int64_t rows,
+                                 const double *var_df, const double *var_sigma_guess,
+                                 const double *var_sigma_upper_limit, const double *var_initial_sigma,
+                                 const double *initial_state_mean, const double *initial_state_variance) {
+  if (!e) return fail(BA_E_INVALID, "null engine");
+  MUTATE(e);
+  if (!predictors) return fail(BA_E_INVALID, "null argument");
+  if (xdim < 1) return fail(BA_E_INVALID, "a dynamic regression needs at least one predictor");
+  if (rows <= 0) return fail(BA_E_INVALID, "a dynamic regression needs at least one row of predictors");
+  if (ssg_dyn_check(predictors, rows, xdim) >= 0) return fail(BA_E_INVALID, "the predictors of a dynamic regression must be finite");
+  if (e->ss_level_set) ssg_clear(e);   // (a local-level specification is replaced, not extended)
+  e->ss_level_set = false;
+  const int rc = ssg_add(e, SSG_DYNAMIC_REGRESSION, nullptr, var_df, var_sigma_guess, var_sigma_upper_limit,
+                         var_initial_sigma, nullptr, initial_state_mean, initial_state_variance, xdim);
+  if (rc) return rc;
+  e->dyn_predictors[e->ssg.nblocks - 1].assign(predictors, predictors + (size_t)rows * (size_t)xdim);
+  return BA_OK;
+}
+
+// replace a dynamic regression's predictors, or extend them (the rows past T serve forecasts: the
+// reference's add_forecast_data)
+int ba_ss_set_dynamic_predictors(ba_engine *e, int32_t block, const double *predictors, int64_t rows) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!predictors || rows <= 0) return fail(BA_E_INVALID, "bad argument");
+  if (!e->ssm_set || block < 0 || block >= e->ssg.nblocks) return fail(BA_E_INVALID, "state model index out of range");
+  const SsgBlock &k = e->ssg.blk[block];
+  if (!k.dynreg) return fail(BA_E_INVALID, "not a dynamic regression state model");
+  if (ssg_dyn_check(predictors, rows, k.dim) >= 0) return fail(BA_E_INVALID, "the predictors of a dynamic regression must be finite");
+  e->dyn_predictors[block].assign(predictors, predictors + (size_t)rows * (size_t)k.dim);
+  e->dyn_rows = 0;   // (packed again by the next call that launches)
+  return BA_OK;
+}
+
+// predictors == nullptr: the row count alone
+int ba_ss_get_dynamic_predictors(ba_engine *e, int32_t block, double *predictors, int64_t *rows) {
+  if (!e) return fail(BA_E_INVALID, "null engine");
+  if (!e->ssm_set || block < 0 || block >= e->ssg.nblocks) return fail(BA_E_INVALID, "state model index out of range");
+  if (!e->ssg.blk[block].dynreg) return fail(BA_E_INVALID, "not a dynamic regression state model");
+  const std::vector<double> &c = e->dyn_predictors[block];
+  if (rows) *rows = (int64_t)c.size() / e->ssg.blk[block].dim;
+  if (predictors && !c.empty()) std::memcpy(predictors, c.data(), c.size() * sizeof(double));
   return BA_OK;
 }
 
@@ -280,12 +363,13 @@ int ba_ss_get_state_model(ba_engine *e, int64_t chain, int32_t block, double *va
   }
   int rc = ba_sync(e);
   if (rc) return rc;
-  HIP_TRY(pinned_reserve(e, (6 + AR_MAX + AR_SUF_STRIDE) * 8));
-  double *hv = (double *)e->pinned, *hphi = hv + 6, *hsuf = hphi + AR_MAX;
+  // (variances, n, sums of squares: up to SSG_MAX_VAR each -- a dynamic regression's d)
+  HIP_TRY(pinned_reserve(e, (3 * SSG_MAX_VAR + AR_MAX + AR_SUF_STRIDE) * 8));
+  double *hv = (double *)e->pinned, *hphi = hv + 3 * SSG_MAX_VAR, *hsuf = hphi + AR_MAX;
   const size_t at = (size_t)chain * SSG_MAX_VAR + k.var0;
   HIP_TRY(hipMemcpyAsync(hv, e->dssm_sigsq.ptr + at, (size_t)k.nvar * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(hv + 2, e->dssm_n.ptr + at, (size_t)k.nvar * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(hv + 4, e->dssm_ss.ptr + at, (size_t)k.nvar * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(hv + SSG_MAX_VAR, e->dssm_n.ptr + at, (size_t)k.nvar * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(hv + 2 * SSG_MAX_VAR, e->dssm_ss.ptr + at, (size_t)k.nvar * 8, hipMemcpyDeviceToHost, e->stream));
   if (is_ar) {
     const size_t slot = (size_t)chain * SSG_MAX_AR + k.ar_index;
     HIP_TRY(hipMemcpyAsync(hphi, e->dar_phi.ptr + slot * AR_MAX, AR_MAX * 8, hipMemcpyDeviceToHost, e->stream));
@@ -298,8 +382,8 @@ int ba_ss_get_state_model(ba_engine *e, int64_t chain, int32_t block, double *va
   if (is_student && phi) { phi[0] = hphi[0]; phi[1] = hphi[1]; }
   for (int v = 0; v < k.nvar; ++v) {
     if (variances) variances[v] = hv[v];
-    if (suf_n) suf_n[v] = hv[2 + v];
-    if (suf_ss) suf_ss[v] = hv[4 + v];
+    if (suf_n) suf_n[v] = hv[SSG_MAX_VAR + v];
+    if (suf_ss) suf_ss[v] = hv[2 * SSG_MAX_VAR + v];
   }
   if (k.kind == SSG_SEMILOCAL) {
     // (phi, mu) of the slope's NonzeroMeanAr1Model; its Ar1Suf -- sumsq, sum, cross, n, first,

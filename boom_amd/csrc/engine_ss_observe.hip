@@ -86,6 +86,10 @@ int ba_ss_prediction_errors(ba_engine *e, int64_t chain_first, int64_t chain_cou
       F.qw_stride = 2 * (int64_t)T;
     }
     if (ssg_has(e->ssg, SSG_HAS_CALENDAR)) F.cal = e->dhol_cal.ptr;   // (one table for every draw: the record needs none)
+    if (ssg_has(e->ssg, SSG_HAS_DYNREG)) {   // (the same: the predictors are shared by the chains and the draws)
+      F.dyn = e->ddyn.ptr;
+      F.dyn_cols = ssg_dyn_columns(e->ssg);
+    }
   } else {
     // the local-level path: the same kernel on a one-block list
     SsgSpec one{};

@@ -47,6 +47,13 @@ enum { SSG_LOCAL_LEVEL = 1, SSG_LOCAL_LINEAR_TREND = 2, SSG_SEASONAL = 3, SSG_AR
        // its flags share the packed table of the holidays (bit SSG_CAL_SEASON of byte b), their prefix
        // counts sit behind the table (see SsParams::cal), and such a list is served by the HD instances
        SSG_CALENDAR_SEASONAL = 11 };
+// DynamicRegressionStateModel with the independent random-walk sampler (bsts AddDynamicRegression): no
+// kind of ba_ss_add_state_model -- it comes through ba_ss_add_dynamic_regression with its predictors --
+// but ssg_abi_kind names such a block by this number.  d coefficients, T = I, RQR = diag(sigma_i^2),
+// Z_t = x_t: a row of data.  Stored as SSG_LOCAL_LEVEL of dimension d with SsgBlock::dynreg set, d
+// variance slots and d state-error rows; the predictors of a list are one table for all chains
+// (SsParams::dyn), and such a list is served by the DR instances of the general kernel.
+enum { SSG_DYNAMIC_REGRESSION = 12 };
 // the packed calendar: entry t holds block b's position at time t in byte b, SSG_CAL_OFF where the
 // block is inactive at t (or is no holiday block).  A calendar seasonal's byte: SSG_CAL_SEASON where
 // time t starts a new season (its other bits are not read).
@@ -77,6 +84,10 @@ struct SsgBlock {
   int32_t sl_truncate, sl_positive;   // semilocal: NonzeroMeanAr1Sampler::force_stationary / force_ar1_positive
   int32_t ar_spike;    // autoregression: its sampler is the ArSpikeSlabSampler of ar_spike_kernel.hip (0: ArPosteriorSampler, in the state kernel)
   int32_t holiday;     // local level of dimension dim: a random-walk holiday (SSG_HOLIDAY), its positions in the packed calendar
+  // local level of dimension dim: a dynamic regression (SSG_DYNAMIC_REGRESSION): 1 + the column of the
+  // list's predictor table its first coefficient reads (0: no such block).  Variance slot i of the
+  // block reads Philox sampler id sid[0] + 16 i (sid[1] is not used).
+  int32_t dynreg;
 };
 // is the block a calendar seasonal (SSG_CALENDAR_SEASONAL: its season starts are read from the packed calendar)?
 __host__ __device__ inline bool ssg_is_calendar(const SsgBlock &k) { return k.kind == SSG_SEASONAL && k.phase == SSG_PHASE_CALENDAR; }
@@ -97,7 +108,8 @@ struct SsgSpec {
 };
 struct SsmParams {
   const SsgSpec *spec;                  // device copy
-  int32_t m, nblocks, nvar, nar, ld, bl, nerr, pad;   // (the launch's copies of the scalars)
+  int32_t m, nblocks, nvar, nar, ld, bl, nerr;   // (the launch's copies of the scalars)
+  int32_t ndyn;                         // the columns of the dynamic regressions' predictor table (0: the list has none)
   // the block list is [local level | local linear trend] [+ seasonal of duration 1] [+ one
   // autoregression] with m <= 16: the shape-specialised kernel runs (ssm_template_kernel.hip);
   // tpl_trend = 0: the general kernel
@@ -194,6 +206,12 @@ struct SsParams {
   // start a new season of block b (rows of other blocks are 0).
   const uint64_t *cal;
   int64_t cal_count;
+  // the dynamic regressions' predictors: dyn_rows >= T rows of dyn_cols doubles, row t = the x_t of the
+  // list's dynamic blocks side by side in state order, one table for all chains (nullptr: the list holds
+  // no such block).  Read by the DR instances and the forecast (rows T .. T + horizon - 1).
+  const double *dyn;
+  int64_t dyn_rows;
+  int32_t dyn_cols, dyn_pad;
 };
 
 // The Student local linear trend's own chain state (slt_kernel.hip).  c = 0 the level, 1 the slope.

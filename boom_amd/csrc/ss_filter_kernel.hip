@@ -187,6 +187,10 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
   bool hol = false;
   int hsh = 0, hfirst = 0;
   double hvar = 0.0;
+  // a dynamic regression's lanes (P.dyn): Z_t's entry is the lane's predictor at t -- column dcol of the
+  // table's row t --, T is the identity and the lane's own variance is added every step
+  bool dr = false;
+  int dcol = 0;
   for (int b = 0; b < B.nb; ++b) {
     const unsigned d = B.at(b);
     const int kd = SsfBlocks::kind_of(d), f = SsfBlocks::first_of(d), n = SsfBlocks::dim_of(d), v0 = SsfBlocks::var0_of(d);
@@ -205,12 +209,21 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
       zsel = false;
       qdiag = 0.0;
     }
+    if (kd == SSG_LOCAL_LEVEL && P.dyn && Q.blk[b].dynreg) {
+      dr = true; dcol = Q.blk[b].dynreg - 1 + w;
+      zsel = false;
+      qdiag = s_var[v0 + w];
+    }
     a = Q.a0[lane];
     // (a semilocal trend's third component IS the slope's long-run mean)
     if (kd == SSG_SEMILOCAL && w == 2) a = s_phi[SsfBlocks::arx_of(d) * AR_MAX + 1];
     P0l = Q.P0[lane];
   }
   const unsigned long long zmask = __ballot(zsel && lane < m);
+  const unsigned long long drmask = __ballot(dr && lane < m);
+  // (the lane's predictor of the step, and the next step's on its way while this one is worked on)
+  double xw = 0.0, xn = 0.0;
+  if (dr) xn = P.dyn[dcol];
   const bool act = lane < m;
   for (int e = lane; e < m * ld; e += SSF_WAVE) s_P[e] = 0.0;
   ssf_sync();
@@ -245,6 +258,10 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
         zmask_t |= __ballot(hol && lane == hfirst + (int)((cw >> hsh) & 0xffu));
         hgain = hol && lane == hfirst + (int)((cn >> hsh) & 0xffu);
       }
+      if (P.dyn) {
+        xw = xn;
+        if (dr && tb + s + 1 < T) xn = P.dyn[(size_t)(tb + s + 1) * P.dyn_cols + dcol];
+      }
       if (!dead) {
         // PZ, F, v
         double pz = 0.0;
@@ -252,11 +269,22 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
           const double *prow = s_P + lane * ld;
           for (unsigned long long zm = zmask_t; zm; zm &= zm - 1) pz += prow[__builtin_ctzll(zm)];
         }
+        for (unsigned long long zm = drmask; zm; zm &= zm - 1) {   // (Z_t = x_t on these components)
+          const int j = __builtin_ctzll(zm);
+          const double xj = ssf_rl(xw, j);
+          if (act) pz += xj * s_P[lane * ld + j];
+        }
         double za = 0.0, zpz = 0.0;
         for (unsigned long long zm = zmask_t; zm; zm &= zm - 1) {
           const int j = __builtin_ctzll(zm);
           za += ssf_rl(a, j);
           zpz += ssf_rl(pz, j);
+        }
+        for (unsigned long long zm = drmask; zm; zm &= zm - 1) {
+          const int j = __builtin_ctzll(zm);
+          const double xj = ssf_rl(xw, j);
+          za += xj * ssf_rl(a, j);
+          zpz += xj * ssf_rl(pz, j);
         }
         F = zpz + sigsq;
         if (!(F > 0.0) || !(F <= 1.79769313486231570815e308)) {

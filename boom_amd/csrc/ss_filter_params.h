@@ -37,6 +37,9 @@ struct SsFilterParams {
   // the packed calendar of the random-walk holidays and the calendar seasonals (SsParams::cal), at least
   // T entries; nullptr: no such block
   const uint64_t *cal;
+  // the dynamic regressions' predictors (SsParams::dyn), at least T rows of dyn_cols; nullptr: no such block
+  const double *dyn;
+  int32_t dyn_cols, dyn_pad;
 };
 
 hipError_t launch_ss_filter(hipStream_t stream, const SsFilterParams &P);

@@ -256,7 +256,8 @@ __device__ __forceinline__ int semilocal_slope_draw(const double *suf, const dou
 // of 60 000 instructions that ran out of the instruction cache).
 struct Blocks {
   unsigned desc;   // kind (3 bits) | first (7) | dim (7) | index of its first variance parameter (5) | autoregression slot (3) |
-                   // a random-walk holiday (1: set and read by the HD instances of ssg_simsmooth_kernel only)
+                   // a random-walk holiday (1: set and read by the HD instances of ssg_simsmooth_kernel only) |
+                   // a dynamic regression (1: set and read by its DR instances only)
   unsigned dp;     // seasonal: duration (16 bits) | phase (16)  (a calendar seasonal: 1 | 0xffff, its closed forms never fire)
   unsigned rc;     // seasonal: (index of the step's transition + 1 - phase) mod duration (16 bits: 0 = it moves) |
                    //           the rotating layout's cursor (16): physical slot of the block's first component
@@ -272,6 +273,7 @@ struct Blocks {
   static __device__ __forceinline__ int var0_of(unsigned d) { return (int)((d >> 17) & 31u); }
   static __device__ __forceinline__ int arx_of(unsigned d) { return (int)((d >> 22) & 7u); }
   static __device__ __forceinline__ bool holiday_of(unsigned d) { return ((d >> 25) & 1u) != 0; }
+  static __device__ __forceinline__ bool dynreg_of(unsigned d) { return ((d >> 26) & 1u) != 0; }
   // block b's words, wave-uniform
   __device__ __forceinline__ unsigned udesc(int b) const { return (unsigned)__builtin_amdgcn_readlane((int)desc, b); }
   __device__ __forceinline__ unsigned urc(int b) const { return (unsigned)__builtin_amdgcn_readlane((int)rc, b); }

@@ -20,8 +20,12 @@ namespace {
 // time tm + 1 -- drawn only where that time is active, as the reference does -- and the returned
 // Z'st is that of time tm + 2, the time simulate_multiplex_forecast observes the new state at.
 // A calendar seasonal steps into a new season where entry tm + 1 carries SSG_CAL_SEASON.
+// dyn: the predictor table of the list's dynamic regressions (dyn_cols columns, rows up to tm + 2; nullptr:
+// none).  Such a block advances with one error per coefficient, in order, and the returned Z'st weighs its
+// components with row tm + 2 of the table.
 __device__ __forceinline__ double ssg_forecast_step(const SsmParams &M, const SsgSpec &Q, int chain, int lane, int tm,
-                                                    SeqRng &rng, double &st, const uint64_t *cal = nullptr) {
+                                                    SeqRng &rng, double &st, const uint64_t *cal = nullptr,
+                                                    const double *dyn = nullptr, int dyn_cols = 0) {
   const int m = M.m, nb = M.nblocks;
   double nx = st;
   for (int b = 0; b < nb; ++b) {
@@ -34,6 +38,11 @@ __device__ __forceinline__ double ssg_forecast_step(const SsmParams &M, const Ss
       if (!(k & SSG_CAL_OFF)) {
         const double e0 = d_rnorm(rng, 0.0, sqrt(sg[0]));
         if (lane == f + k) nx = st + e0;
+      }
+    } else if (K.kind == SSG_LOCAL_LEVEL && K.dynreg) {
+      for (int q = 0; q < n; ++q) {
+        const double eq = d_rnorm(rng, 0.0, sqrt(sg[q]));
+        if (lane == f + q) nx = st + eq;
       }
     } else if (K.kind == SSG_LOCAL_LEVEL) {
       const double e0 = d_rnorm(rng, 0.0, sqrt(sg[0]));
@@ -89,6 +98,14 @@ __device__ __forceinline__ double ssg_forecast_step(const SsmParams &M, const Ss
     if (K.holiday) {   // (the position Z selects at the new state's time, if that time is active)
       const int k = cal ? (int)((cal[tm + 2] >> (8 * b)) & 0xffu) : SSG_CAL_OFF;
       if (!(k & SSG_CAL_OFF)) zs += rl(st, K.first + k);
+      continue;
+    }
+    if (K.dynreg) {   // (Z = the predictors of the new state's time)
+      const double *x = dyn + (size_t)(tm + 2) * dyn_cols + (K.dynreg - 1);
+      for (int i = 0; i < K.dim; ++i) {
+        const double zv = x[i] * rl(st, K.first + i);
+        zs = (b == 0 && i == 0) ? zv : zs + zv;
+      }
       continue;
     }
     for (int i = 0; i < (K.kind == SSG_TRIG ? K.dim : 1); i += 2) {

@@ -65,7 +65,8 @@
 // (this header: the kernel template.  ssm_kernel.hip instantiates the scalar and the H_t instances and
 // holds the launcher and the forecast kernel; ssm_qt_kernel.hip instantiates the Q_t instances -- a
 // file of their own so that the two compile side by side: 24 instances in one file took about 5 min
-// against 3 min 06 s for the 16 -- and ssm_hd_kernel.hip, a third, the calendar instances.)
+// against 3 min 06 s for the 16 -- ssm_hd_kernel.hip, a third, the calendar instances, and
+// ssm_dr_kernel.hip, a fourth, the dynamic regression's.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -87,9 +88,10 @@ constexpr int SSG_V_FAILED = 1 << 30;   // s_vprog: the variance pass stopped (F
 }  // namespace
 
 // LDS of the passes, in doubles: two block buffers (bl x m each) | P (m x ld) | a block's
-// normals / smoothed disturbances | the autoregression blocks' xtx rows
-__host__ __device__ inline int ssg_pass_lds_doubles(int m, int ld, int bl, int nerr, int nar) {
-  return 2 * bl * m + m * ld + (bl * (nerr + 1) + SSG_MAX_STATE + 8) + nar * AR_MAX * (AR_MAX + 1);
+// normals / smoothed disturbances | the autoregression blocks' xtx rows | a time block's rows of the
+// dynamic regressions' predictor table, one staging buffer per wave (ndyn columns; lists without: 0)
+__host__ __device__ inline int ssg_pass_lds_doubles(int m, int ld, int bl, int nerr, int nar, int ndyn = 0) {
+  return 2 * bl * m + m * ld + (bl * (nerr + 1) + SSG_MAX_STATE + 8) + nar * AR_MAX * (AR_MAX + 1) + 2 * bl * ndyn;
 }
 
 // grid = chains, block = 128, dynamic LDS = max(the normals generator's lists, the
@@ -139,7 +141,18 @@ __host__ __device__ inline int ssg_pass_lds_doubles(int m, int ld, int bl, int n
 // sigma = 0; the variance draw reads sampler id 7 + 16 per earlier seasonal block of either kind (one
 // family in ssg_stream_id).  A regular calendar therefore draws what the seasonal of that duration and
 // phase draws, bit for bit.
-template <bool SMALL, int LDC, bool GLOB, bool HT = false, bool QT = false, bool HD = false>
+// DR: the list holds a dynamic regression (SsgBlock::dynreg; bit 26 of Blocks::desc, set below): a block of
+// d coefficients, each a local level in everything -- T = I, an error row and a variance slot of its own,
+// sigma_i z, + sigma_i^2 on its diagonal entry, the statistics per lane with n = T - 1 -- except its
+// observation row: Z_t = x_t, row t of the list's predictor table (P.dyn, ndyn columns, one table for all
+// chains; the block's columns start at dynreg - 1).  A time block's rows are contiguous in the table: each
+// wave copies them into a staging buffer of its own behind the autoregressions' rows ahead of the block's
+// step loop (the two waves are at different time blocks at the same moment), and a step reads them from
+// LDS: a lane of the block its own entry (xw below: the weight where the other instances have zsel),
+// wave 1's PZ the block's whole row, a broadcast read per component.  No step waits for HBM.  The block
+// draws d state-error normals per step whatever the sigmas (sigma_i = 0 scales its normal to 0) and d for
+// the initial state (rmvn_mt).  Variance slot i of the block reads sampler id sid[0] + 16 i.
+template <bool SMALL, int LDC, bool GLOB, bool HT = false, bool QT = false, bool HD = false, bool DR = false>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void ssg_simsmooth_kernel(SsParams P, int draw_variances) {
   constexpr int SSG_BATCH = SMALL ? 4 : 8;   // entries of a column / row of P asked of the LDS together
   extern __shared__ __align__(16) unsigned char s_raw[];
@@ -183,7 +196,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       for (int v = 0; v < (K.kind == SSG_SEMILOCAL ? 1 : K.nvar); ++v) {
         const int vi = K.var0 + v;
         const size_t at = (size_t)chain * SSG_MAX_VAR + vi;
-        SeqRng rng{PhiloxKey{P.seed_lo, P.seed_hi, gchain, (uint32_t)K.sid[v]}, M.pos_var[at]};
+        SeqRng rng{PhiloxKey{P.seed_lo, P.seed_hi, gchain, (uint32_t)((DR && K.dynreg) ? K.sid[0] + 16 * v : K.sid[v])}, M.pos_var[at]};
         int bad = 0;
         const double DF = M.var_n[at] + Q.prior_df[vi];
         const double SSQ = M.var_ss[at] + Q.prior_ss[vi];
@@ -273,6 +286,21 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
   Blocks B;
   B.load(Q, nb, lane);
   if (HD && lane < nb && Q.blk[lane].holiday) B.desc |= 1u << 25;
+  if (DR && lane < nb && Q.blk[lane].dynreg) B.desc |= 1u << 26;
+  // (DR) lane b: the first column of block b in the predictor table; ND: the table's columns; this wave's
+  // staging buffer; the lane holds a coefficient -- its column, and its predictor at the step in hand
+  const int dc0_l = (DR && lane < nb && Q.blk[lane].dynreg) ? Q.blk[lane].dynreg - 1 : 0;
+  const int ND = DR ? P.dyn_cols : 0;
+  double *sdyn = s_axx + M.nar * AR_MAX * (AR_MAX + 1) + wave * BL * ND;
+  bool dr_l = false;
+  int dcol_l = 0;
+  double xw = 0.0;
+  // the rows of time block tb into this wave's staging buffer
+  auto dyn_stage = [&](int tb, int nstep) {
+    const double *g = P.dyn + (size_t)tb * ND;
+    for (int i = lane; i < nstep * ND; i += WAVE) sdyn[i] = g[i];
+    wave_lds_sync();
+  };
   LaneInfo LI{-1, 0, 0, 0, 0, 0.0};
   // (HD) lane b: block b is a calendar seasonal; calmask: bit b the same, wave-uniform
   const bool cals_l = HD && lane < nb && ssg_is_calendar(Q.blk[lane]);
@@ -333,6 +361,21 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       const bool mine = lane >= f && lane < f + n;
       const bool hol = HD && Blocks::holiday_of(d);
       if (HD && mine && hol) { hol_l = true; hsh_l = 8 * b; }
+      if (DR && Blocks::dynreg_of(d)) {
+        // a dynamic regression: every component a level with a variance, an error row, a state-error normal
+        // at every step and a normal of the initial state (rmvn_mt) of its own
+        if (mine) {
+          dr_l = true; dcol_l = __builtin_amdgcn_readlane(dc0_l, b) + (lane - f);
+          LI.blk = b; LI.kind = kd; LI.first = f; LI.dim = n;
+          var_l = v0 + (lane - f);
+          cbefore_l = cb + (lane - f);
+          erow_l = eb + (lane - f);
+          sbefore_l = sb;
+          ipos_l = ip + (lane - f); init_l = true;
+        }
+        eb += n; ip += n; cb += n;
+        continue;
+      }
       const bool second = (kd == SSG_LOCAL_LINEAR_TREND || kd == SSG_SEMILOCAL) && lane == f + 1;
       const int within = kd == SSG_TRIG ? lane - f : (second ? 1 : 0);   // (a trig block: an error term per component)
       if (mine) {
@@ -400,6 +443,10 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
   // HD: a calendar entry's position for this lane's block (holiday lanes only) / for block b (wave-uniform)
   auto hpos_l = [&](unsigned long long w) -> int { return (int)((w >> hsh_l) & 0xffu); };
   auto hpos_b = [](unsigned long long w, int b) -> int { return (int)((w >> (8 * b)) & 0xffu); };
+
+  // DR: Z'v of the step in hand -- the coefficients' lanes weigh in with their predictors (the call sites
+  // keep zdot itself for the other instances)
+  auto zdr = [&](double v) -> double { return wsum<SMALL>(dr_l ? xw * v : (LI.template zsel<GLOB>(lane) ? v : 0.0)); };
 
   const double H = HT ? 0.0 : P.sigsq[chain], sqrtH = sqrt(H);
   const int dH = HT ? 1 : (sqrtH != 0.0);
@@ -487,9 +534,11 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       // (HD: the calendar's entries t -- Z_t -- and t + 1 -- RQR_t -- of the block's steps, one per lane)
       unsigned long long cw_l = SSG_CAL_NONE, cn_l = SSG_CAL_NONE;
       if (HD) { if (lane < nstep) cw_l = P.cal[tt]; cn_l = cal_next(tt, lane < nstep); }
+      if (DR) dyn_stage(tb, nstep);
       double F_l = 1.0;
 #pragma nounroll
       for (int s = 0; s < nstep; ++s) {
+        if (DR) xw = dr_l ? sdyn[s * ND + dcol_l] : 0.0;
         const bool obs = __builtin_amdgcn_readlane(ob_l, s) != 0;
         const unsigned mv = (HD ? hmoving(rlw(cn_l, s)) : B.moving());   // (the transition OUT of t)
         const double qa = QT ? rl(qa_l, s) : 0.0, qb = QT ? rl(qb_l, s) : 0.0;
@@ -507,6 +556,14 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
               if (k & SSG_CAL_OFF) continue;
               zl += k;
             }
+            if (DR && Blocks::dynreg_of(B.udesc(b))) {   // (the block's rows, weighed by x_t, in component order)
+              const double *xr = sdyn + s * ND + __builtin_amdgcn_readlane(dc0_l, b);
+              const int n = Blocks::dim_of(B.udesc(b));
+#pragma nounroll
+              for (int i = 0; i < n; ++i)
+                if (mylane) PZ += xr[i] * s_P[(zl + i) * ld + lane];
+              continue;
+            }
             if (mylane) PZ += s_P[zl * ld + lane];
           }
         } else {
@@ -519,6 +576,16 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
               const int k = hpos_b(cw, b);
               on = on && !(k & SSG_CAL_OFF);
               zl += k & (SSG_CAL_OFF - 1);
+            }
+            if (DR && Blocks::dynreg_of(B.udesc(b))) {
+              const double *xr = sdyn + s * ND + __builtin_amdgcn_readlane(dc0_l, b);
+              const int n = Blocks::dim_of(B.udesc(b));
+              double acc = 0.0;
+#pragma nounroll
+              for (int i = 0; i < n; ++i)
+                if (on) acc += xr[i] * s_P[(zl + i) * ld + lane];
+              pz[b] = acc;
+              continue;
             }
             pz[b] = on ? s_P[zl * ld + lane] : 0.0;
           }
@@ -539,7 +606,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
               if (mylane) PZ += s_P[(f + i) * ld + lane];
           }
         }
-        const double F = zdot<SMALL, GLOB>(LI, PZ, lane) + (HT ? rl(h_l, s) : H);
+        const double F = (DR ? zdr(PZ) : zdot<SMALL, GLOB>(LI, PZ, lane)) + (HT ? rl(h_l, s) : H);
         if (!(F > 0.0)) { status = CHAIN_FORECAST_VARIANCE; break; }
         if (lane == s) F_l = F;
         const double Finv = 1.0 / F;
@@ -567,6 +634,16 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
             }
             const int kn = hpos_b(cn, b);
             if (!(kn & SSG_CAL_OFF) && lane == f + kn) col[kn * ld] += s_sig2[Blocks::var0_of(d)];
+          } else if (DR && Blocks::dynreg_of(d)) {
+            // every component a level: the rank-one term, + sigma_i^2 on its own diagonal entry
+            const int v0 = Blocks::var0_of(d);
+#pragma nounroll
+            for (int i = 0; i < n; ++i) {
+              double v = col[i * ld];
+              if (obs) v -= (s_tv[f + i] * PZ) * Finv;
+              if (lane == f + i) v += s_sig2[v0 + i];
+              col[i * ld] = v;
+            }
           } else if (kd == SSG_LOCAL_LEVEL) {
             double v = col[0];
             if (obs) v -= (s_tv[f] * PZ) * Finv;
@@ -811,6 +888,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       // (HD: the calendar's entry t of the block's steps -- the error INTO t and Z_t --, one per lane)
       unsigned long long cw_l = SSG_CAL_NONE;
       if (HD && in_l) cw_l = P.cal[tt];
+      if (DR) dyn_stage(tb, nstep);
       // the block's normals, in stream order
       const int zstart = tb == 0 ? 0 : zoffset(tb);
       const int zend = (tb + nstep >= T) ? N : zoffset(tb + nstep);
@@ -820,6 +898,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
 #pragma nounroll
       for (int s = 0; s < nstep; ++s) {
         if (HD) { const unsigned long long cw = rlw(cw_l, s); if (hol_l) LI.cur = hpos_l(cw); }
+        if (DR) xw = dr_l ? sdyn[s * ND + dcol_l] : 0.0;
         if (tb + s == 0) {
           // simulate_initial_state: mean_i + sd_i z_i
           const double z = (mylane && init_l) ? s_z[ipos_l] : 0.0;
@@ -834,6 +913,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
           advance(B, LI, mv, lane);
           bool err = false;
           if (HD && hol_l) err = lane == LI.first + LI.cur;   // (the active position, if the step has one)
+          else if (DR && dr_l) err = true;
           else if (LI.kind == SSG_LOCAL_LEVEL) err = sig_l != 0.0;
           else if (LI.kind == SSG_LOCAL_LINEAR_TREND) err = true;
           else if (LI.kind == SSG_AR) err = lane == LI.first;
@@ -851,7 +931,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
         }
         const double zh = dH ? s_z[zo] : 0.0;
         zo += dH;
-        const double yplus = zdot<SMALL, GLOB>(LI, alpha, lane) + (HT ? rl(sh_l, s) : sqrtH) * zh;   // simulate_adjusted_observation
+        const double yplus = (DR ? zdr(alpha) : zdot<SMALL, GLOB>(LI, alpha, lane)) + (HT ? rl(sh_l, s) : sqrtH) * zh;   // simulate_adjusted_observation
         const double w = rl(ys_l, s) - yplus;
         if (lane == s) w_l = w;
         if (mylane) blk[s * m + lane] = alpha;
@@ -887,14 +967,16 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       const int ob_l = (in_l && P.observed[tt]) ? 1 : 0;
       unsigned long long cw_l = SSG_CAL_NONE, cn_l = SSG_CAL_NONE;
       if (HD) { if (in_l) cw_l = P.cal[tt]; cn_l = cal_next(tt, in_l); }
+      if (DR) dyn_stage(tb, nstep);
       double ef_l = 0.0;
 #pragma nounroll
       for (int s = 0; s < nstep; ++s) {
         if (HD) { const unsigned long long cw = rlw(cw_l, s); if (hol_l) LI.cur = hpos_l(cw); }
+        if (DR) xw = dr_l ? sdyn[s * ND + dcol_l] : 0.0;
         const double K = mylane ? blk[s * m + lane] : 0.0;
         const bool obs = __builtin_amdgcn_readlane(ob_l, s) != 0;
         const unsigned mv = (HD ? hmoving(rlw(cn_l, s)) : B.moving());   // (the transition OUT of t)
-        const double e = obs ? rl(w_l, s) - zdot<SMALL, GLOB>(LI, delta, lane) : 0.0;
+        const double e = obs ? rl(w_l, s) - (DR ? zdr(delta) : zdot<SMALL, GLOB>(LI, delta, lane)) : 0.0;
         if (lane == s) ef_l = obs ? e / F_l : 0.0;
         delta = vecT<SMALL, GLOB>(B, LI, delta, lane, mv) + K * e;
         advance(B, LI, mv, lane);
@@ -922,8 +1004,10 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
     // (HD: the calendar's entries t -- Z_t -- and t + 1 -- the row the error of t -> t + 1 lands on)
     unsigned long long cw_l = SSG_CAL_NONE, cn_l = SSG_CAL_NONE;
     if (HD) { if (in_l) cw_l = P.cal[tt]; cn_l = cal_next(tt, in_l); }
+    if (DR) dyn_stage(tb, nstep);
 #pragma nounroll
     for (int s = nstep - 1; s >= 0; --s) {
+      if (DR) xw = dr_l ? sdyn[s * ND + dcol_l] : 0.0;
       const double K = mylane ? blk[s * m + lane] : 0.0;
       const unsigned mv = (HD ? hmoving(rlw(cn_l, s)) : B.moving());   // (the transition t -> t + 1)
       const unsigned long long cw = HD ? rlw(cw_l, s) : 0ull, cn = HD ? rlw(cn_l, s) : 0ull;
@@ -933,6 +1017,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
         const int kn = hpos_l(cn);
         const bool off = (kn & SSG_CAL_OFF) != 0;
         if (lane == LI.first + (off ? 0 : kn)) s_z[erow_l * BL + s] = off ? 0.0 : r;
+      } else if (DR && dr_l) {
+        s_z[erow_l * BL + s] = r;   // (an error row per coefficient)
       } else if (mylane) {
         bool carrier;
         if (LI.kind == SSG_SEASONAL) carrier = lane == LI.first + LI.cur;
@@ -947,7 +1033,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       retreat(B, LI, mv, lane);
       // + Z coef (layout of t)
       if (HD && hol_l) LI.cur = hpos_l(cw);
-      if (LI.template zsel<GLOB>(lane)) r += coef;
+      if (DR && dr_l) r += xw * coef;   // (+ x_t coef)
+      else if (LI.template zsel<GLOB>(lane)) r += coef;
       if (!mylane) r = 0.0;
     }
     wave_lds_sync();
@@ -996,6 +1083,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
           const unsigned long long cw = HD ? rlw(cw_l, s) : 0ull;
           if (HD && hol_l) {
             carrier = lane == LI.first + hpos_l(cw);
+          } else if (DR && dr_l) {
+            carrier = true;
           } else if (mylane) {
             if (LI.kind == SSG_SEASONAL) carrier = LI.moves(mv) && lane == LI.first + LI.cur;
             else if (LI.kind == SSG_LOCAL_LINEAR_TREND || (GLOB && LI.kind == SSG_TRIG)) carrier = true;
@@ -1046,6 +1135,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       const int ob_l = (in_l && P.observed[tt]) ? 1 : 0;
       unsigned long long cw_l = SSG_CAL_NONE;   // (HD: entry t -- the component the step into t landed on, and Z_t)
       if (HD && in_l) cw_l = P.cal[tt];
+      if (DR) dyn_stage(tb, nstep);
       // (wave 0 only leaves early when THIS wave's variance pass failed, and then this wave has left too)
       while (__hip_atomic_load(&s_cprog, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= bi)
         __builtin_amdgcn_s_sleep(8);
@@ -1054,6 +1144,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       for (int s = 0; s < nstep; ++s) {
         const double st = mylane ? buf[s * m + lane] : 0.0;
         if (HD) { const unsigned long long cw = rlw(cw_l, s); if (hol_l) LI.cur = hpos_l(cw); }
+        if (DR) xw = dr_l ? sdyn[s * ND + dcol_l] : 0.0;
         unsigned mv = 0;
         double tot_then = 0.0;   // seasonal: sum of the block at t - 1 (kept by the lanes of the block)
         if (tb + s > 0) {
@@ -1145,7 +1236,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
         }
         const bool obs = __builtin_amdgcn_readlane(ob_l, s) != 0;
         // (HT: Z_t'alpha_t itself, every step: the Student family's offset)
-        const double resid = HT ? zdot<SMALL, GLOB>(LI, st, lane) : (obs ? rl(y_l, s) - zdot<SMALL, GLOB>(LI, st, lane) : 0.0);
+        const double resid = HT ? (DR ? zdr(st) : zdot<SMALL, GLOB>(LI, st, lane)) : (obs ? rl(y_l, s) - (DR ? zdr(st) : zdot<SMALL, GLOB>(LI, st, lane)) : 0.0);
         if (lane == s) res_l = resid;
         if (obs) { yty += resid * resid; nobs += 1.0; }
       }
@@ -1168,6 +1259,12 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       if (lane == f) {
         M.var_n[at] = cnt;
         M.var_ss[at] = tot;
+      }
+    } else if (DR && Blocks::dynreg_of(d)) {
+      // (a slot per coefficient: its own lane's sum, in time order)
+      if (LI.blk == b) {
+        M.var_n[at + (lane - f)] = (double)(T - 1);
+        M.var_ss[at + (lane - f)] = suf_l;
       }
     } else if (kd == SSG_LOCAL_LEVEL) {
       if (lane == f) {
@@ -1233,5 +1330,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
 hipError_t launch_ssg_qt(hipStream_t stream, const SsParams &P, int draw_variances, size_t lds);
 // the holiday instances' launch (ssm_hd_kernel.hip)
 hipError_t launch_ssg_hd(hipStream_t stream, const SsParams &P, int draw_variances, size_t lds);
+// the dynamic regression's instances' launch (ssm_dr_kernel.hip)
+hipError_t launch_ssg_dr(hipStream_t stream, const SsParams &P, int draw_variances, size_t lds);
 
 }  // namespace boom_amd

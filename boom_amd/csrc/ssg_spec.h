@@ -17,8 +17,8 @@ namespace boom_amd {
 
 // ---- one row per C-ABI kind (include/boom_amd.h, ba_ss_add_state_model) ------------------
 // the mark a kind leaves on its stored block: nvar = 0 | SsgSpec::student_block | SsgBlock::ar_spike |
-// SsgBlock::holiday | phase SSG_PHASE_CALENDAR
-enum SsgMark { SSG_MARK_NONE, SSG_MARK_STATIC, SSG_MARK_STUDENT, SSG_MARK_AR_SPIKE, SSG_MARK_HOLIDAY, SSG_MARK_CALENDAR };
+// SsgBlock::holiday | phase SSG_PHASE_CALENDAR | SsgBlock::dynreg
+enum SsgMark { SSG_MARK_NONE, SSG_MARK_STATIC, SSG_MARK_STUDENT, SSG_MARK_AR_SPIKE, SSG_MARK_HOLIDAY, SSG_MARK_CALENDAR, SSG_MARK_DYNREG };
 // the sampler families: variance parameter v reads id base + 16 per earlier block that is a
 // member of the parameter's family (a semilocal trend counts for the level family and for its
 // slope's own; a static intercept, a holiday and a Student trend are in no level family)
@@ -51,29 +51,53 @@ inline const SsgKind *ssg_kind_row(int32_t kind) {
   };
   return kind >= 1 && kind <= 11 ? &rows[kind - 1] : nullptr;
 }
+// The row of a dynamic regression of d coefficients (ba_ss_add_dynamic_regression: no kind of
+// ba_ss_add_state_model, so no row of the table above): a local level per coefficient -- d variance
+// parameters, d slots, a state-error row per component, sigma may start at 0 --, an initial state drawn
+// by rmvn (positive variances).  Sampler ids: a convention of ours -- BOOM draws the d variances from
+// one generator -- residue 10, which no family uses: variance slot i of the block reads 10 + 16 x (the
+// dynamic coefficients earlier in the list, this block's first i among them); with at most 16 slots the
+// largest id is 250.  SsgBlock::sid[0] holds the block's first, the others follow from it.
+enum { SSG_DYNREG_SAMPLER = 10 };
+inline const SsgKind *ssg_dynreg_row(int32_t d) {
+  static SsgKind rows[SSG_MAX_STATE + 1];
+  if (d < 1 || d > SSG_MAX_STATE) return nullptr;
+  rows[d] = SsgKind{SSG_LOCAL_LEVEL, SSG_MARK_DYNREG, d, 0, 0, d, d, 0, false, false, false, false, false, 0, {{0, SSG_DYNREG_SAMPLER}, {0, 0}}};
+  return &rows[d];
+}
+// the dynamic coefficients of the first `upto` blocks of a list (all: the columns of its predictor table)
+inline int32_t ssg_dyn_columns(const SsgSpec &q, int upto = SSG_MAX_BLOCKS) {
+  int32_t n = 0;
+  for (int i = 0; i < q.nblocks && i < upto; ++i) n += q.blk[i].dynreg ? q.blk[i].dim : 0;
+  return n;
+}
 // the C-ABI kind block i of a list was appended as (the one place that reads the marks back)
 inline int32_t ssg_abi_kind(const SsgSpec &q, int i) {
   const SsgBlock &k = q.blk[i];
   if (i == q.student_block - 1) return SSG_STUDENT_TREND;
   if (k.holiday) return SSG_HOLIDAY;
+  if (k.dynreg) return SSG_DYNAMIC_REGRESSION;
   if (k.ar_spike) return SSG_AUTO_AR;
   if (ssg_is_calendar(k)) return SSG_CALENDAR_SEASONAL;
   if (k.kind == SSG_LOCAL_LEVEL && k.nvar == 0) return SSG_STATIC_INTERCEPT;
   return k.kind;
 }
-inline const SsgKind &ssg_row_of(const SsgSpec &q, int i) { return *ssg_kind_row(ssg_abi_kind(q, i)); }
+inline const SsgKind &ssg_row_of(const SsgSpec &q, int i) {
+  return q.blk[i].dynreg ? *ssg_dynreg_row(q.blk[i].dim) : *ssg_kind_row(ssg_abi_kind(q, i));
+}
 
 // ---- what a list holds ---------------------------------------------------------------------
 // a Student local linear trend (the general kernel's QT instances) | an autoregression with a
 // spike-and-slab prior (ar_spike_kernel.hip) | a random-walk holiday | a calendar seasonal (the HD
-// instances, a calendar per block) | a block of either kind: the list has a calendar
+// instances, a calendar per block) | a block of either kind: the list has a calendar | a dynamic
+// regression (the DR instances, a table of predictors)
 enum SsgFeature { SSG_HAS_STUDENT_TREND = 1, SSG_HAS_AR_SPIKE = 2, SSG_HAS_HOLIDAY = 4, SSG_HAS_CALENDAR_SEASONAL = 8,
-                  SSG_HAS_CALENDAR = SSG_HAS_HOLIDAY | SSG_HAS_CALENDAR_SEASONAL };
+                  SSG_HAS_CALENDAR = SSG_HAS_HOLIDAY | SSG_HAS_CALENDAR_SEASONAL, SSG_HAS_DYNREG = 16 };
 inline bool ssg_has(const SsgSpec &q, int features) {
   int has = q.student_block ? SSG_HAS_STUDENT_TREND : 0;
   for (int i = 0; i < q.nblocks; ++i)
     has |= (q.blk[i].ar_spike ? SSG_HAS_AR_SPIKE : 0) | (q.blk[i].holiday ? SSG_HAS_HOLIDAY : 0) |
-           (ssg_is_calendar(q.blk[i]) ? SSG_HAS_CALENDAR_SEASONAL : 0);
+           (ssg_is_calendar(q.blk[i]) ? SSG_HAS_CALENDAR_SEASONAL : 0) | (q.blk[i].dynreg ? SSG_HAS_DYNREG : 0);
   return (has & features) != 0;
 }
 
@@ -82,8 +106,8 @@ inline bool ssg_has(const SsgSpec &q, int features) {
 inline void ssg_template_shape(const SsgSpec &q, int32_t *trend, int32_t *nseasons, int32_t *ar_lags) {
   *trend = *nseasons = *ar_lags = 0;
   if (q.nblocks < 1 || q.nblocks > 3 || q.m > 16) return;
-  // (a Student trend, a spike-and-slab autoregression, a holiday, a calendar seasonal: the general kernel's instances)
-  if (ssg_has(q, SSG_HAS_STUDENT_TREND | SSG_HAS_AR_SPIKE | SSG_HAS_CALENDAR)) return;
+  // (a Student trend, a spike-and-slab autoregression, a holiday, a calendar seasonal, a dynamic regression: the general kernel's instances)
+  if (ssg_has(q, SSG_HAS_STUDENT_TREND | SSG_HAS_AR_SPIKE | SSG_HAS_CALENDAR | SSG_HAS_DYNREG)) return;
   for (int i = 0; i < q.nblocks; ++i)
     if (q.blk[i].nvar == 0) return;   // (a static intercept: the general kernel)
   int b = 0, tr = 0, ns = 0, lags = 0;
@@ -115,14 +139,18 @@ enum SsgUse { SSG_USE_APPEND, SSG_USE_LAUNCH, SSG_USE_LOOKAHEAD, SSG_USE_FORECAS
 // a look-ahead above 1; SSG_USE_FORECAST: ba_ss_forecast, the Gaussian family's.  Where two
 // refusals apply, the first below is given.
 inline const char *ssg_refusal(const SsgSpec *q, SsFamily family, SsgUse use, int32_t kind = 0) {
-  static const char *const only_gaussian[4] = {
+  static const char *const only_gaussian[5] = {
       "the Student local linear trend is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)",
       "the spike-and-slab autoregression is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)",
       "the random-walk holiday is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)",
-      "the calendar seasonal is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)"};
+      "the calendar seasonal is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)",
+      "the dynamic regression is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)"};
+  static const char *const dynreg_student = "a list that holds both a dynamic regression and a Student local linear trend is not built";
+  static const char *const dynreg_holiday = "a list that holds both a dynamic regression and a random-walk holiday is not built";
+  static const char *const dynreg_calseas = "a list that holds both a dynamic regression and a calendar seasonal is not built";
   static const char *const holiday_student = "a list that holds both a random-walk holiday and a Student local linear trend is not built";
   static const char *const calseas_student = "a list that holds both a calendar seasonal and a Student local linear trend is not built";
-  static const int special[4] = {SSG_HAS_STUDENT_TREND, SSG_HAS_AR_SPIKE, SSG_HAS_HOLIDAY, SSG_HAS_CALENDAR_SEASONAL};
+  static const int special[5] = {SSG_HAS_STUDENT_TREND, SSG_HAS_AR_SPIKE, SSG_HAS_HOLIDAY, SSG_HAS_CALENDAR_SEASONAL, SSG_HAS_DYNREG};
   const bool other = family != SS_FAMILY_GAUSSIAN;
   auto has = [&](int f) { return q && ssg_has(*q, f); };
   switch (use) {
@@ -130,14 +158,23 @@ inline const char *ssg_refusal(const SsgSpec *q, SsFamily family, SsgUse use, in
       if (kind == SSG_STUDENT_TREND) {
         if (has(SSG_HAS_HOLIDAY)) return holiday_student;
         if (has(SSG_HAS_CALENDAR_SEASONAL)) return calseas_student;
+        if (has(SSG_HAS_DYNREG)) return dynreg_student;
         return other ? only_gaussian[0] : nullptr;
       }
       if (kind == SSG_AUTO_AR) return other ? only_gaussian[1] : nullptr;
-      if (kind == SSG_HOLIDAY) return other ? only_gaussian[2] : (has(SSG_HAS_STUDENT_TREND) ? holiday_student : nullptr);
-      if (kind == SSG_CALENDAR_SEASONAL) return other ? only_gaussian[3] : (has(SSG_HAS_STUDENT_TREND) ? calseas_student : nullptr);
+      if (kind == SSG_HOLIDAY)
+        return other ? only_gaussian[2] : (has(SSG_HAS_STUDENT_TREND) ? holiday_student : (has(SSG_HAS_DYNREG) ? dynreg_holiday : nullptr));
+      if (kind == SSG_CALENDAR_SEASONAL)
+        return other ? only_gaussian[3] : (has(SSG_HAS_STUDENT_TREND) ? calseas_student : (has(SSG_HAS_DYNREG) ? dynreg_calseas : nullptr));
+      if (kind == SSG_DYNAMIC_REGRESSION) {   // (ssg_append_dynreg's)
+        if (other) return only_gaussian[4];
+        if (has(SSG_HAS_STUDENT_TREND)) return dynreg_student;
+        if (has(SSG_HAS_HOLIDAY)) return dynreg_holiday;
+        return has(SSG_HAS_CALENDAR_SEASONAL) ? dynreg_calseas : nullptr;
+      }
       return nullptr;
     case SSG_USE_LAUNCH:
-      for (int i = 0; other && i < 4; ++i)
+      for (int i = 0; other && i < 5; ++i)
         if (has(special[i])) return only_gaussian[i];
       return nullptr;
     case SSG_USE_LOOKAHEAD:
@@ -168,9 +205,11 @@ inline void ssg_finish(SsgSpec &q) {
   // steps per block of the passes: the most that leaves FOUR workgroups to a CU's 160 KB of
   // LDS (all 1024 chains of a launch resident; at m = 59 sixteen steps left room for three,
   // and the launch ran as two rounds), never below 8; see ssg_pass_lds_doubles
+  // (a list with dynamic regressions: a time block's predictor rows as well, staged once per wave)
+  const int ndyn = ssg_dyn_columns(q);
   q.bl = 64;
   while (q.bl > 8 && (2 * q.bl * q.m + q.m * q.ld + q.bl * (q.nerr + 1) + SSG_MAX_STATE + 8 +
-                      q.nar * AR_MAX * (AR_MAX + 1)) * 8 > 39 * 1024)
+                      q.nar * AR_MAX * (AR_MAX + 1) + 2 * q.bl * ndyn) * 8 > 39 * 1024)
     q.bl /= 2;
 }
 // ArModel's constructor: "Attempt to initialize ArModel with an illegal value of the
@@ -257,6 +296,8 @@ inline const char *ar_spike_prior_parse(const int32_t *iparams, const double *in
   return nullptr;
 }
 
+inline SsgRefusal ssg_append_tail(SsgSpec &q, SsgInitial I, int32_t kind, const SsgKind *row, SsgBlock k,
+                                   const ArSpikePrior &spike, const SsgModelArgs &A);
 inline SsgRefusal ssg_append(SsgSpec &q, SsgInitial I, SsFamily family, int32_t kind, const SsgModelArgs &A) {
   auto invalid = [](const char *text) { return SsgRefusal{BA_E_INVALID, text}; };
   const SsgKind *row = ssg_kind_row(kind);
@@ -354,6 +395,14 @@ inline SsgRefusal ssg_append(SsgSpec &q, SsgInitial I, SsFamily family, int32_t 
       break;
   }
   k.dim = row->dim ? row->dim : row->dim_mul * ip[0] + row->dim_add;
+  return ssg_append_tail(q, I, kind, row, k, spike, A);
+}
+// the append's second half -- the limits, the arrays' checks, the block into the list --, shared with
+// ssg_append_dynreg: `k` has its kind, marks and dimension, `row` is its row
+inline SsgRefusal ssg_append_tail(SsgSpec &q, SsgInitial I, int32_t kind, const SsgKind *row, SsgBlock k,
+                                  const ArSpikePrior &spike, const SsgModelArgs &A) {
+  auto invalid = [](const char *text) { return SsgRefusal{BA_E_INVALID, text}; };
+  const double *phi = A.initial_phi;
   if (q.m + k.dim > SSG_MAX_STATE) return invalid("state dimension exceeds 64");
   if (q.nvar + row->nslot > SSG_MAX_VAR) return invalid("more than 16 variance parameters");
   for (int v = 0; v < k.nvar; ++v) {
@@ -377,8 +426,9 @@ inline SsgRefusal ssg_append(SsgSpec &q, SsgInitial I, SsFamily family, int32_t 
     q.prior_ss[vi] = 2 * (A.var_df[v] * A.var_sigma_guess[v] * A.var_sigma_guess[v] / 2.0);
     q.sigma_max[vi] = A.var_sigma_upper_limit[v];
     I.sigsq[vi] = A.var_initial_sigma[v] * A.var_initial_sigma[v];
-    k.sid[v] = ssg_stream_id(q, *row, v);
+    if (row->mark != SSG_MARK_DYNREG) k.sid[v] = ssg_stream_id(q, *row, v);
   }
+  if (row->mark == SSG_MARK_DYNREG) k.sid[0] = SSG_DYNREG_SAMPLER + 16 * ssg_dyn_columns(q);
   if (row->mark == SSG_MARK_STATIC) {
     // StaticInterceptStateModel: T = 1, RQR = 0, nothing to learn and no sampler -- a local level
     // whose variance (a slot of its own: variance 0, a sampler that is never run) is 0
@@ -421,6 +471,56 @@ inline SsgRefusal ssg_append(SsgSpec &q, SsgInitial I, SsFamily family, int32_t 
   q.nvar += row->nslot;
   ssg_finish(q);
   return {BA_OK, nullptr};
+}
+
+// DynamicRegressionStateModel(X) + DynamicRegressionIndependentPosteriorSampler on a specification
+// (ba_ss_add_dynamic_regression): d coefficients, one ChisqModel(df, sigma_guess) and sigma upper limit
+// each.  The predictors themselves are the engine's (ssg_dyn_check: finite).
+inline SsgRefusal ssg_append_dynreg(SsgSpec &q, SsgInitial I, SsFamily family, int32_t d, const SsgModelArgs &A) {
+  auto invalid = [](const char *text) { return SsgRefusal{BA_E_INVALID, text}; };
+  if (!A.var_df || !A.var_sigma_guess || !A.var_sigma_upper_limit || !A.var_initial_sigma || !A.initial_state_mean ||
+      !A.initial_state_variance)
+    return invalid("null argument");
+  if (q.nblocks >= SSG_MAX_BLOCKS) return invalid("more than 8 state models");
+  if (d < 1) return invalid("a dynamic regression needs at least one predictor");
+  if (q.m + (int64_t)d > SSG_MAX_STATE) return invalid("state dimension exceeds 64");
+  if (const char *refused = ssg_refusal(&q, family, SSG_USE_APPEND, SSG_DYNAMIC_REGRESSION)) return {BA_E_STATE, refused};
+  SsgBlock k{};
+  k.kind = SSG_LOCAL_LEVEL;
+  k.nvar = d;
+  k.duration = 1;
+  k.ar_index = -1;
+  k.dim = d;
+  k.dynreg = 1 + ssg_dyn_columns(q);
+  return ssg_append_tail(q, I, SSG_DYNAMIC_REGRESSION, ssg_dynreg_row(d), k, ArSpikePrior{}, A);
+}
+// the predictors of a dynamic regression, rows x xdim row-major: the first entry that is not finite, or -1
+inline int64_t ssg_dyn_check(const double *predictors, int64_t rows, int32_t xdim) {
+  for (int64_t i = 0; i < rows * (int64_t)xdim; ++i)
+    if (!std::isfinite(predictors[i])) return i;
+  return -1;
+}
+// the shortest predictor table of a list's dynamic blocks (-1: the list has none) ...
+inline int64_t ssg_dyn_rows(const SsgSpec &q, const std::vector<double> *predictors) {
+  int64_t rows = -1;
+  for (int b = 0; b < q.nblocks; ++b) {
+    if (!q.blk[b].dynreg) continue;
+    const int64_t n = (int64_t)predictors[b].size() / q.blk[b].dim;
+    rows = rows < 0 ? n : std::min(rows, n);
+  }
+  return rows;
+}
+// ... and the list's table (SsParams::dyn): row t = the blocks' x_t side by side, in state order
+inline std::vector<double> ssg_pack_predictors(const SsgSpec &q, const std::vector<double> *predictors, int64_t rows) {
+  const int cols = ssg_dyn_columns(q);
+  std::vector<double> table((size_t)rows * (size_t)cols, 0.0);
+  for (int b = 0; b < q.nblocks; ++b) {
+    if (!q.blk[b].dynreg) continue;
+    const int c0 = q.blk[b].dynreg - 1, d = q.blk[b].dim;
+    for (int64_t t = 0; t < rows; ++t)
+      for (int i = 0; i < d; ++i) table[(size_t)t * cols + c0 + i] = predictors[b][(size_t)t * d + i];
+  }
+  return table;
 }
 
 // ---- the calendars of the random-walk holidays and the calendar seasonals, packed -----------

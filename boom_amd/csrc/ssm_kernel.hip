@@ -30,7 +30,7 @@ __global__ __launch_bounds__(64) void ssg_forecast_kernel(SsParams P, int horizo
   SeqRng rng{PhiloxKey{P.seed_lo, P.seed_hi, (uint32_t)(P.chain_offset + chain), 5u}, pos_forecast[chain]};
   for (int i = 0; i < horizon; ++i) {
     // (the transition's index is T - 2 + i)
-    const double zs = ssg_forecast_step(M, Q, chain, lane, T - 2 + i, rng, st, P.cal);
+    const double zs = ssg_forecast_step(M, Q, chain, lane, T - 2 + i, rng, st, P.cal, P.dyn, P.dyn_cols);
     const double obs = d_rnorm(rng, zs, sd_obs);
     double part = 0.0;
     for (int j = lane; j < p; j += WAVE) part += newX[(size_t)j * horizon + i] * beta[j];
@@ -48,7 +48,7 @@ hipError_t launch_ssm_forecast(hipStream_t stream, const SsParams &P, int horizo
 }
 
 size_t ssm_dynamic_lds(const SsmParams &M) {
-  size_t need = (size_t)ssg_pass_lds_doubles(M.m, M.ld, M.bl, M.nerr, M.nar) * sizeof(double);
+  size_t need = (size_t)ssg_pass_lds_doubles(M.m, M.ld, M.bl, M.nerr, M.nar, M.ndyn) * sizeof(double);
   if (need < sizeof(NormalsLds)) need = sizeof(NormalsLds);
   if (need < sizeof(ArLds)) need = sizeof(ArLds);
   return (need + 15) & ~(size_t)15;
@@ -62,7 +62,7 @@ hipError_t launch_ssm_simsmooth(hipStream_t stream, const SsParams &P, int draw_
   hipError_t err;
   {
     KtScope kt(stream, KT_SSM);
-    if (P.ssm.tpl_trend > 0 && !P.h && !P.qw && !P.cal) {
+    if (P.ssm.tpl_trend > 0 && !P.h && !P.qw && !P.cal && !P.dyn) {
       err = launch_ssm_template(stream, P, draw_variances);
       if (err != hipSuccess) return err;
     } else {
@@ -76,7 +76,10 @@ hipError_t launch_ssm_simsmooth(hipStream_t stream, const SsParams &P, int draw_
         return hipSuccess;
       };
       const bool glob = P.ssm.glob != 0;   // (a trig or semilocal block in the list)
-      if (P.cal) {   // a random-walk holiday in the list: the calendar's instances
+      if (P.dyn) {   // a dynamic regression in the list: the predictor table's instances
+        if (P.h || P.qw || P.cal) return hipErrorInvalidValue;   // (the rule book refuses such a list)
+        err = launch_ssg_dr(stream, P, draw_variances, lds);
+      } else if (P.cal) {   // a random-walk holiday in the list: the calendar's instances
         if (P.h || P.qw) return hipErrorInvalidValue;   // (the observation families and the Student trend refuse such a list)
         err = launch_ssg_hd(stream, P, draw_variances, lds);
       } else if (P.qw) {   // a Student local linear trend in the list: the per-step state variance's instances

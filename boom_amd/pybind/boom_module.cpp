@@ -386,6 +386,29 @@ PYBIND11_MODULE(_boom, boom) {
       .def("set_prior", &RandomWalkHolidayStateModel::set_prior, py::arg("df"), py::arg("sigma_guess"),
            py::arg("sigma_upper_limit") = std::numeric_limits<double>::infinity());
 
+  py::class_<DynamicRegressionStateModel, Ptr<DynamicRegressionStateModel>>(
+      boom, "DynamicRegressionStateModel",
+      "DynamicRegressionStateModel(predictors): regression coefficients that follow independent random walks.  "
+      "predictors: rows x d, row t = x_t; rows past the length of the series serve forecasts.  One variance, "
+      "ChisqModel(df, sigma_guess) prior and sigma upper limit per coefficient.")
+      .def(py::init([](const NpArray &predictors) { return new DynamicRegressionStateModel(matrix_from(predictors)); }),
+           py::arg("predictors"))
+      .def_property_readonly("state_dimension", &DynamicRegressionStateModel::state_dimension)
+      .def_property_readonly("xdim", &DynamicRegressionStateModel::xdim)
+      .def_property_readonly("predictors", [](const DynamicRegressionStateModel &m) {
+        py::array_t<double> out({m.rows(), m.xdim()});
+        std::copy(m.predictors().begin(), m.predictors().end(), out.mutable_data());
+        return out;
+      })
+      .def("set_sigsq", [](DynamicRegressionStateModel &m, const NpArray &v) { m.set_sigsq(vector_from(v)); },
+           "the coefficients' innovation variances")
+      .def("set_initial_state_mean", [](DynamicRegressionStateModel &m, const NpArray &v) { m.set_initial_state_mean(vector_from(v)); })
+      .def("set_initial_state_variance",
+           [](DynamicRegressionStateModel &m, const NpArray &v) { m.set_initial_state_variance(vector_from(v)); },
+           "the diagonal of the initial state's variance")
+      .def("set_prior", &DynamicRegressionStateModel::set_prior, py::arg("coefficient"), py::arg("df"), py::arg("sigma_guess"),
+           py::arg("sigma_upper_limit") = std::numeric_limits<double>::infinity());
+
   py::class_<MonthlyAnnualCycle, Ptr<MonthlyAnnualCycle>>(
       boom, "MonthlyAnnualCycle",
       "MonthlyAnnualCycle(year, month, day): a month-of-year effect for daily data, 12 seasons that start on the "
@@ -502,6 +525,7 @@ PYBIND11_MODULE(_boom, boom) {
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<SemilocalLinearTrendStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<StudentLocalLinearTrendStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<RandomWalkHolidayStateModel> &s) { m.add_state(s); })
+      .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<DynamicRegressionStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<MonthlyAnnualCycle> &s) { m.add_state(s); })
       .def("student_trend_nu", [](const StateSpaceRegressionModel &m, int chain) { return to_numpy(m.student_trend_nu(chain)); },
            py::arg("chain") = 0, "(nu_level, nu_slope) of the StudentLocalLinearTrendStateModel in one chain's draw")

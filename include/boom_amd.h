@@ -825,6 +825,40 @@ int ba_ss_set_season_calendar(ba_engine *e, int32_t block, const uint8_t *new_se
 int ba_ss_get_season_calendar(ba_engine *e, int32_t block, uint8_t *new_season, int64_t *count);
 int ba_monthly_cycle_calendar(int32_t year, int32_t month, int32_t day, int64_t count, uint8_t *out);
 
+/* DynamicRegressionStateModel(X) + DynamicRegressionIndependentPosteriorSampler (one ChisqModel(df,
+ * sigma_guess) and sigma upper limit per coefficient), bsts AddDynamicRegression with
+ * DynamicRegressionRandomWalkOptions (StateModels/DynamicRegressionStateModel.cpp,
+ * create_state_model.cpp:1245-1287).  predictors: rows x xdim, row-major, row t = x_t; finite.
+ * A block of xdim coefficients: T = I, RQR = diag(sigma_1^2 .. sigma_xdim^2), Z_t = x_t;
+ * observe_state adds (now[i] - then[i])^2 per coefficient, n = T - 1 each.  The block cannot exist
+ * without its data, so it has a call of its own instead of a kind of ba_ss_add_state_model (kind 12
+ * there is refused as any unknown kind); the call appends to the list exactly as
+ * ba_ss_add_state_model does, and the first one after ba_ss_clear_state_models starts a new list.
+ * The var_* arrays, initial_state_mean and initial_state_variance hold xdim entries each; an initial
+ * sigma may be 0, the initial state is rmvn(mean, diagonal variance): the variances must be positive.
+ * Limits: 1 <= xdim, state dimension <= 64, 16 variance parameters in the list (the block takes xdim).
+ * rows >= T is needed by a sweep, ba_ss_impute_state, ba_ss_draw_next and ba_ss_prediction_errors,
+ * rows >= T + horizon by ba_ss_forecast (the reference's add_forecast_data): each refuses with a text
+ * when the rows are too few.  ba_ss_set_dynamic_predictors replaces the block's predictors (or extends
+ * them with the forecast's rows); under a look-ahead it is a mutator like the others.
+ * ba_ss_get_dynamic_predictors: *rows = the rows set; predictors may be NULL to ask for the count
+ * alone, else it has room for rows x xdim doubles.  ba_ss_get_state_model reports the block's xdim
+ * variances and sufficient statistics (arrays of xdim); ba_ss_get_state_draw and
+ * ba_ss_state_dimension serve it unchanged.
+ * RNG streams (a convention of this library; BOOM draws the d variances from one generator):
+ * variance slot i of the block reads the chain's sampler id 10 + 16 x (the dynamic coefficients
+ * earlier in the list, those of this block included); at most 16 slots, so at most 250.  In the
+ * state draw the block takes xdim stream-2 normals for the initial state and xdim per step, whatever
+ * the sigmas.  Refused with a text, in either order of the calls: the Student-t / Poisson / logit
+ * observation families; a list that also holds a Student local linear trend (kind 8), a random-walk
+ * holiday (kind 10) or a calendar seasonal (kind 11).  Not built: the hierarchical and the AR forms. */
+int ba_ss_add_dynamic_regression(ba_engine *e, int32_t xdim, const double *predictors, int64_t rows,
+                                 const double *var_df, const double *var_sigma_guess,
+                                 const double *var_sigma_upper_limit, const double *var_initial_sigma,
+                                 const double *initial_state_mean, const double *initial_state_variance);
+int ba_ss_set_dynamic_predictors(ba_engine *e, int32_t block, const double *predictors, int64_t rows);
+int ba_ss_get_dynamic_predictors(ba_engine *e, int32_t block, double *predictors, int64_t *rows);
+
 /* ---- bsts(family = "student"): StateSpaceStudentRegressionModel with
  * StateSpaceStudentPosteriorSampler (Models/StateSpace/StateSpaceStudentRegressionModel.cpp,
  * PosteriorSamplers/StateSpaceStudentPosteriorSampler.cpp:56-126) ----------------------------

@@ -491,6 +491,44 @@ class RandomWalkHolidayStateModel {
   double sigma_ = 1.0, df_ = 1.0, guess_ = 1.0, upper_ = infinity();
 };
 
+// DynamicRegressionStateModel(X) with a DynamicRegressionIndependentPosteriorSampler (StateModels/
+// DynamicRegressionStateModel.cpp; bsts AddDynamicRegression with DynamicRegressionRandomWalkOptions):
+// ba_ss_add_dynamic_regression.  predictors: one row per time point, row t = x_t; rows past the series'
+// length serve forecasts (the reference's add_forecast_data).  One variance, prior and sigma upper limit
+// per coefficient.
+class DynamicRegressionStateModel {
+ public:
+  explicit DynamicRegressionStateModel(const Matrix &predictors) : xdim_(predictors.ncol()), rows_(predictors.nrow()) {
+    if (xdim_ < 1 || rows_ < 1) report_error("a dynamic regression needs at least one row and one column of predictors");
+    x_.resize((size_t)rows_ * xdim_);   // (row-major, as the C-ABI takes them)
+    for (int t = 0; t < rows_; ++t)
+      for (int i = 0; i < xdim_; ++i) x_[(size_t)t * xdim_ + i] = predictors(t, i);
+    a0_ = Vector(xdim_, 0.0);
+    P0_ = Vector(xdim_, 1.0);
+    sigma_ = Vector(xdim_, 1.0);
+    df_ = Vector(xdim_, 1.0);
+    guess_ = Vector(xdim_, 1.0);
+    upper_ = Vector(xdim_, infinity());
+  }
+  int state_dimension() const { return xdim_; }
+  int xdim() const { return xdim_; }
+  int rows() const { return rows_; }
+  const Vector &predictors() const { return x_; }   // rows x xdim, row-major
+  void set_sigsq(const Vector &s) { check_size(s); for (int i = 0; i < xdim_; ++i) sigma_[i] = std::sqrt(s[i]); }
+  void set_initial_state_mean(const Vector &m) { check_size(m); a0_ = m; }
+  void set_initial_state_variance(const Vector &diagonal) { check_size(diagonal); P0_ = diagonal; }
+  // coefficient i's ChisqModel(df, sigma_guess) and sigma upper limit
+  void set_prior(int i, double df, double sigma_guess, double sigma_upper_limit = infinity()) {
+    if (i < 0 || i >= xdim_) report_error("coefficient index out of range");
+    df_[i] = df; guess_[i] = sigma_guess; upper_[i] = sigma_upper_limit;
+  }
+  void check_size(const Vector &v) const {
+    if ((int)v.size() != xdim_) report_error("a dynamic regression takes one entry per predictor");
+  }
+  int xdim_, rows_;
+  Vector x_, a0_, P0_, sigma_, df_, guess_, upper_;
+};
+
 // ArStateModel(number_of_lags) with an ArPosteriorSampler (StateModels/ArStateModel.hpp:53,
 // TimeSeries/PosteriorSamplers/ArPosteriorSampler.hpp)
 class ArStateModel {
@@ -654,6 +692,7 @@ class StateSpaceRegressionModel : public Model {
   void add_state(const Ptr<StudentLocalLinearTrendStateModel> &s) { Entry e; e.kind = 8; e.student_trend = s; models_.push_back(e); finalized_ = false; }
   void add_state(const Ptr<RandomWalkHolidayStateModel> &s) { Entry e; e.kind = 10; e.holiday = s; models_.push_back(e); finalized_ = false; }
   void add_state(const Ptr<MonthlyAnnualCycle> &s) { Entry e; e.kind = 11; e.monthly = s; models_.push_back(e); finalized_ = false; }
+  void add_state(const Ptr<DynamicRegressionStateModel> &s) { Entry e; e.kind = 12; e.dynreg = s; models_.push_back(e); finalized_ = false; }
   int number_of_state_models() const { return (int)models_.size(); }
   bool has_student_trend() const {
     for (const Entry &e : models_) if (e.kind == 8) return true;
@@ -666,7 +705,8 @@ class StateSpaceRegressionModel : public Model {
     int m = 0;
     for (const Entry &e : models_)
       m += (e.kind == 1 || e.kind == 5) ? 1 : (e.kind == 2 || e.kind == 8) ? 2 : e.kind == 3 ? e.seasonal->state_dimension()
-           : e.kind == 6 ? e.trig->state_dimension() : e.kind == 7 ? 3 : e.kind == 10 ? e.holiday->state_dimension() : e.kind == 11 ? e.monthly->state_dimension() : e.ar->lags_;
+           : e.kind == 6 ? e.trig->state_dimension() : e.kind == 7 ? 3 : e.kind == 10 ? e.holiday->state_dimension() : e.kind == 11 ? e.monthly->state_dimension()
+           : e.kind == 12 ? e.dynreg->state_dimension() : e.ar->lags_;
     return m;
   }
   void finalize_state() {
@@ -685,6 +725,10 @@ class StateSpaceRegressionModel : public Model {
           const int32_t ip[3] = {s.width_, 0, 0};
           eng_->check(ba_ss_add_state_model(h, 10, ip, &s.df_, &s.guess_, &s.upper_, &s.sigma_, nullptr, s.a0_.data(), s.P0_.data()));
           eng_->check(ba_ss_set_holiday_calendar(h, (int32_t)b, s.positions_.data(), (int64_t)s.positions_.size()));
+        } else if (e.kind == 12) {
+          const DynamicRegressionStateModel &s = *e.dynreg;
+          eng_->check(ba_ss_add_dynamic_regression(h, s.xdim_, s.x_.data(), s.rows_, s.df_.data(), s.guess_.data(), s.upper_.data(),
+                                                   s.sigma_.data(), s.a0_.data(), s.P0_.data()));
         } else if (e.kind == 11) {
           const MonthlyAnnualCycle &s = *e.monthly;
           const int32_t ip[3] = {s.nseasons(), 0, 0};
@@ -804,9 +848,11 @@ class StateSpaceRegressionModel : public Model {
     std::vector<double> out;
     for (size_t b = 0; b < models_.size(); ++b) {
       if (models_[b].kind == 5) continue;
-      double v[2] = {0, 0};
+      double v[16] = {0, 0};   // (a dynamic regression: one per coefficient, at most the list's 16 slots)
       eng_->check(ba_ss_get_state_model(eng_->get(), chain, (int32_t)b, v, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
       out.push_back(v[0]);
+      if (models_[b].kind == 12)
+        for (int i = 1; i < models_[b].dynreg->xdim(); ++i) out.push_back(v[i]);
       if (models_[b].kind == 2 || models_[b].kind == 7 || models_[b].kind == 8) out.push_back(v[1]);
     }
     Vector ans(out.size());
@@ -881,7 +927,7 @@ class StateSpaceRegressionModel : public Model {
   }
  private:
   struct Entry {
-    int kind = 0;   // 1 local level, 2 local linear trend, 3 seasonal, 4 autoregression, 5 static intercept, 6 trig, 7 semilocal linear trend, 8 Student local linear trend, 10 random-walk holiday, 11 monthly annual cycle (a calendar seasonal)
+    int kind = 0;   // 1 local level, 2 local linear trend, 3 seasonal, 4 autoregression, 5 static intercept, 6 trig, 7 semilocal linear trend, 8 Student local linear trend, 10 random-walk holiday, 11 monthly annual cycle (a calendar seasonal), 12 dynamic regression
     Ptr<LocalLevelStateModel> level;
     Ptr<LocalLinearTrendStateModel> trend;
     Ptr<SeasonalStateModel> seasonal;
@@ -891,6 +937,7 @@ class StateSpaceRegressionModel : public Model {
     Ptr<SemilocalLinearTrendStateModel> semilocal;
     Ptr<StudentLocalLinearTrendStateModel> student_trend;
     Ptr<RandomWalkHolidayStateModel> holiday;
+    Ptr<DynamicRegressionStateModel> dynreg;
     Ptr<MonthlyAnnualCycle> monthly;
   };
   int student_trend_block() const {
