@@ -17,7 +17,7 @@
 //   3. sigma^2 from (n, relative_sse) with the sigma upper limit.
 // The included set is compacted by ballot and prefix count: lane k < n holds the k-th included
 // lag; log_model_prob and the coefficient draw factor the selected sub-matrix with ar_chol and
-// solve with ar_lsolve / ar_ltsolve (ssg_device.h).
+// solve with ar_lsolve / ar_ltsolve (ar_sampler_device.h).
 #include <hip/hip_runtime.h>
 
 #include "ktimer.h"

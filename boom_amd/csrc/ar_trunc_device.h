@@ -1,6 +1,6 @@
 // The two-sided truncated normal of the autoregression samplers (rtrun_norm_2_mt and its
 // Tn2Sampler): one definition for the kernels that draw AR coefficients one at a time
-// (ssg_device.h, ssm_template_kernel.hip) and for the test probe that calls it directly.
+// (ar_sampler_device.h: ar_draw; ssg_device.h: the semilocal slope) and for the test probe that calls it directly.
 #pragma once
 #include <hip/hip_runtime.h>
 

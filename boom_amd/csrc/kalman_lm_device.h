@@ -15,9 +15,8 @@ namespace {
 
 // (diagnostic build -DBA_KSTAMPS: chain 0 prints its cycles per phase -- KSTAMP, diag.h)
 
-#ifndef BA_HAVE_WAVE_HELPERS   // (ssvs_device.h, when it comes first, has the same four)
-constexpr int WAVE = 64;
-
+// (WAVE: wave_lanes.h, through stream_normals.h)
+#ifndef BA_HAVE_WAVE_HELPERS   // (ssvs_device.h, when it comes first, has the same three)
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double dpp_f64(double x, double fill) {
   const unsigned long long u = __builtin_bit_cast(unsigned long long, x);

@@ -91,6 +91,22 @@ struct SsgBlock {
 };
 // is the block a calendar seasonal (SSG_CALENDAR_SEASONAL: its season starts are read from the packed calendar)?
 __host__ __device__ inline bool ssg_is_calendar(const SsgBlock &k) { return k.kind == SSG_SEASONAL && k.phase == SSG_PHASE_CALENDAR; }
+// A block as one 32-bit word, for the kernels that keep block b's word in lane b of a register and
+// fetch it with v_readlane: kind (3 bits) | first (7) | dim (7) | index of its first variance
+// parameter (5) | autoregression slot (3).  Bits 25 and up belong to the kernel that holds the word
+// (Blocks of ssg_device.h, SsfBlocks of ss_filter_kernel.hip: each says what it keeps there).
+struct SsgBlockWord {
+  static __host__ __device__ __forceinline__ int kind_of(unsigned d) { return (int)(d & 7u); }
+  static __host__ __device__ __forceinline__ int first_of(unsigned d) { return (int)((d >> 3) & 127u); }
+  static __host__ __device__ __forceinline__ int dim_of(unsigned d) { return (int)((d >> 10) & 127u); }
+  static __host__ __device__ __forceinline__ int var0_of(unsigned d) { return (int)((d >> 17) & 31u); }
+  static __host__ __device__ __forceinline__ int arx_of(unsigned d) { return (int)((d >> 22) & 7u); }
+  static __host__ __device__ __forceinline__ unsigned pack(const SsgBlock &K) {
+    const unsigned lo = (unsigned)K.kind | ((unsigned)K.first << 3) | ((unsigned)K.dim << 10) | ((unsigned)K.var0 << 17);
+    const int arx = K.ar_index;   // (-1: the block has no autoregression slot)
+    return lo | ((unsigned)(arx < 0 ? 0 : arx) << 22);
+  }
+};
 // the specification, in device memory (read through the scalar cache)
 struct SsgSpec {
   int32_t m, nblocks, nvar, nar;

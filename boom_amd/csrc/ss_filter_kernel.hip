@@ -24,35 +24,16 @@
 
 #include "ktimer.h"
 #include "ss_filter_params.h"
+#include "wave_lanes.h"
 
 namespace boom_amd {
 
 namespace {
 
-constexpr int SSF_WAVE = 64;
-
-__device__ __forceinline__ void ssf_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// value of lane `src` (wave-uniform src)
-__device__ __forceinline__ double ssf_rl(double x, int src) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, src);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), src);
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-
-// block b's words: kind (3 bits) | first (7) | dim (7) | first variance slot (5) | autoregression slot (3) | has a variance (1)
-struct SsfBlocks {
-  unsigned desc;   // lane b: block b
+// lane b: block b's word (SsgBlockWord: bits 0 - 24) | bit 25: the block has a variance (a static intercept has none)
+struct SsfBlocks : SsgBlockWord {
+  unsigned desc;
   int nb;
-  static __device__ __forceinline__ int kind_of(unsigned d) { return (int)(d & 7u); }
-  static __device__ __forceinline__ int first_of(unsigned d) { return (int)((d >> 3) & 127u); }
-  static __device__ __forceinline__ int dim_of(unsigned d) { return (int)((d >> 10) & 127u); }
-  static __device__ __forceinline__ int var0_of(unsigned d) { return (int)((d >> 17) & 31u); }
-  static __device__ __forceinline__ int arx_of(unsigned d) { return (int)((d >> 22) & 7u); }
   static __device__ __forceinline__ bool has_var(unsigned d) { return ((d >> 25) & 1u) != 0; }
   __device__ __forceinline__ unsigned at(int b) const { return (unsigned)__builtin_amdgcn_readlane((int)desc, b); }
 };
@@ -107,7 +88,7 @@ __device__ __forceinline__ void ssf_apply_T(const SsfBlocks &B, unsigned mv, con
   }
 }
 
-__global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
+__global__ __launch_bounds__(WAVE) void ss_filter_kernel(SsFilterParams P) {
   extern __shared__ double s_P[];   // m x ld
   __shared__ double s_phi[SSG_MAX_AR * AR_MAX], s_var[SSG_MAX_VAR], s_tc[SSG_MAX_STATE], s_ts[SSG_MAX_STATE];
   const int lane = (int)threadIdx.x, row = (int)blockIdx.x;
@@ -123,9 +104,9 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
   {
     const uint8_t *gam = P.src.gamma + chain * P.src.gamma_stride;
     const double *bet = P.src.beta + chain * P.src.beta_stride;
-    for (int t0 = 0; t0 < T; t0 += SSF_WAVE)
+    for (int t0 = 0; t0 < T; t0 += WAVE)
       if (t0 + lane < T) err[t0 + lane] = P.y[t0 + lane];
-    for (int j0 = 0; j0 < p; j0 += SSF_WAVE) {
+    for (int j0 = 0; j0 < p; j0 += WAVE) {
       const int jl = j0 + lane;
       const bool inc = jl < p && gam[jl] != 0;
       const unsigned long long incmask = __ballot(inc);
@@ -133,11 +114,11 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
       const int cnt = __popcll(incmask);
       // lane k <- the k-th included column of the batch (ascending)
       const int rank = __popcll(incmask & ((1ull << lane) - 1ull));
-      __shared__ int s_idx[SSF_WAVE];
-      __shared__ double s_beta[SSF_WAVE];
+      __shared__ int s_idx[WAVE];
+      __shared__ double s_beta[WAVE];
       if (inc) { s_idx[rank] = jl; s_beta[rank] = bet[jl]; }
-      ssf_sync();
-      for (int t0 = 0; t0 < T; t0 += SSF_WAVE) {
+      wave_lds_sync();
+      for (int t0 = 0; t0 < T; t0 += WAVE) {
         const int t = t0 + lane;
         if (t < T) {
           double ys = err[t];
@@ -145,7 +126,7 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
           err[t] = ys;
         }
       }
-      ssf_sync();
+      wave_lds_sync();
     }
   }
 
@@ -162,8 +143,7 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
   bool calb = false;     // lane b: block b is a calendar seasonal -- it moves where the calendar's entry t + 1 says so
   if (lane < P.nblocks) {
     const SsgBlock &K = Q.blk[lane];
-    B.desc = (unsigned)K.kind | ((unsigned)K.first << 3) | ((unsigned)K.dim << 10) | ((unsigned)K.var0 << 17) |
-             ((unsigned)(K.ar_index < 0 ? 0 : K.ar_index) << 22) | ((unsigned)(K.nvar > 0 ? 1 : 0) << 25);
+    B.desc = SsfBlocks::pack(K) | ((unsigned)(K.nvar > 0 ? 1 : 0) << 25);
     calb = ssg_is_calendar(K);
     if (K.kind == SSG_SEASONAL) {
       dur = K.duration;
@@ -176,7 +156,7 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
   const unsigned always =(unsigned)__ballot(SsfBlocks::kind_of(B.desc) == SSG_LOCAL_LINEAR_TREND ||
                                             SsfBlocks::kind_of(B.desc) == SSG_AR || SsfBlocks::kind_of(B.desc) == SSG_TRIG ||
                                             SsfBlocks::kind_of(B.desc) == SSG_SEMILOCAL);
-  ssf_sync();
+  wave_lds_sync();
   // per lane: is the component one Z selects; the variance its diagonal entry gains every step;
   // the seasonal block it is the first component of (-1: none); its part in a Student trend (1 level, 2 slope)
   bool zsel = false;
@@ -225,16 +205,16 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
   double xw = 0.0, xn = 0.0;
   if (dr) xn = P.dyn[dcol];
   const bool act = lane < m;
-  for (int e = lane; e < m * ld; e += SSF_WAVE) s_P[e] = 0.0;
-  ssf_sync();
+  for (int e = lane; e < m * ld; e += WAVE) s_P[e] = 0.0;
+  wave_lds_sync();
   if (act) s_P[lane * ld + lane] = P0l;
-  ssf_sync();
+  wave_lds_sync();
 
   const double *qw = P.qw ? P.qw + chain * P.qw_stride : nullptr;
   const double nan = __builtin_nan("");
   double ll = 0.0;
   bool dead = false;
-  for (int tb = 0; tb < T; tb += SSF_WAVE) {
+  for (int tb = 0; tb < T; tb += WAVE) {
     const int tt = tb + lane;
     const double ys_l = tt < T ? err[tt] : 0.0;
     const unsigned long long obsmask = __ballot(tt < T && P.observed[tt] != 0);
@@ -244,7 +224,7 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
     // (the calendar's entries t -- Z_t -- and t + 1 -- RQR_t -- of the block's steps, one per lane)
     unsigned long long cw_l = SSG_CAL_NONE, cn_l = SSG_CAL_NONE;
     if (P.cal) { if (tt < T) cw_l = P.cal[tt]; if (tt + 1 < T) cn_l = P.cal[tt + 1]; }
-    const int ns = T - tb < SSF_WAVE ? T - tb : SSF_WAVE;
+    const int ns = T - tb < WAVE ? T - tb : WAVE;
     for (int s = 0; s < ns; ++s) {
       const bool obs = ((obsmask >> s) & 1ull) != 0;
       double vout = nan, F = nan;
@@ -252,8 +232,8 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
       bool hgain = false;   // this lane's diagonal entry gains the holiday's variance at this step
       bool calmove = false; // lane b: calendar seasonal b steps into a new season
       if (P.cal) {
-        const unsigned long long cw = __builtin_bit_cast(unsigned long long, ssf_rl(__builtin_bit_cast(double, cw_l), s));
-        const unsigned long long cn = __builtin_bit_cast(unsigned long long, ssf_rl(__builtin_bit_cast(double, cn_l), s));
+        const unsigned long long cw = __builtin_bit_cast(unsigned long long, rl(__builtin_bit_cast(double, cw_l), s));
+        const unsigned long long cn = __builtin_bit_cast(unsigned long long, rl(__builtin_bit_cast(double, cn_l), s));
         calmove = calb && ((cn >> (8 * (lane & 7))) & (unsigned long long)SSG_CAL_SEASON) != 0;
         zmask_t |= __ballot(hol && lane == hfirst + (int)((cw >> hsh) & 0xffu));
         hgain = hol && lane == hfirst + (int)((cn >> hsh) & 0xffu);
@@ -271,20 +251,20 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
         }
         for (unsigned long long zm = drmask; zm; zm &= zm - 1) {   // (Z_t = x_t on these components)
           const int j = __builtin_ctzll(zm);
-          const double xj = ssf_rl(xw, j);
+          const double xj = rl(xw, j);
           if (act) pz += xj * s_P[lane * ld + j];
         }
         double za = 0.0, zpz = 0.0;
         for (unsigned long long zm = zmask_t; zm; zm &= zm - 1) {
           const int j = __builtin_ctzll(zm);
-          za += ssf_rl(a, j);
-          zpz += ssf_rl(pz, j);
+          za += rl(a, j);
+          zpz += rl(pz, j);
         }
         for (unsigned long long zm = drmask; zm; zm &= zm - 1) {
           const int j = __builtin_ctzll(zm);
-          const double xj = ssf_rl(xw, j);
-          za += xj * ssf_rl(a, j);
-          zpz += xj * ssf_rl(pz, j);
+          const double xj = rl(xw, j);
+          za += xj * rl(a, j);
+          zpz += xj * rl(pz, j);
         }
         F = zpz + sigsq;
         if (!(F > 0.0) || !(F <= 1.79769313486231570815e308)) {
@@ -293,14 +273,14 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
           F = nan;
           if (lane == 0) atomicMin(P.flag, (int)chain);
         } else {
-          const double ys = ssf_rl(ys_l, s);
+          const double ys = rl(ys_l, s);
           const double v = obs ? ys - za : 0.0;
           const double Finv = 1.0 / F;
           if (obs) {
             if (act) {
               a += pz * (v * Finv);
               double *prow = s_P + lane * ld;
-              for (int j = 0; j < m; ++j) prow[j] -= (pz * ssf_rl(pz, j)) * Finv;
+              for (int j = 0; j < m; ++j) prow[j] -= (pz * rl(pz, j)) * Finv;
             }
           }
           vout = v;
@@ -308,20 +288,20 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
           const unsigned mv = (unsigned)__ballot(lane < B.nb && SsfBlocks::kind_of(B.desc) == SSG_SEASONAL && (calb ? calmove : rc == 0)) & seasmask;
           if (always | mv) {
             if (act) s_P[lane * ld + m] = a;
-            ssf_sync();
-            for (int c = lane; c <= m; c += SSF_WAVE) ssf_apply_T(B, mv, s_phi, s_tc, s_ts, s_P + c, ld);
-            ssf_sync();
+            wave_lds_sync();
+            for (int c = lane; c <= m; c += WAVE) ssf_apply_T(B, mv, s_phi, s_tc, s_ts, s_P + c, ld);
+            wave_lds_sync();
             if (act) {
               ssf_apply_T(B, mv, s_phi, s_tc, s_ts, s_P + lane * ld, 1);
               a = s_P[lane * ld + m];
             }
-            ssf_sync();
+            wave_lds_sync();
             // (the two passes agree only up to rounding: the upper triangle is the variance)
             if (act)
               for (int j = 0; j < lane; ++j) s_P[lane * ld + j] = s_P[j * ld + lane];
           }
           // (the step's Student-trend weights: every lane reads them, the trend's two lanes use them)
-          const double wl = ssf_rl(wl_l, s), ws = ssf_rl(ws_l, s);
+          const double wl = rl(wl_l, s), ws = rl(ws_l, s);
           if (act) {
             double q = qdiag;
             if (stu) q = qdiag / (stu == 1 ? wl : ws);
@@ -329,7 +309,7 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
             if (hgain) q = hvar;
             if (q != 0.0) s_P[lane * ld + lane] += q;
           }
-          ssf_sync();
+          wave_lds_sync();
         }
       }
       if (lane < B.nb) { rc = rc + 1 == dur ? 0 : rc + 1; }
@@ -339,7 +319,7 @@ __global__ __launch_bounds__(SSF_WAVE) void ss_filter_kernel(SsFilterParams P) {
     // summed in step order
     const bool ob_l = ((obsmask >> lane) & 1ull) != 0;
     const double term = ob_l ? -0.5 * (1.8378770664093454835606594728112 + log(F_l) + v_l * v_l / F_l) : 0.0;
-    for (int s = 0; s < ns; ++s) ll += ssf_rl(term, s);
+    for (int s = 0; s < ns; ++s) ll += rl(term, s);
     if (tt < T) {
       err[tt] = (P.standardize && ob_l) ? v_l / sqrt(F_l) : v_l;
       if (var_out) var_out[tt] = F_l;
@@ -355,7 +335,7 @@ size_t ss_filter_lds(int m, int ld) { return (size_t)m * ld * sizeof(double); }
 hipError_t launch_ss_filter(hipStream_t stream, const SsFilterParams &P) {
   if (P.chain_count <= 0) return hipSuccess;
   KtScope kt(stream, KT_SS_FILTER);
-  hipLaunchKernelGGL(ss_filter_kernel, dim3((unsigned)P.chain_count), dim3(SSF_WAVE), ss_filter_lds(P.m, P.ld), stream, P);
+  hipLaunchKernelGGL(ss_filter_kernel, dim3((unsigned)P.chain_count), dim3(WAVE), ss_filter_lds(P.m, P.ld), stream, P);
   return hipGetLastError();
 }
 

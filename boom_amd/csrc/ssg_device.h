@@ -1,63 +1,20 @@
 // Device helpers of the general structural state-space kernel (ssm_kernel.hip: one chain per
-// workgroup, any state dimension <= 64): cross-lane moves, the ArPosteriorSampler, the block list and the
-// transition's action on lane-distributed vectors.  See ssm_kernel.hip for the model.
+// workgroup, any state dimension <= 64): the semilocal slope's sampler, the block list and the
+// transition's action on lane-distributed vectors; the cross-lane moves are wave_lanes.h's, the
+// ArPosteriorSampler is ar_sampler_device.h's.  See ssg_simsmooth.h for the model.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ar_sampler_device.h"
 #include "ar_trunc_device.h"
 #include "device_rng.h"
 #include "kalman_params.h"
 #include "stream_normals.h"
+#include "wave_lanes.h"
 
 namespace boom_amd {
 
 namespace {
-
-constexpr int WAVE = 64;
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double sdpp(double x, double fill) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-  const unsigned long long f = __builtin_bit_cast(unsigned long long, fill);
-  const int lo = __builtin_amdgcn_update_dpp((int)(unsigned)f, (int)(unsigned)u, CTRL, ROW_MASK, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp((int)(unsigned)(f >> 32), (int)(unsigned)(u >> 32), CTRL, ROW_MASK, 0xf, false);
-  return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-// value of lane `src` (wave-uniform src)
-__device__ __forceinline__ double rl(double x, int src) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, src);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), src);
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-// a 64-bit word of lane `src` (wave-uniform src)
-__device__ __forceinline__ unsigned long long rlw(unsigned long long u, int src) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, src);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), src);
-  return ((unsigned long long)hi << 32) | lo;
-}
-// sum over the first 16 lanes (the others hold 0), everywhere
-__device__ __forceinline__ double row_total(double x) {
-  x += sdpp<0x111, 0xf>(x, 0.0);  // row_shr:1
-  x += sdpp<0x112, 0xf>(x, 0.0);
-  x += sdpp<0x114, 0xf>(x, 0.0);
-  x += sdpp<0x118, 0xf>(x, 0.0);
-  return rl(x, 15);
-}
-// sum over the wave (lanes that do not take part hold 0), everywhere.  SMALL: the state
-// has at most 16 components -- one row of lanes
-template <bool SMALL>
-__device__ __forceinline__ double wsum(double x) {
-  x += sdpp<0x111, 0xf>(x, 0.0);
-  x += sdpp<0x112, 0xf>(x, 0.0);
-  x += sdpp<0x114, 0xf>(x, 0.0);
-  x += sdpp<0x118, 0xf>(x, 0.0);
-  if (SMALL) return rl(x, 15);
-  return ((rl(x, 15) + rl(x, 31)) + rl(x, 47)) + rl(x, 63);
-}
-// the value of lane - 1 (lane 0: 0) / of lane + 1 (lane 63: 0): wave_shr:1 / wave_shl:1
-__device__ __forceinline__ double from_below(double x) { return sdpp<0x138, 0xf>(x, 0.0); }
-__device__ __forceinline__ double from_above(double x) { return sdpp<0x130, 0xf>(x, 0.0); }
 
 __device__ __forceinline__ int sprev(int c, int ns) { return c == 0 ? ns - 1 : c - 1; }   // the cursor after a move
 __device__ __forceinline__ int snext(int c, int ns) { return c + 1 == ns ? 0 : c + 1; }   // ... before it
@@ -76,125 +33,6 @@ __device__ __forceinline__ void blk_store(double *g, const double *lds, int n, i
   wave_lds_sync();
   for (int i = lane; i < n; i += WAVE) g[i] = lds[i];
   wave_lds_sync();
-}
-
-// ---- ArPosteriorSampler::draw for one chain, by one (whole) wave.  Vectors sit one
-// component per lane (lane i < L), the L x L matrices in LDS at leading dimension
-// AR_MAX; every lane reads the same random numbers.
-struct ArLds {
-  double X[AR_MAX * AR_MAX];    // xtx
-  double Lc[AR_MAX * AR_MAX];   // chol(xtx)
-  double Lp[AR_MAX * AR_MAX];   // chol(xtx / sigsq)
-};
-// lower Cholesky factor of `scale` * A (A symmetric, full storage); false: not positive definite
-__device__ __forceinline__ bool ar_chol(const double *A, double scale, double *Lc, int L, int lane) {
-  for (int j = 0; j < L; ++j) {
-    double sacc = 0.0;
-    if (lane >= j && lane < L) {
-      sacc = A[lane * AR_MAX + j] * scale;
-      for (int k = 0; k < j; ++k) sacc -= Lc[lane * AR_MAX + k] * Lc[j * AR_MAX + k];
-    }
-    const double djj = rl(sacc, j);
-    if (!(djj > 0.0)) return false;
-    const double d = sqrt(djj);
-    if (lane == j) Lc[j * AR_MAX + j] = d;
-    else if (lane > j && lane < L) Lc[lane * AR_MAX + j] = sacc / d;
-    __builtin_amdgcn_wave_barrier();
-  }
-  return true;
-}
-// x: Lc x = b
-__device__ __forceinline__ double ar_lsolve(const double *Lc, double b, int L, int lane) {
-  double x = 0.0;
-  for (int i = 0; i < L; ++i) {
-    const double tot = row_total((lane < i) ? Lc[i * AR_MAX + lane] * x : 0.0);
-    const double xi = (rl(b, i) - tot) / Lc[i * AR_MAX + i];
-    if (lane == i) x = xi;
-  }
-  return x;
-}
-// x: Lc' x = b
-__device__ __forceinline__ double ar_ltsolve(const double *Lc, double b, int L, int lane) {
-  double x = 0.0;
-  for (int i = L - 1; i >= 0; --i) {
-    const double tot = row_total((lane > i && lane < L) ? Lc[lane * AR_MAX + i] * x : 0.0);
-    const double xi = (rl(b, i) - tot) / Lc[i * AR_MAX + i];
-    if (lane == i) x = xi;
-  }
-  return x;
-}
-// ArModel::check_stationary (ArModel.cpp:142-170).  The quick bound sum |phi| < 1,
-// then -- where the reference finds the polynomial's roots (Jenkins-Traub) -- the
-// equivalent step-down recursion: every partial autocorrelation inside (-1, 1).
-__device__ __forceinline__ bool ar_stationary(double a, int L, int lane) {
-  if (row_total((lane < L) ? fabs(a) : 0.0) < 1.0) return true;
-  for (int k = L; k >= 1; --k) {
-    const double r = rl(a, k - 1);
-    if (!(fabs(r) < 1.0)) return false;
-    const double den = 1.0 - r * r;
-    const int src = k - 2 - lane;
-    const double rev = __shfl(a, src < 0 ? 0 : src);
-    if (lane < k - 1) a = (a + r * rev) / den;
-  }
-  return true;
-}
-// draw_phi (up to three multivariate proposals, else one coefficient at a time) and
-// draw_sigma.  suf: the block's sufficient statistics; phi_l: the lane's coefficient
-// (in: current, out: drawn); *sigsq likewise.
-__device__ __forceinline__ int ar_draw(ArLds &W, const double *suf, int L, double prior_df, double prior_ss,
-                                       double sigma_max, SeqRng &rng, double &phi_l, double &sigsq, int lane) {
-  for (int e = lane; e < AR_MAX * AR_MAX; e += WAVE) W.X[e] = suf[e];
-  const double xty = (lane < L) ? suf[AR_SUF_XTY + lane] : 0.0;
-  const double yty = suf[AR_SUF_YTY], n = suf[AR_SUF_N];
-  __builtin_amdgcn_wave_barrier();
-  if (!ar_chol(W.X, 1.0, W.Lc, L, lane)) return CHAIN_NOT_PD;
-  const double phi_hat = ar_ltsolve(W.Lc, ar_lsolve(W.Lc, xty, L, lane), L, lane);
-  // rmvn_ivar(phi_hat, xtx / sigsq)
-  if (!ar_chol(W.X, 1.0 / sigsq, W.Lp, L, lane)) return CHAIN_NOT_PD;
-  bool ok = false;
-  for (int attempt = 0; attempt < 3 && !ok; ++attempt) {
-    double z = 0.0;
-    for (int i = 0; i < L; ++i) {
-      const double zi = d_rnorm(rng, 0.0, 1.0);
-      if (lane == i) z = zi;
-    }
-    const double zs = ar_ltsolve(W.Lp, z, L, lane);   // (whole wave: the lanes talk to each other)
-    const double cand = (lane < L) ? zs + phi_hat : 0.0;
-    ok = ar_stationary(cand, L, lane);
-    if (ok) phi_l = cand;
-  }
-  if (!ok) {
-    double ph = phi_l;
-    if (!ar_stationary(ph, L, lane)) return CHAIN_RNG_BRANCH;
-    for (int i = 0; i < L; ++i) {
-      const double initial_phi = rl(ph, i);
-      double lo = -1, hi = 1;
-      const double ivar = W.X[i * AR_MAX + i];
-      const double dot = row_total((lane < L) ? ph * W.X[lane * AR_MAX + i] : 0.0);
-      const double mu = (rl(xty, i) - (dot - initial_phi * ivar)) / ivar;
-      for (;;) {
-        int bad = 0;
-        const double candidate = ar_rtrun_norm_2(rng, mu, sqrt(1.0 / ivar), lo, hi, &bad);
-        if (bad) return CHAIN_RNG_BRANCH;
-        if (lane == i) ph = candidate;
-        if (ar_stationary(ph, L, lane)) break;
-        if (candidate > initial_phi) hi = candidate; else lo = candidate;
-      }
-    }
-    phi_l = ph;
-  }
-  // draw_sigma: ss = phi' xtx phi - 2 phi' xty + yty, df = n
-  double row = 0.0;
-  for (int j = 0; j < L; ++j) {
-    const double pj = rl(phi_l, j);
-    if (lane < L) row += W.X[lane * AR_MAX + j] * pj;
-  }
-  const double quad = row_total((lane < L) ? phi_l * row : 0.0);
-  const double lin = row_total((lane < L) ? phi_l * xty : 0.0);
-  const double ss = quad - 2 * lin + yty;
-  int bad = 0;
-  sigsq = d_draw_variance(rng, n + prior_df, ss + prior_ss, sigma_max, &bad);
-  return bad ? CHAIN_RNG_BRANCH : CHAIN_OK;
 }
 
 // ---- NonzeroMeanAr1Sampler::draw (NonzeroMeanAr1Sampler.cpp:51-155) for a semilocal trend's slope
@@ -254,10 +92,9 @@ __device__ __forceinline__ int semilocal_slope_draw(const double *suf, const dou
 // advance in one vector operation and a loop over blocks is a ROLLED loop that fetches its
 // block with v_readlane -- eight unrolled copies of every per-block code path made a kernel
 // of 60 000 instructions that ran out of the instruction cache).
-struct Blocks {
-  unsigned desc;   // kind (3 bits) | first (7) | dim (7) | index of its first variance parameter (5) | autoregression slot (3) |
-                   // a random-walk holiday (1: set and read by the HD instances of ssg_simsmooth_kernel only) |
-                   // a dynamic regression (1: set and read by its DR instances only)
+struct Blocks : SsgBlockWord {
+  unsigned desc;   // the block's word (SsgBlockWord: bits 0 - 24) | bit 25: a random-walk holiday (set and read by the
+                   // HD instances of ssg_simsmooth_kernel only) | bit 26: a dynamic regression (its DR instances only)
   unsigned dp;     // seasonal: duration (16 bits) | phase (16)  (a calendar seasonal: 1 | 0xffff, its closed forms never fire)
   unsigned rc;     // seasonal: (index of the step's transition + 1 - phase) mod duration (16 bits: 0 = it moves) |
                    //           the rotating layout's cursor (16): physical slot of the block's first component
@@ -267,11 +104,6 @@ struct Blocks {
   unsigned armask;     // bit b: block b is an autoregression
   unsigned trigmask;   // bit b: block b is a trig model (pairs of components that rotate)
   unsigned slmask;     // bit b: block b is a semilocal linear trend (level, slope, the slope's long-run mean)
-  static __device__ __forceinline__ int kind_of(unsigned d) { return (int)(d & 7u); }
-  static __device__ __forceinline__ int first_of(unsigned d) { return (int)((d >> 3) & 127u); }
-  static __device__ __forceinline__ int dim_of(unsigned d) { return (int)((d >> 10) & 127u); }
-  static __device__ __forceinline__ int var0_of(unsigned d) { return (int)((d >> 17) & 31u); }
-  static __device__ __forceinline__ int arx_of(unsigned d) { return (int)((d >> 22) & 7u); }
   static __device__ __forceinline__ bool holiday_of(unsigned d) { return ((d >> 25) & 1u) != 0; }
   static __device__ __forceinline__ bool dynreg_of(unsigned d) { return ((d >> 26) & 1u) != 0; }
   // block b's words, wave-uniform
@@ -282,8 +114,7 @@ struct Blocks {
     desc = 0; dp = 1; rc = 0;
     if (lane < nblocks) {
       const SsgBlock &K = Q.blk[lane];
-      desc = (unsigned)K.kind | ((unsigned)K.first << 3) | ((unsigned)K.dim << 10) |
-             ((unsigned)K.var0 << 17) | ((unsigned)(K.ar_index < 0 ? 0 : K.ar_index) << 22);
+      desc = pack(K);
       dp = (unsigned)K.duration | ((unsigned)K.phase << 16);
     }
     const int kd = kind_of(desc);

@@ -62,11 +62,13 @@
 //     selects, the column pass, the pass over the lane's row that applies T' from the
 //     right).  (PZ_i PZ_k) / F is formed as a commutative product first and the two passes
 //     sum in the same order, so P stays exactly symmetric.
-// (this header: the kernel template.  ssm_kernel.hip instantiates the scalar and the H_t instances and
-// holds the launcher and the forecast kernel; ssm_qt_kernel.hip instantiates the Q_t instances -- a
-// file of their own so that the two compile side by side: 24 instances in one file took about 5 min
-// against 3 min 06 s for the 16 -- ssm_hd_kernel.hip, a third, the calendar instances, and
-// ssm_dr_kernel.hip, a fourth, the dynamic regression's.)
+// (this header: the kernel template and ssg_launch_variant, the one place that turns a launch's (ld, glob)
+// into an instance.  An instance is named by its key <LDC, GLOB, SsgVariant>; which variant serves a launch
+// is ssg_choose_kernel's decision (ssg_instances.h), taken by launch_ssm_simsmooth.  Each variant's 8
+// instances are made where its launch_ssg_* is defined, a line that calls ssg_launch_variant: plain and HT
+// in ssm_kernel.hip (with the launcher and the forecast kernel), QT in ssm_qt_kernel.hip, HD in
+// ssm_hd_kernel.hip, DR in ssm_dr_kernel.hip -- files of their own so that they compile side by side: 24
+// instances in one file took about 5 min against 3 min 06 s for 16, a file of 8 takes 74 s.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -80,6 +82,7 @@
 
 #include "ssg_device.h"
 #include "ssg_forecast_device.h"
+#include "ssg_instances.h"
 
 namespace boom_amd {
 
@@ -95,7 +98,10 @@ __host__ __device__ inline int ssg_pass_lds_doubles(int m, int ld, int bl, int n
 }
 
 // grid = chains, block = 128, dynamic LDS = max(the normals generator's lists, the
-// sampler's matrices, ssg_pass_lds_doubles).  SMALL: m <= 16.
+// sampler's matrices, ssg_pass_lds_doubles).  An instance's key is <LDC, GLOB, V>; the names the body
+// uses -- SMALL, HT, QT, HD, DR -- are derived from the key at the top of the body: SMALL is LDC == 17
+// (m <= 16), and exactly one of HT / QT / HD / DR is true for the variant V of that name, none for
+// SSG_V_PLAIN (ssg_instances.h).
 // LDC: the leading dimension of P as a compile-time constant (17 / 33 / 61 / 65, chosen from
 // the state dimension by ssg_finish): an entry's LDS address is then an immediate offset from
 // the lane's column or row, where a run-time ld cost an address computation per entry.
@@ -152,8 +158,10 @@ __host__ __device__ inline int ssg_pass_lds_doubles(int m, int ld, int bl, int n
 // wave 1's PZ the block's whole row, a broadcast read per component.  No step waits for HBM.  The block
 // draws d state-error normals per step whatever the sigmas (sigma_i = 0 scales its normal to 0) and d for
 // the initial state (rmvn_mt).  Variance slot i of the block reads sampler id sid[0] + 16 i.
-template <bool SMALL, int LDC, bool GLOB, bool HT = false, bool QT = false, bool HD = false, bool DR = false>
+template <int LDC, bool GLOB, SsgVariant V>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void ssg_simsmooth_kernel(SsParams P, int draw_variances) {
+  constexpr bool SMALL = LDC == 17;
+  constexpr bool HT = V == SSG_V_HT, QT = V == SSG_V_QT, HD = V == SSG_V_HD, DR = V == SSG_V_DR;
   constexpr int SSG_BATCH = SMALL ? 4 : 8;   // entries of a column / row of P asked of the LDS together
   extern __shared__ __align__(16) unsigned char s_raw[];
   __shared__ int s_flag;
@@ -1326,11 +1334,34 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
   }
 }
 
-// the Q_t instances' launch (ssm_qt_kernel.hip): `lds` bytes of dynamic LDS as ssm_dynamic_lds sizes them
+// The launch of variant V: the instance whose LDC is the launch's leading dimension (ssg_finish,
+// ssg_spec.h -- the host sized the LDS by it, so the value compared and the value compiled in are ONE
+// template argument) and whose GLOB says whether the list holds a trig or semilocal block.  `lds`: bytes of
+// dynamic LDS as ssm_dynamic_lds sizes them.  The translation unit that calls this makes V's 8 instances.
+template <SsgVariant V, int LDC, int... REST>
+hipError_t ssg_launch_ld(hipStream_t stream, const SsParams &P, int draw_variances, size_t lds) {
+  if (P.ssm.ld == LDC) {
+    const auto kernel = P.ssm.glob != 0 ? ssg_simsmooth_kernel<LDC, true, V> : ssg_simsmooth_kernel<LDC, false, V>;
+    // (more than 64 KB of dynamic LDS has to be asked for -- per device, so every time)
+    if (lds > 65536) {
+      const hipError_t e2 = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e2 != hipSuccess) return e2;
+    }
+    hipLaunchKernelGGL(kernel, dim3(P.chain_count), dim3(2 * WAVE), lds, stream, P, draw_variances);
+    return hipSuccess;
+  }
+  if constexpr (sizeof...(REST) > 0) return ssg_launch_ld<V, REST...>(stream, P, draw_variances, lds);
+  return hipErrorInvalidValue;
+}
+template <SsgVariant V>
+hipError_t ssg_launch_variant(hipStream_t stream, const SsParams &P, int draw_variances, size_t lds) {
+  return ssg_launch_ld<V, 17, 33, 61, 65>(stream, P, draw_variances, lds);
+}
+// one per variant, each in the file that makes its instances (see the head of this file)
+hipError_t launch_ssg_plain(hipStream_t stream, const SsParams &P, int draw_variances, size_t lds);
+hipError_t launch_ssg_ht(hipStream_t stream, const SsParams &P, int draw_variances, size_t lds);
 hipError_t launch_ssg_qt(hipStream_t stream, const SsParams &P, int draw_variances, size_t lds);
-// the holiday instances' launch (ssm_hd_kernel.hip)
 hipError_t launch_ssg_hd(hipStream_t stream, const SsParams &P, int draw_variances, size_t lds);
-// the dynamic regression's instances' launch (ssm_dr_kernel.hip)
 hipError_t launch_ssg_dr(hipStream_t stream, const SsParams &P, int draw_variances, size_t lds);
 
 }  // namespace boom_amd

@@ -1,6 +1,6 @@
 // The general structural state-space kernel's launchers and the forecast kernel.  The kernel itself --
 // the state half of StateSpacePosteriorSampler::draw() for any list of state models -- is the template
-// of ssg_simsmooth.h; this file instantiates its scalar and H_t instances.
+// of ssg_simsmooth.h; this file makes its plain and H_t instances (launch_ssg_plain, launch_ssg_ht).
 #include "ssg_simsmooth.h"
 
 namespace boom_amd {
@@ -56,53 +56,25 @@ size_t ssm_dynamic_lds(const SsmParams &M) {
 
 hipError_t launch_ssm_template(hipStream_t stream, const SsParams &P, int draw_variances);
 
+hipError_t launch_ssg_plain(hipStream_t stream, const SsParams &P, int draw_variances, size_t lds) { return ssg_launch_variant<SSG_V_PLAIN>(stream, P, draw_variances, lds); }
+hipError_t launch_ssg_ht(hipStream_t stream, const SsParams &P, int draw_variances, size_t lds) { return ssg_launch_variant<SSG_V_HT>(stream, P, draw_variances, lds); }
+
 hipError_t launch_ssm_simsmooth(hipStream_t stream, const SsParams &P, int draw_variances) {
-  const dim3 grid(P.chain_count), block(2 * WAVE);
   const size_t lds = ssm_dynamic_lds(P.ssm);
-  hipError_t err;
+  const SsgChoice choice = ssg_choose_kernel(P);   // (ssg_instances.h: nothing else decides)
+  if (choice.kernel == SSG_CHOICE_INVALID) return hipErrorInvalidValue;
+  hipError_t err = hipErrorInvalidValue;
   {
     KtScope kt(stream, KT_SSM);
-    if (P.ssm.tpl_trend > 0 && !P.h && !P.qw && !P.cal && !P.dyn) {
-      err = launch_ssm_template(stream, P, draw_variances);
-      if (err != hipSuccess) return err;
-    } else {
-      // (more than 64 KB of dynamic LDS has to be asked for -- per device, so every time)
-      auto go = [&](auto kernel) -> hipError_t {
-        if (lds > 65536) {
-          const hipError_t e2 = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-          if (e2 != hipSuccess) return e2;
-        }
-        hipLaunchKernelGGL(kernel, grid, block, lds, stream, P, draw_variances);
-        return hipSuccess;
-      };
-      const bool glob = P.ssm.glob != 0;   // (a trig or semilocal block in the list)
-      if (P.dyn) {   // a dynamic regression in the list: the predictor table's instances
-        if (P.h || P.qw || P.cal) return hipErrorInvalidValue;   // (the rule book refuses such a list)
-        err = launch_ssg_dr(stream, P, draw_variances, lds);
-      } else if (P.cal) {   // a random-walk holiday in the list: the calendar's instances
-        if (P.h || P.qw) return hipErrorInvalidValue;   // (the observation families and the Student trend refuse such a list)
-        err = launch_ssg_hd(stream, P, draw_variances, lds);
-      } else if (P.qw) {   // a Student local linear trend in the list: the per-step state variance's instances
-        if (P.h) return hipErrorInvalidValue;   // (the observation families refuse such a list)
-        err = launch_ssg_qt(stream, P, draw_variances, lds);
-      } else if (P.h) {   // the per-step observation variance's instances
-        switch (P.ssm.ld) {
-          case 17: err = glob ? go(ssg_simsmooth_kernel<true, 17, true, true>) : go(ssg_simsmooth_kernel<true, 17, false, true>); break;
-          case 33: err = glob ? go(ssg_simsmooth_kernel<false, 33, true, true>) : go(ssg_simsmooth_kernel<false, 33, false, true>); break;
-          case 61: err = glob ? go(ssg_simsmooth_kernel<false, 61, true, true>) : go(ssg_simsmooth_kernel<false, 61, false, true>); break;
-          case 65: err = glob ? go(ssg_simsmooth_kernel<false, 65, true, true>) : go(ssg_simsmooth_kernel<false, 65, false, true>); break;
-          default: return hipErrorInvalidValue;
-        }
-      } else
-      switch (P.ssm.ld) {   // ssg_leading_dimension(m)
-        case 17: err = glob ? go(ssg_simsmooth_kernel<true, 17, true>) : go(ssg_simsmooth_kernel<true, 17, false>); break;
-        case 33: err = glob ? go(ssg_simsmooth_kernel<false, 33, true>) : go(ssg_simsmooth_kernel<false, 33, false>); break;
-        case 61: err = glob ? go(ssg_simsmooth_kernel<false, 61, true>) : go(ssg_simsmooth_kernel<false, 61, false>); break;
-        case 65: err = glob ? go(ssg_simsmooth_kernel<false, 65, true>) : go(ssg_simsmooth_kernel<false, 65, false>); break;
-        default: return hipErrorInvalidValue;
-      }
-      if (err != hipSuccess) return err;
+    if (choice.kernel == SSG_CHOICE_TEMPLATE) err = launch_ssm_template(stream, P, draw_variances);
+    else switch (choice.variant) {
+      case SSG_V_DR: err = launch_ssg_dr(stream, P, draw_variances, lds); break;
+      case SSG_V_HD: err = launch_ssg_hd(stream, P, draw_variances, lds); break;
+      case SSG_V_QT: err = launch_ssg_qt(stream, P, draw_variances, lds); break;
+      case SSG_V_HT: err = launch_ssg_ht(stream, P, draw_variances, lds); break;
+      case SSG_V_PLAIN: err = launch_ssg_plain(stream, P, draw_variances, lds); break;
     }
+    if (err != hipSuccess) return err;
     err = hipGetLastError();
   }
   if (err != hipSuccess) return err;

@@ -39,10 +39,11 @@
 #include "diag.h"
 #include "ktimer.h"
 
-#include "ar_trunc_device.h"
+#include "ar_sampler_device.h"   // (the autoregression block's ArPosteriorSampler: the general kernel's)
 #include "device_rng.h"
 #include "kalman_params.h"
 #include "stream_normals.h"
+#include "wave_lanes.h"
 
 // (round 4) This is the round-3 kernel, kept as the FAST PATH of the block lists that
 // are its template -- [local level | local linear trend] [+ seasonal of duration 1]
@@ -54,8 +55,8 @@ namespace boom_amd {
 
 namespace {
 
-constexpr int WAVE = 64;
-constexpr int SSM_MAX = 16;        // the template's state dimension limit (= AR_MAX)
+constexpr int SSM_MAX = 16;        // the template's state dimension limit
+static_assert(SSM_MAX == AR_MAX, "the sampler's matrices (ArLds) and the template's share one leading dimension");
 constexpr int PLD = SSM_MAX + 1;   // leading dimension of the state variance in LDS
 constexpr int V_FAILED = 1 << 30;  // s_vprog: the variance pass stopped (F <= 0)
 
@@ -77,30 +78,6 @@ __device__ __forceinline__ Tpl make_tpl(const SsmParams &M) {
   const int ar0 = M.tpl_trend + (M.tpl_nseasons > 0 ? M.tpl_nseasons - 1 : 0);
   return Tpl{M.spec, M, M.m, M.tpl_trend, M.tpl_nseasons, M.tpl_nseasons > 0 ? M.tpl_trend : -1,
              M.tpl_ar_lags, ar0, M.tpl_trend + (M.tpl_nseasons > 0 ? 1 : 0)};
-}
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double sdpp(double x, double fill) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-  const unsigned long long f = __builtin_bit_cast(unsigned long long, fill);
-  const int lo = __builtin_amdgcn_update_dpp((int)(unsigned)f, (int)(unsigned)u, CTRL, ROW_MASK, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp((int)(unsigned)(f >> 32), (int)(unsigned)(u >> 32), CTRL, ROW_MASK, 0xf, false);
-  return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-// value of lane `src` (wave-uniform src)
-__device__ __forceinline__ double rl(double x, int src) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, src);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), src);
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-// sum over the first 16 lanes (the vector's lanes; the others hold 0), everywhere
-__device__ __forceinline__ double row_total(double x) {
-  x += sdpp<0x111, 0xf>(x, 0.0);  // row_shr:1
-  x += sdpp<0x112, 0xf>(x, 0.0);
-  x += sdpp<0x114, 0xf>(x, 0.0);
-  x += sdpp<0x118, 0xf>(x, 0.0);
-  return rl(x, 15);
 }
 
 // the structure of the transition matrix
@@ -184,126 +161,6 @@ __device__ __forceinline__ void blk_store(double *g, const double *lds, int n, i
   __builtin_amdgcn_wave_barrier();
   for (int i = lane; i < n; i += WAVE) g[i] = lds[i];
   __builtin_amdgcn_wave_barrier();
-}
-
-// ---- ArPosteriorSampler::draw for one chain, by one (whole) wave.  Vectors sit one
-// component per lane (lane i < L), the L x L matrices in LDS at leading dimension
-// SSM_MAX; every lane reads the same random numbers.
-struct ArLds {
-  double X[SSM_MAX * SSM_MAX];    // xtx
-  double Lc[SSM_MAX * SSM_MAX];   // chol(xtx)
-  double Lp[SSM_MAX * SSM_MAX];   // chol(xtx / sigsq)
-};
-// lower Cholesky factor of `scale` * A (A symmetric, full storage); false: not positive definite
-__device__ __forceinline__ bool ar_chol(const double *A, double scale, double *Lc, int L, int lane) {
-  for (int j = 0; j < L; ++j) {
-    double sacc = 0.0;
-    if (lane >= j && lane < L) {
-      sacc = A[lane * SSM_MAX + j] * scale;
-      for (int k = 0; k < j; ++k) sacc -= Lc[lane * SSM_MAX + k] * Lc[j * SSM_MAX + k];
-    }
-    const double djj = rl(sacc, j);
-    if (!(djj > 0.0)) return false;
-    const double d = sqrt(djj);
-    if (lane == j) Lc[j * SSM_MAX + j] = d;
-    else if (lane > j && lane < L) Lc[lane * SSM_MAX + j] = sacc / d;
-    __builtin_amdgcn_wave_barrier();
-  }
-  return true;
-}
-// x: Lc x = b
-__device__ __forceinline__ double ar_lsolve(const double *Lc, double b, int L, int lane) {
-  double x = 0.0;
-  for (int i = 0; i < L; ++i) {
-    const double tot = row_total((lane < i) ? Lc[i * SSM_MAX + lane] * x : 0.0);
-    const double xi = (rl(b, i) - tot) / Lc[i * SSM_MAX + i];
-    if (lane == i) x = xi;
-  }
-  return x;
-}
-// x: Lc' x = b
-__device__ __forceinline__ double ar_ltsolve(const double *Lc, double b, int L, int lane) {
-  double x = 0.0;
-  for (int i = L - 1; i >= 0; --i) {
-    const double tot = row_total((lane > i && lane < L) ? Lc[lane * SSM_MAX + i] * x : 0.0);
-    const double xi = (rl(b, i) - tot) / Lc[i * SSM_MAX + i];
-    if (lane == i) x = xi;
-  }
-  return x;
-}
-// ArModel::check_stationary (ArModel.cpp:142-170).  The quick bound sum |phi| < 1,
-// then -- where the reference finds the polynomial's roots (Jenkins-Traub) -- the
-// equivalent step-down recursion: every partial autocorrelation inside (-1, 1).
-__device__ __forceinline__ bool ar_stationary(double a, int L, int lane) {
-  if (row_total((lane < L) ? fabs(a) : 0.0) < 1.0) return true;
-  for (int k = L; k >= 1; --k) {
-    const double r = rl(a, k - 1);
-    if (!(fabs(r) < 1.0)) return false;
-    const double den = 1.0 - r * r;
-    const int src = k - 2 - lane;
-    const double rev = __shfl(a, src < 0 ? 0 : src);
-    if (lane < k - 1) a = (a + r * rev) / den;
-  }
-  return true;
-}
-// draw_phi (up to three multivariate proposals, else one coefficient at a time) and
-// draw_sigma.  phi_l: the lane's coefficient (in: current, out: drawn); *sigsq likewise.
-__device__ __forceinline__ int ar_draw(ArLds &W, const Tpl &Q, int chain, SeqRng &rng, double &phi_l,
-                                       double &sigsq, int lane) {
-  const int L = Q.ar_lags;
-  const double *suf = Q.ar_suf(chain);
-  for (int e = lane; e < SSM_MAX * SSM_MAX; e += WAVE) W.X[e] = suf[e];
-  const double xty = (lane < L) ? suf[AR_SUF_XTY + lane] : 0.0;
-  const double yty = suf[AR_SUF_YTY], n = suf[AR_SUF_N];
-  __builtin_amdgcn_wave_barrier();
-  if (!ar_chol(W.X, 1.0, W.Lc, L, lane)) return CHAIN_NOT_PD;
-  const double phi_hat = ar_ltsolve(W.Lc, ar_lsolve(W.Lc, xty, L, lane), L, lane);
-  // rmvn_ivar(phi_hat, xtx / sigsq)
-  if (!ar_chol(W.X, 1.0 / sigsq, W.Lp, L, lane)) return CHAIN_NOT_PD;
-  bool ok = false;
-  for (int attempt = 0; attempt < 3 && !ok; ++attempt) {
-    double z = 0.0;
-    for (int i = 0; i < L; ++i) {
-      const double zi = d_rnorm(rng, 0.0, 1.0);
-      if (lane == i) z = zi;
-    }
-    const double zs = ar_ltsolve(W.Lp, z, L, lane);   // (whole wave: the lanes talk to each other)
-    const double cand = (lane < L) ? zs + phi_hat : 0.0;
-    ok = ar_stationary(cand, L, lane);
-    if (ok) phi_l = cand;
-  }
-  if (!ok) {
-    double ph = phi_l;
-    if (!ar_stationary(ph, L, lane)) return CHAIN_RNG_BRANCH;
-    for (int i = 0; i < L; ++i) {
-      const double initial_phi = rl(ph, i);
-      double lo = -1, hi = 1;
-      const double ivar = W.X[i * SSM_MAX + i];
-      const double dot = row_total((lane < L) ? ph * W.X[lane * SSM_MAX + i] : 0.0);
-      const double mu = (rl(xty, i) - (dot - initial_phi * ivar)) / ivar;
-      for (;;) {
-        int bad = 0;
-        const double candidate = ar_rtrun_norm_2(rng, mu, sqrt(1.0 / ivar), lo, hi, &bad);
-        if (bad) return CHAIN_RNG_BRANCH;
-        if (lane == i) ph = candidate;
-        if (ar_stationary(ph, L, lane)) break;
-        if (candidate > initial_phi) hi = candidate; else lo = candidate;
-      }
-    }
-    phi_l = ph;
-  }
-  // draw_sigma: ss = phi' xtx phi - 2 phi' xty + yty, df = n
-  double row = 0.0;
-  for (int j = 0; j < L; ++j) {
-    const double pj = rl(phi_l, j);
-    if (lane < L) row += W.X[lane * SSM_MAX + j] * pj;
-  }
-  const double quad = row_total((lane < L) ? phi_l * row : 0.0);
-  const double lin = row_total((lane < L) ? phi_l * xty : 0.0);
-  const double ss = quad - 2 * lin + yty;
-  int bad = 0;
-  sigsq = d_draw_variance(rng, n + Q.S->prior_df[Q.av], ss + Q.S->prior_ss[Q.av], Q.S->sigma_max[Q.av], &bad);
-  return bad ? CHAIN_RNG_BRANCH : CHAIN_OK;
 }
 
 // ---- time across the lanes (round 4).  Two of the five passes have no gain in them: the
@@ -506,7 +363,8 @@ __global__ __launch_bounds__(128) void ssm_simsmooth_kernel(SsParams P, int draw
         // (the sampler's vectors sit at lanes 0 .. L - 1)
         double ph = __shfl(phl, lane + S.a0);
         if (lane >= S.na) ph = 0.0;
-        const int st = ar_draw(s_lds.ar, Q, chain, rng, ph, sig2a, lane);
+        const int st = ar_draw(s_lds.ar, Q.ar_suf(chain), Q.ar_lags, Q.S->prior_df[Q.av], Q.S->prior_ss[Q.av], Q.S->sigma_max[Q.av],
+                                   rng, ph, sig2a, lane);
         if (st != CHAIN_OK) {
           if (lane == 0) s_flag = st;
         } else {

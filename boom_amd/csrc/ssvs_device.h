@@ -9,12 +9,12 @@
 #include "device_rng.h"
 #include "diag.h"
 #include "ssvs_params.h"
+#include "wave_lanes.h"   // (WAVE)
 
 namespace boom_amd {
 
 namespace {
 
-constexpr int WAVE = 64;
 #define BA_INF (__builtin_inf())
 
 // (the diagnostic builds' cycle stamps -- STAMP, SUBSTAMP, TSTAMP, HSTAMP -- are diag.h's)

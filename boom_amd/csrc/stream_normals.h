@@ -29,6 +29,7 @@
 
 #include "device_rng.h"
 #include "ssvs_params.h"
+#include "wave_lanes.h"   // (wave_lds_sync: the one-wave team's hand-off)
 
 namespace boom_amd {
 
@@ -40,14 +41,6 @@ enum : int { STATE_SLOT_STRIDE = 256 };
 template <class Params>
 __host__ __device__ inline int ss_slot_serve(const Params &P) {
   return (P.slot_limit >= 2 && P.slot_limit < STATE_SLOT_STRIDE) ? (P.slot_limit & ~1) : STATE_SLOT_STRIDE;
-}
-
-// LDS hand-off between the lanes of one wavefront (DS operations of a wave
-// complete in order: only the compiler has to be told)
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // (the generator needs no LDS any more; kept so that the kernels' LDS layouts keep their names)

@@ -217,6 +217,23 @@ def general_spec(y, blocks):
     return out
 
 
+def kernel_instance(blocks):
+    """ssg_finish's rule (boom_amd/csrc/ssg_spec.h) for a list of block dicts: (state dimension, leading
+    dimension of P = the LDC of the general kernel's instance, steps per time block, GLOB = a trig or
+    semilocal block in the list).  A dynamic regression ("predictors" in the dict) has an error row and a
+    predictor column per coefficient, a trig block an error row per component, a trend two, the others one."""
+    m = sum(b["dim"] for b in blocks)
+    ndyn = sum(b["dim"] for b in blocks if "predictors" in b)
+    nerr = sum(b["dim"] if ("predictors" in b or b["kind"] == KIND_TRIG) else
+               (2 if b["kind"] in (KIND_LOCAL_LINEAR_TREND, KIND_SEMILOCAL, 8) else 1) for b in blocks)   # (8: a Student trend)
+    nar = sum(b["kind"] in (KIND_AR, KIND_SEMILOCAL) for b in blocks)
+    ld = 17 if m <= 16 else (33 if m <= 32 else (61 if m <= 60 else 65))
+    bl = 64
+    while bl > 8 and (2 * bl * m + m * ld + bl * (nerr + 1) + 64 + 8 + nar * 16 * 17 + 2 * bl * ndyn) * 8 > 39 * 1024:
+        bl //= 2
+    return m, ld, bl, any(b["kind"] in (KIND_TRIG, KIND_SEMILOCAL) for b in blocks)
+
+
 def general_arrays(blocks):
     """the flat arrays of ref_ssg_run / bo_ssm_add_block / ba_ss_add_state"""
     nb = len(blocks)

@@ -4,7 +4,7 @@ tests/test_ss_dynreg_gpu.py).  T = 70 crosses one edge of the kernel's 64-step t
 import numpy as np
 
 import ss_dynreg_oracle as sdo
-from cases import general_data, general_spec
+from cases import general_data, general_spec, kernel_instance
 
 P = 3            # regression coefficients
 HORIZON = 10
@@ -32,8 +32,8 @@ def predictors(rows, d, seed, hard=None):
 MISSING = (12, 64)   # (64: the first step of the second time block)
 
 
-def data(T, seasonal=((4, 1),), seed=5, missing=MISSING, trig=None):
-    X, y, _, _ = general_data(T, P, 2, list(seasonal), seed=seed + T, trig=trig)
+def data(T, seasonal=((4, 1),), seed=5, missing=MISSING, trig=None, p=P):
+    X, y, _, _ = general_data(T, p, 2, list(seasonal), seed=seed + T, trig=trig)
     obs = np.ones(T, np.uint8)
     obs[[t for t in missing if t < T]] = 0
     return X, y, obs
@@ -72,12 +72,26 @@ def list_two(y, T):
         sdo.dynreg_block(predictors(T + HORIZON, 2, 36, hard=T), s, [0.2, 0.4])]
 
 
-def chain_parameters(chains, seed):
+def list_instance(y, T, seasons, glob):
+    """[a one-frequency trig block: GLOB +] a duration-1 seasonal that pads the state to the leading dimension
+    wanted (18, 34, 61 seasons: 33, 61, 65) + dynamic regression d = 2: the kernel instances the lists above
+    do not reach"""
+    pad = ([("trig", 12.0, [1.0])] if glob else []) + [("seasonal", seasons, 1)]
+    return general_spec(y, pad) + [sdo.dynreg_block(predictors(T + HORIZON, 2, 40, hard=T), sdy_of(y), [0.3, 0.5])]
+
+
+def instance_case(seasons, glob):
+    """(T, make, data arguments) of test_impute_state_matches_restatement: two time blocks and three steps"""
+    T = 2 * kernel_instance(list_instance(np.arange(8.0), 8, seasons, glob))[2] + 3
+    return T, lambda y, T: list_instance(y, T, seasons, glob), dict(seasonal=(), missing=(5, T - 2), p=2)
+
+
+def chain_parameters(chains, seed, p=P):
     """every chain its own regression parameters"""
     rs = np.random.Generator(np.random.PCG64(seed))
-    gam = (rs.uniform(size=(chains, P)) < 0.6).astype(np.uint8)
+    gam = (rs.uniform(size=(chains, p)) < 0.6).astype(np.uint8)
     gam[:, 0] = 1
-    return gam, rs.standard_normal((chains, P)) * gam
+    return gam, rs.standard_normal((chains, p)) * gam
 
 
 

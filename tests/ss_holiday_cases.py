@@ -4,7 +4,7 @@ two (63 | 64 and 127 | 128)."""
 import numpy as np
 
 import ss_holiday_oracle as sho
-from cases import general_data, general_spec
+from cases import general_data, general_spec, kernel_instance
 
 P = 3            # regression coefficients
 HORIZON = 10
@@ -42,8 +42,8 @@ def calendars_a(T):
 MISSING_A = (21, 64)   # an active day; the first step of the second time block (active too)
 
 
-def data(T, seasonal=((7, 1),), seed=5, missing=MISSING_A, trig=None):
-    X, y, _, _ = general_data(T, P, 2, list(seasonal), seed=seed + T, trig=trig)
+def data(T, seasonal=((7, 1),), seed=5, missing=MISSING_A, trig=None, p=P):
+    X, y, _, _ = general_data(T, p, 2, list(seasonal), seed=seed + T, trig=trig)
     obs = np.ones(T, np.uint8)
     obs[[t for t in missing if t < T]] = 0
     return X, y, obs
@@ -73,12 +73,28 @@ def list_d(y, T):
     return general_spec(y, [("level",)]) + [sho.holiday_block(2, np.full(T, -1), sdy, 0.5)]
 
 
-def chain_parameters(chains, seed):
+def list_instance(y, T, seasons, glob):
+    """a holiday of width 2 [+ a one-frequency trig block: GLOB] + a duration-1 seasonal that pads the state to
+    the leading dimension wanted (18, 34, 61 seasons: 33, 61, 65): the kernel instances the lists above do
+    not reach"""
+    sdy = float(np.std(y, ddof=1))
+    cal = calendar(2, T, [(0, 1, 1), (T // 2, 0, 2), (T - 1, 0, 1)])
+    pad = ([("trig", 12.0, [1.0])] if glob else []) + [("seasonal", seasons, 1)]
+    return [sho.holiday_block(2, cal, sdy, 0.5)] + general_spec(y, pad)
+
+
+def instance_case(seasons, glob):
+    """(T, make, data arguments) of test_impute_state_matches_restatement: two time blocks and three steps"""
+    T = 2 * kernel_instance(list_instance(np.arange(8.0), 8, seasons, glob))[2] + 3
+    return T, lambda y, T: list_instance(y, T, seasons, glob), dict(seasonal=(), missing=(5, T - 2), p=2)
+
+
+def chain_parameters(chains, seed, p=P):
     """every chain its own regression parameters"""
     rs = np.random.Generator(np.random.PCG64(seed))
-    gam = (rs.uniform(size=(chains, P)) < 0.6).astype(np.uint8)
+    gam = (rs.uniform(size=(chains, p)) < 0.6).astype(np.uint8)
     gam[:, 0] = 1
-    return gam, rs.standard_normal((chains, P)) * gam
+    return gam, rs.standard_normal((chains, p)) * gam
 
 
 # ---- the whole-rounds loop of the GPU test: list (a), T = 70

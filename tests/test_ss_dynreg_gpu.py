@@ -125,6 +125,12 @@ EDGE_CASES = {
     "GLOB, T=130": (130, sdc.list_glob, GLOB_DATA),
     "two blocks, T=70": (70, sdc.list_two, dict(seasonal=())),
     "two blocks, T=130": (130, sdc.list_two, dict(seasonal=())),
+    # the dynamic regression's instances no list above reaches (2 chains, p = 2)
+    "instance LDC 33, GLOB": sdc.instance_case(18, True),
+    "instance LDC 61": sdc.instance_case(34, False),
+    "instance LDC 61, GLOB": sdc.instance_case(34, True),
+    "instance LDC 65": sdc.instance_case(61, False),
+    "instance LDC 65, GLOB": sdc.instance_case(61, True),
 }
 
 
@@ -146,11 +152,11 @@ def check_state_models(eng, o, ch, tag):
 @pytest.mark.parametrize("name", list(EDGE_CASES))
 def test_impute_state_matches_restatement(oracle, name):
     T, make, kw = EDGE_CASES[name]
-    chains, seed, sigsq = 3, 41, 0.8
+    chains, seed, sigsq = (2 if name.startswith("instance") else 3), 41, 0.8
     X, y, obs = sdc.data(T, **kw)
     assert not obs.all()
     blocks = make(y, T)
-    gam, beta = sdc.chain_parameters(chains, 8)
+    gam, beta = sdc.chain_parameters(chains, 8, X.shape[1])
     eng = engine(chains, seed, y, X, obs, blocks, gam[0])
     for c in range(chains):
         eng.set_state(gam[c], beta[c], sigsq, chain=c)

@@ -89,6 +89,12 @@ EDGE_CASES = {
     "c (GLOB), T=70": (70, shc.list_c, dict(seasonal=(), trig=[(12.0, [1.0, 2.0])], missing=(31, 63))),
     "c (GLOB), T=130": (130, shc.list_c, dict(seasonal=(), trig=[(12.0, [1.0, 2.0])], missing=(31, 64, 128))),
     "d (never active), T=70": (70, shc.list_d, dict(seasonal=())),
+    # the calendar instances no list above reaches (2 chains, p = 2)
+    "instance LDC 33, GLOB": shc.instance_case(18, True),
+    "instance LDC 61": shc.instance_case(34, False),
+    "instance LDC 61, GLOB": shc.instance_case(34, True),
+    "instance LDC 65": shc.instance_case(61, False),
+    "instance LDC 65, GLOB": shc.instance_case(61, True),
 }
 
 
@@ -109,10 +115,10 @@ def check_state_models(eng, o, ch, tag):
 @pytest.mark.parametrize("name", list(EDGE_CASES))
 def test_impute_state_matches_restatement(oracle, name):
     T, make, kw = EDGE_CASES[name]
-    chains, seed, sigsq = 4, 41, 0.8
+    chains, seed, sigsq = (2 if name.startswith("instance") else 4), 41, 0.8
     X, y, obs = shc.data(T, **kw)
     blocks = make(y, T)
-    gam, beta = shc.chain_parameters(chains, 8)
+    gam, beta = shc.chain_parameters(chains, 8, X.shape[1])
     eng = engine(chains, seed, y, X, obs, blocks, gam[0])
     for c in range(chains):
         eng.set_state(gam[c], beta[c], sigsq, chain=c)

@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 import ss_student_oracle as sso
-from cases import bsts_priors, general_data, general_spec
+from cases import bsts_priors, general_data, general_spec, kernel_instance
 
 gpu = pytest.mark.gpu
 RTOL = 1e-8
@@ -71,16 +71,30 @@ def chain_parameters(p, chains, seed):
 
 
 # ---- 3. identities ---------------------------------------------------------------------------
+TRIG = ("trig", 12.0, [1.0])
+
+
 @gpu
 @pytest.mark.parametrize("desc,T,missing", [
     ([("trend",), ("seasonal", 4, 1)], 70, 0.05),     # a 64-step block boundary, a partial last block
     ([("level",), ("seasonal", 20, 1)], 40, 0.0),     # m = 20 > 16: blocks of 32 steps
+    # the H_t instances no list above reaches (T = None: two time blocks and three steps, 2 chains, p = 2):
+    # a seasonal that pads the state to the leading dimension, a one-frequency trig block for GLOB
+    ([("level",), ("seasonal", 4, 1), TRIG], None, 0.0),     # LDC 17, GLOB
+    ([("level",), ("seasonal", 18, 1), TRIG], None, 0.0),    # LDC 33, GLOB
+    ([("level",), ("seasonal", 34, 1)], None, 0.0),          # LDC 61
+    ([("level",), ("seasonal", 34, 1), TRIG], None, 0.0),    # LDC 61, GLOB
+    ([("level",), ("seasonal", 61, 1)], None, 0.0),          # LDC 65
+    ([("level",), ("seasonal", 61, 1), TRIG], None, 0.0),    # LDC 65, GLOB
 ])
 @pytest.mark.parametrize("weight", [1.0, 4.0])
 def test_constant_weights_equal_the_scalar_kernel(desc, T, missing, weight):
     """w = 1: the Gaussian engine's impute_state at the same sigma^2, bit for bit; w = 4: at
     sigma^2 / 4 (exact in binary)"""
     p, chains, seed, sigsq = 3, 4, 77, 0.5
+    if T is None:
+        p, chains = 2, 2
+        T = 2 * kernel_instance(general_spec(np.arange(8.0), desc))[2] + 3
     seas = [(b[1], b[2]) for b in desc if b[0] == "seasonal"]
     X, y, _, obs = general_data(T, p, 2, seas, seed=T, missing_frac=missing)
     blocks = general_spec(y, desc)

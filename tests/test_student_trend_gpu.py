@@ -21,7 +21,7 @@ import pytest
 import ss_student_oracle as sso
 import ss_student_trend_oracle as sto
 import student_trend_cases as stc
-from cases import bsts_priors, general_data
+from cases import bsts_priors, general_data, kernel_instance
 
 gpu = pytest.mark.gpu
 RTOL = 1e-8
@@ -55,18 +55,6 @@ def state_stream(oracle, seed, chain):
 
 
 # ---- identities ------------------------------------------------------------------------------------
-def steps_per_block(blocks):
-    """ssg_finish's rule (ssg_spec.h): the leading dimension of P and the steps per time block"""
-    m = sum(b["dim"] for b in blocks)
-    nerr = sum(b["dim"] if b["kind"] == 6 else (2 if b["kind"] in (2, 7, 8) else 1) for b in blocks)
-    nar = sum(b["kind"] in (4, 7) for b in blocks)
-    ld = 17 if m <= 16 else (33 if m <= 32 else (61 if m <= 60 else 65))
-    bl = 64
-    while bl > 8 and (2 * bl * m + m * ld + bl * (nerr + 1) + 64 + 8 + nar * 16 * 17) * 8 > 39 * 1024:
-        bl //= 2
-    return m, ld, bl
-
-
 ST = ("student_trend",)
 # (list, T or None = one step more than a time block, missing fraction, the expected leading dimension)
 IDENTITY_LISTS = [
@@ -99,7 +87,7 @@ def test_constant_weights_equal_the_scalar_kernel(desc, T, missing, ld):
     p, chains, seed, sigsq = 3, 4, 77, 0.5
     seas = [(b[1], b[2]) for b in desc if b[0] == "seasonal"]
     probe = stc.student_trend_spec(np.arange(8.0), desc)
-    m, ld_rule, bl = steps_per_block(probe)
+    m, ld_rule, bl, _ = kernel_instance(probe)
     assert ld_rule == ld
     if T is None:
         T = bl + 1
