@@ -193,6 +193,12 @@ SIGNATURES = {
     "ba_ss_add_dynamic_regression": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp]),
     "ba_ss_set_dynamic_predictors": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int64]),
     "ba_ss_get_dynamic_predictors": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_int64)]),
+    "ba_ss_add_regression_holiday": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_double, C.c_double, _dp,
+                                               C.POINTER(C.c_int32)]),
+    "ba_ss_set_regression_holiday_calendar": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int64]),
+    "ba_ss_get_regression_holiday_calendar": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "ba_ss_get_regression_holiday": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp, _dp]),
+    "ba_ss_set_regression_holiday": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp]),
     "ba_ss_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
     "ba_ss_prediction_errors": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp]),
     "ba_ss_student_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
@@ -863,12 +869,21 @@ class Engine:
         series' length and any forecast horizon; default: the series' length + 366);
         "dynamic_regression": predictors (rows x d, row t = x_t; rows past the series serve forecasts) and
         d entries each of df, sigma_guess, sigma_upper_limit, initial_sigma, a0, P0 -- it goes through
-        ba_ss_add_dynamic_regression, a numeric kind 12 to ba_ss_add_state_model, which refuses it), nseasons, duration, t0, lags, df, sigma_guess, sigma_upper_limit, initial_sigma
+        ba_ss_add_dynamic_regression, a numeric kind 12 to ba_ss_add_state_model, which refuses it;
+        "regression_holiday": widths (one per holiday), prior = (mean, sd) and, optionally, calendar --
+        ss_set_regression_holiday_calendar's flat indices -- and coefficients (the initial ones): no block of
+        the list, ss_add_regression_holiday numbers such models on their own), nseasons, duration, t0, lags, df, sigma_guess, sigma_upper_limit, initial_sigma
         (one entry per variance parameter; none for kind 5), initial_phi, rotations (kind 6: the
         (cos, sin) pairs of the transition matrix), a0, P0 (tests/cases.py: general_spec)"""
         self._check(self.lib.ba_ss_clear_state_models(self._h))
         self._blocks = []
+        self._rh_ncoef = []
         for b in blocks:
+            if b["kind"] == "regression_holiday":
+                model = self.ss_add_regression_holiday(b["widths"], b["prior"][0], b["prior"][1], b.get("coefficients"))
+                if b.get("calendar") is not None:
+                    self.ss_set_regression_holiday_calendar(model, b["calendar"])
+                continue
             if b["kind"] == "monthly":
                 n = int(b.get("calendar_length", self.T + 366))
                 b = dict(b, kind=11, nseasons=12, calendar=monthly_cycle_calendar(*b["first_date"], n))
@@ -1064,6 +1079,54 @@ class Engine:
         pos = np.ascontiguousarray(positions, dtype=np.int32)
         self._check(self.lib.ba_ss_set_holiday_calendar(self._h, block, pos.ctypes.data_as(C.POINTER(C.c_int32)),
                                                         pos.size))
+
+    def ss_add_regression_holiday(self, widths, prior_mean, prior_sd, coefficients=None):
+        """a regression holiday model on the list of state models (at least one state model first): one
+        coefficient per day of each holiday's window, all N(prior_mean, prior_sd^2); returns its index
+        among the list's regression holiday models"""
+        w = np.ascontiguousarray(widths, dtype=np.int32)
+        c = None if coefficients is None else np.ascontiguousarray(coefficients, dtype=np.float64)
+        if c is not None and c.size != int(w.sum()):
+            raise ValueError("coefficients: one per day of every holiday's window")
+        model = C.c_int32()
+        self._check(self.lib.ba_ss_add_regression_holiday(self._h, w.size, w.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                          float(prior_mean), float(prior_sd),
+                                                          None if c is None else _p(c), C.byref(model)))
+        if not hasattr(self, "_rh_ncoef"):
+            self._rh_ncoef = []
+        del self._rh_ncoef[model.value:]
+        self._rh_ncoef.append(int(w.sum()))
+        return model.value
+
+    def ss_set_regression_holiday_calendar(self, model, index):
+        """a regression holiday model's calendar: entry t is -1 (inactive) or the flat index offset_h + day
+        of the coefficient active at time t; at least T entries, those past T serve forecasts"""
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        self._check(self.lib.ba_ss_set_regression_holiday_calendar(self._h, model, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                                   idx.size))
+
+    def ss_get_regression_holiday_calendar(self, model):
+        n = C.c_int64()
+        self._check(self.lib.ba_ss_get_regression_holiday_calendar(self._h, model, None, C.byref(n)))
+        idx = np.zeros(max(n.value, 1), np.int32)
+        self._check(self.lib.ba_ss_get_regression_holiday_calendar(self._h, model, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                                   C.byref(n)))
+        return idx[:n.value]
+
+    def ss_get_regression_holiday(self, chain, model):
+        """one chain's coefficients of a regression holiday model, the totals of its last observe_state and
+        the counts (the same for every chain)"""
+        n = self._rh_ncoef[model] if 0 <= model < len(getattr(self, "_rh_ncoef", [])) else 1
+        coef, tot, cnt = np.zeros(n), np.zeros(n), np.zeros(n)
+        self._check(self.lib.ba_ss_get_regression_holiday(self._h, chain, model, _p(coef), _p(tot), _p(cnt)))
+        return dict(coefficients=coef, totals=tot, counts=cnt)
+
+    def ss_set_regression_holiday(self, chain, model, coefficients):
+        """the coefficients of one chain, or of every chain (chain = -1)"""
+        c = np.ascontiguousarray(coefficients, dtype=np.float64)
+        if not (0 <= model < len(getattr(self, "_rh_ncoef", []))) or c.size != self._rh_ncoef[model]:
+            raise ValueError("coefficients: one per day of every holiday's window of the model")
+        self._check(self.lib.ba_ss_set_regression_holiday(self._h, chain, model, _p(c)))
 
     def ss_set_dynamic_predictors(self, block, predictors):
         """a dynamic regression's predictors (state model `block`), rows x d: replaced, or extended with the

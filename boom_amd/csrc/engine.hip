@@ -1051,7 +1051,7 @@ const char *ba_kernel_class_name(int32_t cls) {
       "xtx_mfma_kernel+plane_sum_kernel+col_reduce_kernel", "poisson_impute_kernel",
       "kalman_prepare_kernel", "ss_round_kernel", "student_impute_kernel", "student_sigma_nu_kernel",
       "quantile_impute_kernel", "mlogit_impute_kernel", "student_ss_kernels", "poisson_ss_kernels", "logit_ss_kernels",
-      "student_trend_kernels", "ss_filter_kernel", "ar_spike_kernel"};
+      "student_trend_kernels", "ss_filter_kernel", "ar_spike_kernel", "reg_holiday_kernels"};
   return (cls >= 0 && cls < KT_CLASSES) ? names[cls] : "";
 }
 

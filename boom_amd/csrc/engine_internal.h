@@ -36,6 +36,7 @@
 #include "products.h"
 #include "quantile_params.h"
 #include "ss_filter_params.h"
+#include "ssg_regholiday.h"
 #include "ssg_spec.h"
 #include "ssvs_params.h"
 #include "student_params.h"
@@ -61,13 +62,18 @@ int launch_suf_from_xy(hipStream_t stream, int64_t n, int p, const double *X,
                        double *planes /* suf_row_slices(n, p) * p * p doubles, or null */);
 // kalman_kernel.hip
 hipError_t launch_ssm_simsmooth(hipStream_t stream, const SsParams &P, int draw_variances);
-hipError_t launch_ssm_forecast(hipStream_t stream, const SsParams &P, int horizon, const double *newX,
+hipError_t launch_ssm_forecast(hipStream_t stream, const SsParams &P, const RhParams &R, int horizon, const double *newX,
                                uint64_t *pos_forecast, double *out);
 // slt_kernel.hip: the Student local linear trend's sampler (before a state draw) and its observe_state (after it)
 hipError_t launch_slt_params(hipStream_t stream, const SsParams &P, const SltParams &U);
 hipError_t launch_slt_weights(hipStream_t stream, const SsParams &P, const SltParams &U);
 // ar_spike_kernel.hip: the ArSpikeSlabSampler of every spike-and-slab autoregression block (before a state draw)
 hipError_t launch_ar_spike(hipStream_t stream, const SsParams &P, const ArSpikeParams &U);
+// reg_holiday_kernel.hip: the regression holiday models' sampler and the chains' series (before a state draw;
+// draw = 0: the series alone), their observe_state (after it), and y_c = y for every chain
+hipError_t launch_rh_draw(hipStream_t stream, const SsParams &P, const RhParams &R, int draw);
+hipError_t launch_rh_observe(hipStream_t stream, const SsParams &P, const RhParams &R);
+hipError_t launch_rh_fill(hipStream_t stream, const RhParams &R, int T, int chains);
 // ss_family_forecast_kernel.hip: family = SS_FORECAST_*; scale = the horizon's exposures / rounded trial
 // counts (Poisson, logit), nu = every chain's degrees of freedom (Student-t); the other is not read
 hipError_t launch_ss_family_forecast(hipStream_t stream, const SsParams &P, int family, int horizon,
@@ -479,6 +485,20 @@ struct ba_engine {
   std::vector<double> dyn_predictors[SSG_MAX_BLOCKS];
   DevBuf<double> ddyn;
   int64_t dyn_rows = 0;
+  // RegressionHolidayStateModel (ssg_regholiday.h; reg_holiday_kernel.hip): the list's models -- no blocks
+  // of ssg: they belong to the list and are dropped with it --, what follows from their calendars and the
+  // observed flags on the device (rh_count entries of the table, 0: to be packed again), and per chain the
+  // coefficients, the totals of the last state draw (RH_MAX_COEF each), the sampler's stream position and
+  // the series less the models' effects (T)
+  std::vector<RhModel> rh_models;
+  std::vector<uint8_t> ss_observed;   // the data's observed flags, host side (the counts)
+  DevBuf<int32_t> drh_table, drh_steps;
+  DevBuf<double> drh_counts, drh_coef, drh_totals, drh_y;
+  DevBuf<uint64_t> drh_pos;
+  int64_t rh_count = 0;
+  int32_t rh_nsteps = 0;
+  int32_t rh_first[RH_MAX_MODELS + 1] = {};
+  std::vector<double> rh_counts;      // the counts per flat coefficient, host side (ba_ss_get_regression_holiday)
   // ba_ss_prediction_errors (ss_filter_kernel.hip): its outputs on the device (errors, forecast
   // variances, log likelihoods, the forecast-variance flag), the local-level path's one-block
   // list, and the stream the filter of a look-ahead's recorded draw runs on beside the batch
@@ -596,7 +616,7 @@ inline bool ss_lane_major(const ba_engine &e) { return !e.ssm_set && e.T <= LM_T
 inline size_t ss_pitch(const ba_engine &e) { return ss_lane_major(e) ? (size_t)LM_TP : (size_t)e.T; }
 // the rule book of the state models on this engine's list (ssg_refusal, ssg_spec.h): BA_OK, or the refusal
 inline int ss_refused(const ba_engine *e, DataKind kind, SsgUse use) {
-  const char *text = ssg_refusal(e->ssm_set ? &e->ssg : nullptr, ss_family(kind), use);
+  const char *text = ssg_refusal(e->ssm_set ? &e->ssg : nullptr, ss_family(kind), use, 0, e->ssm_set ? (int)e->rh_models.size() : 0);
   return text ? fail(BA_E_STATE, text) : BA_OK;
 }
 // engine_ss.hip
@@ -604,6 +624,7 @@ int64_t ssm_work_stride(const ba_engine &e);
 void fill_ss_params(ba_engine *e, SsParams &S);
 bool fill_ar_spike_params(ba_engine *e, ArSpikeParams &U);
 void fill_slt_params(ba_engine *e, SltParams &U);
+bool fill_rh_params(ba_engine *e, RhParams &R);
 int ss_prepare(ba_engine *e, DataKind kind = DATA_STATE_SPACE);
 int ss_sweep_impl(ba_engine *e, int32_t nsweeps, int rec_slot);
 int ss_escalate(ba_engine *e, std::vector<int32_t> &st);

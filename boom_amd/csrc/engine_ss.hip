@@ -95,7 +95,37 @@ void fill_ss_params(ba_engine *e, SsParams &S) {
       S.dyn_rows = e->dyn_rows;
       S.dyn_cols = ssg_dyn_columns(e->ssg);
     }
+    if (!e->rh_models.empty()) {
+      // regression holiday models: every chain's series less their effects (rh_draw_kernel writes it)
+      S.y = e->drh_y.ptr;
+      S.y_stride = e->T;
+      S.ssm.tpl_trend = S.ssm.tpl_nseasons = S.ssm.tpl_ar_lags = 0;   // (whatever ba_ss_set_tuning asked for)
+    }
   }
+}
+
+// the list's regression holiday models (false: it has none)
+bool fill_rh_params(ba_engine *e, RhParams &R) {
+  R = RhParams{};
+  if (!e->ssm_set || e->rh_models.empty()) return false;
+  R.nmodels = (int32_t)e->rh_models.size();
+  R.ncoef = e->rh_first[R.nmodels];
+  R.nsteps = e->rh_nsteps;
+  R.count = e->rh_count;
+  R.table = e->drh_table.ptr;
+  R.steps = e->drh_steps.ptr;
+  R.counts = e->drh_counts.ptr;
+  R.coef = e->drh_coef.ptr;
+  R.totals = e->drh_totals.ptr;
+  R.pos = e->drh_pos.ptr;
+  R.y = e->drh_y.ptr;
+  R.y_shared = e->dss_y.ptr;
+  for (int k = 0; k <= RH_MAX_MODELS; ++k) R.first[k] = e->rh_first[k];
+  for (int k = 0; k < R.nmodels; ++k) {
+    R.prior_mean[k] = e->rh_models[(size_t)k].prior_mean;
+    R.prior_sd[k] = e->rh_models[(size_t)k].prior_sd;
+  }
+  return true;
 }
 
 // the list's spike-and-slab autoregressions (false: it has none)
@@ -125,6 +155,7 @@ void fill_slt_params(ba_engine *e, SltParams &U) {
 
 // the state half of a state-space sweep: the structural kernel when a trend /
 // seasonal specification is set, the local-level kernel otherwise
+static hipError_t launch_state_models(ba_engine *e, const SsParams &S, int draw);
 static hipError_t launch_state_kernel(ba_engine *e, const SsParams &S, int draw) {
   ArSpikeParams V;
   if (draw && fill_ar_spike_params(e, V)) {
@@ -133,6 +164,18 @@ static hipError_t launch_state_kernel(ba_engine *e, const SsParams &S, int draw)
     hipError_t err = launch_ar_spike(e->stream, S, V);
     if (err != hipSuccess) return err;
   }
+  RhParams R;
+  if (fill_rh_params(e, R)) {
+    // the regression holiday models: their sampler and the chains' series ahead of the state kernel (the
+    // series every time: a setter may have changed the coefficients), their observe_state behind it
+    hipError_t err = launch_rh_draw(e->stream, S, R, draw);
+    if (err == hipSuccess) err = launch_state_models(e, S, draw);
+    if (err == hipSuccess) err = launch_rh_observe(e->stream, S, R);
+    return err;
+  }
+  return launch_state_models(e, S, draw);
+}
+static hipError_t launch_state_models(ba_engine *e, const SsParams &S, int draw) {
   if (e->ssm_set && e->ssg.student_block) {
     // a Student local linear trend: its sampler with the other state models' (they are drawn at the
     // head of the state kernel, every one from its own stream), and observe_state -- the new weights
@@ -310,6 +353,20 @@ int ss_prepare(ba_engine *e, DataKind kind) {
         HIP_TRY(hipMemsetAsync(e->dslt_count.ptr, 0, C * 8, s));
       }
     }
+    if (e->ssm_set && !e->rh_models.empty()) {
+      // new RegressionHolidayStateModels: the initial coefficients, empty totals (as the variance
+      // statistics before the first state draw), the sampler's stream at its start
+      HIP_TRY(e->drh_coef.resize(C * RH_MAX_COEF));
+      HIP_TRY(e->drh_totals.resize(C * RH_MAX_COEF));
+      HIP_TRY(e->drh_pos.resize(C));
+      std::vector<double> c0(C * RH_MAX_COEF, 0.0);
+      for (size_t c = 0; c < C; ++c)
+        for (size_t k = 0; k < e->rh_models.size(); ++k)
+          std::copy(e->rh_models[k].initial.begin(), e->rh_models[k].initial.end(), c0.begin() + c * RH_MAX_COEF + e->rh_first[k]);
+      HIP_TRY(hipMemcpy(e->drh_coef.ptr, c0.data(), c0.size() * 8, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemsetAsync(e->drh_totals.ptr, 0, C * RH_MAX_COEF * 8, s));
+      HIP_TRY(hipMemsetAsync(e->drh_pos.ptr, 0, C * 8, s));
+    }
     HIP_TRY(hipStreamSynchronize(s));  // (the host vectors above go out of scope)
     e->ss_initialized = false;
   }
@@ -333,6 +390,7 @@ int ba_ss_set_data(ba_engine *e, int32_t T, int32_t p, const double *y,
   std::vector<double> Xo((size_t)T * p), yo(T);
   std::vector<uint8_t> obs(T, 1);
   double nobs = 0;
+  e->rh_count = 0;   // (the regression holidays' counts and series follow the data)
   for (int t = 0; t < T; ++t) {
     if (observed) obs[t] = observed[t] ? 1 : 0;
     nobs += obs[t];
@@ -351,6 +409,7 @@ int ba_ss_set_data(ba_engine *e, int32_t T, int32_t p, const double *y,
   HIP_TRY(hipMemcpy(e->dss_y.ptr, y, (size_t)T * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->dss_X.ptr, X, (size_t)T * p * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->dss_obs.ptr, obs.data(), T, hipMemcpyHostToDevice));
+  e->ss_observed = obs;
   if (T <= LM_TP) {
     std::vector<double> Xt((size_t)LM_TP * p, 0.0), yt(LM_TP, 0.0);
     std::vector<uint32_t> mask(LM_THREADS, 0u);

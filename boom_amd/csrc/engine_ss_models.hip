@@ -39,8 +39,38 @@ static int dyn_prepare(ba_engine *e, int64_t extra) {
   return BA_OK;
 }
 
+// The regression holiday models' calendars the same way: every model's covers the series and `extra`
+// steps beyond it; the shared table, the active steps and the counts go to the device, and every chain's
+// series starts again from the data's, when a calendar or the data has changed.
+static int rh_prepare(ba_engine *e, int64_t extra) {
+  if (!e->ssm_set || e->rh_models.empty() || e->data_kind != DATA_STATE_SPACE) return BA_OK;
+  int code = BA_OK;
+  const std::string refused = rh_launch_refusal(e->rh_models, (int64_t)e->T, extra, &code);
+  if (!refused.empty()) return fail(code, refused);
+  const size_t C = (size_t)e->cfg.chains, T = (size_t)e->T;
+  if (e->rh_count != 0 && e->drh_y.count == C * T) return BA_OK;
+  const RhPacked K = rh_pack(e->rh_models, (int64_t)e->T, e->ss_observed.data());
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (nothing in flight reads the tables that are replaced)
+  HIP_TRY(e->drh_table.resize(K.table.size()));
+  HIP_TRY(e->drh_steps.resize(std::max<size_t>(K.steps.size(), 1)));
+  HIP_TRY(e->drh_counts.resize(K.counts.size()));
+  HIP_TRY(e->drh_y.resize(C * T));
+  HIP_TRY(hipMemcpy(e->drh_table.ptr, K.table.data(), K.table.size() * 4, hipMemcpyHostToDevice));
+  if (!K.steps.empty()) HIP_TRY(hipMemcpy(e->drh_steps.ptr, K.steps.data(), K.steps.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->drh_counts.ptr, K.counts.data(), K.counts.size() * 8, hipMemcpyHostToDevice));
+  e->rh_count = K.count;
+  e->rh_nsteps = (int32_t)K.steps.size();
+  for (int k = 0; k <= RH_MAX_MODELS; ++k) e->rh_first[k] = K.first[k];
+  e->rh_counts = K.counts;
+  RhParams R;
+  fill_rh_params(e, R);
+  HIP_TRY(launch_rh_fill(e->stream, R, (int)e->T, (int)e->cfg.chains));
+  return BA_OK;
+}
+
 int hol_prepare(ba_engine *e, int64_t extra) {
   if (int rc = dyn_prepare(e, extra)) return rc;
+  if (int rc = rh_prepare(e, extra)) return rc;
   if (!e->ssm_set || !ssg_has(e->ssg, SSG_HAS_CALENDAR)) return BA_OK;
   for (int b = 0; b < e->ssg.nblocks; ++b) {
     const bool seas = ssg_is_calendar(e->ssg.blk[b]);
@@ -105,6 +135,8 @@ static void ssg_clear(ba_engine *e) {
   for (int b = 0; b < SSG_MAX_BLOCKS; ++b) { e->hol_calendar[b].clear(); e->season_calendar[b].clear(); e->dyn_predictors[b].clear(); }
   e->hol_cal_count = 0;
   e->dyn_rows = 0;
+  e->rh_models.clear();   // (the regression holiday models belong to the list)
+  e->rh_count = 0;
   for (int i = 0; i < 3; ++i) e->ssg_template_var[i] = -1;
   e->ssg_template_ar = -1;
   e->ssm_set = false;
@@ -249,6 +281,102 @@ int ba_ss_get_dynamic_predictors(ba_engine *e, int32_t block, double *predictors
   const std::vector<double> &c = e->dyn_predictors[block];
   if (rows) *rows = (int64_t)c.size() / e->ssg.blk[block].dim;
   if (predictors && !c.empty()) std::memcpy(predictors, c.data(), c.size() * sizeof(double));
+  return BA_OK;
+}
+
+// RegressionHolidayStateModel (ssg_regholiday.h): nholidays holidays of the given widths, one coefficient
+// per day of each window, all under the prior N(prior_mean, prior_sd^2); no block of the list
+int ba_ss_add_regression_holiday(ba_engine *e, int32_t nholidays, const int32_t *widths, double prior_mean,
+                                 double prior_sd, const double *initial_coefficients, int32_t *model_out) {
+  if (!e) return fail(BA_E_INVALID, "null engine");
+  MUTATE(e);
+  if (const char *refused = rh_add_refusal(e->rh_models, e->ssm_set, nholidays, widths, prior_mean, prior_sd, initial_coefficients))
+    return fail(BA_E_INVALID, refused);
+  if (const char *refused = ssg_refusal(&e->ssg, ss_family(e->data_kind), SSG_USE_APPEND, SSG_REGRESSION_HOLIDAY))
+    return fail(BA_E_STATE, refused);
+  RhModel m;
+  m.widths.assign(widths, widths + nholidays);
+  m.prior_mean = prior_mean;
+  m.prior_sd = prior_sd;
+  m.initial.assign((size_t)m.ncoef(), 0.0);
+  if (initial_coefficients) m.initial.assign(initial_coefficients, initial_coefficients + m.ncoef());
+  e->rh_models.push_back(m);
+  for (size_t k = 0; k < e->rh_models.size(); ++k) e->rh_first[k + 1] = e->rh_first[k] + e->rh_models[k].ncoef();
+  for (size_t k = e->rh_models.size(); k < RH_MAX_MODELS; ++k) e->rh_first[k + 1] = e->rh_first[k];
+  e->rh_count = 0;
+  e->dss_scratch.release();   // (the chains start again, as after ba_ss_add_state_model)
+  if (model_out) *model_out = (int32_t)e->rh_models.size() - 1;
+  return BA_OK;
+}
+
+// a regression holiday model's calendar: entry t is -1 (no holiday of the model is active at time t) or
+// the flat index offset_h + day of the coefficient that is
+int ba_ss_set_regression_holiday_calendar(ba_engine *e, int32_t model, const int32_t *index, int64_t count) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!index || count <= 0) return fail(BA_E_INVALID, "bad argument");
+  if (!e->ssm_set || model < 0 || model >= (int32_t)e->rh_models.size()) return fail(BA_E_INVALID, "regression holiday model index out of range");
+  RhModel &m = e->rh_models[(size_t)model];
+  const int64_t bad = rh_calendar_check(index, count, m.ncoef());
+  if (bad >= 0) {
+    char buf[200];
+    std::snprintf(buf, sizeof buf, "regression holiday calendar entry %lld is %d: it must be -1 (inactive) or a coefficient index in [0, %d)",
+                  (long long)bad, (int)index[bad], (int)m.ncoef());
+    return fail(BA_E_INVALID, buf);
+  }
+  m.calendar.assign(index, index + count);
+  e->rh_count = 0;   // (packed again by the next call that launches)
+  return BA_OK;
+}
+
+// index == nullptr: the count alone
+int ba_ss_get_regression_holiday_calendar(ba_engine *e, int32_t model, int32_t *index, int64_t *count) {
+  if (!e) return fail(BA_E_INVALID, "null engine");
+  if (!e->ssm_set || model < 0 || model >= (int32_t)e->rh_models.size()) return fail(BA_E_INVALID, "regression holiday model index out of range");
+  const std::vector<int32_t> &c = e->rh_models[(size_t)model].calendar;
+  if (count) *count = (int64_t)c.size();
+  if (index && !c.empty()) std::memcpy(index, c.data(), c.size() * sizeof(int32_t));
+  return BA_OK;
+}
+
+static int rh_ready(ba_engine *e, int32_t model) {
+  if (e->data_kind != DATA_STATE_SPACE) return fail(BA_E_STATE, set_data_first(DATA_STATE_SPACE));
+  if (!e->ssm_set || e->rh_models.empty()) return fail(BA_E_STATE, "the list of state models holds no regression holiday model");
+  if (model < 0 || model >= (int32_t)e->rh_models.size()) return fail(BA_E_INVALID, "regression holiday model index out of range");
+  return ss_prepare(e);
+}
+
+// one chain's coefficients of model `model`, the totals its last observe_state left and the counts (the
+// same for every chain); any output may be nullptr
+int ba_ss_get_regression_holiday(ba_engine *e, int64_t chain, int32_t model, double *coefficients, double *totals,
+                                 double *counts) {
+  ENGINE_PROLOGUE(e);
+  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  int rc = rh_ready(e, model);
+  if (rc) return rc;
+  rc = ba_sync(e);
+  if (rc) return rc;
+  const size_t at = (size_t)chain * RH_MAX_COEF + (size_t)e->rh_first[model], n = (size_t)e->rh_models[(size_t)model].ncoef();
+  if (coefficients) HIP_TRY(hipMemcpy(coefficients, e->drh_coef.ptr + at, n * 8, hipMemcpyDeviceToHost));
+  if (totals) HIP_TRY(hipMemcpy(totals, e->drh_totals.ptr + at, n * 8, hipMemcpyDeviceToHost));
+  if (counts) std::memcpy(counts, e->rh_counts.data() + e->rh_first[model], n * 8);
+  return BA_OK;
+}
+
+// chain == -1: every chain
+int ba_ss_set_regression_holiday(ba_engine *e, int64_t chain, int32_t model, const double *coefficients) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (!coefficients) return fail(BA_E_INVALID, "null argument");
+  if (chain < -1 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  int rc = rh_ready(e, model);
+  if (rc) return rc;
+  const size_t n = (size_t)e->rh_models[(size_t)model].ncoef(), C = (size_t)e->cfg.chains;
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(coefficients[i])) return fail(BA_E_INVALID, "the coefficients must be finite");
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (size_t c = chain < 0 ? 0 : (size_t)chain; c < (chain < 0 ? C : (size_t)chain + 1); ++c)
+    HIP_TRY(hipMemcpy(e->drh_coef.ptr + c * RH_MAX_COEF + (size_t)e->rh_first[model], coefficients, n * 8, hipMemcpyHostToDevice));
   return BA_OK;
 }
 

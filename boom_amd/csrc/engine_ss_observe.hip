@@ -21,8 +21,11 @@ int ba_ss_forecast(ba_engine *e, int32_t horizon, const double *newX, double *ou
   HIP_TRY(hipMemcpyAsync(dnx.ptr, newX, h * p * 8, hipMemcpyHostToDevice, e->stream));
   SsParams S;
   fill_ss_params(e, S);
-  if (e->ssm_set)
-    HIP_TRY(launch_ssm_forecast(e->stream, S, horizon, dnx.ptr, e->dpos_forecast.ptr, dout.ptr));
+  if (e->ssm_set) {
+    RhParams R;
+    fill_rh_params(e, R);   // (a regression holiday: its coefficient active at T + i on top)
+    HIP_TRY(launch_ssm_forecast(e->stream, S, R, horizon, dnx.ptr, e->dpos_forecast.ptr, dout.ptr));
+  }
   else
     HIP_TRY(launch_ss_forecast(e->stream, S, horizon, dnx.ptr, e->dpos_forecast.ptr, dout.ptr));
   HIP_TRY(hipMemcpyAsync(out, dout.ptr, C * h * 8, hipMemcpyDeviceToHost, e->stream));
@@ -73,6 +76,17 @@ int ba_ss_prediction_errors(ba_engine *e, int64_t chain_first, int64_t chain_cou
   F.chain_count = (int32_t)chain_count;
   F.standardize = standardize ? 1 : 0;
   F.y = e->dss_y.ptr;
+  if (e->ssm_set && !e->rh_models.empty()) {
+    // regression holiday models: the chains' series less their effects, written from the coefficients as
+    // they are now (a look-ahead above 1 is refused with such a model: always live)
+    SsParams S;
+    fill_ss_params(e, S);
+    RhParams R;
+    fill_rh_params(e, R);
+    HIP_TRY(launch_rh_draw(s, S, R, 0));
+    F.y = e->drh_y.ptr;
+    F.y_stride = (int64_t)e->T;
+  }
   F.X = e->dss_X.ptr;
   F.observed = e->dss_obs.ptr;
   if (e->ssm_set) {

@@ -66,6 +66,14 @@ enum { AR_SPIKE_BAD_DRAW = 14 };
 // the Student trend's streams: its sampler's four draws (read in sequence) and the weights' slots
 enum : uint32_t { SLT_PARAM_STREAM = 160u, SLT_WEIGHT_STREAM = 161u };
 enum { SLT_WEIGHT_STRIDE = 256, SLT_BLOCK = 256 };
+// RegressionHolidayStateModel (bsts AddRegressionHoliday; ba_ss_add_regression_holiday): no block of the
+// list -- its state is the constant 1 with variance 0 -- but an offset on the observation series: a list
+// carries up to RH_MAX_MODELS such models of RH_MAX_COEF coefficients together (reg_holiday_kernel.hip).
+// ssg_refusal names the model by this number.  Its coefficient sampler reads a stream of its own.
+enum { SSG_REGRESSION_HOLIDAY = 13, RH_MAX_MODELS = 4, RH_MAX_COEF = 256 };
+enum : uint32_t { RH_COEF_STREAM = 162u };
+// rh_draw_kernel's own chain status: a coefficient draw that is not finite
+enum { RH_BAD_DRAW = 15 };
 // the observation families of ss_family_forecast_kernel.hip (launch_ss_family_forecast)
 enum { SS_FORECAST_STUDENT = 0, SS_FORECAST_POISSON = 1, SS_FORECAST_LOGIT = 2 };
 // a chain's ArModel sufficient statistics (per autoregression block): xtx (lags x lags at
@@ -207,8 +215,10 @@ struct SsParams {
   const double *h;
   int64_t h_stride;
   // the Poisson family (StateSpacePoissonModel): the filtered series is every chain's own latent
-  // value, y_stride doubles apart (0: the one series shared by all chains).  Read by the HT
-  // instances only.
+  // value, y_stride doubles apart (0: the one series shared by all chains).  A list with regression
+  // holiday models (RhParams) passes every chain's series less the models' effects the same way.  Read by
+  // every instance of the general kernel; the template kernel reads the shared series only
+  // (ssg_choose_kernel never picks it for a launch with a stride).
   int64_t y_stride;
   // the Student local linear trend (SsgSpec::student_block): every chain's weights, qw_stride doubles
   // apart -- the level's T, then the slope's T; entry t scales the state error of the step t -> t + 1
@@ -240,6 +250,25 @@ struct SltParams {
   uint64_t *count;    // chains: state draws observed so far (the s of the weights' slots)
   int32_t nu_kind[2]; // the nu priors: STUDENT_NU_UNIFORM (a, b) / STUDENT_NU_GAMMA (a, b)
   double nu_a[2], nu_b[2];
+};
+
+// The regression holiday models of a list (reg_holiday_kernel.hip).  Coefficient j of model k is flat
+// coefficient first[k] + j of the list (model order, then coefficient order).
+struct RhParams {
+  int32_t nmodels, ncoef;    // models of the list (0: none), their coefficients together
+  int32_t nsteps;            // the steps of [0, T) at which a model is active
+  int32_t pad;
+  int64_t count;             // entries of the table (>= T; a forecast reads entries T .. T + horizon - 1)
+  const int32_t *table;      // count x RH_MAX_MODELS: entry (t, k) = the flat coefficient of model k active at t, or -1
+  const int32_t *steps;      // nsteps, ascending
+  const double *counts;      // ncoef: the observed active steps of [0, T) per coefficient (every chain's)
+  double *coef;              // chains x RH_MAX_COEF
+  double *totals;            // chains x RH_MAX_COEF: the residual sums of the last state draw
+  uint64_t *pos;             // chains: position in RH_COEF_STREAM
+  double *y;                 // chains x T: the series less the models' effects (SsParams::y with y_stride = T)
+  const double *y_shared;    // T: the data's series
+  int32_t first[RH_MAX_MODELS + 1];
+  double prior_mean[RH_MAX_MODELS], prior_sd[RH_MAX_MODELS];
 };
 
 // The spike-and-slab autoregressions of a list (ar_spike_kernel.hip).  The prior of the block in

@@ -36,6 +36,7 @@ enum KernelClass {
   KT_SS_STUDENT_TREND, // slt_params_kernel / slt_weights_kernel (the Student local linear trend state model)
   KT_SS_FILTER,        // ss_filter_kernel (ba_ss_prediction_errors: the forward-only filter of the chains' current draw)
   KT_SS_AUTOAR,        // ar_spike_kernel (the spike-and-slab autoregression state model's sampler)
+  KT_SS_REGHOLIDAY,    // rh_draw_kernel / rh_observe_kernel (the regression holiday state model)
   KT_CLASSES
 };
 

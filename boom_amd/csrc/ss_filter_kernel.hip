@@ -105,7 +105,7 @@ __global__ __launch_bounds__(WAVE) void ss_filter_kernel(SsFilterParams P) {
     const uint8_t *gam = P.src.gamma + chain * P.src.gamma_stride;
     const double *bet = P.src.beta + chain * P.src.beta_stride;
     for (int t0 = 0; t0 < T; t0 += WAVE)
-      if (t0 + lane < T) err[t0 + lane] = P.y[t0 + lane];
+      if (t0 + lane < T) err[t0 + lane] = P.y[(size_t)chain * (size_t)P.y_stride + t0 + lane];
     for (int j0 = 0; j0 < p; j0 += WAVE) {
       const int jl = j0 + lane;
       const bool inc = jl < p && gam[jl] != 0;

@@ -40,6 +40,9 @@ struct SsFilterParams {
   // the dynamic regressions' predictors (SsParams::dyn), at least T rows of dyn_cols; nullptr: no such block
   const double *dyn;
   int32_t dyn_cols, dyn_pad;
+  // y is every chain's own series, y_stride doubles apart (SsParams::y_stride: a list with regression
+  // holiday models); 0: the one series shared by the chains
+  int64_t y_stride;
 };
 
 hipError_t launch_ss_filter(hipStream_t stream, const SsFilterParams &P);

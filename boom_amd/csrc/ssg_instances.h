@@ -22,10 +22,12 @@ struct SsgChoice {
 
 // The launch's kernel, from the tables the launch carries.  Invalid: two tables at once, or a table
 // shorter than the series (every step reads its calendar entry / its row of predictors; the kernel's
-// staging buffers are sized by ssm.ndyn columns).
+// staging buffers are sized by ssm.ndyn columns).  A series per chain (y_stride: the Poisson family's with
+// h, a list with regression holiday models without) is the general kernel's whatever the shape: the
+// template kernel reads the shared series.
 inline SsgChoice ssg_choose_kernel(const SsParams &P) {
   const SsgChoice invalid{SSG_CHOICE_INVALID, SSG_V_PLAIN};
-  if (P.ssm.tpl_trend > 0 && !P.h && !P.qw && !P.cal && !P.dyn) return {SSG_CHOICE_TEMPLATE, SSG_V_PLAIN};
+  if (P.ssm.tpl_trend > 0 && !P.h && !P.qw && !P.cal && !P.dyn && P.y_stride == 0) return {SSG_CHOICE_TEMPLATE, SSG_V_PLAIN};
   if (P.dyn) {
     if (P.h || P.qw || P.cal) return invalid;
     if (P.dyn_rows < P.T || P.dyn_cols < 1 || P.dyn_cols != P.ssm.ndyn) return invalid;

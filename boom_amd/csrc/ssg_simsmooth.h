@@ -113,8 +113,9 @@ __host__ __device__ inline int ssg_pass_lds_doubles(int m, int ld, int bl, int n
 // sigma^2.  A block's H_t sit one step per lane beside the observed flags; wave 1 reads them
 // into F_t, wave 0 into y+_t.  H_t > 0 always, so every step draws its observation normal.  The
 // last pass leaves Z_t'alpha_t (every step) where the HT = false instances leave the residuals.
-// The HT instances also read the series from P.y + chain * P.y_stride (the Poisson family's
-// latent values, one series per chain; the Student-t family passes stride 0).
+// Every instance reads the series from P.y + chain * P.y_stride: stride 0 is the one series shared by
+// the chains; the Poisson family (HT) passes its latent values, a list with regression holiday models the
+// series less their effects (reg_holiday_kernel.hip), one series per chain.
 // QT: the list holds a Student local linear trend (SsgSpec::student_block): its two state errors have
 // the per-step variances sigma^2 / w_t (P.qw, the chain's level weights then its slope weights).  A
 // time block's sigma^2 / w_t (and sigma / sqrt(w_t)) sit one step per lane beside the observed flags -- the
@@ -460,6 +461,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
   const int dH = HT ? 1 : (sqrtH != 0.0);
   const double *hser = HT ? P.h + (size_t)chain * P.h_stride : nullptr;
   const double *beta = P.beta + (size_t)chain * p;
+  const double *yser = P.y + (size_t)chain * P.y_stride;        // (the chain's own series, if it has one)
   double *w0 = P.scratch + (size_t)chain * P.scratch_stride;   // y* -> w = y* - y+ -> (v - v+) / F
   double *sres = w0 + T;                                       // F_t, then residuals (input of the X'e GEMM)
   double *wk = M.work + (size_t)chain * M.work_stride;
@@ -484,7 +486,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
         pred += P.X[(size_t)(base + l) * T + (t < T ? t : T - 1)] * bb;
       }
     }
-    if (t < T) w0[t] = (HT ? P.y[(size_t)chain * P.y_stride + t] : P.y[t]) - pred;   // (HT: the chain's own series, if it has one)
+    if (t < T) w0[t] = yser[t] - pred;
   }
 
   SSTAMP(1);
@@ -1139,7 +1141,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       const int nstep = (T - tb < BL) ? T - tb : BL;
       const bool in_l = lane < nstep;
       double *buf = (bi & 1) ? s_blk1 : s_blk0;
-      const double y_l = in_l ? P.y[tt] : 0.0;
+      const double y_l = in_l ? yser[tt] : 0.0;
       const int ob_l = (in_l && P.observed[tt]) ? 1 : 0;
       unsigned long long cw_l = SSG_CAL_NONE;   // (HD: entry t -- the component the step into t landed on, and Z_t)
       if (HD && in_l) cw_l = P.cal[tt];

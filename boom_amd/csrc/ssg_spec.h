@@ -137,14 +137,16 @@ enum SsgUse { SSG_USE_APPEND, SSG_USE_LAUNCH, SSG_USE_LOOKAHEAD, SSG_USE_FORECAS
 // The refusal (BA_E_STATE) of `use` under observation family `family`, or nullptr.  q: the list
 // (nullptr: none is set).  SSG_USE_APPEND: `kind` is about to be appended to q; SSG_USE_LOOKAHEAD:
 // a look-ahead above 1; SSG_USE_FORECAST: ba_ss_forecast, the Gaussian family's.  Where two
-// refusals apply, the first below is given.
-inline const char *ssg_refusal(const SsgSpec *q, SsFamily family, SsgUse use, int32_t kind = 0) {
-  static const char *const only_gaussian[5] = {
+// refusals apply, the first below is given.  regholidays: the regression holiday models the list carries
+// (ssg_regholiday.h: no blocks of q; SSG_USE_APPEND with kind SSG_REGRESSION_HOLIDAY: one is about to be added).
+inline const char *ssg_refusal(const SsgSpec *q, SsFamily family, SsgUse use, int32_t kind = 0, int regholidays = 0) {
+  static const char *const only_gaussian[6] = {
       "the Student local linear trend is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)",
       "the spike-and-slab autoregression is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)",
       "the random-walk holiday is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)",
       "the calendar seasonal is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)",
-      "the dynamic regression is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)"};
+      "the dynamic regression is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)",
+      "the regression holiday is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)"};
   static const char *const dynreg_student = "a list that holds both a dynamic regression and a Student local linear trend is not built";
   static const char *const dynreg_holiday = "a list that holds both a dynamic regression and a random-walk holiday is not built";
   static const char *const dynreg_calseas = "a list that holds both a dynamic regression and a calendar seasonal is not built";
@@ -172,13 +174,15 @@ inline const char *ssg_refusal(const SsgSpec *q, SsFamily family, SsgUse use, in
         if (has(SSG_HAS_HOLIDAY)) return dynreg_holiday;
         return has(SSG_HAS_CALENDAR_SEASONAL) ? dynreg_calseas : nullptr;
       }
+      if (kind == SSG_REGRESSION_HOLIDAY) return other ? only_gaussian[5] : nullptr;   // (beside every Gaussian block)
       return nullptr;
     case SSG_USE_LAUNCH:
       for (int i = 0; other && i < 5; ++i)
         if (has(special[i])) return only_gaussian[i];
-      return nullptr;
+      return other && regholidays > 0 ? only_gaussian[5] : nullptr;
     case SSG_USE_LOOKAHEAD:
-      return has(SSG_HAS_STUDENT_TREND) ? "the look-ahead does not carry a Student local linear trend's weights: use a look-ahead of 1" : nullptr;
+      if (has(SSG_HAS_STUDENT_TREND)) return "the look-ahead does not carry a Student local linear trend's weights: use a look-ahead of 1";
+      return regholidays > 0 ? "the look-ahead does not carry a regression holiday's coefficients: use a look-ahead of 1" : nullptr;
     case SSG_USE_FORECAST:
       if (family == SS_FAMILY_STUDENT) return "forecasts with Student-t observation noise are not implemented";
       if (family == SS_FAMILY_POISSON) return "forecasts with Poisson observation noise are not implemented";

@@ -14,8 +14,9 @@ namespace boom_amd {
 // reference (advance_to_timestamp, StateSpaceModelBase.cpp:455-459) forecast step i
 // uses the transition matrix and state errors of time T - 2 + i.  The state's step is
 // ssg_forecast_step (ssg_forecast_device.h), which the observation families' forecast kernel
-// (ss_family_forecast_kernel.hip) runs too.
-__global__ __launch_bounds__(64) void ssg_forecast_kernel(SsParams P, int horizon, const double *newX,
+// (ss_family_forecast_kernel.hip) runs too.  The list's regression holiday models (R.nmodels; none: 0) add
+// their coefficient active at time T + i to the forecast, model by model: (obs + pred) + effect.
+__global__ __launch_bounds__(64) void ssg_forecast_kernel(SsParams P, RhParams R, int horizon, const double *newX,
                                                           uint64_t *pos_forecast, double *out) {
   const int chain = (int)blockIdx.x + P.chain_first, lane = threadIdx.x;
   if ((int)blockIdx.x >= P.chain_count) return;
@@ -35,14 +36,19 @@ __global__ __launch_bounds__(64) void ssg_forecast_kernel(SsParams P, int horizo
     double part = 0.0;
     for (int j = lane; j < p; j += WAVE) part += newX[(size_t)j * horizon + i] * beta[j];
     const double pred = wsum<false>(part);
-    if (lane == 0) out[(size_t)chain * horizon + i] = obs + pred;
+    double fc = obs + pred;
+    for (int k = 0; k < R.nmodels; ++k) {
+      const int j = R.table[(size_t)(T + i) * RH_MAX_MODELS + k];
+      if (j >= 0) fc = fc + R.coef[(size_t)chain * RH_MAX_COEF + j];
+    }
+    if (lane == 0) out[(size_t)chain * horizon + i] = fc;
   }
   if (lane == 0) pos_forecast[chain] = rng.pos;
 }
 
-hipError_t launch_ssm_forecast(hipStream_t stream, const SsParams &P, int horizon, const double *newX,
+hipError_t launch_ssm_forecast(hipStream_t stream, const SsParams &P, const RhParams &R, int horizon, const double *newX,
                                uint64_t *pos_forecast, double *out) {
-  hipLaunchKernelGGL(ssg_forecast_kernel, dim3(P.chain_count), dim3(WAVE), 0, stream, P, horizon, newX,
+  hipLaunchKernelGGL(ssg_forecast_kernel, dim3(P.chain_count), dim3(WAVE), 0, stream, P, R, horizon, newX,
                      pos_forecast, out);
   return hipGetLastError();
 }

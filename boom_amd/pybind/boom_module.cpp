@@ -386,6 +386,26 @@ PYBIND11_MODULE(_boom, boom) {
       .def("set_prior", &RandomWalkHolidayStateModel::set_prior, py::arg("df"), py::arg("sigma_guess"),
            py::arg("sigma_upper_limit") = std::numeric_limits<double>::infinity());
 
+  py::class_<RegressionHolidayStateModel, Ptr<RegressionHolidayStateModel>>(
+      boom, "RegressionHolidayStateModel",
+      "RegressionHolidayStateModel(widths, prior_mean, prior_sd): one coefficient per day of each holiday's influence "
+      "window, shared across the years, all N(prior_mean, prior_sd^2).  BayesBoom's add_holiday takes a Holiday; this "
+      "module has no Date or Holiday classes, so the model takes the holidays' window widths and set_calendar what the "
+      "holidays amount to: index[t] = -1 where no holiday of the model is active at time t, else offset_h + the day's "
+      "position in holiday h's window (offset_h: the widths of the holidays before h).  Entries past the length of "
+      "the series serve forecasts.  The model is no block of the state: state_dimension, state() and "
+      "state_variances() of the model that holds it do not count it.")
+      .def(py::init([](const std::vector<int32_t> &widths, double prior_mean, double prior_sd) {
+             return new RegressionHolidayStateModel(widths, prior_mean, prior_sd);
+           }),
+           py::arg("widths"), py::arg("prior_mean"), py::arg("prior_sd"))
+      .def_property_readonly("number_of_coefficients", &RegressionHolidayStateModel::number_of_coefficients)
+      .def_property_readonly("widths", [](const RegressionHolidayStateModel &m) { return m.widths(); })
+      .def_property_readonly("calendar", [](const RegressionHolidayStateModel &m) { return m.calendar(); })
+      .def("set_calendar", &RegressionHolidayStateModel::set_calendar, py::arg("index"))
+      .def("set_coefficients", [](RegressionHolidayStateModel &m, const NpArray &v) { m.set_coefficients(vector_from(v)); },
+           py::arg("coefficients"), "the initial coefficients, one per day of every holiday's window (default: zeros)");
+
   py::class_<DynamicRegressionStateModel, Ptr<DynamicRegressionStateModel>>(
       boom, "DynamicRegressionStateModel",
       "DynamicRegressionStateModel(predictors): regression coefficients that follow independent random walks.  "
@@ -526,6 +546,11 @@ PYBIND11_MODULE(_boom, boom) {
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<StudentLocalLinearTrendStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<RandomWalkHolidayStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<DynamicRegressionStateModel> &s) { m.add_state(s); })
+      .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<RegressionHolidayStateModel> &s) { m.add_state(s); })
+      .def("regression_holiday_coefficients", [](const StateSpaceRegressionModel &m, int chain, int which) {
+             return to_numpy(m.regression_holiday_coefficients(chain, which));
+           }, py::arg("chain") = 0, py::arg("which") = 0,
+           "the coefficients of the which-th RegressionHolidayStateModel in one chain's draw")
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<MonthlyAnnualCycle> &s) { m.add_state(s); })
       .def("student_trend_nu", [](const StateSpaceRegressionModel &m, int chain) { return to_numpy(m.student_trend_nu(chain)); },
            py::arg("chain") = 0, "(nu_level, nu_slope) of the StudentLocalLinearTrendStateModel in one chain's draw")

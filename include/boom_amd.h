@@ -859,6 +859,50 @@ int ba_ss_add_dynamic_regression(ba_engine *e, int32_t xdim, const double *predi
 int ba_ss_set_dynamic_predictors(ba_engine *e, int32_t block, const double *predictors, int64_t rows);
 int ba_ss_get_dynamic_predictors(ba_engine *e, int32_t block, double *predictors, int64_t *rows);
 
+/* RegressionHolidayStateModel with its own sample_posterior (the scalar model's), bsts
+ * AddRegressionHoliday (StateModels/RegressionHolidayStateModel.cpp, create_state_model.cpp:952-986).
+ * A model holds nholidays holidays; holiday h has a window of widths[h] >= 1 days and one coefficient
+ * per day of it, shared across the years, all under the one prior N(prior_mean, prior_sd^2) (prior_sd
+ * positive and finite).  initial_coefficients: sum of the widths, holiday by holiday (NULL: zeros).
+ * *model_out (may be NULL) = the model's index among the list's regression holiday models.
+ * The model's state is the constant 1 with variance 0 and its Z_t is the coefficient active at t: on
+ * the device it is an offset on the observation series, not a block.  ba_ss_state_dimension,
+ * ba_ss_get_state_draw and ba_ss_get_state_model do not count it (the reference's state vector
+ * carries a trailing constant 1 per model; bsts's "state contribution" of the model at time t is
+ * coefficient[index(t)], which the caller forms from ba_ss_get_regression_holiday and the calendar).
+ * The models belong to the list of state models -- at least one state model has to be there first --
+ * and are dropped with it (ba_ss_clear_state_models, ba_ss_set_structural).  Limits: 4 models and 256
+ * coefficients per list.  Allowed beside every Gaussian state model.
+ * ba_ss_set_regression_holiday_calendar: entry t is -1 (no holiday of the model is active at time t)
+ * or the flat index offset_h + day in [0, sum of the widths) of the coefficient that is -- the caller
+ * flattens (holiday, day), as it turns dates into positions for kind 10; one entry per time, so one
+ * holiday of a model is active at a time by construction (two models may coincide).  count >= T is
+ * needed by a sweep, ba_ss_impute_state, ba_ss_draw_next and ba_ss_prediction_errors, count >= T +
+ * horizon by ba_ss_forecast, which adds the coefficient active at T + i: (obs + pred) + effect, model
+ * by model.  Each refuses with a text when the entries are too few.  The setter is a mutator like the
+ * others; the getter is shaped like ba_ss_get_holiday_calendar.
+ * A round (ba_ss_sweep) draws the observation model, then every coefficient in (model, coefficient)
+ * order -- precision = count / sigma^2 + 1 / prior_sd^2, mean = (total / sigma^2 + prior_mean /
+ * prior_sd^2) / precision, rnorm(mean, sqrt(1 / precision)) with the sigma^2 just drawn --, then the
+ * state, whose observe_state leaves total = the sum over the coefficient's observed steps of (y_t -
+ * x_t'beta) - Z_t'alpha_t + coefficient and count = those steps (the same for every chain; 0: the
+ * prior's draw).  Before the first state draw the totals are empty.
+ * ba_ss_get_regression_holiday: one chain's coefficients, totals and the counts of a model (sum of the
+ * widths each; any may be NULL).  ba_ss_set_regression_holiday: the coefficients of one chain, or of
+ * every chain (chain = -1); a mutator.
+ * RNG stream (a convention of this library; BOOM draws from the model's own generator): the chain's
+ * sampler id 162, one position per chain for all its models.
+ * Refused with a text, in either order of the calls: the Student-t / Poisson / logit observation
+ * families; a look-ahead above 1 (the record does not carry the coefficients).  Not built: the
+ * hierarchical model, the dynamic-intercept variant, ba_group_* forwarding. */
+int ba_ss_add_regression_holiday(ba_engine *e, int32_t nholidays, const int32_t *widths, double prior_mean,
+                                 double prior_sd, const double *initial_coefficients, int32_t *model_out);
+int ba_ss_set_regression_holiday_calendar(ba_engine *e, int32_t model, const int32_t *index, int64_t count);
+int ba_ss_get_regression_holiday_calendar(ba_engine *e, int32_t model, int32_t *index, int64_t *count);
+int ba_ss_get_regression_holiday(ba_engine *e, int64_t chain, int32_t model, double *coefficients, double *totals,
+                                 double *counts);
+int ba_ss_set_regression_holiday(ba_engine *e, int64_t chain, int32_t model, const double *coefficients);
+
 /* ---- bsts(family = "student"): StateSpaceStudentRegressionModel with
  * StateSpaceStudentPosteriorSampler (Models/StateSpace/StateSpaceStudentRegressionModel.cpp,
  * PosteriorSamplers/StateSpaceStudentPosteriorSampler.cpp:56-126) ----------------------------

@@ -529,6 +529,46 @@ class DynamicRegressionStateModel {
   Vector x_, a0_, P0_, sigma_, df_, guess_, upper_;
 };
 
+// RegressionHolidayStateModel with its own sample_posterior (StateModels/RegressionHolidayStateModel.cpp;
+// bsts AddRegressionHoliday): ba_ss_add_regression_holiday.  One coefficient per day of each holiday's
+// window, shared across the years, all under the prior N(prior_mean, prior_sd^2).  There is no Date /
+// Holiday layer here: where the reference's add_holiday takes a Holiday, this one takes the holidays'
+// window widths, and set_calendar the calendar they would reveal -- index[t] = -1 where no holiday of the
+// model is active at time t, else offset_h + days_into_influence_window (offset_h: the widths of the
+// holidays before h).  Entries past the series' length serve forecasts.  On the device the model is an
+// offset on the series, not a block of the state: state_dimension() of the model that holds it, its state
+// draw and state_variances() do not count it.
+class RegressionHolidayStateModel {
+ public:
+  RegressionHolidayStateModel(const std::vector<int32_t> &widths, double prior_mean, double prior_sd)
+      : widths_(widths), prior_mean_(prior_mean), prior_sd_(prior_sd) {
+    if (widths.empty()) report_error("a regression holiday model needs at least one holiday");
+    for (int32_t w : widths) {
+      if (w < 1) report_error("a holiday's width must be at least 1");
+      ncoef_ += w;
+    }
+    if (!(prior_sd > 0.0)) report_error("the prior standard deviation must be positive");
+    coef_ = Vector(ncoef_, 0.0);
+  }
+  int number_of_coefficients() const { return ncoef_; }
+  const std::vector<int32_t> &widths() const { return widths_; }
+  const std::vector<int32_t> &calendar() const { return calendar_; }
+  void set_calendar(const std::vector<int32_t> &index) {
+    for (int32_t k : index)
+      if (k < -1 || k >= ncoef_) report_error("a calendar entry must be -1 (inactive) or a coefficient index in [0, sum of the widths)");
+    calendar_ = index;
+  }
+  // the initial coefficients (default: zeros)
+  void set_coefficients(const Vector &c) {
+    if ((int)c.size() != ncoef_) report_error("a regression holiday model takes one coefficient per day of every holiday's window");
+    coef_ = c;
+  }
+  std::vector<int32_t> widths_, calendar_;
+  double prior_mean_, prior_sd_;
+  int ncoef_ = 0;
+  Vector coef_;
+};
+
 // ArStateModel(number_of_lags) with an ArPosteriorSampler (StateModels/ArStateModel.hpp:53,
 // TimeSeries/PosteriorSamplers/ArPosteriorSampler.hpp)
 class ArStateModel {
@@ -693,14 +733,17 @@ class StateSpaceRegressionModel : public Model {
   void add_state(const Ptr<RandomWalkHolidayStateModel> &s) { Entry e; e.kind = 10; e.holiday = s; models_.push_back(e); finalized_ = false; }
   void add_state(const Ptr<MonthlyAnnualCycle> &s) { Entry e; e.kind = 11; e.monthly = s; models_.push_back(e); finalized_ = false; }
   void add_state(const Ptr<DynamicRegressionStateModel> &s) { Entry e; e.kind = 12; e.dynreg = s; models_.push_back(e); finalized_ = false; }
+  // (no block of the state: the engine numbers the regression holiday models on their own)
+  void add_state(const Ptr<RegressionHolidayStateModel> &s) { reg_holidays_.push_back(s); finalized_ = false; }
   int number_of_state_models() const { return (int)models_.size(); }
   bool has_student_trend() const {
     for (const Entry &e : models_) if (e.kind == 8) return true;
     return false;
   }
+  bool has_regression_holiday() const { return !reg_holidays_.empty(); }
   // anything but a lone local level (which runs the local-level kernels; the Student-t family
-  // always sends the list)
-  bool structural() const { return list_always_ || !(models_.size() == 1 && models_[0].kind == 1); }
+  // always sends the list, and so does a model with a regression holiday)
+  bool structural() const { return list_always_ || !reg_holidays_.empty() || !(models_.size() == 1 && models_[0].kind == 1); }
   int state_dimension() const {
     int m = 0;
     for (const Entry &e : models_)
@@ -782,8 +825,24 @@ class StateSpaceRegressionModel : public Model {
           eng_->check(ba_ss_add_state_model(h, 4, ip, &s.df_, &s.guess_, &s.upper_, &s.sigma_, s.phi_.data(), s.a0_.data(), s.P0_.data()));
         }
       }
+      for (size_t k = 0; k < reg_holidays_.size(); ++k) {
+        const RegressionHolidayStateModel &s = *reg_holidays_[k];
+        int32_t model = -1;
+        eng_->check(ba_ss_set_lookahead(h, 1));   // (the engine refuses a look-ahead with this model)
+        eng_->check(ba_ss_add_regression_holiday(h, (int32_t)s.widths_.size(), s.widths_.data(), s.prior_mean_, s.prior_sd_,
+                                                 s.coef_.data(), &model));
+        if (!s.calendar_.empty())
+          eng_->check(ba_ss_set_regression_holiday_calendar(h, model, s.calendar_.data(), (int64_t)s.calendar_.size()));
+      }
     }
     finalized_ = true;
+  }
+  // the coefficients of the `which`-th RegressionHolidayStateModel in one chain's current draw
+  Vector regression_holiday_coefficients(int chain = 0, int which = 0) const {
+    if (which < 0 || which >= (int)reg_holidays_.size()) report_error("The model has no such RegressionHolidayStateModel.");
+    Vector v(reg_holidays_[which]->number_of_coefficients());
+    eng_->check(ba_ss_get_regression_holiday(eng_->get(), chain, which, v.data(), nullptr, nullptr));
+    return v;
   }
   // the coefficients and error variance of the `which`-th ArStateModel in one chain's current draw
   Vector ar_phi(int chain = 0, int which = 0) const {
@@ -956,6 +1015,7 @@ class StateSpaceRegressionModel : public Model {
   Ptr<Engine> eng_;
   int T_, p_;
   std::vector<Entry> models_;
+  std::vector<Ptr<RegressionHolidayStateModel>> reg_holidays_;
   bool finalized_ = false;
   bool list_always_ = false;
 };
@@ -976,8 +1036,9 @@ class StateSpacePosteriorSampler : public PosteriorSampler {
     model->engine()->check(ba_set_state(h, -1, g0.data(), nullptr, 1.0));
     // the callers' per-iteration loop at the device's rate (ba_ss_draw_next serves the
     // rounds from batches enqueued ahead; nothing a caller does can observe it)
-    // (a StudentLocalLinearTrendStateModel's weights are not in the look-ahead's snapshots: one round per draw)
-    model->engine()->check(ba_ss_set_lookahead(h, model->has_student_trend() ? 1 : 64));
+    // (a StudentLocalLinearTrendStateModel's weights and a RegressionHolidayStateModel's coefficients are not
+    // in the look-ahead's snapshots: one round per draw)
+    model->engine()->check(ba_ss_set_lookahead(h, (model->has_student_trend() || model->has_regression_holiday()) ? 1 : 64));
   }
   void set_lookahead(int rounds) { model_->engine()->check(ba_ss_set_lookahead(model_->engine()->get(), rounds)); }
   void draw() override {                     // StateSpacePosteriorSampler.cpp:42-64
