@@ -199,6 +199,10 @@ SIGNATURES = {
     "ba_ss_get_regression_holiday_calendar": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "ba_ss_get_regression_holiday": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp, _dp]),
     "ba_ss_set_regression_holiday": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp]),
+    "ba_ss_add_hierarchical_regression_holiday": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_double, _dp,
+                                                            C.POINTER(C.c_int32)]),
+    "ba_ss_get_hierarchical_regression_holiday": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp]),
+    "ba_ss_set_hierarchical_regression_holiday": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp]),
     "ba_ss_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
     "ba_ss_prediction_errors": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp]),
     "ba_ss_student_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
@@ -872,15 +876,25 @@ class Engine:
         ba_ss_add_dynamic_regression, a numeric kind 12 to ba_ss_add_state_model, which refuses it;
         "regression_holiday": widths (one per holiday), prior = (mean, sd) and, optionally, calendar --
         ss_set_regression_holiday_calendar's flat indices -- and coefficients (the initial ones): no block of
-        the list, ss_add_regression_holiday numbers such models on their own), nseasons, duration, t0, lags, df, sigma_guess, sigma_upper_limit, initial_sigma
+        the list, ss_add_regression_holiday numbers such models on their own;
+        "hierarchical_regression_holiday": nholidays, width, mean_prior = (mean, variance), variance_prior =
+        (variance_guess, variance_guess_weight) and, optionally, calendar and coefficients as the plain model's --
+        one of the list's regression holiday models, through ss_add_hierarchical_regression_holiday), nseasons, duration, t0, lags, df, sigma_guess, sigma_upper_limit, initial_sigma
         (one entry per variance parameter; none for kind 5), initial_phi, rotations (kind 6: the
         (cos, sin) pairs of the transition matrix), a0, P0 (tests/cases.py: general_spec)"""
         self._check(self.lib.ba_ss_clear_state_models(self._h))
         self._blocks = []
         self._rh_ncoef = []
+        self._rhh_width = {}
         for b in blocks:
             if b["kind"] == "regression_holiday":
                 model = self.ss_add_regression_holiday(b["widths"], b["prior"][0], b["prior"][1], b.get("coefficients"))
+                if b.get("calendar") is not None:
+                    self.ss_set_regression_holiday_calendar(model, b["calendar"])
+                continue
+            if b["kind"] == "hierarchical_regression_holiday":
+                model = self.ss_add_hierarchical_regression_holiday(b["nholidays"], b["width"], b["mean_prior"][0], b["mean_prior"][1],
+                                                                    b["variance_prior"][0], b["variance_prior"][1], b.get("coefficients"))
                 if b.get("calendar") is not None:
                     self.ss_set_regression_holiday_calendar(model, b["calendar"])
                 continue
@@ -1097,6 +1111,50 @@ class Engine:
         del self._rh_ncoef[model.value:]
         self._rh_ncoef.append(int(w.sum()))
         return model.value
+
+    def ss_add_hierarchical_regression_holiday(self, nholidays, width, mean_prior_mean, mean_prior_variance, variance_guess,
+                                               variance_guess_weight, coefficients=None):
+        """a hierarchical regression holiday model on the list of state models: nholidays holidays of one width d,
+        their coefficient vectors N(mu, Omega^-1) with mu ~ N(mean_prior_mean, mean_prior_variance) and
+        Omega ~ Wishart(variance_guess_weight, variance_guess_weight x variance_guess); returns its index among the
+        list's regression holiday models (the calendar and the coefficients go through the plain model's calls)"""
+        d = int(width)
+        m0 = np.ascontiguousarray(mean_prior_mean, dtype=np.float64).reshape(-1)
+        v0 = np.ascontiguousarray(mean_prior_variance, dtype=np.float64).reshape(-1)
+        g = np.ascontiguousarray(variance_guess, dtype=np.float64).reshape(-1)
+        if d >= 1 and (m0.size != d or v0.size != d * d or g.size != d * d):
+            raise ValueError("mean_prior_mean: width entries; mean_prior_variance, variance_guess: width x width")
+        c = None if coefficients is None else np.ascontiguousarray(coefficients, dtype=np.float64).reshape(-1)
+        if c is not None and c.size != int(nholidays) * d:
+            raise ValueError("coefficients: one per day of every holiday's window")
+        model = C.c_int32()
+        self._check(self.lib.ba_ss_add_hierarchical_regression_holiday(self._h, int(nholidays), d, _p(m0), _p(v0), _p(g),
+                                                                       float(variance_guess_weight),
+                                                                       None if c is None else _p(c), C.byref(model)))
+        if not hasattr(self, "_rh_ncoef"):
+            self._rh_ncoef = []
+        del self._rh_ncoef[model.value:]
+        self._rh_ncoef.append(int(nholidays) * d)
+        if not hasattr(self, "_rhh_width"):
+            self._rhh_width = {}
+        self._rhh_width[model.value] = d
+        return model.value
+
+    def ss_get_hierarchical_regression_holiday(self, chain, model):
+        """one chain's hyper-mean and hyper-precision of a hierarchical regression holiday model"""
+        d = getattr(self, "_rhh_width", {}).get(model, 1)
+        mean, prec = np.zeros(d), np.zeros((d, d))
+        self._check(self.lib.ba_ss_get_hierarchical_regression_holiday(self._h, chain, model, _p(mean), _p(prec)))
+        return dict(mean=mean, precision=prec)
+
+    def ss_set_hierarchical_regression_holiday(self, chain, model, mean, precision):
+        """the hyper-mean and hyper-precision of one chain, or of every chain (chain = -1)"""
+        d = getattr(self, "_rhh_width", {}).get(model, 1)
+        m = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
+        q = np.ascontiguousarray(precision, dtype=np.float64).reshape(-1)
+        if m.size != d or q.size != d * d:
+            raise ValueError("mean: width entries; precision: width x width")
+        self._check(self.lib.ba_ss_set_hierarchical_regression_holiday(self._h, chain, model, _p(m), _p(q)))
 
     def ss_set_regression_holiday_calendar(self, model, index):
         """a regression holiday model's calendar: entry t is -1 (inactive) or the flat index offset_h + day

@@ -54,6 +54,8 @@ const char *status_message(int st) {
       return "Weights must be finite and non-negative.";
     case AR_SPIKE_BAD_DRAW:
       return "A coefficient or variance draw of the spike-and-slab autoregression sampler came out non-finite.";
+    case RHH_BAD_DRAW:
+      return "A draw of the hierarchical regression holiday sampler met a matrix that is not positive definite or came out non-finite.";
     default:
       return "unknown chain status";
   }
@@ -73,6 +75,7 @@ int status_code(int st) {
     case MLVS_ILLEGAL_START: return BA_E_ILLEGAL_START;
     case STUDENT_BAD_WEIGHT: return BA_E_INVALID;
     case AR_SPIKE_BAD_DRAW: return BA_E_INVALID;
+    case RHH_BAD_DRAW: return BA_E_NOT_PD;
     default: return BA_E_INVALID;
   }
 }

@@ -71,7 +71,8 @@ hipError_t launch_slt_weights(hipStream_t stream, const SsParams &P, const SltPa
 hipError_t launch_ar_spike(hipStream_t stream, const SsParams &P, const ArSpikeParams &U);
 // reg_holiday_kernel.hip: the regression holiday models' sampler and the chains' series (before a state draw;
 // draw = 0: the series alone), their observe_state (after it), and y_c = y for every chain
-hipError_t launch_rh_draw(hipStream_t stream, const SsParams &P, const RhParams &R, int draw);
+hipError_t launch_rh_draw(hipStream_t stream, const SsParams &P, const RhParams &R, int draw, int hier = 0);
+hipError_t launch_rhh_draw(hipStream_t stream, const SsParams &P, const RhParams &R, const RhhParams &Q);
 hipError_t launch_rh_observe(hipStream_t stream, const SsParams &P, const RhParams &R);
 hipError_t launch_rh_fill(hipStream_t stream, const RhParams &R, int T, int chains);
 // ss_family_forecast_kernel.hip: family = SS_FORECAST_*; scale = the horizon's exposures / rounded trial
@@ -495,6 +496,10 @@ struct ba_engine {
   DevBuf<int32_t> drh_table, drh_steps;
   DevBuf<double> drh_counts, drh_coef, drh_totals, drh_y;
   DevBuf<uint64_t> drh_pos;
+  // the hierarchical ones among them: the hyperparameters (RH_MAX_MODELS x RHH_HYPER_STRIDE), and per
+  // chain and model the hyper-mean and hyper-precision, per chain the position in RHH_STREAM
+  DevBuf<double> drhh_hyper, drhh_mu, drhh_omega;
+  DevBuf<uint64_t> drhh_pos;
   int64_t rh_count = 0;
   int32_t rh_nsteps = 0;
   int32_t rh_first[RH_MAX_MODELS + 1] = {};
@@ -625,6 +630,7 @@ void fill_ss_params(ba_engine *e, SsParams &S);
 bool fill_ar_spike_params(ba_engine *e, ArSpikeParams &U);
 void fill_slt_params(ba_engine *e, SltParams &U);
 bool fill_rh_params(ba_engine *e, RhParams &R);
+bool fill_rhh_params(ba_engine *e, RhhParams &Q);   // (false: no hierarchical model)
 int ss_prepare(ba_engine *e, DataKind kind = DATA_STATE_SPACE);
 int ss_sweep_impl(ba_engine *e, int32_t nsweeps, int rec_slot);
 int ss_escalate(ba_engine *e, std::vector<int32_t> &st);

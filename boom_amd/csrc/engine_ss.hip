@@ -128,6 +128,26 @@ bool fill_rh_params(ba_engine *e, RhParams &R) {
   return true;
 }
 
+// the hierarchical ones among the list's regression holiday models (false: it has none)
+bool fill_rhh_params(ba_engine *e, RhhParams &Q) {
+  Q = RhhParams{};
+  if (!e->ssm_set) return false;
+  Q.nmodels = (int32_t)e->rh_models.size();
+  for (int k = 0; k < Q.nmodels; ++k) {
+    const RhModel &m = e->rh_models[(size_t)k];
+    if (!m.hier) continue;
+    Q.mask |= 1 << k;
+    Q.width[k] = m.width;
+    Q.nhol[k] = (int32_t)m.widths.size();
+    Q.nu0[k] = m.nu0;
+  }
+  Q.hyper = e->drhh_hyper.ptr;
+  Q.mu = e->drhh_mu.ptr;
+  Q.omega = e->drhh_omega.ptr;
+  Q.pos = e->drhh_pos.ptr;
+  return Q.mask != 0;
+}
+
 // the list's spike-and-slab autoregressions (false: it has none)
 bool fill_ar_spike_params(ba_engine *e, ArSpikeParams &U) {
   U = ArSpikeParams{};
@@ -168,7 +188,12 @@ static hipError_t launch_state_kernel(ba_engine *e, const SsParams &S, int draw)
   if (fill_rh_params(e, R)) {
     // the regression holiday models: their sampler and the chains' series ahead of the state kernel (the
     // series every time: a setter may have changed the coefficients), their observe_state behind it
-    hipError_t err = launch_rh_draw(e->stream, S, R, draw);
+    // (a hierarchical model's sampler first: the plain kernel takes its coefficients as they then are and
+    // writes the series from all models', in model order)
+    RhhParams Q;
+    const bool hier = fill_rhh_params(e, Q);
+    hipError_t err = (draw && hier) ? launch_rhh_draw(e->stream, S, R, Q) : hipSuccess;
+    if (err == hipSuccess) err = launch_rh_draw(e->stream, S, R, draw, Q.mask);
     if (err == hipSuccess) err = launch_state_models(e, S, draw);
     if (err == hipSuccess) err = launch_rh_observe(e->stream, S, R);
     return err;
@@ -366,6 +391,35 @@ int ss_prepare(ba_engine *e, DataKind kind) {
       HIP_TRY(hipMemcpy(e->drh_coef.ptr, c0.data(), c0.size() * 8, hipMemcpyHostToDevice));
       HIP_TRY(hipMemsetAsync(e->drh_totals.ptr, 0, C * RH_MAX_COEF * 8, s));
       HIP_TRY(hipMemsetAsync(e->drh_pos.ptr, 0, C * 8, s));
+      // ... and the hierarchical ones' hyperparameters, mu and Omega as the models were added with
+      const size_t W = RHH_MAX_WIDTH, MU = RH_MAX_MODELS * W, OM = RH_MAX_MODELS * W * W;
+      HIP_TRY(e->drhh_hyper.resize(RH_MAX_MODELS * RHH_HYPER_STRIDE));
+      HIP_TRY(e->drhh_mu.resize(C * MU));
+      HIP_TRY(e->drhh_omega.resize(C * OM));
+      HIP_TRY(e->drhh_pos.resize(C));
+      std::vector<double> hy(RH_MAX_MODELS * RHH_HYPER_STRIDE, 0.0), mu0(C * MU, 0.0), om0(C * OM, 0.0);
+      for (size_t k = 0; k < e->rh_models.size(); ++k) {
+        const RhModel &m = e->rh_models[k];
+        if (!m.hier) continue;
+        const size_t d = (size_t)m.width;
+        double *h = hy.data() + k * RHH_HYPER_STRIDE;
+        for (size_t r = 0; r < d; ++r) {
+          h[RHH_HYPER_SINV0MU0 + r] = m.sinv0mu0[r];
+          for (size_t c2 = 0; c2 < d; ++c2) {
+            h[RHH_HYPER_SINV0 + r * W + c2] = m.sinv0[r * d + c2];
+            h[RHH_HYPER_S0 + r * W + c2] = m.s0[r * d + c2];
+          }
+        }
+        for (size_t c = 0; c < C; ++c)
+          for (size_t r = 0; r < d; ++r) {
+            mu0[c * MU + k * W + r] = m.initial_mu[r];
+            for (size_t c2 = 0; c2 < d; ++c2) om0[c * OM + k * W * W + r * W + c2] = m.initial_omega[r * d + c2];
+          }
+      }
+      HIP_TRY(hipMemcpy(e->drhh_hyper.ptr, hy.data(), hy.size() * 8, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(e->drhh_mu.ptr, mu0.data(), mu0.size() * 8, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(e->drhh_omega.ptr, om0.data(), om0.size() * 8, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemsetAsync(e->drhh_pos.ptr, 0, C * 8, s));
     }
     HIP_TRY(hipStreamSynchronize(s));  // (the host vectors above go out of scope)
     e->ss_initialized = false;

@@ -380,6 +380,73 @@ int ba_ss_set_regression_holiday(ba_engine *e, int64_t chain, int32_t model, con
   return BA_OK;
 }
 
+// HierarchicalRegressionHolidayStateModel (ssg_regholiday.h: rhh_add_refusal): nholidays holidays of one
+// width under beta_h ~ N(mu, Omega^-1) with mu and Omega drawn; one of the list's regression holiday models
+int ba_ss_add_hierarchical_regression_holiday(ba_engine *e, int32_t nholidays, int32_t width,
+                                              const double *mean_prior_mean, const double *mean_prior_variance,
+                                              const double *variance_guess, double variance_guess_weight,
+                                              const double *initial_coefficients, int32_t *model_out) {
+  if (!e) return fail(BA_E_INVALID, "null engine");
+  MUTATE(e);
+  if (const char *refused = rhh_add_refusal(e->rh_models, e->ssm_set, nholidays, width, mean_prior_mean, mean_prior_variance,
+                                            variance_guess, variance_guess_weight, initial_coefficients))
+    return fail(BA_E_INVALID, refused);
+  if (const char *refused = ssg_refusal(&e->ssg, ss_family(e->data_kind), SSG_USE_APPEND, SSG_REGRESSION_HOLIDAY))
+    return fail(BA_E_STATE, refused);
+  e->rh_models.push_back(rhh_model(nholidays, width, mean_prior_mean, mean_prior_variance, variance_guess,
+                                   variance_guess_weight, initial_coefficients));
+  for (size_t k = 0; k < e->rh_models.size(); ++k) e->rh_first[k + 1] = e->rh_first[k] + e->rh_models[k].ncoef();
+  for (size_t k = e->rh_models.size(); k < RH_MAX_MODELS; ++k) e->rh_first[k + 1] = e->rh_first[k];
+  e->rh_count = 0;
+  e->dss_scratch.release();   // (the chains start again, as after ba_ss_add_state_model)
+  if (model_out) *model_out = (int32_t)e->rh_models.size() - 1;
+  return BA_OK;
+}
+
+// one chain's hyper-mean (d) and hyper-precision (d x d, row-major) of model `model`; either may be nullptr
+int ba_ss_get_hierarchical_regression_holiday(ba_engine *e, int64_t chain, int32_t model, double *mean, double *precision) {
+  ENGINE_PROLOGUE(e);
+  if (chain < 0 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  int rc = rh_ready(e, model);
+  if (rc) return rc;
+  const RhModel &m = e->rh_models[(size_t)model];
+  if (!m.hier) return fail(BA_E_INVALID, "not a hierarchical regression holiday model");
+  rc = ba_sync(e);
+  if (rc) return rc;
+  const size_t W = RHH_MAX_WIDTH, d = (size_t)m.width, at = (size_t)chain * RH_MAX_MODELS + (size_t)model;
+  if (mean) HIP_TRY(hipMemcpy(mean, e->drhh_mu.ptr + at * W, d * 8, hipMemcpyDeviceToHost));
+  if (precision) {
+    std::vector<double> om(W * W);
+    HIP_TRY(hipMemcpy(om.data(), e->drhh_omega.ptr + at * W * W, W * W * 8, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < d; ++r)
+      for (size_t c = 0; c < d; ++c) precision[r * d + c] = om[r * W + c];
+  }
+  return BA_OK;
+}
+
+// chain == -1: every chain
+int ba_ss_set_hierarchical_regression_holiday(ba_engine *e, int64_t chain, int32_t model, const double *mean,
+                                              const double *precision) {
+  ENGINE_PROLOGUE(e);
+  MUTATE(e);
+  if (chain < -1 || chain >= e->cfg.chains) return fail(BA_E_INVALID, "chain index out of range");
+  int rc = rh_ready(e, model);
+  if (rc) return rc;
+  const RhModel &m = e->rh_models[(size_t)model];
+  if (const char *refused = rhh_set_refusal(m, mean, precision)) return fail(BA_E_INVALID, refused);
+  const size_t W = RHH_MAX_WIDTH, d = (size_t)m.width, C = (size_t)e->cfg.chains;
+  std::vector<double> om(W * W, 0.0);
+  for (size_t r = 0; r < d; ++r)
+    for (size_t c = 0; c < d; ++c) om[r * W + c] = precision[r * d + c];
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (size_t c = chain < 0 ? 0 : (size_t)chain; c < (chain < 0 ? C : (size_t)chain + 1); ++c) {
+    const size_t at = c * RH_MAX_MODELS + (size_t)model;
+    HIP_TRY(hipMemcpy(e->drhh_mu.ptr + at * W, mean, d * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->drhh_omega.ptr + at * W * W, om.data(), W * W * 8, hipMemcpyHostToDevice));
+  }
+  return BA_OK;
+}
+
 // MonthlyAnnualCycle's calendar from the date of the first observation (proleptic Gregorian): out[t] = 1
 // where the day `t` days after (year, month, day) is the first of a month
 int ba_monthly_cycle_calendar(int32_t year, int32_t month, int32_t day, int64_t count, uint8_t *out) {

@@ -74,6 +74,19 @@ enum { SSG_REGRESSION_HOLIDAY = 13, RH_MAX_MODELS = 4, RH_MAX_COEF = 256 };
 enum : uint32_t { RH_COEF_STREAM = 162u };
 // rh_draw_kernel's own chain status: a coefficient draw that is not finite
 enum { RH_BAD_DRAW = 15 };
+// HierarchicalRegressionHolidayStateModel (bsts AddHierarchicalRegressionHoliday;
+// ba_ss_add_hierarchical_regression_holiday): a regression holiday model whose holidays share one window
+// width d <= RHH_MAX_WIDTH and whose coefficient vectors share the prior N(mu, Omega^-1), mu and Omega drawn
+// too (hier_holiday_kernel.hip).  One of the list's RH_MAX_MODELS models; all of a chain's hierarchical
+// models read one position of the sampler id RHH_STREAM.  RHH_BAD_DRAW: a factor that is not positive
+// definite or a number that is not finite in rhh_draw_kernel.
+enum { RHH_MAX_WIDTH = 16 };
+enum : uint32_t { RHH_STREAM = 163u };
+enum { RHH_BAD_DRAW = 16 };
+// a model's hyperparameters on the device, d x d matrices row-major at leading dimension RHH_MAX_WIDTH:
+// Sigma0^-1 | S0 = nu0 x variance_guess | Sigma0^-1 mu0
+enum { RHH_HYPER_SINV0 = 0, RHH_HYPER_S0 = RHH_MAX_WIDTH * RHH_MAX_WIDTH, RHH_HYPER_SINV0MU0 = 2 * RHH_MAX_WIDTH * RHH_MAX_WIDTH,
+       RHH_HYPER_STRIDE = RHH_HYPER_SINV0MU0 + RHH_MAX_WIDTH };
 // the observation families of ss_family_forecast_kernel.hip (launch_ss_family_forecast)
 enum { SS_FORECAST_STUDENT = 0, SS_FORECAST_POISSON = 1, SS_FORECAST_LOGIT = 2 };
 // a chain's ArModel sufficient statistics (per autoregression block): xtx (lags x lags at
@@ -269,6 +282,19 @@ struct RhParams {
   const double *y_shared;    // T: the data's series
   int32_t first[RH_MAX_MODELS + 1];
   double prior_mean[RH_MAX_MODELS], prior_sd[RH_MAX_MODELS];
+};
+
+// The hierarchical ones among them (hier_holiday_kernel.hip): model k is hierarchical where width[k] > 0,
+// with nhol[k] holidays of that width; its coefficients, counts and totals are RhParams's.
+struct RhhParams {
+  int32_t nmodels;                 // the list's regression holiday models, plain ones included
+  int32_t mask;                    // bit k: model k is hierarchical
+  int32_t width[RH_MAX_MODELS], nhol[RH_MAX_MODELS];
+  double nu0[RH_MAX_MODELS];       // the Wishart prior's degrees of freedom
+  const double *hyper;             // RH_MAX_MODELS x RHH_HYPER_STRIDE
+  double *mu;                      // chains x RH_MAX_MODELS x RHH_MAX_WIDTH
+  double *omega;                   // chains x RH_MAX_MODELS x RHH_MAX_WIDTH^2 (row-major, leading dimension RHH_MAX_WIDTH)
+  uint64_t *pos;                   // chains: position in RHH_STREAM
 };
 
 // The spike-and-slab autoregressions of a list (ar_spike_kernel.hip).  The prior of the block in

@@ -31,7 +31,9 @@
 
 namespace boom_amd {
 
-__global__ __launch_bounds__(64) void rh_draw_kernel(SsParams P, RhParams R, int draw) {
+// hier: bit k set where model k is hierarchical -- rhh_draw_kernel (hier_holiday_kernel.hip, launched just
+// before) has drawn its coefficients, which are read here as a setter's are
+__global__ __launch_bounds__(64) void rh_draw_kernel(SsParams P, RhParams R, int draw, int hier) {
   const int chain = (int)blockIdx.x + P.chain_first, lane = (int)threadIdx.x;
   if ((int)blockIdx.x >= P.chain_count) return;
   if (P.status[chain] != CHAIN_OK) return;
@@ -47,6 +49,10 @@ __global__ __launch_bounds__(64) void rh_draw_kernel(SsParams P, RhParams R, int
     bool bad = false;
     for (int k = 0; k < R.nmodels; ++k) {
       const double mu = R.prior_mean[k], tausq = R.prior_sd[k] * R.prior_sd[k];
+      if ((hier >> k) & 1) {
+        for (int j = R.first[k] + lane; j < R.first[k + 1]; j += WAVE) s_coef[j] = coef[j];
+        continue;
+      }
       for (int j = R.first[k]; j < R.first[k + 1]; ++j) {
         const double precision = R.counts[j] / sigsq + 1.0 / tausq;
         double mean = tot[j] / sigsq + mu / tausq;
@@ -138,9 +144,9 @@ __global__ __launch_bounds__(256) void rh_fill_kernel(RhParams R, int T, int cha
     R.y[i] = R.y_shared[i % (size_t)T];
 }
 
-hipError_t launch_rh_draw(hipStream_t stream, const SsParams &P, const RhParams &R, int draw) {
+hipError_t launch_rh_draw(hipStream_t stream, const SsParams &P, const RhParams &R, int draw, int hier) {
   KtScope kt(stream, KT_SS_REGHOLIDAY);
-  hipLaunchKernelGGL(rh_draw_kernel, dim3((unsigned)P.chain_count), dim3(WAVE), 0, stream, P, R, draw);
+  hipLaunchKernelGGL(rh_draw_kernel, dim3((unsigned)P.chain_count), dim3(WAVE), 0, stream, P, R, draw, hier);
   return hipGetLastError();
 }
 

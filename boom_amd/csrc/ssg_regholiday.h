@@ -10,6 +10,11 @@
 // w_0 .. w_{H-1}; its coefficients are flattened holiday by holiday, and its calendar is one int32 per
 // time: -1, or the flat index offset_h + day.  One entry per time: "one holiday active at a time" within
 // a model holds by construction.
+//
+// A hierarchical model (HierarchicalRegressionHolidayStateModel, bsts AddHierarchicalRegressionHoliday) is
+// such a model with a flag: one width d <= RHH_MAX_WIDTH for all its holidays, the flat index h d + day, and the
+// hyperparameters of its coefficient vectors' prior N(mu, Omega^-1) -- Sigma0^-1, Sigma0^-1 mu0 and S0 formed
+// once here, by the Cholesky factor and inverse below (rhh_add_refusal, rhh_model).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -27,6 +32,13 @@ struct RhModel {
   double prior_mean = 0.0, prior_sd = 1.0;   // the one prior N(mu, tau^2) of all its coefficients
   std::vector<double> initial;         // sum w_h coefficients
   std::vector<int32_t> calendar;       // as the caller gave it (empty: not set yet)
+  // a hierarchical model (HierarchicalRegressionHolidayStateModel; rhh_add_refusal): every width is `width`,
+  // the prior above is not used; d x d matrices row-major at leading dimension d
+  bool hier = false;
+  int32_t width = 0;
+  double nu0 = 0.0;                    // variance_guess_weight
+  std::vector<double> sinv0, s0, sinv0mu0;      // Sigma0^-1, S0 = nu0 x variance_guess, Sigma0^-1 mu0: formed once
+  std::vector<double> initial_mu, initial_omega;   // the reference's MvnModel(d): 0 and the identity
   int32_t ncoef() const { int32_t n = 0; for (int32_t w : widths) n += w; return n; }
 };
 
@@ -56,6 +68,116 @@ inline const char *rh_add_refusal(const std::vector<RhModel> &models, bool has_s
   if (!(prior_sd > 0.0) || !std::isfinite(prior_sd)) return "the prior standard deviation must be positive and finite";
   for (int64_t i = 0; initial_coefficients && i < n; ++i)
     if (!std::isfinite(initial_coefficients[i])) return "the initial coefficients must be finite";
+  return nullptr;
+}
+
+// The lower Cholesky factor of the d x d matrix A (row-major, leading dimension d; its lower triangle is
+// read) into L, zero above the diagonal: false where a pivot is not positive and finite.
+inline bool rh_cholesky(const double *A, int32_t d, double *L) {
+  for (int32_t i = 0; i < d * d; ++i) L[i] = 0.0;
+  for (int32_t j = 0; j < d; ++j)
+    for (int32_t r = j; r < d; ++r) {
+      double s = A[r * d + j];
+      for (int32_t k = 0; k < j; ++k) s -= L[r * d + k] * L[j * d + k];
+      if (r == j) {
+        if (!(s > 0.0) || !std::isfinite(s)) return false;
+        L[j * d + j] = std::sqrt(s);
+      } else {
+        L[r * d + j] = s / L[j * d + j];
+      }
+    }
+  return true;
+}
+
+// symmetric (to the bit) and positive definite, every entry finite
+inline bool rh_is_spd(const double *A, int32_t d) {
+  for (int32_t r = 0; r < d; ++r)
+    for (int32_t c = 0; c < d; ++c)
+      if (!std::isfinite(A[r * d + c]) || A[r * d + c] != A[c * d + r]) return false;
+  std::vector<double> L((size_t)d * d);
+  return rh_cholesky(A, d, L.data());
+}
+
+// the inverse of a symmetric positive definite matrix by its factor: W = L^-1, then W'W; false as rh_cholesky
+inline bool rh_spd_inverse(const double *A, int32_t d, double *out) {
+  std::vector<double> L((size_t)d * d), W((size_t)d * d, 0.0);
+  if (!rh_cholesky(A, d, L.data())) return false;
+  for (int32_t c = 0; c < d; ++c)
+    for (int32_t i = c; i < d; ++i) {
+      double s = i == c ? 1.0 : 0.0;
+      for (int32_t k = c; k < i; ++k) s -= L[i * d + k] * W[k * d + c];
+      W[i * d + c] = s / L[i * d + i];
+    }
+  for (int32_t r = 0; r < d; ++r)
+    for (int32_t c = 0; c < d; ++c) {
+      double s = 0.0;
+      for (int32_t k = r > c ? r : c; k < d; ++k) s += W[k * d + r] * W[k * d + c];
+      out[r * d + c] = s;
+    }
+  return true;
+}
+
+// ba_ss_add_hierarchical_regression_holiday's arguments against the list so far, as rh_add_refusal
+inline const char *rhh_add_refusal(const std::vector<RhModel> &models, bool has_state_model, int32_t nholidays, int32_t width,
+                                   const double *mean_prior_mean, const double *mean_prior_variance,
+                                   const double *variance_guess, double variance_guess_weight,
+                                   const double *initial_coefficients) {
+  if (!mean_prior_mean || !mean_prior_variance || !variance_guess) return "null argument";
+  if (nholidays < 1) return "a regression holiday model needs at least one holiday";
+  if (!has_state_model) return "a regression holiday model goes on a list of state models: add a state model first";
+  if ((int)models.size() >= RH_MAX_MODELS) return "more than 4 regression holiday models";
+  if (width < 1) return "a holiday's width must be at least 1";
+  if (width > RHH_MAX_WIDTH) return "the holidays of a hierarchical regression holiday model are at most 16 days wide";
+  const int64_t n = (int64_t)nholidays * width;
+  if (n + rh_total_coef(models) > RH_MAX_COEF) return "more than 256 regression holiday coefficients";
+  for (int32_t i = 0; i < width; ++i)
+    if (!std::isfinite(mean_prior_mean[i])) return "the prior mean of the holidays' mean must be finite";
+  for (int32_t i = 0; i < width * width; ++i)
+    if (!std::isfinite(mean_prior_variance[i]) || !std::isfinite(variance_guess[i]))
+      return "the prior variance of the holidays' mean and the variance guess must be finite";
+  if (!std::isfinite(variance_guess_weight)) return "the variance guess weight must be finite";
+  if (!(variance_guess_weight > (double)(width - 1)))
+    return "the variance guess weight must exceed the holidays' width less 1 (the Wishart prior's degrees of freedom)";
+  if (!rh_is_spd(mean_prior_variance, width)) return "the prior variance of the holidays' mean must be symmetric and positive definite";
+  if (!rh_is_spd(variance_guess, width)) return "the variance guess must be symmetric and positive definite";
+  for (int64_t i = 0; initial_coefficients && i < n; ++i)
+    if (!std::isfinite(initial_coefficients[i])) return "the initial coefficients must be finite";
+  return nullptr;
+}
+
+// the model those arguments describe (they have passed rhh_add_refusal)
+inline RhModel rhh_model(int32_t nholidays, int32_t width, const double *mean_prior_mean, const double *mean_prior_variance,
+                         const double *variance_guess, double variance_guess_weight, const double *initial_coefficients) {
+  RhModel m;
+  const int32_t d = width;
+  m.hier = true;
+  m.width = d;
+  m.widths.assign((size_t)nholidays, d);
+  m.nu0 = variance_guess_weight;
+  m.initial.assign((size_t)nholidays * d, 0.0);
+  if (initial_coefficients) m.initial.assign(initial_coefficients, initial_coefficients + (size_t)nholidays * d);
+  m.sinv0.assign((size_t)d * d, 0.0);
+  rh_spd_inverse(mean_prior_variance, d, m.sinv0.data());
+  m.s0.assign((size_t)d * d, 0.0);
+  for (int32_t i = 0; i < d * d; ++i) m.s0[(size_t)i] = variance_guess[i] * variance_guess_weight;
+  m.sinv0mu0.assign((size_t)d, 0.0);
+  for (int32_t r = 0; r < d; ++r)
+    for (int32_t c = 0; c < d; ++c) m.sinv0mu0[(size_t)r] += m.sinv0[(size_t)(r * d + c)] * mean_prior_mean[c];
+  m.initial_mu.assign((size_t)d, 0.0);
+  m.initial_omega.assign((size_t)d * d, 0.0);
+  for (int32_t r = 0; r < d; ++r) m.initial_omega[(size_t)(r * d + r)] = 1.0;
+  return m;
+}
+
+// ba_ss_set_hierarchical_regression_holiday's arguments: nullptr, or the refusal
+inline const char *rhh_set_refusal(const RhModel &m, const double *mean, const double *precision) {
+  if (!m.hier) return "not a hierarchical regression holiday model";
+  if (!mean || !precision) return "null argument";
+  for (int32_t i = 0; i < m.width; ++i)
+    if (!std::isfinite(mean[i])) return "the mean must be finite";
+  for (int32_t i = 0; i < m.width * m.width; ++i)
+    if (!std::isfinite(precision[i])) return "the precision must be finite";
+  if (!rh_is_spd(precision, m.width)) return "the precision must be symmetric and positive definite";
   return nullptr;
 }
 

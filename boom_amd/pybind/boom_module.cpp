@@ -406,6 +406,29 @@ PYBIND11_MODULE(_boom, boom) {
       .def("set_coefficients", [](RegressionHolidayStateModel &m, const NpArray &v) { m.set_coefficients(vector_from(v)); },
            py::arg("coefficients"), "the initial coefficients, one per day of every holiday's window (default: zeros)");
 
+  py::class_<HierarchicalRegressionHolidayStateModel, Ptr<HierarchicalRegressionHolidayStateModel>>(
+      boom, "HierarchicalRegressionHolidayStateModel",
+      "HierarchicalRegressionHolidayStateModel(nholidays, width, mean_prior_mean, mean_prior_variance, variance_guess, "
+      "variance_guess_weight): nholidays holidays of one window width whose coefficient vectors are N(mu, Omega^-1), with "
+      "mu ~ N(mean_prior_mean, mean_prior_variance) and Omega ~ Wishart(variance_guess_weight, variance_guess_weight x "
+      "variance_guess) drawn by HierGaussianRegressionAsisSampler.  As RegressionHolidayStateModel it takes a calendar in "
+      "place of Holiday objects: index[t] = -1, or h x width + the day's position in holiday h's window.")
+      .def(py::init([](int nholidays, int width, const NpArray &mean, const NpArray &variance, const NpArray &guess, double weight) {
+             return new HierarchicalRegressionHolidayStateModel(nholidays, width, vector_from(mean), matrix_from(variance),
+                                                                matrix_from(guess), weight);
+           }),
+           py::arg("nholidays"), py::arg("width"), py::arg("mean_prior_mean"), py::arg("mean_prior_variance"),
+           py::arg("variance_guess"), py::arg("variance_guess_weight"))
+      .def_property_readonly("number_of_coefficients", &HierarchicalRegressionHolidayStateModel::number_of_coefficients)
+      .def_property_readonly("calendar", [](const HierarchicalRegressionHolidayStateModel &m) { return m.calendar(); })
+      .def("set_calendar", &HierarchicalRegressionHolidayStateModel::set_calendar, py::arg("index"))
+      .def("set_coefficients", [](HierarchicalRegressionHolidayStateModel &m, const NpArray &v) { m.set_coefficients(vector_from(v)); },
+           py::arg("coefficients"), "the initial coefficients, holiday by holiday (default: zeros)")
+      .def("holiday_mean", [](const HierarchicalRegressionHolidayStateModel &m, int chain) { return to_numpy(m.holiday_mean(chain)); },
+           py::arg("chain") = 0, "mu in one chain's draw")
+      .def("holiday_precision", [](const HierarchicalRegressionHolidayStateModel &m, int chain) { return matrix_to_numpy(m.holiday_precision(chain)); },
+           py::arg("chain") = 0, "Omega in one chain's draw");
+
   py::class_<DynamicRegressionStateModel, Ptr<DynamicRegressionStateModel>>(
       boom, "DynamicRegressionStateModel",
       "DynamicRegressionStateModel(predictors): regression coefficients that follow independent random walks.  "
@@ -547,6 +570,7 @@ PYBIND11_MODULE(_boom, boom) {
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<RandomWalkHolidayStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<DynamicRegressionStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<RegressionHolidayStateModel> &s) { m.add_state(s); })
+      .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<HierarchicalRegressionHolidayStateModel> &s) { m.add_state(s); })
       .def("regression_holiday_coefficients", [](const StateSpaceRegressionModel &m, int chain, int which) {
              return to_numpy(m.regression_holiday_coefficients(chain, which));
            }, py::arg("chain") = 0, py::arg("which") = 0,

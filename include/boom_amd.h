@@ -894,7 +894,7 @@ int ba_ss_get_dynamic_predictors(ba_engine *e, int32_t block, double *predictors
  * sampler id 162, one position per chain for all its models.
  * Refused with a text, in either order of the calls: the Student-t / Poisson / logit observation
  * families; a look-ahead above 1 (the record does not carry the coefficients).  Not built: the
- * hierarchical model, the dynamic-intercept variant, ba_group_* forwarding. */
+ * dynamic-intercept variant, ba_group_* forwarding (the hierarchical model: below). */
 int ba_ss_add_regression_holiday(ba_engine *e, int32_t nholidays, const int32_t *widths, double prior_mean,
                                  double prior_sd, const double *initial_coefficients, int32_t *model_out);
 int ba_ss_set_regression_holiday_calendar(ba_engine *e, int32_t model, const int32_t *index, int64_t count);
@@ -902,6 +902,34 @@ int ba_ss_get_regression_holiday_calendar(ba_engine *e, int32_t model, int32_t *
 int ba_ss_get_regression_holiday(ba_engine *e, int64_t chain, int32_t model, double *coefficients, double *totals,
                                  double *counts);
 int ba_ss_set_regression_holiday(ba_engine *e, int64_t chain, int32_t model, const double *coefficients);
+
+/* HierarchicalRegressionHolidayStateModel (bsts AddHierarchicalRegressionHoliday) with its sampler,
+ * HierGaussianRegressionAsisSampler: a regression holiday model whose nholidays holidays share one window
+ * width d <= 16 and whose coefficient vectors share the prior beta_h ~ N(mu, Omega^-1), with
+ * mu ~ N(mean_prior_mean, mean_prior_variance) (d and d x d, row-major) and Omega ~ Wishart(
+ * variance_guess_weight, variance_guess_weight x variance_guess).  bsts passes no residual-variance prior:
+ * sigma^2 is the observation model's.  The model takes one of the list's four regression holiday slots and
+ * its nholidays x d coefficients count towards the 256; its calendar, coefficients, totals and counts go
+ * through the calls above (flat index h d + day).  Every chain starts at mu = 0 and Omega = I, the
+ * reference's MvnModel(d).  *model_out: its index among the list's regression holiday models.
+ * Refused with a text beyond the plain model's refusals: d > 16; a weight not above d - 1; a
+ * mean_prior_variance or variance_guess that is not symmetric positive definite; entries not finite.
+ * ba_ss_get_ / ba_ss_set_hierarchical_regression_holiday: one chain's mu (d) and Omega (d x d, row-major;
+ * either may be NULL in the getter); the setter takes chain = -1 for every chain, is a mutator and refuses
+ * an Omega that is not symmetric positive definite.
+ * RNG stream (a convention of this library; BOOM draws from the sampler's generator and, for the first
+ * draw of mu, the global one): the chain's sampler id 163, one position per chain for all its hierarchical
+ * models, in (model, step) order.  A draw with a factor that is not positive definite or a result that is
+ * not finite stops the chain (status 16) and leaves its coefficients, mu, Omega and position as they were.
+ * Departures from BOOM, all in DESIGN 3.26: totals and counts are the plain model's (missing days are
+ * skipped, time 0 is observed); the centred draw's xtx is formed from the current counts every time. */
+int ba_ss_add_hierarchical_regression_holiday(ba_engine *e, int32_t nholidays, int32_t width,
+                                              const double *mean_prior_mean, const double *mean_prior_variance,
+                                              const double *variance_guess, double variance_guess_weight,
+                                              const double *initial_coefficients, int32_t *model_out);
+int ba_ss_get_hierarchical_regression_holiday(ba_engine *e, int64_t chain, int32_t model, double *mean, double *precision);
+int ba_ss_set_hierarchical_regression_holiday(ba_engine *e, int64_t chain, int32_t model, const double *mean,
+                                              const double *precision);
 
 /* ---- bsts(family = "student"): StateSpaceStudentRegressionModel with
  * StateSpaceStudentPosteriorSampler (Models/StateSpace/StateSpaceStudentRegressionModel.cpp,

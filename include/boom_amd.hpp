@@ -569,6 +569,68 @@ class RegressionHolidayStateModel {
   Vector coef_;
 };
 
+// HierarchicalRegressionHolidayStateModel with HierGaussianRegressionAsisSampler
+// (StateModels/HierarchicalRegressionHolidayStateModel.cpp; bsts AddHierarchicalRegressionHoliday):
+// ba_ss_add_hierarchical_regression_holiday.  nholidays holidays of one window width; holiday h's coefficient
+// vector is N(mu, Omega^-1) with mu ~ N(mean_prior_mean, mean_prior_variance) and Omega ~ Wishart(
+// variance_guess_weight, variance_guess_weight x variance_guess), both drawn with the coefficients.  As the
+// plain model it takes window widths and a calendar in place of Holiday objects (index[t] = h x width + day),
+// and is an offset on the series, not a block of the state.  holiday_mean / holiday_precision read one chain's
+// mu and Omega once the model that holds it has been given its sampler.
+class HierarchicalRegressionHolidayStateModel {
+ public:
+  HierarchicalRegressionHolidayStateModel(int nholidays, int width, const Vector &mean_prior_mean, const SpdMatrix &mean_prior_variance,
+                                          const SpdMatrix &variance_guess, double variance_guess_weight)
+      : nholidays_(nholidays), width_(width), mean_prior_mean_(mean_prior_mean), mean_prior_variance_(mean_prior_variance),
+        variance_guess_(variance_guess), weight_(variance_guess_weight) {
+    if (nholidays < 1) report_error("a regression holiday model needs at least one holiday");
+    if (width < 1) report_error("a holiday's width must be at least 1");
+    if ((int)mean_prior_mean.size() != width || mean_prior_variance.nrow() != width || mean_prior_variance.ncol() != width ||
+        variance_guess.nrow() != width || variance_guess.ncol() != width)
+      report_error("the prior mean takes width entries, the prior variance and the variance guess width x width");
+    coef_ = Vector((size_t)nholidays * width, 0.0);
+  }
+  int number_of_coefficients() const { return nholidays_ * width_; }
+  int number_of_holidays() const { return nholidays_; }
+  int width() const { return width_; }
+  const std::vector<int32_t> &calendar() const { return calendar_; }
+  void set_calendar(const std::vector<int32_t> &index) {
+    for (int32_t k : index)
+      if (k < -1 || k >= number_of_coefficients()) report_error("a calendar entry must be -1 (inactive) or a coefficient index in [0, nholidays x width)");
+    calendar_ = index;
+  }
+  // the initial coefficients (default: zeros)
+  void set_coefficients(const Vector &c) {
+    if ((int)c.size() != number_of_coefficients()) report_error("a regression holiday model takes one coefficient per day of every holiday's window");
+    coef_ = c;
+  }
+  Vector holiday_mean(int chain = 0) const {
+    Vector v((size_t)width_);
+    bound()->check(ba_ss_get_hierarchical_regression_holiday(engine_->get(), chain, index_, v.data(), nullptr));
+    return v;
+  }
+  SpdMatrix holiday_precision(int chain = 0) const {
+    SpdMatrix m(width_, width_);   // (symmetric: the row-major entries are the column-major ones)
+    bound()->check(ba_ss_get_hierarchical_regression_holiday(engine_->get(), chain, index_, nullptr, m.data()));
+    return m;
+  }
+  int nholidays_, width_;
+  Vector mean_prior_mean_;
+  SpdMatrix mean_prior_variance_, variance_guess_;
+  double weight_;
+  std::vector<int32_t> calendar_;
+  Vector coef_;
+  // set when the model that holds it hands its list to the engine
+  Ptr<Engine> engine_;
+  int32_t index_ = -1;
+
+ private:
+  const Ptr<Engine> &bound() const {
+    if (!engine_ || index_ < 0) report_error("the model is on no state space model with a sampler yet");
+    return engine_;
+  }
+};
+
 // ArStateModel(number_of_lags) with an ArPosteriorSampler (StateModels/ArStateModel.hpp:53,
 // TimeSeries/PosteriorSamplers/ArPosteriorSampler.hpp)
 class ArStateModel {
@@ -734,7 +796,9 @@ class StateSpaceRegressionModel : public Model {
   void add_state(const Ptr<MonthlyAnnualCycle> &s) { Entry e; e.kind = 11; e.monthly = s; models_.push_back(e); finalized_ = false; }
   void add_state(const Ptr<DynamicRegressionStateModel> &s) { Entry e; e.kind = 12; e.dynreg = s; models_.push_back(e); finalized_ = false; }
   // (no block of the state: the engine numbers the regression holiday models on their own)
-  void add_state(const Ptr<RegressionHolidayStateModel> &s) { reg_holidays_.push_back(s); finalized_ = false; }
+  void add_state(const Ptr<RegressionHolidayStateModel> &s) { reg_holidays_.push_back(s); hier_holidays_.push_back(nullptr); finalized_ = false; }
+  // (a hierarchical one takes a place among them: reg_holidays_[k] is null where hier_holidays_[k] is not)
+  void add_state(const Ptr<HierarchicalRegressionHolidayStateModel> &s) { reg_holidays_.push_back(nullptr); hier_holidays_.push_back(s); finalized_ = false; }
   int number_of_state_models() const { return (int)models_.size(); }
   bool has_student_trend() const {
     for (const Entry &e : models_) if (e.kind == 8) return true;
@@ -826,9 +890,20 @@ class StateSpaceRegressionModel : public Model {
         }
       }
       for (size_t k = 0; k < reg_holidays_.size(); ++k) {
-        const RegressionHolidayStateModel &s = *reg_holidays_[k];
         int32_t model = -1;
         eng_->check(ba_ss_set_lookahead(h, 1));   // (the engine refuses a look-ahead with this model)
+        if (hier_holidays_[k]) {
+          HierarchicalRegressionHolidayStateModel &s = *hier_holidays_[k];
+          eng_->check(ba_ss_add_hierarchical_regression_holiday(h, s.nholidays_, s.width_, s.mean_prior_mean_.data(),
+                                                                s.mean_prior_variance_.data(), s.variance_guess_.data(), s.weight_,
+                                                                s.coef_.data(), &model));
+          if (!s.calendar_.empty())
+            eng_->check(ba_ss_set_regression_holiday_calendar(h, model, s.calendar_.data(), (int64_t)s.calendar_.size()));
+          s.engine_ = eng_;
+          s.index_ = model;
+          continue;
+        }
+        const RegressionHolidayStateModel &s = *reg_holidays_[k];
         eng_->check(ba_ss_add_regression_holiday(h, (int32_t)s.widths_.size(), s.widths_.data(), s.prior_mean_, s.prior_sd_,
                                                  s.coef_.data(), &model));
         if (!s.calendar_.empty())
@@ -840,7 +915,7 @@ class StateSpaceRegressionModel : public Model {
   // the coefficients of the `which`-th RegressionHolidayStateModel in one chain's current draw
   Vector regression_holiday_coefficients(int chain = 0, int which = 0) const {
     if (which < 0 || which >= (int)reg_holidays_.size()) report_error("The model has no such RegressionHolidayStateModel.");
-    Vector v(reg_holidays_[which]->number_of_coefficients());
+    Vector v(hier_holidays_[which] ? hier_holidays_[which]->number_of_coefficients() : reg_holidays_[which]->number_of_coefficients());
     eng_->check(ba_ss_get_regression_holiday(eng_->get(), chain, which, v.data(), nullptr, nullptr));
     return v;
   }
@@ -1016,6 +1091,7 @@ class StateSpaceRegressionModel : public Model {
   int T_, p_;
   std::vector<Entry> models_;
   std::vector<Ptr<RegressionHolidayStateModel>> reg_holidays_;
+  std::vector<Ptr<HierarchicalRegressionHolidayStateModel>> hier_holidays_;
   bool finalized_ = false;
   bool list_always_ = false;
 };
@@ -1036,8 +1112,8 @@ class StateSpacePosteriorSampler : public PosteriorSampler {
     model->engine()->check(ba_set_state(h, -1, g0.data(), nullptr, 1.0));
     // the callers' per-iteration loop at the device's rate (ba_ss_draw_next serves the
     // rounds from batches enqueued ahead; nothing a caller does can observe it)
-    // (a StudentLocalLinearTrendStateModel's weights and a RegressionHolidayStateModel's coefficients are not
-    // in the look-ahead's snapshots: one round per draw)
+    // (a StudentLocalLinearTrendStateModel's weights and a RegressionHolidayStateModel's coefficients -- a
+    // hierarchical one's too -- are not in the look-ahead's snapshots: one round per draw)
     model->engine()->check(ba_ss_set_lookahead(h, (model->has_student_trend() || model->has_regression_holiday()) ? 1 : 64));
   }
   void set_lookahead(int rounds) { model_->engine()->check(ba_ss_set_lookahead(model_->engine()->get(), rounds)); }
