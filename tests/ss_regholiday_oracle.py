@@ -7,8 +7,8 @@ T = 1, RQR = 0, a0 = 1, P0 = 0; Z_t = coefficient[h(t)][d(t)] where a holiday is
 model is a dict (reg_holiday_model) whose calendar holds one flat index offset_h + day per time, or -1.
 
 Because the state is deterministic, the state draw of a list with such models is the state draw of the list
-without them on the series y_t - (the models' effects at t): the state half below is ss_holiday_oracle's
-(or a class built on it, ss_dynreg_oracle's), fed that series.  augmented_structure() builds the model the
+without them on the series y_t - (the models' effects at t): the state half below is
+ss_state_models_oracle's StateOracle, fed that series.  augmented_structure() builds the model the
 long way -- a constant component per model with Z_t = its coefficient -- for the test that the two agree.
 
 CONVENTIONS (the device's; the reference draws from the model's own generator): the coefficients of all
@@ -24,8 +24,7 @@ import ctypes as C
 
 import numpy as np
 
-import ss_holiday_oracle as sho
-from ss_holiday_oracle import LEVEL, f64
+from ss_state_models_oracle import LEVEL, Structure, f64
 
 REGHOLIDAY = "regression_holiday"
 STREAM = 162
@@ -145,7 +144,7 @@ def dummies_posterior_mean(model, response, observed, T, sigsq):
     return np.linalg.solve(A, b)
 
 
-class AugmentedStructure(sho.Structure):
+class AugmentedStructure(Structure):
     """the list with every regression holiday model as the reference has it: one more state component per
     model, the constant 1 (a0 = 1, P0 = 0, no error), observed through Z_t = the model's coefficient"""
 
@@ -164,8 +163,8 @@ class AugmentedStructure(sho.Structure):
 
 
 class RegHolidayOracle:
-    """one chain: `base` restates the state half of the list without the models (a sho.HolidayOracle or a
-    class built on it); this class adds the models' coefficients, totals and stream"""
+    """one chain: `base` restates the state half of the list without the models (a StateOracle of
+    ss_state_models_oracle); this class adds the models' coefficients, totals and stream"""
 
     def __init__(self, o, base, models, y, X, seed, chain):
         self.o, self.L, self.base, self.models = o, o.lib, base, models

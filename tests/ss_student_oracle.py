@@ -178,13 +178,14 @@ def simulate_forward(S, sigsq, H, rnorm):
     return st, ys
 
 
-def impute_state(S, sigsq, ystar, observed, H, rnorm, FK=None):
+def impute_state(S, sigsq, ystar, observed, H, rnorm, FK=None, simulate=simulate_forward):
     """Base::impute_state (StateSpaceModelBase.cpp:278-291): the state draw, T x m.  The data
-    filter and the simulation filter share F_t and K_t (FK: computed already)"""
+    filter and the simulation filter share F_t and K_t (FK: computed already); simulate: the
+    simulation of a Structure whose state errors are not the ones above"""
     T = len(ystar)
     F, K = FK if FK is not None else gains(S, sigsq, observed, H)
     v = innovations(S, K, ystar, observed)
-    st, ys = simulate_forward(S, sigsq, H, rnorm)
+    st, ys = simulate(S, sigsq, H, rnorm)
     vs = innovations(S, K, ys, observed)
     r, r0 = disturbance_smooth(S, v, F, K)
     rs, r0s = disturbance_smooth(S, vs, F, K)

@@ -96,23 +96,7 @@ def simulate_forward(S, sigsq, H, rnorm):
 def impute_state(S, sigsq, ystar, observed, H, rnorm):
     """sso.impute_state on simulate_forward above (the filter, the smoother and the mean correction
     read the per-step state variance through S.rqr)"""
-    T = len(ystar)
-    F, K = sso.gains(S, sigsq, observed, H)
-    v = sso.innovations(S, K, ystar, observed)
-    st, ys = simulate_forward(S, sigsq, H, rnorm)
-    vs = sso.innovations(S, K, ys, observed)
-    r, r0 = sso.disturbance_smooth(S, v, F, K)
-    rs, r0s = sso.disturbance_smooth(S, vs, F, K)
-    mean_obs = S.a0 + S.P0 * r0
-    mean_sim = S.a0 + S.P0 * r0s
-    out = st.copy()
-    for t in range(T):
-        if t > 0:
-            Tm, q = S.Tmat(t - 1), S.rqr(t - 1, sigsq)
-            mean_obs = Tm @ mean_obs + q * r[t - 1]
-            mean_sim = Tm @ mean_sim + q * rs[t - 1]
-        out[t] += mean_obs - mean_sim
-    return out
+    return sso.impute_state(S, sigsq, ystar, observed, H, rnorm, simulate=simulate_forward)
 
 
 def residuals(S, st):

@@ -25,6 +25,7 @@ import pytest
 import autoar_cases as ac
 import ss_autoar_oracle as sao
 from cases import bsts_priors, general_data, general_spec
+from ss_gpu_helpers import refused
 
 gpu = pytest.mark.gpu
 U = 2.0 ** -53
@@ -346,13 +347,6 @@ def test_model_frequencies_match_the_exact_posterior():
 
 
 # ---- 7: the interface ------------------------------------------------------------------------------------
-def refused(fn, text):
-    import boom_amd
-    with pytest.raises(boom_amd.BoomAmdError) as e:
-        fn()
-    assert text in str(e.value), str(e.value)
-
-
 @gpu
 def test_refusals_and_their_texts():
     import boom_amd

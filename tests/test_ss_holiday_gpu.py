@@ -22,28 +22,9 @@ import ss_holiday_cases as shc
 import ss_holiday_oracle as sho
 import ss_student_oracle as sso
 from cases import bsts_priors, general_spec
+from ss_gpu_helpers import RTOL, close, engine, refused
 
 gpu = pytest.mark.gpu
-RTOL = 1e-8
-
-
-def close(a, b, rtol=RTOL):
-    a, b = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
-    return bool(np.all(np.abs(a - b) <= rtol * np.abs(b)))
-
-
-def engine(chains, seed, y, X, obs, blocks, g0, kernel=None):
-    import boom_amd
-    prior, _, sig_up = bsts_priors(X, y, 2)
-    eng = boom_amd.Engine(chains, seed=seed)
-    eng.ss_set_data(y, X, obs)
-    eng.set_priors(prior["b"], prior["ominv"], prior["pi"], prior["df"], prior["sigma_guess"],
-                   sigma_upper_limit=sig_up)
-    eng.ss_set_state_models(blocks)
-    if kernel is not None:
-        eng.ss_set_tuning(kernel=kernel)
-    eng.set_state(g0)
-    return eng
 
 
 # ---- 1. identity ---------------------------------------------------------------------------------------
@@ -279,13 +260,6 @@ def test_prediction_errors_match_restatement(oracle):
 
 
 # ---- 7. interface ------------------------------------------------------------------------------------------------
-def refused(fn, text):
-    import boom_amd
-    with pytest.raises(boom_amd.BoomAmdError) as e:
-        fn()
-    assert text in str(e.value), str(e.value)
-
-
 @gpu
 def test_refusals_and_their_texts():
     import boom_amd

@@ -24,6 +24,7 @@ import ss_regholiday_cases as src
 import ss_regholiday_oracle as sro
 import student_trend_cases as stc
 from cases import bsts_priors, general_data, general_spec
+from ss_gpu_helpers import refused
 
 gpu = pytest.mark.gpu
 CHAINS = 4
@@ -348,13 +349,6 @@ def test_forecast_and_prediction_errors_equal_the_twins():
 
 
 # ---- 6. interface --------------------------------------------------------------------------------------------
-def refused(fn, text):
-    import boom_amd
-    with pytest.raises(boom_amd.BoomAmdError) as e:
-        fn()
-    assert text in str(e.value), str(e.value)
-
-
 @gpu
 def test_refusals_round_trips_and_the_list_reset():
     import boom_amd

@@ -20,6 +20,7 @@ import pytest
 
 import ss_student_oracle as sso
 from cases import bsts_priors, general_data, general_spec, kernel_instance
+from ss_gpu_helpers import refused
 
 gpu = pytest.mark.gpu
 RTOL = 1e-8
@@ -255,13 +256,6 @@ def small_problem():
     T, p = 30, 3
     X, y, _, _ = general_data(T, p, 1, [], seed=2)
     return T, p, X, y, general_spec(y, [("level",)])
-
-
-def refused(fn, text):
-    import boom_amd
-    with pytest.raises(boom_amd.BoomAmdError) as e:
-        fn()
-    assert text in str(e.value), str(e.value)
 
 
 @gpu

@@ -22,6 +22,7 @@ import ss_student_oracle as sso
 import ss_student_trend_oracle as sto
 import student_trend_cases as stc
 from cases import bsts_priors, general_data, kernel_instance
+from ss_gpu_helpers import refused
 
 gpu = pytest.mark.gpu
 RTOL = 1e-8
@@ -282,13 +283,6 @@ def test_state_draws_have_the_dense_posterior_moments():
 
 
 # ---- interface -------------------------------------------------------------------------------------------
-def refused(fn, text):
-    import boom_amd
-    with pytest.raises(boom_amd.BoomAmdError) as e:
-        fn()
-    assert text in str(e.value), str(e.value)
-
-
 @gpu
 def test_refusals_and_their_texts():
     import boom_amd
