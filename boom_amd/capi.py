@@ -191,6 +191,8 @@ SIGNATURES = {
     "ba_ss_get_season_calendar": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_int64)]),
     "ba_monthly_cycle_calendar": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_uint8)]),
     "ba_ss_add_dynamic_regression": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "ba_ss_add_dynamic_regression_ar": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                  C.POINTER(C.c_int32)]),
     "ba_ss_set_dynamic_predictors": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int64]),
     "ba_ss_get_dynamic_predictors": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_int64)]),
     "ba_ss_add_regression_holiday": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_double, C.c_double, _dp,
@@ -874,6 +876,10 @@ class Engine:
         "dynamic_regression": predictors (rows x d, row t = x_t; rows past the series serve forecasts) and
         d entries each of df, sigma_guess, sigma_upper_limit, initial_sigma, a0, P0 -- it goes through
         ba_ss_add_dynamic_regression, a numeric kind 12 to ba_ss_add_state_model, which refuses it;
+        "dynamic_regression_ar": predictors (rows x d) and lags -- every coefficient an autoregression of that
+        many lags --, d entries each of df, sigma_guess, sigma_upper_limit, initial_sigma, and d x lags each of
+        a0, P0 (default 0 and 1, bsts's) and initial_phi (default zeros): d state models of the list, one per
+        coefficient, through ba_ss_add_dynamic_regression_ar;
         "regression_holiday": widths (one per holiday), prior = (mean, sd) and, optionally, calendar --
         ss_set_regression_holiday_calendar's flat indices -- and coefficients (the initial ones): no block of
         the list, ss_add_regression_holiday numbers such models on their own;
@@ -915,6 +921,28 @@ class Engine:
                 self._check(self.lib.ba_ss_add_dynamic_regression(self._h, x.shape[1], _p(x), x.shape[0],
                                                                   *[_p(a) for a in arrs]))
                 self._blocks.append(dict(kind="dynamic_regression", nvar=x.shape[1], lags=0))
+                continue
+            elif b["kind"] == "dynamic_regression_ar":
+                x = np.ascontiguousarray(b["predictors"], dtype=np.float64)
+                if x.ndim != 2:
+                    raise ValueError("predictors: a rows x d array")
+                d, L = x.shape[1], int(b["lags"])
+                arrs = [np.ascontiguousarray(b[k], dtype=np.float64) for k in
+                        ("df", "sigma_guess", "sigma_upper_limit", "initial_sigma")]
+                if any(a.size != d for a in arrs):
+                    raise ValueError("an AR dynamic regression takes one entry per predictor of df, sigma_guess, "
+                                     "sigma_upper_limit and initial_sigma")
+                n = d * max(L, 0)
+                a0 = np.ascontiguousarray(b.get("a0", np.zeros(n)), dtype=np.float64).ravel()
+                p0 = np.ascontiguousarray(b.get("P0", np.ones(n)), dtype=np.float64).ravel()
+                ph = None if b.get("initial_phi") is None else np.ascontiguousarray(b["initial_phi"], dtype=np.float64).ravel()
+                if a0.size != n or p0.size != n or (ph is not None and ph.size != n):
+                    raise ValueError("an AR dynamic regression takes d x lags entries of a0, P0 and initial_phi")
+                first = C.c_int32()
+                self._check(self.lib.ba_ss_add_dynamic_regression_ar(self._h, d, L, _p(x), x.shape[0], *[_p(a) for a in arrs],
+                                                                     None if ph is None else _p(ph), _p(a0), _p(p0), C.byref(first)))
+                assert first.value == len(self._blocks)
+                self._blocks += [dict(kind="dynamic_regression_ar", nvar=1, lags=L, xcols=d) for _ in range(d)]
                 continue
             kind = int(b["kind"])
             ip = np.zeros(4, np.int32)
@@ -1188,16 +1216,17 @@ class Engine:
 
     def ss_set_dynamic_predictors(self, block, predictors):
         """a dynamic regression's predictors (state model `block`), rows x d: replaced, or extended with the
-        rows a forecast needs (at least T rows; T + horizon for ss_forecast)"""
+        rows a forecast needs (at least T rows; T + horizon for ss_forecast).  An AR dynamic regression: all
+        its d columns, on the model's first block"""
         x = np.ascontiguousarray(predictors, dtype=np.float64)
-        if x.ndim != 2 or x.shape[1] != self._blocks[block]["nvar"]:
+        if x.ndim != 2 or x.shape[1] != self._blocks[block].get("xcols", self._blocks[block]["nvar"]):
             raise ValueError("predictors: a rows x d array")
         self._check(self.lib.ba_ss_set_dynamic_predictors(self._h, block, _p(x), x.shape[0]))
 
     def ss_get_dynamic_predictors(self, block):
         n = C.c_int64()
         self._check(self.lib.ba_ss_get_dynamic_predictors(self._h, block, None, C.byref(n)))
-        d = self._blocks[block]["nvar"]
+        d = self._blocks[block].get("xcols", self._blocks[block]["nvar"])
         x = np.zeros((max(n.value, 1), d))
         self._check(self.lib.ba_ss_get_dynamic_predictors(self._h, block, _p(x), C.byref(n)))
         return x[:n.value]

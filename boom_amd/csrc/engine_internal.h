@@ -481,9 +481,13 @@ struct ba_engine {
   // holidays' positions, with their prefix counts behind the table (SsParams::cal)
   std::vector<uint8_t> season_calendar[SSG_MAX_BLOCKS];
   // DynamicRegressionStateModel (SsgBlock::dynreg): every such block's predictors as the caller gave
-  // them (rows x dim, row-major), and the list's table on the device (SsParams::dyn; dyn_rows rows -- the
+  // them (rows x dim, row-major; a block of an AR dynamic regression: its one column), and the list's table on the device (SsParams::dyn; dyn_rows rows -- the
   // shortest block's --, 0: to be packed again)
   std::vector<double> dyn_predictors[SSG_MAX_BLOCKS];
+  // DynamicRegressionArStateModel (SSG_DYNAMIC_REGRESSION_AR): which blocks form one model -- block b of such
+  // a model: the model's first block and its coefficients (0: block b is of no such model).  Each of its
+  // blocks keeps its own column in dyn_predictors (rows x 1).
+  int32_t dynar_first[SSG_MAX_BLOCKS] = {}, dynar_xdim[SSG_MAX_BLOCKS] = {};
   DevBuf<double> ddyn;
   int64_t dyn_rows = 0;
   // RegressionHolidayStateModel (ssg_regholiday.h; reg_holiday_kernel.hip): the list's models -- no blocks

@@ -15,7 +15,7 @@ static int dyn_prepare(ba_engine *e, int64_t extra) {
   if (!e->ssm_set || !ssg_has(e->ssg, SSG_HAS_DYNREG)) return BA_OK;
   for (int b = 0; b < e->ssg.nblocks; ++b) {
     if (!e->ssg.blk[b].dynreg) continue;
-    const int64_t n = (int64_t)e->dyn_predictors[b].size() / e->ssg.blk[b].dim;
+    const int64_t n = (int64_t)e->dyn_predictors[b].size() / ssg_dyn_width(e->ssg.blk[b]);
     char buf[240];
     if (n < (int64_t)e->T) {
       std::snprintf(buf, sizeof buf, "the predictors of state model %d have %lld rows, the series has %d time points",
@@ -124,6 +124,7 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
   e->hol_calendar[e->ssg.nblocks - 1].clear();
   e->season_calendar[e->ssg.nblocks - 1].clear();
   e->dyn_predictors[e->ssg.nblocks - 1].clear();
+  e->dynar_xdim[e->ssg.nblocks - 1] = 0;
   e->dyn_rows = 0;
   e->ssm_set = true;
   e->ss_level_set = false;
@@ -132,7 +133,7 @@ static int ssg_add(ba_engine *e, int32_t kind, const int32_t *iparams, const dou
 }
 static void ssg_clear(ba_engine *e) {
   e->ssg = SsgSpec{};
-  for (int b = 0; b < SSG_MAX_BLOCKS; ++b) { e->hol_calendar[b].clear(); e->season_calendar[b].clear(); e->dyn_predictors[b].clear(); }
+  for (int b = 0; b < SSG_MAX_BLOCKS; ++b) { e->hol_calendar[b].clear(); e->season_calendar[b].clear(); e->dyn_predictors[b].clear(); e->dynar_xdim[b] = 0; }
   e->hol_cal_count = 0;
   e->dyn_rows = 0;
   e->rh_models.clear();   // (the regression holiday models belong to the list)
@@ -258,6 +259,50 @@ int ba_ss_add_dynamic_regression(ba_engine *e, int32_t xdim, const double *predi
   return BA_OK;
 }
 
+// DynamicRegressionArStateModel(X, lags) with DynamicRegressionArPosteriorSampler: xdim autoregression blocks
+// with a row of data (ssg_append_dynreg_ar), all or none.  predictors: rows x xdim row-major, row t = x_t.
+int ba_ss_add_dynamic_regression_ar(ba_engine *e, int32_t xdim, int32_t lags, const double *predictors, int64_t rows,
+                                    const double *var_df, const double *var_sigma_guess,
+                                    const double *var_sigma_upper_limit, const double *var_initial_sigma,
+                                    const double *initial_phi, const double *initial_state_mean,
+                                    const double *initial_state_variance, int32_t *first_block_out) {
+  if (!e) return fail(BA_E_INVALID, "null engine");
+  MUTATE(e);
+  if (!predictors) return fail(BA_E_INVALID, "null argument");
+  if (xdim < 1) return fail(BA_E_INVALID, "a dynamic regression needs at least one predictor");
+  if (rows <= 0) return fail(BA_E_INVALID, "a dynamic regression needs at least one row of predictors");
+  if (ssg_dyn_check(predictors, rows, xdim) >= 0) return fail(BA_E_INVALID, "the predictors of a dynamic regression must be finite");
+  // (a local-level specification is replaced, not extended -- once the append is known to go through)
+  SsgSpec list = e->ss_level_set ? SsgSpec{} : e->ssg;
+  const SsgInitial initial{e->ssg_initial_sigsq, e->ssg_initial_phi, e->ar_spike_prior,
+                           e->slt_nu_kind, e->slt_nu_a, e->slt_nu_b, e->slt_initial_nu};
+  const SsgModelArgs args{nullptr, var_df, var_sigma_guess, var_sigma_upper_limit, var_initial_sigma,
+                          initial_phi, initial_state_mean, initial_state_variance};
+  const SsgRefusal r = ssg_append_dynreg_ar(list, initial, ss_family(e->data_kind), xdim, lags, args);
+  if (r.text) return fail(r.code, r.text);
+  if (e->ss_level_set) ssg_clear(e);
+  e->ss_level_set = false;
+  e->ssg = list;
+  const int first = e->ssg.nblocks - xdim;
+  for (int i = 0; i < xdim; ++i) {
+    const int b = first + i;
+    e->hol_calendar[b].clear();
+    e->season_calendar[b].clear();
+    e->dyn_predictors[b].resize((size_t)rows);
+    for (int64_t t = 0; t < rows; ++t) e->dyn_predictors[b][(size_t)t] = predictors[(size_t)t * xdim + i];
+    e->dynar_first[b] = first;
+    e->dynar_xdim[b] = xdim;
+  }
+  e->dyn_rows = 0;
+  e->ssm_set = true;
+  e->dss_scratch.release();
+  if (first_block_out) *first_block_out = first;
+  return BA_OK;
+}
+
+static const char *const dynar_not_first =
+    "a block of an AR dynamic regression that is not the model's first: its predictors are set and read on the model's first block";
+
 // replace a dynamic regression's predictors, or extend them (the rows past T serve forecasts: the
 // reference's add_forecast_data)
 int ba_ss_set_dynamic_predictors(ba_engine *e, int32_t block, const double *predictors, int64_t rows) {
@@ -267,6 +312,16 @@ int ba_ss_set_dynamic_predictors(ba_engine *e, int32_t block, const double *pred
   if (!e->ssm_set || block < 0 || block >= e->ssg.nblocks) return fail(BA_E_INVALID, "state model index out of range");
   const SsgBlock &k = e->ssg.blk[block];
   if (!k.dynreg) return fail(BA_E_INVALID, "not a dynamic regression state model");
+  if (const int xdim = e->dynar_xdim[block]) {   // (an AR dynamic regression: all its columns, on its first block)
+    if (e->dynar_first[block] != block) return fail(BA_E_INVALID, dynar_not_first);
+    if (ssg_dyn_check(predictors, rows, xdim) >= 0) return fail(BA_E_INVALID, "the predictors of a dynamic regression must be finite");
+    for (int i = 0; i < xdim; ++i) {
+      e->dyn_predictors[block + i].resize((size_t)rows);
+      for (int64_t t = 0; t < rows; ++t) e->dyn_predictors[block + i][(size_t)t] = predictors[(size_t)t * xdim + i];
+    }
+    e->dyn_rows = 0;
+    return BA_OK;
+  }
   if (ssg_dyn_check(predictors, rows, k.dim) >= 0) return fail(BA_E_INVALID, "the predictors of a dynamic regression must be finite");
   e->dyn_predictors[block].assign(predictors, predictors + (size_t)rows * (size_t)k.dim);
   e->dyn_rows = 0;   // (packed again by the next call that launches)
@@ -279,6 +334,14 @@ int ba_ss_get_dynamic_predictors(ba_engine *e, int32_t block, double *predictors
   if (!e->ssm_set || block < 0 || block >= e->ssg.nblocks) return fail(BA_E_INVALID, "state model index out of range");
   if (!e->ssg.blk[block].dynreg) return fail(BA_E_INVALID, "not a dynamic regression state model");
   const std::vector<double> &c = e->dyn_predictors[block];
+  if (const int xdim = e->dynar_xdim[block]) {   // (an AR dynamic regression: rows x xdim, on its first block)
+    if (e->dynar_first[block] != block) return fail(BA_E_INVALID, dynar_not_first);
+    if (rows) *rows = (int64_t)c.size();
+    if (predictors)
+      for (int i = 0; i < xdim; ++i)
+        for (size_t t = 0; t < c.size(); ++t) predictors[t * (size_t)xdim + i] = e->dyn_predictors[block + i][t];
+    return BA_OK;
+  }
   if (rows) *rows = (int64_t)c.size() / e->ssg.blk[block].dim;
   if (predictors && !c.empty()) std::memcpy(predictors, c.data(), c.size() * sizeof(double));
   return BA_OK;

@@ -54,6 +54,14 @@ enum { SSG_LOCAL_LEVEL = 1, SSG_LOCAL_LINEAR_TREND = 2, SSG_SEASONAL = 3, SSG_AR
 // variance slots and d state-error rows; the predictors of a list are one table for all chains
 // (SsParams::dyn), and such a list is served by the DR instances of the general kernel.
 enum { SSG_DYNAMIC_REGRESSION = 12 };
+// DynamicRegressionArStateModel with DynamicRegressionArPosteriorSampler (bsts AddDynamicRegression with
+// DynamicRegressionArOptions(lags)): every coefficient an autoregression of `lags` lags.  It comes through
+// ba_ss_add_dynamic_regression_ar; ssg_abi_kind names each of its blocks by this number.  Stored as xdim
+// consecutive blocks of kind SSG_AR and dimension lags with SsgBlock::dynreg set: block i's first component is
+// coefficient i (Z_t = x_{t,i} there, 0 on its lags), T = the autoregression's, RQR = sigma_i^2 at the first
+// component; each block has an autoregression slot, a variance slot and an error row as kind 4 has.  Which
+// blocks form one model is the engine's knowledge.  Served by the DR instances.
+enum { SSG_DYNAMIC_REGRESSION_AR = 14 };
 // the packed calendar: entry t holds block b's position at time t in byte b, SSG_CAL_OFF where the
 // block is inactive at t (or is no holiday block).  A calendar seasonal's byte: SSG_CAL_SEASON where
 // time t starts a new season (its other bits are not read).
@@ -108,6 +116,8 @@ struct SsgBlock {
   // local level of dimension dim: a dynamic regression (SSG_DYNAMIC_REGRESSION): 1 + the column of the
   // list's predictor table its first coefficient reads (0: no such block).  Variance slot i of the
   // block reads Philox sampler id sid[0] + 16 i (sid[1] is not used).
+  // An autoregression (kind SSG_AR) with the field set: one coefficient of an AR dynamic regression
+  // (SSG_DYNAMIC_REGRESSION_AR) -- 1 + the column its first component reads; its sampler id is sid[0] as kind 4's.
   int32_t dynreg;
 };
 // is the block a calendar seasonal (SSG_CALENDAR_SEASONAL: its season starts are read from the packed calendar)?

@@ -194,6 +194,11 @@ __global__ __launch_bounds__(WAVE) void ss_filter_kernel(SsFilterParams P) {
       zsel = false;
       qdiag = s_var[v0 + w];
     }
+    // (one coefficient of an AR dynamic regression: the autoregression's first component reads the block's column)
+    if (kd == SSG_AR && P.dyn && Q.blk[b].dynreg && w == 0) {
+      dr = true; dcol = Q.blk[b].dynreg - 1;
+      zsel = false;
+    }
     a = Q.a0[lane];
     // (a semilocal trend's third component IS the slope's long-run mean)
     if (kd == SSG_SEMILOCAL && w == 2) a = s_phi[SsfBlocks::arx_of(d) * AR_MAX + 1];

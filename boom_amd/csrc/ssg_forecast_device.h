@@ -22,7 +22,8 @@ namespace {
 // A calendar seasonal steps into a new season where entry tm + 1 carries SSG_CAL_SEASON.
 // dyn: the predictor table of the list's dynamic regressions (dyn_cols columns, rows up to tm + 2; nullptr:
 // none).  Such a block advances with one error per coefficient, in order, and the returned Z'st weighs its
-// components with row tm + 2 of the table.
+// components with row tm + 2 of the table.  An autoregression block with SsgBlock::dynreg set (one coefficient
+// of an AR dynamic regression) advances as an autoregression and weighs its first component with its column.
 __device__ __forceinline__ double ssg_forecast_step(const SsmParams &M, const SsgSpec &Q, int chain, int lane, int tm,
                                                     SeqRng &rng, double &st, const uint64_t *cal = nullptr,
                                                     const double *dyn = nullptr, int dyn_cols = 0) {
@@ -102,7 +103,7 @@ __device__ __forceinline__ double ssg_forecast_step(const SsmParams &M, const Ss
     }
     if (K.dynreg) {   // (Z = the predictors of the new state's time)
       const double *x = dyn + (size_t)(tm + 2) * dyn_cols + (K.dynreg - 1);
-      for (int i = 0; i < K.dim; ++i) {
+      for (int i = 0; i < (K.kind == SSG_AR ? 1 : K.dim); ++i) {
         const double zv = x[i] * rl(st, K.first + i);
         zs = (b == 0 && i == 0) ? zv : zs + zv;
       }

@@ -159,6 +159,13 @@ __host__ __device__ inline int ssg_pass_lds_doubles(int m, int ld, int bl, int n
 // wave 1's PZ the block's whole row, a broadcast read per component.  No step waits for HBM.  The block
 // draws d state-error normals per step whatever the sigmas (sigma_i = 0 scales its normal to 0) and d for
 // the initial state (rmvn_mt).  Variance slot i of the block reads sampler id sid[0] + 16 i.
+// The DR instances also serve the AR dynamic regression (SSG_DYNAMIC_REGRESSION_AR): an autoregression block
+// (kind SSG_AR) with the bit set is ONE coefficient and its lags.  Its first lane alone is a data lane -- dr_l,
+// its column of the table, xw = x_t there; the lag lanes weigh 0 in zdr -- and wave 1's PZ takes the row of
+// its first component alone, weighed by x_t.  Everything else is the autoregression's: T and T' with the
+// lane's phi, one state-error normal per step whatever sigma, `lags` normals of the initial state, the
+// ArModel statistics, ar_draw ahead of the state draw with the AR family's sampler id.  drlev() below is
+// "a dynamic regression whose components are levels", the test the plain form's sites make.
 template <int LDC, bool GLOB, SsgVariant V>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void ssg_simsmooth_kernel(SsParams P, int draw_variances) {
   constexpr bool SMALL = LDC == 17;
@@ -310,6 +317,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
     for (int i = lane; i < nstep * ND; i += WAVE) sdyn[i] = g[i];
     wave_lds_sync();
   };
+  // (DR) the block's word says: a dynamic regression of levels (the plain form; not an autoregression with a row of data)
+  auto drlev = [](unsigned d) -> bool { return Blocks::dynreg_of(d) && Blocks::kind_of(d) == SSG_LOCAL_LEVEL; };
   LaneInfo LI{-1, 0, 0, 0, 0, 0.0};
   // (HD) lane b: block b is a calendar seasonal; calmask: bit b the same, wave-uniform
   const bool cals_l = HD && lane < nb && ssg_is_calendar(Q.blk[lane]);
@@ -370,7 +379,12 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       const bool mine = lane >= f && lane < f + n;
       const bool hol = HD && Blocks::holiday_of(d);
       if (HD && mine && hol) { hol_l = true; hsh_l = 8 * b; }
-      if (DR && Blocks::dynreg_of(d)) {
+      // (an autoregression with a row of data: its first lane reads the block's column; the rest is kind 4's, below)
+      if (DR && Blocks::dynreg_of(d) && kd == SSG_AR) {
+        const int c0 = __builtin_amdgcn_readlane(dc0_l, b);
+        if (lane == f) { dr_l = true; dcol_l = c0; }
+      }
+      if (DR && drlev(d)) {
         // a dynamic regression: every component a level with a variance, an error row, a state-error normal
         // at every step and a normal of the initial state (rmvn_mt) of its own
         if (mine) {
@@ -568,7 +582,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
             }
             if (DR && Blocks::dynreg_of(B.udesc(b))) {   // (the block's rows, weighed by x_t, in component order)
               const double *xr = sdyn + s * ND + __builtin_amdgcn_readlane(dc0_l, b);
-              const int n = Blocks::dim_of(B.udesc(b));
+              const int n = drlev(B.udesc(b)) ? Blocks::dim_of(B.udesc(b)) : 1;   // (an autoregression: row `first` alone)
 #pragma nounroll
               for (int i = 0; i < n; ++i)
                 if (mylane) PZ += xr[i] * s_P[(zl + i) * ld + lane];
@@ -589,7 +603,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
             }
             if (DR && Blocks::dynreg_of(B.udesc(b))) {
               const double *xr = sdyn + s * ND + __builtin_amdgcn_readlane(dc0_l, b);
-              const int n = Blocks::dim_of(B.udesc(b));
+              const int n = drlev(B.udesc(b)) ? Blocks::dim_of(B.udesc(b)) : 1;
               double acc = 0.0;
 #pragma nounroll
               for (int i = 0; i < n; ++i)
@@ -644,7 +658,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
             }
             const int kn = hpos_b(cn, b);
             if (!(kn & SSG_CAL_OFF) && lane == f + kn) col[kn * ld] += s_sig2[Blocks::var0_of(d)];
-          } else if (DR && Blocks::dynreg_of(d)) {
+          } else if (DR && drlev(d)) {
             // every component a level: the rank-one term, + sigma_i^2 on its own diagonal entry
             const int v0 = Blocks::var0_of(d);
 #pragma nounroll
@@ -1270,7 +1284,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
         M.var_n[at] = cnt;
         M.var_ss[at] = tot;
       }
-    } else if (DR && Blocks::dynreg_of(d)) {
+    } else if (DR && drlev(d)) {
       // (a slot per coefficient: its own lane's sum, in time order)
       if (LI.blk == b) {
         M.var_n[at + (lane - f)] = (double)(T - 1);

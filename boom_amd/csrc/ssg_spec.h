@@ -66,9 +66,11 @@ inline const SsgKind *ssg_dynreg_row(int32_t d) {
   return &rows[d];
 }
 // the dynamic coefficients of the first `upto` blocks of a list (all: the columns of its predictor table)
+// (a block of an AR dynamic regression -- stored kind SSG_AR -- holds one coefficient and its lags: one column)
+inline int32_t ssg_dyn_width(const SsgBlock &k) { return !k.dynreg ? 0 : (k.kind == SSG_AR ? 1 : k.dim); }
 inline int32_t ssg_dyn_columns(const SsgSpec &q, int upto = SSG_MAX_BLOCKS) {
   int32_t n = 0;
-  for (int i = 0; i < q.nblocks && i < upto; ++i) n += q.blk[i].dynreg ? q.blk[i].dim : 0;
+  for (int i = 0; i < q.nblocks && i < upto; ++i) n += ssg_dyn_width(q.blk[i]);
   return n;
 }
 // the C-ABI kind block i of a list was appended as (the one place that reads the marks back)
@@ -76,14 +78,16 @@ inline int32_t ssg_abi_kind(const SsgSpec &q, int i) {
   const SsgBlock &k = q.blk[i];
   if (i == q.student_block - 1) return SSG_STUDENT_TREND;
   if (k.holiday) return SSG_HOLIDAY;
-  if (k.dynreg) return SSG_DYNAMIC_REGRESSION;
+  if (k.dynreg) return k.kind == SSG_AR ? (int32_t)SSG_DYNAMIC_REGRESSION_AR : (int32_t)SSG_DYNAMIC_REGRESSION;
   if (k.ar_spike) return SSG_AUTO_AR;
   if (ssg_is_calendar(k)) return SSG_CALENDAR_SEASONAL;
   if (k.kind == SSG_LOCAL_LEVEL && k.nvar == 0) return SSG_STATIC_INTERCEPT;
   return k.kind;
 }
+// (a block of an AR dynamic regression: an autoregression's row -- slot, family and sampler id are kind 4's)
 inline const SsgKind &ssg_row_of(const SsgSpec &q, int i) {
-  return q.blk[i].dynreg ? *ssg_dynreg_row(q.blk[i].dim) : *ssg_kind_row(ssg_abi_kind(q, i));
+  if (q.blk[i].dynreg) return q.blk[i].kind == SSG_AR ? *ssg_kind_row(SSG_AR) : *ssg_dynreg_row(q.blk[i].dim);
+  return *ssg_kind_row(ssg_abi_kind(q, i));
 }
 
 // ---- what a list holds ---------------------------------------------------------------------
@@ -168,7 +172,7 @@ inline const char *ssg_refusal(const SsgSpec *q, SsFamily family, SsgUse use, in
         return other ? only_gaussian[2] : (has(SSG_HAS_STUDENT_TREND) ? holiday_student : (has(SSG_HAS_DYNREG) ? dynreg_holiday : nullptr));
       if (kind == SSG_CALENDAR_SEASONAL)
         return other ? only_gaussian[3] : (has(SSG_HAS_STUDENT_TREND) ? calseas_student : (has(SSG_HAS_DYNREG) ? dynreg_calseas : nullptr));
-      if (kind == SSG_DYNAMIC_REGRESSION) {   // (ssg_append_dynreg's)
+      if (kind == SSG_DYNAMIC_REGRESSION || kind == SSG_DYNAMIC_REGRESSION_AR) {   // (ssg_append_dynreg's, ssg_append_dynreg_ar's)
         if (other) return only_gaussian[4];
         if (has(SSG_HAS_STUDENT_TREND)) return dynreg_student;
         if (has(SSG_HAS_HOLIDAY)) return dynreg_holiday;
@@ -498,6 +502,49 @@ inline SsgRefusal ssg_append_dynreg(SsgSpec &q, SsgInitial I, SsFamily family, i
   k.dynreg = 1 + ssg_dyn_columns(q);
   return ssg_append_tail(q, I, SSG_DYNAMIC_REGRESSION, ssg_dynreg_row(d), k, ArSpikePrior{}, A);
 }
+// DynamicRegressionArStateModel(X, lags) + DynamicRegressionArPosteriorSampler on a specification
+// (ba_ss_add_dynamic_regression_ar): xdim consecutive blocks of stored kind SSG_AR and dimension lags, one per
+// coefficient -- block i's first component is the coefficient, observed through column i of the model's
+// predictors (SsgBlock::dynreg), the others are its lags -- each with what an autoregression (kind 4) has: an
+// autoregression slot, a variance slot, a state-error row, the AR family's sampler id.  The var_* arrays
+// hold xdim entries (an initial sigma is positive, as kind 4's), initial_phi (nullptr: zeros; every row stationary), initial_state_mean and
+// initial_state_variance xdim x lags.  Limits: 1 <= lags <= AR_MAX, 1 <= xdim, and the list's: SSG_MAX_AR
+// autoregression slots (so xdim <= 4), SSG_MAX_BLOCKS blocks, state dimension 64, 16 variance slots.
+// All xdim blocks are appended, or none.
+inline SsgRefusal ssg_append_dynreg_ar(SsgSpec &q, SsgInitial I, SsFamily family, int32_t xdim, int32_t lags, const SsgModelArgs &A) {
+  auto invalid = [](const char *text) { return SsgRefusal{BA_E_INVALID, text}; };
+  if (!A.var_df || !A.var_sigma_guess || !A.var_sigma_upper_limit || !A.var_initial_sigma || !A.initial_state_mean ||
+      !A.initial_state_variance)
+    return invalid("null argument");
+  if (xdim < 1) return invalid("a dynamic regression needs at least one predictor");
+  if (lags < 1) return invalid("lags must be positive");
+  if (lags > AR_MAX) return invalid("more than 16 lags");
+  if (q.nblocks + (int64_t)xdim > SSG_MAX_BLOCKS) return invalid("more than 8 state models");
+  if (q.nar + (int64_t)xdim > SSG_MAX_AR) return invalid("more than 4 autoregression state models");
+  if (q.m + (int64_t)xdim * lags > SSG_MAX_STATE) return invalid("state dimension exceeds 64");
+  if (const char *refused = ssg_refusal(&q, family, SSG_USE_APPEND, SSG_DYNAMIC_REGRESSION_AR)) return {BA_E_STATE, refused};
+  const SsgSpec before = q;
+  const double zeros[AR_MAX] = {};
+  for (int i = 0; i < xdim; ++i) {
+    SsgBlock k{};
+    k.kind = SSG_AR;
+    k.nvar = 1;
+    k.duration = 1;
+    k.ar_index = q.nar;
+    k.lags = lags;
+    k.dim = lags;
+    k.dynreg = 1 + ssg_dyn_columns(q);
+    const SsgModelArgs Ai{nullptr, A.var_df + i, A.var_sigma_guess + i, A.var_sigma_upper_limit + i, A.var_initial_sigma + i,
+                          A.initial_phi ? A.initial_phi + (size_t)i * lags : zeros, A.initial_state_mean + (size_t)i * lags,
+                          A.initial_state_variance + (size_t)i * lags};
+    const SsgRefusal r = ssg_append_tail(q, I, SSG_AR, ssg_kind_row(SSG_AR), k, ArSpikePrior{}, Ai);
+    if (r.text) {
+      q = before;
+      return r;
+    }
+  }
+  return {BA_OK, nullptr};
+}
 // the predictors of a dynamic regression, rows x xdim row-major: the first entry that is not finite, or -1
 inline int64_t ssg_dyn_check(const double *predictors, int64_t rows, int32_t xdim) {
   for (int64_t i = 0; i < rows * (int64_t)xdim; ++i)
@@ -509,7 +556,7 @@ inline int64_t ssg_dyn_rows(const SsgSpec &q, const std::vector<double> *predict
   int64_t rows = -1;
   for (int b = 0; b < q.nblocks; ++b) {
     if (!q.blk[b].dynreg) continue;
-    const int64_t n = (int64_t)predictors[b].size() / q.blk[b].dim;
+    const int64_t n = (int64_t)predictors[b].size() / ssg_dyn_width(q.blk[b]);
     rows = rows < 0 ? n : std::min(rows, n);
   }
   return rows;
@@ -520,7 +567,7 @@ inline std::vector<double> ssg_pack_predictors(const SsgSpec &q, const std::vect
   std::vector<double> table((size_t)rows * (size_t)cols, 0.0);
   for (int b = 0; b < q.nblocks; ++b) {
     if (!q.blk[b].dynreg) continue;
-    const int c0 = q.blk[b].dynreg - 1, d = q.blk[b].dim;
+    const int c0 = q.blk[b].dynreg - 1, d = ssg_dyn_width(q.blk[b]);
     for (int64_t t = 0; t < rows; ++t)
       for (int i = 0; i < d; ++i) table[(size_t)t * cols + c0 + i] = predictors[b][(size_t)t * d + i];
   }

@@ -452,6 +452,33 @@ PYBIND11_MODULE(_boom, boom) {
       .def("set_prior", &DynamicRegressionStateModel::set_prior, py::arg("coefficient"), py::arg("df"), py::arg("sigma_guess"),
            py::arg("sigma_upper_limit") = std::numeric_limits<double>::infinity());
 
+  py::class_<DynamicRegressionArStateModel, Ptr<DynamicRegressionArStateModel>>(
+      boom, "DynamicRegressionArStateModel",
+      "DynamicRegressionArStateModel(predictors, lags): regression coefficients that each follow an autoregression "
+      "of `lags` lags.  predictors: rows x d, row t = x_t; rows past the length of the series serve forecasts.  "
+      "Per coefficient one ArModel (phi, sigma) with a ChisqModel(df, sigma_guess) prior and sigma upper limit.  "
+      "The arrays over the state (initial mean and variance, phi) are d x lags.")
+      .def(py::init([](const NpArray &predictors, int lags) { return new DynamicRegressionArStateModel(matrix_from(predictors), lags); }),
+           py::arg("predictors"), py::arg("lags"))
+      .def_property_readonly("state_dimension", &DynamicRegressionArStateModel::state_dimension)
+      .def_property_readonly("xdim", &DynamicRegressionArStateModel::xdim)
+      .def_property_readonly("lags", &DynamicRegressionArStateModel::lags)
+      .def_property_readonly("predictors", [](const DynamicRegressionArStateModel &m) {
+        py::array_t<double> out({m.rows(), m.xdim()});
+        std::copy(m.predictors().begin(), m.predictors().end(), out.mutable_data());
+        return out;
+      })
+      .def("set_sigsq", [](DynamicRegressionArStateModel &m, const NpArray &v) { m.set_sigsq(vector_from(v)); },
+           "the coefficients' innovation variances")
+      .def("set_phi", [](DynamicRegressionArStateModel &m, const NpArray &v) { m.set_phi(vector_from(v)); },
+           "the autoregressions' initial coefficients, d x lags (row-major), every row stationary")
+      .def("set_initial_state_mean", [](DynamicRegressionArStateModel &m, const NpArray &v) { m.set_initial_state_mean(vector_from(v)); })
+      .def("set_initial_state_variance",
+           [](DynamicRegressionArStateModel &m, const NpArray &v) { m.set_initial_state_variance(vector_from(v)); },
+           "the diagonal of the initial state's variance")
+      .def("set_prior", &DynamicRegressionArStateModel::set_prior, py::arg("coefficient"), py::arg("df"), py::arg("sigma_guess"),
+           py::arg("sigma_upper_limit") = std::numeric_limits<double>::infinity());
+
   py::class_<MonthlyAnnualCycle, Ptr<MonthlyAnnualCycle>>(
       boom, "MonthlyAnnualCycle",
       "MonthlyAnnualCycle(year, month, day): a month-of-year effect for daily data, 12 seasons that start on the "
@@ -569,6 +596,7 @@ PYBIND11_MODULE(_boom, boom) {
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<StudentLocalLinearTrendStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<RandomWalkHolidayStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<DynamicRegressionStateModel> &s) { m.add_state(s); })
+      .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<DynamicRegressionArStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<RegressionHolidayStateModel> &s) { m.add_state(s); })
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<HierarchicalRegressionHolidayStateModel> &s) { m.add_state(s); })
       .def("regression_holiday_coefficients", [](const StateSpaceRegressionModel &m, int chain, int which) {
@@ -590,6 +618,10 @@ PYBIND11_MODULE(_boom, boom) {
            py::arg("chain") = 0, py::arg("which") = 0,
            "(AR(1) coefficient, long-run mean) of the which-th SemilocalLinearTrendStateModel's slope in one chain's draw")
       .def_property_readonly("number_of_state_models", &StateSpaceRegressionModel::number_of_state_models)
+      .def("dynamic_regression_ar_phi",
+           [](const StateSpaceRegressionModel &m, int chain, int which) { return matrix_to_numpy(m.dynamic_regression_ar_phi(chain, which)); },
+           py::arg("chain") = 0, py::arg("which") = 0,
+           "the autoregression coefficients of the which-th DynamicRegressionArStateModel in one chain's current draw, d x lags")
       .def("ar_phi", [](const StateSpaceRegressionModel &m, int chain, int which) { return to_numpy(m.ar_phi(chain, which)); },
            py::arg("chain") = 0, py::arg("which") = 0,
            "the coefficients of the which-th ArStateModel in one chain's current draw")

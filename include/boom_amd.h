@@ -851,11 +851,42 @@ int ba_monthly_cycle_calendar(int32_t year, int32_t month, int32_t day, int64_t 
  * state draw the block takes xdim stream-2 normals for the initial state and xdim per step, whatever
  * the sigmas.  Refused with a text, in either order of the calls: the Student-t / Poisson / logit
  * observation families; a list that also holds a Student local linear trend (kind 8), a random-walk
- * holiday (kind 10) or a calendar seasonal (kind 11).  Not built: the hierarchical and the AR forms. */
+ * holiday (kind 10) or a calendar seasonal (kind 11).  The AR form is ba_ss_add_dynamic_regression_ar
+ * below.  Not built: the hierarchical form (bsts does not reach it either). */
 int ba_ss_add_dynamic_regression(ba_engine *e, int32_t xdim, const double *predictors, int64_t rows,
                                  const double *var_df, const double *var_sigma_guess,
                                  const double *var_sigma_upper_limit, const double *var_initial_sigma,
                                  const double *initial_state_mean, const double *initial_state_variance);
+/* DynamicRegressionArStateModel(X, lags) + DynamicRegressionArPosteriorSampler, bsts AddDynamicRegression
+ * with DynamicRegressionArOptions(lags) (StateModels/DynamicRegressionArStateModel.cpp,
+ * PosteriorSamplers/DynamicRegressionArPosteriorSampler.cpp): every coefficient follows an autoregression
+ * of `lags` lags, beta_{t+1,i} = phi_i' (beta_{t,i}, .., beta_{t-lags+1,i}) + N(0, sigma_i^2), and
+ * Z_t = x_{t,i} at coefficient i's current value, 0 at its lags.  The call appends xdim consecutive state
+ * models, one per coefficient, each of dimension `lags` and each in everything but its observation row
+ * an autoregression (kind 4): ArModel statistics add_mixture_data(now[0], then, 1), ArPosteriorSampler's
+ * draw (draw_phi with 3 multivariate proposals and the univariate fallback, then draw_sigma), the
+ * initial state StateModelBase::simulate_initial_state's.  *first_block_out (may be NULL) = the index
+ * of the model's first block; block first + i is coefficient i.  All xdim blocks are appended, or none.
+ * predictors: rows x xdim row-major, finite.  var_df, var_sigma_guess, var_sigma_upper_limit,
+ * var_initial_sigma: xdim entries (an initial sigma must be positive, as kind 4's).  initial_phi: xdim x lags row-major, every row stationary (NULL: zeros).
+ * initial_state_mean, initial_state_variance: xdim x lags (bsts: 0 and 1); variances positive.
+ * Limits: 1 <= lags <= 16, 1 <= xdim, and those of the list: 4 autoregression slots (each coefficient
+ * takes one, so xdim <= 4 less the list's other autoregressions and semilocal trends), 8 state models,
+ * state dimension 64, 16 variance parameters.
+ * ba_ss_set_dynamic_predictors / ba_ss_get_dynamic_predictors on the model's FIRST block set and return
+ * all xdim columns (rows x xdim); on another block of the model they refuse with a text.
+ * ba_ss_get_state_model, ba_ss_get_state_draw and ba_ss_state_dimension serve each block as they serve
+ * kind 4 (phi, the ArModel statistics, one variance).  Rows needed: as for ba_ss_add_dynamic_regression.
+ * RNG: block by block the AR family's sampler id (12 + 16 per earlier autoregression of the list), read
+ * in sequence as kind 4 reads it; in the state draw each block takes `lags` stream-2 normals for the
+ * initial state and one per step.  Refusals as for ba_ss_add_dynamic_regression, in either order of the
+ * calls; a plain dynamic regression in the same list is allowed (they share the predictor table by
+ * column).  The look-ahead, ba_ss_forecast and ba_ss_prediction_errors serve the model. */
+int ba_ss_add_dynamic_regression_ar(ba_engine *e, int32_t xdim, int32_t lags, const double *predictors, int64_t rows,
+                                    const double *var_df, const double *var_sigma_guess,
+                                    const double *var_sigma_upper_limit, const double *var_initial_sigma,
+                                    const double *initial_phi, const double *initial_state_mean,
+                                    const double *initial_state_variance, int32_t *first_block_out);
 int ba_ss_set_dynamic_predictors(ba_engine *e, int32_t block, const double *predictors, int64_t rows);
 int ba_ss_get_dynamic_predictors(ba_engine *e, int32_t block, double *predictors, int64_t *rows);
 

@@ -529,6 +529,50 @@ class DynamicRegressionStateModel {
   Vector x_, a0_, P0_, sigma_, df_, guess_, upper_;
 };
 
+// DynamicRegressionArStateModel(X, lags) with a DynamicRegressionArPosteriorSampler (StateModels/
+// DynamicRegressionArStateModel.cpp; bsts AddDynamicRegression with DynamicRegressionArOptions(lags)):
+// ba_ss_add_dynamic_regression_ar.  Every coefficient follows an autoregression of `lags` lags with its own
+// ArModel (phi, sigma) and ArPosteriorSampler.  The state holds, coefficient by coefficient, the coefficient
+// and its lags: state_dimension() = xdim x lags.  On the device the model is xdim state models of the list,
+// one per coefficient (at most 4 less the list's other autoregressions and semilocal trends).  The arrays
+// that run over the state -- initial mean and variance, the coefficients phi -- are xdim x lags, row-major.
+class DynamicRegressionArStateModel {
+ public:
+  DynamicRegressionArStateModel(const Matrix &predictors, int lags) : xdim_(predictors.ncol()), rows_(predictors.nrow()), lags_(lags) {
+    if (xdim_ < 1 || rows_ < 1) report_error("a dynamic regression needs at least one row and one column of predictors");
+    if (lags_ < 1) report_error("lags must be positive");
+    x_.resize((size_t)rows_ * xdim_);   // (row-major, as the C-ABI takes them)
+    for (int t = 0; t < rows_; ++t)
+      for (int i = 0; i < xdim_; ++i) x_[(size_t)t * xdim_ + i] = predictors(t, i);
+    a0_ = Vector(xdim_ * lags_, 0.0);   // (bsts: mean 0, variance 1)
+    P0_ = Vector(xdim_ * lags_, 1.0);
+    phi_ = Vector(xdim_ * lags_, 0.0);
+    sigma_ = Vector(xdim_, 1.0);
+    df_ = Vector(xdim_, 1.0);
+    guess_ = Vector(xdim_, 1.0);
+    upper_ = Vector(xdim_, infinity());
+  }
+  int state_dimension() const { return xdim_ * lags_; }
+  int xdim() const { return xdim_; }
+  int lags() const { return lags_; }
+  int rows() const { return rows_; }
+  const Vector &predictors() const { return x_; }   // rows x xdim, row-major
+  void set_sigsq(const Vector &s) { check_size(s, xdim_); for (int i = 0; i < xdim_; ++i) sigma_[i] = std::sqrt(s[i]); }
+  void set_phi(const Vector &phi) { check_size(phi, xdim_ * lags_); phi_ = phi; }
+  void set_initial_state_mean(const Vector &m) { check_size(m, xdim_ * lags_); a0_ = m; }
+  void set_initial_state_variance(const Vector &diagonal) { check_size(diagonal, xdim_ * lags_); P0_ = diagonal; }
+  // coefficient i's ChisqModel(df, sigma_guess) and sigma upper limit
+  void set_prior(int i, double df, double sigma_guess, double sigma_upper_limit = infinity()) {
+    if (i < 0 || i >= xdim_) report_error("coefficient index out of range");
+    df_[i] = df; guess_[i] = sigma_guess; upper_[i] = sigma_upper_limit;
+  }
+  void check_size(const Vector &v, int n) const {
+    if ((int)v.size() != n) report_error("an AR dynamic regression takes one entry per predictor, or per predictor and lag");
+  }
+  int xdim_, rows_, lags_;
+  Vector x_, a0_, P0_, phi_, sigma_, df_, guess_, upper_;
+};
+
 // RegressionHolidayStateModel with its own sample_posterior (StateModels/RegressionHolidayStateModel.cpp;
 // bsts AddRegressionHoliday): ba_ss_add_regression_holiday.  One coefficient per day of each holiday's
 // window, shared across the years, all under the prior N(prior_mean, prior_sd^2).  There is no Date /
@@ -795,6 +839,7 @@ class StateSpaceRegressionModel : public Model {
   void add_state(const Ptr<RandomWalkHolidayStateModel> &s) { Entry e; e.kind = 10; e.holiday = s; models_.push_back(e); finalized_ = false; }
   void add_state(const Ptr<MonthlyAnnualCycle> &s) { Entry e; e.kind = 11; e.monthly = s; models_.push_back(e); finalized_ = false; }
   void add_state(const Ptr<DynamicRegressionStateModel> &s) { Entry e; e.kind = 12; e.dynreg = s; models_.push_back(e); finalized_ = false; }
+  void add_state(const Ptr<DynamicRegressionArStateModel> &s) { Entry e; e.kind = 14; e.dynreg_ar = s; models_.push_back(e); finalized_ = false; }
   // (no block of the state: the engine numbers the regression holiday models on their own)
   void add_state(const Ptr<RegressionHolidayStateModel> &s) { reg_holidays_.push_back(s); hier_holidays_.push_back(nullptr); finalized_ = false; }
   // (a hierarchical one takes a place among them: reg_holidays_[k] is null where hier_holidays_[k] is not)
@@ -813,7 +858,7 @@ class StateSpaceRegressionModel : public Model {
     for (const Entry &e : models_)
       m += (e.kind == 1 || e.kind == 5) ? 1 : (e.kind == 2 || e.kind == 8) ? 2 : e.kind == 3 ? e.seasonal->state_dimension()
            : e.kind == 6 ? e.trig->state_dimension() : e.kind == 7 ? 3 : e.kind == 10 ? e.holiday->state_dimension() : e.kind == 11 ? e.monthly->state_dimension()
-           : e.kind == 12 ? e.dynreg->state_dimension() : e.ar->lags_;
+           : e.kind == 12 ? e.dynreg->state_dimension() : e.kind == 14 ? e.dynreg_ar->state_dimension() : e.ar->lags_;
     return m;
   }
   void finalize_state() {
@@ -831,17 +876,21 @@ class StateSpaceRegressionModel : public Model {
           const RandomWalkHolidayStateModel &s = *e.holiday;
           const int32_t ip[3] = {s.width_, 0, 0};
           eng_->check(ba_ss_add_state_model(h, 10, ip, &s.df_, &s.guess_, &s.upper_, &s.sigma_, nullptr, s.a0_.data(), s.P0_.data()));
-          eng_->check(ba_ss_set_holiday_calendar(h, (int32_t)b, s.positions_.data(), (int64_t)s.positions_.size()));
+          eng_->check(ba_ss_set_holiday_calendar(h, engine_block(b), s.positions_.data(), (int64_t)s.positions_.size()));
         } else if (e.kind == 12) {
           const DynamicRegressionStateModel &s = *e.dynreg;
           eng_->check(ba_ss_add_dynamic_regression(h, s.xdim_, s.x_.data(), s.rows_, s.df_.data(), s.guess_.data(), s.upper_.data(),
                                                    s.sigma_.data(), s.a0_.data(), s.P0_.data()));
+        } else if (e.kind == 14) {
+          const DynamicRegressionArStateModel &s = *e.dynreg_ar;
+          eng_->check(ba_ss_add_dynamic_regression_ar(h, s.xdim_, s.lags_, s.x_.data(), s.rows_, s.df_.data(), s.guess_.data(), s.upper_.data(),
+                                                      s.sigma_.data(), s.phi_.data(), s.a0_.data(), s.P0_.data(), nullptr));
         } else if (e.kind == 11) {
           const MonthlyAnnualCycle &s = *e.monthly;
           const int32_t ip[3] = {s.nseasons(), 0, 0};
           const std::vector<uint8_t> flags = s.calendar(T_);
           eng_->check(ba_ss_add_state_model(h, 11, ip, &s.df_, &s.guess_, &s.upper_, &s.sigma_, nullptr, s.a0_.data(), s.P0_.data()));
-          eng_->check(ba_ss_set_season_calendar(h, (int32_t)b, flags.data(), (int64_t)flags.size()));
+          eng_->check(ba_ss_set_season_calendar(h, engine_block(b), flags.data(), (int64_t)flags.size()));
         } else if (e.kind == 1) {
           const LocalLevelStateModel &s = *e.level;
           eng_->check(ba_ss_add_state_model(h, 1, nullptr, &s.df_, &s.guess_, &s.upper_, &s.sigma_, nullptr, &s.a0_, &s.P0_));
@@ -923,19 +972,37 @@ class StateSpaceRegressionModel : public Model {
   Vector ar_phi(int chain = 0, int which = 0) const {
     const int b = ar_block(which);
     Vector v(models_[b].ar->lags_);
-    eng_->check(ba_ss_get_state_model(eng_->get(), chain, b, nullptr, nullptr, nullptr, v.data(), nullptr, nullptr, nullptr, nullptr));
+    eng_->check(ba_ss_get_state_model(eng_->get(), chain, engine_block(b), nullptr, nullptr, nullptr, v.data(), nullptr, nullptr, nullptr, nullptr));
     return v;
+  }
+  // the coefficients of the `which`-th DynamicRegressionArStateModel's autoregressions in one chain's current
+  // draw: xdim x lags, row i = coefficient i's phi (their error variances: state_variances)
+  Matrix dynamic_regression_ar_phi(int chain = 0, int which = 0) const {
+    int seen = 0;
+    for (size_t b = 0; b < models_.size(); ++b) {
+      if (models_[b].kind != 14 || seen++ != which) continue;
+      const DynamicRegressionArStateModel &s = *models_[b].dynreg_ar;
+      Matrix phi(s.xdim_, s.lags_);
+      Vector v(s.lags_);
+      for (int i = 0; i < s.xdim_; ++i) {
+        eng_->check(ba_ss_get_state_model(eng_->get(), chain, engine_block(b) + i, nullptr, nullptr, nullptr, v.data(), nullptr, nullptr, nullptr, nullptr));
+        for (int j = 0; j < s.lags_; ++j) phi(i, j) = v[j];
+      }
+      return phi;
+    }
+    report_error("The model has no such DynamicRegressionArStateModel.");
+    return Matrix();
   }
   // the inclusion indicators of the `which`-th ArStateModel (one with set_spike_slab_prior) in one chain
   std::vector<bool> ar_inclusion(int chain = 0, int which = 0) const {
     const int b = ar_block(which);
     std::vector<uint8_t> g(models_[b].ar->lags_);
-    eng_->check(ba_ss_get_ar_inclusion(eng_->get(), chain, b, g.data()));
+    eng_->check(ba_ss_get_ar_inclusion(eng_->get(), chain, engine_block(b), g.data()));
     return std::vector<bool>(g.begin(), g.end());
   }
   double ar_sigsq(int chain = 0, int which = 0) const {
     double s2;
-    eng_->check(ba_ss_get_state_model(eng_->get(), chain, ar_block(which), &s2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    eng_->check(ba_ss_get_state_model(eng_->get(), chain, engine_block(ar_block(which)), &s2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
     return s2;
   }
   // the slope model of the `which`-th SemilocalLinearTrendStateModel in one chain's current draw:
@@ -945,7 +1012,7 @@ class StateSpaceRegressionModel : public Model {
     for (size_t b = 0; b < models_.size(); ++b) {
       if (models_[b].kind != 7 || seen++ != which) continue;
       Vector v(2);
-      eng_->check(ba_ss_get_state_model(eng_->get(), chain, (int32_t)b, nullptr, nullptr, nullptr, v.data(), nullptr, nullptr, nullptr, nullptr));
+      eng_->check(ba_ss_get_state_model(eng_->get(), chain, engine_block(b), nullptr, nullptr, nullptr, v.data(), nullptr, nullptr, nullptr, nullptr));
       return v;
     }
     report_error("The model has no such SemilocalLinearTrendStateModel.");
@@ -955,7 +1022,7 @@ class StateSpaceRegressionModel : public Model {
   // weights, 2 x time_dimension (row 0 the level's, row 1 the slope's)
   Vector student_trend_nu(int chain = 0) const {
     Vector v(2);
-    eng_->check(ba_ss_get_state_model(eng_->get(), chain, student_trend_block(), nullptr, nullptr, nullptr, v.data(), nullptr, nullptr, nullptr, nullptr));
+    eng_->check(ba_ss_get_state_model(eng_->get(), chain, engine_block(student_trend_block()), nullptr, nullptr, nullptr, v.data(), nullptr, nullptr, nullptr, nullptr));
     return v;
   }
   Matrix student_trend_weights(int chain = 0) const {
@@ -983,7 +1050,14 @@ class StateSpaceRegressionModel : public Model {
     for (size_t b = 0; b < models_.size(); ++b) {
       if (models_[b].kind == 5) continue;
       double v[16] = {0, 0};   // (a dynamic regression: one per coefficient, at most the list's 16 slots)
-      eng_->check(ba_ss_get_state_model(eng_->get(), chain, (int32_t)b, v, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+      if (models_[b].kind == 14) {   // (an AR dynamic regression: a state model of the engine's list per coefficient)
+        for (int i = 0; i < models_[b].dynreg_ar->xdim(); ++i) {
+          eng_->check(ba_ss_get_state_model(eng_->get(), chain, engine_block(b) + i, v, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+          out.push_back(v[0]);
+        }
+        continue;
+      }
+      eng_->check(ba_ss_get_state_model(eng_->get(), chain, engine_block(b), v, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
       out.push_back(v[0]);
       if (models_[b].kind == 12)
         for (int i = 1; i < models_[b].dynreg->xdim(); ++i) out.push_back(v[i]);
@@ -1061,7 +1135,7 @@ class StateSpaceRegressionModel : public Model {
   }
  private:
   struct Entry {
-    int kind = 0;   // 1 local level, 2 local linear trend, 3 seasonal, 4 autoregression, 5 static intercept, 6 trig, 7 semilocal linear trend, 8 Student local linear trend, 10 random-walk holiday, 11 monthly annual cycle (a calendar seasonal), 12 dynamic regression
+    int kind = 0;   // 1 local level, 2 local linear trend, 3 seasonal, 4 autoregression, 5 static intercept, 6 trig, 7 semilocal linear trend, 8 Student local linear trend, 10 random-walk holiday, 11 monthly annual cycle (a calendar seasonal), 12 dynamic regression, 14 AR dynamic regression
     Ptr<LocalLevelStateModel> level;
     Ptr<LocalLinearTrendStateModel> trend;
     Ptr<SeasonalStateModel> seasonal;
@@ -1072,8 +1146,15 @@ class StateSpaceRegressionModel : public Model {
     Ptr<StudentLocalLinearTrendStateModel> student_trend;
     Ptr<RandomWalkHolidayStateModel> holiday;
     Ptr<DynamicRegressionStateModel> dynreg;
+    Ptr<DynamicRegressionArStateModel> dynreg_ar;
     Ptr<MonthlyAnnualCycle> monthly;
   };
+  // the index of model b's (first) state model in the engine's list: an AR dynamic regression is one per coefficient
+  int32_t engine_block(size_t b) const {
+    int32_t at = 0;
+    for (size_t i = 0; i < b && i < models_.size(); ++i) at += models_[i].kind == 14 ? models_[i].dynreg_ar->xdim() : 1;
+    return at;
+  }
   int student_trend_block() const {
     for (size_t b = 0; b < models_.size(); ++b)
       if (models_[b].kind == 8) return (int)b;
