@@ -207,6 +207,7 @@ SIGNATURES = {
     "ba_ss_set_hierarchical_regression_holiday": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp]),
     "ba_ss_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
     "ba_ss_prediction_errors": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp]),
+    "ba_ss_holdout_prediction_errors": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
     "ba_ss_student_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
     "ba_ss_poisson_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp]),
     "ba_ss_logit_forecast": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp]),
@@ -1291,6 +1292,31 @@ class Engine:
         if log_likelihood:
             out["log_likelihood"] = ll
         return out
+
+    def ss_holdout_prediction_errors(self, newX, newY, standardize=False, chains=None, variances=False):
+        """bsts.prediction.errors' holdout part for every chain's current draw: the one-step prediction
+        errors of the len(newY) rows (newX: len(newY) x p; None where p = 0) that follow the series, from the
+        chain's drawn final state.  chains as in ss_prediction_errors; chains x horizon, or with variances a
+        dict of errors and variances (F_i, the same shape)"""
+        if chains is None:
+            first, count = 0, self.chains
+        elif isinstance(chains, range):
+            if chains.step != 1:
+                raise ValueError("chains: a contiguous range")
+            first, count = chains.start, len(chains)
+        else:
+            first, count = (int(v) for v in chains)
+        newY = _f64(newY).ravel()
+        h = newY.shape[0]
+        nx = None
+        if newX is not None and np.size(newX) > 0:
+            nx = _fcol(np.asarray(newX, dtype=np.float64).reshape(h, -1))
+        rows = max(count, 0)
+        err = np.zeros((rows, h))
+        var = np.zeros((rows, h)) if variances else None
+        self._check(self.lib.ba_ss_holdout_prediction_errors(self._h, first, count, 1 if standardize else 0, h,
+                                                             _p(nx), _p(newY), _p(err), _p(var)))
+        return dict(errors=err, variances=var) if variances else err
 
     def ss_get_state(self, chain, state=True, suf=True):
         """state=False / suf=False: do not ask for the state path / the level model's

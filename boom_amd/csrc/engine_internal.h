@@ -516,6 +516,8 @@ struct ba_engine {
   DevBuf<int32_t> dssf_flag;
   DevBuf<uint8_t> dssf_spec;
   hipStream_t ssf_stream = nullptr;
+  // ba_ss_holdout_prediction_errors: the caller's holdout rows on the device (the outputs are the arrays above)
+  DevBuf<double> dssf_newx, dssf_newy;
   // ---- look-ahead on the bsts path (ba_ss_set_lookahead / ba_ss_draw_next): a batch of
   // `len` sweep rounds per enqueue, every round's draw recorded on the device -- gamma,
   // beta, sigma^2, the state models' variances and coefficients for EVERY chain, the

@@ -171,6 +171,114 @@ int ba_ss_prediction_errors(ba_engine *e, int64_t chain_first, int64_t chain_cou
   return BA_OK;
 }
 
+// One-step prediction errors of `horizon` rows behind the series (bsts.prediction.errors; the holdout
+// instance of ss_filter_kernel.hip): from every chain's drawn final state, at the live parameters.  It enters
+// as ba_ss_forecast does -- a look-ahead is settled to the draw being served, the calendars and predictors
+// must cover T .. T + horizon - 1 -- and observes as ba_ss_prediction_errors does.
+int ba_ss_holdout_prediction_errors(ba_engine *e, int64_t chain_first, int64_t chain_count, int32_t standardize,
+                                    int32_t horizon, const double *newX, const double *newY, double *errors,
+                                    double *variances) {
+  ENGINE_PROLOGUE(e);
+  if (ss_refused(e, e->data_kind, SSG_USE_HOLDOUT_ERRORS)) return BA_E_STATE;
+  if (e->data_kind != DATA_STATE_SPACE) return fail(BA_E_STATE, set_data_first(DATA_STATE_SPACE));
+  if (horizon <= 0) return fail(BA_E_INVALID, "the horizon must be positive");
+  if (!newY || !errors || (!newX && e->p > 0)) return fail(BA_E_INVALID, "null argument");
+  for (int32_t i = 0; i < horizon; ++i)
+    if (!std::isfinite(newY[i])) {
+      char buf[96];
+      std::snprintf(buf, sizeof buf, "holdout response %d is not finite: a holdout has no missing steps", (int)i);
+      return fail(BA_E_INVALID, buf);
+    }
+  if (chain_first < 0 || chain_count <= 0 || chain_first >= e->cfg.chains || chain_count > e->cfg.chains - chain_first)
+    return fail(BA_E_INVALID, "chain range out of bounds");
+  if (e->dss_scratch.count == 0 || !e->ss_initialized || (e->ssm_set && e->dssm_work.count == 0))
+    return fail(BA_E_STATE, "no state draw yet: run ba_ss_sweep or ba_ss_impute_state first");
+  int rc = hol_prepare(e, horizon);   // (the calendars' entries and the predictors' rows T .. T + horizon - 1)
+  if (rc) return rc;
+  rc = ba_sync(e);
+  if (rc) return rc;
+  const size_t p = (size_t)e->p, T = (size_t)e->T, n = (size_t)chain_count, h = (size_t)horizon;
+  hipStream_t s = e->stream;
+  if (e->dssf_err.count < n * h) HIP_TRY(e->dssf_err.resize(n * h));
+  if (variances && e->dssf_var.count < n * h) HIP_TRY(e->dssf_var.resize(n * h));
+  if (e->dssf_flag.count == 0) HIP_TRY(e->dssf_flag.resize(1));
+  if (e->dssf_newy.count < h) HIP_TRY(e->dssf_newy.resize(h));
+  if (p > 0 && e->dssf_newx.count < h * p) HIP_TRY(e->dssf_newx.resize(h * p));
+  HIP_TRY(hipMemcpyAsync(e->dssf_newy.ptr, newY, h * 8, hipMemcpyHostToDevice, s));
+  if (p > 0) HIP_TRY(hipMemcpyAsync(e->dssf_newx.ptr, newX, h * p * 8, hipMemcpyHostToDevice, s));
+  SsFilterParams F{};
+  F.T = horizon;
+  F.time0 = e->T;
+  F.p = e->p;
+  F.chain_first = (int32_t)chain_first;
+  F.chain_count = (int32_t)chain_count;
+  F.standardize = standardize ? 1 : 0;
+  F.y = e->dssf_newy.ptr;
+  F.X = e->dssf_newx.ptr;
+  if (e->ssm_set) {
+    F.spec = reinterpret_cast<const SsgSpec *>(e->dssg_spec.ptr);
+    F.m = e->ssg.m;
+    F.nblocks = e->ssg.nblocks;
+    F.nvar = e->ssg.nvar;
+    F.nar = e->ssg.nar;
+    if (ssg_has(e->ssg, SSG_HAS_CALENDAR)) F.cal = e->dhol_cal.ptr;
+    if (ssg_has(e->ssg, SSG_HAS_DYNREG)) {
+      F.dyn = e->ddyn.ptr;
+      F.dyn_cols = ssg_dyn_columns(e->ssg);
+    }
+    // the state draw: [T][m] behind the chain's first m T doubles of work (ssg_forecast_kernel's start)
+    F.state = e->dssm_work.ptr + (size_t)e->ssg.m * T + (T - 1) * (size_t)e->ssg.m;
+    F.state_stride = ssm_work_stride(*e);
+    F.src.var = e->dssm_sigsq.ptr;
+    F.src.var_stride = SSG_MAX_VAR;
+    F.src.phi = e->ssg.nar > 0 ? e->dar_phi.ptr : nullptr;
+    F.src.phi_stride = SSG_MAX_AR * AR_MAX;
+  } else {
+    // the local-level path: a one-block list, as ba_ss_prediction_errors builds it
+    SsgSpec one{};
+    one.m = one.nblocks = one.nvar = 1;
+    one.blk[0].kind = SSG_LOCAL_LEVEL;
+    one.blk[0].dim = 1;
+    one.blk[0].nvar = 1;
+    one.blk[0].duration = 1;
+    one.blk[0].ar_index = -1;
+    one.a0[0] = e->ss_a0;
+    one.P0[0] = e->ss_P0;
+    if (e->dssf_spec.count == 0) HIP_TRY(e->dssf_spec.resize(sizeof(SsgSpec)));
+    HIP_TRY(hipMemcpy(e->dssf_spec.ptr, &one, sizeof(SsgSpec), hipMemcpyHostToDevice));
+    F.spec = reinterpret_cast<const SsgSpec *>(e->dssf_spec.ptr);
+    F.m = F.nblocks = F.nvar = 1;
+    F.nar = 0;
+    // (ss_forecast_kernel's start)
+    F.state = e->dss_scratch.ptr + (size_t)SS_STATE_ARRAY * ss_pitch(*e) + (size_t)(ss_lane_major(*e) ? lm_at((int)T - 1) : (int)T - 1);
+    F.state_stride = (int64_t)SS_SCRATCH_ARRAYS * (int64_t)ss_pitch(*e);
+    F.src.var = e->dlev_sigsq.ptr;
+    F.src.var_stride = 1;
+  }
+  F.ld = (F.m + 1) | 1;
+  F.src.gamma = e->dgamma.ptr;
+  F.src.beta = e->dbeta.ptr;
+  F.src.sigsq = e->dsigsq.ptr;
+  F.src.gamma_stride = F.src.beta_stride = (int64_t)p;
+  F.src.sigsq_stride = 1;
+  F.errors = e->dssf_err.ptr;
+  F.variances = variances ? e->dssf_var.ptr : nullptr;
+  F.flag = e->dssf_flag.ptr;
+  int32_t flag = 0;
+  HIP_TRY(hipMemsetAsync(e->dssf_flag.ptr, 0x7f, 4, s));
+  HIP_TRY(launch_ss_filter_holdout(s, F));
+  HIP_TRY(hipMemcpyAsync(errors, e->dssf_err.ptr, n * h * 8, hipMemcpyDeviceToHost, s));
+  if (variances) HIP_TRY(hipMemcpyAsync(variances, e->dssf_var.ptr, n * h * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&flag, e->dssf_flag.ptr, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (flag >= 0 && flag < e->cfg.chains) {
+    char buf[64];
+    std::snprintf(buf, sizeof buf, " (chain %lld)", (long long)(e->cfg.chain_offset + (int64_t)flag));
+    return fail(BA_E_FORECAST_VARIANCE, std::string("Found a zero (or negative) forecast variance!") + buf);
+  }
+  return BA_OK;
+}
+
 }  // extern "C"
 
 // ---- forecasts of the three families: simulate_forecast of StateSpaceStudentRegressionModel,

@@ -18,6 +18,10 @@
 // chain's output row; the serial pass reads it back 64 steps at a time and overwrites it.
 // log F, v^2 / F and v / sqrt F are taken after every block of 64 steps, a step per lane, and
 // the log likelihood's terms summed in step order: the logarithm is off the serial path.
+//
+// The same kernel body serves the one-step HOLDOUT prediction errors (StateSpaceRegressionModel::
+// one_step_holdout_prediction_errors, StateSpaceRegressionModel.cpp:280-305) as its second instance: the
+// caller's rows behind the series, filtered from the chain's drawn final state with the variance RQR_{T-1}.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -88,6 +92,24 @@ __device__ __forceinline__ void ssf_apply_T(const SsfBlocks &B, unsigned mv, con
   }
 }
 
+// the variance one lane's diagonal entry of P gains with RQR_t: its own every step (a Student trend's divided by
+// the step's weight), a seasonal's first component where the block moves at t, a holiday's entry where the
+// calendar's entry t + 1 puts the block
+__device__ __forceinline__ double ssf_rqr_diag(double qdiag, int stu, double wl, double ws, int seas_first, unsigned mv,
+                                               double seas_var, bool hgain, double hvar) {
+  double q = qdiag;
+  if (stu) q = qdiag / (stu == 1 ? wl : ws);
+  if (seas_first >= 0 && ((mv >> seas_first) & 1u)) q = seas_var;
+  if (hgain) q = hvar;
+  return q;
+}
+
+// HOLDOUT = false: the in-sample filter (ba_ss_prediction_errors).  HOLDOUT = true: the same steps over the
+// caller's h rows behind the series (ba_ss_holdout_prediction_errors; ss_filter_params.h says what the
+// parameters mean there): the prologue and the step loop are the in-sample ones on a time base of the series'
+// length; what differs is the initial condition -- a = T_{T-1} alpha, P = RQR_{T-1} --, that every step is
+// observed and that there is no log likelihood.
+template <bool HOLDOUT>
 __global__ __launch_bounds__(WAVE) void ss_filter_kernel(SsFilterParams P) {
   extern __shared__ double s_P[];   // m x ld
   __shared__ double s_phi[SSG_MAX_AR * AR_MAX], s_var[SSG_MAX_VAR], s_tc[SSG_MAX_STATE], s_ts[SSG_MAX_STATE];
@@ -96,6 +118,7 @@ __global__ __launch_bounds__(WAVE) void ss_filter_kernel(SsFilterParams P) {
   const int64_t chain = (int64_t)P.chain_first + row;
   const int T = P.T, p = P.p, m = P.m, ld = P.ld;
   const SsgSpec &Q = *P.spec;
+  const int time0 = HOLDOUT ? P.time0 : 0;   // the time of row 0
   double *err = P.errors + (size_t)row * T;
   double *var_out = P.variances ? P.variances + (size_t)row * T : nullptr;
 
@@ -147,7 +170,7 @@ __global__ __launch_bounds__(WAVE) void ss_filter_kernel(SsFilterParams P) {
     calb = ssg_is_calendar(K);
     if (K.kind == SSG_SEASONAL) {
       dur = K.duration;
-      rc = (1 - K.phase) % dur;
+      rc = (time0 + 1 - K.phase) % dur;
       if (rc < 0) rc += dur;
     }
   }
@@ -208,11 +231,29 @@ __global__ __launch_bounds__(WAVE) void ss_filter_kernel(SsFilterParams P) {
   const unsigned long long drmask = __ballot(dr && lane < m);
   // (the lane's predictor of the step, and the next step's on its way while this one is worked on)
   double xw = 0.0, xn = 0.0;
-  if (dr) xn = P.dyn[dcol];
+  if (dr) xn = P.dyn[(size_t)time0 * P.dyn_cols + dcol];
   const bool act = lane < m;
   for (int e = lane; e < m * ld; e += WAVE) s_P[e] = 0.0;
   wave_lds_sync();
-  if (act) s_P[lane * ld + lane] = P0l;
+  if (!HOLDOUT) {
+    if (act) s_P[lane * ld + lane] = P0l;
+  } else {
+    // a = T_{T-1} alpha, by one lane on column m; P = RQR_{T-1}: the step T - 1 moves a seasonal where time T
+    // starts a season, and a holiday gains its variance at the position of entry T
+    const unsigned long long c0 = P.cal ? P.cal[time0] : (unsigned long long)SSG_CAL_NONE;
+    const bool calmove0 = calb && ((c0 >> (8 * (lane & 7))) & (unsigned long long)SSG_CAL_SEASON) != 0;
+    const unsigned mv0 = (unsigned)__ballot(lane < B.nb && SsfBlocks::kind_of(B.desc) == SSG_SEASONAL &&
+                                            (calb ? calmove0 : rc == (dur == 1 ? 0 : 1))) & seasmask;
+    if (act) s_P[lane * ld + m] = P.state[chain * P.state_stride + lane];
+    wave_lds_sync();
+    if (lane == 0) ssf_apply_T(B, mv0, s_phi, s_tc, s_ts, s_P + m, ld);
+    wave_lds_sync();
+    if (act) {
+      a = s_P[lane * ld + m];
+      const bool hgain0 = hol && lane == hfirst + (int)((c0 >> hsh) & 0xffu);
+      s_P[lane * ld + lane] = ssf_rqr_diag(qdiag, 0, 1.0, 1.0, seas_first, mv0, seas_var, hgain0, hvar);
+    }
+  }
   wave_lds_sync();
 
   const double *qw = P.qw ? P.qw + chain * P.qw_stride : nullptr;
@@ -222,13 +263,14 @@ __global__ __launch_bounds__(WAVE) void ss_filter_kernel(SsFilterParams P) {
   for (int tb = 0; tb < T; tb += WAVE) {
     const int tt = tb + lane;
     const double ys_l = tt < T ? err[tt] : 0.0;
-    const unsigned long long obsmask = __ballot(tt < T && P.observed[tt] != 0);
+    const unsigned long long obsmask = __ballot(tt < T && (HOLDOUT || P.observed[tt] != 0));
     double wl_l = 1.0, ws_l = 1.0;
     if (qw && tt < T) { wl_l = qw[tt]; ws_l = qw[(size_t)T + tt]; }
     double v_l = 0.0, F_l = 0.0;
     // (the calendar's entries t -- Z_t -- and t + 1 -- RQR_t -- of the block's steps, one per lane)
     unsigned long long cw_l = SSG_CAL_NONE, cn_l = SSG_CAL_NONE;
-    if (P.cal) { if (tt < T) cw_l = P.cal[tt]; if (tt + 1 < T) cn_l = P.cal[tt + 1]; }
+    // (entry and row time0 + T are never read: the last step's transition feeds nothing)
+    if (P.cal) { if (tt < T) cw_l = P.cal[time0 + tt]; if (tt + 1 < T) cn_l = P.cal[time0 + tt + 1]; }
     const int ns = T - tb < WAVE ? T - tb : WAVE;
     for (int s = 0; s < ns; ++s) {
       const bool obs = ((obsmask >> s) & 1ull) != 0;
@@ -245,7 +287,7 @@ __global__ __launch_bounds__(WAVE) void ss_filter_kernel(SsFilterParams P) {
       }
       if (P.dyn) {
         xw = xn;
-        if (dr && tb + s + 1 < T) xn = P.dyn[(size_t)(tb + s + 1) * P.dyn_cols + dcol];
+        if (dr && tb + s + 1 < T) xn = P.dyn[(size_t)(time0 + tb + s + 1) * P.dyn_cols + dcol];
       }
       if (!dead) {
         // PZ, F, v
@@ -308,10 +350,7 @@ __global__ __launch_bounds__(WAVE) void ss_filter_kernel(SsFilterParams P) {
           // (the step's Student-trend weights: every lane reads them, the trend's two lanes use them)
           const double wl = rl(wl_l, s), ws = rl(ws_l, s);
           if (act) {
-            double q = qdiag;
-            if (stu) q = qdiag / (stu == 1 ? wl : ws);
-            if (seas_first >= 0 && ((mv >> seas_first) & 1u)) q = seas_var;
-            if (hgain) q = hvar;
+            const double q = ssf_rqr_diag(qdiag, stu, wl, ws, seas_first, mv, seas_var, hgain, hvar);
             if (q != 0.0) s_P[lane * ld + lane] += q;
           }
           wave_lds_sync();
@@ -323,25 +362,40 @@ __global__ __launch_bounds__(WAVE) void ss_filter_kernel(SsFilterParams P) {
     // the block's log likelihood terms and standardised errors, a step per lane; the terms are
     // summed in step order
     const bool ob_l = ((obsmask >> lane) & 1ull) != 0;
-    const double term = ob_l ? -0.5 * (1.8378770664093454835606594728112 + log(F_l) + v_l * v_l / F_l) : 0.0;
-    for (int s = 0; s < ns; ++s) ll += rl(term, s);
+    if (!HOLDOUT) {
+      const double term = ob_l ? -0.5 * (1.8378770664093454835606594728112 + log(F_l) + v_l * v_l / F_l) : 0.0;
+      for (int s = 0; s < ns; ++s) ll += rl(term, s);
+    }
     if (tt < T) {
       err[tt] = (P.standardize && ob_l) ? v_l / sqrt(F_l) : v_l;
       if (var_out) var_out[tt] = F_l;
     }
   }
-  if (lane == 0) P.loglik[row] = dead ? nan : ll;
+  if (!HOLDOUT && lane == 0) P.loglik[row] = dead ? nan : ll;
 }
 
 }  // namespace
 
+// One instance per translation unit: a second kernel in this one changes the code the compiler makes for the
+// first (its register allocation), and the in-sample instance is kept byte-stable.  This file makes the
+// in-sample instance; ss_filter_holdout_kernel.hip defines SS_FILTER_HOLDOUT_UNIT, includes this file and makes
+// the holdout instance from the same source.
+#ifndef SS_FILTER_HOLDOUT_UNIT
 size_t ss_filter_lds(int m, int ld) { return (size_t)m * ld * sizeof(double); }
 
 hipError_t launch_ss_filter(hipStream_t stream, const SsFilterParams &P) {
   if (P.chain_count <= 0) return hipSuccess;
   KtScope kt(stream, KT_SS_FILTER);
-  hipLaunchKernelGGL(ss_filter_kernel, dim3((unsigned)P.chain_count), dim3(WAVE), ss_filter_lds(P.m, P.ld), stream, P);
+  hipLaunchKernelGGL(ss_filter_kernel<false>, dim3((unsigned)P.chain_count), dim3(WAVE), ss_filter_lds(P.m, P.ld), stream, P);
   return hipGetLastError();
 }
+#else
+hipError_t launch_ss_filter_holdout(hipStream_t stream, const SsFilterParams &P) {
+  if (P.chain_count <= 0) return hipSuccess;
+  KtScope kt(stream, KT_SS_FILTER);
+  hipLaunchKernelGGL(ss_filter_kernel<true>, dim3((unsigned)P.chain_count), dim3(WAVE), ss_filter_lds(P.m, P.ld), stream, P);
+  return hipGetLastError();
+}
+#endif
 
 }  // namespace boom_amd

@@ -1,5 +1,5 @@
 // Launch parameters of the one-step prediction error kernel (ss_filter_kernel.hip), shared
-// with the host side (engine_ss.hip: ba_ss_prediction_errors).
+// with the host side (engine_ss_observe.hip: ba_ss_prediction_errors, ba_ss_holdout_prediction_errors).
 #pragma once
 #include <stdint.h>
 
@@ -43,9 +43,18 @@ struct SsFilterParams {
   // y is every chain's own series, y_stride doubles apart (SsParams::y_stride: a list with regression
   // holiday models); 0: the one series shared by the chains
   int64_t y_stride;
+  // ---- the holdout instance only (launch_ss_filter_holdout: ba_ss_holdout_prediction_errors).  There T is the
+  // number of holdout rows h -- y the caller's h responses (y_stride 0), X its h x p predictors, column-major
+  // at leading dimension h, errors and variances chain_count x h; observed, loglik and qw are not read --
+  // and the filter runs on the time indices time0 .. time0 + h - 1:
+  int32_t time0, time0_pad;   // the series' length: the time of the first holdout row
+  // component k of chain c's state draw at time time0 - 1 sits at state[c * state_stride + k]
+  const double *state;
+  int64_t state_stride;
 };
 
 hipError_t launch_ss_filter(hipStream_t stream, const SsFilterParams &P);
+hipError_t launch_ss_filter_holdout(hipStream_t stream, const SsFilterParams &P);
 size_t ss_filter_lds(int m, int ld);
 
 }  // namespace boom_amd

@@ -137,7 +137,7 @@ inline void ssg_template_shape(const SsgSpec &q, int32_t *trend, int32_t *nseaso
 // ---- the rule book: which state model goes with which observation family, with a Student trend
 // in the same list, and with the look-ahead, the forecast and the prediction errors ---------------
 enum SsFamily { SS_FAMILY_GAUSSIAN, SS_FAMILY_STUDENT, SS_FAMILY_POISSON, SS_FAMILY_LOGIT };
-enum SsgUse { SSG_USE_APPEND, SSG_USE_LAUNCH, SSG_USE_LOOKAHEAD, SSG_USE_FORECAST, SSG_USE_PREDICTION_ERRORS };
+enum SsgUse { SSG_USE_APPEND, SSG_USE_LAUNCH, SSG_USE_LOOKAHEAD, SSG_USE_FORECAST, SSG_USE_PREDICTION_ERRORS, SSG_USE_HOLDOUT_ERRORS };
 // The refusal (BA_E_STATE) of `use` under observation family `family`, or nullptr.  q: the list
 // (nullptr: none is set).  SSG_USE_APPEND: `kind` is about to be appended to q; SSG_USE_LOOKAHEAD:
 // a look-ahead above 1; SSG_USE_FORECAST: ba_ss_forecast, the Gaussian family's.  Where two
@@ -194,6 +194,13 @@ inline const char *ssg_refusal(const SsgSpec *q, SsFamily family, SsgUse use, in
       return has(SSG_HAS_STUDENT_TREND) ? "forecasts with a Student local linear trend are not implemented" : nullptr;
     case SSG_USE_PREDICTION_ERRORS:
       return other ? "one-step prediction errors are built for the Gaussian observation model only" : nullptr;
+    case SSG_USE_HOLDOUT_ERRORS:   // (ba_ss_holdout_prediction_errors)
+      if (other) return "holdout prediction errors are built for the Gaussian observation model only";
+      // (the reference's const method filters the block in its MIXTURE behaviour and reads its weight vectors at
+      // T + i, past their end -- StudentLocalLinearTrend.cpp:178-185)
+      if (has(SSG_HAS_STUDENT_TREND))
+        return "holdout prediction errors with a Student local linear trend are not defined: the reference reads the trend's weights past the end of the series";
+      return regholidays > 0 ? "holdout prediction errors with a regression holiday model are not built" : nullptr;
   }
   return nullptr;
 }

@@ -584,6 +584,10 @@ PYBIND11_MODULE(_boom, boom) {
              return matrix_to_numpy(m.one_step_prediction_errors(standardize));
            }, py::arg("standardize") = false,
            "the one-step prediction errors of every chain's current draw (time_dimension x chains)")
+      .def("one_step_holdout_prediction_errors", [](StateSpaceRegressionModel &m, const NpArray &newX, const NpArray &newY, bool standardize) {
+             return matrix_to_numpy(m.one_step_holdout_prediction_errors(matrix_from(newX), vector_from(newY), standardize));
+           }, py::arg("newX"), py::arg("newY"), py::arg("standardize") = false,
+           "the one-step prediction errors of the holdout rows behind the series, from every chain's current draw and final state (chains x horizon)")
       .def("log_likelihood", [](StateSpaceRegressionModel &m) { return to_numpy(m.log_likelihood()); },
            "the filter's log likelihood of every chain's current draw (one entry per chain)")
       .def("add_state", [](StateSpaceRegressionModel &m, const Ptr<LocalLevelStateModel> &s) { m.add_state(s); })

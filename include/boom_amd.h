@@ -1158,6 +1158,33 @@ int ba_ss_forecast(ba_engine *e, int32_t horizon, const double *newX, double *ou
  * reported as by ba_ss_forecast. */
 int ba_ss_prediction_errors(ba_engine *e, int64_t chain_first, int64_t chain_count, int32_t standardize,
                             double *errors, double *variances, double *log_likelihood);
+/* bsts.prediction.errors(model, cutpoints = ...): StateSpaceRegressionModel::
+ * one_step_holdout_prediction_errors(newX, newY, final_state, standardize)
+ * (StateSpaceRegressionModel.cpp:280-305; StateSpaceModel's twin is the call with p = 0) for chains
+ * [chain_first, chain_first + chain_count): the one-step prediction errors of `horizon` holdout rows that
+ * follow the engine's series, at the parameters ba_ss_prediction_errors would read live at that moment
+ * and from the chain's drawn final state alpha (time T - 1, what ba_ss_forecast starts from).  The filter
+ * starts at a = T_{T-1} alpha, P = RQR_{T-1} and runs on the time indices T .. T + horizon - 1 with no
+ * missing step: v_i = newY_i - newX_i'beta - Z_{T+i}'a, F_i = Z_{T+i}'P Z_{T+i} + sigma^2, then the update
+ * and the transition as ba_ss_prediction_errors does them.  A seasonal's phase is counted on from T; a
+ * holiday's or calendar seasonal's calendar and a dynamic regression's predictors are read at T ..
+ * T + horizon - 1, the rows ba_ss_forecast(horizon) needs (the same refusals when they are too few).
+ * newX: horizon x p column-major, as ba_ss_forecast's (NULL where p = 0); newY: horizon finite numbers;
+ * errors (v_i; standardize != 0: v_i / sqrt(F_i)) and variances (F_i; may be NULL): chain_count x horizon,
+ * a chain's values together; all on the host.  bsts calls it after every draw on the series cut at the
+ * cutpoint and appends the result to ba_ss_prediction_errors' in-sample errors.  It needs a state draw
+ * (BA_E_STATE "no state draw yet ..." as ba_ss_forecast), settles a look-ahead to the draw being served as
+ * ba_ss_forecast does, and is an observer otherwise: no stream position, state path, sufficient statistic,
+ * status or snapshot changes.  A forecast variance that is not positive and finite: as
+ * ba_ss_prediction_errors (NaN from that step on, BA_E_FORECAST_VARIANCE with the chain's index).
+ * Refused with BA_E_STATE: the Student-t, Poisson and logit families ("holdout prediction errors are built
+ * for the Gaussian observation model only"); a list with a Student local linear trend (the reference's
+ * method reads the trend's weights past the end of the series: nothing defined to reproduce); a list with
+ * regression holiday models, plain or hierarchical (not built).  BA_E_INVALID: horizon <= 0, a null newY or
+ * errors, a null newX with p > 0, a newY entry that is not finite, a chain range out of bounds. */
+int ba_ss_holdout_prediction_errors(ba_engine *e, int64_t chain_first, int64_t chain_count, int32_t standardize,
+                                    int32_t horizon, const double *newX, const double *newY, double *errors,
+                                    double *variances);
 /* state(): T doubles of one chain; level sigsq; level suf (n, sumsq) */
 int ba_ss_get_state(ba_engine *e, int64_t chain, double *state,
                     double *level_sigsq, double *level_n, double *level_sumsq);

@@ -1091,6 +1091,23 @@ class StateSpaceRegressionModel : public Model {
     eng_->check(ba_ss_prediction_errors(eng_->get(), 0, eng_->chains(), standardize ? 1 : 0, ans.data(), nullptr, nullptr));
     return ans;
   }
+  // StateSpaceRegressionModel::one_step_holdout_prediction_errors(newX, newY, final_state, standardize)
+  // (StateSpaceRegressionModel.cpp:280-305) for EVERY chain's current draw and its own final state: chains x
+  // newY.size(), row c = chain c (bsts.prediction.errors' holdout part).  Refused by the engine: the Student-t,
+  // Poisson and logit families, a Student local linear trend, regression holiday models.
+  Matrix one_step_holdout_prediction_errors(const Matrix &newX, const Vector &newY, bool standardize = false) {
+    if (newX.nrow() != (int)newY.size()) report_error("X and y do not match in one_step_holdout_prediction_errors.");
+    if (newX.ncol() != p_) report_error("The holdout predictors do not match the model dimension.");
+    finalize_state();
+    const int h = (int)newY.size(), chains = (int)eng_->chains();
+    std::vector<double> rows((size_t)chains * (size_t)(h > 0 ? h : 0));
+    eng_->check(ba_ss_holdout_prediction_errors(eng_->get(), 0, chains, standardize ? 1 : 0, h, p_ > 0 ? newX.data() : nullptr,
+                                                newY.data(), rows.data(), nullptr));
+    Matrix ans(chains, h);
+    for (int c = 0; c < chains; ++c)
+      for (int i = 0; i < h; ++i) ans(c, i) = rows[(size_t)c * h + i];
+    return ans;
+  }
   // the filter's log likelihood of every chain's current draw (bsts's log.likelihood), one entry per chain
   Vector log_likelihood() {
     finalize_state();
