@@ -24,6 +24,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "probe_dev.h"
+
 namespace boom_amd {
 // (never called: the probe launches the kernels itself)
 void kt_mark(hipStream_t, int, bool) {}
@@ -44,30 +46,6 @@ namespace {
 
 enum : int { IP_BAD_REQUEST = -1 };
 enum Kind : int { K_PROBIT, K_LOGIT, K_LOGIT_SS, K_PG, K_POISSON, K_POISSON_SS, K_SS_H, K_SS_SUF };
-
-template <class T>
-struct Dev {
-  T *ptr = nullptr;
-  T *host;
-  size_t bytes;
-  hipError_t err = hipSuccess;
-  Dev(const T *h, size_t count) : host(const_cast<T *>(h)), bytes(count * sizeof(T)) {
-    if (!h || !count) return;
-    err = hipMalloc((void **)&ptr, bytes);
-    if (err == hipSuccess) err = hipMemcpy(ptr, h, bytes, hipMemcpyHostToDevice);
-  }
-  hipError_t back() { return ptr ? hipMemcpy(host, ptr, bytes, hipMemcpyDeviceToHost) : hipSuccess; }
-  ~Dev() {
-    if (ptr) (void)hipFree(ptr);
-  }
-  Dev(const Dev &) = delete;
-};
-
-#define IP_TRY(expr)                              \
-  do {                                            \
-    hipError_t e__ = (expr);                      \
-    if (e__ != hipSuccess) return (int)e__;       \
-  } while (0)
 
 #define IP_ARGS                                                                                                     \
   int n, int p, int chains, int slot_limit, int64_t chain_offset, const double *X, size_t nX, const uint8_t *gamma, \

@@ -61,41 +61,51 @@ def expand_design(Xsubject, Xchoice, n, M):
     return X
 
 
-def lse(eta):
+def lse(eta, M=math):
     """lse_safe (cpputil/lse.cpp:27-40)"""
     m = max(eta)
     if m == -math.inf:
         return m
     tot = 0.0
     for e in eta:
-        tot += math.exp(e - m)
-    return m + math.log(tot) if tot > 0 else -math.inf
+        tot += M.exp(e - m)
+    return m + M.log(tot) if tot > 0 else -math.inf
 
 
-def lse2(x, y):
+def lse2(x, y, M=math):
     """cpputil/lse.hpp:31-39"""
     if x < y:
         x, y = y, x
-    return x + math.log1p(math.exp(y - x))
+    return x + M.log1p(M.exp(y - x))
 
 
-def unmix_posterior(v):
+# The scalar functions here (lse and lse2 above too) take the math functions they call as `M` (exp, log, log1p, isfinite,
+# inf), the module `math` unless the caller says otherwise: tests/latent_ref.py passes
+# imputer_ref's table, which moves the results as another library would.
+def _fused(v, M):
+    """an a + b c the device may round once: a table's replays move it by an ulp (M.fused); the
+    value itself on the plain module"""
+    f = getattr(M, "fused", None)
+    return v if f is None else f(v)
+
+
+def unmix_posterior(v, M=math):
     """the ten normalised posterior terms of unmix (MLVS_data_imputer.cpp:76-82)"""
     pp = []
     for c in range(10):
         xs = (v - _MU[c]) / _SD[c]
-        pp.append(_LOGW[c] + -(LN_SQRT_2PI + 0.5 * xs * xs + _LOGSD[c]))
+        pp.append(_LOGW[c] + -_fused(LN_SQRT_2PI + 0.5 * xs * xs + _LOGSD[c], M))
     mx = max(pp)
     nc = 0.0
     for c in range(10):
-        pp[c] = math.exp(pp[c] - mx)
+        pp[c] = M.exp(pp[c] - mx)
         nc += pp[c]
     return [q / nc for q in pp]
 
 
-def unmix(v, unif):
+def unmix(v, unif, M=math):
     """(component, margin): rmulti_mt (distributions/rmulti.cpp:41-78) on the posterior terms"""
-    pp = unmix_posterior(v)
+    pp = unmix_posterior(v, M)
     probsum = 0.0
     for q in pp:
         probsum += q
@@ -111,33 +121,36 @@ def unmix(v, unif):
     return ind, margin
 
 
-def rlexp(loglam, unif, stats):
+def rlexp(loglam, unif, stats, M=math):
     """distributions/rlexp.cpp:25-31"""
     while True:
         u = unif()
-        a = -math.log(u)
-        ans = math.log(a) if a > 0 else -math.inf
+        a = -M.log(u)
+        ans = M.log(a) if a > 0 else -math.inf
         if math.isfinite(ans):
             return ans - loglam
         stats["retries"] += 1
 
 
-def impute_point(eta, y, unif, stats=None, shift=True):
-    """(u, w) of one observation, M each; unif() reads the observation's slot.  shift=False
-    leaves the component's mean in (the utilities themselves)"""
+def impute_point(eta, y, unif, stats=None, shift=True, M=math):
+    """(u, w) of one observation, one per choice; unif() reads the observation's slot.  shift=False
+    leaves the component's mean in (the utilities themselves).  stats["comps"], where the caller
+    put a list there, gets every choice's mixture component"""
     stats = stats if stats is not None else {"retries": 0, "unmix_margin": math.inf}
-    M = len(eta)
-    loglam = lse(eta)
+    nch = len(eta)
+    loglam = lse(eta, M)
     if not math.isfinite(loglam) or not all(math.isfinite(e) for e in eta):
         raise RuntimeError("non-finite linear predictor")
-    logzmin = rlexp(loglam, unif, stats)
-    u, w = [0.0] * M, [0.0] * M
-    for m in range(M):
+    logzmin = rlexp(loglam, unif, stats, M)
+    u, w = [0.0] * nch, [0.0] * nch
+    for m in range(nch):
         um = -logzmin
         if m != y:
-            um = -lse2(logzmin, rlexp(eta[m], unif, stats))
-        k, mg = unmix(um - eta[m], unif)
+            um = -lse2(logzmin, rlexp(eta[m], unif, stats, M), M)
+        k, mg = unmix(um - eta[m], unif, M)
         stats["unmix_margin"] = min(stats.get("unmix_margin", math.inf), mg)
+        if "comps" in stats:
+            stats["comps"].append(k)
         if shift:
             um -= _MU[k]
         u[m] = um

@@ -50,10 +50,11 @@ def rig(mu, lam, z, u, root=smaller_root):
     return np.where(u > mu / (mu + x), mu * mu / x, x)
 
 
-def impute_point(y, eta, shift, norm, unif):
+def impute_point(y, eta, shift, norm, unif, rig=rig):
     """(w, z, t) of one observation: w = lambda_inv, z = w y* = w y - shift with
     shift = 1 - 2 q, t the root's argument; norm() / unif() read the observation's slot, and
-    are not called when the residual is 0 or 1 / r is not finite"""
+    are not called when the residual is 0 or 1 / r is not finite.  rig: the inverse-Gaussian draw
+    given its normal and uniform (tests/latent_ref.py passes this module's on another math table)"""
     r = abs(y - eta)
     with np.errstate(divide="ignore", over="ignore"):
         mu = np.float64(1.0) / np.float64(r)

@@ -67,16 +67,21 @@ def nu_log_post(nu, u, n_log_sigma, prior):
     return lp + (n * c - n_log_sigma) - 0.5 * (nu + 1) * float(np.sum(np.log1p(u / nu)))
 
 
-def slice_draw_nu(unif, rexp1, logf, x, dx):
+def slice_draw_nu(unif, rexp1, logf, x, dx, stats=None, fused=None):
     """ScalarSliceSampler::draw for a target bounded below at 0 (find_limits ->
     find_upper_limit with its random extra doublings, then shrink).  unif() / rexp1() read
     the sampler's stream.  Returns (new x, new suggested_dx, smallest relative margin of the
-    slice comparisons)."""
+    slice comparisons).  stats (a dict): gets the number of doublings and of shrinks, and the
+    margin so far where the sampler raises; fused: what a device that rounds the candidate's
+    lo + (hi - lo) u once makes of it (tests/latent_ref.py's replays)."""
     margin = [np.inf]
+    stats = {} if stats is None else stats
+    stats.update(doublings=0, shrinks=0, margin=np.inf)
 
     def note(a, b):
         if np.isfinite(a) and np.isfinite(b):
             margin[0] = min(margin[0], abs(a - b) / max(abs(a), abs(b), 1e-300))
+            stats["margin"] = margin[0]
 
     logp_slice = logf(x) - rexp1()
     if not np.isfinite(logp_slice):
@@ -92,6 +97,7 @@ def slice_draw_nu(unif, rexp1, logf, x, dx):
         logphi = logf(hi)
         note(logphi, logp_slice)
         doublings += 1
+        stats["doublings"] = doublings
         if doublings > 100:
             raise SliceError("more than 100 doublings")
     if np.isnan(logphi):
@@ -99,6 +105,8 @@ def slice_draw_nu(unif, rexp1, logf, x, dx):
     tries = 0
     while True:
         cand = lo + (hi - lo) * unif()
+        if fused is not None and lo != 0.0:
+            cand = fused(cand)
         lp = logf(cand)
         note(lp, logp_slice)
         if not lp < logp_slice:
@@ -109,6 +117,7 @@ def slice_draw_nu(unif, rexp1, logf, x, dx):
             lo = cand
         dx = hi - lo
         tries += 1
+        stats["shrinks"] = tries
         if tries > 100:
             raise SliceError("number of tries exceeded")
 
