@@ -369,6 +369,11 @@ class Engine:
                                             int(draw_beta), int(draw_sigma)))
 
     def set_tuning(self, waves_per_chain=0, walk_policy=-1, kcap_start=0):
+        """overrides of choices the engine makes itself (the same chains whatever is set).
+        walk_policy: -1 default (1); 0 batch mode only; 1 adaptive, 2 always the table -- with
+        helper wavefronts both run EVERY table walk beside the master's tail, the one a sweep
+        starts with and the ones resumed after a stop; 3 adaptive, no walk forked; 4 adaptive,
+        forking at a sweep's start only (what 1 did before resumed walks forked: A/B, tests)"""
         self._check(self.lib.ba_set_tuning(self._h, waves_per_chain, walk_policy, kcap_start))
 
     def set_rebuild_policy(self, policy):
@@ -474,7 +479,10 @@ class Engine:
                     # after plain sweeps of the product library: rebuilds that kept the
                     # leading factor columns, and how many columns they kept (the
                     # diagnostic stamp builds use these slots for cycles)
-                    partial_rebuilds=float(sc[9]), columns_kept=float(sc[10]))
+                    partial_rebuilds=float(sc[9]), columns_kept=float(sc[10]),
+                    # ... table walks resumed after a stop (or started unforked) that ran
+                    # beside the master's tail, and those that found a stop and rolled it back
+                    reforks=float(sc[11]), refork_rollbacks=float(sc[12]))
 
     def summaries_device(self, ptr):
         self._check(self.lib.ba_summaries_device(self._h, ptr))

@@ -21,6 +21,13 @@
 //                                              determinants, 3 w and the model's value, 4
 //                                              publish / restore; 5 and 6 are COUNTS (rebuilds,
 //                                              columns kept); 7 everything else               core
+//   -DBA_STAMPS -DBA_STAMPS6  MSTAMP(c, i)     the master's "everything else" of TSTAMP, split: 0
+//                                              waiting for a table walk it did not fork, 1
+//                                              waiting at the join, 2 its share of the fill
+//                                              rounds, 3 events (rebuild or slot switch); 4, 5
+//                                              and 6 are COUNTS (sweeps with a stop, walks
+//                                              forked other than a sweep's first, those rolled
+//                                              back); 7 everything else                       core
 //   -DBA_PSTAMPS              PSTAMP(i)        the sweep kernel's prologue (absolute stamps)  core
 //   -DBA_KSTAMPS              KSTAMP(i)        the local-level Kalman kernel's phases, and
 //                             SSTAMP(i)        the structural kernels' (chain 0 prints)       core
@@ -65,6 +72,13 @@ struct StampCtx { long long last; double ph[8]; };
 #else
 #define FSTAMP(c, i) BA_STAMP_OFF
 #define FCOUNT(c, i, x) BA_STAMP_OFF
+#endif
+#if defined(BA_STAMPS) && defined(BA_STAMPS6)
+#define MSTAMP(c, i) BA_STAMP_ADD((c).ph, (c).last, i, BA_CORE_CLOCK, double)
+#define MCOUNT(c, i, x) do { (c).ph[i] += (double)(x); } while (0)
+#else
+#define MSTAMP(c, i) BA_STAMP_OFF
+#define MCOUNT(c, i, x) BA_STAMP_OFF
 #endif
 #ifdef BA_PSTAMPS
 #define PSTAMP(i) pst[i] = (long long)BA_CORE_CLOCK

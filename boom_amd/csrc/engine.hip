@@ -1366,7 +1366,7 @@ int ba_set_tuning(ba_engine *e, int32_t waves_per_chain, int32_t walk_policy,
   if (!e) return fail(BA_E_INVALID, "null engine");
   if (!(waves_per_chain == 0 || waves_per_chain == 1 || waves_per_chain == 2 || waves_per_chain == 4))
     return fail(BA_E_INVALID, "waves_per_chain must be 0, 1, 2 or 4");
-  if (walk_policy < -1 || walk_policy > 3) return fail(BA_E_INVALID, "walk_policy must be in [-1, 3]");
+  if (walk_policy < -1 || walk_policy > 4) return fail(BA_E_INVALID, "walk_policy must be in [-1, 4]");
   if (kcap_start < 0) return fail(BA_E_INVALID, "kcap_start must be non-negative");
   MUTATE(e);
   if (e->state_ready) {

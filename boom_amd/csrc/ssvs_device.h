@@ -1246,7 +1246,9 @@ __device__ __forceinline__ void propose_swap(const SsvsParams &P, Chain &ch,
 // stream numbers whatever happens, so the tail's stream position is known when
 // the sweep starts.  Wave 1 shuffles and walks the table while the master runs
 // the tail (swap proposal, sigma, beta) as if no flip were going to be accepted;
-// at the join a stop in the walk rolls the tail back.
+// at the join a stop in the walk rolls the tail back.  A walk resumed after a stop (and the
+// unforked first walk after a table was built) forks the same way -- the tail's position does
+// not depend on what the rest of the walk finds -- unless walk_policy is 3 or 4.
 //
 // The master's state machine: PH_BEGIN (shuffle or fork) -> PH_FLIPS (rounds of
 // proposals / table walks up to the next stop; a stop queues an event) ->
@@ -1256,7 +1258,8 @@ __device__ __forceinline__ void propose_swap(const SsvsParams &P, Chain &ch,
 enum : int { CMD_EXIT = 0, CMD_EVAL = 1, CMD_UNIF = 2, CMD_DECIDE = 3, CMD_SHUFFLE_DECIDE = 4 };
 // control block (doubles): 0 cmd, 1 k, 2 i0, 3..8 the current model's scalars
 // (their home), 9 nflips; u64 view at 10: flip_pos / uniform base position;
-// evaluator slots from 16; 44.. the forked tail's roll-back copy; 48.. the
+// evaluator slots from 16; 44.. the forked tail's roll-back copy (47: the walk
+// outstanding is not the sweep's first); 48.. the
 // launch's scalar accumulators (ACC_* order)
 enum : int { CT_CMD = 0, CT_K = 1, CT_I0 = 2, CT_LOGP = 3, CT_LP = 4, CT_LDV = 5,
              CT_LDA = 6, CT_Q = 7, CT_C = 8, CT_NFLIPS = 9, CT_POS = 10, CT_PERMSEL = 12,

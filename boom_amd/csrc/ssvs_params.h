@@ -43,10 +43,14 @@ enum {
   // build (shuffle uniforms, shuffle serial, refactor, proposal batches, swap,
   // sigma, beta, rest).  The production library's LDS sweep kernels count in two of them:
   // rebuilds that kept leading factor columns, and the columns they kept
-  // (SsvsParams::rebuild_policy; not slot 8, where the adaptive sampler keeps a margin)
+  // (SsvsParams::rebuild_policy; not slot 8, where the adaptive sampler keeps a margin),
+  // and in two more: table walks that ran beside the master's tail other than a quiet
+  // sweep's first (resumed after a stop, or started unforked), and those that found a stop
   ACC_PHASE0 = 8,
   ACC_PARTIAL_REBUILDS = 9,
   ACC_COLUMNS_KEPT = 10,
+  ACC_REFORKS = 11,
+  ACC_REFORK_ROLLBACKS = 12,
   ACC_COUNT = 16
 };
 
@@ -79,7 +83,9 @@ struct SsvsParams {
   const double *v_diag;    // chains x p
   // how a sweep's proposals are walked (ssvs_kernel.hip): 0 batch mode only, 1
   // adaptive (table look-ups after quiet sweeps; the default), 2 always the
-  // table, 3 adaptive without the forked quiet sweep (diagnostic A/B)
+  // table, 3 adaptive without the forked quiet sweep (diagnostic A/B), 4 adaptive,
+  // forking at a sweep's start only.  Under 1 and 2 the helper's table walks ALWAYS run
+  // beside the master's tail: the walk resumed after a stop forks again (4: it does not)
   int32_t walk_policy;
   int32_t slab_scales;  // mode 1: slab precision is Omega^{-1} / sigma^2 (MvnGivenScalarSigma)
 

@@ -256,7 +256,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
   AS_LDS int *sum_n = to_lds<int>(smem + lay.park + 1536);   // sweeps counted
   AS_LDS int *sum_g = to_lds<int>(smem + lay.park + 1792);   // variable (-1: none)
   sum_b[lane] = 0.0; sum_b2[lane] = 0.0; sum_n[lane] = 0; sum_g[lane] = -1;
-  if (lane < 11) ctl[CT_ACC + lane] = (lane == ACC_MIN_MARGIN) ? BA_INF : 0.0;
+  if (lane < 13) ctl[CT_ACC + lane] = (lane == ACC_MIN_MARGIN) ? BA_INF : 0.0;
   wave_sync();
 #define ACC_ADD(slot, x) do { if (lane == 0) ctl[CT_ACC + (slot)] += (double)(x); } while (0)
 #define ACC_MIN(x) do { if (lane == 0) ctl[CT_ACC + ACC_MIN_MARGIN] = fmin(ctl[CT_ACC + ACC_MIN_MARGIN], (x)); } while (0)
@@ -297,7 +297,8 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
   // runs the sweep's tail (swap proposal, sigma, beta) on the assumption that
   // no flip will be accepted -- the tail's stream position is known up front
   // (shuffle and flips consume p - 1 + nflips numbers whatever happens).  At
-  // the join a stop in the walk rolls the tail back.
+  // the join a stop in the walk rolls the tail back.  Stopped sweeps fork again: the walk
+  // resumed after the stop was served runs beside the tail in the same way (PH_FLIPS).
   bool spec = false;          // a forked walk is outstanding
   bool have_dr = false;       // wave 1's slot holds a walk result not yet handled
   int after_join = PH_COMMIT, spec_status = CHAIN_OK;
@@ -366,6 +367,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
       // tail running ahead waits for the join) --------------------------
       // (outside this block only logp, SS and pd of the model live in registers;
       // the scalars the evaluations need have their home in the control block)
+      MSTAMP(sx, 7);
       if (pe.kind == EV_FORCE && pe.f2 < 0 && other_ok && pe.f1 == other_var) {
         gam0_fresh = false;
         // The accepted flip leads to the model the other slot still holds (a
@@ -404,6 +406,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
         pe.lfw = pe.lrev = 0.0;
         pe.check_legal = false;
         STAMP(2);
+        MSTAMP(sx, 3);
         continue;
       }
       gam0_fresh = false;
@@ -496,6 +499,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
       pe.check_legal = false;
       STAMP(2);
       FSTAMP(sx, 4);
+      MSTAMP(sx, 3);
       continue;
     }
 
@@ -536,6 +540,17 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
         use_table = (P.walk_policy != 0) && (stops_prev <= 1 || P.walk_policy == 2);
         stops_prev = stops_now;
         stops_now = 0;
+        if (W > 1) {
+          // what a roll-back restores, parked once per sweep: nothing but a tail that stands
+          // changes these, so the copy serves the sweep's first walk and every resumed one
+          park[lane] = beta_m;
+          if (lane == 0) {
+            ctl[CT_ROLL + 0] = sigsq;
+            ctl[CT_ROLL + 1] = (double)failures;
+            ctl[CT_ROLL + 2] = beta_valid ? 1.0 : 0.0;
+            ctl[CT_ROLL + 3] = 0.0;   // (1: the outstanding walk is not the sweep's first)
+          }
+        }
         if (W > 1 && use_table && table_valid && model_checked && p > 1 && P.walk_policy != 3 && P.mode != 2 && !MLVS) {
           // ---- fork: wave 1 takes the permutation side of the sweep
           wave_sync();
@@ -561,12 +576,6 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
           TSTAMP(sx, 2);
           spec = true;
           spec_status = CHAIN_OK;
-          park[lane] = beta_m;
-          if (lane == 0) {
-            ctl[CT_ROLL + 0] = sigsq;
-            ctl[CT_ROLL + 1] = (double)failures;
-            ctl[CT_ROLL + 2] = beta_valid ? 1.0 : 0.0;
-          }
           i0 = 0;
           phase = commit_pending ? PH_COMMIT : PH_SWAP;  // (the joined sweep's summaries ride along)
           STAMP(1);
@@ -648,6 +657,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
         DecideResult dr;
         if (W > 1) {
           if (!have_dr) {
+          MSTAMP(sx, 7);
           if (lane == 0) {
             ctl[CT_CMD] = (double)CMD_DECIDE;
             ctl[CT_I0] = (double)i0;
@@ -657,7 +667,27 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
             ((AS_LDS uint64_t *)(ctl + CT_POS))[0] = flip_pos;
           }
           __syncthreads();
+          if (P.walk_policy < 3 && P.mode != 2 && !MLVS) {
+            // ---- this walk forks as a quiet sweep's does: the tail's stream position is
+            // flip_pos + nflips whatever the rest of the walk finds, so the master runs the
+            // tail beside it and meets wave 1 at the join (a stop there rolls the tail back).
+            // The condition is the fork's: table and model are good or no walk would have been
+            // commanded (use_table: the policy is not 0; model_checked holds from the first
+            // PH_BEGIN on), and p > 1 is there for the fork's shuffle, which this walk has not
+            // -- with that term spelt out <4, 4, 4> took 16 B/lane more scratch.  What a
+            // roll-back restores was parked at the sweep's start.
+            spec = true;
+            spec_status = CHAIN_OK;
+            if (lane == 0) ctl[CT_ROLL + 3] = 1.0;
+            MCOUNT(sx, 5, 1);
+#ifndef BA_STAMPS
+            ACC_ADD(ACC_REFORKS, 1);
+#endif
+            phase = commit_pending ? PH_COMMIT : PH_SWAP;
+            continue;
+          }
           __syncthreads();
+          MSTAMP(sx, 0);
           }
           have_dr = false;
           const lds_f64 *sl = ctl + CT_SLOT0 + CT_SLOT_STRIDE * 1;
@@ -677,6 +707,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
           continue;
         }
         ACC_ADD(ACC_PROPOSALS, dr.spos + 1 - i0);
+        MCOUNT(sx, 4, stops_now == 0);
         ++stops_now;
         i0 = dr.spos + 1;
         if (dr.kind == STOP_BAD) {
@@ -708,6 +739,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
         evmode = EVM_FILL;   // (re)build the table for the current model
         base = fill_j;
       }
+      MSTAMP(sx, 7);
       if (W > 1) {
         if (lane == 0) {
           ctl[CT_CMD] = (double)CMD_EVAL;
@@ -735,6 +767,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
           table_valid = true;
         }
         STAMP(3);
+        MSTAMP(sx, 2);
         continue;
       }
       // first stop over the whole round, in sweep order
@@ -760,6 +793,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
       const int kind = uni((int)sl[SL_KIND]);
       const int nprop = spos + 1 - i0;
       ACC_ADD(ACC_PROPOSALS, nprop);
+      MCOUNT(sx, 4, stops_now == 0);
       ++stops_now;
       if (kind == STOP_BAD) {
         status = CHAIN_NEGATIVE_SS;
@@ -810,13 +844,18 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
     }
 
     if (phase == PH_JOIN) {
+      MSTAMP(sx, 7);
       __syncthreads();
+      MSTAMP(sx, 1);
       spec = false;
+      // (where the walk that was outstanding began: read back from the command it was given,
+      // not carried in a register across the tail)
+      i0 = uni((int)ctl[CT_I0]);
       const lds_f64 *sl = ctl + CT_SLOT0 + CT_SLOT_STRIDE * 1;
       if ((int)sl[SL_F] < 0) {
         // no stop: the sweep's flips are all rejected and what ran ahead stands
         ACC_MIN(sl[SL_MARGIN]);
-        ACC_ADD(ACC_PROPOSALS, nflips);
+        ACC_ADD(ACC_PROPOSALS, nflips - i0);
         status = spec_status;
         phase = after_join;
         if (after_join == PH_COMMIT && status == CHAIN_OK) {
@@ -834,6 +873,10 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
         pe.kind = EV_NONE; pe.f1 = pe.f2 = -1; pe.lfw = pe.lrev = 0.0; pe.check_legal = false;
         have_dr = true;
         phase = PH_FLIPS;
+        MCOUNT(sx, 6, ctl[CT_ROLL + 3]);
+#ifndef BA_STAMPS
+        ACC_ADD(ACC_REFORK_ROLLBACKS, ctl[CT_ROLL + 3]);
+#endif
       }
       STAMP(3);
       continue;
@@ -976,7 +1019,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
   // (the chain's scalar accumulators, lane i <-> slot i: read here, with the summaries'
   // loads, written at the end -- not a round trip of lane 0's own after everything else)
   double *acc_row = P.acc + (size_t)chain * ACC_COUNT;
-  const double acc_old = (lane < 11) ? acc_row[lane] : 0.0;
+  const double acc_old = (lane < 13) ? acc_row[lane] : 0.0;
 #endif
   if (sum_g[lane] >= 0 && sum_n[lane]) {
     const size_t o = (size_t)chain * p + sum_g[lane];
@@ -1041,16 +1084,17 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
 #endif
 #if defined(BA_STAMPS) && defined(BA_STAMPS4)
     // (phases are wave 1's)
-#elif defined(BA_STAMPS) && (defined(BA_STAMPS2) || defined(BA_STAMPS3) || defined(BA_STAMPS5))
+#elif defined(BA_STAMPS) && (defined(BA_STAMPS2) || defined(BA_STAMPS3) || defined(BA_STAMPS5) || defined(BA_STAMPS6))
     SUBSTAMP(sx, 7);
     FSTAMP(sx, 7);
+    MSTAMP(sx, 7);
     for (int i = 0; i < 8; ++i) a[ACC_PHASE0 + i] += sx.ph[i];
 #elif defined(BA_STAMPS)
     for (int i = 0; i < 8; ++i) { a[ACC_PHASE0 + i] += st_ph[i]; a[ACC_SLOT_HITS] += st_ph[i]; }
 #endif
   }
 #ifndef BA_STAMPS
-  if (lane < 11) {
+  if (lane < 13) {
     const double inc = (lane == ACC_SWEEPS) ? (double)done : ctl[CT_ACC + lane];
     acc_row[lane] = (lane == ACC_MIN_MARGIN) ? fmin(acc_old, inc) : acc_old + inc;
   }

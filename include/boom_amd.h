@@ -146,7 +146,9 @@ int ba_set_options(ba_engine *e, int32_t max_flips, double swap_threshold,
  *   waves_per_chain  0 = engine chooses; 1, 2 or 4 wavefronts per chain
  *   walk_policy      -1 = default (adaptive); 0 batch mode only, 1 adaptive,
  *                    2 always the proposal table, 3 adaptive without forked
- *                    quiet sweeps
+ *                    quiet sweeps, 4 adaptive with a fork at a sweep's start
+ *                    only (under 1 and 2 a table walk resumed after a stop
+ *                    runs beside the sweep's tail as well)
  *   kcap_start       0 = default; first model capacity tried (16, 32, ...) */
 int ba_set_tuning(ba_engine *e, int32_t waves_per_chain, int32_t walk_policy,
                   int32_t kcap_start);

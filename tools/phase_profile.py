@@ -7,7 +7,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SUBN = os.environ.get("SUBSTAMPS", "0")
 SUB = SUBN != "0"
-os.environ["BOOM_AMD_LIB"] = os.path.join(ROOT, "tools", "build", {"0": "libboomamd_stamps.so", "1": "libboomamd_stamps2.so", "2": "libboomamd_stamps3.so", "3": "libboomamd_stamps4.so", "4": "libboomamd_stamps5.so"}[SUBN])
+os.environ["BOOM_AMD_LIB"] = os.path.join(ROOT, "tools", "build", {"0": "libboomamd_stamps.so", "1": "libboomamd_stamps2.so", "2": "libboomamd_stamps3.so", "3": "libboomamd_stamps4.so", "4": "libboomamd_stamps5.so", "5": "libboomamd_stamps6.so"}[SUBN])
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import time
@@ -52,6 +52,9 @@ elif SUBN == "3":
 elif SUBN == "4":
     names = ["rebuild: gathers, prior, shift, r, c", "rebuild: inserted row", "rebuild: column loop, log dets",
              "rebuild: w, model value", "rebuild: publish / restore", None, None, "everything else"]
+elif SUBN == "5":
+    names = ["master: waiting for an unforked walk", "master: waiting at the join", "master: fill rounds",
+             "master: events (rebuild / slot switch)", None, None, None, "everything else"]
 elif SUB:
     names = ["batch: index fetch", "batch: classify", "batch: V gather", "batch: V solve",
              "batch: A gather", "batch: A solve", "batch: epilogue", "outside batches"]
@@ -63,6 +66,15 @@ if SUBN == "4":
     print("rebuilds/sweep %.4f, cycles/rebuild %.0f (column loop %.0f = %.1f %%), columns kept/rebuild %.2f"
           % (nreb / sm["sweeps"], ph[:5].sum() / max(nreb, 1), ph[2] / max(nreb, 1),
              100 * ph[2] / max(ph[:5].sum(), 1), kept / max(nreb, 1)))
+if SUBN == "5":
+    # (slots 4, 5 and 6 of this build are counts, not cycles)
+    nstop, nref, nroll = ph[4], ph[5], ph[6]
+    ph = ph.copy()
+    ph[4] = ph[5] = ph[6] = 0.0
+    print("sweeps with a stop/sweep %.4f, walks forked other than a sweep's first/sweep %.4f, of those rolled back %.4f;"
+          " per sweep with a stop: unforked-walk wait %.0f, join wait %.0f, fill rounds %.0f, events %.0f cycles"
+          % (nstop / sm["sweeps"], nref / sm["sweeps"], nroll / sm["sweeps"], ph[0] / max(nstop, 1),
+             ph[1] / max(nstop, 1), ph[2] / max(nstop, 1), ph[3] / max(nstop, 1)))
 tot = ph.sum()
 if not SUB:
     print("  per chain: mean %.0f cycles, slowest %.0f cycles (%.2fx)" % (tot / chains, sm["slot_hits"], sm["slot_hits"] * chains / tot))
