@@ -67,6 +67,23 @@ py::array_t<double> matrix_to_numpy(const Matrix &m) {
 }
 Vector optional_vector(const py::object &a) { return a.is_none() ? Vector() : vector_from(a.cast<NpArray>()); }
 
+// what the models of the latent-data families (Poisson, logit) share; scale: a forecast's exposures or trials
+template <class Model, class... Extra>
+py::class_<Model, Extra...> latent_data_class(py::class_<Model, Extra...> cls, const char *scale, const char *forecast_doc) {
+  return cls
+      .def("latent_values", [](const Model &m, int chain) { return to_numpy(m.latent_values(chain)); },
+           py::arg("chain") = 0, "the latent values of one chain (0 at a missing step)")
+      .def("latent_precisions", [](const Model &m, int chain) { return to_numpy(m.latent_precisions(chain)); },
+           py::arg("chain") = 0, "the latent values' precisions in one chain (0 at a missing step)")
+      .def("set_latent_data", [](Model &m, const NpArray &value, const NpArray &precision, int chain) {
+             m.set_latent_data(vector_from(value), vector_from(precision), chain);
+           }, py::arg("value"), py::arg("precision"), py::arg("chain") = -1)
+      .def("impute_state", &Model::impute_state)
+      .def("simulate_forecast", [](Model &m, const NpArray &predictors, const py::object &scale) {
+             return forecast_to_numpy(m.simulate_forecast(matrix_from(predictors), optional_vector(scale)));
+           }, py::arg("predictors"), py::arg(scale) = py::none(), forecast_doc);
+}
+
 // GlmCoefs as the drivers use it: model.coef.drop_all() / add / inc / Beta
 struct CoefView {
   RegressionModel *model;
@@ -813,7 +830,9 @@ PYBIND11_MODULE(_boom, boom) {
 
   // ---- bsts family = "poisson" (StateSpacePoissonModel, StateSpacePoissonPosteriorSampler): the
   // state space model's bindings, inherited, + the Poisson observation model's ------------------
-  py::class_<StateSpacePoissonModel, StateSpaceRegressionModel, Ptr<StateSpacePoissonModel>>(boom, "StateSpacePoissonModel")
+  latent_data_class(py::class_<StateSpacePoissonModel, StateSpaceRegressionModel, Ptr<StateSpacePoissonModel>>(
+                        boom, "StateSpacePoissonModel"), "exposure",
+                    "one predictive draw of the next counts per chain (chains x horizon); exposure: default ones")
       .def(py::init([](const NpArray &counts, const NpArray &exposure, const NpArray &predictors,
                        const std::vector<bool> &is_observed, int chains, uint64_t seed, int device) {
              return new StateSpacePoissonModel(vector_from(counts), vector_from(exposure), matrix_from(predictors),
@@ -832,19 +851,7 @@ PYBIND11_MODULE(_boom, boom) {
            },
            py::arg("counts"), py::arg("ncomp"), py::arg("mu"), py::arg("sigma"), py::arg("weight"),
            py::arg("largest_index"),
-           "the reference's normal mixtures for the negative log-gamma densities (its data)")
-      .def("latent_values", [](const StateSpacePoissonModel &m, int chain) { return to_numpy(m.latent_values(chain)); },
-           py::arg("chain") = 0, "the latent values of one chain (0 at a missing step)")
-      .def("latent_precisions", [](const StateSpacePoissonModel &m, int chain) { return to_numpy(m.latent_precisions(chain)); },
-           py::arg("chain") = 0, "the latent values' precisions in one chain (0 at a missing step)")
-      .def("set_latent_data", [](StateSpacePoissonModel &m, const NpArray &value, const NpArray &precision, int chain) {
-             m.set_latent_data(vector_from(value), vector_from(precision), chain);
-           }, py::arg("value"), py::arg("precision"), py::arg("chain") = -1)
-      .def("impute_state", &StateSpacePoissonModel::impute_state)
-      .def("simulate_forecast", [](StateSpacePoissonModel &m, const NpArray &predictors, const py::object &exposure) {
-             return forecast_to_numpy(m.simulate_forecast(matrix_from(predictors), optional_vector(exposure)));
-           }, py::arg("predictors"), py::arg("exposure") = py::none(),
-           "one predictive draw of the next counts per chain (chains x horizon); exposure: default ones");
+           "the reference's normal mixtures for the negative log-gamma densities (its data)");
   py::class_<StateSpacePoissonPosteriorSampler, PosteriorSampler, Ptr<StateSpacePoissonPosteriorSampler>>(
       boom, "StateSpacePoissonPosteriorSampler")
       .def(py::init([](StateSpacePoissonModel *model, const Ptr<MvnModel> &slab,
@@ -858,26 +865,16 @@ PYBIND11_MODULE(_boom, boom) {
 
   // ---- bsts family = "logit" (StateSpaceLogitModel, StateSpaceLogitPosteriorSampler): the state
   // space model's bindings, inherited, + the binomial logit observation model's -----------------
-  py::class_<StateSpaceLogitModel, StateSpaceRegressionModel, Ptr<StateSpaceLogitModel>>(boom, "StateSpaceLogitModel")
+  latent_data_class(py::class_<StateSpaceLogitModel, StateSpaceRegressionModel, Ptr<StateSpaceLogitModel>>(
+                        boom, "StateSpaceLogitModel"), "trials",
+                    "one predictive draw of the next success counts per chain (chains x horizon); trials: default ones")
       .def(py::init([](const NpArray &successes, const NpArray &trials, const NpArray &predictors,
                        const std::vector<bool> &is_observed, int chains, uint64_t seed, int device, int clt_threshold) {
              return new StateSpaceLogitModel(vector_from(successes), vector_from(trials), matrix_from(predictors),
                                              is_observed, chains, seed, device, clt_threshold);
            }),
            py::arg("successes"), py::arg("trials"), py::arg("predictors"), py::arg("is_observed") = std::vector<bool>(),
-           py::arg("chains") = 1, py::arg("seed") = 8675309ull, py::arg("device") = 0, py::arg("clt_threshold") = 5)
-      .def("latent_values", [](const StateSpaceLogitModel &m, int chain) { return to_numpy(m.latent_values(chain)); },
-           py::arg("chain") = 0, "the latent values of one chain (0 at a missing step)")
-      .def("latent_precisions", [](const StateSpaceLogitModel &m, int chain) { return to_numpy(m.latent_precisions(chain)); },
-           py::arg("chain") = 0, "the latent values' precisions in one chain (0 at a missing step)")
-      .def("set_latent_data", [](StateSpaceLogitModel &m, const NpArray &value, const NpArray &precision, int chain) {
-             m.set_latent_data(vector_from(value), vector_from(precision), chain);
-           }, py::arg("value"), py::arg("precision"), py::arg("chain") = -1)
-      .def("impute_state", &StateSpaceLogitModel::impute_state)
-      .def("simulate_forecast", [](StateSpaceLogitModel &m, const NpArray &predictors, const py::object &trials) {
-             return forecast_to_numpy(m.simulate_forecast(matrix_from(predictors), optional_vector(trials)));
-           }, py::arg("predictors"), py::arg("trials") = py::none(),
-           "one predictive draw of the next success counts per chain (chains x horizon); trials: default ones");
+           py::arg("chains") = 1, py::arg("seed") = 8675309ull, py::arg("device") = 0, py::arg("clt_threshold") = 5);
   py::class_<StateSpaceLogitPosteriorSampler, PosteriorSampler, Ptr<StateSpaceLogitPosteriorSampler>>(
       boom, "StateSpaceLogitPosteriorSampler")
       .def(py::init([](StateSpaceLogitModel *model, const Ptr<MvnModel> &slab,

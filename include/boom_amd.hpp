@@ -25,6 +25,7 @@
 #include <random>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "boom_amd.h"
@@ -1619,160 +1620,138 @@ class StateSpaceStudentPosteriorSampler : public PosteriorSampler {
   Ptr<ChisqModel> siginv_;
 };
 
-// ---- bsts family = "poisson" --------------------------------------------------------------
+// ---- bsts family = "poisson", "logit" ------------------------------------------------------
+// What the two latent-data families share: an observed step carries a latent value and its
+// precision, the observation model's sampler takes a fixed-precision slab, and sigma^2 stays 1.
+// A family is its entry points and the words of its texts.
+struct LatentDataFamily {
+  int (*sweep)(ba_engine *, int32_t);
+  int (*impute_state)(ba_engine *);
+  int (*get_latent)(ba_engine *, int64_t, double *, double *);
+  int (*set_latent)(ba_engine *, int64_t, const double *, const double *);
+  int (*forecast)(ba_engine *, int32_t, const double *, const double *, double *);
+  const char *forecast_scale_text;   // a forecast's exposures (trials) of the wrong length
+  const char *name;                  // in the sampler's texts
+};
+inline const LatentDataFamily kPoissonFamily = {
+    ba_ss_poisson_sweep, ba_ss_poisson_impute_state, ba_ss_poisson_get_latent, ba_ss_poisson_set_latent,
+    ba_ss_poisson_forecast, "One exposure per forecast step is needed.", "Poisson"};
+inline const LatentDataFamily kLogitFamily = {
+    ba_ss_logit_sweep, ba_ss_logit_impute_state, ba_ss_logit_get_latent, ba_ss_logit_set_latent,
+    ba_ss_logit_forecast, "One trial count per forecast step is needed.", "logit"};
+// the state of StateSpaceRegressionModel under a latent-data observation model, on the device.
+// One observation per time step, regression present.  Chain 0 backs the accessors' defaults.
+class StateSpaceLatentDataModel : public StateSpaceRegressionModel {
+ public:
+  // one chain's latent data (Augmented{Poisson,Binomial}RegressionData::latent_data_value and
+  // the precisions behind latent_data_variance); 0 at a missing step
+  Vector latent_values(int chain = 0) const { return latent(chain).first; }
+  Vector latent_precisions(int chain = 0) const { return latent(chain).second; }
+  void set_latent_data(const Vector &value, const Vector &precision, int chain = -1) {   // set_latent_data, every step (chain -1: every chain)
+    if ((int)value.size() != time_dimension() || (int)precision.size() != time_dimension())
+      report_error("One latent value and one precision per time step are needed.");
+    engine()->check(family_.set_latent(engine()->get(), chain, value.data(), precision.data()));
+  }
+  void impute_state() {   // Base::impute_state with the current parameters and latent data
+    finalize_state();
+    engine()->check(family_.impute_state(engine()->get()));
+  }
+  // simulate_forecast(rng, forecast_predictors, exposure or trials, final_state) for EVERY chain's
+  // current draw: column c is chain c's draw of the next (success) counts (an empty scale: ones)
+  Matrix simulate_forecast(const Matrix &predictors, const Vector &scale = Vector()) {
+    if (predictors.ncol() != xdim()) report_error("The forecast predictors do not match the model dimension.");
+    if (!scale.empty() && (int)scale.size() != predictors.nrow()) report_error(family_.forecast_scale_text);
+    Matrix ans(predictors.nrow(), engine()->chains());
+    engine()->check(family_.forecast(engine()->get(), predictors.nrow(), predictors.data(),
+                                     scale.empty() ? nullptr : scale.data(), ans.data()));
+    return ans;
+  }
+  const LatentDataFamily &family() const { return family_; }
+ protected:
+  template <class... Args>   // (args: the family's constructor of StateSpaceRegressionModel)
+  StateSpaceLatentDataModel(const LatentDataFamily &family, Args &&...args)
+      : StateSpaceRegressionModel(std::forward<Args>(args)...), family_(family) {}
+ private:
+  std::pair<Vector, Vector> latent(int chain) const {
+    Vector v(time_dimension()), q(time_dimension());
+    engine()->check(family_.get_latent(engine()->get(), chain, v.data(), q.data()));
+    return {v, q};
+  }
+  const LatentDataFamily &family_;
+};
+// ... and its sampler: the priors of the observation model's sampler, a fixed-precision slab and a spike
+class StateSpaceLatentDataPosteriorSampler : public PosteriorSampler {
+ public:
+  void draw() override {                     // StateSpacePosteriorSampler.cpp:42-64
+    model_->finalize_state();
+    check(model_->family().sweep(h(), 1));
+    check(ba_sync(h()));
+  }
+  double logpri() const override {
+    report_error(std::string("logpri() is not implemented for the ") + model_->family().name + " state space sampler");
+    return 0;
+  }
+  void set_seed(unsigned long s) override { check(ba_seed(h(), s)); }
+  void limit_model_selection(int max_flips) {
+    check(ba_sss_set_slab(h(), slab_->mu().data(), slab_->siginv().data(), 0, max_flips));
+  }
+ protected:
+  StateSpaceLatentDataPosteriorSampler(StateSpaceLatentDataModel *model, const Ptr<MvnModel> &slab,
+                                       const Ptr<VariableSelectionPrior> &spike)
+      : model_(model), slab_(slab) {
+    if (slab->dim() != model->xdim()) report_error("Slab does not match model dimension.");
+    if ((int)spike->potential_nvars() != model->xdim()) report_error("Spike does not match model dimension.");
+    limit_model_selection(-1);
+    check(ba_set_spike(h(), spike->prior_inclusion_probabilities().data(), spike->max_model_size()));
+    std::vector<uint8_t> g0(model->xdim(), 0);
+    check(ba_set_state(h(), -1, g0.data(), nullptr, 1.0));
+  }
+ private:
+  ba_engine *h() const { return model_->engine()->get(); }
+  void check(int rc) const { model_->engine()->check(rc); }
+  StateSpaceLatentDataModel *model_;
+  Ptr<MvnModel> slab_;
+};
+
 // StateSpacePoissonModel + StateSpacePoissonPosteriorSampler (Models/StateSpace/
-// StateSpacePoissonModel.hpp, PosteriorSamplers/StateSpacePoissonPosteriorSampler.cpp:79-147): the
-// state of StateSpaceRegressionModel under PoissonRegressionModel's observations, on the device
-// (ba_ss_poisson_*).  One observation per time step, regression present.  The mixture table is
-// handed over as PoissonRegressionModel's is.  Chain 0 backs the accessors' defaults.
-class StateSpacePoissonModel : public StateSpaceRegressionModel {
+// StateSpacePoissonModel.hpp, PosteriorSamplers/StateSpacePoissonPosteriorSampler.cpp:79-147):
+// PoissonRegressionModel's observations (ba_ss_poisson_*).  The mixture table is handed over as
+// PoissonRegressionModel's is; slab and spike as PoissonRegressionSpikeSlabSampler takes them.
+class StateSpacePoissonModel : public StateSpaceLatentDataModel {
  public:
   StateSpacePoissonModel(const Vector &counts, const Vector &exposure, const Matrix &X,
                          const std::vector<bool> &observed, int chains = 1, uint64_t seed = 8675309, int device = 0)
-      : StateSpaceRegressionModel(PoissonFamily(), counts, exposure, X, observed, chains, seed, device) {}
+      : StateSpaceLatentDataModel(kPoissonFamily, PoissonFamily(), counts, exposure, X, observed, chains, seed, device) {}
   void set_mixture_table(const NormalMixtureTable &t) {
     if (t.counts.size() != t.ncomp.size()) report_error("the mixture table's counts and ncomp differ in length");
     engine()->check(ba_poisson_set_mixtures(engine()->get(), (int32_t)t.counts.size(), t.counts.data(), t.ncomp.data(),
                                             t.mu.data(), t.sigma.data(), t.weight.data(), t.largest_index));
   }
-  // one chain's latent data (AugmentedPoissonRegressionData::latent_data_value and the
-  // precisions behind latent_data_variance); 0 at a missing step
-  Vector latent_values(int chain = 0) const {
-    Vector v(time_dimension()), q(time_dimension());
-    engine()->check(ba_ss_poisson_get_latent(engine()->get(), chain, v.data(), q.data()));
-    return v;
-  }
-  Vector latent_precisions(int chain = 0) const {
-    Vector v(time_dimension()), q(time_dimension());
-    engine()->check(ba_ss_poisson_get_latent(engine()->get(), chain, v.data(), q.data()));
-    return q;
-  }
-  void set_latent_data(const Vector &value, const Vector &precision, int chain = -1) {   // set_latent_data, every step (chain -1: every chain)
-    if ((int)value.size() != time_dimension() || (int)precision.size() != time_dimension())
-      report_error("One latent value and one precision per time step are needed.");
-    engine()->check(ba_ss_poisson_set_latent(engine()->get(), chain, value.data(), precision.data()));
-  }
-  void impute_state() {   // Base::impute_state with the current parameters and latent data
-    finalize_state();
-    engine()->check(ba_ss_poisson_impute_state(engine()->get()));
-  }
-  // simulate_forecast(rng, forecast_predictors, exposure, final_state) for EVERY chain's current
-  // draw: column c is chain c's draw of the next counts (an empty exposure: ones)
-  Matrix simulate_forecast(const Matrix &predictors, const Vector &exposure = Vector()) {
-    if (predictors.ncol() != xdim()) report_error("The forecast predictors do not match the model dimension.");
-    if (!exposure.empty() && (int)exposure.size() != predictors.nrow())
-      report_error("One exposure per forecast step is needed.");
-    Matrix ans(predictors.nrow(), engine()->chains());
-    engine()->check(ba_ss_poisson_forecast(engine()->get(), predictors.nrow(), predictors.data(),
-                                           exposure.empty() ? nullptr : exposure.data(), ans.data()));
-    return ans;
-  }
 };
-// StateSpacePoissonPosteriorSampler(model, observation model sampler's priors): slab and spike as
-// PoissonRegressionSpikeSlabSampler takes them
-class StateSpacePoissonPosteriorSampler : public PosteriorSampler {
+class StateSpacePoissonPosteriorSampler : public StateSpaceLatentDataPosteriorSampler {
  public:
   StateSpacePoissonPosteriorSampler(StateSpacePoissonModel *model, const Ptr<MvnModel> &slab,
                                     const Ptr<VariableSelectionPrior> &spike)
-      : model_(model), slab_(slab) {
-    if (slab->dim() != model->xdim()) report_error("Slab does not match model dimension.");
-    if ((int)spike->potential_nvars() != model->xdim()) report_error("Spike does not match model dimension.");
-    check(ba_sss_set_slab(h(), slab->mu().data(), slab->siginv().data(), 0, -1));
-    check(ba_set_spike(h(), spike->prior_inclusion_probabilities().data(), spike->max_model_size()));
-    std::vector<uint8_t> g0(model->xdim(), 0);
-    check(ba_set_state(h(), -1, g0.data(), nullptr, 1.0));
-  }
-  void draw() override {                     // StateSpacePosteriorSampler.cpp:42-64
-    model_->finalize_state();
-    check(ba_ss_poisson_sweep(h(), 1));
-    check(ba_sync(h()));
-  }
-  double logpri() const override { report_error("logpri() is not implemented for the Poisson state space sampler"); return 0; }
-  void set_seed(unsigned long s) override { check(ba_seed(h(), s)); }
-  void limit_model_selection(int max_flips) {
-    check(ba_sss_set_slab(h(), slab_->mu().data(), slab_->siginv().data(), 0, max_flips));
-  }
- private:
-  ba_engine *h() const { return model_->engine()->get(); }
-  void check(int rc) const { model_->engine()->check(rc); }
-  StateSpacePoissonModel *model_;
-  Ptr<MvnModel> slab_;
+      : StateSpaceLatentDataPosteriorSampler(model, slab, spike) {}
 };
 
-// ---- bsts family = "logit" ----------------------------------------------------------------
 // StateSpaceLogitModel + StateSpaceLogitPosteriorSampler (Models/StateSpace/
-// StateSpaceLogitModel.hpp, PosteriorSamplers/StateSpaceLogitPosteriorSampler.cpp:49-123): the
-// state of StateSpaceRegressionModel under BinomialLogitModel's observations, on the device
-// (ba_ss_logit_*).  One observation per time step, regression present.  Chain 0 backs the
-// accessors' defaults.
-class StateSpaceLogitModel : public StateSpaceRegressionModel {
+// StateSpaceLogitModel.hpp, PosteriorSamplers/StateSpaceLogitPosteriorSampler.cpp:49-123):
+// BinomialLogitModel's observations (ba_ss_logit_*); slab and spike as BinomialLogitSpikeSlabSampler
+// takes them.
+class StateSpaceLogitModel : public StateSpaceLatentDataModel {
  public:
   StateSpaceLogitModel(const Vector &successes, const Vector &trials, const Matrix &X,
                        const std::vector<bool> &observed, int chains = 1, uint64_t seed = 8675309, int device = 0,
                        int clt_threshold = 5)
-      : StateSpaceRegressionModel(LogitFamily(), successes, trials, X, observed, clt_threshold, chains, seed, device) {}
-  // one chain's latent data (AugmentedBinomialRegressionData::latent_data_value and the
-  // precisions behind latent_data_variance); 0 at a missing step
-  Vector latent_values(int chain = 0) const {
-    Vector v(time_dimension()), q(time_dimension());
-    engine()->check(ba_ss_logit_get_latent(engine()->get(), chain, v.data(), q.data()));
-    return v;
-  }
-  Vector latent_precisions(int chain = 0) const {
-    Vector v(time_dimension()), q(time_dimension());
-    engine()->check(ba_ss_logit_get_latent(engine()->get(), chain, v.data(), q.data()));
-    return q;
-  }
-  void set_latent_data(const Vector &value, const Vector &precision, int chain = -1) {   // set_latent_data, every step (chain -1: every chain)
-    if ((int)value.size() != time_dimension() || (int)precision.size() != time_dimension())
-      report_error("One latent value and one precision per time step are needed.");
-    engine()->check(ba_ss_logit_set_latent(engine()->get(), chain, value.data(), precision.data()));
-  }
-  void impute_state() {   // Base::impute_state with the current parameters and latent data
-    finalize_state();
-    engine()->check(ba_ss_logit_impute_state(engine()->get()));
-  }
-  // simulate_forecast(rng, forecast_predictors, trials, final_state) for EVERY chain's current
-  // draw: column c is chain c's draw of the next success counts (an empty trials: ones)
-  Matrix simulate_forecast(const Matrix &predictors, const Vector &trials = Vector()) {
-    if (predictors.ncol() != xdim()) report_error("The forecast predictors do not match the model dimension.");
-    if (!trials.empty() && (int)trials.size() != predictors.nrow())
-      report_error("One trial count per forecast step is needed.");
-    Matrix ans(predictors.nrow(), engine()->chains());
-    engine()->check(ba_ss_logit_forecast(engine()->get(), predictors.nrow(), predictors.data(),
-                                         trials.empty() ? nullptr : trials.data(), ans.data()));
-    return ans;
-  }
+      : StateSpaceLatentDataModel(kLogitFamily, LogitFamily(), successes, trials, X, observed, clt_threshold, chains, seed,
+                                  device) {}
 };
-// StateSpaceLogitPosteriorSampler(model, observation model sampler's priors): slab and spike as
-// BinomialLogitSpikeSlabSampler takes them
-class StateSpaceLogitPosteriorSampler : public PosteriorSampler {
+class StateSpaceLogitPosteriorSampler : public StateSpaceLatentDataPosteriorSampler {
  public:
   StateSpaceLogitPosteriorSampler(StateSpaceLogitModel *model, const Ptr<MvnModel> &slab,
                                   const Ptr<VariableSelectionPrior> &spike)
-      : model_(model), slab_(slab) {
-    if (slab->dim() != model->xdim()) report_error("Slab does not match model dimension.");
-    if ((int)spike->potential_nvars() != model->xdim()) report_error("Spike does not match model dimension.");
-    check(ba_sss_set_slab(h(), slab->mu().data(), slab->siginv().data(), 0, -1));
-    check(ba_set_spike(h(), spike->prior_inclusion_probabilities().data(), spike->max_model_size()));
-    std::vector<uint8_t> g0(model->xdim(), 0);
-    check(ba_set_state(h(), -1, g0.data(), nullptr, 1.0));
-  }
-  void draw() override {                     // StateSpacePosteriorSampler.cpp:42-64
-    model_->finalize_state();
-    check(ba_ss_logit_sweep(h(), 1));
-    check(ba_sync(h()));
-  }
-  double logpri() const override { report_error("logpri() is not implemented for the logit state space sampler"); return 0; }
-  void set_seed(unsigned long s) override { check(ba_seed(h(), s)); }
-  void limit_model_selection(int max_flips) {
-    check(ba_sss_set_slab(h(), slab_->mu().data(), slab_->siginv().data(), 0, max_flips));
-  }
- private:
-  ba_engine *h() const { return model_->engine()->get(); }
-  void check(int rc) const { model_->engine()->check(rc); }
-  StateSpaceLogitModel *model_;
-  Ptr<MvnModel> slab_;
+      : StateSpaceLatentDataPosteriorSampler(model, slab, spike) {}
 };
 
 // ---- Quantile regression spike and slab --------------------------------------------------

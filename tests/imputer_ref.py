@@ -639,7 +639,7 @@ POISSON_EXPOSURE = [1.0, 0.25, 40.0]
 def poisson_table():
     """the mixtures of the fixture tests/test_poisson_gpu.py loads, as a table that ends at its
     last count: (dict for Mixtures, counts y of the cases: 0, 1, inside, the last, one beyond)"""
-    from test_oracle_golden import _golden_mix, load
+    from golden_lib import _golden_mix, load
     mix = dict(_golden_mix(load("poisson_exposure")))
     last = int(mix["counts"][-1])
     mix["largest_index"] = last + 1

@@ -1,27 +1,17 @@
 """A restatement of StateSpacePosteriorSampler::draw() for StateSpaceLogitModel (bsts family =
 "logit") on the device's substreams, one chain, in Python over the oracle's primitives: the parity
-yardstick of ba_ss_logit_sweep, built as tests/ss_poisson_oracle.py is (whose structure, filter,
-state-model statistics, SpikeSlabSampler driver and dense posterior it imports).
+yardstick of ba_ss_logit_sweep.  The round is tests/ss_family_oracle.py's (StateSpaceLogitPosterior
+Sampler.cpp:82-123); this file is what the family adds to it.
 
-Per-step data: an observed step carries successes y_t, trials n_t, a latent value v_t and a
-precision q_t (0 and 4 / n_t in a new model, StateSpaceLogitModel.cpp:67-74); the filter sees
-v_t - x_t'beta with the observation variance H_t = 1 / q_t; a missing step has no observation and
-H_t = pi^2 / 3, and its successes and trials are never read.
+Per-step data: an observed step carries successes y_t and trials n_t; a new model has v_t = 0 and
+q_t = 4 / n_t (StateSpaceLogitModel.cpp:67-74); a missing step has H_t = pi^2 / 3, and its successes
+and trials are never read.
 
-One draw() (StateSpacePosteriorSampler.cpp:42-64, StateSpaceLogitPosteriorSampler.cpp:82-123):
-  0. the first time: impute_state with the latent data in hand, then one imputation whose values
-     are all overwritten in step 3 before anything reads them -- only its slots are used up, so
-     round r of a fresh sampler imputes with s = r + 1;
-  1. the observation model's sampler with fix_latent_data(true) (BinomialLogitSpikeSlabSampler::
-     draw: its own shuffle -- every position swaps with one drawn from the whole range --, then
-     indicators and beta at sigma^2 = 1 with a fixed-precision slab) on the complete-data
-     statistics the last impute_state left (X'QX, X'Q(v - Z alpha), observed steps), stream 3;
-  2. every state model's variance draw (ss_student_oracle's);
-  3. impute_nonstate_latent_data: BinomialLogitCltDataImputer::impute(n_t, y_t, eta_t) with
-     eta_t = Z_t'alpha_t + x_t'beta (alpha the last state draw, beta the new one) for the observed
-     steps, stream 9, slot s T + t of 256 in the sampler's s-th imputation; v_t = sum / info,
-     q_t = info;
-  4. impute_state: the simulation smoother with H_t, then the statistics over the observed steps.
+The observation model's sampler is BinomialLogitSpikeSlabSampler::draw with its own shuffle (every
+position swaps with one drawn from the whole range).
+
+The imputation: BinomialLogitCltDataImputer::impute(n_t, y_t, eta_t) for the observed steps, stream 9,
+slot s T + t of 256 in the sampler's s-th imputation; v_t = sum / info, q_t = info.
 
 The imputer (BinomialLogitDataImputer.cpp:119-211):
   n_t <= clt_threshold  per trial a logistic draw on the side of 0 its outcome says (bo_runif on
@@ -43,10 +33,9 @@ import math
 
 import numpy as np
 
-from oracle_lib import BoRng, _dp, _u8, f64, fcol
-from ss_poisson_oracle import (Structure, bonferroni_bound, dense_posterior, impute_state,  # noqa: F401
-                               moment_z, state_model_suf, _copy)
-from ss_student_oracle import SsStudentOracle
+from oracle_lib import BoRng, _dp
+from ss_family_oracle import SsFamilyOracle, draw_sss
+from ss_poisson_oracle import _copy
 
 LOGIT_STREAM, LOGIT_STRIDE = 9, 256
 MISSING_VARIANCE = 3.289868133696452872944830333292   # Constants::pi_squared_over_3
@@ -73,8 +62,6 @@ def declare(L):
     L.bo_rmulti.restype = C.c_int
     L.bo_test_rbinom.argtypes = [C.c_void_p, C.c_uint, C.c_double]
     L.bo_test_rbinom.restype = C.c_uint
-    L.bo_sss_set_shuffle_kind.argtypes = [C.c_void_p, C.c_int]
-    L.bo_sss_set_shuffle_kind.restype = None
 
 
 class Record:
@@ -263,70 +250,19 @@ def impute(o, seed, chain, successes, trials, eta, observed, s, clt, rec):
     return total, info
 
 
-def observation_variances(q, observed):
-    return np.array([1.0 / q[t] if observed[t] else MISSING_VARIANCE for t in range(len(q))])
-
-
-def draw_sss(o, rng, xtx, xty, mu, prec, pi, gamma, beta, max_flips=-1):
-    """BinomialLogitSpikeSlabSampler::draw_model_indicators / draw_beta with a fixed-precision slab:
-    ss_poisson_oracle.draw_sss with the sampler's own shuffle (bo_sss, scales = 0, shuffle kind 1)
-    continuing the stream `rng` (updated in place): (gamma, beta)"""
-    L, p = o.lib, len(xty)
-    o._declare_sss()
-    declare(L)
-    h = L.bo_sss_create(p, _dp(fcol(xtx)), _dp(f64(xty)), 0, _dp(f64(mu)), _dp(fcol(prec)), _dp(f64(pi)))
-    try:
-        L.bo_sss_set_shuffle_kind(h, 1)
-        L.bo_sss_set_options(h, -1, int(max_flips))
-        L.bo_sss_set_state(h, _u8(np.ascontiguousarray(gamma, dtype=np.uint8)), _dp(f64(beta)))
-        C.memmove(L.bo_sss_rng(h), C.byref(rng), C.sizeof(BoRng))
-        st = L.bo_sss_draw_model_indicators(h, 1.0)
-        if st == 0:
-            st = L.bo_sss_draw_beta(h, 1.0)
-        if st:
-            raise RuntimeError("SpikeSlabSampler status %d" % st)
-        g, b = np.zeros(p, dtype=np.uint8), np.zeros(p)
-        L.bo_sss_get_state(h, _u8(g), _dp(b))
-        C.memmove(C.byref(rng), L.bo_sss_rng(h), C.sizeof(BoRng))
-    finally:
-        L.bo_sss_destroy(h)
-    return g, b
-
-
-class SsLogitOracle:
+class SsLogitOracle(SsFamilyOracle):
     """one chain of StateSpaceLogitPosteriorSampler on the device's substreams"""
+
+    MISSING_VARIANCE = MISSING_VARIANCE
+    SHUFFLE_KIND = 1
 
     def __init__(self, o, successes, trials, X, observed, blocks, mu, prec, pi, seed, chain, gamma0, beta0=None,
                  clt_threshold=5, max_flips=-1):
-        self.o, self.L = o, o.lib
-        declare(self.L)
-        self.X = np.asarray(X, dtype=np.float64)
-        self.T, self.p = self.X.shape
-        self.obs = (np.ones(self.T, bool) if observed is None else np.asarray(observed).astype(bool))
+        declare(o.lib)
         self.successes, self.trials = np.asarray(successes, dtype=float), np.asarray(trials, dtype=float)
         self.clt = int(clt_threshold)
-        self.S = Structure(blocks)
-        self.mu, self.prec, self.pi = f64(mu), np.asarray(prec, dtype=np.float64), f64(pi)
-        self.seed, self.chain, self.max_flips = int(seed), int(chain), int(max_flips)
-        self.gamma = np.ascontiguousarray(gamma0, dtype=np.uint8).copy()
-        self.beta = np.zeros(self.p) if beta0 is None else f64(beta0) * self.gamma
-        # the state models' parameters, priors and samplers' streams: the Student restatement's
-        # (built on a series that only sizes the handle; its observation model is not used)
-        helper = SsStudentOracle(o, np.zeros(self.T), self.X, None if observed is None else observed, blocks,
-                                 self.mu, self.prec, self.pi, seed, chain, self.gamma)
-        self._sm = helper
-        self.var = helper.var
-        self.suf_n, self.suf_ss = helper.suf_n, helper.suf_ss
-        self.sss_rng = o.rng_philox(self.seed, self.chain, 3, 0)
-        self.state_rng = o.rng_philox(self.seed, self.chain, 2, 0)
-        # a new model: v = 0, q = 4 / n_t (a missing step's trials are not read)
-        self.v = np.zeros(self.T)
-        self.q = np.array([4.0 / self.trials[t] if self.obs[t] else 0.0 for t in range(self.T)])
-        self.state = None
-        self.initialized = False
-        self.imputations = 0
-        self.rounds = 0
         self.record = Record()
+        SsFamilyOracle.__init__(self, o, X, observed, blocks, mu, prec, pi, seed, chain, gamma0, beta0, max_flips)
 
     @property
     def margin(self):
@@ -336,68 +272,16 @@ class SsLogitOracle:
     def btpe(self):
         return self.record.btpe
 
-    def _rnorm(self, mu, sd):
-        return self.L.bo_rnorm(C.byref(self.state_rng), float(mu), float(sd))
+    def initial_precisions(self):
+        # (a missing step's trials are not read)
+        return np.array([4.0 / self.trials[t] if self.obs[t] else 0.0 for t in range(self.T)])
 
-    def xbeta(self):
-        inc = np.flatnonzero(self.gamma)
-        return self.X[:, inc] @ self.beta[inc]
-
-    def offset(self):
-        return self.state @ self.S.Z
-
-    def H(self):
-        return observation_variances(self.q, self.obs)
-
-    def set_latent(self, v, q):
-        self.v = np.where(self.obs, np.asarray(v, dtype=float), 0.0)
-        self.q = np.where(self.obs, np.asarray(q, dtype=float), 0.0)
-
-    def impute_latent(self, keep=True):
-        """impute_nonstate_latent_data; keep = False: the slots are used up and nothing is stored"""
-        s = self.imputations
-        self.imputations += 1
-        if not keep:
-            return s
+    def impute(self, s):
         total, info = impute(self.o, self.seed, self.chain, self.successes, self.trials, self.offset() + self.xbeta(),
                              self.obs, s, self.clt, self.record)
         ob = self.obs
         self.v, self.q = np.zeros(self.T), np.zeros(self.T)
         self.v[ob], self.q[ob] = total[ob] / info[ob], info[ob]
-        return s
-
-    def impute_state(self):
-        ystar = self.v - self.xbeta()
-        self.state = impute_state(self.S, self.var, ystar, self.obs, self.H(), self._rnorm)
-        self.suf_n, self.suf_ss = state_model_suf(self.S, self.state)
-        # update_complete_data_sufficient_statistics: observed steps, response v - Z alpha, weight q
-        ob = self.obs
-        z = ((self.v - self.offset()) * self.q)[ob]
-        Xo, qo = self.X[ob], self.q[ob]
-        self.xtx, self.xty = Xo.T @ (Xo * qo[:, None]), Xo.T @ z
-        return self.state
-
-    def draw_observation_model(self):
-        self.gamma, self.beta = draw_sss(self.o, self.sss_rng, self.xtx, self.xty, self.mu, self.prec, self.pi,
-                                         self.gamma, self.beta, self.max_flips)
-
-    def draw_state_models(self):
-        sm = self._sm
-        sm.var, sm.suf_n, sm.suf_ss = self.var, self.suf_n, self.suf_ss
-        sm.draw_state_models()
-        self.var = sm.var
-
-    def draw(self):
-        if not self.initialized:
-            self.impute_state()
-            self.initialized = True
-            self.impute_latent(keep=False)   # (every value is overwritten below before it is read)
-        self.draw_observation_model()
-        self.draw_state_models()
-        self.last_s = self.impute_latent()
-        self.impute_state()
-        self.rounds += 1
-        return self.gamma.copy(), self.beta.copy()
 
 
 def logit_regression_rounds(o, X, y, ntrials, mu, prec, pi, seed, chain, gamma0, nsweeps, clt_threshold=5,
@@ -415,6 +299,7 @@ def logit_regression_rounds(o, X, y, ntrials, mu, prec, pi, seed, chain, gamma0,
     for s in range(nsweeps):
         inc = np.flatnonzero(gamma)
         total, info = impute(o, seed, chain, y, ntrials, X[:, inc] @ beta[inc], obs, s, clt_threshold, rec)
-        gamma, beta = draw_sss(o, rng, X.T @ (X * info[:, None]), X.T @ total, mu, prec, pi, gamma, beta, max_flips)
+        gamma, beta = draw_sss(o, rng, X.T @ (X * info[:, None]), X.T @ total, mu, prec, pi, gamma, beta, max_flips,
+                               SsLogitOracle.SHUFFLE_KIND)
         G[s], B[s] = gamma, beta
     return G, B, rec

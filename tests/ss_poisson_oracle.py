@@ -1,28 +1,18 @@
 """A restatement of StateSpacePosteriorSampler::draw() for StateSpacePoissonModel (bsts family =
 "poisson") on the device's substreams, one chain, in Python over the oracle's primitives: the
-parity yardstick of ba_ss_poisson_sweep, built as tests/ss_student_oracle.py is (whose filter,
-smoother, state-model statistics and dense posterior it imports).
+parity yardstick of ba_ss_poisson_sweep.  The round is tests/ss_family_oracle.py's (StateSpacePoisson
+PosteriorSampler.cpp:79-147); this file is what the family adds to it.
 
-Per-step data: an observed step carries a latent value v_t and a precision q_t (0 and 1 in a new
-model); the filter sees v_t - x_t'beta with the observation variance H_t = 1 / q_t; a missing step
-has no observation and H_t = pi^2 / 6, and its count and exposure are never read.
+Per-step data: a new model has v_t = 0 and q_t = 1; a missing step has H_t = pi^2 / 6, and its count
+and exposure are never read.
 
-One draw() (StateSpacePosteriorSampler.cpp:42-64, StateSpacePoissonPosteriorSampler.cpp:79-147):
-  0. the first time: impute_state with the latent data in hand, then one imputation whose values
-     are all overwritten in step 3 before anything reads them -- only its slots are used up, so
-     round r of a fresh sampler imputes with s = r + 1;
-  1. the observation model's sampler with fix_latent_data(true) (PoissonRegressionSpikeSlabSampler.cpp:
-     55-59): inclusion indicators and beta at sigma^2 = 1 with a fixed-precision slab on the
-     complete-data statistics the last impute_state left (X'QX, X'Q(v - Z alpha), observed
-     steps), stream 3;
-  2. every state model's variance draw (ss_student_oracle's);
-  3. impute_nonstate_latent_data: PoissonDataImputer::impute(y_t, exposure_t, eta_t) with eta_t =
-     Z_t'alpha_t + x_t'beta (alpha the last state draw, beta the new one) for the observed steps,
-     stream 11, slot s T + t of 256 in the sampler's s-th imputation: the last event time by
-     Cheng's BC beta sampler, the event past the interval (three branches at |eta| >= 600), the
-     two unmixing draws; q_t = q_ext (+ q_int if y_t > 0), v_t = (q_ext (z_ext - mu_ext)
-     (+ q_int (z_int - mu_int))) / q_t, the external term first;
-  4. impute_state: the simulation smoother with H_t, then the statistics over the observed steps.
+The observation model's sampler is PoissonRegressionSpikeSlabSampler (.cpp:55-59) with the plain shuffle.
+
+The imputation: PoissonDataImputer::impute(y_t, exposure_t, eta_t) for the observed steps, stream 11,
+slot s T + t of 256 in the sampler's s-th imputation: the last event time by Cheng's BC beta sampler,
+the event past the interval (three branches at |eta| >= 600), the two unmixing draws; q_t = q_ext
+(+ q_int if y_t > 0), v_t = (q_ext (z_ext - mu_ext) (+ q_int (z_int - mu_int))) / q_t, the external
+term first.
 
 The imputer's values come from the oracle's primitives (bo_test_rbeta_a1, bo_exp_rand,
 bo_rmulti); a replay of the same uniforms on a copy of the stream (bo_unif, bo_runif) restates
@@ -35,9 +25,8 @@ import math
 
 import numpy as np
 
-from oracle_lib import BoRng, _dp, _u8, f64, fcol
-from ss_student_oracle import (Structure, bonferroni_bound, dense_posterior, impute_state,  # noqa: F401
-                               moment_z, state_model_suf, SsStudentOracle)
+from oracle_lib import BoRng, _dp, f64
+from ss_family_oracle import SsFamilyOracle, draw_sss
 
 POISSON_STREAM, POISSON_STRIDE = 11, 256
 MISSING_VARIANCE = 1.6449340668482264061   # Constants::pi_squared_over_6
@@ -238,129 +227,26 @@ def impute(o, seed, chain, M, counts, exposure, eta, observed, s):
     return v, q, margin
 
 
-def observation_variances(q, observed):
-    return np.array([1.0 / q[t] if observed[t] else MISSING_VARIANCE for t in range(len(q))])
-
-
-def draw_sss(o, rng, xtx, xty, mu, prec, pi, gamma, beta, max_flips=-1):
-    """SpikeSlabSampler::draw_model_indicators / draw_beta at sigma^2 = 1 with a fixed-precision
-    slab (bo_sss, scales = 0) continuing the stream `rng` (updated in place): (gamma, beta)"""
-    L, p = o.lib, len(xty)
-    o._declare_sss()
-    h = L.bo_sss_create(p, _dp(fcol(xtx)), _dp(f64(xty)), 0, _dp(f64(mu)), _dp(fcol(prec)), _dp(f64(pi)))
-    try:
-        L.bo_sss_set_options(h, -1, int(max_flips))
-        L.bo_sss_set_state(h, _u8(np.ascontiguousarray(gamma, dtype=np.uint8)), _dp(f64(beta)))
-        C.memmove(L.bo_sss_rng(h), C.byref(rng), C.sizeof(BoRng))
-        st = L.bo_sss_draw_model_indicators(h, 1.0)
-        if st == 0:
-            st = L.bo_sss_draw_beta(h, 1.0)
-        if st:
-            raise RuntimeError("SpikeSlabSampler status %d" % st)
-        g, b = np.zeros(p, dtype=np.uint8), np.zeros(p)
-        L.bo_sss_get_state(h, _u8(g), _dp(b))
-        C.memmove(C.byref(rng), L.bo_sss_rng(h), C.sizeof(BoRng))
-    finally:
-        L.bo_sss_destroy(h)
-    return g, b
-
-
-class SsPoissonOracle:
+class SsPoissonOracle(SsFamilyOracle):
     """one chain of StateSpacePoissonPosteriorSampler on the device's substreams"""
+
+    MISSING_VARIANCE = MISSING_VARIANCE
 
     def __init__(self, o, counts, exposure, X, observed, blocks, mix, mu, prec, pi, seed, chain, gamma0,
                  beta0=None, max_flips=-1):
-        self.o, self.L = o, o.lib
-        declare(self.L)
+        declare(o.lib)
         self.counts, self.exposure = np.asarray(counts, dtype=float), np.asarray(exposure, dtype=float)
-        self.X = np.asarray(X, dtype=np.float64)
-        self.T, self.p = self.X.shape
-        self.obs = (np.ones(self.T, bool) if observed is None else np.asarray(observed).astype(bool))
-        self.S = Structure(blocks)
         self.M = Mixtures(mix)
-        self.mu, self.prec, self.pi = f64(mu), np.asarray(prec, dtype=np.float64), f64(pi)
-        self.seed, self.chain, self.max_flips = int(seed), int(chain), int(max_flips)
-        self.gamma = np.ascontiguousarray(gamma0, dtype=np.uint8).copy()
-        self.beta = np.zeros(self.p) if beta0 is None else f64(beta0) * self.gamma
-        # the state models' parameters, priors and samplers' streams: the Student restatement's
-        # (built on a series that only sizes the handle; its observation model is not used)
-        y0 = np.zeros(self.T)
-        helper = SsStudentOracle(o, y0, self.X, None if observed is None else observed, blocks, self.mu,
-                                 self.prec, self.pi, seed, chain, self.gamma)
-        self._sm = helper
-        self.var = helper.var
-        self.suf_n, self.suf_ss = helper.suf_n, helper.suf_ss
-        self.sss_rng = o.rng_philox(self.seed, self.chain, 3, 0)
-        self.state_rng = o.rng_philox(self.seed, self.chain, 2, 0)
-        self.v = np.zeros(self.T)
-        self.q = np.where(self.obs, 1.0, 0.0)
-        self.state = None
-        self.initialized = False
-        self.imputations = 0
-        self.rounds = 0
         self.margin = np.inf   # the imputer's branch comparisons'
+        SsFamilyOracle.__init__(self, o, X, observed, blocks, mu, prec, pi, seed, chain, gamma0, beta0, max_flips)
 
-    def _rnorm(self, mu, sd):
-        return self.L.bo_rnorm(C.byref(self.state_rng), float(mu), float(sd))
+    def initial_precisions(self):
+        return np.where(self.obs, 1.0, 0.0)
 
-    def xbeta(self):
-        inc = np.flatnonzero(self.gamma)
-        return self.X[:, inc] @ self.beta[inc]
-
-    def offset(self):
-        return self.state @ self.S.Z
-
-    def H(self):
-        return observation_variances(self.q, self.obs)
-
-    def set_latent(self, v, q):
-        self.v = np.where(self.obs, np.asarray(v, dtype=float), 0.0)
-        self.q = np.where(self.obs, np.asarray(q, dtype=float), 0.0)
-
-    def impute_latent(self, keep=True):
-        """impute_nonstate_latent_data; keep = False: the slots are used up and nothing is stored"""
-        s = self.imputations
-        self.imputations += 1
-        if not keep:
-            return s
-        v, q, m = impute(self.o, self.seed, self.chain, self.M, self.counts, self.exposure,
-                         self.offset() + self.xbeta(), self.obs, s)
-        self.v, self.q = v, q
+    def impute(self, s):
+        self.v, self.q, m = impute(self.o, self.seed, self.chain, self.M, self.counts, self.exposure,
+                                   self.offset() + self.xbeta(), self.obs, s)
         self.margin = min(self.margin, m)
-        return s
-
-    def impute_state(self):
-        ystar = self.v - self.xbeta()
-        self.state = impute_state(self.S, self.var, ystar, self.obs, self.H(), self._rnorm)
-        self.suf_n, self.suf_ss = state_model_suf(self.S, self.state)
-        # update_complete_data_sufficient_statistics: observed steps, response v - Z alpha, weight q
-        ob = self.obs
-        z = ((self.v - self.offset()) * self.q)[ob]
-        Xo, qo = self.X[ob], self.q[ob]
-        self.xtx, self.xty = Xo.T @ (Xo * qo[:, None]), Xo.T @ z
-        return self.state
-
-    def draw_observation_model(self):
-        self.gamma, self.beta = draw_sss(self.o, self.sss_rng, self.xtx, self.xty, self.mu, self.prec, self.pi,
-                                         self.gamma, self.beta, self.max_flips)
-
-    def draw_state_models(self):
-        sm = self._sm
-        sm.var, sm.suf_n, sm.suf_ss = self.var, self.suf_n, self.suf_ss
-        sm.draw_state_models()
-        self.var = sm.var
-
-    def draw(self):
-        if not self.initialized:
-            self.impute_state()
-            self.initialized = True
-            self.impute_latent(keep=False)   # (every value is overwritten below before it is read)
-        self.draw_observation_model()
-        self.draw_state_models()
-        self.last_s = self.impute_latent()
-        self.impute_state()
-        self.rounds += 1
-        return self.gamma.copy(), self.beta.copy()
 
 
 def poisson_regression_rounds(o, X, y, exposure, mix, mu, prec, pi, seed, chain, gamma0, nsweeps, max_flips=-1):
@@ -381,20 +267,3 @@ def poisson_regression_rounds(o, X, y, exposure, mix, mu, prec, pi, seed, chain,
         gamma, beta = draw_sss(o, rng, X.T @ (X * q[:, None]), X.T @ (v * q), mu, prec, pi, gamma, beta, max_flips)
         G[s], B[s] = gamma, beta
     return G, B, margin
-
-
-def fixed_case():
-    """T = 12, a local linear trend, latent values around a random walk, precisions over four
-    decades and one missing step"""
-    T = 12
-    rs = np.random.Generator(np.random.PCG64(6))
-    v = np.cumsum(rs.standard_normal(T)) + 1.0
-    from cases import general_spec
-    blocks = general_spec(v, [("trend",)])
-    blocks[0]["initial_sigma"] = np.array([0.55, 0.22])
-    S = Structure(blocks)
-    var = [blocks[0]["initial_sigma"] ** 2]
-    obs = np.ones(T, bool)
-    obs[7] = False
-    q = np.exp(rs.uniform(np.log(1e-2), np.log(1e2), T))
-    return blocks, S, var, v, obs, q, observation_variances(q, obs)

@@ -296,25 +296,73 @@ def fixed_case():
     return blocks, S, var, y, obs, w, sigsq, nu, H
 
 
-class SsStudentOracle:
+def oracle_stream_ids(o, T, blocks):
+    """the stream of every variance sampler of a level / trend / seasonal list, per block, as
+    bo_ssm_block_stream_id reports it (a handle on a series of zeros: the ids depend on the list alone)"""
+    L = o.lib
+    dummy = dict(b=np.zeros(1), ominv=np.eye(1), pi=np.full(1, 0.5), df=1.0, sigma_guess=1.0)
+    h = o._ssg_build(np.zeros(T), np.zeros((T, 1)), None, dummy, blocks)
+    ids = [[L.bo_ssm_block_stream_id(h, k, v) for v in range(len(b["initial_sigma"]))] for k, b in enumerate(blocks)]
+    L.bo_ssm_destroy.argtypes = [C.c_void_p]
+    L.bo_ssm_destroy(h)
+    return ids
+
+
+class StateModelSamplers:
+    """the state models' half of one chain, whatever the observation model: every model's variances,
+    their priors, statistics and samplers' streams (stream_ids: per block, one id per variance), and the
+    state stream"""
+
+    def __init__(self, o, blocks, seed, chain, stream_ids):
+        self.o, self.L = o, o.lib
+        self.L.bo_rnorm.argtypes = [C.c_void_p, C.c_double, C.c_double]
+        self.L.bo_rnorm.restype = C.c_double
+        self.blocks = blocks
+        self.seed, self.chain = int(seed), int(chain)
+        self.var = [f64(b["initial_sigma"]) ** 2 for b in blocks]
+        self.var_prior = [(2 * (f64(b["df"]) / 2.0), 2 * (f64(b["df"]) * f64(b["sigma_guess"]) ** 2 / 2.0),
+                           f64(b["sigma_upper_limit"])) for b in blocks]
+        self.var_rng = [[o.rng_philox(self.seed, self.chain, sid, 0) for sid in row] for row in stream_ids]
+        self.suf_n = [np.zeros(2) for _ in blocks]
+        self.suf_ss = [np.zeros(2) for _ in blocks]
+        self.state_rng = o.rng_philox(self.seed, self.chain, 2, 0)
+
+    def _rnorm(self, mu, sd):
+        return self.L.bo_rnorm(C.byref(self.state_rng), float(mu), float(sd))
+
+    def _draw_variance(self, rng, DF, SS, smax):
+        if np.isinf(smax):
+            return 1.0 / self.o.gammas(rng, DF / 2, SS / 2, 1)[0]
+        return 1.0 / self.o.trun_gammas(rng, DF / 2, SS / 2, 1.0 / (smax * smax), 1)[0]
+
+    def draw_block_variances(self, k):
+        pdf, pss, smax = self.var_prior[k]
+        for v in range(len(self.var[k])):
+            d = self._draw_variance(self.var_rng[k][v], self.suf_n[k][v] + pdf[v], self.suf_ss[k][v] + pss[v], smax[v])
+            if self.blocks[k]["kind"] == TREND:
+                d = 1.0 / (1.0 / d)   # ZeroMeanMvnIndependenceSampler: siginv = 1 / draw, Sigma its inverse
+            self.var[k][v] = d
+
+    def draw_state_models(self):
+        """every state model's sampler, in model order"""
+        for k in range(len(self.blocks)):
+            self.draw_block_variances(k)
+
+
+class SsStudentOracle(StateModelSamplers):
     """one chain of StateSpaceStudentPosteriorSampler on the device's substreams"""
 
     def __init__(self, o, y, X, observed, blocks, mu, prec, pi, seed, chain, gamma0, beta0=None,
                  sigsq0=1.0, nu0=30.0, nu_prior=(0, 0.1, 100.0), sigma_prior=(1.0, 1.0),
                  sigma_max=np.inf, max_flips=-1):
-        self.o, self.L = o, o.lib
         o._declare_sss()
-        L = self.L
-        L.bo_rng_slot.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
-        L.bo_rng_slot.restype = None
-        L.bo_rnorm.argtypes = [C.c_void_p, C.c_double, C.c_double]
-        L.bo_rnorm.restype = C.c_double
+        o.lib.bo_rng_slot.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
+        o.lib.bo_rng_slot.restype = None
         self.y, self.X = f64(y), np.asarray(X, dtype=np.float64)
         self.T, self.p = self.X.shape
         self.obs = (np.ones(self.T, bool) if observed is None else np.asarray(observed).astype(bool))
         self.S = Structure(blocks)
         self.mu, self.prec, self.pi = f64(mu), np.asarray(prec, dtype=np.float64), f64(pi)
-        self.seed, self.chain = int(seed), int(chain)
         self.gamma = np.ascontiguousarray(gamma0, dtype=np.uint8).copy()
         self.beta = np.zeros(self.p) if beta0 is None else f64(beta0) * self.gamma
         self.sigsq, self.nu, self.dx = float(sigsq0), float(nu0), 1.0
@@ -322,20 +370,8 @@ class SsStudentOracle:
         df, guess = sigma_prior
         self.prior_df, self.prior_ss = 2 * (df / 2.0), 2 * (df * guess * guess / 2.0)
         self.sigma_max, self.max_flips = float(sigma_max), int(max_flips)
-        # the state models' parameters, priors and samplers' streams
-        self.var = [f64(b["initial_sigma"]) ** 2 for b in blocks]
-        self.var_prior = [(2 * (f64(b["df"]) / 2.0), 2 * (f64(b["df"]) * f64(b["sigma_guess"]) ** 2 / 2.0),
-                           f64(b["sigma_upper_limit"])) for b in blocks]
-        dummy = dict(b=self.mu, ominv=self.prec, pi=self.pi, df=1.0, sigma_guess=1.0)
-        h = o._ssg_build(self.y, self.X, None if observed is None else observed, dummy, blocks)
-        self.var_rng = [[o.rng_philox(self.seed, self.chain, L.bo_ssm_block_stream_id(h, k, v), 0)
-                         for v in range(len(self.var[k]))] for k in range(len(blocks))]
-        L.bo_ssm_destroy.argtypes = [C.c_void_p]
-        L.bo_ssm_destroy(h)
-        self.suf_n = [np.zeros(2) for _ in blocks]
-        self.suf_ss = [np.zeros(2) for _ in blocks]
+        StateModelSamplers.__init__(self, o, blocks, seed, chain, oracle_stream_ids(o, self.T, blocks))
         self.sss_rng = o.rng_philox(self.seed, self.chain, 3, 0)
-        self.state_rng = o.rng_philox(self.seed, self.chain, 2, 0)
         self.w = np.where(self.obs, 1.0, 0.0)
         self.state = None
         self.initialized = False
@@ -350,9 +386,6 @@ class SsStudentOracle:
         self.L.bo_rng_seed_philox(C.byref(r), self.seed, self.chain, stream, 0)
         self.L.bo_rng_slot(C.byref(r), int(index), int(stride))
         return r
-
-    def _rnorm(self, mu, sd):
-        return self.L.bo_rnorm(C.byref(self.state_rng), float(mu), float(sd))
 
     def xbeta(self):
         inc = np.flatnonzero(self.gamma)
@@ -427,21 +460,6 @@ class SsStudentOracle:
         rexp1 = lambda: 1.0 * L.bo_exp_rand(C.byref(rng))                    # noqa: E731
         self.nu, self.dx, m = slice_draw_nu(unif, rexp1, logf, self.nu, self.dx)
         self.margin = min(self.margin, m)
-
-    def draw_state_models(self):
-        o = self.o
-        for k, b in enumerate(self.S.blocks):
-            pdf, pss, smax = self.var_prior[k]
-            for v in range(len(self.var[k])):
-                DF, SS = self.suf_n[k][v] + pdf[v], self.suf_ss[k][v] + pss[v]
-                rng = self.var_rng[k][v]
-                if np.isinf(smax[v]):
-                    d = 1.0 / o.gammas(rng, DF / 2, SS / 2, 1)[0]
-                else:
-                    d = 1.0 / o.trun_gammas(rng, DF / 2, SS / 2, 1.0 / (smax[v] * smax[v]), 1)[0]
-                if b["kind"] == TREND:
-                    d = 1.0 / (1.0 / d)   # ZeroMeanMvnIndependenceSampler: siginv = 1 / draw, Sigma its inverse
-                self.var[k][v] = d
 
     def draw(self):
         if not self.initialized:

@@ -197,37 +197,23 @@ def block_stream_ids(blocks):
     return out
 
 
-class StudentTrendOracle:
+class StudentTrendOracle(sso.StateModelSamplers):
     """the state half of one chain's StateSpacePosteriorSampler::draw for a list of level / trend /
     seasonal blocks and one Student local linear trend, on the device's substreams; the regression
     half (the adjusted series y - X beta, the observation variance) is given by the caller"""
 
     def __init__(self, o, T, observed, blocks, seed, chain):
-        self.o, self.L = o, o.lib
-        L = self.L
-        L.bo_rng_slot.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
-        L.bo_rng_slot.restype = None
-        L.bo_rnorm.argtypes = [C.c_void_p, C.c_double, C.c_double]
-        L.bo_rnorm.restype = C.c_double
+        sso.StateModelSamplers.__init__(self, o, blocks, seed, chain, block_stream_ids(blocks))
+        self.L.bo_rng_slot.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
+        self.L.bo_rng_slot.restype = None
         self.T = int(T)
         self.obs = np.ones(self.T, bool) if observed is None else np.asarray(observed).astype(bool)
-        self.blocks = blocks
         self.S = TrendStructure(blocks, self.T)
         self.qt = self.S.qt
-        self.seed, self.chain = int(seed), int(chain)
-        self.var = [np.array(b["initial_sigma"], dtype=float) ** 2 for b in blocks]
-        self.var_prior = [(2 * (np.asarray(b["df"], float) / 2.0),
-                           2 * (np.asarray(b["df"], float) * np.asarray(b["sigma_guess"], float) ** 2 / 2.0),
-                           np.asarray(b["sigma_upper_limit"], float)) for b in blocks]
         q = blocks[self.qt]
         self.nu = np.array(q["initial_nu"], dtype=float)
         self.nu_prior = [tuple(q["nu_priors"][0]), tuple(q["nu_priors"][1])]
-        ids = block_stream_ids(blocks)
-        self.var_rng = [[o.rng_philox(self.seed, self.chain, sid, 0) for sid in row] for row in ids]
         self.param_rng = o.rng_philox(self.seed, self.chain, PARAM_STREAM, 0)
-        self.state_rng = o.rng_philox(self.seed, self.chain, 2, 0)
-        self.suf_n = [np.zeros(2) for _ in blocks]
-        self.suf_ss = [np.zeros(2) for _ in blocks]
         self.res = np.zeros((2, 0))
         self.wsuf = np.zeros(6)
         self.state = None
@@ -247,9 +233,6 @@ class StudentTrendOracle:
         self.L.bo_rng_seed_philox(C.byref(r), self.seed, self.chain, stream, 0)
         self.L.bo_rng_slot(C.byref(r), int(index), int(stride))
         return r
-
-    def _rnorm(self, mu, sd):
-        return self.L.bo_rnorm(C.byref(self.state_rng), float(mu), float(sd))
 
     def observe_state(self):
         """over the draw in hand: residuals, the weighted statistics (old weights), the new weights"""
@@ -275,11 +258,6 @@ class StudentTrendOracle:
         self.observe_state()
         return self.state
 
-    def _draw_variance(self, rng, DF, SS, smax):
-        if np.isinf(smax):
-            return 1.0 / self.o.gammas(rng, DF / 2, SS / 2, 1)[0]
-        return 1.0 / self.o.trun_gammas(rng, DF / 2, SS / 2, 1.0 / (smax * smax), 1)[0]
-
     def draw_parameters(self):
         """StudentLocalLinearTrendPosteriorSampler::draw"""
         L, k, rng = self.L, self.qt, self.param_rng
@@ -302,13 +280,8 @@ class StudentTrendOracle:
 
     def draw_state_models(self):
         """every state model's sampler, in model order"""
-        for k, b in enumerate(self.blocks):
+        for k in range(len(self.blocks)):
             if k == self.qt:
                 self.draw_parameters()
-                continue
-            pdf, pss, smax = self.var_prior[k]
-            for v in range(len(self.var[k])):
-                d = self._draw_variance(self.var_rng[k][v], self.suf_n[k][v] + pdf[v], self.suf_ss[k][v] + pss[v], smax[v])
-                if b["kind"] == TREND:
-                    d = 1.0 / (1.0 / d)
-                self.var[k][v] = d
+            else:
+                self.draw_block_variances(k)

@@ -18,9 +18,9 @@ import pytest
 
 import family_forecast_ref as ffr
 from cases import general_data, general_spec
-from test_ss_logit_gpu import logit_engine
-from test_ss_poisson_gpu import count_series, poisson_engine
-from test_ss_student_gpu import refused, student_engine
+from ss_family_cases import (count_series, golden_mix, logit_engine, poisson_engine, slab_of, student_engine,
+                             student_slab_of)
+from ss_gpu_helpers import refused
 
 gpu = pytest.mark.gpu
 T, P, CHAINS, WARMUP, HORIZON = 40, 3, 64, 5, 6
@@ -293,9 +293,6 @@ def level_model(boom, blocks):
 @pytest.mark.parametrize("family", ["student", "poisson", "logit"])
 def test_pybind_methods_return_what_capi_returns(family):
     import boom_amd._boom as boom
-    import test_ss_logit_gpu as tl
-    import test_ss_poisson_gpu as tp
-    import test_ss_student_gpu as ts
     chains, seed, rounds = 3, 808, 3
     g0 = np.zeros(P, np.uint8)
     newX = new_predictors(3)
@@ -303,7 +300,7 @@ def test_pybind_methods_return_what_capi_returns(family):
     if family == "student":
         X, y, _, _ = general_data(T, P, 2, [], seed=3)
         blocks = general_spec(y, LISTS["level"])
-        mu, prec, pi = ts.slab_of(P)
+        mu, prec, pi = student_slab_of(P)
         model = boom.StateSpaceStudentRegressionModel(y, X, [], chains=chains, seed=seed)
         model.add_state(level_model(boom, blocks))
         sampler = boom.StateSpaceStudentPosteriorSampler(model, boom.MvnGivenScalarSigma(mu, prec), boom.VariableSelectionPrior(pi),
@@ -312,8 +309,8 @@ def test_pybind_methods_return_what_capi_returns(family):
     elif family == "poisson":
         X, counts, exposure, series = count_series(T, P, 4)
         blocks = general_spec(series, LISTS["level"])
-        mu, prec, pi = tp.slab_of(P)
-        mix = tp.golden_mix()
+        mu, prec, pi = slab_of(P)
+        mix = golden_mix()
         model = boom.StateSpacePoissonModel(counts, exposure, X, [], chains=chains, seed=seed)
         model.set_mixture_table([int(c) for c in mix["counts"]], [int(c) for c in mix["ncomp"]], mix["mu"], mix["sigma"],
                                 mix["weight"], mix["largest_index"])
@@ -323,7 +320,7 @@ def test_pybind_methods_return_what_capi_returns(family):
     else:
         X, successes, trials, series = fair_coin_series(5)
         blocks = general_spec(series, LISTS["level"])
-        mu, prec, pi = tl.slab_of(P)
+        mu, prec, pi = slab_of(P)
         model = boom.StateSpaceLogitModel(successes, trials, X, [], chains=chains, seed=seed)
         model.add_state(level_model(boom, blocks))
         sampler = boom.StateSpaceLogitPosteriorSampler(model, boom.MvnModel(mu, prec, True), boom.VariableSelectionPrior(pi))

@@ -12,14 +12,10 @@ import os
 import numpy as np
 import pytest
 
+from golden_lib import GOLD, _golden_mix, load  # noqa: F401  (other modules take them from here too)
 from oracle_lib import ssvs_options
 
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 RTOL = 1e-9
-
-
-def load(name):
-    return np.load(os.path.join(GOLD, name + ".npz"))
 
 
 def relerr(a, b, floor=1e-3):
@@ -549,11 +545,6 @@ def test_logit_spike_slab_matches_reference(oracle, name):
     assert o["status"] == 0
     assert np.array_equal(o["gamma"], g["gamma"])
     assert relerr(o["beta"], g["beta"]) < 1e-9
-
-
-def _golden_mix(g):
-    return dict(counts=g["mix_counts"], ncomp=g["mix_ncomp"], mu=g["mix_mu"], sigma=g["mix_sigma"],
-                weight=g["mix_weight"], largest_index=int(g["mix_largest_index"]))
 
 
 @pytest.mark.parametrize("name", ["poisson_small_counts", "poisson_exposure", "poisson_large_counts",

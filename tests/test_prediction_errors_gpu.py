@@ -244,7 +244,7 @@ def test_no_replay_under_the_lookahead():
 
 def test_refusals():
     from test_family_forecast_gpu import LISTS as FAMILY_LISTS, family_engine
-    from test_ss_student_gpu import refused
+    from ss_gpu_helpers import refused
     text = "one-step prediction errors are built for the Gaussian observation model only"
     for family in ("student", "poisson", "logit"):
         eng, _ = family_engine(family, FAMILY_LISTS["level"], 7, chains=2, warmup=0)

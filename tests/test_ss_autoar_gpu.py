@@ -404,7 +404,7 @@ def test_refusals_and_their_texts():
 @gpu
 def test_poisson_family_refuses_the_block():
     import boom_amd
-    from test_ss_poisson_gpu import count_series, golden_mix
+    from ss_family_cases import count_series, golden_mix
     T, p = 30, 3
     X, counts, exposure, y = count_series(T, p, 4)
     e = boom_amd.Engine(2, seed=1)

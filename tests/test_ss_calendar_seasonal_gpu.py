@@ -330,7 +330,7 @@ def test_refusals_and_their_texts():
     assert eng.ss_forecast(np.zeros((2, scc.P))).shape == (2, 2)
     # the other observation families: the block added on such data ...
     text = "the calendar seasonal is built for the Gaussian observation model only"
-    from test_ss_poisson_gpu import count_series, golden_mix
+    from ss_family_cases import count_series, golden_mix
     Xc, counts, exposure, _ = count_series(T, scc.P, 4)
     families = [
         (lambda e: e.ss_student_set_data(y, X, None), lambda e: e.ss_student_sweep(1), True),

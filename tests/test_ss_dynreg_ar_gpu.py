@@ -410,7 +410,7 @@ def test_refusals_accessors_and_their_texts():
     assert eng.ss_forecast(np.zeros((2, sdc.P))).shape == (2, 2)
     # the other observation families: the model added on such data ...
     text = "the dynamic regression is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)"
-    from test_ss_poisson_gpu import count_series, golden_mix
+    from ss_family_cases import count_series, golden_mix
     Xc, counts, exposure, _ = count_series(T, sdc.P, 4)
     families = [
         (lambda e: e.ss_student_set_data(y, X, None), lambda e: e.ss_student_sweep(1), True),

@@ -18,12 +18,11 @@ before the device is compared with it:
 import numpy as np
 import pytest
 
+import ss_family_checks as checks
 import ss_logit_oracle as slo
-from test_oracle_golden import load
-
-
-def relerr(a, b, floor=1e-3):
-    return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), floor)))
+from golden_lib import load
+from ss_family_cases import RECOVERY_COEF, binomial_series, recovery_data, relerr
+from ss_family_checks import LOGIT
 
 
 @pytest.mark.parametrize("name", ["logit_bernoulli", "logit_binomial4", "logit_binomial60_large_sample",
@@ -45,88 +44,39 @@ def test_imputer_reproduces_the_pinned_regression_sampler(oracle, name):
 
 
 def small_case(nan_at_missing=False):
-    from test_ss_logit_gpu import binomial_series, slab_of, spec
-    T, p = 30, 3
-    X, successes, trials, series = binomial_series(T, p, 3, max_trials=8, seasons=4)   # (both branches at threshold 5)
-    obs = np.ones(T, np.uint8)
-    obs[[4, 17]] = 0
-    blocks = spec(series, [("trend",), ("seasonal", 4, 1)])
-    if nan_at_missing:
-        successes, trials = successes.copy(), trials.copy()
-        successes[[4, 17]] = np.nan
-        trials[[4, 17]] = np.nan
-    g0 = np.zeros(p, np.uint8)
-    g0[0] = 1
-    return X, successes, trials, obs, blocks, slab_of(p), g0
+    return checks.small_case(binomial_series(30, 3, 3, max_trials=8, seasons=4), nan_at_missing)   # (both branches at threshold 5)
 
 
 def test_first_draw(oracle):
-    X, successes, trials, obs, blocks, (mu, prec, pi), g0 = small_case()
+    case = small_case()
+    trials = case[1][1]
     assert trials.min() < trials.max()
-    o = slo.SsLogitOracle(oracle, successes, trials, X, obs, blocks, mu, prec, pi, 7, 1, g0)
-    o.impute_state()
-    ob = obs.astype(bool)
-    Xo, q0 = X[ob], 4.0 / trials[ob]
-    xqx = Xo.T @ (Xo * q0[:, None])
-    assert np.allclose(o.xtx, xqx, rtol=1e-14, atol=0)
-    assert np.allclose(o.xty, -(Xo.T @ (o.offset()[ob] * q0)), rtol=1e-12, atol=1e-13)
-    # ... and draw() from the start: the first imputation uses up s = 0 and stores nothing
-    o = slo.SsLogitOracle(oracle, successes, trials, X, obs, blocks, mu, prec, pi, 7, 1, g0)
-    seen = []
-    keep = o.draw_observation_model
-
-    def spy():
-        seen.append((o.imputations, o.xtx.copy(), o.v.copy(), o.q.copy()))
-        keep()
-    o.draw_observation_model = spy
-    for r in range(3):
-        o.draw()
-        assert o.last_s == r + 1 and o.imputations == r + 2
-    imputations, xtx, v, q = seen[0]
-    assert imputations == 1 and np.all(v == 0) and np.array_equal(q, np.where(ob, 4.0 / trials, 0.0))
-    assert np.allclose(xtx, xqx, rtol=1e-14, atol=0)
-    assert np.all(o.q[ob] > 0) and np.all(o.q[~ob] == 0) and np.all(np.isfinite(o.state))
+    checks.first_draw(LOGIT, oracle, case, lambda data: 4.0 / data[1])   # (a new model: q = 4 / n_t)
 
 
 def test_missing_steps_read_neither_successes_nor_trials(oracle):
-    runs = []
-    for nan in (False, True):
-        X, successes, trials, obs, blocks, (mu, prec, pi), g0 = small_case(nan)
-        o = slo.SsLogitOracle(oracle, successes, trials, X, obs, blocks, mu, prec, pi, 7, 0, g0)
-        for _ in range(3):
-            o.draw()
-        runs.append((o.gamma.copy(), o.beta.copy(), o.v.copy(), o.q.copy(), o.state.copy()))
-    for a, b in zip(*runs):
-        assert np.all(np.isfinite(b)) and np.array_equal(a, b)
+    checks.missing_steps_read_no_data(LOGIT, oracle, small_case)
 
 
 def test_parity_seeds_keep_their_margins(oracle):
     """the whole-round cases of the device test: every checked chain's smallest branch margin
     stays above 1e-9 over the rounds compared (a seed that does not is changed, not the bar), and
     no binomial draw takes BTPE, whose comparisons the record does not hold"""
-    from test_ss_logit_gpu import ROUND_CASES, round_case
-    for k in range(len(ROUND_CASES)):
-        c = round_case(k)
+    def before(c):
         # n min(p, 1 - p) <= n / 2 < 30 whatever the linear predictor
         assert c["trials"].max() / 2 < 30
-        oracle.set_slot_limit(c["slots"])
-        try:
-            for chain in c["check"]:
-                o = c["oracle"](oracle, chain)
-                for _ in range(c["rounds"]):
-                    o.draw()
-                print("case %d chain %d: margin %.3e, BTPE draws %d" % (k, chain, o.margin, o.btpe))
-                assert o.margin > 1e-9, (k, chain, o.margin)
-                assert o.btpe == 0, (k, chain, o.btpe)
-        finally:
-            oracle.set_slot_limit(0)
+
+    def end(k, chain, o):
+        print("case %d chain %d: margin %.3e, BTPE draws %d" % (k, chain, o.margin, o.btpe))
+        assert o.margin > 1e-9, (k, chain, o.margin)
+        assert o.btpe == 0, (k, chain, o.btpe)
+    checks.parity_seeds_keep_their_margins(LOGIT, oracle, end, before)
 
 
 def test_recovery_data_have_clear_signals_and_quiet_nulls():
     """a binomial logistic regression by Newton's method with the generating state as offset: the
     coefficients' z-scores (see the docstring of test_ss_logit_recovers_the_signals)"""
-    from test_ss_logit_gpu import RECOVERY_COEF, recovery_data
-    X, successes, trials, _, path = recovery_data(with_path=True)
+    X, successes, trials, _, path = recovery_data("logit", with_path=True)
     p = X.shape[1]
     b = np.zeros(p)
     for _ in range(50):

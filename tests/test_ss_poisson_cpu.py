@@ -17,12 +17,11 @@ CPU before the device is compared with it:
 import numpy as np
 import pytest
 
+import ss_family_checks as checks
 import ss_poisson_oracle as spo
-from test_oracle_golden import _golden_mix, load
-
-
-def relerr(a, b, floor=1e-3):
-    return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), floor)))
+from golden_lib import _golden_mix, load
+from ss_family_cases import RECOVERY_COEF, count_series, recovery_data, relerr
+from ss_family_checks import POISSON
 
 
 @pytest.mark.parametrize("name", ["poisson_exposure", "poisson_small_counts"])
@@ -42,83 +41,31 @@ def test_imputer_reproduces_the_pinned_regression_sampler(oracle, name):
 
 
 def small_case(nan_at_missing=False):
-    from test_ss_poisson_gpu import count_series, golden_mix, slab_of, spec
-    T, p = 30, 3
-    X, counts, exposure, series = count_series(T, p, 3, seasons=4)
-    obs = np.ones(T, np.uint8)
-    obs[[4, 17]] = 0
-    blocks = spec(series, [("trend",), ("seasonal", 4, 1)])
-    if nan_at_missing:
-        counts, exposure = counts.copy(), exposure.copy()
-        counts[[4, 17]] = np.nan
-        exposure[[4, 17]] = np.nan
-    g0 = np.zeros(p, np.uint8)
-    g0[0] = 1
-    return X, counts, exposure, obs, blocks, golden_mix(), slab_of(p), g0
+    return checks.small_case(count_series(30, 3, 3, seasons=4), nan_at_missing)
 
 
 def test_first_draw(oracle):
-    X, counts, exposure, obs, blocks, mix, (mu, prec, pi), g0 = small_case()
-    o = spo.SsPoissonOracle(oracle, counts, exposure, X, obs, blocks, mix, mu, prec, pi, 7, 1, g0)
-    o.impute_state()
-    ob = obs.astype(bool)
-    Xo = X[ob]
-    assert np.allclose(o.xtx, Xo.T @ Xo, rtol=1e-14, atol=0)
-    assert np.allclose(o.xty, -(Xo.T @ o.offset()[ob]), rtol=1e-12, atol=1e-13)
-    # ... and draw() from the start: the first imputation uses up s = 0 and stores nothing
-    o = spo.SsPoissonOracle(oracle, counts, exposure, X, obs, blocks, mix, mu, prec, pi, 7, 1, g0)
-    seen = []
-    keep = o.draw_observation_model
-
-    def spy():
-        seen.append((o.imputations, o.xtx.copy(), o.v.copy(), o.q.copy()))
-        keep()
-    o.draw_observation_model = spy
-    for r in range(3):
-        o.draw()
-        assert o.last_s == r + 1 and o.imputations == r + 2
-    imputations, xtx, v, q = seen[0]
-    assert imputations == 1 and np.all(v == 0) and np.array_equal(q, ob.astype(float))
-    assert np.allclose(xtx, Xo.T @ Xo, rtol=1e-14, atol=0)
-    assert np.all(o.q[ob] > 0) and np.all(o.q[~ob] == 0) and np.all(np.isfinite(o.state))
+    checks.first_draw(POISSON, oracle, small_case(), lambda data: np.ones(len(data[0])))   # (a new model: q = 1)
 
 
 def test_missing_steps_read_neither_count_nor_exposure(oracle):
-    runs = []
-    for nan in (False, True):
-        X, counts, exposure, obs, blocks, mix, (mu, prec, pi), g0 = small_case(nan)
-        o = spo.SsPoissonOracle(oracle, counts, exposure, X, obs, blocks, mix, mu, prec, pi, 7, 0, g0)
-        for _ in range(3):
-            o.draw()
-        runs.append((o.gamma.copy(), o.beta.copy(), o.v.copy(), o.q.copy(), o.state.copy()))
-    for a, b in zip(*runs):
-        assert np.all(np.isfinite(b)) and np.array_equal(a, b)
+    checks.missing_steps_read_no_data(POISSON, oracle, small_case)
 
 
 def test_parity_seeds_keep_their_margins(oracle):
     """the whole-round cases of the device test: every checked chain's smallest branch margin
     stays above 1e-9 over the rounds compared (a seed that does not is changed, not the bar)"""
-    from test_ss_poisson_gpu import ROUND_CASES, round_case
-    for k in range(len(ROUND_CASES)):
-        c = round_case(k)
-        oracle.set_slot_limit(c["slots"])
-        try:
-            for chain in c["check"]:
-                o = c["oracle"](oracle, chain)
-                for _ in range(c["rounds"]):
-                    o.draw()
-                print("case %d chain %d: margin %.3e" % (k, chain, o.margin))
-                assert o.margin > 1e-9, (k, chain, o.margin)
-        finally:
-            oracle.set_slot_limit(0)
+    def end(k, chain, o):
+        print("case %d chain %d: margin %.3e" % (k, chain, o.margin))
+        assert o.margin > 1e-9, (k, chain, o.margin)
+    checks.parity_seeds_keep_their_margins(POISSON, oracle, end)
 
 
 def test_recovery_data_have_clear_signals_and_quiet_nulls():
     """a Poisson regression by Newton's method with offset log(exposure) + the generating state:
     the coefficients' z-scores (see the docstring of test_ss_poisson_recovers_the_signals)"""
-    from test_ss_poisson_gpu import RECOVERY_COEF, RECOVERY_SEED, RECOVERY_SHAPE, count_series
-    T, p = RECOVERY_SHAPE
-    X, counts, exposure, _, path = count_series(T, p, RECOVERY_SEED, coef=RECOVERY_COEF, with_path=True)
+    X, counts, exposure, _, path = recovery_data("poisson", with_path=True)
+    p = X.shape[1]
     assert counts.max() < 26   # (the clip did not bind)
     off = np.log(exposure) + path
     b = np.zeros(p)

@@ -1,7 +1,8 @@
 """bsts family = "poisson" on the device (ba_ss_poisson_*): StateSpacePoissonModel with
 StateSpacePoissonPosteriorSampler -- the general structural kernel on every chain's own latent
 series v_t with the per-step observation variance H_t = 1 / q_t, the Poisson imputation at
-eta_t = Z_t'alpha_t + x_t'beta over the observed steps, the round's order.
+eta_t = Z_t'alpha_t + x_t'beta over the observed steps, the round's order.  The bodies the family
+shares with the logit one are tests/ss_family_checks.py's.
 
   identity      the state draw on latent data set the same in every chain against the Gaussian
                 engine's on y = v, bit for bit
@@ -18,61 +19,12 @@ eta_t = Z_t'alpha_t + x_t'beta over the observed steps, the round's order.
 import numpy as np
 import pytest
 
-import ss_poisson_oracle as spo
-from cases import general_data, general_spec
-from test_oracle_golden import _golden_mix, load
-from test_ss_student_gpu import chain_parameters, gaussian_engine, refused, relerr, state_stream
+import ss_family_checks as checks
+from ss_family_cases import ROUND_CASES, count_series, golden_mix, poisson_engine, recovery_data, slab_of, spec
+from ss_family_checks import POISSON
+from ss_gpu_helpers import refused
 
 gpu = pytest.mark.gpu
-RTOL = 1e-8
-MAX_COUNT = 26   # (tests/golden/poisson_exposure.npz holds the mixture of every count 1 .. 26)
-
-
-def golden_mix():
-    return _golden_mix(load("poisson_exposure"))
-
-
-def slab_of(p, expected=2.5):
-    return np.zeros(p), np.eye(p), np.full(p, min(0.9, expected / p))
-
-
-def count_series(T, p, seed, coef=(0.5, -0.4), seasons=0, with_path=False):
-    """counts from a known log-rate path (a random walk, X beta, a seasonal pattern), clipped to
-    MAX_COUNT; returns X, counts, exposures and log(counts + 1/2), which sizes the state priors
-    (with_path: the state's part of the log rate too)"""
-    rs = np.random.Generator(np.random.PCG64(seed))
-    X = rs.standard_normal((T, p))
-    beta = np.zeros(p)
-    beta[:len(coef)] = coef
-    path = 1.0 + np.cumsum(0.05 * rs.standard_normal(T))
-    if seasons:
-        pattern = 0.4 * rs.standard_normal(seasons)
-        path = path + (pattern - pattern.mean())[np.arange(T) % seasons]
-    exposure = rs.uniform(0.5, 2.0, T)
-    counts = np.minimum(rs.poisson(exposure * np.exp(path + X @ beta)), MAX_COUNT).astype(float)
-    if with_path:
-        return X, counts, exposure, np.log(counts + 0.5), path
-    return X, counts, exposure, np.log(counts + 0.5)
-
-
-def spec(series, desc, upper=np.inf):
-    blocks = general_spec(series, desc)
-    for b in blocks:
-        b["sigma_upper_limit"] = np.full(len(b["sigma_upper_limit"]), float(upper))
-    return blocks
-
-
-def poisson_engine(chains, seed, counts, exposure, X, obs, blocks, g0, pi=None, max_flips=-1):
-    import boom_amd
-    p = X.shape[1]
-    mu, prec, pi0 = slab_of(p)
-    eng = boom_amd.Engine(chains, seed=seed)
-    eng.ss_poisson_set_data(counts, exposure, X, golden_mix(), obs)
-    eng.sss_set_slab(mu, prec, scales_with_sigsq=False, max_flips=max_flips)
-    eng.set_spike(pi0 if pi is None else pi)
-    eng.ss_set_state_models(blocks)
-    eng.set_state(g0)
-    return eng
 
 
 # ---- 1. identity ---------------------------------------------------------------------------------
@@ -84,192 +36,41 @@ def poisson_engine(chains, seed, counts, exposure, X, obs, blocks, g0, pi=None, 
     ([("level",), ("seasonal", 20, 1)], 70, 0.0),
 ])
 def test_shared_latent_data_equal_the_scalar_kernel(desc, T, missing):
-    """q = 1: the Gaussian engine's impute_state on y = v at sigma^2 = 1, bit for bit; then q = 4:
-    at sigma^2 = 1/4 (exact in binary) -- the per-chain series read through y_stride is the shared
-    one, and the scalar and Student paths are what they were"""
-    p, chains, seed = 3, 4, 77
-    seas = [(b[1], b[2]) for b in desc if b[0] == "seasonal"]
-    X, v, _, obs = general_data(T, p, 2, seas, seed=T, missing_frac=missing)
-    blocks = general_spec(v, desc)
-    gam, beta = chain_parameters(p, chains, 3)
-    counts, exposure = np.ones(T), np.ones(T)
-    for q in (1.0, 4.0):
-        a = poisson_engine(chains, seed, counts, exposure, X, obs, blocks, gam[0])
-        b = gaussian_engine(chains, seed, v, X, obs, blocks, gam[0])
-        for c in range(chains):
-            a.set_state(gam[c], beta[c], 1.0, chain=c)
-            b.set_state(gam[c], beta[c], 1.0 / q, chain=c)
-        a.ss_poisson_set_latent(v, np.full(T, q))
-        a.ss_poisson_impute_state()
-        b.ss_impute_state()
-        for c in range(chains):
-            assert np.array_equal(a.ss_get_state_draw(c), b.ss_get_state_draw(c)), (q, c)
-            for k in range(len(blocks)):
-                u, w = a.ss_get_state_model(c, k), b.ss_get_state_model(c, k)
-                assert np.array_equal(u["suf_ss"], w["suf_ss"]) and np.array_equal(u["suf_n"], w["suf_n"]), (q, c, k)
+    checks.shared_latent_data_equal_the_scalar_kernel(POISSON, desc, T, missing)
 
 
 # ---- 2. filter edges -----------------------------------------------------------------------------
 @gpu
 def test_impute_state_matches_restatement_on_every_chains_own_series(oracle):
-    """values and precisions that differ from chain to chain (the test that fails if the kernel
-    reads chain 0's series for every chain), precisions from 1e-3 to 1e3, the first step and a
-    step of the second block of 64 missing"""
-    desc, T, p, chains, seed = [("trend",), ("seasonal", 4, 1)], 70, 3, 4, 41
-    X, y, _, _ = general_data(T, p, 2, [(4, 1)], seed=12)
-    obs = np.ones(T, np.uint8)
-    obs[[0, 66]] = 0
-    blocks = general_spec(y, desc)
-    gam, beta = chain_parameters(p, chains, 8)
-    eng = poisson_engine(chains, seed, np.ones(T), np.ones(T), X, obs, blocks, gam[0])
-    rs = np.random.Generator(np.random.PCG64(2))
-    V = y[None, :] + rs.standard_normal((chains, T))
-    Q = np.exp(rs.uniform(np.log(1e-3), np.log(1e3), (chains, T)))
-    Q[:, [1, 65]] = [1e-3, 1e3]
-    for c in range(chains):
-        eng.set_state(gam[c], beta[c], 1.0, chain=c)
-        eng.ss_poisson_set_latent(V[c], Q[c], chain=c)
-    eng.ss_poisson_impute_state()
-    S = spo.Structure(blocks)
-    var = [np.asarray(b["initial_sigma"], float) ** 2 for b in blocks]
-    ob = obs.astype(bool)
-    for c in range(chains):
-        H = spo.observation_variances(Q[c], ob)
-        assert H[0] == spo.MISSING_VARIANCE and H[66] == H[0]
-        inc = np.flatnonzero(gam[c])
-        want = spo.impute_state(S, var, V[c] - X[:, inc] @ beta[c][inc], ob, H, state_stream(oracle, seed, c))
-        got = eng.ss_get_state_draw(c)
-        assert np.max(np.abs(got - want)) < 1e-8 * np.abs(want).max(), c
-        n, ss = spo.state_model_suf(S, want)
-        for k in range(len(blocks)):
-            sm = eng.ss_get_state_model(c, k)
-            nv = len(sm["variances"])
-            assert np.array_equal(sm["suf_n"], n[k][:nv]), (c, k)
-            assert relerr(sm["suf_ss"], ss[k][:nv], 1e-300) < RTOL, (c, k)
-        v, q = eng.ss_poisson_get_latent(c)
-        assert np.array_equal(v, np.where(ob, V[c], 0.0)) and np.array_equal(q, np.where(ob, Q[c], 0.0)), c
+    checks.impute_state_matches_restatement_on_every_chains_own_series(POISSON, oracle)
 
 
 # ---- 3. whole rounds -----------------------------------------------------------------------------
-ROUND_CASES = [
-    # blocks, T, rounds, missing steps, the state models' sigma upper limit, slot limit, seed
-    ([("level",)], 40, 12, [], np.inf, 0, 57),
-    ([("trend",), ("seasonal", 4, 1)], 40, 12, [5, 23], np.inf, 0, 58),
-    ([("trend",)], 40, 12, [], 0.2, 0, 59),
-    ([("level",)], 300, 3, [], np.inf, 0, 60),     # two workgroups of the imputation, five blocks of 64 steps
-    ([("level",)], 40, 12, [7], np.inf, 2, 61),    # a slot serves 2 uniforms: the imputation reads its spill streams
-]
-
-
-def round_case(k):
-    desc, T, rounds, miss, upper, slots, seed = ROUND_CASES[k]
-    p, chains = 5, 4
-    seasons = max([b[1] for b in desc if b[0] == "seasonal"], default=0)
-    X, counts, exposure, series = count_series(T, p, 31 + k, seasons=seasons)
-    obs = np.ones(T, np.uint8)
-    obs[miss] = 0
-    blocks = spec(series, desc, upper)
-    g0 = np.zeros(p, np.uint8)
-    g0[0] = 1
-    mu, prec, pi = slab_of(p)
-
-    def make_oracle(o, chain):
-        return spo.SsPoissonOracle(o, counts, exposure, X, obs, blocks, golden_mix(), mu, prec, pi, seed, chain, g0)
-    return dict(T=T, p=p, chains=chains, seed=seed, rounds=rounds, X=X, counts=counts, exposure=exposure, obs=obs,
-                blocks=blocks, g0=g0, slots=slots, check=[0, chains - 1], oracle=make_oracle)
-
-
 @gpu
-@pytest.mark.parametrize("k", range(len(ROUND_CASES)))
+@pytest.mark.parametrize("k", range(len(ROUND_CASES["poisson"])))
 def test_rounds_match_restatement(oracle, k):
-    c = round_case(k)
-
-    def engine():
-        e = poisson_engine(c["chains"], c["seed"], c["counts"], c["exposure"], c["X"], c["obs"], c["blocks"], c["g0"])
-        e.set_slot_limit(c["slots"])
-        return e
-    eng = engine()
-    oracle.set_slot_limit(c["slots"])
-    try:
-        ora = {ch: c["oracle"](oracle, ch) for ch in c["check"]}
-        for r in range(c["rounds"]):
-            eng.ss_poisson_sweep(1)   # (round 0: the start from v = 0, q = 1; it imputes with s = 1)
-            gam, beta, sig = eng.get_states()
-            for ch, o in ora.items():
-                g, b = o.draw()
-                tag = (k, ch, r)
-                assert o.last_s == r + 1
-                assert np.array_equal(gam[ch], g), tag
-                assert relerr(beta[ch], b) < RTOL, tag
-                assert sig[ch] == 1.0
-                v, q = eng.ss_poisson_get_latent(ch)
-                assert relerr(q, o.q, 1e-300) < RTOL and relerr(v, o.v) < RTOL, tag
-                st = eng.ss_get_state_draw(ch)
-                assert np.max(np.abs(st - o.state)) < 1e-8 * np.abs(o.state).max(), tag
-                for j, blk in enumerate(c["blocks"]):
-                    sm = eng.ss_get_state_model(ch, j)
-                    nv = len(sm["variances"])
-                    assert relerr(sm["variances"], o.var[j], 1e-300) < RTOL, tag + (j,)
-                    assert np.array_equal(sm["suf_n"], o.suf_n[j][:nv]), tag + (j,)
-                    assert relerr(sm["suf_ss"], o.suf_ss[j][:nv], 1e-300) < RTOL, tag + (j,)
-    finally:
-        oracle.set_slot_limit(0)
-    for ch, o in ora.items():
+    def end(k, ch, o):
         print("case %d chain %d: smallest branch margin of the imputer %.3e" % (k, ch, o.margin))
         assert o.margin > 1e-9, (ch, o.margin)
-    # several rounds in one call: the same draws
-    eng2 = engine()
-    eng2.ss_poisson_sweep(c["rounds"])
-    for u, w in zip(eng.get_states(), eng2.get_states()):
-        assert np.array_equal(u, w)
-    for u, w in zip(eng.ss_poisson_get_latent(1), eng2.ss_poisson_get_latent(1)):
-        assert np.array_equal(u, w)
-    assert np.array_equal(eng.ss_get_state_draw(1), eng2.ss_get_state_draw(1))
+    checks.rounds_match_restatement(POISSON, oracle, k, end)
 
 
 # ---- 4. distribution -----------------------------------------------------------------------------
 @gpu
 def test_state_draws_have_the_dense_posterior_moments():
-    blocks, S, var, v, obs, q, H = spo.fixed_case()
-    T, chains = len(v), 4096
-    X = np.ones((T, 1))
-    g0 = np.zeros(1, np.uint8)
-    eng = poisson_engine(chains, 20263, np.ones(T), np.ones(T), X, obs.astype(np.uint8), blocks, g0)
-    eng.ss_poisson_set_latent(v, q)
-    eng.ss_poisson_impute_state()
-    draws = np.stack([eng.ss_get_state_draw(c).reshape(-1) for c in range(chains)])
-    mean, cov = spo.dense_posterior(S, var, v, obs, H)
-    d = len(mean)
-    bound = spo.bonferroni_bound(d + d * (d + 1) // 2)   # (fixed with the seed before any run)
-    zm, zc = spo.moment_z(draws, mean, cov)
-    print("largest |z|: mean %.3f covariance %.3f, bound %.3f" % (np.abs(zm).max(), np.abs(zc).max(), bound))
-    assert np.abs(zm).max() < bound
-    assert np.abs(zc).max() < bound
+    checks.state_draws_have_the_dense_posterior_moments(POISSON, 20263)
 
 
 # ---- 5. interface --------------------------------------------------------------------------------
-def small_problem():
-    T, p = 30, 3
-    X, counts, exposure, series = count_series(T, p, 2)
-    return T, p, X, counts, exposure, spec(series, [("level",)])
-
-
 @gpu
 def test_refusals_and_their_texts():
     import boom_amd
-    T, p, X, counts, exposure, blocks = small_problem()
+    T, p, X, (counts, exposure), series, blocks = POISSON.small()
     mu, prec, pi = slab_of(p)
     mix = golden_mix()
     g0 = np.zeros(p, np.uint8)
     eng = boom_amd.Engine(2, seed=1)
-    first = "call ba_ss_poisson_set_data first"
-    # the family's calls on an engine without its data
-    refused(lambda: eng.ss_poisson_sweep(1), first)
-    refused(lambda: eng.ss_poisson_get_latent(0), first)
-    eng.ss_set_data(np.log(counts + 0.5), X, None)
-    refused(lambda: eng.ss_poisson_sweep(1), first)
-    refused(lambda: eng.ss_poisson_impute_state(), first)
-    refused(lambda: eng.ss_poisson_set_latent(np.zeros(T), np.ones(T)), first)
+    checks.refusals_before_the_data(POISSON, eng, T, X, np.log(counts + 0.5))
     # the data: counts and exposures are checked at the observed steps only
     obs = np.ones(T, np.uint8)
     obs[3] = 0
@@ -286,9 +87,7 @@ def test_refusals_and_their_texts():
     # no state list
     eng.sss_set_slab(mu, prec, scales_with_sigsq=False)
     eng.set_spike(pi)
-    refused(lambda: eng.ss_poisson_sweep(1), "call ba_ss_add_state_model first")
-    eng.ss_set_local_level(0.01, 0.1, 1.0, 0.0, 1.0, 1.0)
-    refused(lambda: eng.ss_poisson_sweep(1), "not ba_ss_set_local_level")
+    checks.refusals_without_a_state_list(POISSON, eng)
     eng.ss_set_state_models(blocks)
     eng.set_state(g0)
     # sweeps of other kinds
@@ -300,20 +99,12 @@ def test_refusals_and_their_texts():
         refused(call, use)
     refused(lambda: eng.ss_forecast(np.zeros((2, p))), "forecasts with Poisson observation noise are not implemented")
     # latent data
-    for bad, text in ((-1.0, "precision must be non-negative."), (0.0, "must be positive and finite"),
-                      (np.inf, "must be positive and finite"), (np.nan, "must be positive and finite")):
-        q = np.ones(T)
-        q[4] = bad
-        refused(lambda: eng.ss_poisson_set_latent(np.zeros(T), q), text)
+    checks.refusals_of_latent_data(POISSON, eng, T)
     q = np.ones(T)
     q[3] = -1.0                                            # (a missing step's entries are not read)
     eng.ss_poisson_set_latent(np.zeros(T), q)
     # a slab that scales with sigma^2
-    eng.sss_set_slab(mu, prec, scales_with_sigsq=True)
-    refused(lambda: eng.ss_poisson_sweep(1), "fixed-precision slab (scales_with_sigsq = 0)")
-    eng.sss_set_slab(mu, prec, scales_with_sigsq=False)
-    eng.ss_poisson_sweep(2)
-    assert eng.ss_get_state_draw(0).shape == (T, 1)
+    checks.refusal_of_the_other_slab(POISSON, eng, T, mu, prec, "fixed-precision slab (scales_with_sigsq = 0)")
     v, q = eng.ss_poisson_get_latent(0)
     assert v[3] == 0.0 and q[3] == 0.0 and np.all(q[obs.astype(bool)] > 0)
 
@@ -322,7 +113,7 @@ def test_refusals_and_their_texts():
 def test_a_sweep_without_mixtures_is_refused():
     import boom_amd
     from boom_amd.capi import _fcol, _f64, _p
-    T, p, X, counts, exposure, blocks = small_problem()
+    T, p, X, (counts, exposure), _, blocks = POISSON.small()
     eng = boom_amd.Engine(2, seed=1)
     eng._check(eng.lib.ba_ss_poisson_set_data(eng._h, T, p, _p(_f64(counts)), _p(_f64(exposure)), _p(_fcol(X)), None))
     eng.p, eng.T = p, T
@@ -342,84 +133,23 @@ def test_a_sweep_without_mixtures_is_refused():
 
 @gpu
 def test_recorded_draws_and_get_state():
-    T, p, X, counts, exposure, blocks = small_problem()
-    g0 = np.zeros(p, np.uint8)
-    g0[0] = 1
-    chains, seed, n = 3, 19, 6
-    a = poisson_engine(chains, seed, counts, exposure, X, None, blocks, g0)
-    a.enable_draws(n)
-    a.ss_poisson_sweep(n)
-    g, b, s = a.get_draws(0, n)
-    b1 = poisson_engine(chains, seed, counts, exposure, X, None, blocks, g0)
-    for r in range(n):
-        b1.ss_poisson_sweep(1)
-        gg, bb, ss = b1.get_state(0)
-        assert np.array_equal(g[r], gg) and np.array_equal(b[r], bb) and s[r] == ss == 1.0, r
-    gg, bb, ss = a.get_state(0)
-    assert np.array_equal(g[-1], gg) and np.array_equal(b[-1], bb) and s[-1] == ss
+    checks.recorded_draws_and_get_state(POISSON)
 
 
 @gpu
 def test_pybind_classes_agree_with_the_c_abi():
-    """boom.StateSpacePoissonModel + StateSpacePoissonPosteriorSampler (the façade of
-    include/boom_amd.hpp behind them): three rounds == the engine through the C-ABI on the same
-    seed, bit for bit"""
-    import boom_amd._boom as boom
-    T, p, chains, seed = 40, 4, 3, 23
-    X, counts, exposure, series = count_series(T, p, 6, seasons=4)
-    obs = np.ones(T, np.uint8)
-    obs[[9, 30]] = 0
-    desc = [("level",), ("seasonal", 4, 1)]
-    blocks = general_spec(series, desc)
-    mu, prec, pi = slab_of(p)
+    X, counts, exposure, series = count_series(40, 4, 6, seasons=4)
     mix = golden_mix()
-    model = boom.StateSpacePoissonModel(counts, exposure, X, [bool(o) for o in obs], chains=chains, seed=seed)
-    model.set_mixture_table([int(c) for c in mix["counts"]], [int(c) for c in mix["ncomp"]], mix["mu"], mix["sigma"],
-                            mix["weight"], mix["largest_index"])
-    b = blocks[0]
-    level = boom.LocalLevelStateModel(float(b["initial_sigma"][0]))
-    level.set_initial_state_mean(float(b["a0"][0]))
-    level.set_initial_state_variance(float(b["P0"][0]))
-    level.set_prior(b["df"][0], b["sigma_guess"][0], b["sigma_upper_limit"][0])
-    b = blocks[1]
-    seas = boom.SeasonalStateModel(4)
-    seas.set_sigsq(b["initial_sigma"][0] ** 2)
-    seas.set_prior(b["df"][0], b["sigma_guess"][0], b["sigma_upper_limit"][0])
-    seas.set_initial_state_mean(b["a0"])
-    seas.set_initial_state_variance(b["P0"][0])
-    model.add_state(level)
-    model.add_state(seas)
-    with pytest.raises(Exception, match="Slab does not match model dimension."):
-        boom.StateSpacePoissonPosteriorSampler(model, boom.MvnModel(np.zeros(p + 1), np.eye(p + 1), True),
-                                               boom.VariableSelectionPrior(pi))
-    with pytest.raises(Exception, match="Spike does not match model dimension."):
-        boom.StateSpacePoissonPosteriorSampler(model, boom.MvnModel(mu, prec, True),
-                                               boom.VariableSelectionPrior(np.full(p + 1, 0.5)))
-    sampler = boom.StateSpacePoissonPosteriorSampler(model, boom.MvnModel(mu, prec, True), boom.VariableSelectionPrior(pi))
-    model.set_method(sampler)
-    assert model.state_dimension == 4
-    eng = poisson_engine(chains, seed, counts, exposure, X, obs, blocks, np.zeros(p, np.uint8))
-    for _ in range(3):
-        model.sample_posterior()
-        eng.ss_poisson_sweep(1)
-    for u, w in zip(model.chain_states(), eng.get_states()):
-        assert np.array_equal(u, w)
-    for c in range(chains):
-        v, q = eng.ss_poisson_get_latent(c)
-        assert np.array_equal(model.latent_values(c), v) and np.array_equal(model.latent_precisions(c), q)
-        assert np.array_equal(model.state(c), eng.ss_get_state_draw(c).T)
-    # set_latent_data and impute_state through the classes
-    model.set_latent_data(series, np.full(T, 2.0))
-    model.impute_state()
-    eng.ss_poisson_set_latent(series, np.full(T, 2.0))
-    eng.ss_poisson_impute_state()
-    assert np.array_equal(model.state(1), eng.ss_get_state_draw(1).T)
+
+    def model_of(boom, is_observed, chains, seed):
+        model = boom.StateSpacePoissonModel(counts, exposure, X, is_observed, chains=chains, seed=seed)
+        model.set_mixture_table([int(c) for c in mix["counts"]], [int(c) for c in mix["ncomp"]], mix["mu"], mix["sigma"],
+                                mix["weight"], mix["largest_index"])
+        return model
+    checks.latent_pybind_classes_agree_with_the_c_abi(POISSON, X, (counts, exposure), series, model_of)
 
 
 # ---- 6. signal recovery --------------------------------------------------------------------------
-RECOVERY_SHAPE, RECOVERY_SEED, RECOVERY_COEF = (200, 6), 11, (0.5, -0.5)
-
-
 @gpu
 def test_ss_poisson_recovers_the_signals():
     """a series whose rate depends on 2 of 6 predictors: after 150 + 100 rounds of 64 chains the
@@ -435,8 +165,8 @@ def test_ss_poisson_recovers_the_signals():
     data seed is therefore one whose four null predictors all have |z| < 1 in a plain Poisson
     regression with the generating state as offset, which tests/test_ss_poisson_cpu.py checks
     without this sampler; the two signals sit at |z| > 10."""
-    T, p = RECOVERY_SHAPE
-    X, counts, exposure, series = count_series(T, p, RECOVERY_SEED, coef=RECOVERY_COEF)
+    X, counts, exposure, series = recovery_data("poisson")
+    p = X.shape[1]
     blocks = spec(series, [("level",)])
     eng = poisson_engine(64, 5, counts, exposure, X, None, blocks, np.zeros(p, np.uint8), pi=np.full(p, 1.0 / p))
     eng.ss_poisson_sweep(150)

@@ -435,7 +435,7 @@ def test_refusals_round_trips_and_the_list_reset():
     assert np.array_equal(twins[0], twins[1])
     # the other observation families: the model added on such data ...
     text = "the regression holiday is built for the Gaussian observation model only (not the Student-t, Poisson and logit families)"
-    from test_ss_poisson_gpu import count_series, golden_mix
+    from ss_family_cases import count_series, golden_mix
     Xc, counts, exposure, _ = count_series(T, src.P, 4)
     families = [
         (lambda e: e.ss_student_set_data(y, X, None), lambda e: e.ss_student_sweep(1), True),

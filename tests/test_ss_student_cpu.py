@@ -16,6 +16,7 @@ import pytest
 import ss_student_oracle as sso
 from cases import bsts_priors, general_data, general_spec
 from oracle_lib import ssvs_options
+from ss_family_cases import ROUND_CASES, round_case
 
 
 @pytest.mark.parametrize("desc,T,missing", [
@@ -76,14 +77,14 @@ def test_varying_weights_match_the_dense_posterior():
 def test_parity_seeds_keep_their_margins(oracle):
     """the whole-round cases of the device test: every checked chain's slice margin stays
     above 1e-9 over the rounds compared, so none of them is skipped (the cap is one in ten)"""
-    from test_ss_student_gpu import ROUND_CASES, round_case
+    cases = range(len(ROUND_CASES["student"]))
     skipped = 0
-    for k in range(len(ROUND_CASES)):
-        c = round_case(k)
+    for k in cases:
+        c = round_case("student", k)
         for chain in c["check"]:
             o = c["oracle"](oracle, chain)
             for _ in range(c["rounds"]):
                 o.draw()
             skipped += o.margin < 1e-9
-    total = sum(len(round_case(k)["check"]) for k in range(len(ROUND_CASES)))
+    total = sum(len(round_case("student", k)["check"]) for k in cases)
     assert skipped * 10 <= total, (skipped, total)

@@ -13,62 +13,18 @@ steps, the round's order.
   distribution  4096 chains' state draws against the dense Gaussian posterior
   interface     refusals and their texts, recorded draws, ba_get_state
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
+import ss_family_checks as checks
 import ss_student_oracle as sso
-from cases import bsts_priors, general_data, general_spec, kernel_instance
+from cases import general_data, general_spec, kernel_instance
+from ss_family_cases import (ROUND_CASES, chain_parameters, gaussian_engine, relerr, round_case, state_stream,
+                             student_engine, student_slab_of as slab_of)
+from ss_family_checks import RTOL, STUDENT
 from ss_gpu_helpers import refused
 
 gpu = pytest.mark.gpu
-RTOL = 1e-8
-
-
-def relerr(a, b, floor=1e-3):
-    a, b = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
-    return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), floor)))
-
-
-def slab_of(p):
-    return np.zeros(p), 0.1 * np.eye(p), np.full(p, min(0.9, 2.5 / p))
-
-
-def student_engine(chains, seed, y, X, obs, blocks, g0, nu_prior=(0, 0.1, 100.0), sigma_prior=(1.0, 1.0),
-                   sigma_max=np.inf):
-    import boom_amd
-    p = X.shape[1]
-    mu, prec, pi = slab_of(p)
-    eng = boom_amd.Engine(chains, seed=seed)
-    eng.ss_student_set_data(y, X, obs)
-    eng.sss_set_slab(mu, prec, scales_with_sigsq=True)
-    eng.set_spike(pi)
-    eng.set_sigma_prior(sigma_prior[0], sigma_prior[1], sigma_max)
-    eng.student_set_nu_prior(*nu_prior)
-    eng.ss_set_state_models(blocks)
-    eng.set_state(g0)
-    return eng
-
-
-def gaussian_engine(chains, seed, y, X, obs, blocks, g0):
-    import boom_amd
-    prior, _, sig_up = bsts_priors(X, y, 2)
-    eng = boom_amd.Engine(chains, seed=seed)
-    eng.ss_set_data(y, X, obs)
-    eng.set_priors(prior["b"], prior["ominv"], prior["pi"], prior["df"], prior["sigma_guess"],
-                   sigma_upper_limit=sig_up)
-    eng.ss_set_state_models(blocks)
-    eng.ss_set_tuning(kernel=0)   # the general kernel: the one the H_t instances are instances of
-    eng.set_state(g0)
-    return eng
-
-
-def chain_parameters(p, chains, seed):
-    rs = np.random.Generator(np.random.PCG64(seed))
-    gam = (rs.uniform(size=(chains, p)) < 0.6).astype(np.uint8)
-    gam[:, 0] = 1
-    return gam, rs.standard_normal((chains, p)) * gam
 
 
 # ---- 3. identities ---------------------------------------------------------------------------
@@ -108,22 +64,10 @@ def test_constant_weights_equal_the_scalar_kernel(desc, T, missing, weight):
     a.ss_student_set_weights(np.full(T, weight))
     a.ss_student_impute_state()
     b.ss_impute_state()
-    for c in range(chains):
-        assert np.array_equal(a.ss_get_state_draw(c), b.ss_get_state_draw(c)), c
-        for k in range(len(blocks)):
-            u, v = a.ss_get_state_model(c, k), b.ss_get_state_model(c, k)
-            assert np.array_equal(u["suf_ss"], v["suf_ss"]) and np.array_equal(u["suf_n"], v["suf_n"]), (c, k)
+    checks.same_state_and_statistics(a, b, chains, blocks)
 
 
 # ---- 4. filter edges ---------------------------------------------------------------------------
-def state_stream(oracle, seed, chain):
-    L = oracle.lib
-    L.bo_rnorm.argtypes = [C.c_void_p, C.c_double, C.c_double]
-    L.bo_rnorm.restype = C.c_double
-    rng = oracle.rng_philox(seed, chain, 2, 0)
-    return lambda mu, sd: L.bo_rnorm(C.byref(rng), float(mu), float(sd))
-
-
 @gpu
 @pytest.mark.parametrize("nu", [5.0, 2.0, 1.5])
 def test_impute_state_matches_restatement_at_the_edges(oracle, nu):
@@ -161,40 +105,13 @@ def test_impute_state_matches_restatement_at_the_edges(oracle, nu):
 
 
 # ---- 5. whole rounds ----------------------------------------------------------------------------
-ROUND_CASES = [
-    # blocks, missing steps, sigma upper limit, nu prior
-    ([("trend",), ("seasonal", 4, 1)], [], 1.5, (1, 2.0, 0.1)),
-    ([("level",)], [5, 23], np.inf, (0, 0.1, 100.0)),
-]
-
-
-def round_case(k):
-    desc, miss, smax, nup = ROUND_CASES[k]
-    T, p, chains, seed, rounds = 40, 5, 4, 57 + k, 12
-    seas = [(b[1], b[2]) for b in desc if b[0] == "seasonal"]
-    X, y, _, _ = general_data(T, p, 2, seas, seed=31 + k)
-    rs = np.random.Generator(np.random.PCG64(9 + k))
-    y = y + np.where(rs.uniform(size=T) < 0.1, 6.0 * rs.standard_normal(T), 0.0)   # a few outliers
-    obs = np.ones(T, np.uint8)
-    obs[miss] = 0
-    blocks = general_spec(y, desc)
-    g0 = np.zeros(p, np.uint8)
-    g0[0] = 1
-    mu, prec, pi = slab_of(p)
-
-    def make_oracle(o, chain):
-        return sso.SsStudentOracle(o, y, X, obs, blocks, mu, prec, pi, seed, chain, g0, nu_prior=nup,
-                                   sigma_max=smax)
-    return dict(T=T, p=p, chains=chains, seed=seed, rounds=rounds, X=X, y=y, obs=obs, blocks=blocks, g0=g0,
-                smax=smax, nup=nup, check=[0, chains - 1], oracle=make_oracle)
-
-
 @gpu
-@pytest.mark.parametrize("k", range(len(ROUND_CASES)))
+@pytest.mark.parametrize("k", range(len(ROUND_CASES["student"])))
 def test_rounds_match_restatement(oracle, k):
-    c = round_case(k)
-    eng = student_engine(c["chains"], c["seed"], c["y"], c["X"], c["obs"], c["blocks"], c["g0"],
-                         nu_prior=c["nup"], sigma_max=c["smax"])
+    """(the family's own loop: sigma^2 and nu are drawn, the weights stand where the others have value and
+    precision, and the device reports margins of its own)"""
+    c = round_case("student", k)
+    eng = c["engine"]()
     ora = {ch: c["oracle"](oracle, ch) for ch in c["check"]}
     for r in range(c["rounds"]):
         eng.ss_student_sweep(1)   # (round 0: the start from all weights 1, two weight imputations)
@@ -208,20 +125,12 @@ def test_rounds_match_restatement(oracle, k):
             assert relerr(sig[ch], s2, 1e-300) < RTOL and relerr(nu[ch], v, 1e-300) < RTOL, tag
             assert sig[ch] <= c["smax"] ** 2
             assert relerr(eng.ss_student_get_weights(ch), o.w, 1e-300) < RTOL, tag
-            st = eng.ss_get_state_draw(ch)
-            assert np.max(np.abs(st - o.state)) < 1e-8 * np.abs(o.state).max(), tag
-            for j, blk in enumerate(c["blocks"]):
-                sm = eng.ss_get_state_model(ch, j)
-                nv = len(sm["variances"])
-                assert relerr(sm["variances"], o.var[j], 1e-300) < RTOL, tag + (j,)
-                assert np.array_equal(sm["suf_n"], o.suf_n[j][:nv]), tag + (j,)
-                assert relerr(sm["suf_ss"], o.suf_ss[j][:nv], 1e-300) < RTOL, tag + (j,)
+            checks.state_and_models_match(eng, o, c["blocks"], ch, tag)
     margin = eng.student_get_margin()
     for ch, o in ora.items():
         assert o.margin > 1e-9 and margin[ch] > 1e-9, (ch, o.margin, margin[ch])
     # several rounds in one call: the same draws
-    eng2 = student_engine(c["chains"], c["seed"], c["y"], c["X"], c["obs"], c["blocks"], c["g0"],
-                          nu_prior=c["nup"], sigma_max=c["smax"])
+    eng2 = c["engine"]()
     eng2.ss_student_sweep(c["rounds"])
     for u, v in zip(eng.get_states(), eng2.get_states()):
         assert np.array_equal(u, v)
@@ -241,45 +150,24 @@ def test_state_draws_have_the_dense_posterior_moments():
     eng.student_set_nu(nu)
     eng.ss_student_set_weights(w)
     eng.ss_student_impute_state()
-    draws = np.stack([eng.ss_get_state_draw(c).reshape(-1) for c in range(chains)])
-    mean, cov = sso.dense_posterior(S, var, y, obs, H)
-    d = len(mean)
-    bound = sso.bonferroni_bound(d + d * (d + 1) // 2)   # (fixed with the seed before any run)
-    zm, zc = sso.moment_z(draws, mean, cov)
-    print("largest |z|: mean %.3f covariance %.3f, bound %.3f" % (np.abs(zm).max(), np.abs(zc).max(), bound))
-    assert np.abs(zm).max() < bound
-    assert np.abs(zc).max() < bound
+    checks.draws_have_the_moments(eng, chains, S, var, y, obs, H)
 
 
 # ---- 7. interface -------------------------------------------------------------------------------
-def small_problem():
-    T, p = 30, 3
-    X, y, _, _ = general_data(T, p, 1, [], seed=2)
-    return T, p, X, y, general_spec(y, [("level",)])
-
-
 @gpu
 def test_refusals_and_their_texts():
     import boom_amd
-    T, p, X, y, blocks = small_problem()
+    T, p, X, (y,), _, blocks = STUDENT.small()
     mu, prec, pi = slab_of(p)
     g0 = np.zeros(p, np.uint8)
     eng = boom_amd.Engine(2, seed=1)
-    # the family's calls on an engine without its data
-    refused(lambda: eng.ss_student_sweep(1), "call ba_ss_student_set_data first")
-    refused(lambda: eng.ss_student_get_weights(0), "call ba_ss_student_set_data first")
-    eng.ss_set_data(y, X, None)
-    refused(lambda: eng.ss_student_sweep(1), "call ba_ss_student_set_data first")
-    refused(lambda: eng.ss_student_impute_state(), "call ba_ss_student_set_data first")
-    refused(lambda: eng.ss_student_set_weights(np.ones(T)), "call ba_ss_student_set_data first")
+    checks.refusals_before_the_data(STUDENT, eng, T, X, y)
     # no state list
     eng.ss_student_set_data(y, X, None)
     eng.sss_set_slab(mu, prec, scales_with_sigsq=True)
     eng.set_spike(pi)
     eng.set_sigma_prior(1.0, 1.0)
-    refused(lambda: eng.ss_student_sweep(1), "call ba_ss_add_state_model first")
-    eng.ss_set_local_level(0.01, 0.1, 1.0, float(y[0]), 1.0, 1.0)
-    refused(lambda: eng.ss_student_sweep(1), "not ba_ss_set_local_level")
+    checks.refusals_without_a_state_list(STUDENT, eng, level_mean=float(y[0]))
     eng.ss_set_state_models(blocks)
     eng.set_state(g0)
     # sweeps of other kinds
@@ -293,32 +181,13 @@ def test_refusals_and_their_texts():
         w[4] = bad
         refused(lambda: eng.ss_student_set_weights(w), "Weights must be finite and non-negative.")
     # a slab that does not scale with sigma^2
-    eng.sss_set_slab(mu, prec, scales_with_sigsq=False)
-    refused(lambda: eng.ss_student_sweep(1), "scales with sigma^2 (scales_with_sigsq = 1)")
-    eng.sss_set_slab(mu, prec, scales_with_sigsq=True)
-    eng.ss_student_sweep(2)
-    assert eng.ss_get_state_draw(0).shape == (T, 1)
+    checks.refusal_of_the_other_slab(STUDENT, eng, T, mu, prec, "scales with sigma^2 (scales_with_sigsq = 1)")
 
 
 @gpu
 def test_recorded_draws_and_get_state():
-    T, p, X, y, blocks = small_problem()
-    g0 = np.zeros(p, np.uint8)
-    g0[0] = 1
-    chains, seed, n = 3, 19, 6
-    a = student_engine(chains, seed, y, X, None, blocks, g0)
-    a.enable_draws(n)
-    a.ss_student_sweep(n)
-    g, b, s = a.get_draws(0, n)
-    nus = a.student_get_nu_draws(0, n)
-    b1 = student_engine(chains, seed, y, X, None, blocks, g0)
-    for r in range(n):
-        b1.ss_student_sweep(1)
-        gg, bb, ss = b1.get_state(0)
-        assert np.array_equal(g[r], gg) and np.array_equal(b[r], bb) and s[r] == ss, r
-        assert nus[r] == b1.student_get_nu(0), r
-    gg, bb, ss = a.get_state(0)
-    assert np.array_equal(g[-1], gg) and np.array_equal(b[-1], bb) and s[-1] == ss
+    checks.recorded_draws_and_get_state(STUDENT, recorded=(lambda a, n: a.student_get_nu_draws(0, n),
+                                                           lambda b1: b1.student_get_nu(0)))
 
 
 @gpu
@@ -333,31 +202,14 @@ def test_pybind_classes_agree_with_the_c_abi():
     blocks = general_spec(y, desc)
     mu, prec, pi = slab_of(p)
     model = boom.StateSpaceStudentRegressionModel(y, X, [bool(o) for o in obs], chains=chains, seed=seed)
-    b = blocks[0]
-    level = boom.LocalLevelStateModel(float(b["initial_sigma"][0]))
-    level.set_initial_state_mean(float(b["a0"][0]))
-    level.set_initial_state_variance(float(b["P0"][0]))
-    level.set_prior(b["df"][0], b["sigma_guess"][0], b["sigma_upper_limit"][0])
-    b = blocks[1]
-    seas = boom.SeasonalStateModel(4)
-    seas.set_sigsq(b["initial_sigma"][0] ** 2)
-    seas.set_prior(b["df"][0], b["sigma_guess"][0], b["sigma_upper_limit"][0])
-    seas.set_initial_state_mean(b["a0"])
-    seas.set_initial_state_variance(b["P0"][0])
-    model.add_state(level)
-    model.add_state(seas)
+    for sm in checks.level_and_seasonal(boom, blocks):
+        model.add_state(sm)
     sampler = boom.StateSpaceStudentPosteriorSampler(model, boom.MvnGivenScalarSigma(mu, prec),
                                                      boom.VariableSelectionPrior(pi), boom.ChisqModel(1.0, 1.0),
                                                      boom.UniformModel(0.1, 100.0))
     model.set_method(sampler)
-    assert model.state_dimension == 4
     eng = student_engine(chains, seed, y, X, obs, blocks, np.zeros(p, np.uint8))
-    for _ in range(3):
-        model.sample_posterior()
-        eng.ss_student_sweep(1)
-    for u, v in zip(model.chain_states(), eng.get_states()):
-        assert np.array_equal(u, v)
+    checks.three_rounds_agree(STUDENT, model, eng)
     for c in range(chains):
         assert model.nu(c) == eng.student_get_nu(c) and model.sigsq(c) == eng.get_state(c)[2]
         assert np.array_equal(model.weights(c), eng.ss_student_get_weights(c))
-        assert np.array_equal(model.state(c), eng.ss_get_state_draw(c).T)

@@ -10,7 +10,6 @@ tests/golden/poisson_exposure.npz holds."""
 import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -19,6 +18,7 @@ import numpy as np  # noqa: E402
 
 import boom_amd  # noqa: E402
 from cases import bsts_priors, general_spec  # noqa: E402
+from ss_bench_timing import timed  # noqa: E402
 
 T, p, chains = (int(v) for v in (sys.argv[1:4] or (2000, 100, 1024)))
 nsw = int(sys.argv[4]) if len(sys.argv) > 4 else 10
@@ -27,21 +27,6 @@ mix = dict(counts=g["mix_counts"], ncomp=g["mix_ncomp"], mu=g["mix_mu"], sigma=g
            weight=g["mix_weight"], largest_index=int(g["mix_largest_index"]))
 g0 = np.zeros(p, np.uint8)
 g0[0] = 1
-
-
-def timed(eng, sweep):
-    sweep(max(2, nsw // 2))   # burn-in: the models grow to their size
-    t0 = time.perf_counter()
-    sweep(nsw)
-    dt = time.perf_counter() - t0
-    eng.set_kernel_timing(True)
-    eng.kernel_times(reset=True)
-    sweep(nsw)
-    kt = eng.kernel_times(reset=True)
-    eng.set_kernel_timing(False)
-    return dict(ms_per_round=dt / nsw * 1e3, kernel_ms_per_round={k: round(v[0] / nsw, 4) for k, v in kt.items()},
-                launches_per_round={k: v[1] / nsw for k, v in kt.items()},
-                kbar=float(eng.get_states()[0].sum(1).mean()))
 
 
 def shape(nseasons):
@@ -63,7 +48,7 @@ def shape(nseasons):
     poi.set_spike(np.full(p, 5.0 / p))
     poi.ss_set_state_models(blocks)
     poi.set_state(g0)
-    poisson = timed(poi, poi.ss_poisson_sweep)
+    poisson = timed(poi, poi.ss_poisson_sweep, nsw)
     del poi
 
     stu = boom_amd.Engine(chains, seed=4)
@@ -73,7 +58,7 @@ def shape(nseasons):
     stu.set_sigma_prior(1.0, 1.0)
     stu.ss_set_state_models(blocks)
     stu.set_state(g0)
-    student = timed(stu, stu.ss_student_sweep)
+    student = timed(stu, stu.ss_student_sweep, nsw)
     del stu
 
     prior, _, sig_up = bsts_priors(X, y, 5)
@@ -83,7 +68,7 @@ def shape(nseasons):
     gau.ss_set_state_models(blocks)
     gau.ss_set_tuning(kernel=0)
     gau.set_state(g0)
-    gaussian = timed(gau, gau.ss_sweep)
+    gaussian = timed(gau, gau.ss_sweep, nsw)
     del gau
 
     draw = lambda r: r["kernel_ms_per_round"].get("ssm_simsmooth_kernel", 0.0)   # noqa: E731

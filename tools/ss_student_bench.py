@@ -8,7 +8,6 @@ usage: ss_student_bench.py [T p chains [timed rounds [nseasons]]]   (default: T 
 import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -17,6 +16,7 @@ import numpy as np  # noqa: E402
 
 import boom_amd  # noqa: E402
 from cases import bsts_priors, general_spec  # noqa: E402
+from ss_bench_timing import timed  # noqa: E402
 
 T, p, chains = (int(v) for v in (sys.argv[1:4] or (2000, 100, 1024)))
 nsw = int(sys.argv[4]) if len(sys.argv) > 4 else 10
@@ -34,21 +34,6 @@ g0 = np.zeros(p, np.uint8)
 g0[0] = 1
 
 
-def timed(eng, sweep):
-    sweep(max(2, nsw // 2))   # burn-in: the models grow to their size
-    t0 = time.perf_counter()
-    sweep(nsw)
-    dt = time.perf_counter() - t0
-    eng.set_kernel_timing(True)
-    eng.kernel_times(reset=True)
-    sweep(nsw)
-    kt = eng.kernel_times(reset=True)
-    eng.set_kernel_timing(False)
-    return dict(ms_per_round=dt / nsw * 1e3, kernel_ms_per_round={k: round(v[0] / nsw, 4) for k, v in kt.items()},
-                launches_per_round={k: v[1] / nsw for k, v in kt.items()},
-                kbar=float(eng.get_states()[0].sum(1).mean()))
-
-
 stu = boom_amd.Engine(chains, seed=4)
 stu.ss_student_set_data(y, X, None)
 stu.sss_set_slab(np.zeros(p), 0.01 * np.eye(p), scales_with_sigsq=True)
@@ -56,7 +41,7 @@ stu.set_spike(np.full(p, 5.0 / p))
 stu.set_sigma_prior(1.0, 1.0)
 stu.ss_set_state_models(blocks)
 stu.set_state(g0)
-student = timed(stu, stu.ss_student_sweep)
+student = timed(stu, stu.ss_student_sweep, nsw)
 del stu
 
 prior, _, sig_up = bsts_priors(X, y, 5)
@@ -66,7 +51,7 @@ gau.set_priors(prior["b"], prior["ominv"], prior["pi"], prior["df"], prior["sigm
 gau.ss_set_state_models(blocks)
 gau.ss_set_tuning(kernel=0)
 gau.set_state(g0)
-gaussian = timed(gau, gau.ss_sweep)
+gaussian = timed(gau, gau.ss_sweep, nsw)
 
 ks, kg = student["kernel_ms_per_round"].get("ssm_simsmooth_kernel", 0.0), gaussian["kernel_ms_per_round"].get("ssm_simsmooth_kernel", 0.0)
 print(json.dumps(dict(T=T, p=p, chains=chains, rounds=nsw, state_models=[d[0] for d in desc], nseasons=nseasons,
