@@ -28,6 +28,16 @@
 //                                              and 6 are COUNTS (sweeps with a stop, walks
 //                                              forked other than a sweep's first, those rolled
 //                                              back); 7 everything else                       core
+//   -DBA_STAMPS -DBA_STAMPS7  XSTAMP(c, i)     the master's "everything else" of MSTAMP, itemised:
+//                                              0 a join's bookkeeping (behind the barrier), 1 the
+//                                              loop top (a phase's end to the next phase's first
+//                                              line: the loop's condition, the event test, the
+//                                              phase dispatch), 2 PH_FLIPS bookkeeping around a
+//                                              walk or a stop, 3 batch-mode rounds, 4 PH_BEGIN's
+//                                              decisions ahead of the sweep-start copy, 5 a sweep
+//                                              start that does not fork (the all-threads shuffle);
+//                                              6 is a COUNT (passes of the loop); 7 what the other
+//                                              sets name (TSTAMP's pieces, waits, fills, events)   core
 //   -DBA_PSTAMPS              PSTAMP(i)        the sweep kernel's prologue (absolute stamps)  core
 //   -DBA_KSTAMPS              KSTAMP(i)        the local-level Kalman kernel's phases, and
 //                             SSTAMP(i)        the structural kernels' (chain 0 prints)       core
@@ -79,6 +89,13 @@ struct StampCtx { long long last; double ph[8]; };
 #else
 #define MSTAMP(c, i) BA_STAMP_OFF
 #define MCOUNT(c, i, x) BA_STAMP_OFF
+#endif
+#if defined(BA_STAMPS) && defined(BA_STAMPS7)
+#define XSTAMP(c, i) BA_STAMP_ADD((c).ph, (c).last, i, BA_CORE_CLOCK, double)
+#define XCOUNT(c, i, x) do { (c).ph[i] += (double)(x); } while (0)
+#else
+#define XSTAMP(c, i) BA_STAMP_OFF
+#define XCOUNT(c, i, x) BA_STAMP_OFF
 #endif
 #ifdef BA_PSTAMPS
 #define PSTAMP(i) pst[i] = (long long)BA_CORE_CLOCK

@@ -1249,6 +1249,11 @@ __device__ __forceinline__ void propose_swap(const SsvsParams &P, Chain &ch,
 // at the join a stop in the walk rolls the tail back.  A walk resumed after a stop (and the
 // unforked first walk after a table was built) forks the same way -- the tail's position does
 // not depend on what the rest of the walk finds -- unless walk_policy is 3 or 4.
+// The fork's shuffle targets: with two wavefronts the master draws none of them.  It leaves the
+// position its tail ended at in the control block (CT_NEXT); a walk that found no stop lets that
+// tail stand, and wave 1, idle from the join to the next command, draws the next sweep's targets
+// from there.  The fork's command names the position again: targets drawn for another one (or
+// none) are drawn by wave 1 then.  With four wavefronts all share them behind the command.
 //
 // The master's state machine: PH_BEGIN (shuffle or fork) -> PH_FLIPS (rounds of
 // proposals / table walks up to the next stop; a stop queues an event) ->
@@ -1258,12 +1263,13 @@ __device__ __forceinline__ void propose_swap(const SsvsParams &P, Chain &ch,
 enum : int { CMD_EXIT = 0, CMD_EVAL = 1, CMD_UNIF = 2, CMD_DECIDE = 3, CMD_SHUFFLE_DECIDE = 4 };
 // control block (doubles): 0 cmd, 1 k, 2 i0, 3..8 the current model's scalars
 // (their home), 9 nflips; u64 view at 10: flip_pos / uniform base position;
+// 15 (u64): where the next sweep starts if the forked tail stands, ~0 once wave 1 took it;
 // evaluator slots from 16; 44.. the forked tail's roll-back copy (47: the walk
 // outstanding is not the sweep's first); 48.. the
 // launch's scalar accumulators (ACC_* order)
 enum : int { CT_CMD = 0, CT_K = 1, CT_I0 = 2, CT_LOGP = 3, CT_LP = 4, CT_LDV = 5,
              CT_LDA = 6, CT_Q = 7, CT_C = 8, CT_NFLIPS = 9, CT_POS = 10, CT_PERMSEL = 12,
-             CT_EVMODE = 13, CT_CUR = 14,
+             CT_EVMODE = 13, CT_CUR = 14, CT_NEXT = 15,
              CT_SLOT0 = 16, CT_SLOT_STRIDE = 6, CT_ROLL = 44, CT_ACC = 48 };
 // slot: SL_F = permutation position of the wave's earliest stop (-1: none)
 enum : int { SL_F = 0, SL_J = 1, SL_KIND = 2, SL_LOGU = 3, SL_MARGIN = 4, SL_DELTA = 5 };
@@ -1293,6 +1299,40 @@ __device__ __forceinline__ void shuffle_targets(const PhiloxKey &key, uint64_t p
         }
       }
     }
+  }
+}
+
+// Who draws the p - 1 targets of a forked sweep's shuffle (CMD_SHUFFLE_DECIDE), called by every
+// wavefront of the workgroup once the command barrier is behind it; the master passes wave 0.
+//   W == 2, p <= FORK_SOLO_MAX_P
+//           wave 1 draws them all and the master none: wave 1 is the only reader of oth
+//           (parallel_shuffle), so its own wave_sync stands where a workgroup barrier would.
+//           (The same call, behind a join, is wave 1's draw AHEAD of the next fork: the helpers'
+//           loop in ssvs_sweep_body.h);
+//   otherwise
+//           every wavefront its share, then all meet at a workgroup barrier (there is none for
+//           the helpers alone).
+// Which lane computes which Philox block is all that differs: the targets are the same.
+// Up to FORK_SOLO_MAX_P variables, that is: wave 1's draw ahead of the fork hides in the stretch
+// from a join to the next command, ≈ 5.7 k cycles, which is what 64 lanes take for the ≈ 4.5 passes
+// of p = 512 (≈ 1.27 k a pass of 128 targets).  Every pass beyond that holds the master at the
+// command barrier, where the shared draw costs it half the passes and a barrier: on that count
+// the two are level near p = 1200, and at p = 4096 wave 1 alone measured 4.4 % slower than the
+// shared draw -- so larger models keep the shared draw of W > 2.
+constexpr int FORK_SOLO_MAX_P = 1024;
+template <int W>
+__device__ __forceinline__ bool fork_targets_solo(int p) { return W == 2 && p <= FORK_SOLO_MAX_P; }
+template <int W>
+__device__ __forceinline__ void fork_shuffle_targets(const PhiloxKey &key, uint64_t pos, int p,
+                                                     int wave, int lane, lds_u16 *oth) {
+  if (fork_targets_solo<W>(p)) {
+    if (wave != 0) {
+      shuffle_targets(key, pos, p, lane, WAVE, oth);
+      wave_sync();
+    }
+  } else {
+    shuffle_targets(key, pos, p, threadIdx.x, WAVE * W, oth);
+    __syncthreads();
   }
 }
 

@@ -145,7 +145,13 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
     // ---- helper waves: serve the master's commands ---------------------------
     sx_unused.last = (long long)__builtin_readcyclecounter();
     for (int i = 0; i < 8; ++i) sx_unused.ph[i] = 0.0;
+    // (two wavefronts: wave 1 draws a forked sweep's shuffle targets ahead of the fork's command,
+    // see the loop's end.  pre_ok: oth holds the targets of a shuffle from position pre_pos)
+    constexpr bool PREDRAW = W == 2 && !MLVS;
+    bool pre_ok = false;
+    uint64_t pre_pos = 0;
     for (;;) {
+      bool quiet = false;   // the command was a walk, and it found no stop
       HSTAMP(sx_unused, 7);
       __syncthreads();
       HSTAMP(sx_unused, 5);
@@ -168,11 +174,15 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
         HSTAMP(sx_unused, 6);
       } else if (cmd == CMD_DECIDE || cmd == CMD_SHUFFLE_DECIDE) {
         if (cmd == CMD_SHUFFLE_DECIDE) {
-          // the shuffle's p - 1 uniforms: every wavefront of the workgroup its share, the
-          // master too before it starts on the tail (it has the slack: wave 1's side of a
-          // quiet sweep is the longer one) -- then all meet once more
-          shuffle_targets(key, upos, p, threadIdx.x, WAVE * W, ch.oth);
-          __syncthreads();
+          // the shuffle's p - 1 uniforms.  With two wavefronts they are all wave 1's and the master
+          // goes straight to the tail, no second barrier: between fork and join the two sides
+          // are about as long as each other, and what wave 1 has to spare is the stretch from a
+          // join to the next command -- so it has usually drawn them THERE already (the loop's
+          // end), and draws them here only when it has not, or for another position.  With more
+          // wavefronts every one takes its share, the master too, and all meet once more
+          // (fork_shuffle_targets, ssvs_device.h)
+          if (!(PREDRAW && pre_ok && pre_pos == upos)) fork_shuffle_targets<W>(key, upos, p, wave, lane, ch.oth);
+          pre_ok = false;
         }
         if (wave == 1) {
           const int sel = (int)ctl[CT_PERMSEL];
@@ -197,13 +207,31 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
             sl[SL_LOGU] = dr.logu;
             sl[SL_MARGIN] = dr.margin;
           }
+          quiet = PREDRAW && fork_targets_solo<W>(p) && uni(dr.spos) < 0 && P.walk_policy < 3;
         }
       } else {  // CMD_UNIF: this wave's share of the shuffle uniforms
         if (p > 1) shuffle_targets(key, upos, p, threadIdx.x, WAVE * W, ch.oth, P.mode == 2);
+        pre_ok = false;
       }
       HSTAMP(sx_unused, 7);
       __syncthreads();
       HSTAMP(sx_unused, 5);
+      if (PREDRAW && quiet) {
+        // A walk that found no stop lets the tail stand, and the next sweep then forks from the
+        // position the tail ended at (the master left it in CT_NEXT before the join).  Until that
+        // fork's command comes wave 1 has nothing to do -- the master is between the join and the
+        // fork: bookkeeping, the loop, the sweep's start -- so it draws the next shuffle's targets
+        // now and the fork finds them made.  A guess only: the fork's command says where the
+        // shuffle really starts, and targets drawn for another position are drawn again there.
+        const uint64_t npos = uni(((AS_LDS const uint64_t *)(ctl + CT_NEXT))[0]);
+        if (npos != ~0ull) {
+          fork_shuffle_targets<W>(key, npos, p, wave, lane, ch.oth);
+          if (lane == 0) ((AS_LDS uint64_t *)(ctl + CT_NEXT))[0] = ~0ull;   // (taken: the master writes the next one behind the next command)
+          pre_ok = true;
+          pre_pos = npos;
+          HSTAMP(sx_unused, 0);
+        }
+      }
     }
 #if defined(BA_STAMPS) && defined(BA_STAMPS4)
     if (wave == 1 && lane == 0) {
@@ -257,6 +285,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
   AS_LDS int *sum_g = to_lds<int>(smem + lay.park + 1792);   // variable (-1: none)
   sum_b[lane] = 0.0; sum_b2[lane] = 0.0; sum_n[lane] = 0; sum_g[lane] = -1;
   if (lane < 13) ctl[CT_ACC + lane] = (lane == ACC_MIN_MARGIN) ? BA_INF : 0.0;
+  if (W == 2 && lane == 0) ((AS_LDS uint64_t *)(ctl + CT_NEXT))[0] = ~0ull;   // (no tail has ended yet)
   wave_sync();
 #define ACC_ADD(slot, x) do { if (lane == 0) ctl[CT_ACC + (slot)] += (double)(x); } while (0)
 #define ACC_MIN(x) do { if (lane == 0) ctl[CT_ACC + ACC_MIN_MARGIN] = fmin(ctl[CT_ACC + ACC_MIN_MARGIN], (x)); } while (0)
@@ -302,7 +331,8 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
   bool spec = false;          // a forked walk is outstanding
   bool have_dr = false;       // wave 1's slot holds a walk result not yet handled
   int after_join = PH_COMMIT, spec_status = CHAIN_OK;
-  // Between a join and the next fork wave 1 has nothing to do, so the master
+  // Between a join and the next fork wave 1 has nothing to do but draw the next shuffle's
+  // targets (two wavefronts: the helpers' loop), so the master
   // keeps that stretch short: a joined sweep's summaries are committed AFTER the
   // next sweep has been forked, and the sweep-start copy of gamma is skipped
   // while gamma has not moved.
@@ -362,12 +392,14 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
       asm volatile("" : "+v"(lane));
       ch.lane = lane;
     }
+    XCOUNT(sx, 6, 1);
     if (pe.kind != EV_NONE && !spec) {
       // ---- the one place where a model is (re)built (a swap proposed by a
       // tail running ahead waits for the join) --------------------------
       // (outside this block only logp, SS and pd of the model live in registers;
       // the scalars the evaluations need have their home in the control block)
       MSTAMP(sx, 7);
+      XSTAMP(sx, 1);
       if (pe.kind == EV_FORCE && pe.f2 < 0 && other_ok && pe.f1 == other_var) {
         gam0_fresh = false;
         // The accepted flip leads to the model the other slot still holds (a
@@ -407,6 +439,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
         pe.check_legal = false;
         STAMP(2);
         MSTAMP(sx, 3);
+        XSTAMP(sx, 7);
         continue;
       }
       gam0_fresh = false;
@@ -500,10 +533,12 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
       STAMP(2);
       FSTAMP(sx, 4);
       MSTAMP(sx, 3);
+      XSTAMP(sx, 7);
       continue;
     }
 
     if (phase == PH_BEGIN) {
+      XSTAMP(sx, 1);
       if (sweep + (commit_pending ? 1 : 0) >= nsweeps) {
         if (!commit_pending) break;
         phase = PH_COMMIT;  // the last sweep's summaries, then out
@@ -515,11 +550,13 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
         const bool will_fork = nflips > 0 && W > 1 && ut && table_valid && mc && p > 1 && P.walk_policy != 3 && P.mode != 2 && !MLVS;
         if (commit_pending && !will_fork) {
           phase = PH_COMMIT;  // nothing to overlap with: commit first
+          XSTAMP(sx, 4);
           continue;
         }
       }
       STAMP(7);
       TSTAMP(sx, 7);
+      XSTAMP(sx, 4);
       if (nflips > 0) {
         // remember the sweep's starting point (restored if the chain has to
         // stop inside this sweep for lack of model capacity)
@@ -563,8 +600,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
             ((AS_LDS uint64_t *)(ctl + CT_POS))[0] = pos;
           }
           __syncthreads();
-          shuffle_targets(key, pos, p, threadIdx.x, WAVE * W, ch.oth);   // (the master's share: see the helpers' loop)
-          __syncthreads();
+          fork_shuffle_targets<W>(key, pos, p, 0, lane, ch.oth);   // (the master's share, none with two wavefronts: see the helpers' loop)
           {  // the shuffled order will be in the other buffer
             lds_u16 *tmp = ch.perm;
             ch.perm = ch.perm_alt;
@@ -574,6 +610,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
           flip_pos = pos + (uint64_t)(p - 1);
           pos = flip_pos + (uint64_t)nflips;
           TSTAMP(sx, 2);
+          XSTAMP(sx, 7);
           spec = true;
           spec_status = CHAIN_OK;
           i0 = 0;
@@ -641,12 +678,15 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
       }
       i0 = 0;
       phase = PH_FLIPS;
+      XSTAMP(sx, 5);
       continue;
     }
 
     if (phase == PH_FLIPS) {
+      XSTAMP(sx, 1);
       if (nflips == 0 || i0 >= nflips) {
         phase = PH_SWAP;
+        XSTAMP(sx, 2);
         continue;
       }
       // ---- Metropolised flips, 64 * W proposals per round
@@ -684,10 +724,13 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
             ACC_ADD(ACC_REFORKS, 1);
 #endif
             phase = commit_pending ? PH_COMMIT : PH_SWAP;
+            XSTAMP(sx, 2);
             continue;
           }
+          XSTAMP(sx, 2);
           __syncthreads();
           MSTAMP(sx, 0);
+          XSTAMP(sx, 7);
           }
           have_dr = false;
           const lds_f64 *sl = ctl + CT_SLOT0 + CT_SLOT_STRIDE * 1;
@@ -704,6 +747,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
         if (dr.spos < 0) {  // walked to the end without a stop
           ACC_ADD(ACC_PROPOSALS, nflips - i0);
           i0 = nflips;
+          XSTAMP(sx, 2);
           continue;
         }
         ACC_ADD(ACC_PROPOSALS, dr.spos + 1 - i0);
@@ -732,6 +776,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
           pe.kind = EV_TRY_GE;
           pe.lu = dr.logu;
         }
+        XSTAMP(sx, 2);
         continue;
       }
       int evmode = EVM_BATCH, base = i0;
@@ -740,6 +785,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
         base = fill_j;
       }
       MSTAMP(sx, 7);
+      XSTAMP(sx, 2);
       if (W > 1) {
         if (lane == 0) {
           ctl[CT_CMD] = (double)CMD_EVAL;
@@ -768,6 +814,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
         }
         STAMP(3);
         MSTAMP(sx, 2);
+        XSTAMP(sx, 7);
         continue;
       }
       // first stop over the whole round, in sweep order
@@ -786,6 +833,7 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
         const int n = (nflips - i0 < WAVE * W) ? (nflips - i0) : WAVE * W;
         ACC_ADD(ACC_PROPOSALS, n);
         i0 += WAVE * W;
+        XSTAMP(sx, 3);
         continue;
       }
       const lds_f64 *sl = ctl + CT_SLOT0 + CT_SLOT_STRIDE * wstop;
@@ -821,11 +869,13 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
         pe.lu = uni((double)sl[SL_LOGU]);
       }
       i0 += nprop;
+      XSTAMP(sx, 3);
       continue;
     }
 
     if (phase == PH_SWAP) {
       TSTAMP(sx, 7);
+      XSTAMP(sx, 1);
       rng.set_pos(pos);
       if (nflips > 0) propose_swap(P, ch, rng, pe, &status);
       pos = rng.get_pos();
@@ -840,13 +890,16 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
       }
       STAMP(4);
       TSTAMP(sx, 3);
+      XSTAMP(sx, 7);
       continue;
     }
 
     if (phase == PH_JOIN) {
       MSTAMP(sx, 7);
+      XSTAMP(sx, 1);
       __syncthreads();
       MSTAMP(sx, 1);
+      XSTAMP(sx, 7);
       spec = false;
       // (where the walk that was outstanding began: read back from the command it was given,
       // not carried in a register across the tail)
@@ -879,12 +932,14 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
 #endif
       }
       STAMP(3);
+      XSTAMP(sx, 0);
       continue;
     }
 
     if (phase == PH_COMMIT) {
       // ---- summaries
       TSTAMP(sx, 7);
+      XSTAMP(sx, 1);
       k = ch.k;
       gprev = (lane < k) ? (int)ch.g[lane] : 0;
       kprev = k;
@@ -935,11 +990,13 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
       commit_pending = false;
       phase = spec ? PH_SWAP : PH_BEGIN;  // (spec: this was the previous sweep's commit, riding on a fork)
       TSTAMP(sx, 0);
+      XSTAMP(sx, 7);
       continue;
     }
 
     // ---- PH_TAIL: sigma, beta, summaries
     TSTAMP(sx, 7);
+    XSTAMP(sx, 1);
     k = ch.k;
     rng.set_pos(pos);
     // draw_sigma (BregVsSampler.cpp:313-324)
@@ -1003,7 +1060,11 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
       beta_valid = true;  // empty model: all coefficients zero
     }
     STAMP(6);
+    XSTAMP(sx, 7);
     after_join = PH_COMMIT;
+    // (two wavefronts: where the next sweep starts if this tail stands -- wave 1 draws that sweep's
+    // shuffle targets behind the join, see the helpers' loop)
+    if (W == 2 && !MLVS && spec && lane == 0) ((AS_LDS uint64_t *)(ctl + CT_NEXT))[0] = pos;
     phase = spec ? PH_JOIN : PH_COMMIT;
   }
 
@@ -1084,10 +1145,11 @@ __device__ __forceinline__ void ssvs_sweep_body(SsvsParams P, int nsweeps, const
 #endif
 #if defined(BA_STAMPS) && defined(BA_STAMPS4)
     // (phases are wave 1's)
-#elif defined(BA_STAMPS) && (defined(BA_STAMPS2) || defined(BA_STAMPS3) || defined(BA_STAMPS5) || defined(BA_STAMPS6))
+#elif defined(BA_STAMPS) && (defined(BA_STAMPS2) || defined(BA_STAMPS3) || defined(BA_STAMPS5) || defined(BA_STAMPS6) || defined(BA_STAMPS7))
     SUBSTAMP(sx, 7);
     FSTAMP(sx, 7);
     MSTAMP(sx, 7);
+    XSTAMP(sx, 7);
     for (int i = 0; i < 8; ++i) a[ACC_PHASE0 + i] += sx.ph[i];
 #elif defined(BA_STAMPS)
     for (int i = 0; i < 8; ++i) { a[ACC_PHASE0 + i] += st_ph[i]; a[ACC_SLOT_HITS] += st_ph[i]; }

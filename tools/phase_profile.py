@@ -7,7 +7,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SUBN = os.environ.get("SUBSTAMPS", "0")
 SUB = SUBN != "0"
-os.environ["BOOM_AMD_LIB"] = os.path.join(ROOT, "tools", "build", {"0": "libboomamd_stamps.so", "1": "libboomamd_stamps2.so", "2": "libboomamd_stamps3.so", "3": "libboomamd_stamps4.so", "4": "libboomamd_stamps5.so", "5": "libboomamd_stamps6.so"}[SUBN])
+os.environ["BOOM_AMD_LIB"] = os.path.join(ROOT, "tools", "build", {"0": "libboomamd_stamps.so", "1": "libboomamd_stamps2.so", "2": "libboomamd_stamps3.so", "3": "libboomamd_stamps4.so", "4": "libboomamd_stamps5.so", "5": "libboomamd_stamps6.so", "6": "libboomamd_stamps7.so"}[SUBN])
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import time
@@ -55,6 +55,11 @@ elif SUBN == "4":
 elif SUBN == "5":
     names = ["master: waiting for an unforked walk", "master: waiting at the join", "master: fill rounds",
              "master: events (rebuild / slot switch)", None, None, None, "everything else"]
+elif SUBN == "6":
+    names = ["master: a join's bookkeeping", "master: loop top (phase end to phase start)",
+             "master: PH_FLIPS around a walk or a stop", "master: batch-mode rounds",
+             "master: PH_BEGIN ahead of the copy", "master: sweep start without a fork", None,
+             "named by SUBSTAMPS 2 and 5"]
 elif SUB:
     names = ["batch: index fetch", "batch: classify", "batch: V gather", "batch: V solve",
              "batch: A gather", "batch: A solve", "batch: epilogue", "outside batches"]
@@ -75,6 +80,12 @@ if SUBN == "5":
           " per sweep with a stop: unforked-walk wait %.0f, join wait %.0f, fill rounds %.0f, events %.0f cycles"
           % (nstop / sm["sweeps"], nref / sm["sweeps"], nroll / sm["sweeps"], ph[0] / max(nstop, 1),
              ph[1] / max(nstop, 1), ph[2] / max(nstop, 1), ph[3] / max(nstop, 1)))
+if SUBN == "6":
+    # (slot 6 of this build is a count, not cycles)
+    npass = ph[6]
+    ph = ph.copy()
+    ph[6] = 0.0
+    print("passes of the master's loop/sweep %.2f, loop-top cycles/pass %.0f" % (npass / sm["sweeps"], ph[1] / max(npass, 1)))
 tot = ph.sum()
 if not SUB:
     print("  per chain: mean %.0f cycles, slowest %.0f cycles (%.2fx)" % (tot / chains, sm["slot_hits"], sm["slot_hits"] * chains / tot))
