@@ -227,6 +227,34 @@ def test_log_model_prob_of_models_beyond_64_variables(oracle):
     assert _same(eng.get_states(), ref.get_states())
 
 
+def test_log_model_prob_at_the_large_model_kernels_panel_edges(oracle):
+    """the build's panel edges through the C ABI, up to the large-model kernel's capacity (1024
+    variables, 16 panels): k = 128 (the last size with the matrix cores' inverses), 192 / 193 and
+    256 / 257 (three panels become four, four five), 449 (a last tile of one row), 512, 1024; one
+    variable more is BA_E_MODEL_TOO_LARGE and leaves the engine usable"""
+    import boom_amd
+    p = 1100
+    suf, prior, g0 = _case(p=p, nsig=6, seed=29, n=1500)
+    eng = make_engine(2, 4, suf=suf, prior=prior, g0=g0)
+    rng = np.random.Generator(np.random.PCG64(9))
+    sizes = [128, 192, 193, 256, 257, 449, 512, 1024]
+    gammas = np.zeros((len(sizes), p), np.uint8)
+    for row, k in enumerate(sizes):
+        gammas[row, 0] = 1                                  # (the prior forces the intercept in)
+        gammas[row, 1 + rng.choice(p - 1, k - 1, replace=False)] = 1
+    assert list(gammas.sum(axis=1)) == sizes
+    want = oracle.log_model_prob(suf, prior, gammas)
+    got = eng.log_model_prob(gammas)
+    assert np.isfinite(want).all()
+    assert np.max(np.abs(got - want) / np.maximum(1.0, np.abs(want))) < 1e-9
+    too_large = np.zeros((1, p), np.uint8)
+    too_large[0, :1025] = 1
+    with pytest.raises(boom_amd.BoomAmdError) as ei:
+        eng.log_model_prob(too_large)
+    assert ei.value.code == -8                              # BA_E_MODEL_TOO_LARGE
+    assert np.array_equal(eng.log_model_prob(gammas[:3]), got[:3])
+
+
 def test_overlapping_sweep_launches_hand_chains_over(oracle):
     """Consecutive ba_sweep calls with nothing in between run on two streams and hand the
     chains over one by one (a workgroup of the next launch takes a chain the current launch

@@ -213,6 +213,37 @@ def test_state_space_with_a_large_regression_model(oracle):
     assert max(o["gamma"].sum(axis=1).max() for o in ora.values()) > 64
 
 
+def test_model_hovering_across_128_variables(oracle):
+    """110 signals and a prior that lets about twenty of the 90 noise variables in: the model size
+    settles around 128, the edge where the large-model kernel's proposals change from the matrix
+    cores (k <= 128) to the per-lane panel solves and where two panels become three.  Every checked
+    chain crosses it in both directions within the 12 sweeps -- asserted on the oracle's own trace
+    before anything is compared."""
+    from test_partial_rebuild_gpu import _crosses
+    X, y, _ = regression_data(600, 200, 110, seed=61)
+    suf = oracle.neregsuf(X, y)
+    prior = spike_slab_prior(suf, 156, kappa=2.0)
+    g0 = np.zeros(200, np.uint8)
+    g0[0] = 1
+    chains, seed, nsw, check = 3, 37, 12, [0, 1, 2]
+    ora = _oracle_runs(oracle, suf, prior, ssvs_options(), seed, g0, nsw, check)
+    for c in check:
+        assert ora[c]["status"] == 0
+        ksize = ora[c]["gamma"].sum(axis=1).astype(np.int64)[None, :]
+        assert _crosses(ksize, 128), (c, ksize)
+        assert ora[c]["min_margin"] > 1e-9
+    eng = make_engine(chains, seed, suf=suf, prior=prior, g0=g0)
+    for s in range(nsw):
+        eng.sweep(1)
+        gam, beta, sig = eng.get_states()
+        for c in check:
+            o = ora[c]
+            assert np.array_equal(gam[c], o["gamma"][s]), (c, s)
+            assert relerr(beta[c], o["beta"][s]) < RTOL, (c, s)
+            assert abs(sig[c] - o["sigsq"][s]) < RTOL * sig[c], (c, s)
+    assert eng.get_summaries()["min_margin"] > 1e-9
+
+
 @pytest.mark.parametrize("p", [80, 150])
 def test_rank_deficient_large_model_is_the_reference_error(oracle, p):
     """the same two failures as test_ssvs_gpu's rank-deficient case, on a model of more than 64
